@@ -6,10 +6,14 @@
 #include <thread>
 
 #include <cstdio>
+#include <unistd.h>
 
 using namespace htsl;
 
 static int failures = 0;
+static std::string scratch_dir;  // private to this run (mkdtemp): a fixed name under a shared /tmp may belong to someone else
+
+static std::string scratch(const char *name) { return scratch_dir + "/" + name; }
 #define CHECK(cond)                                                     \
     do {                                                                \
         if (!(cond)) { fprintf(stderr, "FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond); failures++; } \
@@ -50,7 +54,8 @@ static std::vector<uint8_t> bgzf_block(const std::vector<uint8_t> &payload, int 
 }
 
 static bool reader_rejects(const std::vector<uint8_t> &bytes) {
-    const char *path = "/tmp/hts_selftest.bin";
+    const std::string bin = scratch("hts_selftest.bin");
+    const char *path = bin.c_str();
     FILE *f = fopen(path, "wb");
     fwrite(bytes.data(), 1, bytes.size(), f);
     fclose(f);
@@ -66,6 +71,12 @@ static bool reader_rejects(const std::vector<uint8_t> &bytes) {
 }
 
 int main() {
+    {
+        const char *t = getenv("TMPDIR");
+        std::string tmpl = std::string(t && *t ? t : "/tmp") + "/hts_selftest_XXXXXX";
+        if (!mkdtemp(&tmpl[0])) { perror("hts_selftest: mkdtemp"); return 1; }
+        scratch_dir = tmpl;
+    }
     // ---- well-formed aux area: accepted, tags found, updates work
     {
         Rec r = make_rec({'N', 'M', 'C', 3, 'r', 's', 'C', 1, 'X', 'Z', 'Z', 'h', 'i', 0, 'B', 'B', 'B', 's', 2, 0, 0, 0, 1, 0, 2, 0});
@@ -138,7 +149,8 @@ int main() {
     // ---- block reading equals record reading: SAM text and the BAM written from it (records that span BGZF blocks and
     // gulps, batches that end in the middle of a block), and a block written back equals the records written back
     {
-        const char *sam_path = "/tmp/hts_selftest.sam", *bam_path = "/tmp/hts_selftest.bam", *bam2_path = "/tmp/hts_selftest2.bam";
+        const std::string sam = scratch("hts_selftest.sam"), bam = scratch("hts_selftest.bam"), bam2 = scratch("hts_selftest2.bam");
+        const char *sam_path = sam.c_str(), *bam_path = bam.c_str(), *bam2_path = bam2.c_str();
         {
             FILE *f = fopen(sam_path, "w");
             fprintf(f, "@HD\tVN:1.6\tSO:unsorted\n@SQ\tSN:chr1\tLN:100000\n@SQ\tSN:chr2\tLN:5000\n");
@@ -258,6 +270,8 @@ int main() {
             b.data()[b.size() - 1] = 1;
         }
     }
+    for (const char *name : {"hts_selftest.bin", "hts_selftest.sam", "hts_selftest.bam", "hts_selftest2.bam"}) unlink(scratch(name).c_str());
+    rmdir(scratch_dir.c_str());
     if (failures) {
         fprintf(stderr, "%d check(s) failed\n", failures);
         return 1;

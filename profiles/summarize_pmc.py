@@ -35,7 +35,7 @@ def load(d):
 calib_bytes = 2 << 30
 wcal = [v["WRITE_SIZE"] for k, v in cw.items() if "calib_write" in k][0] * 1024 / calib_bytes
 fcal = [v["FETCH_SIZE"] for k, v in cf.items() if "calib_read" in k][0] * 1024 / calib_bytes
-out = {"source": "rocprofv3 --pmc (separate passes) on `python3 bench.py --config %s --steps 2 --warmup 1 --no-cpu --no-e2e --slots 1`, MI355X; "
+out = {"source": "rocprofv3 --pmc (separate passes) on `python3 bench.py --config %s --steps 2 --warmup 1 --no-cpu --no-e2e --slots 1 --full`, MI355X; "
                  "per-launch averages over all launches of the run" % config,
        "workload": config,
        "units": "FETCH_SIZE/WRITE_SIZE are KiB; corrected as MI355X_MICROARCH.md §HBM prescribes and as calibrated here",

@@ -53,7 +53,7 @@ def test_cli_sam_output_matches_golden(tag):
     _check_records(recs, exp)
 
 
-def test_cli_bam_roundtrip_and_ubam():
+def test_cli_bam_roundtrip_and_ubam(tmp_path):
     tag = "anno_c2"
     exp, floor_len, window = _expected(tag)
     base = ["annotate", "--min-length", str(floor_len), "-w%d" % window]
@@ -69,7 +69,7 @@ def test_cli_bam_roundtrip_and_ubam():
     _check_records(rb, exp)
     assert all(r["tags"]["rs.bamtype"] == "C" for r in rb)  # bam_aux_update_int of a ubyte
     # BAM in -> SAM out: annotating the annotated BAM again replaces the tags in place, same values
-    tmp = os.path.join(os.environ.get("TMPDIR", "/tmp"), "fade_cli_rt.bam")
+    tmp = str(tmp_path / "fade_cli_rt.bam")
     open(tmp, "wb").write(pb.stdout)
     p2 = _run(base + [tmp, fa])
     assert p2.returncode == 0, p2.stderr.decode()
@@ -382,12 +382,12 @@ def test_cli_out_shards_every_lane_a_complete_file(lanes_bam):
     assert _stats_lines(p.stderr) == _stats_lines(lanes_bam["one_err"])
 
 
-def test_cli_a_failing_lane_ends_the_run(lanes_bam):
+def test_cli_a_failing_lane_ends_the_run(lanes_bam, tmp_path):
     """One lane that cannot work (its device does not exist) fails; the parent must notice whichever lane ends first, stop
     the others and report — not wait for lanes in order, and not leave lanes waiting for a dead peer."""
     p = subprocess.run([FADE, "annotate", "--gpus", "3", "-w", "100", "-b", lanes_bam["bam"], lanes_bam["fa"]], stdout=subprocess.PIPE,
-                       stderr=subprocess.PIPE, timeout=300, env=dict(os.environ, FADE_DEVICE_MAP="0,0,63"))
+                       stderr=subprocess.PIPE, timeout=300, env=dict(os.environ, FADE_DEVICE_MAP="0,0,63", TMPDIR=str(tmp_path)))
     assert p.returncode != 0
     assert b"lane 2 of 3 failed" in p.stderr, p.stderr.decode()[-1500:]
-    left = [f for f in os.listdir(os.environ.get("TMPDIR", "/tmp")) if f.startswith("fade_lanes_")]
+    left = [f for f in os.listdir(tmp_path) if f.startswith("fade_lanes_")]
     assert left == [], left
