@@ -131,6 +131,10 @@ size_t fadehip_batch_bytes(int n_reads, long n_cigar_ops, long n_seq_bytes);
 int fadehip_batch_bind(void* base, int n_reads, long n_cigar_ops, long n_seq_bytes, fadehip_read_batch* b);
 int fadehip_sw_batch(fadehip_ctx* ctx, int n, const(ubyte)* q, const(long)* q_off,
         const(ubyte)* r, const(long)* r_off, fadehip_sw_result* out_);
+/// parasail's stats mode (stats.d:123,164): Parasail(alphabet, open, ext, match, mismatch).aligner!("sw","stats","striped","16")
+struct fadehip_sw_stats_result { int score, end_query, end_ref, matches, similar, length; }
+int fadehip_sw_stats_batch(fadehip_ctx* ctx, const(int)* scoring4 /* open, ext, match, mismatch */, int n,
+        const(ubyte)* q, const(long)* q_off, const(ubyte)* r, const(long)* r_off, fadehip_sw_stats_result* out_);
 int fadehip_genome_upload(fadehip_ctx* ctx, int n_contigs, const(long)* lengths, const(ubyte*)* seqs);
 int fadehip_annotate_upload(fadehip_ctx* ctx, int slot, const(fadehip_read_batch)* batch);
 int fadehip_annotate_run(fadehip_ctx* ctx, int slot, int floor_len, int window);

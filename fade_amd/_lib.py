@@ -32,7 +32,7 @@ EXPORTS = [
     "fadehip_sync", "fadehip_last_run_profile", "fadehip_stats_allreduce",
     "fadehip_bgzf_deflate_submit", "fadehip_bgzf_deflate_wait", "fadehip_stats_allreduce_rank", "fadehip_bgzf_inflate",
     "fadehip_bam_open", "fadehip_bam_front", "fadehip_bam_front_raw", "fadehip_bam_back", "fadehip_bam_totals", "fadehip_bam_close",
-    "fadehip_bam_prepare",
+    "fadehip_bam_prepare", "fadehip_sw_stats_batch",
 ]
 BGZF_BLOCK = 0xff00
 BGZF_LANES = 2
@@ -58,6 +58,9 @@ SW_DTYPE = np.dtype([("score", "<i4"), ("end_query", "<i4"), ("end_ref", "<i4"),
                      ("beg_ref", "<i4"), ("n_ops", "<i4"), ("ops", "<u4", (MAX_OPS,))])
 ALN_DTYPE = np.dtype([("read_idx", "<i4"), ("art", "<i4"), ("win_start", "<i8"), ("win_len", "<i4"),
                       ("clip_left", "<i4"), ("clip_right", "<i4"), ("aligned_len", "<i4"), ("sw", SW_DTYPE)])
+# fadehip_sw_stats_result: parasail's stats mode (stats.d:123,164)
+SW_STATS_DTYPE = np.dtype([("score", "<i4"), ("end_query", "<i4"), ("end_ref", "<i4"), ("matches", "<i4"),
+                           ("similar", "<i4"), ("length", "<i4")])
 assert SW_DTYPE.itemsize == C.sizeof(SwResult)
 assert ALN_DTYPE.itemsize == C.sizeof(Aln)
 
@@ -120,6 +123,7 @@ def load():
     L.fadehip_batch_bind.argtypes = [vp, i32, i64, i64, C.POINTER(ReadBatch)]
     L.fadehip_annotate_results.argtypes = [vp, C.c_int, C.POINTER(AnnoView)]
     L.fadehip_sw_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+    L.fadehip_sw_stats_batch.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
     L.fadehip_genome_upload.argtypes = [vp, i32, vp, vp]
     L.fadehip_annotate_upload.argtypes = [vp, C.c_int, C.POINTER(ReadBatch)]
     L.fadehip_annotate_run.argtypes = [vp, C.c_int, i32, i32]

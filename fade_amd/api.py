@@ -15,7 +15,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import ALN_DTYPE, SW_DTYPE, FadeHipError
+from ._lib import ALN_DTYPE, SW_DTYPE, SW_STATS_DTYPE, FadeHipError
 
 CIGAR_OPS = "MIDNSHP=X"
 NT16 = "=ACMGRSVTWYHKDBN"
@@ -94,6 +94,36 @@ class Context:
         qc = np.frombuffer(b"".join(qs), dtype=np.uint8) if q_off[-1] else np.zeros(0, np.uint8)
         rc = np.frombuffer(b"".join(rs), dtype=np.uint8) if r_off[-1] else np.zeros(0, np.uint8)
         return self.sw_batch_packed(qc, q_off, rc, r_off)
+
+    # ---- parasail's stats mode: the inverted-repeat search of `fade stats` (stats.d:87,123,164)
+    def sw_stats_batch_packed(self, q_concat, q_off, r_concat, r_off, scoring=(3, 8, 10, -5)):
+        q_concat = np.ascontiguousarray(q_concat, dtype=np.uint8)
+        r_concat = np.ascontiguousarray(r_concat, dtype=np.uint8)
+        q_off = np.ascontiguousarray(q_off, dtype=np.int64)
+        r_off = np.ascontiguousarray(r_off, dtype=np.int64)
+        sc = np.ascontiguousarray(scoring, dtype=np.int32)
+        if sc.shape != (4,):
+            raise ValueError("scoring is (open, ext, match, mismatch)")
+        n = len(q_off) - 1
+        out = np.zeros(n, dtype=SW_STATS_DTYPE)
+        self._chk(self._L.fadehip_sw_stats_batch(self._h, sc.ctypes.data, n, q_concat.ctypes.data, q_off.ctypes.data,
+                                                 r_concat.ctypes.data, r_off.ctypes.data, out.ctypes.data))
+        return out
+
+    def sw_stats_batch(self, qs, rs, scoring=(3, 8, 10, -5)):
+        """Parasail("ACTGN", *scoring).aligner!("sw", "stats", "striped", "16") over the pairs (qs[k], rs[k]): a structured
+        array (score, end_query, end_ref, matches, similar, length) in the order of the pairs."""
+        if len(qs) != len(rs):
+            raise ValueError("qs and rs differ in length")
+        qb = [q.encode() if isinstance(q, str) else bytes(q) for q in qs]
+        rb = [r.encode() if isinstance(r, str) else bytes(r) for r in rs]
+        q_off = np.zeros(len(qb) + 1, dtype=np.int64)
+        r_off = np.zeros(len(rb) + 1, dtype=np.int64)
+        np.cumsum([len(q) for q in qb], out=q_off[1:])
+        np.cumsum([len(r) for r in rb], out=r_off[1:])
+        qc = np.frombuffer(b"".join(qb), dtype=np.uint8) if q_off[-1] else np.zeros(0, np.uint8)
+        rc = np.frombuffer(b"".join(rb), dtype=np.uint8) if r_off[-1] else np.zeros(0, np.uint8)
+        return self.sw_stats_batch_packed(qc, q_off, rc, r_off, scoring)
 
     # ---- level 2: annotateTask over a batch (anno.d:55-110)
     def genome_upload(self, names, seqs):

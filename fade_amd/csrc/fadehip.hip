@@ -10,6 +10,7 @@
 #include "bgzf_deflate.hpp"
 #include "bgzf_inflate.hpp"
 #include "bam_device.hpp"
+#include "sw_stats.hpp"
 #include <rccl/rccl.h>
 #include <algorithm>
 #include <chrono>
@@ -185,6 +186,10 @@ struct fadehip_ctx {
     // genome
     DevBuf genome, contig_len, contig_base;
     DevBuf l1_q, l1_r, l1_qn, l1_rn, l1_bad, l1_work, l1_aln;  // level 1 (fadehip_sw_batch): kept between calls, grow only
+    // fadehip_sw_stats_batch: its own stream and buffers (kept between calls, grow only), so that it leaves the slots alone
+    hipStream_t stats_stream = nullptr;
+    DevBuf st_q, st_r, st_work, st_out, st_scratch;
+    std::mutex stats_mu;
     int n_contigs = 0;
     std::vector<int64_t> h_contig_len;
     std::vector<uint64_t> h_contig_base;
@@ -1444,6 +1449,8 @@ void fadehip_destroy(fadehip_ctx *ctx) {
     if (ctx->inf.stream) (void)hipStreamDestroy(ctx->inf.stream);
     release(ctx->genome);
     for (DevBuf *b : {&ctx->l1_q, &ctx->l1_r, &ctx->l1_qn, &ctx->l1_rn, &ctx->l1_bad, &ctx->l1_work, &ctx->l1_aln}) release(*b);
+    for (DevBuf *b : {&ctx->st_q, &ctx->st_r, &ctx->st_work, &ctx->st_out, &ctx->st_scratch}) release(*b);
+    if (ctx->stats_stream) (void)hipStreamDestroy(ctx->stats_stream);
     release(ctx->contig_len);
     release(ctx->contig_base);
     if (g_err_ctx == ctx) g_err_ctx = nullptr;
@@ -1625,6 +1632,111 @@ int fadehip_sw_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *q, const int64_
         }
         out[k] = o;
     }
+    return 0;
+}
+
+// parasail's stats mode (sw_stats.hpp).  Pairs sorted by (lq, lr) so that neighbouring waves sweep alike; each sorted range
+// of a row class is one launch; results go straight to the caller's order.
+int fadehip_sw_stats_batch(fadehip_ctx *ctx, const int32_t scoring[4], int32_t n, const uint8_t *q, const int64_t *q_off,
+                           const uint8_t *r, const int64_t *r_off, fadehip_sw_stats_result *out) {
+    if (!ctx) return set_err(nullptr, FADEHIP_E_INVALID, "ctx is NULL");
+    if (!scoring || n < 0 || (n > 0 && (!q_off || !r_off || !out))) return set_err(ctx, FADEHIP_E_INVALID, "NULL argument");
+    const int32_t open = scoring[0], ext = scoring[1], match = scoring[2], mismatch = scoring[3];
+    const int32_t SC_MAX = 32767;
+    if (open < 1 || ext < 1 || match < 1 || mismatch > 0 || open > SC_MAX || ext > SC_MAX || match > SC_MAX || mismatch < -SC_MAX)
+        return set_err(ctx, FADEHIP_E_UNSUPPORTED,
+                       "stats scoring open %d ext %d match %d mismatch %d outside open, ext, match in [1, %d], mismatch in [-%d, 0]",
+                       open, ext, match, mismatch, SC_MAX, SC_MAX);
+    if (n == 0) return 0;
+    std::vector<uint64_t> keys((size_t)n);
+    int64_t q_total = 0, r_total = 0;
+    for (int k = 0; k < n; k++) {
+        const int64_t lq = q_off[k + 1] - q_off[k], lr = r_off[k + 1] - r_off[k];
+        if (q_off[k] < 0 || r_off[k] < 0 || lq < 0 || lr < 0)
+            return set_err(ctx, FADEHIP_E_INVALID, "offsets must be non-negative and non-decreasing (pair %d)", k);
+        if (lq > FADEHIP_MAX_LONG_QUERY || lr > FADEHIP_MAX_LONG_QUERY)
+            return set_err(ctx, FADEHIP_E_UNSUPPORTED, "pair %d has %lld x %lld bases (max %d each)", k, (long long)lq,
+                           (long long)lr, FADEHIP_MAX_LONG_QUERY);
+        const uint64_t kq = (lq == 0 || lr == 0) ? 0 : (uint64_t)lq;  // empty pairs sort first (the one-row class)
+        keys[(size_t)k] = (kq << 48) | ((uint64_t)lr << 32) | (uint32_t)k;
+    }
+    q_total = q_off[n];
+    r_total = r_off[n];
+    if ((q_total > 0 && !q) || (r_total > 0 && !r)) return set_err(ctx, FADEHIP_E_INVALID, "NULL argument");
+    std::sort(keys.begin(), keys.end());
+    std::vector<StatsWork> wl((size_t)n);
+    // row classes: R = 1, 2, 4, 8 rows per lane (one strip), then the multi-strip class
+    const int cls_max_lq[5] = {64, 128, 256, 512, FADEHIP_MAX_LONG_QUERY};
+    size_t cls_begin[6] = {0, 0, 0, 0, 0, 0};
+    int long_max_lr = 0;
+    {
+        int c = 0;
+        for (size_t s = 0; s < (size_t)n; s++) {
+            const int k = (int)(uint32_t)keys[s];
+            StatsWork &w = wl[s];
+            w.q_base = (uint64_t)q_off[k];
+            w.r_base = (uint64_t)r_off[k];
+            w.lq = (int32_t)(q_off[k + 1] - q_off[k]);
+            w.lr = (int32_t)(r_off[k + 1] - r_off[k]);
+            w.idx = k;
+            w.pad = 0;
+            const int klq = (int)(keys[s] >> 48);
+            while (klq > cls_max_lq[c]) cls_begin[++c] = s;
+            if (c == 4) long_max_lr = std::max(long_max_lr, w.lr);
+        }
+        while (c < 5) cls_begin[++c] = (size_t)n;
+    }
+    std::lock_guard<std::mutex> lk(ctx->stats_mu);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (!ctx->stats_stream) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->stats_stream, hipStreamNonBlocking));
+    hipStream_t st = ctx->stats_stream;
+    // multi-strip pairs: a scratch row of long_max_lr entries per wave, at most 256 MB of them
+    const size_t row_bytes = (size_t)std::max(long_max_lr, 1) * 2 * sizeof(int4);
+    const size_t n_long = cls_begin[5] - cls_begin[4];
+    int long_blocks = 0;
+    if (n_long) {
+        const size_t waves = std::max<size_t>(1, std::min<size_t>({n_long, ((size_t)256 << 20) / row_bytes, (size_t)2048}));
+        long_blocks = (int)((waves + STATS_WAVES_PER_BLOCK - 1) / STATS_WAVES_PER_BLOCK);
+    }
+    int rc = 0;
+    if ((rc = reserve(ctx, ctx->st_q, (size_t)q_total + 1)) || (rc = reserve(ctx, ctx->st_r, (size_t)r_total + 1)) ||
+        (rc = reserve(ctx, ctx->st_work, (size_t)n * sizeof(StatsWork))) ||
+        (rc = reserve(ctx, ctx->st_out, (size_t)n * sizeof(fadehip_sw_stats_result))) ||
+        (long_blocks && (rc = reserve(ctx, ctx->st_scratch, (size_t)long_blocks * STATS_WAVES_PER_BLOCK * row_bytes))))
+        return rc;
+    if (q_total) HIPCHK(ctx, hipMemcpyAsync(ctx->st_q.p, q, (size_t)q_total, hipMemcpyHostToDevice, st));
+    if (r_total) HIPCHK(ctx, hipMemcpyAsync(ctx->st_r.p, r, (size_t)r_total, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->st_work.p, wl.data(), (size_t)n * sizeof(StatsWork), hipMemcpyHostToDevice, st));
+    StatsScoring sc;
+    sc.open = open;
+    sc.ext = ext;
+    sc.match = match;
+    sc.mismatch = mismatch;
+    sc.rules = ctx->sc.rules;
+    const StatsWork *d_work = (const StatsWork *)ctx->st_work.p;
+    const uint8_t *d_q = (const uint8_t *)ctx->st_q.p, *d_r = (const uint8_t *)ctx->st_r.p;
+    fadehip_sw_stats_result *d_out = (fadehip_sw_stats_result *)ctx->st_out.p;
+    const dim3 blk(64 * STATS_WAVES_PER_BLOCK);
+    for (int c = 0; c < 5; c++) {
+        const size_t cnt = cls_begin[c + 1] - cls_begin[c];
+        if (!cnt) continue;
+        const StatsWork *wk = d_work + cls_begin[c];
+        if (c == 4) {
+            hipLaunchKernelGGL(sw_stats_kernel<STATS_STRIP_R>, dim3((unsigned)long_blocks), blk, 0, st, wk, (int32_t)cnt, d_q, d_r,
+                               d_out, (int4 *)ctx->st_scratch.p, std::max(long_max_lr, 1), sc);
+        } else {
+            const unsigned g = (unsigned)std::min<size_t>((cnt + STATS_WAVES_PER_BLOCK - 1) / STATS_WAVES_PER_BLOCK, 16384);
+            switch (c) {
+            case 0: hipLaunchKernelGGL(sw_stats_kernel<1>, dim3(g), blk, 0, st, wk, (int32_t)cnt, d_q, d_r, d_out, (int4 *)nullptr, 0, sc); break;
+            case 1: hipLaunchKernelGGL(sw_stats_kernel<2>, dim3(g), blk, 0, st, wk, (int32_t)cnt, d_q, d_r, d_out, (int4 *)nullptr, 0, sc); break;
+            case 2: hipLaunchKernelGGL(sw_stats_kernel<4>, dim3(g), blk, 0, st, wk, (int32_t)cnt, d_q, d_r, d_out, (int4 *)nullptr, 0, sc); break;
+            default: hipLaunchKernelGGL(sw_stats_kernel<8>, dim3(g), blk, 0, st, wk, (int32_t)cnt, d_q, d_r, d_out, (int4 *)nullptr, 0, sc); break;
+            }
+        }
+        HIPCHK(ctx, hipGetLastError());
+    }
+    HIPCHK(ctx, hipMemcpyAsync(out, d_out, (size_t)n * sizeof(fadehip_sw_stats_result), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
     return 0;
 }
 

@@ -16,6 +16,8 @@
 #include "../../../include/fadehip.h"
 
 #include <atomic>
+#include <cerrno>
+#include <cmath>
 #include <chrono>
 #include <climits>
 #include <cstdlib>
@@ -66,6 +68,8 @@ static void print_anno_help() {
             "    --out-shards with --gpus N: every device writes a complete file PREFIX.<k>.bam (.sam), nothing is merged\n"
             "         --batch records per device batch (default 262144)\n"
             "         --stats print the stats.d summary of this run to stderr\n"
+            "     --stats-tsv PATH: write what `fade stats` prints for this run's output to PATH (one device)\n"
+            "      --clip-tsv PATH: write what `fade stats-clip` prints for this run's output to PATH (one device)\n"
             "-h        --help This help information.\n\n",
             kHeader);
 }
@@ -75,6 +79,7 @@ struct Opts {
     bool bam = false, ubam = false, help = false, stats = false, timing = false, clip = false;
     std::vector<std::string> pos;
     std::string out_shards;  // --out-shards PREFIX (with --gpus N)
+    std::string stats_tsv, clip_tsv;  // --stats-tsv PATH, --clip-tsv PATH: the stats.d / noclip.d reports of this run
     std::string seen;  // one letter per option met: t m w b u c h g(pus) B(atch) s(tats) T(iming) S(hards)
 };
 
@@ -115,6 +120,15 @@ static bool parse_opts(int argc, char **argv, Opts &o, std::string &err) {
                 }
                 if (val.empty()) { err = "Invalid value for option --out-shards: (empty)"; return false; }
                 o.out_shards = val;
+            }
+            else if (name == "stats-tsv" || name == "clip-tsv") {
+                o.seen += name == "stats-tsv" ? 'P' : 'Q';
+                if (!has_val) {
+                    if (i + 1 >= argc) { err = "Missing value for argument --" + name; return false; }
+                    val = argv[++i];
+                }
+                if (val.empty()) { err = "Invalid value for option --" + name + ": (empty)"; return false; }
+                (name == "stats-tsv" ? o.stats_tsv : o.clip_tsv) = val;
             }
             else if (name == "bam") { o.seen += 'b'; o.bam = true; }
             else if (name == "ubam") { o.seen += 'u'; o.ubam = true; }
@@ -440,6 +454,241 @@ static void apply_tags(Chunk &c, const Header &h, Pool &pool) {
         }
     }, CPU_TAGS);
 }
+
+// `fade stats` (stats.d:75-186) and `fade stats-clip` (noclip.d:17-73) over this run's output, written while the tags are
+// applied (`fade annotate --stats-tsv / --clip-tsv`): every value a row needs is here already — the record, its rs and the
+// four artifact strings.  The inverted-repeat search of a chunk's artifact sides is one fadehip_sw_stats_batch call.
+struct Reports {
+    FILE *st = nullptr, *cl = nullptr;
+    std::string st_path, cl_path;
+    bool on() const { return st || cl; }
+    void open(const Opts &o) {
+        auto op = [](const std::string &p) {
+            FILE *f = fopen(p.c_str(), "wb");
+            if (!f) throw std::runtime_error("cannot open " + p + " for writing: " + strerror(errno));
+            return f;
+        };
+        if (!o.stats_tsv.empty()) {
+            st_path = o.stats_tsv;
+            st = op(st_path);
+            fputs("qname\trname\tpos\tcigar\tart_start\tart_end\taln_rname\taln_start\taln_end\tart_cigar\tstemloop\tstemloop_rc\t"
+                  "predicted_inverted_repeat\tIR_identity\tavgbq\tart_avgbq\tart_bq\tIR_bq\tflagbinary\tflag\tstrand\n", st);
+        }
+        if (!o.clip_tsv.empty()) {
+            cl_path = o.clip_tsv;
+            cl = op(cl_path);
+            fputs("qname\tsc_q_scores\tsc_seq\tsc_avg_bq\tavg_bq\tart_status\n", cl);
+        }
+    }
+    void close() {  // throws if a write failed
+        std::string bad;
+        if (st && (fflush(st) || ferror(st))) bad = st_path;
+        if (cl && (fflush(cl) || ferror(cl))) bad = cl_path;
+        if (st) fclose(st);
+        if (cl) fclose(cl);
+        st = cl = nullptr;
+        if (!bad.empty()) throw std::runtime_error("writing " + bad + " failed");
+    }
+    ~Reports() {
+        if (st) fclose(st);
+        if (cl) fclose(cl);
+    }
+    void add(const Chunk &c, const Header &h, fadehip_ctx *ctx);
+};
+
+// D's to!string of a float quotient, as OutStats::ratio prints it: %g, nan, inf
+static void append_ratio(std::string &s, uint64_t num, uint64_t den) {
+    const float v = (float)num / (float)den;
+    char b[64];
+    if (std::isnan(v)) snprintf(b, sizeof b, "nan");
+    else if (std::isinf(v)) snprintf(b, sizeof b, "inf");
+    else snprintf(b, sizeof b, "%g", (double)v);
+    s += b;
+}
+
+static int64_t cigar_string_aligned_length(const std::string &cig, bool &ok) {  // dhtslib cigarFromString(..).alignedLength
+    int64_t n = 0, len = 0;
+    bool digits = false;
+    ok = !cig.empty();
+    for (char ch : cig) {
+        if (ch >= '0' && ch <= '9') { len = len * 10 + (ch - '0'); digits = true; continue; }
+        const char *o = strchr(CIGAR_STR, ch);
+        if (!o || !*o || !digits) { ok = false; return 0; }
+        if (FADEHIP_OP_CONSUMES_REF((uint32_t)(o - CIGAR_STR))) n += len;
+        len = 0;
+        digits = false;
+    }
+    if (digits) ok = false;
+    return n;
+}
+
+static std::vector<std::string> split_on(const std::string &s, char sep) {
+    std::vector<std::string> v;
+    size_t b = 0;
+    for (;;) {
+        const size_t e = s.find(sep, b);
+        v.push_back(s.substr(b, e == std::string::npos ? std::string::npos : e - b));
+        if (e == std::string::npos) return v;
+        b = e + 1;
+    }
+}
+
+void Reports::add(const Chunk &c, const Header &h, fadehip_ctx *ctx) {
+    const size_t n = c.n_records();
+    std::vector<uint8_t> rs(n, 0);
+    for (size_t k = 0; k < c.sent.size(); k++) rs[c.sent[k]] = c.rs_sent[k];
+    std::vector<int> art_of(n, -1);
+    for (size_t k = 0; k < c.art.size(); k++) art_of[c.sent[(size_t)c.art[k].read_idx]] = (int)k;
+    auto fail = [](const RecView &v, const char *what) {
+        throw std::runtime_error(std::string("record ") + v.qname() + ": " + what);
+    };
+    std::string clip_out;
+    struct Side {
+        size_t rec;
+        std::string head, stemloop, ab_slice;  // columns qname .. stemloop_rc, the stem loop, art_bq
+        std::string tail;                      // flagbinary, flag, strand
+        uint64_t qsum;
+        int l_seq;
+    };
+    std::vector<Side> sides;
+    std::string q, r;
+    std::vector<int64_t> q_off(1, 0), r_off(1, 0);
+    for (size_t i = 0; i < n; i++) {
+        const uint8_t rsv = rs[i];
+        if (!(rsv & 1)) continue;  // neither report looks at a record without a soft clip (rs bit 0)
+        const RecView v = c.blk.view(i);
+        const int ls = v.l_seq();
+        const uint8_t *ql = v.qual();
+        uint64_t qsum = 0;
+        for (int j = 0; j < ls; j++) qsum += ql[j];
+        auto base = [&](int j) { return NT16_STR[(v.seq()[j >> 1] >> ((~j & 1) << 2)) & 15]; };
+        if (cl) {  // noclip.d:22-71 with parse_clips' quirk (util.d:37-62)
+            uint32_t clips[2] = {0, 0};
+            bool first = true;
+            for (int k = 0; k < v.n_cigar(); k++) {
+                const uint32_t op = v.cigar_op(k);
+                if ((op & 15) == 5) continue;
+                const bool sc = (op & 15) == 4;
+                if (first && !sc) first = false;
+                else if (first && sc) clips[0] = op;
+                else if (sc) clips[1] = op;
+            }
+            for (int side = 0; side < 2; side++) {
+                if (!clips[side]) continue;
+                const int len = (int)(clips[side] >> 4);
+                if (ls == 0) fail(v, "a soft-clipped record without bases (SEQ *): stats-clip has no clip to report");
+                if (len > ls) fail(v, "soft clip longer than the read");
+                const int b0 = side == 0 ? 0 : ls - len;
+                uint64_t ssum = 0;
+                clip_out.append(v.qname());
+                clip_out += '\t';
+                for (int j = b0; j < b0 + len; j++) {
+                    ssum += ql[j];
+                    clip_out += (char)(uint8_t)(ql[j] + 33);  // ubyte arithmetic: 0xff wraps to ' '
+                }
+                clip_out += '\t';
+                for (int j = b0; j < b0 + len; j++) clip_out += base(j);
+                clip_out += '\t';
+                append_ratio(clip_out, ssum, (uint64_t)len);
+                clip_out += '\t';
+                append_ratio(clip_out, qsum, (uint64_t)ls);
+                clip_out += '\t';
+                clip_out += (rsv & (side == 0 ? 2 : 4)) ? "true" : "false";
+                clip_out += '\n';
+            }
+        }
+        if (!st || !(rsv & 6)) continue;
+        if (art_of[i] < 0) fail(v, "artifact record without its alignment");
+        std::string t[4];
+        artifact_strings(v, c.art[(size_t)art_of[i]], h, t);
+        if (v.tid() < 0 || v.tid() >= (int)h.names.size()) fail(v, "artifact record without a reference");
+        std::string cig;
+        int64_t al = 0;
+        int first_s = -1, last_s = -1;
+        for (int k = 0; k < v.n_cigar(); k++) {
+            const uint32_t op = v.cigar_op(k);
+            append_int(cig, op >> 4);
+            cig += CIGAR_STR[std::min<uint32_t>(op & 15, 9)];
+            if (FADEHIP_OP_CONSUMES_REF(op & 15)) al += op >> 4;
+            if ((op & 15) == 4) {
+                if (first_s < 0) first_s = (int)(op >> 4);
+                last_s = (int)(op >> 4);
+            }
+        }
+        if (first_s < 0) fail(v, "artifact record without a soft clip");
+        const std::vector<std::string> am = split_on(t[0], ';'), as = split_on(t[1], ';'), ar = split_on(t[2], ';');
+        if (am.size() < 2 || as.size() < 2 || ar.size() < 2) fail(v, "malformed am / as / ar tag");
+        const int64_t pos = v.pos();
+        for (int side = 0; side < 2; side++) {
+            if (!(rsv & (side == 0 ? 2 : 4))) continue;
+            const std::vector<std::string> f = split_on(am[(size_t)side], ',');
+            if (f.size() < 3) fail(v, "malformed am tag");
+            char *e = nullptr;
+            const long aln_start = strtol(f[1].c_str(), &e, 10);
+            bool ok = !f[1].empty() && !*e;
+            const int64_t aln_len = cigar_string_aligned_length(f[2], ok);
+            const std::string &sl = as[(size_t)side], &slrc = ar[(size_t)side];
+            if (!ok || sl.empty() || t[3].size() < sl.size()) fail(v, "malformed am / as / ab tag");
+            Side s;
+            s.rec = i;
+            s.head = v.qname();
+            s.head += '\t'; s.head += h.names[(size_t)v.tid()];
+            s.head += '\t'; append_int(s.head, pos);
+            s.head += '\t'; s.head += cig;
+            s.head += '\t'; append_int(s.head, side == 0 ? pos - first_s : pos + al);
+            s.head += '\t'; append_int(s.head, side == 0 ? pos : pos + al + last_s);
+            s.head += '\t'; s.head += f[0];
+            s.head += '\t'; s.head += f[1];
+            s.head += '\t'; append_int(s.head, (int64_t)aln_start + aln_len);
+            s.head += '\t'; s.head += f[2];
+            s.head += '\t'; s.head += sl;
+            s.head += '\t'; s.head += slrc;
+            s.stemloop = sl;
+            s.ab_slice = side == 0 ? t[3].substr(0, sl.size()) : t[3].substr(t[3].size() - sl.size());
+            char fb[16];
+            for (int b = 0; b < 8; b++) fb[b] = (rsv >> (7 - b)) & 1 ? '1' : '0';
+            fb[8] = 0;
+            s.tail = fb;
+            s.tail += '\t'; append_int(s.tail, rsv);
+            s.tail += '\t'; s.tail += (v.flag() & 16) ? "+" : "-";
+            s.qsum = qsum;
+            s.l_seq = ls;
+            const size_t end = (3 * sl.size() + 2) / 4;  // round(0.75 * length): half away from zero
+            q.append(sl, 0, end);
+            r += slrc;
+            q_off.push_back((int64_t)q.size());
+            r_off.push_back((int64_t)r.size());
+            sides.push_back(std::move(s));
+        }
+    }
+    if (!sides.empty()) {
+        std::vector<fadehip_sw_stats_result> res(sides.size());
+        static const int32_t scoring[4] = {3, 8, 10, -5};  // stats.d:87
+        if (fadehip_sw_stats_batch(ctx, scoring, (int32_t)sides.size(), (const uint8_t *)q.data(), q_off.data(),
+                                   (const uint8_t *)r.data(), r_off.data(), res.data()))
+            throw std::runtime_error(std::string("stats alignment: ") + fadehip_last_error(ctx));
+        std::string out;
+        for (size_t k = 0; k < sides.size(); k++) {
+            const Side &s = sides[k];
+            const size_t ir = (size_t)res[k].end_query + 1;
+            if (ir > s.stemloop.size()) throw std::runtime_error("stats alignment ended beyond the stem loop");
+            uint64_t bsum = 0;
+            for (unsigned char ch : s.ab_slice) bsum += ch;
+            out += s.head;
+            out += '\t'; out.append(s.stemloop, 0, ir);
+            out += '\t'; append_ratio(out, (uint64_t)res[k].matches, (uint64_t)res[k].length);
+            out += '\t'; append_ratio(out, s.qsum, (uint64_t)s.l_seq);
+            out += '\t'; append_ratio(out, bsum, s.stemloop.size());
+            out += '\t'; out += s.ab_slice;
+            out += '\t'; out.append(s.ab_slice, 0, ir);
+            out += '\t'; out += s.tail;
+            out += '\n';
+        }
+        if (!out.empty()) fwrite(out.data(), 1, out.size(), st);
+    }
+    if (!clip_out.empty()) fwrite(clip_out.data(), 1, clip_out.size(), cl);
+}
+
 
 // FADE_TRACE=1: every start / stop pair of a named stage clock as a line on stderr at the end (ms since the first one)
 struct StageTrace {
@@ -1564,6 +1813,8 @@ static int annotate_main(const std::string &cl, const Opts &o) {
     } ctx_guard{ctxs, blocks};
     Pool pool(nthreads);
     try {
+        Reports reports;  // --stats-tsv / --clip-tsv: filled by the writer stage, chunk after chunk
+        reports.open(o);
         Reader reader(o.pos[1], &pool);   // anno.d:22 (every stage's parallel work runs on the one pool)
         if (lane.on) reader.restrict_to(lane.range);  // this lane's records only
         // (the reader starts at once: the first batches inflate while the FASTA loads and the genome goes to HBM)
@@ -1706,6 +1957,7 @@ static int annotate_main(const std::string &cl, const Opts &o) {
                 while (q_out.pop(c)) {
                     ck_tags.start();
                     apply_tags(*c, hdr, pool);
+                    if (reports.on()) reports.add(*c, hdr, ctxs[(size_t)c->dev]);
                     ck_tags.stop();
                     ck_write.start();
                     writer.write_block(c->blk, c->bout);
@@ -1817,6 +2069,7 @@ static int annotate_main(const std::string &cl, const Opts &o) {
         }
         if (failed) return 1;
         writer.close();
+        reports.close();
         if (n_oversize && !lane.on)
             fprintf(stderr, "[W::fade annotate] %lld soft-clipped reads were not re-aligned: read longer than %d bases or window longer than %d\n",
                     (long long)n_oversize, FADEHIP_MAX_LONG_QUERY, prm.max_ref_len);
@@ -2305,7 +2558,7 @@ int main(int argc, char **argv) {
             fprintf(stderr, "std.getopt.GetOptException: %s\n", err.c_str());
             return 1;
         }
-        if (!options_allowed(o, "tmwbugBsTS")) return 1;
+        if (!options_allowed(o, "tmwbugBsTSPQ")) return 1;
         // app.d:84-89: helpWanted | args.length < 3 (args = prog, "annotate", positionals...)
         if (o.help || o.pos.size() < 2) { print_anno_help(); return 0; }
         if (o.pos.size() < 3) {  // the reference indexes args[2] and dies; say why instead
@@ -2315,6 +2568,12 @@ int main(int argc, char **argv) {
         }
         if (o.bam && o.ubam) {  // app.d:94-99
             fprintf(stderr, "[E::fade-annotate] Please use only one of the b or u flags\n");
+            return 1;
+        }
+        const bool reports = !o.stats_tsv.empty() || !o.clip_tsv.empty();
+        if (reports && (o.gpus > 1 || !o.out_shards.empty())) {  // the reports are written in record order by one writer
+            fprintf(stderr, "[E::fade-annotate] %s goes with one device: not with %s\n", !o.stats_tsv.empty() ? "--stats-tsv" : "--clip-tsv",
+                    o.gpus > 1 ? "--gpus N > 1" : "--out-shards");
             return 1;
         }
         if (!o.out_shards.empty() && o.gpus < 2) {
@@ -2333,7 +2592,7 @@ int main(int argc, char **argv) {
             }
         }
         // BAM file in, BAM or uBAM out: the file path on the device (FADE_BAM_DEVICE=0: the host pipeline)
-        if ((o.bam || o.ubam) && (o.gpus <= 1 || lane_env().on) && !(getenv("FADE_BAM_DEVICE") && atoi(getenv("FADE_BAM_DEVICE")) == 0)) {
+        if (!reports && (o.bam || o.ubam) && (o.gpus <= 1 || lane_env().on) && !(getenv("FADE_BAM_DEVICE") && atoi(getenv("FADE_BAM_DEVICE")) == 0)) {
             bool fall_back = true;
             const int src = annotate_stream_main(cl, o, &fall_back);
             if (src == 0 || !fall_back) return src;
@@ -2393,7 +2652,8 @@ int main(int argc, char **argv) {
         return out_main(cl, o);
     }
     if (sub == "stats" || sub == "stats-clip") {
-        fprintf(stderr, "[E::fade] %s is outside the MI355X annotate hot path; run the reference fade for it\n", sub.c_str());
+        fprintf(stderr, "[E::fade] %s is outside the MI355X annotate hot path; run the reference fade for it, or write its report "
+                        "during the run: fade annotate %s PATH\n", sub.c_str(), sub == "stats" ? "--stats-tsv" : "--clip-tsv");
         return 1;
     }
     if (sub == "-h" || sub == "--help") { print_full_help(); return 0; }

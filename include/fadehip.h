@@ -129,6 +129,19 @@ typedef struct {
 int fadehip_sw_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *q, const int64_t *q_off,
                      const uint8_t *r, const int64_t *r_off, fadehip_sw_result *out);
 
+/* What `fade stats` reads from parasail's stats mode (stats.d:123,164): score, 0-based inclusive end cell, and the
+ * matches / similar / length of the path that ends in it. */
+typedef struct { int32_t score, end_query, end_ref, matches, similar, length; } fadehip_sw_stats_result;
+/* stats.d:123,164 — Parasail(alphabet, open, ext, match, mismatch).aligner!("sw","stats","striped","16") over n pairs.
+ * Scores come with the call (the ctx's rules apply): open >= 1, ext >= 1 (ext may exceed open), match >= 1,
+ * mismatch <= 0, each of magnitude <= 32767; anything else is FADEHIP_E_UNSUPPORTED.  q and r may each hold
+ * 0 .. FADEHIP_MAX_LONG_QUERY bases; a pair with an empty string gives all zeros.  Strings and offsets as in
+ * fadehip_sw_batch.  Synchronous, on a stream and buffers of its own (calls on one ctx are serialised by a lock): it may
+ * be called from any thread while annotate slots are in flight and does not touch their buffers. */
+int fadehip_sw_stats_batch(fadehip_ctx *ctx, const int32_t scoring[4] /* open, ext, match, mismatch */, int32_t n,
+                           const uint8_t *q, const int64_t *q_off, const uint8_t *r, const int64_t *r_off,
+                           fadehip_sw_stats_result *out);
+
 /* ------------------------------------------------------ Level 2: annotateTask over a batch -- */
 /* Upload the indexed FASTA once (what IndexedFastaFile + fetchSequence serve, analysis.d:63).
  * seqs[c] holds lengths[c] ASCII residues (any case; upper-cased on device as analysis.d:63 does).
