@@ -87,6 +87,7 @@ struct Slot {
         const uint8_t *h_base = nullptr;
         uint32_t hist[NUM_LISTS] = {};
         int max_lq = 0;
+        int l_seq_lo = 0, l_seq_hi = INT32_MAX;  // the caller's l_seq_min / l_seq_max (hinted upload), else no bound
         int64_t span_bound = 0;
         int n_reads = 0, n_skipped = 0;
         int buf = 0;
@@ -129,6 +130,7 @@ struct Slot {
     uint32_t hist[NUM_LISTS] = {};      // upload: records per read-length class (gate-passing ones when the CIGARs were scanned)
     int64_t span_bound = 0;             // upload: max cigar.alignedLength (the caller's bound or the scan's)
     int max_lq = 0;                     // upload: longest read
+    int l_seq_lo = 0, l_seq_hi = INT32_MAX;  // upload: l_seq range the caller announced (the gate fails records outside it)
     uint32_t out_bound = 0, out_cap = 0;  // upload: alignments at most; run: entries of the result array
     std::vector<std::pair<int64_t, int>> wide;
     bool use_ckpt = false;              // this run's score passes leave wave snapshots (see run_class_two_pass)
@@ -1115,6 +1117,8 @@ int enqueue_run(fadehip_ctx *ctx, Slot &s) {
     g.wave_lr_bound = s.wave_lr_bound;
     g.long_lr_bound = s.long_max_lr;
     g.long_lq_bound = std::max(s.long_max_lq, 1);
+    g.l_seq_lo = s.l_seq_lo;
+    g.l_seq_hi = s.l_seq_hi;
     g.rs = (uint8_t *)s.rs.p;
     for (int c = 0; c < NUM_LISTS; c++) {
         g.work[c] = (Work *)s.work[c].p;
@@ -1183,7 +1187,7 @@ int finish_run(fadehip_ctx *ctx, Slot &s, int slot) {
         if (errbits & 64u) return set_err(ctx, FADEHIP_E_INVALID, "batch has a record whose cigar_off / seq_off are not non-decreasing within the arrays, or l_seq < 0");
         if (errbits & 8u) return set_err(ctx, FADEHIP_E_INVALID, "batch has a mapped soft-clipped record whose seq_packed slice is shorter than its l_seq");
         if (errbits & 16u) return set_err(ctx, FADEHIP_E_INVALID, "batch has a record whose cigar.alignedLength exceeds ref_span_bound=%lld", (long long)s.span_bound);
-        if (errbits & 32u) return set_err(ctx, FADEHIP_E_INVALID, "batch has more records to re-align than its bounds said (n_with_seq / l_seq_min / l_seq_max too small?)");
+        if (errbits & 32u) return set_err(ctx, FADEHIP_E_INVALID, "batch has more records to re-align than its bounds said, or a read outside them (n_with_seq too small, or an l_seq outside l_seq_min / l_seq_max?)");
         return set_err(ctx, FADEHIP_E_INVALID, "batch has a mapped soft-clipped read whose tid is not a contig of the uploaded genome");
     }
     for (int c = 0; c < NUM_CLASSES; c++)  // what pass 2 served: sizes the next run's persistent launch
@@ -1817,6 +1821,8 @@ int fadehip_annotate_upload(fadehip_ctx *ctx, int slot, const fadehip_read_batch
     nx.out_bound = 0;
     nx.wide.clear();
     nx.max_lq = 0;
+    nx.l_seq_lo = 0;
+    nx.l_seq_hi = INT32_MAX;
     nx.span_bound = b->ref_span_bound;
     nx.h_base = nullptr;
     if (n == 0) { nx.valid = true; return 0; }
@@ -1843,6 +1849,10 @@ int fadehip_annotate_upload(fadehip_ctx *ctx, int slot, const fadehip_read_batch
         for (int c = c_lo; c <= c_hi; c++) hist[c] = (uint32_t)b->n_with_seq;  // any of them may be of any length in between
         max_lq = std::min(b->l_seq_max, MAX_LONG_QUERY);
         nx.out_bound = (uint32_t)b->n_with_seq;
+        // the row classes and the score kernels are chosen from these bounds: the gate fails the batch for a record with
+        // bases outside them (an l_seq_max that is too small but in the same row class raises no list overflow)
+        nx.l_seq_lo = b->l_seq_min;
+        nx.l_seq_hi = b->l_seq_max;
     } else {
         const bool scan = b->ref_span_bound <= 0, scan_wide = scan || b->ref_span_bound > WIDE_MIN_SPAN;
         uint8_t cls_of[33];  // class of a read of 16 k - 15 .. 16 k bases
@@ -1910,6 +1920,8 @@ int fadehip_annotate_run(fadehip_ctx *ctx, int slot, int32_t floor_len, int32_t 
         s.h_base = nx.h_base;
         memcpy(s.hist, nx.hist, sizeof s.hist);
         s.max_lq = nx.max_lq;
+        s.l_seq_lo = nx.l_seq_lo;
+        s.l_seq_hi = nx.l_seq_hi;
         s.span_bound = nx.span_bound;
         s.out_bound = nx.out_bound;
         s.wide = nx.wide;
@@ -2594,6 +2606,8 @@ int bam_front_impl(fadehip_bam_stream *st, const uint8_t *members, size_t n_byte
         s.wide_all = false;
         s.out_bound = n_sent;
         s.max_lq = 0;
+        s.l_seq_lo = 0;  // (the bounds below are counted on the device over these very records)
+        s.l_seq_hi = INT32_MAX;
         s.span_bound = 1;
         if (n_sent) {
             const int lmin = (int)std::min<uint32_t>(h_counts->l_seq_min, (uint32_t)MAX_LONG_QUERY), lmax = (int)std::min<uint32_t>(h_counts->l_seq_max, (uint32_t)MAX_LONG_QUERY);

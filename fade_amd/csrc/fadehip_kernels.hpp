@@ -163,6 +163,7 @@ struct GateArgs {
     int32_t max_ref_len;
     int32_t wave_lr_bound;       // longest window the wave kernels' launches were sized for (LDS, snapshots): the host's bound
     int32_t long_lr_bound, long_lq_bound;  // the same for the long list's row and trace buffers
+    int32_t l_seq_lo, l_seq_hi;  // l_seq range the caller announced for the records with bases (0 / INT32_MAX: none)
     uint32_t list_cap[NUM_LISTS];  // entries reserved per work list (from the host's count of the batch's read lengths)
     uint32_t out_cap;            // entries of the run's result array (all lists report into one array)
     uint32_t n_cigar_ops, n_seq_bytes;  // lengths of cigar_ops / seq_packed: the offsets are checked against them HERE
@@ -193,6 +194,10 @@ __global__ __launch_bounds__(GATE_BLOCK) void gate_kernel(GateArgs a) {
         // when the caller passes its bounds): a record that fails is skipped and the batch is failed at results
         bool bad_rec = c0 > c1 || c1 > a.n_cigar_ops || so0 > so1 || so1 > a.n_seq_bytes || lq < 0;
         if (bad_rec) { errbits |= 64u; c1 = c0; }
+        // the caller's l_seq_min / l_seq_max chose the row classes and score kernels of the run: a record with bases outside
+        // them fails the batch, and is never scored by a kernel with fewer rows than its read
+        const bool out_of_bounds = !bad_rec && so1 > so0 && (lq < a.l_seq_lo || lq > a.l_seq_hi);
+        if (out_of_bounds) errbits |= 32u;
         // anno.d:61: count S ops; util.d:37-62 parse_clips; dhtslib alignedLength (M,D,N,=,X)
         int n_soft = 0;
         uint32_t clipL = 0, clipR = 0;
@@ -220,6 +225,7 @@ __global__ __launch_bounds__(GATE_BLOCK) void gate_kernel(GateArgs a) {
         a.rs[i] = rs;
         st_bits = 4u | (rs & 1u) | ((rs >> 4) & 2u);  // bit2 read, bit0 clipped, bit1 sup
         const int32_t tid = a.tid[i];
+        if (out_of_bounds) want = false;
         if (want && (tid < 0 || tid >= a.n_contigs)) {
             errbits |= 1u;  // mapped record without a valid contig
             want = false;

@@ -176,8 +176,9 @@ typedef struct {
      * seq_packed slice — only those can be re-aligned) and the shortest / longest l_seq among THOSE.  With
      * n_with_seq > 0 (and ref_span_bound > 0) fadehip_annotate_upload does no per-record host work: the launches and
      * result buffers of the run are sized from these bounds, and cigar_off / seq_off / l_seq are validated by the gate
-     * kernel before anything is dereferenced through them.  A bound that turns out too small fails the batch at results
-     * (FADEHIP_E_INVALID); it is never trusted for memory safety.  0 = unknown. */
+     * kernel before anything is dereferenced through them.  A bound that turns out wrong (more records with bases than
+     * n_with_seq, or one whose l_seq lies outside [l_seq_min, l_seq_max]) fails the batch at results (FADEHIP_E_INVALID);
+     * it is never trusted for memory safety.  0 = unknown. */
     int32_t n_with_seq;
     int32_t l_seq_min, l_seq_max;
     int32_t reserved;

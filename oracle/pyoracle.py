@@ -137,15 +137,27 @@ def sw_batch(q_concat, q_off, r_concat, r_off, threads=1, striped=False, max_ops
 
 
 class GenomeHolder:
-    """Keeps Python-side buffers alive for a fo_genome."""
+    """Keeps Python-side buffers alive for a fo_genome.
+
+    str / bytes contigs are copied.  numpy uint8 arrays are passed by pointer (views into one shared array
+    included), so a multi-gigabase genome whose contigs are views of one pool costs no copy; the arrays are kept alive
+    here.  The oracle reads exactly lengths[c] residues of each contig: no terminator is needed."""
 
     def __init__(self, names, seqs):
         self.names = [n.encode() if isinstance(n, str) else n for n in names]
-        self.seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+        self.seqs = []
+        for s in seqs:
+            if isinstance(s, np.ndarray):
+                if s.ndim != 1:
+                    raise ValueError("a contig array must be one-dimensional")
+                self.seqs.append(np.ascontiguousarray(s, dtype=np.uint8))
+            else:
+                self.seqs.append(s.encode() if isinstance(s, str) else bytes(s))
         n = len(names)
         self._names = (C.c_char_p * n)(*self.names)
         self._lens = (C.c_int64 * n)(*[len(s) for s in self.seqs])
-        self._seqs = (C.c_char_p * n)(*self.seqs)
+        self._seqs = (C.c_char_p * n)(*[C.cast(s.ctypes.data, C.c_char_p) if isinstance(s, np.ndarray) else s
+                                        for s in self.seqs])
         self.c = Genome(n, self._names, self._lens, self._seqs)
 
 

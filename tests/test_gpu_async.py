@@ -325,3 +325,73 @@ def test_snapshots_on_and_off_give_the_same_bytes(monkeypatch, name):
                 c.close()
     for o in outs[1:]:
         assert o == outs[0]
+
+
+def _full_length_batch(lengths, n_each, seed=31, window=100):
+    """Reads whose re-aligned query (the reverse complement, analysis.d:40) matches its window over the read's WHOLE length:
+    the best local path of each needs every row of its query.  One left clip of 8 bases: the read is re-aligned."""
+    g = synth.Genome(2, 200_000, 77)
+    rng = np.random.default_rng(seed)
+    parts = []
+    for lq in lengths:
+        n = n_each
+        tid = rng.integers(0, 2, n).astype(np.int32)
+        pos = rng.integers(window + 1000, 200_000 - lq - window - 1000, n)
+        seg = pos - window + rng.integers(0, lq - 8 + 2 * window - lq + 1, n)  # inside [pos - window, pos + lq - 8 + window)
+        idx = g.offsets[tid][:, None] + seg[:, None] + np.arange(lq)[None, :]
+        codes = np.array([1, 2, 4, 8], np.uint8)[(3 - g.codes[idx])[:, ::-1]]
+        if lq & 1:
+            codes = np.concatenate([codes, np.zeros((n, 1), np.uint8)], axis=1)
+        nb = (lq + 1) // 2
+        parts.append(dict(tid=tid, pos=pos.astype(np.int32), flag=np.zeros(n, np.uint16), has_sa=np.zeros(n, np.uint8),
+                          l_seq=np.full(n, lq, np.int32), cigar_off=(np.arange(n + 1) * 2).astype(np.uint32),
+                          cigar_ops=np.tile(np.array([(8 << 4) | 4, ((lq - 8) << 4) | 0], np.uint32), n),
+                          seq_off=(np.arange(n + 1) * nb).astype(np.uint32),
+                          seq_packed=((codes[:, 0::2] << 4) | codes[:, 1::2]).reshape(-1).astype(np.uint8),
+                          qual_off=np.arange(n + 1, dtype=np.int64) * lq, qual=np.full(n * lq, 30, np.uint8)))
+    return g, synth.concat(parts)
+
+
+def _held_to_the_oracle(oracle, g, b, rs, aln, window):
+    G = oracle.GenomeHolder(g.names, [a.tobytes() for a in g.ascii_contigs()])
+    ors, oam = oracle.annotate_batch_soa(G, b, 5, window, threads=8)
+    assert np.array_equal(rs, ors), np.nonzero(rs != ors)[0][:10]
+    tags = fade_amd.format_tags(b, g.names, rs, aln)
+    assert {i: t["am"] for i, t in tags.items()} == {i: a for i, a in enumerate(oam) if a is not None}
+    return len(tags)
+
+
+@pytest.mark.parametrize("true_len,announced", [(50, 36), (64, 56), (96, 80), (128, 104), (160, 150), (250, 230), (1000, 700)])
+def test_an_understated_l_seq_max_in_the_true_row_class_fails_the_batch(ctx, oracle, true_len, announced):
+    """include/fadehip.h: a bound that turns out too small fails the batch at results.  An l_seq_max below the batch's longest
+    read but in the same row class raises no list overflow; the eight-lane score kernels are chosen from it (36 -> 40 rows for
+    reads of 50): the batch must fail, not score a truncated query.  Then the same context gives the oracle's results."""
+    g, b = _full_length_batch([true_len], 300)
+    ctx.genome_upload(g.names, g.ascii_contigs())
+    good = ctx.with_bounds(b)
+    assert good["l_seq_min"] == good["l_seq_max"] == true_len and good["n_with_seq"] == 300
+    assert good["ref_span_bound"] <= 1024  # (upload takes the caller's bounds only up to this span: WIDE_MIN_SPAN)
+    under = dict(good, l_seq_min=announced, l_seq_max=announced)
+    with pytest.raises(fade_amd.FadeHipError) as e:
+        ctx.annotate(under, 5, 100)
+    assert e.value.code == -1
+    rs, aln, st = ctx.annotate(good, 5, 100)
+    assert len(aln) == 300 and all(int(x["sw"]["score"]) == 2 * true_len for x in aln)  # full-length matches
+    _held_to_the_oracle(oracle, g, b, rs, aln, 100)
+
+
+def test_an_overstated_l_seq_min_fails_the_batch_and_loose_bounds_change_nothing(ctx, oracle):
+    """l_seq_min above the batch's shortest read (in the same row class) fails the batch; bounds that are wider than the truth
+    (another row class on either side) give the bytes of the unhinted batch."""
+    g, b = _full_length_batch([36, 44, 50], 200)
+    ctx.genome_upload(g.names, g.ascii_contigs())
+    good = ctx.with_bounds(b)
+    assert (good["l_seq_min"], good["l_seq_max"]) == (36, 50)
+    with pytest.raises(fade_amd.FadeHipError) as e:
+        ctx.annotate(dict(good, l_seq_min=40), 5, 100)
+    assert e.value.code == -1
+    rs0, aln0, st0 = ctx.annotate(b, 5, 100)
+    _held_to_the_oracle(oracle, g, b, rs0, aln0, 100)
+    for lo, hi in ((36, 50), (20, 50), (36, 64), (1, 150), (30, 700)):
+        rs1, aln1, st1 = ctx.annotate(dict(good, l_seq_min=lo, l_seq_max=hi), 5, 100)
+        assert np.array_equal(rs1, rs0) and list(st1) == list(st0) and _key(aln1) == _key(aln0), (lo, hi)
