@@ -754,6 +754,17 @@ __device__ __forceinline__ uint32_t nib8_at(const Nib8 &w, uint64_t n) {
     const uint32_t byte = (uint32_t)((w.word >> (8 * ((n >> 1) - w.byte0))) & 0xffu);
     return (n & 1) ? (byte & 15u) : (byte >> 4);
 }
+// The same eight nibbles as one dword.  Byte-swapped, the sixteen bases of the dword pair run DOWN the 64-bit value a
+// nibble apiece: base n at nibble 15 - (n - 2 byte0), and n0 - 2 byte0 = n0 & 7.
+// nib8_down: nibble k = base n0 + nv - 1 - k (k < nv <= 8), descending.
+// nib8_up_comp: nibble k = the COMPLEMENT of base n0 + k, ascending: v_bfrev_b32 turns the order around and reverses the
+// bits of every nibble, which is the complement of a 4-bit base code (util.d:18-20 seq_comp_table is bit reversal).
+__device__ __forceinline__ uint32_t nib8_down(uint64_t word, uint64_t n0, int nv) {
+    return (uint32_t)(__builtin_bswap64(word) >> (4 * (16 - nv - (int)(n0 & 7u))));
+}
+__device__ __forceinline__ uint32_t nib8_up_comp(uint64_t word, uint64_t n0) {
+    return __builtin_bitreverse32((uint32_t)(__builtin_bswap64(word) >> (4 * (8 - (int)(n0 & 7u)))));
+}
 
 // One alignment: list entry `src`, traced from sweep step c0 on (0 = from the start) into `tq`, where it occupies group g
 // (16-lane row), half `half`; `item` is its index in the launch (thread-per-alignment trace layout only).
@@ -987,12 +998,12 @@ __device__ __forceinline__ void add_artifact_stats(unsigned long long *stats, ui
 // end cell above the last row (analysis.d:102-104 needs a trailing S).  Everything else gets its record
 // here with n_ops = 0 ("not traced").  Level 1 (meta == nullptr) traces everything.
 
-// One alignment of the score pass, right after its wave has its score and end cell (a lane per alignment: the dependent
-// loads of the diagonal walk hide behind the sweeps of the SIMD's other waves; as a kernel of its own the selection
-// waited for wave slots next to the other slots' score passes).  Returns the artifact bits it set (bit0 left, bit1
-// right) | 4 if the read is supplementary.
+// One alignment of the score pass, right after its wave has its score and end cell (as a kernel of its own the selection
+// waited for wave slots next to the other slots' score passes).  FOUR consecutive lanes call it for the same alignment,
+// u = 0 .. 3: they walk the diagonal together, lane 0 writes the record or appends the candidate.  Returns the artifact
+// bits it set (bit0 left, bit1 right) | 4 if the read is supplementary, on lane 0.
 __device__ __forceinline__ uint32_t select_one(const SelArgs &a, const int item, const Work &w, const Fwd &f, const int R,
-                                               const uint8_t *q_nib, const uint8_t *r_nib, const uint32_t rules) {
+                                               const uint8_t *q_nib, const uint8_t *r_nib, const uint32_t rules, const int u) {
     int b = -1;
     uint32_t art_ret = 0;
     Cand c;
@@ -1008,7 +1019,7 @@ __device__ __forceinline__ uint32_t select_one(const SelArgs &a, const int item,
                                f.end_q < (int32_t)w.lq - 1;
             // (without A.6's soft-clip padding no result CIGAR has an S op and analysis.d:78-80 / 102-104 never hold)
             cand = (left || right) && rule(rules, FADEHIP_RULE_PAD_SOFTCLIP);
-            if (!cand) {
+            if (!cand && u == 0) {
                 fadehip_aln o;
                 o.read_idx = (int32_t)w.idx;
                 o.art = 0;
@@ -1047,69 +1058,94 @@ __device__ __forceinline__ uint32_t select_one(const SelArgs &a, const int item,
             // dynamically, so the score pass needs no scratch memory.
             constexpr int MAX_RUNS = 9;
             uint32_t r0 = 0, r1 = 0, r2 = 0, r3 = 0, r4 = 0, r5 = 0, r6 = 0, r7 = 0, r8 = 0;
-            int n_runs = 0, cur_op = -1;
-            uint32_t cur_len = 0;
+            int n_runs = 0, cur_op = 7, cur_start = 0;
             int P = f.score, L = 0;
-            bool ok = false, give_up = false;
+            bool ok = false;
             const int kmax = min(f.end_q, f.end_r) + 1;  // cells of the diagonal inside the matrix
             auto push_run = [&](uint32_t v) {
                 r8 = r7; r7 = r6; r6 = r5; r5 = r4; r4 = r3; r3 = r2; r2 = r1; r1 = r0; r0 = v;
                 n_runs++;
             };
-            // 32 cells per round trip: the loads of four 8-cell pieces are issued together
-            for (int k0 = 0; k0 < kmax && !ok && !give_up; k0 += 32) {
-                Nib8 qw[4], rw[4];
-                uint64_t qlo[4], rlo[4];
-                int nv[4];
+            // 32 cells per round, 8 per lane: lane u of the alignment's four takes cells [k0 + 8 u, k0 + 8 u + 8) of the
+            // diagonal from one aligned dword pair per sequence (as load_nib8 reads them), computes W and the op letter of
+            // each, and the four lanes find the first cell with P <= 0 from their sums (prefix over the four lanes)
+            for (int k0 = 0; k0 < kmax; k0 += 32) {
+                const int kk = k0 + 8 * u;
+                const int nv = max(0, min(8, kmax - kk));
+                int wv[8];
+                uint32_t xb = 0;  // bit k: cell kk + k is an X
+                int S = 0;
 #pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    const int kk = k0 + 8 * u;
-                    nv[u] = max(0, min(8, kmax - kk));
-                    qlo[u] = rlo[u] = 0;
-                    qw[u].word = rw[u].word = 0;
-                    qw[u].byte0 = rw[u].byte0 = 0;
-                    if (nv[u] > 0) {
-                        qlo[u] = rcq ? (uint64_t)w.q_base + (uint32_t)(lq - 1 - f.end_q + kk)
-                                     : (uint64_t)w.q_base + (uint32_t)(f.end_q - kk - (nv[u] - 1));
-                        rlo[u] = w.r_base + (uint64_t)(f.end_r - kk - (nv[u] - 1));
-                        qw[u] = load_nib8(q_nib, qlo[u]);
-                        rw[u] = load_nib8(r_nib, rlo[u]);
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
+                for (int k = 0; k < 8; k++) wv[k] = 0;
+                if (nv > 0) {
+                    const uint64_t qlo = rcq ? (uint64_t)w.q_base + (uint32_t)(lq - 1 - f.end_q + kk)
+                                             : (uint64_t)w.q_base + (uint32_t)(f.end_q - kk - (nv - 1));
+                    const uint64_t rlo = w.r_base + (uint64_t)(f.end_r - kk - (nv - 1));
+                    // cell k at nibble k: the reference (and a forward query) walks down from base lo + nv - 1, the
+                    // reverse-complemented query up from qlo
+                    const uint64_t qw = load_nib8(q_nib, qlo).word, rw = load_nib8(r_nib, rlo).word;
+                    const uint32_t rr = nib8_down(rw, rlo, nv);
+                    const uint32_t qq = rcq ? nib8_up_comp(qw, qlo) : nib8_down(qw, qlo, nv);
 #pragma unroll
                     for (int k = 0; k < 8; k++) {
-                        if (k < nv[u] && !ok && !give_up) {
-                            const uint32_t qraw = nib8_at(qw[u], rcq ? qlo[u] + (uint32_t)k : qlo[u] + (uint32_t)(nv[u] - 1 - k));
-                            const uint32_t qc = rcq ? lut4(COMP_LUT, qraw) : qraw, rc = nib8_at(rw[u], rlo[u] + (uint32_t)(nv[u] - 1 - k));
+                        if (k < nv) {
+                            const uint32_t qc = (qq >> (4 * k)) & 15u, rc = (rr >> (4 * k)) & 15u;
                             const uint32_t cq = lut4(CLASS_LUT, qc), cr = lut4(CLASS_LUT, rc);
                             const int wsc = (cq == 5 || cr == 5) ? 0 : ((cq == cr && (cq != 4 || n_eq_n)) ? a.match : a.mismatch);
-                            const int op = (eq_by_char ? (qc == rc && qc != 0) : wsc > 0) ? 7 : 8;
-                            if (op == cur_op) cur_len++;
-                            else {
-                                if (cur_op >= 0) push_run((cur_len << 4) | (uint32_t)cur_op);
-                                cur_op = op;
-                                cur_len = 1;
-                            }
-                            P -= wsc;
-                            L = k0 + 8 * u + k + 1;
-                            if (P == 0) ok = true;
-                            else if (P < 0) give_up = true;
+                            const bool eq = eq_by_char ? (qc == rc && qc != 0) : wsc > 0;
+                            wv[k] = wsc;
+                            S += wsc;
+                            xb |= (eq ? 0u : 1u) << k;
                         }
                     }
                 }
+                int inc = S;  // inclusive prefix of the four lanes' sums
+                { const int t = __shfl_up(inc, 1, 4); if (u >= 1) inc += t; }
+                { const int t = __shfl_up(inc, 2, 4); if (u >= 2) inc += t; }
+                const int total = __shfl(inc, 3, 4);
+                int Pl = P - (inc - S);
+                uint32_t key = 0xffffu;  // (first cell of the round with P <= 0) << 1 | (P there != 0)
+#pragma unroll
+                for (int k = 0; k < 8; k++) {
+                    if (k < nv) {
+                        Pl -= wv[k];
+                        key = min(key, Pl <= 0 ? ((uint32_t)(8 * u + k) << 1) | (Pl != 0 ? 1u : 0u) : 0xffffu);
+                    }
+                }
+                key = min(key, (uint32_t)__shfl_xor((int)key, 1, 4));
+                key = min(key, (uint32_t)__shfl_xor((int)key, 2, 4));
+                uint32_t xall = xb << (8 * u);
+                xall |= (uint32_t)__shfl_xor((int)xall, 1, 4);
+                xall |= (uint32_t)__shfl_xor((int)xall, 2, 4);
+                const bool stop = key != 0xffffu;
+                const int n_here = stop ? (int)(key >> 1) + 1 : min(32, kmax - k0);  // cells of the round on the path
+                if (k0 == 0) cur_op = (xall & 1u) ? 8 : 7;
+                // a run starts at every cell whose letter differs from the cell before; past eleven runs the count only has
+                // to say "more than ten ops", so the runs stop being recorded there
+                uint32_t chg = (xall ^ ((xall << 1) | (cur_op == 8 ? 1u : 0u))) & (n_here >= 32 ? 0xffffffffu : ((1u << n_here) - 1u));
+                while (chg != 0u && n_runs <= MAX_RUNS + 1) {
+                    const int b = __builtin_ctz(chg);
+                    chg &= chg - 1u;
+                    push_run(((uint32_t)(k0 + b - cur_start) << 4) | (uint32_t)cur_op);
+                    cur_start = k0 + b;
+                    cur_op = ((xall >> b) & 1u) ? 8 : 7;
+                }
+                if (stop) {
+                    L = k0 + (int)(key >> 1) + 1;
+                    ok = (key & 1u) == 0u;
+                    break;
+                }
+                P -= total;
             }
             bool too_many = false;  // a forced diagonal whose CIGAR has more than 10 ops: analysis.d:69-70 rejects it
             if (ok) {
-                push_run((cur_len << 4) | (uint32_t)cur_op);
+                push_run(((uint32_t)(L - cur_start) << 4) | (uint32_t)cur_op);
                 const int lead0 = f.end_q - L + 1, tail0 = lq - 1 - f.end_q;
                 const int n_all = n_runs + ((pad && lead0 > 0) ? 1 : 0) + ((pad && tail0 > 0) ? 1 : 0);
                 too_many = n_all > 10 && a.meta && a.gate && !a.trace_all;
                 if (n_runs > MAX_RUNS && !too_many) ok = false;
             }
-            if (ok) {
-                cand = false;
+            if (ok && u == 0) {
                 fadehip_aln o;
                 o.read_idx = (int32_t)w.idx;
                 o.art = 0;
@@ -1203,8 +1239,9 @@ __device__ __forceinline__ uint32_t select_one(const SelArgs &a, const int item,
                 dst->sw.n_ops = o.sw.n_ops;
                 }
             }
+            if (ok) cand = false;
         }
-        if (cand) {
+        if (cand && u == 0) {
             // sweep steps the path is expected to span: a cell (i, j) is computed at step j + i / R.  Columns:
             // score/2 for clean matches, a quarter more for mismatches, + slack; rows ~ columns.  Any value is
             // correct (a path that leaves the traced steps is re-run from step 0), this one is cheap.
@@ -1299,6 +1336,26 @@ __device__ __forceinline__ uint32_t bfi(uint32_t mask, uint32_t a, uint32_t b) {
     asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(d) : "v"(mask), "v"(a), "v"(b));
     return d;
 }
+
+// Window staging: scale * class of the base whose complemented code is x, for the 16 codes: 8 bytes for codes 0-7, 8 for codes 8-15
+__host__ __device__ constexpr uint64_t make_cls_rc(uint32_t scale, int half) {
+    uint64_t v = 0;
+    for (int x = 0; x < 8; x++) {
+        const uint32_t code = (uint32_t)((COMP_LUT >> (4 * (x + 8 * half))) & 15u);
+        v |= (uint64_t)(scale * ((CLASS_LUT >> (4 * code)) & 15u)) << (8 * x);
+    }
+    return v;
+}
+struct ClsTab { uint64_t lo, hi; };
+constexpr ClsTab CLS7_RC = {make_cls_rc(7, 0), make_cls_rc(7, 1)}, CLS16_RC = {make_cls_rc(16, 0), make_cls_rc(16, 1)};
+// the table entries of four codes (one per byte, 0-15) at once: v_perm_b32 over each 8-byte half, bit 3 picks the half
+__device__ __forceinline__ uint32_t cls4(uint32_t x, const ClsTab t) {
+    const uint32_t sel = x & 0x07070707u;
+    const uint32_t lo = __builtin_amdgcn_perm((uint32_t)(t.lo >> 32), (uint32_t)t.lo, sel);
+    const uint32_t hi = __builtin_amdgcn_perm((uint32_t)(t.hi >> 32), (uint32_t)t.hi, sel);
+    return bfi(((x >> 3) & 0x01010101u) * 0xffu, hi, lo);
+}
+__device__ __forceinline__ uint32_t bytes_below(int c) { return c >= 4 ? 0xffffffffu : (1u << (8 * c)) - 1u; }  // c = 0 .. 4
 
 constexpr int PK_SCALE = 8;  // must stay 8: the shifts below are log2(8) and log2(8) + 16
 
@@ -1451,15 +1508,21 @@ __global__ __launch_bounds__(64, pk_min_waves(R, MODE, LG, WV)) void sw_pk_kerne
             const uint64_t ra0 = wa.r_base + (uint64_t)k0, rb0 = wb.r_base + (uint64_t)k0;
             if (k0 < lrA) na = load_nib8(a.r_nib, ra0);
             if (k0 < lrB) nb = load_nib8(a.r_nib, rb0);
+            // nibble j of vA / vB = the complemented code of column k0 + j (nib8_up_comp); classes of four columns at a time,
+            // even columns in one dword and odd ones in another, as 7 * class (A) and 16 * class (B); columns past the
+            // window take PAD_CLASS
+            const uint32_t vA = nib8_up_comp(na.word, ra0), vB = nib8_up_comp(nb.word, rb0);
+            const int nA = max(0, min(8, lrA - k0)), nB = max(0, min(8, lrB - k0));
+            constexpr uint32_t PADA = 7u * PAD_CLASS * 0x01010101u, PADB = 16u * PAD_CLASS * 0x01010101u;
+            const uint32_t eA = bfi(bytes_below((nA + 1) >> 1), cls4(vA & 0x0f0f0f0fu, CLS7_RC), PADA);
+            const uint32_t oA = bfi(bytes_below(nA >> 1), cls4((vA >> 4) & 0x0f0f0f0fu, CLS7_RC), PADA);
+            const uint32_t eB = bfi(bytes_below((nB + 1) >> 1), cls4(vB & 0x0f0f0f0fu, CLS16_RC), PADB);
+            const uint32_t oB = bfi(bytes_below(nB >> 1), cls4((vB >> 4) & 0x0f0f0f0fu, CLS16_RC), PADB);
             uint32_t o[4];
 #pragma unroll
-            for (int j = 0; j < 8; j++) {
-                uint32_t ca = PAD_CLASS, cb = PAD_CLASS;
-                if (k0 + j < lrA) ca = lut4(CLASS_LUT, nib8_at(na, ra0 + (uint32_t)j));
-                if (k0 + j < lrB) cb = lut4(CLASS_LUT, nib8_at(nb, rb0 + (uint32_t)j));
-                const uint32_t e = (7u * ca + cb) * 16u;
-                if (j & 1) o[j >> 1] |= e << 16;
-                else o[j >> 1] = e;
+            for (int m = 0; m < 4; m++) {  // columns 2m, 2m + 1: (7 classA + classB) * 16 in the low / high half
+                const uint32_t sel = 0x0c000c00u | ((4u + m) << 16) | (uint32_t)m;
+                o[m] = pk_shl4_add(__builtin_amdgcn_perm(oA, eA, sel), __builtin_amdgcn_perm(oB, eB, sel));
             }
             *reinterpret_cast<uint4 *>(lref + (k0 - c0)) = make_uint4(o[0], o[1], o[2], o[3]);
         }
@@ -1846,18 +1909,19 @@ __global__ __launch_bounds__(64, pk_min_waves(R, MODE, LG, WV)) void sw_pk_kerne
         }
         if constexpr (MODE == 1) {
             if (a.sel.enabled) {
-                // every lane of a group holds both results after the butterfly: lane 0 finishes alignment A, lane 1 B
+                // every lane of a group holds both results after the butterfly: lanes 0-3 finish alignment A, lanes 4-7 B
                 uint32_t art = 0;
-                const int item = lig ? itemB : itemA;
-                if (lig < 2 && item < n_items) {
-                    const uint64_t cc = lig ? cb : ca;
+                const int half = lig >> 2;
+                const int item = half ? itemB : itemA;
+                if (lig < 8 && item < n_items) {
+                    const uint64_t cc = half ? cb : ca;
                     Fwd f;
                     f.score = (int32_t)(cc >> 32) / PK_SCALE;
                     f.end_r = cc ? (int32_t)(0xffff - ((cc >> 16) & 0xffff)) : 0;
                     f.end_q = cc ? (int32_t)(0xffff - (cc & 0xffff)) : 0;
                     f.pad = 0;
                     // (R here is pass 2's rows per lane: it sizes the steps a candidate's re-computation will take)
-                    art = select_one(a.sel, item, lig ? wb : wa, f, LG == 8 ? (R + 1) / 2 : R, a.q_nib, a.r_nib, a.sc.rules);
+                    art = select_one(a.sel, item, half ? wb : wa, f, LG == 8 ? (R + 1) / 2 : R, a.q_nib, a.r_nib, a.sc.rules, lig & 3);
                 }
                 if (a.sel.stats) add_artifact_stats(a.sel.stats, art, blockIdx.x);
             }
