@@ -135,6 +135,10 @@ int fadehip_sw_batch(fadehip_ctx* ctx, int n, const(ubyte)* q, const(long)* q_of
 struct fadehip_sw_stats_result { int score, end_query, end_ref, matches, similar, length; }
 int fadehip_sw_stats_batch(fadehip_ctx* ctx, const(int)* scoring4 /* open, ext, match, mismatch */, int n,
         const(ubyte)* q, const(long)* q_off, const(ubyte)* r, const(long)* r_off, fadehip_sw_stats_result* out_);
+/// filter.d:15-91 clipRead over n BAM records (block_size first), concatenated: record k loses trim_left[k] reference bases at
+/// the front when rs[k] & 2, trim_right[k] at the back when rs[k] & 4, or is reset; out_off receives n + 1 offsets into out_
+int fadehip_clip_batch(fadehip_ctx* ctx, int n, const(ubyte)* recs, const(long)* rec_off, const(ubyte)* rs,
+        const(int)* trim_left, const(int)* trim_right, ubyte* out_, long out_cap, long* out_off);
 int fadehip_genome_upload(fadehip_ctx* ctx, int n_contigs, const(long)* lengths, const(ubyte*)* seqs);
 int fadehip_annotate_upload(fadehip_ctx* ctx, int slot, const(fadehip_read_batch)* batch);
 int fadehip_annotate_run(fadehip_ctx* ctx, int slot, int floor_len, int window);
@@ -162,7 +166,7 @@ struct fadehip_bam_config {
     int floor_len;               /// --min-length
     int window;                  /// -w
     int n_ref;                   /// contigs of the BAM header
-    int flags;                   /// 1 (FADEHIP_BAM_STORED): uncompressed BGZF out; 2 (FADEHIP_BAM_NO_OUTPUT): back makes no BGZF (measurement)
+    int flags;                   /// 1 (FADEHIP_BAM_STORED): uncompressed BGZF out; 2 (FADEHIP_BAM_NO_OUTPUT): back makes no BGZF (measurement); 4 (FADEHIP_BAM_CLIP): hard-clip the artifact calls
     const(char*)* ref_names;     /// [n_ref]
     uint first_record;           /// payload bytes of the first member passed that precede the first record
     uint tail_trim;              /// payload bytes at the end of the last member that belong to the next reader
@@ -170,6 +174,7 @@ struct fadehip_bam_config {
 enum FADEHIP_BAM_CHUNKS = 3;
 enum FADEHIP_BAM_STORED = 1;     /// fadehip_bam_config.flags: uncompressed BGZF out (`fade annotate -u`)
 enum FADEHIP_BAM_NO_OUTPUT = 2;  /// ... back releases the annotated records without compressing them (measurement)
+enum FADEHIP_BAM_CLIP = 4;       /// ... artifact calls leave hard-clipped (`fade annotate -c`), by this run's rs and alignments
 int fadehip_bam_open(fadehip_ctx* ctx, const(fadehip_bam_config)* cfg, fadehip_bam_stream** out_);
 int fadehip_bam_prepare(fadehip_bam_stream* st, size_t call_bytes);
 int fadehip_bam_front(fadehip_bam_stream* st, const(void)* members, size_t n_bytes, int last);

@@ -32,8 +32,9 @@ EXPORTS = [
     "fadehip_sync", "fadehip_last_run_profile", "fadehip_stats_allreduce",
     "fadehip_bgzf_deflate_submit", "fadehip_bgzf_deflate_wait", "fadehip_stats_allreduce_rank", "fadehip_bgzf_inflate",
     "fadehip_bam_open", "fadehip_bam_front", "fadehip_bam_front_raw", "fadehip_bam_back", "fadehip_bam_totals", "fadehip_bam_close",
-    "fadehip_bam_prepare", "fadehip_sw_stats_batch",
+    "fadehip_bam_prepare", "fadehip_sw_stats_batch", "fadehip_clip_batch",
 ]
+BAM_STORED, BAM_NO_OUTPUT, BAM_CLIP = 1, 2, 4  # fadehip_bam_config.flags
 BGZF_BLOCK = 0xff00
 BGZF_LANES = 2
 
@@ -124,6 +125,7 @@ def load():
     L.fadehip_annotate_results.argtypes = [vp, C.c_int, C.POINTER(AnnoView)]
     L.fadehip_sw_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp]
     L.fadehip_sw_stats_batch.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
+    L.fadehip_clip_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, i64, vp]
     L.fadehip_genome_upload.argtypes = [vp, i32, vp, vp]
     L.fadehip_annotate_upload.argtypes = [vp, C.c_int, C.POINTER(ReadBatch)]
     L.fadehip_annotate_run.argtypes = [vp, C.c_int, i32, i32]

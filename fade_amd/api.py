@@ -125,6 +125,33 @@ class Context:
         rc = np.frombuffer(b"".join(rb), dtype=np.uint8) if r_off[-1] else np.zeros(0, np.uint8)
         return self.sw_stats_batch_packed(qc, q_off, rc, r_off, scoring)
 
+    # ---- filter.d:15-91 clipRead (`fade out -c`): the device function of the file path's clip=True, on records brought here
+    def clip_batch_packed(self, recs, rec_off, rs, trim_left, trim_right):
+        recs = np.ascontiguousarray(recs, dtype=np.uint8)
+        rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
+        rs = np.ascontiguousarray(rs, dtype=np.uint8)
+        tl = np.ascontiguousarray(trim_left, dtype=np.int32)
+        tr = np.ascontiguousarray(trim_right, dtype=np.int32)
+        n = len(rec_off) - 1
+        if not (len(rs) == len(tl) == len(tr) == n):
+            raise ValueError("rs, trim_left and trim_right hold one entry per record")
+        out = np.zeros(len(recs) + 8 * n + 8, dtype=np.uint8)  # (a clipped record gains at most two H ops)
+        out_off = np.zeros(n + 1, dtype=np.int64)
+        self._chk(self._L.fadehip_clip_batch(self._h, n, recs.ctypes.data, rec_off.ctypes.data, rs.ctypes.data, tl.ctypes.data,
+                                             tr.ctypes.data, out.ctypes.data, len(out), out_off.ctypes.data))
+        return out[:out_off[n]], out_off
+
+    def clip_batch(self, records, rs, trim_left, trim_right):
+        """Hard-clips BAM records (bytes, block_size first) as `fade out -c` does: record k loses trim_left[k] reference
+        bases at the front when rs[k] & 2 and trim_right[k] at the back when rs[k] & 4 (or is reset when a length is not
+        below its aligned length).  Returns the records as a list of bytes, in order."""
+        rb = [bytes(r) for r in records]
+        off = np.zeros(len(rb) + 1, dtype=np.int64)
+        np.cumsum([len(r) for r in rb], out=off[1:])
+        cat = np.frombuffer(b"".join(rb), dtype=np.uint8) if off[-1] else np.zeros(0, np.uint8)
+        out, out_off = self.clip_batch_packed(cat, off, rs, trim_left, trim_right)
+        return [out[out_off[k]:out_off[k + 1]].tobytes() for k in range(len(rb))]
+
     # ---- level 2: annotateTask over a batch (anno.d:55-110)
     def genome_upload(self, names, seqs):
         """seqs: list of bytes / uint8 arrays (raw FASTA residues)."""
@@ -312,10 +339,11 @@ class Context:
         self.bgzf_deflate_submit(lane, data)
         return self.bgzf_deflate_wait(lane)
 
-    def bam_stream(self, ref_names, floor_len=5, window=300, first_record=0, stored=False, tail_trim=0, no_output=False):
+    def bam_stream(self, ref_names, floor_len=5, window=300, first_record=0, stored=False, tail_trim=0, no_output=False, clip=False):
         """The file path on the device (fadehip_bam_*): BGZF members of a BAM's records in, BGZF members of the annotated
-        records out.  ref_names: the BAM header's contigs (the genome must be uploaded)."""
-        return BamStream(self, ref_names, floor_len, window, first_record, stored, tail_trim, no_output)
+        records out.  ref_names: the BAM header's contigs (the genome must be uploaded).  clip: records called artifacts leave
+        hard-clipped (`fade annotate -c`)."""
+        return BamStream(self, ref_names, floor_len, window, first_record, stored, tail_trim, no_output, clip)
 
     def bgzf_inflate(self, members, out_cap=None):
         """Whole BGZF members (bytes / uint8 array) -> their payloads, inflated on the device (CRC32 and ISIZE checked)."""
@@ -449,11 +477,11 @@ def format_tags(batch, contig_names, rs, aln):
 
 
 class BamStream:
-    def __init__(self, ctx, ref_names, floor_len, window, first_record, stored=False, tail_trim=0, no_output=False):
+    def __init__(self, ctx, ref_names, floor_len, window, first_record, stored=False, tail_trim=0, no_output=False, clip=False):
         self._ctx, self._L = ctx, ctx._L
         names = [n.encode() if isinstance(n, str) else bytes(n) for n in ref_names]
         arr = (C.c_char_p * max(len(names), 1))(*names)
-        cfg = _lib.BamConfig(floor_len, window, len(names), (1 if stored else 0) | (2 if no_output else 0), arr, first_record, tail_trim)
+        cfg = _lib.BamConfig(floor_len, window, len(names), (_lib.BAM_STORED if stored else 0) | (_lib.BAM_NO_OUTPUT if no_output else 0) | (_lib.BAM_CLIP if clip else 0), arr, first_record, tail_trim)
         h = C.c_void_p()
         ctx._chk(self._L.fadehip_bam_open(ctx._h, C.byref(cfg), C.byref(h)))
         self._h = h

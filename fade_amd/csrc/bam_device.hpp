@@ -615,10 +615,174 @@ struct ArtStrings {
     }
 };
 
+// ============================================================================================ hard clip
+// `fade annotate --clip` (FADEHIP_BAM_CLIP) / fadehip_clip_batch: filter.d:15-91 clipRead in the pass that writes the records.
+// The decision (rs bits 1 and 2) and the lengths (reference bases of the artifact alignment's CIGAR) are THIS run's results,
+// never tags read back from the record: a record that came in with a wrong-kind rs:Z or am:i keeps that tag as it is
+// (htslib's EINVAL), and `fade out -c` behind `fade annotate` would then clip by the stale tag — the fused pass clips by what
+// it computed.  That is the one deliberate difference from the two-step pipeline.
+//
+// Left (rs & 2): if the length is below the record's aligned length, ops are taken from the front until that many
+// reference bases are gone — every query base taken (leading S and I too) drops a base and a quality and counts into a new
+// leading H, every reference base moves pos; ops that consume neither go without effect.  Right (rs & 4): the same from the
+// back, against what the left step left; pos stays.  A length that is not below the aligned length resets the record: a
+// zero-filled one that keeps its name and the bases and qualities as trimmed so far.  Whole ops at a time (min(len, left)),
+// not base by base; an op of length zero that the walk reaches is dropped.
+__device__ __forceinline__ bool op_consumes_query(uint32_t op) { return (0x193u >> (op & 15u)) & 1u; }  // M I S = X
+
+struct ClipPlan {
+    uint32_t mode;          // 0: the record leaves as it is, 1: clipped, 2: reset
+    uint32_t sb, lseq;      // first surviving base, number of surviving bases
+    int32_t pos;
+    uint32_t cf, ce;        // surviving ops [cf, ce) of the record's CIGAR ...
+    uint32_t eat_f, eat_b;  // ... less these bases of op cf and of op ce - 1
+    uint32_t has_l, has_r, hard_l, hard_r;  // the H ops that go around them
+    uint32_t ncig;          // ops of the new CIGAR
+    uint32_t bin;
+    uint32_t pre;           // bytes in front of the aux area: block_size, fixed fields, name, CIGAR, bases, qualities
+};
+
+// (every lane of a record's group computes the same plan: the loads are broadcasts and there is nothing to pass around)
+__device__ __forceinline__ ClipPlan clip_plan(const RecHdr &r, uint32_t rs, uint32_t trim_l, uint32_t trim_r) {
+    ClipPlan c;
+    c.mode = 0;
+    if (!(rs & 6u)) return c;
+    const uint8_t *cig = r.p + r.cig_off;
+    const uint32_t lq = r.lseq > 0 ? (uint32_t)r.lseq : 0u;
+    uint64_t aligned = 0;
+    for (uint32_t k = 0; k < r.ncig; k++) {
+        const uint32_t op = ld32(cig + 4u * k);
+        if (FADEHIP_OP_CONSUMES_REF(op & 15u)) aligned += op >> 4;
+    }
+    c.cf = 0; c.ce = r.ncig;
+    c.eat_f = c.eat_b = c.has_l = c.has_r = c.hard_l = c.hard_r = 0;
+    int64_t pos = r.pos;
+    bool reset = false;
+    uint64_t hard_l = 0, hard_r = 0;  // (a CIGAR may claim more query bases than l_seq holds: the bases stop at none left)
+    if (rs & 2u) {
+        uint64_t t = trim_l;
+        if (t < aligned) {  // (so the walk ends inside the CIGAR)
+            while (t && c.cf < c.ce) {
+                const uint32_t op = ld32(cig + 4u * c.cf), len = op >> 4;
+                uint32_t k = len;
+                if (FADEHIP_OP_CONSUMES_REF(op & 15u)) { k = (uint32_t)min((uint64_t)len, t); t -= k; pos += k; }
+                if (op_consumes_query(op)) hard_l += k;
+                if (k == len) c.cf++; else c.eat_f = k;
+            }
+            aligned -= trim_l;
+            c.has_l = 1;
+        } else reset = true;
+    }
+    const uint32_t sb = (uint32_t)min(hard_l, (uint64_t)lq);
+    uint32_t left = lq - sb;
+    if (!reset && (rs & 4u)) {
+        uint64_t t = trim_r;
+        if (t < aligned) {
+            while (t && c.ce > c.cf) {
+                const uint32_t op = ld32(cig + 4u * (c.ce - 1u)), len = (op >> 4) - (c.ce - 1u == c.cf ? c.eat_f : 0u);
+                uint32_t k = len;
+                if (FADEHIP_OP_CONSUMES_REF(op & 15u)) { k = (uint32_t)min((uint64_t)len, t); t -= k; }
+                if (op_consumes_query(op)) hard_r += k;
+                if (k == len) c.ce--; else c.eat_b = k;
+            }
+            aligned -= trim_r;
+            c.has_r = 1;
+            left -= (uint32_t)min(hard_r, (uint64_t)left);
+        } else reset = true;
+    }
+    c.sb = sb;
+    c.lseq = left;
+    if (reset) {  // build_rec(name, 0, 0, 0, 0, 0, 0, 0, {}, bases, qualities)
+        c.mode = 2;
+        c.pos = 0;
+        c.ncig = 0;
+        c.bin = 4681;  // reg2bin(0, 1)
+    } else {
+        c.mode = 1;
+        c.pos = (int32_t)pos;
+        c.hard_l = (uint32_t)hard_l;
+        c.hard_r = (uint32_t)hard_r;
+        c.ncig = c.has_l + (c.ce - c.cf) + c.has_r;
+        // reg2bin over the new span, as build_rec has it
+        const int64_t beg = c.pos < 0 ? 0 : c.pos, end = beg + (aligned > 0 ? (int64_t)aligned : 1) - 1;
+        c.bin = beg >> 14 == end >> 14 ? (uint32_t)(4681 + (beg >> 14))
+              : beg >> 17 == end >> 17 ? (uint32_t)(585 + (beg >> 17))
+              : beg >> 20 == end >> 20 ? (uint32_t)(73 + (beg >> 20))
+              : beg >> 23 == end >> 23 ? (uint32_t)(9 + (beg >> 23))
+              : beg >> 26 == end >> 26 ? (uint32_t)(1 + (beg >> 26)) : 0u;
+    }
+    c.pre = 36u + r.lname + 4u * c.ncig + (c.lseq + 1u) / 2u + c.lseq;
+    return c;
+}
+
+// n bytes by the sixteen lanes of a record: (unaligned) dwords, then the bytes that are left
+__device__ __forceinline__ void copy16(uint8_t *to, const uint8_t *from, uint32_t n, uint32_t sl) {
+    const uint32_t whole = n & ~3u;
+    for (uint32_t q = 4u * sl; q < whole; q += 64u) *reinterpret_cast<u32u *>(to + q) = ld32(from + q);
+    if (sl < n - whole) to[whole + sl] = from[whole + sl];
+}
+
+// The clipped (or reset) record up to its aux area, by the record's sixteen lanes: the fixed fields a dword per lane, the
+// name, the new CIGAR an op per lane, the bases — shifted by a nibble when an odd number of them went at the front — and
+// the qualities.  bs_out = the record's block_size as it leaves.
+__device__ __forceinline__ void clip_write_head(const RecHdr &r, const ClipPlan &c, uint8_t *dst, uint32_t bs_out, uint32_t sl) {
+    if (sl < 9u) {
+        uint32_t v = c.mode == 2u ? 0u : ld32(r.p + 4u * sl);  // (reset: refID, pos, mapq, flag, mate fields and tlen are zero)
+        if (sl == 0u) v = bs_out;
+        if (sl == 2u) v = (uint32_t)c.pos;
+        if (sl == 3u) v = (c.mode == 2u ? r.lname : (v & 0xffffu)) | (c.bin << 16);
+        if (sl == 4u) v = (v & 0xffff0000u) | (c.ncig & 0xffffu);
+        if (sl == 5u) v = c.lseq;
+        *reinterpret_cast<u32u *>(dst + 4u * sl) = v;
+    }
+    copy16(dst + 36u, r.p + 36u, r.lname, sl);
+    uint8_t *oc = dst + 36u + r.lname;
+    for (uint32_t j = sl; j < c.ncig; j += 16u) {
+        uint32_t v;
+        const uint32_t idx = c.cf + j - c.has_l;
+        if (c.has_l && j == 0u) v = (c.hard_l << 4) | 5u;
+        else if (idx >= c.ce) v = (c.hard_r << 4) | 5u;
+        else v = ld32(r.p + r.cig_off + 4u * idx) - (((idx == c.cf ? c.eat_f : 0u) + (idx + 1u == c.ce ? c.eat_b : 0u)) << 4);
+        *reinterpret_cast<u32u *>(oc + 4u * j) = v;
+    }
+    uint8_t *os = oc + 4u * c.ncig;
+    const uint8_t *s = r.p + r.seq_off + (c.sb >> 1);
+    const uint32_t nb = (c.lseq + 1u) / 2u, whole = nb & ~3u;
+    const bool odd = c.sb & 1u, pad = c.lseq & 1u;  // pad: the last byte's low nibble is no base (zero, as build_rec leaves it)
+    for (uint32_t q = 4u * sl; q < whole; q += 64u) {
+        uint32_t v = ld32(s + q);
+        if (odd) {  // (the byte behind the dword is a byte of the record: bases or, behind them, the first quality)
+            const uint64_t w = (uint64_t)v | ((uint64_t)s[q + 4u] << 32);
+            v = (uint32_t)((w & 0x0f0f0f0full) << 4) | (uint32_t)((w >> 12) & 0x0f0f0f0full);
+        }
+        if (pad && q + 4u == nb) v &= 0xf0ffffffu;
+        *reinterpret_cast<u32u *>(os + q) = v;
+    }
+    if (sl < nb - whole) {
+        const uint32_t k = whole + sl;
+        uint32_t b = odd ? ((uint32_t)s[k] << 4) | ((uint32_t)s[k + 1u] >> 4) : s[k];
+        if (pad && k + 1u == nb) b &= 0xf0u;
+        os[k] = (uint8_t)b;
+    }
+    copy16(os + nb, r.p + r.qual_off + c.sb, c.lseq, sl);
+}
+
+// reference bases of an artifact alignment's CIGAR: what `fade out -c` parses back from the am tag (filter.d:24-27,58-61)
+__device__ __forceinline__ uint32_t art_ref_len(const fadehip_aln *a) {
+    const int nops = min(a->sw.n_ops, FADEHIP_MAX_OPS);
+    uint32_t n = 0;
+    for (int q = 0; q < nops; q++)
+        if (FADEHIP_OP_CONSUMES_REF(a->sw.ops[q] & 15u)) n += a->sw.ops[q] >> 4;
+    return n;
+}
+
 // The record as it leaves: block_size, the record's bytes, and the tags of anno.d:63,94-107 — appended when absent,
 // updated the way htslib's bam_aux_update_int / bam_aux_update_str do when the record already carries them (first
 // occurrence, in place or replaced at the same position).  One thread; `out` = nullptr counts.  Returns the bytes.
-__device__ __forceinline__ uint32_t emit_record(const RecHdr &r, uint32_t info, uint8_t rs, const fadehip_aln *a, const Names *nm, uint8_t *out) {
+// CLIP: the record is being hard-clipped (clip_plan below); `pre` bytes — block_size, the fixed fields, name, CIGAR, bases and
+// qualities as clipped — go in front of the aux area and are written by the caller's lanes, as is block_size.
+template <bool CLIP>
+__device__ __forceinline__ uint32_t emit_record(const RecHdr &r, uint32_t info, uint8_t rs, const fadehip_aln *a, const Names *nm, uint8_t *out, uint32_t pre = 0) {
     Sink s{out, 4u};  // (block_size is written last)
     ArtStrings st;
     if (a) st.init(&r, a, nm);
@@ -626,10 +790,12 @@ __device__ __forceinline__ uint32_t emit_record(const RecHdr &r, uint32_t info, 
     bool done[5] = {false, a == nullptr, a == nullptr, a == nullptr, a == nullptr};  // (no artifact: the strings are not touched)
     if (!(info & INFO_OURS)) {
         // the body is copied by the caller's wave (rewrite kernel) or counted here
-        s.n += r.bs;
+        if constexpr (CLIP) s.n = pre + (r.end - r.aux_off);
+        else s.n += r.bs;
     } else {
         // fixed part up to the aux area, then field by field
-        for (uint32_t k = 4; k < r.aux_off; k++) s.put(r.p[k]);
+        if constexpr (CLIP) s.n = pre;
+        else for (uint32_t k = 4; k < r.aux_off; k++) s.put(r.p[k]);
         uint32_t q = r.aux_off;
         while (q + 3u <= r.end) {
             const uint32_t fs = aux_field_size(r.p, q + 2u, r.end);
@@ -675,7 +841,7 @@ __device__ __forceinline__ uint32_t emit_record(const RecHdr &r, uint32_t info, 
             st.string(t - 1, s);
             s.put(0);
         }
-    if (out) {
+    if (!CLIP && out) {
         const uint32_t bs = s.n - 4u;
         out[0] = (uint8_t)bs; out[1] = (uint8_t)(bs >> 8); out[2] = (uint8_t)(bs >> 16); out[3] = (uint8_t)(bs >> 24);
     }
@@ -709,6 +875,9 @@ __device__ __forceinline__ const fadehip_aln *aln_of(const TagArgs &a, int32_t s
     return k >= 0 ? a.aln + k : nullptr;
 }
 
+// CLIP (FADEHIP_BAM_CLIP) is a parameter of the kernels themselves, not of a body they share: <false> is, instruction for
+// instruction, the kernel of before the flag existed (a shared body inlined into two kernels was not).
+template <bool CLIP>
 __global__ __launch_bounds__(TAG_BLOCK) void bam_tag_size_kernel(TagArgs a) {
     __shared__ uint64_t red[TAG_BLOCK / 64];
     const uint32_t r1 = min(a.r1_cap, a.counts_in->n_records);
@@ -719,7 +888,20 @@ __global__ __launch_bounds__(TAG_BLOCK) void bam_tag_size_kernel(TagArgs a) {
         uint8_t rs;
         const fadehip_aln *al = aln_of(a, a.sent_of[i - a.r0], &rs);
         const uint32_t info = a.info[i - a.r0];
-        sz = (info & INFO_BAD) ? 0u : emit_record(r, info, rs, al, &a.names, nullptr);
+        if constexpr (CLIP) {
+            ClipPlan c;
+            c.mode = 0;
+            if (al && !(info & INFO_BAD)) {
+                const uint32_t trim = art_ref_len(al);
+                c = clip_plan(r, rs, trim, trim);
+            }
+            if (info & INFO_BAD) sz = 0u;
+            else if (c.mode == 1u) sz = emit_record<true>(r, info, rs, al, &a.names, nullptr, c.pre);
+            else if (c.mode == 2u) sz = c.pre;  // (a reset record has no aux area)
+            else sz = emit_record<false>(r, info, rs, al, &a.names, nullptr);
+        } else {
+            sz = (info & INFO_BAD) ? 0u : emit_record<false>(r, info, rs, al, &a.names, nullptr);
+        }
         a.out_size[i - a.r0] = (uint32_t)sz;
     }
 #pragma unroll
@@ -756,6 +938,7 @@ __global__ __launch_bounds__(1024) void bam_tag_scan_kernel(TagArgs a, uint32_t 
 // a wave that took its records one after the other spent 22 us on each; four chains side by side, and a third of the copy
 // instructions.  A block serves the TAG_BLOCK records of one tag-size block (whose base applies) with REWRITE_WAVES waves.
 constexpr int REWRITE_WAVES = 16;
+template <bool CLIP>
 __global__ __launch_bounds__(REWRITE_WAVES * 64) void bam_rewrite_kernel(TagArgs a) {
     __shared__ uint64_t off[TAG_BLOCK];
     __shared__ uint64_t wave_sum[TAG_BLOCK / 64 + 1];
@@ -793,6 +976,24 @@ __global__ __launch_bounds__(REWRITE_WAVES * 64) void bam_rewrite_kernel(TagArgs
         if (info & INFO_BAD) continue;
         const RecHdr r = rec_header(a.u + a.rec_off[ij]);
         uint8_t *dst = a.o + off[k];
+        if constexpr (CLIP) {
+            // the clipped record: everything in front of the aux area and an aux area that is only copied by the sixteen
+            // lanes, the tags (and an aux area that carries some of them already) by the first
+            uint8_t rs;
+            const fadehip_aln *al = aln_of(a, a.sent_of[ij - a.r0], &rs);
+            if (al) {
+                const uint32_t trim = art_ref_len(al);
+                const ClipPlan c = clip_plan(r, rs, trim, trim);
+                if (c.mode) {
+                    clip_write_head(r, c, dst, a.out_size[ij - a.r0] - 4u, sl);
+                    if (c.mode == 1u) {
+                        if (!(info & INFO_OURS)) copy16(dst + c.pre, r.p + r.aux_off, r.end - r.aux_off, sl);
+                        if (sl == 0) emit_record<true>(r, info, rs, al, &a.names, dst, c.pre);
+                    }
+                    continue;
+                }
+            }
+        }
         if (!(info & INFO_OURS)) {
             const uint32_t nbody = r.end - 4u, whole = nbody & ~3u;
             const uint8_t *from = r.p + 4;
@@ -803,9 +1004,38 @@ __global__ __launch_bounds__(REWRITE_WAVES * 64) void bam_rewrite_kernel(TagArgs
         if (sl == 0) {
             uint8_t rs;
             const fadehip_aln *al = aln_of(a, a.sent_of[ij - a.r0], &rs);
-            emit_record(r, info, rs, al, &a.names, dst);  // (a record without our tags: its body is counted, not written, here)
+            emit_record<false>(r, info, rs, al, &a.names, dst);  // (a record without our tags: its body is counted, not written, here)
         }
     }
+}
+
+// ---- fadehip_clip_batch: clip_plan / clip_write_head over records the caller brings, with the caller's rs and lengths
+struct ClipBatchArgs {
+    const uint8_t *in;
+    const uint64_t *in_off;    // [n + 1]
+    const uint8_t *rs;         // [n]
+    const uint32_t *trim_l, *trim_r;  // [n] reference bases
+    uint32_t n;
+    uint32_t *out_size;        // [n]   (size kernel)
+    const uint64_t *out_off;   // [n]   (write kernel)
+    uint8_t *out;
+};
+__global__ __launch_bounds__(256) void clip_batch_size_kernel(ClipBatchArgs a) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= a.n) return;
+    const RecHdr r = rec_header(a.in + a.in_off[i]);
+    const ClipPlan c = clip_plan(r, a.rs[i], a.trim_l[i], a.trim_r[i]);
+    a.out_size[i] = c.mode == 2u ? c.pre : c.mode == 1u ? c.pre + (r.end - r.aux_off) : r.end;
+}
+__global__ __launch_bounds__(256) void clip_batch_write_kernel(ClipBatchArgs a) {
+    const uint32_t i = blockIdx.x * 16u + (threadIdx.x >> 4), sl = threadIdx.x & 15u;
+    if (i >= a.n) return;
+    const RecHdr r = rec_header(a.in + a.in_off[i]);
+    const ClipPlan c = clip_plan(r, a.rs[i], a.trim_l[i], a.trim_r[i]);
+    uint8_t *dst = a.out + a.out_off[i];
+    if (!c.mode) { copy16(dst, r.p, r.end, sl); return; }
+    clip_write_head(r, c, dst, a.out_size[i] - 4u, sl);
+    if (c.mode == 1u) copy16(dst + c.pre, r.p + r.aux_off, r.end - r.aux_off, sl);
 }
 
 }  // namespace bam

@@ -192,6 +192,10 @@ struct fadehip_ctx {
     hipStream_t stats_stream = nullptr;
     DevBuf st_q, st_r, st_work, st_out, st_scratch;
     std::mutex stats_mu;
+    // fadehip_clip_batch: likewise
+    hipStream_t clip_stream = nullptr;
+    DevBuf cl_in, cl_meta, cl_size, cl_out;
+    std::mutex clip_mu;
     int n_contigs = 0;
     std::vector<int64_t> h_contig_len;
     std::vector<uint64_t> h_contig_base;
@@ -1455,6 +1459,8 @@ void fadehip_destroy(fadehip_ctx *ctx) {
     for (DevBuf *b : {&ctx->l1_q, &ctx->l1_r, &ctx->l1_qn, &ctx->l1_rn, &ctx->l1_bad, &ctx->l1_work, &ctx->l1_aln}) release(*b);
     for (DevBuf *b : {&ctx->st_q, &ctx->st_r, &ctx->st_work, &ctx->st_out, &ctx->st_scratch}) release(*b);
     if (ctx->stats_stream) (void)hipStreamDestroy(ctx->stats_stream);
+    for (DevBuf *b : {&ctx->cl_in, &ctx->cl_meta, &ctx->cl_size, &ctx->cl_out}) release(*b);
+    if (ctx->clip_stream) (void)hipStreamDestroy(ctx->clip_stream);
     release(ctx->contig_len);
     release(ctx->contig_base);
     if (g_err_ctx == ctx) g_err_ctx = nullptr;
@@ -1740,6 +1746,87 @@ int fadehip_sw_stats_batch(fadehip_ctx *ctx, const int32_t scoring[4], int32_t n
         HIPCHK(ctx, hipGetLastError());
     }
     HIPCHK(ctx, hipMemcpyAsync(out, d_out, (size_t)n * sizeof(fadehip_sw_stats_result), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    return 0;
+}
+
+// filter.d:15-91 over records the caller brings: bam_device.hpp's clip_plan / clip_write_head, the functions of the file
+// path under FADEHIP_BAM_CLIP, with the caller's rs and lengths in place of a run's results.
+int fadehip_clip_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const int64_t *rec_off, const uint8_t *rs,
+                       const int32_t *trim_left, const int32_t *trim_right, uint8_t *out, int64_t out_cap, int64_t *out_off) {
+    if (!ctx) return set_err(nullptr, FADEHIP_E_INVALID, "ctx is NULL");
+    if (n < 0 || !rec_off || !out_off || (n > 0 && (!recs || !rs || !trim_left || !trim_right)) || out_cap < 0 || (out_cap > 0 && !out))
+        return set_err(ctx, FADEHIP_E_INVALID, "NULL argument");
+    if (rec_off[0] < 0) return set_err(ctx, FADEHIP_E_INVALID, "offsets must be non-negative and non-decreasing (record 0)");
+    out_off[0] = 0;
+    if (n == 0) return 0;
+    // what the kernels dereference through is checked here: block_size against the offsets, the fields against block_size
+    for (int32_t k = 0; k < n; k++) {
+        const int64_t len = rec_off[k + 1] - rec_off[k];
+        if (len < 0) return set_err(ctx, FADEHIP_E_INVALID, "offsets must be non-negative and non-decreasing (record %d)", k);
+        const uint8_t *p = recs + rec_off[k];
+        uint32_t bs = 0, ncig = 0;
+        int32_t lseq = 0;
+        if (len >= 36) {
+            memcpy(&bs, p, 4);
+            memcpy(&lseq, p + 20, 4);
+            ncig = (uint32_t)p[16] | ((uint32_t)p[17] << 8);
+        }
+        if (len < 36 || len > ((int64_t)1 << 29) || (int64_t)bs + 4 != len || lseq < 0 || p[12] == 0 ||
+            36ull + p[12] + 4ull * ncig + ((uint64_t)lseq + 1) / 2 + (uint64_t)lseq > (uint64_t)len)
+            return set_err(ctx, FADEHIP_E_INVALID, "record %d is malformed (block_size, l_read_name, n_cigar_op and l_seq must fit its %lld bytes)", k, (long long)len);
+        if (trim_left[k] < 0 || trim_right[k] < 0) return set_err(ctx, FADEHIP_E_INVALID, "record %d: negative trim length", k);
+    }
+    const size_t in_bytes = (size_t)(rec_off[n] - rec_off[0]);
+    std::vector<uint64_t> off((size_t)n + 1);
+    for (int32_t k = 0; k <= n; k++) off[(size_t)k] = (uint64_t)(rec_off[k] - rec_off[0]);
+    std::lock_guard<std::mutex> lk(ctx->clip_mu);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (!ctx->clip_stream) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->clip_stream, hipStreamNonBlocking));
+    hipStream_t st = ctx->clip_stream;
+    // cl_meta: in_off [n + 1] u64 | out_off [n + 1] u64 | trim_l [n] u32 | trim_r [n] u32 | rs [n] u8
+    const size_t m_out = 8 * ((size_t)n + 1), m_tl = 2 * m_out, m_tr = m_tl + 4 * (size_t)n, m_rs = m_tr + 4 * (size_t)n;
+    int rc;
+    if ((rc = reserve(ctx, ctx->cl_in, in_bytes + 8)) || (rc = reserve(ctx, ctx->cl_meta, m_rs + (size_t)n + 8)) ||
+        (rc = reserve(ctx, ctx->cl_size, 4 * (size_t)n)))
+        return rc;
+    uint8_t *meta = (uint8_t *)ctx->cl_meta.p;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->cl_in.p, recs + rec_off[0], in_bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(meta, off.data(), m_out, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(meta + m_tl, trim_left, 4 * (size_t)n, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(meta + m_tr, trim_right, 4 * (size_t)n, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(meta + m_rs, rs, (size_t)n, hipMemcpyHostToDevice, st));
+    bam::ClipBatchArgs a;
+    a.in = (const uint8_t *)ctx->cl_in.p;
+    a.in_off = (const uint64_t *)meta;
+    a.rs = meta + m_rs;
+    a.trim_l = (const uint32_t *)(meta + m_tl);
+    a.trim_r = (const uint32_t *)(meta + m_tr);
+    a.n = (uint32_t)n;
+    a.out_size = (uint32_t *)ctx->cl_size.p;
+    a.out_off = (const uint64_t *)(meta + m_out);
+    a.out = nullptr;
+    hipLaunchKernelGGL(bam::clip_batch_size_kernel, dim3(((unsigned)n + 255u) / 256u), dim3(256), 0, st, a);
+    HIPCHK(ctx, hipGetLastError());
+    std::vector<uint32_t> sizes((size_t)n);
+    HIPCHK(ctx, hipMemcpyAsync(sizes.data(), a.out_size, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    uint64_t run = 0;
+    for (int32_t k = 0; k < n; k++) {
+        off[(size_t)k] = run;
+        run += sizes[(size_t)k];
+        out_off[k + 1] = (int64_t)run;
+    }
+    off[(size_t)n] = run;
+    const size_t out_bytes = (size_t)run;
+    if ((int64_t)out_bytes > out_cap)
+        return set_err(ctx, FADEHIP_E_INVALID, "the clipped records take %lld bytes, out holds %lld", (long long)out_bytes, (long long)out_cap);
+    if ((rc = reserve(ctx, ctx->cl_out, out_bytes + 8))) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(meta + m_out, off.data(), m_out, hipMemcpyHostToDevice, st));
+    a.out = (uint8_t *)ctx->cl_out.p;
+    hipLaunchKernelGGL(bam::clip_batch_write_kernel, dim3(((unsigned)n + 15u) / 16u), dim3(256), 0, st, a);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(out, a.out, out_bytes, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     return 0;
 }
@@ -2278,6 +2365,7 @@ struct fadehip_bam_stream {
     int32_t floor_len = 0, window = 0, n_ref = 0;
     uint32_t first_record = 0, tail_trim = 0;
     bool stored = false;  // uncompressed BGZF out
+    bool clip = false;    // FADEHIP_BAM_CLIP: artifact calls leave hard-clipped (the <true> kernels of bam_device.hpp)
     bool no_output = false;  // FADEHIP_BAM_NO_OUTPUT: back gives the call's device bytes back without making BGZF of them
     DevBuf names_text, names_off;
     struct Out {
@@ -2377,7 +2465,8 @@ int bam_finish_call(fadehip_bam_stream *st, uint64_t k) {
         if (out_bytes > ((uint64_t)1 << 31)) return set_err(ctx, FADEHIP_E_UNSUPPORTED, "bam stream: %llu output bytes in one call (at most 2^31)", (unsigned long long)out_bytes);
         if ((rc = reserve_roomy(ctx, out->o, (size_t)out_bytes + 256))) return rc;
         S.ta.o = (uint8_t *)out->o.p;
-        hipLaunchKernelGGL(bam::bam_rewrite_kernel, dim3(S.ntb), dim3(bam::REWRITE_WAVES * 64), 0, q, S.ta);
+        if (st->clip) hipLaunchKernelGGL(bam::bam_rewrite_kernel<true>, dim3(S.ntb), dim3(bam::REWRITE_WAVES * 64), 0, q, S.ta);
+        else hipLaunchKernelGGL(bam::bam_rewrite_kernel<false>, dim3(S.ntb), dim3(bam::REWRITE_WAVES * 64), 0, q, S.ta);
         HIPCHK(ctx, hipGetLastError());
         out->bytes = (size_t)out_bytes;
         std::lock_guard<std::mutex> l(st->mu);
@@ -2656,7 +2745,8 @@ int bam_front_impl(fadehip_bam_stream *st, const uint8_t *members, size_t n_byte
         ta.blk_base = ta.blk_sums + ntb;
         ta.counts = d_counts;
         ta.out_base = 0;
-        hipLaunchKernelGGL(bam::bam_tag_size_kernel, dim3(ntb), dim3(bam::TAG_BLOCK), 0, q, ta);
+        if (st->clip) hipLaunchKernelGGL(bam::bam_tag_size_kernel<true>, dim3(ntb), dim3(bam::TAG_BLOCK), 0, q, ta);
+        else hipLaunchKernelGGL(bam::bam_tag_size_kernel<false>, dim3(ntb), dim3(bam::TAG_BLOCK), 0, q, ta);
         HIPCHK(ctx, hipGetLastError());
         hipLaunchKernelGGL(bam::bam_tag_scan_kernel, dim3(1), dim3(1024), 0, q, ta, ntb);
         HIPCHK(ctx, hipGetLastError());
@@ -2683,7 +2773,7 @@ int bam_front_impl(fadehip_bam_stream *st, const uint8_t *members, size_t n_byte
 
 int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_bam_stream **out) {
     if (!ctx) return set_err(nullptr, FADEHIP_E_INVALID, "ctx is NULL");
-    if (!cfg || !out || cfg->n_ref < 0 || (cfg->n_ref && !cfg->ref_names) || cfg->window < 0 || (cfg->flags & ~(FADEHIP_BAM_STORED | FADEHIP_BAM_NO_OUTPUT)))
+    if (!cfg || !out || cfg->n_ref < 0 || (cfg->n_ref && !cfg->ref_names) || cfg->window < 0 || (cfg->flags & ~(FADEHIP_BAM_STORED | FADEHIP_BAM_NO_OUTPUT | FADEHIP_BAM_CLIP)))
         return set_err(ctx, FADEHIP_E_INVALID, "bam stream: bad configuration");
     if (!ctx->two_pass) return set_err(ctx, FADEHIP_E_UNSUPPORTED, "bam stream: needs the default kernels (FADEHIP_KERNEL unset)");
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -2697,6 +2787,7 @@ int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_ba
     st->tail_trim = cfg->tail_trim;
     st->stored = (cfg->flags & FADEHIP_BAM_STORED) != 0;
     st->no_output = (cfg->flags & FADEHIP_BAM_NO_OUTPUT) != 0;
+    st->clip = (cfg->flags & FADEHIP_BAM_CLIP) != 0;
     std::string text;
     std::vector<uint32_t> off((size_t)cfg->n_ref + 1, 0);
     for (int k = 0; k < cfg->n_ref; k++) {

@@ -64,6 +64,7 @@ static void print_anno_help() {
             "-w --window-size Number of bases considered outside of read or mate region for re-alignment\n"
             "-b         --bam output bam\n"
             "-u        --ubam output uncompressed bam\n"
+            "-c        --clip hard-clip the artifacts in the same pass (what `fade out -c` makes of the annotated file)\n"
             "          --gpus number of MI355X devices, one process each on its own range of the input (default 1)\n"
             "    --out-shards with --gpus N: every device writes a complete file PREFIX.<k>.bam (.sam), nothing is merged\n"
             "         --batch records per device batch (default 262144)\n"
@@ -372,6 +373,8 @@ static void artifact_strings(const R &r, const fadehip_aln &a, const Header &h, 
     for (int k = 0; k < 4; k++) out[k] = l[k] + ";" + rr[k];  // anno.d:100-106
 }
 
+static void clip_read(Rec &rec, uint32_t rsv, const int64_t *ref_len = nullptr);
+
 static void tag_owned_record(Rec &r, uint8_t rs, const fadehip_aln *a, const Header &h) {
     r.aux_update_uint("rs", rs);  // anno.d:63,94
     if (!a) return;
@@ -385,7 +388,9 @@ static void tag_owned_record(Rec &r, uint8_t rs, const fadehip_aln *a, const Hea
 
 // anno.d:94-107 over a chunk: rs for every record (0 for the ones anno.d:61-65 settles without the device), the artifact
 // strings for the few that have them, keeping the reference's tag order rs, am, as, ar, ab
-static void apply_tags(Chunk &c, const Header &h, Pool &pool) {
+// clip (`fade annotate -c`): an artifact call is rebuilt as a whole too, tagged, and then hard-clipped by clip_read — with the
+// lengths of the batch's alignment, not of the am text (a record that came in with am:i keeps that tag and is clipped all the same)
+static void apply_tags(Chunk &c, const Header &h, Pool &pool, bool clip = false) {
     const size_t n = c.n_records();
     std::vector<uint8_t> rs(n, 0);
     for (size_t k = 0; k < c.sent.size(); k++) rs[c.sent[k]] = c.rs_sent[k];
@@ -416,10 +421,18 @@ static void apply_tags(Chunk &c, const Header &h, Pool &pool) {
                 p += 2 + fs;
             }
             const fadehip_aln *a = art_of[i] >= 0 ? &c.art[(size_t)art_of[i]] : nullptr;
-            if (has_ours) {
+            const bool clip_it = clip && a && (rs[i] & 6);
+            if (has_ours || clip_it) {
                 Rec r;
                 r.d.assign(v.bytes(), v.bytes() + v.nbytes());
                 tag_owned_record(r, rs[i], a, h);
+                if (clip_it) {
+                    int64_t n_ref = 0;
+                    for (int q = 0; q < std::min<int>(a->sw.n_ops, FADEHIP_MAX_OPS); q++)
+                        if (FADEHIP_OP_CONSUMES_REF(a->sw.ops[q] & 15u)) n_ref += a->sw.ops[q] >> 4;
+                    const int64_t lens[2] = {n_ref, n_ref};  // (am names the one alignment on both sides)
+                    clip_read(r, rs[i], lens);
+                }
                 owned_t[t].emplace_back((uint32_t)i, std::move(r));
                 continue;
             }
@@ -1046,6 +1059,7 @@ static int annotate_lanes_main(const std::string &cl, const Opts &o, bool *fall_
                                          "-w", std::to_string(o.window), "--batch", std::to_string(o.batch)};
         if (o.bam) args.push_back("-b");
         if (o.ubam) args.push_back("-u");
+        if (o.clip) args.push_back("-c");
         if (o.timing) args.push_back("--timing");
         args.push_back(o.pos[1]);
         args.push_back(o.pos[2]);
@@ -1375,6 +1389,7 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
             cfg.first_record = first_rec;
             cfg.tail_trim = host_inflate ? 0 : tail_trim;
             cfg.flags = o.ubam ? FADEHIP_BAM_STORED : 0;  // -u: uncompressed BGZF (util.d:65-76, SAMWriterTypes.UBAM)
+            if (o.clip) cfg.flags |= FADEHIP_BAM_CLIP;    // -c: the artifact calls leave hard-clipped
             if (fadehip_bam_open(ctx, &cfg, &st)) { create_err = fadehip_last_error(ctx); return 1; }
             const size_t call_bytes = host_inflate ? chunk : std::min<size_t>(chunk * 3, (size_t)1 << 30);
             if (!(getenv("FADE_BAM_PREPARE") && atoi(getenv("FADE_BAM_PREPARE")) == 0) && fadehip_bam_prepare(st, call_bytes)) { create_err = fadehip_last_error(ctx); return 1; }
@@ -1956,7 +1971,7 @@ static int annotate_main(const std::string &cl, const Opts &o) {
             try {
                 while (q_out.pop(c)) {
                     ck_tags.start();
-                    apply_tags(*c, hdr, pool);
+                    apply_tags(*c, hdr, pool, o.clip);
                     if (reports.on()) reports.add(*c, hdr, ctxs[(size_t)c->dev]);
                     ck_tags.stop();
                     ck_write.start();
@@ -2395,8 +2410,9 @@ static Rec build_rec(const std::string &qname, int32_t tid, int32_t pos, int map
     return n;
 }
 
-// filter.d:15-91 clipRead
-static void clip_read(Rec &rec, uint32_t rsv) {
+// filter.d:15-91 clipRead.  ref_len: the reference bases to take left and right when the caller knows them (`fade annotate -c`:
+// the batch's alignment); otherwise they are parsed back from the am tag, as `fade out -c` must.
+static void clip_read(Rec &rec, uint32_t rsv, const int64_t *ref_len) {
     std::vector<uint32_t> cig((size_t)rec.n_cigar());
     for (int k = 0; k < rec.n_cigar(); k++) cig[(size_t)k] = rec.cigar_op(k);
     int64_t pos = rec.pos();
@@ -2413,6 +2429,7 @@ static void clip_read(Rec &rec, uint32_t rsv) {
     const size_t semi = am.find(';');
     const std::string sides[2] = {am.substr(0, semi), semi == std::string::npos ? std::string() : am.substr(semi + 1)};
     auto art_ref_len = [&](int side) -> int64_t {
+        if (ref_len) return ref_len[side];
         const std::string &f = sides[side];
         const size_t c1 = f.find(','), c2 = c1 == std::string::npos ? c1 : f.find(',', c1 + 1);
         std::vector<uint32_t> ac;
@@ -2558,7 +2575,7 @@ int main(int argc, char **argv) {
             fprintf(stderr, "std.getopt.GetOptException: %s\n", err.c_str());
             return 1;
         }
-        if (!options_allowed(o, "tmwbugBsTSPQ")) return 1;
+        if (!options_allowed(o, "tmwbucgBsTSPQ")) return 1;
         // app.d:84-89: helpWanted | args.length < 3 (args = prog, "annotate", positionals...)
         if (o.help || o.pos.size() < 2) { print_anno_help(); return 0; }
         if (o.pos.size() < 3) {  // the reference indexes args[2] and dies; say why instead
@@ -2576,9 +2593,17 @@ int main(int argc, char **argv) {
                     o.gpus > 1 ? "--gpus N > 1" : "--out-shards");
             return 1;
         }
+        if (reports && o.clip) {  // the reports describe the unclipped records
+            fprintf(stderr, "[E::fade-annotate] %s describes unclipped records: not with --clip\n", !o.stats_tsv.empty() ? "--stats-tsv" : "--clip-tsv");
+            return 1;
+        }
         if (!o.out_shards.empty() && o.gpus < 2) {
             fprintf(stderr, "[E::fade-annotate] --out-shards PREFIX writes one file per device: it goes with --gpus N (N >= 2)\n");
             return 1;
+        }
+        if (o.clip && !lane_env().on) {  // filter.d:184-185, as `fade out -c` (once: the lanes of --gpus N stay silent)
+            fprintf(stderr, "[W::fade-out] Using the -c flag means the output SAM/BAM will not be sorted (regardless of prior sorting)\n");
+            fprintf(stderr, "[W::fade-out] You also may need to fix mate information with a tool like Picard FixMateInformation\n");
         }
         // --gpus N on a BAM file: one process per GPU, each on its own share of the input (annotate_lanes_main); input that
         // cannot be cut (a pipe, SAM text, a small file) is read by one process that deals batches to the N devices

@@ -142,6 +142,19 @@ int fadehip_sw_stats_batch(fadehip_ctx *ctx, const int32_t scoring[4] /* open, e
                            const uint8_t *q, const int64_t *q_off, const uint8_t *r, const int64_t *r_off,
                            fadehip_sw_stats_result *out);
 
+/* filter.d:15-91 clipRead (`fade out -c`) over n BAM records (block_size first, as in a file), concatenated, rec_off holding
+ * n + 1 offsets.  Record k is hard-clipped on the left by trim_left[k] reference bases when rs[k] has bit 1 (value 2), then
+ * on the right by trim_right[k] reference bases, measured against what the left step left, when it has bit 2 (value 4): the
+ * query bases that go become H ops, pos moves with the left clip, bin follows the new span; a length that is not below the
+ * aligned length resets the record (a zero-filled one that keeps its name and the bases and qualities trimmed so far, no
+ * CIGAR, no aux).  Every other record and all aux bytes pass unchanged.  The clipped records go to out back to back,
+ * out_off receives n + 1 offsets; out must hold them (a record grows by at most eight bytes).  The device function is the one
+ * the file path runs under FADEHIP_BAM_CLIP; there rs and the lengths are the run's own results.  A record whose
+ * block_size, l_read_name, n_cigar_op and l_seq do not fit its bytes: FADEHIP_E_INVALID, with its index in
+ * fadehip_last_error.  Synchronous, on a stream and buffers of its own, as fadehip_sw_stats_batch. */
+int fadehip_clip_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const int64_t *rec_off, const uint8_t *rs,
+                       const int32_t *trim_left, const int32_t *trim_right, uint8_t *out, int64_t out_cap, int64_t *out_off);
+
 /* ------------------------------------------------------ Level 2: annotateTask over a batch -- */
 /* Upload the indexed FASTA once (what IndexedFastaFile + fetchSequence serve, analysis.d:63).
  * seqs[c] holds lengths[c] ASCII residues (any case; upper-cased on device as analysis.d:63 does).
@@ -336,7 +349,11 @@ typedef struct fadehip_bam_config {
     int32_t flags;                /* FADEHIP_BAM_STORED: uncompressed BGZF out (`fade annotate -u`, htslib's level 0);
                                    * FADEHIP_BAM_NO_OUTPUT: back waits for the call's annotated records (on the device) and gives
                                    * their buffer back without making BGZF of them, *out_bytes = 0 — the rate of the record path
-                                   * alone, from BAM record bytes to annotated record bytes (bench.py's value_from_records) */
+                                   * alone, from BAM record bytes to annotated record bytes (bench.py's value_from_records);
+                                   * FADEHIP_BAM_CLIP: records called artifacts leave hard-clipped (`fade annotate -c`: what
+                                   * `fade out -c` would make of the annotated file, in the same pass — by this run's rs and
+                                   * alignments, never by tags read back; the five tags describe the unclipped read).  It
+                                   * combines with the other two flags and holds for front and front_raw alike */
     const char *const *ref_names; /* [n_ref] NUL-terminated */
     uint32_t first_record;        /* payload bytes of the first member passed to front that precede the first record */
     uint32_t tail_trim;           /* payload bytes at the END of the last member (front's last call) that are not this stream's:
@@ -345,6 +362,7 @@ typedef struct fadehip_bam_config {
 #define FADEHIP_BAM_CHUNKS 3
 #define FADEHIP_BAM_STORED 1
 #define FADEHIP_BAM_NO_OUTPUT 2
+#define FADEHIP_BAM_CLIP 4
 int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_bam_stream **out);
 int fadehip_bam_prepare(fadehip_bam_stream *st, size_t call_bytes);
 int fadehip_bam_front(fadehip_bam_stream *st, const void *members, size_t n_bytes, int last);
