@@ -97,8 +97,11 @@ __device__ __forceinline__ uint32_t canon_decode(uint32_t bits, const uint32_t *
     return 0;
 }
 
-// lens[0..n) -> count[], sorted[], tab[0 .. 1 << T).  The whole wave; false when the lengths over-subscribe the code space.
-__device__ __forceinline__ bool build_table(const uint8_t *lens, int n, uint32_t *count, uint16_t *sorted, uint16_t *tab, int T, int lane) {
+// lens[0..n) -> count[], sorted[], tab[0 .. 1 << T).  The whole wave; false when the lengths are not a code zlib's inflate
+// takes: over-subscribed, or incomplete — but for a single code of one bit (lone_ok: literal/length and distance sets) and
+// for no code at all (none_ok: a block without matches may declare no distance code).
+__device__ __forceinline__ bool build_table(const uint8_t *lens, int n, uint32_t *count, uint16_t *sorted, uint16_t *tab, int T, int lane,
+                                            bool lone_ok, bool none_ok) {
     if (lane < 16) count[lane] = 0;
     wave_lds_sync();
     for (int s = lane; s < n; s += 64) {
@@ -115,7 +118,12 @@ __device__ __forceinline__ bool build_table(const uint8_t *lens, int n, uint32_t
         left = (left << 1) - (int)c;
         if (left < 0) left = -(1 << 20);
     }
-    if ((int)uni((uint32_t)left) < 0) return false;  // (uniform: the caller's loops must not look divergent to the compiler)
+    const int room = (int)uni((uint32_t)left);  // (uniform: the caller's loops must not look divergent to the compiler)
+    if (room < 0) return false;
+    if (room > 0) {  // code space left over, in units of 2^-15: half of it with one 1-bit code, all of it with no code
+        const bool lone = room == (1 << 14) && uni(count[1]) == 1u, none = room == (1 << 15);
+        if (!((lone && lone_ok) || (none && none_ok))) return false;
+    }
     for (int base = 0; base < n; base += 64) {
         const int s = base + lane;
         const uint32_t l = s < n ? (uint32_t)lens[s] : 0u;
@@ -239,8 +247,8 @@ __device__ __forceinline__ uint32_t inflate_member(InfWave *w, const uint8_t *sr
             for (int s = lane; s < 288; s += 64) w->lens[s] = (uint8_t)(s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : 8);
             if (lane < 32) w->lens[288 + lane] = 5;
             wave_lds_sync();
-            if (!build_table(w->lens, 288, w->count[0], w->lit_sorted, w->lit_tab, LIT_BITS, lane) ||
-                !build_table(w->lens + 288, 32, w->count[1], w->dist_sorted, w->dist_tab, DIST_BITS, lane)) { err = INF_E_HEADER; break; }
+            if (!build_table(w->lens, 288, w->count[0], w->lit_sorted, w->lit_tab, LIT_BITS, lane, true, false) ||
+                !build_table(w->lens + 288, 32, w->count[1], w->dist_sorted, w->dist_tab, DIST_BITS, lane, true, true)) { err = INF_E_HEADER; break; }
         } else {
             br.refill();
             const uint32_t hlit = br.bits(5) + 257u, hdist = br.bits(5) + 1u, hclen = br.bits(4) + 4u;
@@ -253,7 +261,7 @@ __device__ __forceinline__ uint32_t inflate_member(InfWave *w, const uint8_t *sr
                 if (lane == 0) w->cl_lens[cl_order((int)k)] = (uint8_t)v;
             }
             wave_lds_sync();
-            if (!build_table(w->cl_lens, 19, w->count[2], w->cl_sorted, w->cl_tab, CL_BITS, lane)) { err = INF_E_HEADER; break; }
+            if (!build_table(w->cl_lens, 19, w->count[2], w->cl_sorted, w->cl_tab, CL_BITS, lane, false, false)) { err = INF_E_HEADER; break; }
             const uint32_t total = hlit + hdist;
             uint32_t k = 0, prev = 0;
             while (k < total && !err) {
@@ -284,8 +292,8 @@ __device__ __forceinline__ uint32_t inflate_member(InfWave *w, const uint8_t *sr
             if (err) break;
             wave_lds_sync();
             if (uni((uint32_t)w->lens[256]) == 0u) { err = INF_E_HEADER; break; }
-            if (!build_table(w->lens, (int)hlit, w->count[0], w->lit_sorted, w->lit_tab, LIT_BITS, lane) ||
-                !build_table(w->lens + hlit, (int)hdist, w->count[1], w->dist_sorted, w->dist_tab, DIST_BITS, lane)) { err = INF_E_HEADER; break; }
+            if (!build_table(w->lens, (int)hlit, w->count[0], w->lit_sorted, w->lit_tab, LIT_BITS, lane, true, false) ||
+                !build_table(w->lens + hlit, (int)hdist, w->count[1], w->dist_sorted, w->dist_tab, DIST_BITS, lane, true, true)) { err = INF_E_HEADER; break; }
         }
         // ---- the block's symbols
         bool eob = false;

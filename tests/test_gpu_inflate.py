@@ -2,7 +2,10 @@
 htslib's bgzf_read + zlib's inflate do under `bam.allRecords` (anno.d:44).  The checker is zlib: members made by zlib at
 every level and strategy (stored, fixed and dynamic Huffman blocks, several DEFLATE blocks per member, long codes,
 overlapping matches) must inflate to the bytes zlib was given; members made by the device compressor must come back;
-corrupt members must end in an error (a status, never a hang or an out-of-bounds access)."""
+corrupt members must end in an error (a status, never a hang or an out-of-bounds access).  Streams of shapes zlib's
+deflate never writes (other writers' block splits, header shapes, long distance codes), the streams zlib's inflate refuses
+(incomplete code-length sets among them: refused here as by zlib) and the decision on bytes behind the final block
+(accepted) are tests/test_gpu_inflate_handbuilt.py's, on the corpus of tests/deflate_cases.py."""
 import struct
 import time
 import zlib
