@@ -139,6 +139,11 @@ int fadehip_sw_stats_batch(fadehip_ctx* ctx, const(int)* scoring4 /* open, ext, 
 /// the front when rs[k] & 2, trim_right[k] at the back when rs[k] & 4, or is reset; out_off receives n + 1 offsets into out_
 int fadehip_clip_batch(fadehip_ctx* ctx, int n, const(ubyte)* recs, const(long)* rec_off, const(ubyte)* rs,
         const(int)* trim_left, const(int)* trim_right, ubyte* out_, long out_cap, long* out_off);
+/// remap.d:11-87 (`fade extract`) over n BAM records: side 2k (left, built when rs[k] & 2) and 2k + 1 (right, rs[k] & 4) of record k
+/// become new mapped records on contig art_tid[s] at the 0-based art_pos[s] with the ops cig[cig_off[s] .. cig_off[s + 1]), the read
+/// reverse-complemented, its qualities reversed; out_off receives 2n + 1 offsets into out_ (a side whose bit is clear takes nothing)
+int fadehip_extract_batch(fadehip_ctx* ctx, int n, const(ubyte)* recs, const(long)* rec_off, const(ubyte)* rs,
+        const(int)* art_tid, const(long)* art_pos, const(long)* cig_off, const(uint)* cig, ubyte* out_, long out_cap, long* out_off);
 int fadehip_genome_upload(fadehip_ctx* ctx, int n_contigs, const(long)* lengths, const(ubyte*)* seqs);
 int fadehip_annotate_upload(fadehip_ctx* ctx, int slot, const(fadehip_read_batch)* batch);
 int fadehip_annotate_run(fadehip_ctx* ctx, int slot, int floor_len, int window);
@@ -166,7 +171,7 @@ struct fadehip_bam_config {
     int floor_len;               /// --min-length
     int window;                  /// -w
     int n_ref;                   /// contigs of the BAM header
-    int flags;                   /// 1 (FADEHIP_BAM_STORED): uncompressed BGZF out; 2 (FADEHIP_BAM_NO_OUTPUT): back makes no BGZF (measurement); 4 (FADEHIP_BAM_CLIP): hard-clip the artifact calls
+    int flags;                   /// 1 (FADEHIP_BAM_STORED): uncompressed BGZF out; 2 (FADEHIP_BAM_NO_OUTPUT): back makes no BGZF (measurement); 4 (FADEHIP_BAM_CLIP): hard-clip the artifact calls; 8 (FADEHIP_BAM_EXTRACT): every call also leaves `fade extract`'s records
     const(char*)* ref_names;     /// [n_ref]
     uint first_record;           /// payload bytes of the first member passed that precede the first record
     uint tail_trim;              /// payload bytes at the end of the last member that belong to the next reader
@@ -174,11 +179,14 @@ struct fadehip_bam_config {
 enum FADEHIP_BAM_CHUNKS = 3;
 enum FADEHIP_BAM_STORED = 1;     /// fadehip_bam_config.flags: uncompressed BGZF out (`fade annotate -u`)
 enum FADEHIP_BAM_NO_OUTPUT = 2;  /// ... back releases the annotated records without compressing them (measurement)
+enum FADEHIP_BAM_EXTRACT = 8;    /// ... every call also builds `fade extract`'s records of its artifact calls (`fade annotate --extract`): fadehip_bam_back_extract
 enum FADEHIP_BAM_CLIP = 4;       /// ... artifact calls leave hard-clipped (`fade annotate -c`), by this run's rs and alignments
 int fadehip_bam_open(fadehip_ctx* ctx, const(fadehip_bam_config)* cfg, fadehip_bam_stream** out_);
 int fadehip_bam_prepare(fadehip_bam_stream* st, size_t call_bytes);
 int fadehip_bam_front(fadehip_bam_stream* st, const(void)* members, size_t n_bytes, int last);
 int fadehip_bam_front_raw(fadehip_bam_stream* st, const(void)* payload, size_t n_bytes, int last);
 int fadehip_bam_back(fadehip_bam_stream* st, const(ubyte)** out_, size_t* out_bytes);
+/// FADEHIP_BAM_EXTRACT: the extract records (uncompressed BAM records, pinned memory) of the call the most recent back finished
+int fadehip_bam_back_extract(fadehip_bam_stream* st, const(ubyte)** recs, size_t* n_bytes, long* n_records);
 int fadehip_bam_totals(fadehip_bam_stream* st, long* stats8, long* n_records, long* n_oversize);
 void fadehip_bam_close(fadehip_bam_stream* st);

@@ -152,6 +152,49 @@ class Context:
         out, out_off = self.clip_batch_packed(cat, off, rs, trim_left, trim_right)
         return [out[out_off[k]:out_off[k + 1]].tobytes() for k in range(len(rb))]
 
+    # ---- remap.d:11-87 (`fade extract`): the device function of the file path's extract=True, on records brought here
+    def extract_batch_packed(self, recs, rec_off, rs, art_tid, art_pos, cig_off, cig, out_cap=None):
+        """Side 2k is the left side of record k (built when rs[k] & 2), side 2k + 1 the right (rs[k] & 4); art_tid and art_pos
+        hold 2n entries, cig_off 2n + 1 offsets into cig (BAM-encoded ops).  Returns (bytes as uint8, out_off int64[2n + 1])."""
+        recs = np.ascontiguousarray(recs, dtype=np.uint8)
+        rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
+        rs = np.ascontiguousarray(rs, dtype=np.uint8)
+        tid = np.ascontiguousarray(art_tid, dtype=np.int32)
+        pos = np.ascontiguousarray(art_pos, dtype=np.int64)
+        cig_off = np.ascontiguousarray(cig_off, dtype=np.int64)
+        cig = np.ascontiguousarray(cig, dtype=np.uint32)
+        n = len(rec_off) - 1
+        if not (len(rs) == n and len(tid) == len(pos) == 2 * n and len(cig_off) == 2 * n + 1):
+            raise ValueError("rs holds one entry per record, art_tid and art_pos two, cig_off 2n + 1")
+        if out_cap is None:  # (every side built, with every op of cig: more than any call can take)
+            out_cap = 2 * (len(recs) + 36 * n) + 4 * len(cig) + 8
+        out = np.zeros(int(out_cap), dtype=np.uint8)
+        out_off = np.zeros(2 * n + 1, dtype=np.int64)
+        self._chk(self._L.fadehip_extract_batch(self._h, n, recs.ctypes.data, rec_off.ctypes.data, rs.ctypes.data, tid.ctypes.data,
+                                                pos.ctypes.data, cig_off.ctypes.data, cig.ctypes.data, out.ctypes.data, len(out),
+                                                out_off.ctypes.data))
+        return out[:out_off[2 * n]], out_off
+
+    def extract_batch(self, records, rs, sides):
+        """`fade extract`'s records of BAM records (bytes, block_size first): sides[k] = (left, right), each None or
+        (tid, pos, ops) with pos 0-based and ops BAM-encoded (len << 4 | op); the left one is built when rs[k] & 2, the
+        right one when rs[k] & 4.  Returns the new records as a list of bytes: left before right, in input order."""
+        rb = [bytes(r) for r in records]
+        n = len(rb)
+        off = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum([len(r) for r in rb], out=off[1:])
+        cat = np.frombuffer(b"".join(rb), dtype=np.uint8) if off[-1] else np.zeros(0, np.uint8)
+        tid, pos, cig_off, cig = np.zeros(2 * n, np.int32), np.zeros(2 * n, np.int64), np.zeros(2 * n + 1, np.int64), []
+        for k in range(n):
+            for side in range(2):
+                s = sides[k][side] if sides[k] is not None else None
+                if s is not None:
+                    tid[2 * k + side], pos[2 * k + side] = s[0], s[1]
+                    cig.extend(int(o) for o in s[2])
+                cig_off[2 * k + side + 1] = len(cig)
+        out, out_off = self.extract_batch_packed(cat, off, rs, tid, pos, cig_off, np.array(cig, dtype=np.uint32))
+        return [out[out_off[s]:out_off[s + 1]].tobytes() for s in range(2 * n) if out_off[s + 1] > out_off[s]]
+
     # ---- level 2: annotateTask over a batch (anno.d:55-110)
     def genome_upload(self, names, seqs):
         """seqs: list of bytes / uint8 arrays (raw FASTA residues)."""
@@ -339,11 +382,12 @@ class Context:
         self.bgzf_deflate_submit(lane, data)
         return self.bgzf_deflate_wait(lane)
 
-    def bam_stream(self, ref_names, floor_len=5, window=300, first_record=0, stored=False, tail_trim=0, no_output=False, clip=False):
+    def bam_stream(self, ref_names, floor_len=5, window=300, first_record=0, stored=False, tail_trim=0, no_output=False, clip=False, extract=False):
         """The file path on the device (fadehip_bam_*): BGZF members of a BAM's records in, BGZF members of the annotated
         records out.  ref_names: the BAM header's contigs (the genome must be uploaded).  clip: records called artifacts leave
-        hard-clipped (`fade annotate -c`)."""
-        return BamStream(self, ref_names, floor_len, window, first_record, stored, tail_trim, no_output, clip)
+        hard-clipped (`fade annotate -c`).  extract: every call also builds `fade extract`'s records of its artifact calls
+        (`fade annotate --extract`); BamStream.back_extract() fetches them after each back()."""
+        return BamStream(self, ref_names, floor_len, window, first_record, stored, tail_trim, no_output, clip, extract)
 
     def bgzf_inflate(self, members, out_cap=None):
         """Whole BGZF members (bytes / uint8 array) -> their payloads, inflated on the device (CRC32 and ISIZE checked)."""
@@ -477,11 +521,11 @@ def format_tags(batch, contig_names, rs, aln):
 
 
 class BamStream:
-    def __init__(self, ctx, ref_names, floor_len, window, first_record, stored=False, tail_trim=0, no_output=False, clip=False):
+    def __init__(self, ctx, ref_names, floor_len, window, first_record, stored=False, tail_trim=0, no_output=False, clip=False, extract=False):
         self._ctx, self._L = ctx, ctx._L
         names = [n.encode() if isinstance(n, str) else bytes(n) for n in ref_names]
         arr = (C.c_char_p * max(len(names), 1))(*names)
-        cfg = _lib.BamConfig(floor_len, window, len(names), (_lib.BAM_STORED if stored else 0) | (_lib.BAM_NO_OUTPUT if no_output else 0) | (_lib.BAM_CLIP if clip else 0), arr, first_record, tail_trim)
+        cfg = _lib.BamConfig(floor_len, window, len(names), (_lib.BAM_STORED if stored else 0) | (_lib.BAM_NO_OUTPUT if no_output else 0) | (_lib.BAM_CLIP if clip else 0) | (_lib.BAM_EXTRACT if extract else 0), arr, first_record, tail_trim)
         h = C.c_void_p()
         ctx._chk(self._L.fadehip_bam_open(ctx._h, C.byref(cfg), C.byref(h)))
         self._h = h
@@ -507,6 +551,12 @@ class BamStream:
         p, n = C.c_void_p(), C.c_size_t(0)
         self._ctx._chk(self._L.fadehip_bam_back(self._h, C.byref(p), C.byref(n)))
         return C.string_at(p, n.value) if n.value else b""
+
+    def back_extract(self):
+        """The extract records of the call the last back() finished: (uncompressed BAM records as bytes, their number)."""
+        p, n, nr = C.c_void_p(), C.c_size_t(0), C.c_int64(0)
+        self._ctx._chk(self._L.fadehip_bam_back_extract(self._h, C.byref(p), C.byref(n), C.byref(nr)))
+        return (C.string_at(p, n.value) if n.value else b""), int(nr.value)
 
     def totals(self):
         st, nr, no = (C.c_int64 * 8)(), C.c_int64(0), C.c_int64(0)

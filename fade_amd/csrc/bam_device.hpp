@@ -1038,5 +1038,189 @@ __global__ __launch_bounds__(256) void clip_batch_write_kernel(ClipBatchArgs a) 
     if (c.mode == 1u) copy16(dst + c.pre, r.p + r.aux_off, r.end - r.aux_off, sl);
 }
 
+// ============================================================================================ extract
+// `fade annotate --extract` (FADEHIP_BAM_EXTRACT) / fadehip_extract_batch: remap.d:11-87 (`fade extract`) in the pass that
+// writes the records.  One new mapped record per artifact side, left (rs & 2) before right (rs & 4), built from the read as
+// it came in (never from the clipped one) and from THIS run's alignment, not from an am tag read back: refID and position
+// of the alignment, its padded CIGAR, the read reverse-complemented, its qualities reversed, flag 0x10 when the read has it
+// clear, everything else what a zero-filled bam1_t holds (mapq 0, mate refID 0, mate pos 0, tlen 0), no aux area.
+// These kernels are of their own: the kernels of a run without the flag are not touched and share no body with them.
+__device__ __forceinline__ uint32_t extract_size(const RecHdr &r, uint32_t nops) {
+    const uint32_t lq = r.lseq > 0 ? (uint32_t)r.lseq : 0u;
+    return 36u + r.lname + 4u * nops + (lq + 1u) / 2u + lq;
+}
+
+// One extract record by sixteen lanes.  The bases eight at a time: bit reversal of a dword of 4-bit codes (v_bfrev_b32)
+// reverses the order of its eight codes AND complements each (util.d:18-20's table is bit reversal of the code), so the
+// dword read from the mirrored end is the output dword; an odd l_seq leaves the input's pad nibble in front of the
+// reversed stream, which is shifted out with the nibble shift clip_write_head uses, and the output's own pad nibble is
+// zeroed.  The qualities are byte-swapped dwords from the mirrored end.
+__device__ __forceinline__ void extract_write(const RecHdr &r, int32_t tid, int64_t pos, const uint32_t *ops, uint32_t nops, uint8_t *dst, uint32_t sl) {
+    const uint32_t lq = r.lseq > 0 ? (uint32_t)r.lseq : 0u, nb = (lq + 1u) / 2u;
+    if (sl < 9u) {
+        uint32_t v = 0u;  // (mate refID, mate pos, tlen)
+        if (sl == 0u) v = 32u + r.lname + 4u * nops + nb + lq;
+        if (sl == 1u) v = (uint32_t)tid;
+        if (sl == 2u) v = (uint32_t)(int32_t)pos;
+        if (sl == 3u) {  // l_read_name, mapq 0, reg2bin over the new CIGAR's span
+            int64_t reflen = 0;
+            for (uint32_t k = 0; k < nops; k++)
+                if (FADEHIP_OP_CONSUMES_REF(ops[k] & 15u)) reflen += ops[k] >> 4;
+            const int64_t beg = pos < 0 ? 0 : pos, end = beg + (reflen > 0 ? reflen : 1) - 1;
+            const uint32_t bin = beg >> 14 == end >> 14 ? (uint32_t)(4681 + (beg >> 14))
+                               : beg >> 17 == end >> 17 ? (uint32_t)(585 + (beg >> 17))
+                               : beg >> 20 == end >> 20 ? (uint32_t)(73 + (beg >> 20))
+                               : beg >> 23 == end >> 23 ? (uint32_t)(9 + (beg >> 23))
+                               : beg >> 26 == end >> 26 ? (uint32_t)(1 + (beg >> 26)) : 0u;
+            v = r.lname | (bin << 16);
+        }
+        if (sl == 4u) v = (nops & 0xffffu) | ((r.flag & 0x10u) ? 0u : 0x100000u);
+        if (sl == 5u) v = lq;
+        *reinterpret_cast<u32u *>(dst + 4u * sl) = v;
+    }
+    copy16(dst + 36u, r.p + 36u, r.lname, sl);
+    uint8_t *oc = dst + 36u + r.lname;
+    for (uint32_t j = sl; j < nops; j += 16u) *reinterpret_cast<u32u *>(oc + 4u * j) = ops[j];
+    uint8_t *os = oc + 4u * nops;
+    const uint8_t *s = r.p + r.seq_off;
+    const bool odd = lq & 1u;
+    {
+        // output bytes [q, q + 4) mirror input bytes [nb - 4 - q, nb - q); with an odd l_seq also the byte in front of them
+        // (for the last output dword that is the byte in front of the bases — a byte of the record, name or CIGAR — and
+        // what it brings lands in the pad nibble, which is cleared)
+        const uint32_t whole = nb & ~3u;
+        for (uint32_t q = 4u * sl; q < whole; q += 64u) {
+            const uint8_t *m = s + (nb - 4u - q);
+            uint32_t v = __builtin_bitreverse32(ld32(m));
+            if (odd) {
+                const uint64_t w = (uint64_t)v | ((uint64_t)(__builtin_bitreverse32(m[-1]) >> 24) << 32);
+                v = (uint32_t)((w & 0x0f0f0f0full) << 4) | (uint32_t)((w >> 12) & 0x0f0f0f0full);
+                if (q + 4u == nb) v &= 0xf0ffffffu;
+            }
+            *reinterpret_cast<u32u *>(os + q) = v;
+        }
+        if (sl < nb - whole) {
+            const uint32_t k = whole + sl;
+            const uint8_t *m = s + (nb - 1u - k);
+            uint32_t b = __builtin_bitreverse32(m[0]) >> 24;
+            if (odd) {
+                b = ((b << 4) | (__builtin_bitreverse32(m[-1]) >> 28)) & 0xffu;
+                if (k + 1u == nb) b &= 0xf0u;
+            }
+            os[k] = (uint8_t)b;
+        }
+    }
+    uint8_t *oq = os + nb;
+    const uint8_t *ql = r.p + r.qual_off;
+    const uint32_t whole = lq & ~3u;
+    for (uint32_t q = 4u * sl; q < whole; q += 64u) *reinterpret_cast<u32u *>(oq + q) = __builtin_bswap32(ld32(ql + (lq - 4u - q)));
+    if (sl < lq - whole) oq[whole + sl] = ql[lq - 1u - (whole + sl)];
+}
+
+// The file path.  TagArgs as the tag kernels have them, with out_size / blk_sums / blk_base / counts / o of the extract
+// stream's own (counts: a second ChunkCounts whose out_bytes the scan fills and whose n_records counts extract records).
+// Thread per record of a TAG_BLOCK block, so that the sizes feed bam_tag_scan_kernel as the tag sizes do and the records
+// come out in input order; a record that is no artifact call costs its thread two index words and nothing of the record.
+__global__ __launch_bounds__(TAG_BLOCK) void bam_extract_size_kernel(TagArgs a) {
+    __shared__ uint64_t red[TAG_BLOCK / 64];
+    const uint32_t r1 = min(a.r1_cap, a.counts_in->n_records);
+    const uint32_t i = a.r0 + blockIdx.x * TAG_BLOCK + threadIdx.x;
+    uint64_t sz = 0;  // bytes, and the number of records above bit 40
+    if (i < r1) {
+        uint8_t rs;
+        const fadehip_aln *al = aln_of(a, a.sent_of[i - a.r0], &rs);
+        if (al && (rs & 6u) && !(a.info[i - a.r0] & INFO_BAD)) {
+            const RecHdr r = rec_header(a.u + a.rec_off[i]);
+            const uint32_t n = (rs & 6u) == 6u ? 2u : 1u;
+            sz = (uint64_t)n * extract_size(r, (uint32_t)min(max(al->sw.n_ops, 0), FADEHIP_MAX_OPS)) | ((uint64_t)n << 40);
+        }
+        a.out_size[i - a.r0] = (uint32_t)sz;
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) sz += (uint64_t)__shfl_xor((long long)sz, m, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sz;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint64_t t = 0;
+        for (int w = 0; w < TAG_BLOCK / 64; w++) t += red[w];
+        a.blk_sums[blockIdx.x] = t & ((1ull << 40) - 1ull);
+        if (t >> 40) atomicAdd(&a.counts->n_records, (uint32_t)(t >> 40));
+    }
+}
+
+// A block per TAG_BLOCK records (whose base applies): the artifact calls among them — a few per cent — are gathered into a
+// list by one scan of (bytes, is-a-call), and the block's sixteen groups of sixteen lanes take them side by side, as the
+// rewrite kernel takes its records: a record is a chain of dependent loads, and several chains at once hide them.
+__global__ __launch_bounds__(TAG_BLOCK) void bam_extract_write_kernel(TagArgs a) {
+    __shared__ uint64_t wave_sum[TAG_BLOCK / 64 + 1];
+    __shared__ uint64_t l_off[TAG_BLOCK];
+    __shared__ uint32_t l_rec[TAG_BLOCK];
+    const uint32_t r1 = min(a.r1_cap, a.counts_in->n_records);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t i0 = a.r0 + blockIdx.x * TAG_BLOCK, i = i0 + threadIdx.x;
+    const uint64_t sz = i < r1 ? (uint64_t)a.out_size[i - a.r0] : 0ull;
+    const uint64_t v = sz | (sz ? 1ull << 40 : 0ull);
+    uint64_t inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t o = (uint64_t)__shfl_up((long long)inc, d, 64);
+        if (lane >= d) inc += o;
+    }
+    if (lane == 63) wave_sum[wave + 1] = inc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        wave_sum[0] = 0;
+        for (int w = 1; w <= TAG_BLOCK / 64; w++) wave_sum[w] += wave_sum[w - 1];
+    }
+    __syncthreads();
+    if (sz) {
+        const uint64_t ex = wave_sum[wave] + inc - v;
+        l_rec[ex >> 40] = threadIdx.x;
+        l_off[ex >> 40] = a.out_base + a.blk_base[blockIdx.x] + (ex & ((1ull << 40) - 1ull));
+    }
+    __syncthreads();
+    const uint32_t cnt = (uint32_t)(wave_sum[TAG_BLOCK / 64] >> 40);
+    const uint32_t sl = threadIdx.x & 15u;
+    for (uint32_t g = threadIdx.x >> 4; g < cnt; g += TAG_BLOCK / 16) {
+        const uint32_t ij = i0 + l_rec[g];
+        const RecHdr r = rec_header(a.u + a.rec_off[ij]);
+        uint8_t rs;
+        const fadehip_aln *al = aln_of(a, a.sent_of[ij - a.r0], &rs);  // (never null: the size pass found the call)
+        const uint32_t nops = (uint32_t)min(max(al->sw.n_ops, 0), FADEHIP_MAX_OPS);
+        const int64_t pos = al->win_start + al->sw.beg_ref;  // what am holds
+        uint8_t *dst = a.o + l_off[g];
+        extract_write(r, r.tid, pos, al->sw.ops, nops, dst, sl);
+        if ((rs & 6u) == 6u) extract_write(r, r.tid, pos, al->sw.ops, nops, dst + extract_size(r, nops), sl);  // (am names the one alignment on both sides)
+    }
+}
+
+// ---- fadehip_extract_batch: extract_write over records the caller brings; side 2k is the left one of record k, 2k + 1 the right
+struct ExtractBatchArgs {
+    const uint8_t *in;
+    const uint64_t *in_off;    // [n + 1]
+    const uint8_t *rs;         // [n]
+    const int32_t *tid;        // [2n]
+    const int64_t *pos;        // [2n]
+    const uint64_t *cig_off;   // [2n + 1]
+    const uint32_t *cig;
+    uint32_t n;
+    uint32_t *out_size;        // [2n]  (size kernel; 0: that side's bit is clear)
+    const uint64_t *out_off;   // [2n]  (write kernel)
+    uint8_t *out;
+};
+__global__ __launch_bounds__(256) void extract_batch_size_kernel(ExtractBatchArgs a) {
+    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+    if (s >= 2u * a.n) return;
+    uint32_t sz = 0;
+    if (a.rs[s >> 1] & (2u << (s & 1u))) sz = extract_size(rec_header(a.in + a.in_off[s >> 1]), (uint32_t)(a.cig_off[s + 1u] - a.cig_off[s]));
+    a.out_size[s] = sz;
+}
+__global__ __launch_bounds__(256) void extract_batch_write_kernel(ExtractBatchArgs a) {
+    const uint32_t s = blockIdx.x * 16u + (threadIdx.x >> 4), sl = threadIdx.x & 15u;
+    if (s >= 2u * a.n || !a.out_size[s]) return;
+    const RecHdr r = rec_header(a.in + a.in_off[s >> 1]);
+    extract_write(r, a.tid[s], a.pos[s], a.cig + a.cig_off[s], (uint32_t)(a.cig_off[s + 1u] - a.cig_off[s]), a.out + a.out_off[s], sl);
+}
+
 }  // namespace bam
 }  // namespace fadehip

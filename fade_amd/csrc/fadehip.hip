@@ -196,6 +196,10 @@ struct fadehip_ctx {
     hipStream_t clip_stream = nullptr;
     DevBuf cl_in, cl_meta, cl_size, cl_out;
     std::mutex clip_mu;
+    // fadehip_extract_batch: likewise
+    hipStream_t extract_stream = nullptr;
+    DevBuf ex_in, ex_meta, ex_size, ex_out;
+    std::mutex extract_mu;
     int n_contigs = 0;
     std::vector<int64_t> h_contig_len;
     std::vector<uint64_t> h_contig_base;
@@ -1461,6 +1465,8 @@ void fadehip_destroy(fadehip_ctx *ctx) {
     if (ctx->stats_stream) (void)hipStreamDestroy(ctx->stats_stream);
     for (DevBuf *b : {&ctx->cl_in, &ctx->cl_meta, &ctx->cl_size, &ctx->cl_out}) release(*b);
     if (ctx->clip_stream) (void)hipStreamDestroy(ctx->clip_stream);
+    for (DevBuf *b : {&ctx->ex_in, &ctx->ex_meta, &ctx->ex_size, &ctx->ex_out}) release(*b);
+    if (ctx->extract_stream) (void)hipStreamDestroy(ctx->extract_stream);
     release(ctx->contig_len);
     release(ctx->contig_base);
     if (g_err_ctx == ctx) g_err_ctx = nullptr;
@@ -1825,6 +1831,103 @@ int fadehip_clip_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const i
     HIPCHK(ctx, hipMemcpyAsync(meta + m_out, off.data(), m_out, hipMemcpyHostToDevice, st));
     a.out = (uint8_t *)ctx->cl_out.p;
     hipLaunchKernelGGL(bam::clip_batch_write_kernel, dim3(((unsigned)n + 15u) / 16u), dim3(256), 0, st, a);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(out, a.out, out_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    return 0;
+}
+
+// remap.d:11-87 over records the caller brings: bam_device.hpp's extract_write, the function of the file path under
+// FADEHIP_BAM_EXTRACT, with the caller's rs, contigs, positions and CIGARs in place of a run's results.
+int fadehip_extract_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const int64_t *rec_off, const uint8_t *rs,
+                          const int32_t *art_tid, const int64_t *art_pos, const int64_t *cig_off, const uint32_t *cig,
+                          uint8_t *out, int64_t out_cap, int64_t *out_off) {
+    if (!ctx) return set_err(nullptr, FADEHIP_E_INVALID, "ctx is NULL");
+    if (n < 0 || n > (1 << 30) || !rec_off || !out_off || (n > 0 && (!recs || !rs || !art_tid || !art_pos || !cig_off)) || out_cap < 0 || (out_cap > 0 && !out))
+        return set_err(ctx, FADEHIP_E_INVALID, "NULL argument");
+    if (rec_off[0] < 0) return set_err(ctx, FADEHIP_E_INVALID, "offsets must be non-negative and non-decreasing (record 0)");
+    out_off[0] = 0;
+    if (n == 0) return 0;
+    // what the kernels dereference through is checked here: block_size against the offsets, the fields against block_size,
+    // the CIGAR offsets of the sides that are built
+    int64_t cig_end = 0;
+    for (int32_t k = 0; k < n; k++) {
+        const int64_t len = rec_off[k + 1] - rec_off[k];
+        if (len < 0) return set_err(ctx, FADEHIP_E_INVALID, "offsets must be non-negative and non-decreasing (record %d)", k);
+        const uint8_t *p = recs + rec_off[k];
+        uint32_t bs = 0, ncig = 0;
+        int32_t lseq = 0;
+        if (len >= 36) {
+            memcpy(&bs, p, 4);
+            memcpy(&lseq, p + 20, 4);
+            ncig = (uint32_t)p[16] | ((uint32_t)p[17] << 8);
+        }
+        if (len < 36 || len > ((int64_t)1 << 29) || (int64_t)bs + 4 != len || lseq < 0 || p[12] == 0 ||
+            36ull + p[12] + 4ull * ncig + ((uint64_t)lseq + 1) / 2 + (uint64_t)lseq > (uint64_t)len)
+            return set_err(ctx, FADEHIP_E_INVALID, "record %d is malformed (block_size, l_read_name, n_cigar_op and l_seq must fit its %lld bytes)", k, (long long)len);
+        for (int side = 0; side < 2; side++) {
+            if (!(rs[k] & (2u << side))) continue;
+            const int64_t c0 = cig_off[2 * (size_t)k + side], c1 = cig_off[2 * (size_t)k + side + 1];
+            if (c0 < 0 || c1 < c0) return set_err(ctx, FADEHIP_E_INVALID, "record %d: the CIGAR offsets of its %s side must be non-negative and non-decreasing", k, side ? "right" : "left");
+            if (c1 - c0 > 65535) return set_err(ctx, FADEHIP_E_INVALID, "record %d: a BAM record holds at most 65535 CIGAR ops", k);
+            if (c1 > c0 && !cig) return set_err(ctx, FADEHIP_E_INVALID, "NULL argument");
+            cig_end = std::max(cig_end, c1);
+        }
+    }
+    const size_t in_bytes = (size_t)(rec_off[n] - rec_off[0]), ns = 2 * (size_t)n;
+    std::vector<uint64_t> off((size_t)n + 1), soff(ns + 1);
+    for (int32_t k = 0; k <= n; k++) off[(size_t)k] = (uint64_t)(rec_off[k] - rec_off[0]);
+    for (size_t q = 0; q <= ns; q++) soff[q] = (uint64_t)cig_off[q];  // (of a side that is not built: never read on the device)
+    std::lock_guard<std::mutex> lk(ctx->extract_mu);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (!ctx->extract_stream) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->extract_stream, hipStreamNonBlocking));
+    hipStream_t st = ctx->extract_stream;
+    // ex_meta: in_off [n + 1] u64 | cig_off [2n + 1] u64 | out_off [2n + 1] u64 | pos [2n] i64 | tid [2n] i32 | cig u32 | rs [n] u8
+    const size_t m_coff = 8 * ((size_t)n + 1), m_out = m_coff + 8 * (ns + 1), m_pos = m_out + 8 * (ns + 1), m_tid = m_pos + 8 * ns,
+                 m_cig = m_tid + 4 * ns, m_rs = m_cig + 4 * (size_t)cig_end;
+    int rc;
+    if ((rc = reserve(ctx, ctx->ex_in, in_bytes + 8)) || (rc = reserve(ctx, ctx->ex_meta, m_rs + (size_t)n + 8)) || (rc = reserve(ctx, ctx->ex_size, 4 * ns)))
+        return rc;
+    uint8_t *meta = (uint8_t *)ctx->ex_meta.p;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->ex_in.p, recs + rec_off[0], in_bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(meta, off.data(), m_coff, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(meta + m_coff, soff.data(), 8 * (ns + 1), hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(meta + m_pos, art_pos, 8 * ns, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(meta + m_tid, art_tid, 4 * ns, hipMemcpyHostToDevice, st));
+    if (cig_end) HIPCHK(ctx, hipMemcpyAsync(meta + m_cig, cig, 4 * (size_t)cig_end, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(meta + m_rs, rs, (size_t)n, hipMemcpyHostToDevice, st));
+    bam::ExtractBatchArgs a;
+    a.in = (const uint8_t *)ctx->ex_in.p;
+    a.in_off = (const uint64_t *)meta;
+    a.rs = meta + m_rs;
+    a.tid = (const int32_t *)(meta + m_tid);
+    a.pos = (const int64_t *)(meta + m_pos);
+    a.cig_off = (const uint64_t *)(meta + m_coff);
+    a.cig = (const uint32_t *)(meta + m_cig);
+    a.n = (uint32_t)n;
+    a.out_size = (uint32_t *)ctx->ex_size.p;
+    a.out_off = (const uint64_t *)(meta + m_out);
+    a.out = nullptr;
+    hipLaunchKernelGGL(bam::extract_batch_size_kernel, dim3(((unsigned)ns + 255u) / 256u), dim3(256), 0, st, a);
+    HIPCHK(ctx, hipGetLastError());
+    std::vector<uint32_t> sizes(ns);
+    HIPCHK(ctx, hipMemcpyAsync(sizes.data(), a.out_size, 4 * ns, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    uint64_t run = 0;
+    for (size_t q = 0; q < ns; q++) {
+        soff[q] = run;
+        run += sizes[q];
+    }
+    soff[ns] = run;
+    const size_t out_bytes = (size_t)run;
+    if ((int64_t)out_bytes > out_cap)
+        return set_err(ctx, FADEHIP_E_INVALID, "the extract records take %lld bytes, out holds %lld", (long long)out_bytes, (long long)out_cap);
+    for (size_t q = 0; q <= ns; q++) out_off[q] = (int64_t)soff[q];
+    if (!out_bytes) return 0;
+    if ((rc = reserve(ctx, ctx->ex_out, out_bytes + 8))) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(meta + m_out, soff.data(), 8 * (ns + 1), hipMemcpyHostToDevice, st));
+    a.out = (uint8_t *)ctx->ex_out.p;
+    hipLaunchKernelGGL(bam::extract_batch_write_kernel, dim3(((unsigned)ns + 15u) / 16u), dim3(256), 0, st, a);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(out, a.out, out_bytes, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
@@ -2367,11 +2470,17 @@ struct fadehip_bam_stream {
     bool stored = false;  // uncompressed BGZF out
     bool clip = false;    // FADEHIP_BAM_CLIP: artifact calls leave hard-clipped (the <true> kernels of bam_device.hpp)
     bool no_output = false;  // FADEHIP_BAM_NO_OUTPUT: back gives the call's device bytes back without making BGZF of them
+    bool extract = false;    // FADEHIP_BAM_EXTRACT: every call also leaves `fade extract`'s records of its artifact calls
     DevBuf names_text, names_off;
     struct Out {
         DevBuf o;
         size_t bytes = 0;
         hipEvent_t ready = nullptr;
+        // extract: the call's extract records on the device, their bytes and number, and the event behind their copy to the host
+        DevBuf x;
+        size_t xbytes = 0;
+        int64_t xrecs = 0;
+        hipEvent_t xready = nullptr;
         int state = 0;  // 0 free, 1 its call's kernels are enqueued up to the tag sizes (to be finished), 2 finished: waiting for back
     } ring[FADEHIP_BAM_CHUNKS];
     // The front half, two calls in flight.  Call k lives in set k & 1 and on the ctx's slot k & 1 (a stream each):
@@ -2387,6 +2496,8 @@ struct fadehip_bam_stream {
         DevBuf comp, blocks, status, ticket;  // members to inflate on the device
         DevBuf u;                             // the call's inflated bytes, the previous call's cut-off record in front
         DevBuf seg, slots, rec_off, info, sent_of, art_of, out_size, blk32, blk64, counts;
+        DevBuf ex_size, ex_blk;               // extract: bytes per record, block sums and bases (the tag arrays' counterparts)
+        bam::TagArgs xa;                      // extract: ta with the extract stream's sizes, sums, counts and output
         PinBuf h_blocks, h_counts;
         uint64_t k = ~0ull;
         uint32_t n_rec = 0, n_sent = 0, ntb = 0;
@@ -2400,6 +2511,15 @@ struct fadehip_bam_stream {
     uint64_t k_front = 0, k_back = 0;
     uint64_t k_sub = 0;                     // calls handed to the compressor (back may run one ahead of the call it returns)
     PinBuf outbuf[FADEHIP_BAM_CHUNKS];      // the members of call k, packed by the kernel itself: pinned, k % FADEHIP_BAM_CHUNKS
+    // extract: the extract records of call k, pinned, k % (FADEHIP_BAM_CHUNKS + 1) — one more than the ring, because the copy is
+    // enqueued when the call is finished, which front may do one back call before the compressor of that ring place starts
+    PinBuf xbuf[FADEHIP_BAM_CHUNKS + 1];
+    const uint8_t *last_x = nullptr;        // fadehip_bam_back_extract: what the most recent back finished
+    size_t last_xbytes = 0;
+    int64_t last_xrecs = 0;
+    bool have_back = false;
+    // the counts of a call as they cross to the host: the call's ChunkCounts and, with extract, the extract stream's behind it
+    size_t counts_bytes() const { return sizeof(bam::ChunkCounts) * (extract ? 2u : 1u); }
     std::mutex mu;
     std::condition_variable cv;
     int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -2474,6 +2594,29 @@ int bam_finish_call(fadehip_bam_stream *st, uint64_t k) {
     }
     if (!out->ready) HIPCHK(ctx, hipEventCreateWithFlags(&out->ready, hipEventDisableTiming | (ctx->blocking_sync ? hipEventBlockingSync : 0)));
     HIPCHK(ctx, hipEventRecord(out->ready, q));
+    if (st->extract) {
+        // behind the event the compressor waits for: the extract records of the call's artifact calls, from the untouched
+        // input records, and their copy into the pinned buffer back_extract hands out (the total came with the tag sizes)
+        out->xbytes = 0;
+        out->xrecs = 0;
+        if (S.n_rec) {
+            const bam::ChunkCounts *xc = (const bam::ChunkCounts *)S.h_counts.p + 1;
+            const uint64_t xb = xc->out_bytes;
+            if (xb > ((uint64_t)1 << 31)) return set_err(ctx, FADEHIP_E_UNSUPPORTED, "bam stream: %llu extract bytes in one call (at most 2^31)", (unsigned long long)xb);
+            if (xb) {
+                PinBuf &xh = st->xbuf[k % (FADEHIP_BAM_CHUNKS + 1)];
+                if ((rc = reserve_roomy(ctx, out->x, (size_t)xb + 256)) || (rc = reserve_pinned(ctx, xh, (size_t)xb + (size_t)xb / 4 + 256))) return rc;
+                S.xa.o = (uint8_t *)out->x.p;
+                hipLaunchKernelGGL(bam::bam_extract_write_kernel, dim3(S.ntb), dim3(bam::TAG_BLOCK), 0, q, S.xa);
+                HIPCHK(ctx, hipGetLastError());
+                HIPCHK(ctx, hipMemcpyAsync(xh.p, out->x.p, (size_t)xb, hipMemcpyDeviceToHost, q));
+                out->xbytes = (size_t)xb;
+                out->xrecs = (int64_t)xc->n_records;
+            }
+        }
+        if (!out->xready) HIPCHK(ctx, hipEventCreateWithFlags(&out->xready, hipEventDisableTiming | (ctx->blocking_sync ? hipEventBlockingSync : 0)));
+        HIPCHK(ctx, hipEventRecord(out->xready, q));
+    }
     S.pending = false;
     st->t_tags += now_s() - t0;
     {
@@ -2559,12 +2702,12 @@ int bam_front_impl(fadehip_bam_stream *st, const uint8_t *members, size_t n_byte
     const uint32_t n_seg = (u_len + bam::SEG - 1) / bam::SEG;
     const uint32_t rec_cap = u_len / 36u + 2u;
     if ((rc = reserve_roomy(ctx, S.seg, 16 * (size_t)std::max(n_seg, 1u))) || (rc = reserve_roomy(ctx, S.slots, 4 * (size_t)bam::SEG_SLOTS * std::max(n_seg, 1u))) ||
-        (rc = reserve_roomy(ctx, S.rec_off, 4 * (size_t)rec_cap)) || (rc = reserve_roomy(ctx, S.counts, sizeof(bam::ChunkCounts))) ||
-        (rc = reserve_pinned(ctx, S.h_counts, sizeof(bam::ChunkCounts) + 16)))
+        (rc = reserve_roomy(ctx, S.rec_off, 4 * (size_t)rec_cap)) || (rc = reserve_roomy(ctx, S.counts, st->counts_bytes())) ||
+        (rc = reserve_pinned(ctx, S.h_counts, st->counts_bytes() + 16)))
         return rc;
     bam::ChunkCounts *d_counts = (bam::ChunkCounts *)S.counts.p;
     bam::ChunkCounts *h_counts = (bam::ChunkCounts *)S.h_counts.p;
-    HIPCHK(ctx, hipMemsetAsync(d_counts, 0, sizeof(bam::ChunkCounts), q));
+    HIPCHK(ctx, hipMemsetAsync(d_counts, 0, st->counts_bytes(), q));
     HIPCHK(ctx, hipMemsetAsync(&d_counts->l_seq_min, 0xff, 4, q));
     bam::FrameArgs fa;
     fa.u = u;
@@ -2617,7 +2760,7 @@ int bam_front_impl(fadehip_bam_stream *st, const uint8_t *members, size_t n_byte
     HIPCHK(ctx, hipGetLastError());
     if (fine) { tr.mark("  pack scan enqueued"); (void)hipStreamSynchronize(q); tr.mark("  waited for"); }
     HIPCHK(ctx, hipMemcpyAsync(h_counts, d_counts, sizeof(bam::ChunkCounts), hipMemcpyDeviceToHost, q));
-    uint32_t *h_tick = (uint32_t *)(S.h_counts.p + sizeof(bam::ChunkCounts));
+    uint32_t *h_tick = (uint32_t *)(S.h_counts.p + st->counts_bytes());
     h_tick[0] = h_tick[1] = 0;
     if (nb) HIPCHK(ctx, hipMemcpyAsync(h_tick, S.ticket.p, 8, hipMemcpyDeviceToHost, q));
     const double t1 = now_s();
@@ -2750,7 +2893,23 @@ int bam_front_impl(fadehip_bam_stream *st, const uint8_t *members, size_t n_byte
         HIPCHK(ctx, hipGetLastError());
         hipLaunchKernelGGL(bam::bam_tag_scan_kernel, dim3(1), dim3(1024), 0, q, ta, ntb);
         HIPCHK(ctx, hipGetLastError());
-        HIPCHK(ctx, hipMemcpyAsync(h_counts, d_counts, sizeof(bam::ChunkCounts), hipMemcpyDeviceToHost, q));
+        if (st->extract) {
+            // the extract records' sizes into the same scan, their total into the ChunkCounts behind the call's own: it crosses
+            // to the host in the copy below, which back reads anyway
+            if ((rc = reserve_roomy(ctx, S.ex_size, 4 * (size_t)n_rec)) || (rc = reserve_roomy(ctx, S.ex_blk, 16 * (size_t)ntb))) return rc;
+            bam::TagArgs &xa = S.xa;
+            xa = ta;
+            xa.out_size = (uint32_t *)S.ex_size.p;
+            xa.blk_sums = (uint64_t *)S.ex_blk.p;
+            xa.blk_base = xa.blk_sums + ntb;
+            xa.counts = d_counts + 1;
+            xa.o = nullptr;
+            hipLaunchKernelGGL(bam::bam_extract_size_kernel, dim3(ntb), dim3(bam::TAG_BLOCK), 0, q, xa);
+            HIPCHK(ctx, hipGetLastError());
+            hipLaunchKernelGGL(bam::bam_tag_scan_kernel, dim3(1), dim3(1024), 0, q, xa, ntb);
+            HIPCHK(ctx, hipGetLastError());
+        }
+        HIPCHK(ctx, hipMemcpyAsync(h_counts, d_counts, st->counts_bytes(), hipMemcpyDeviceToHost, q));
         S.n_sent = n_sent;
         S.ntb = ntb;
     }
@@ -2773,7 +2932,7 @@ int bam_front_impl(fadehip_bam_stream *st, const uint8_t *members, size_t n_byte
 
 int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_bam_stream **out) {
     if (!ctx) return set_err(nullptr, FADEHIP_E_INVALID, "ctx is NULL");
-    if (!cfg || !out || cfg->n_ref < 0 || (cfg->n_ref && !cfg->ref_names) || cfg->window < 0 || (cfg->flags & ~(FADEHIP_BAM_STORED | FADEHIP_BAM_NO_OUTPUT | FADEHIP_BAM_CLIP)))
+    if (!cfg || !out || cfg->n_ref < 0 || (cfg->n_ref && !cfg->ref_names) || cfg->window < 0 || (cfg->flags & ~(FADEHIP_BAM_STORED | FADEHIP_BAM_NO_OUTPUT | FADEHIP_BAM_CLIP | FADEHIP_BAM_EXTRACT)))
         return set_err(ctx, FADEHIP_E_INVALID, "bam stream: bad configuration");
     if (!ctx->two_pass) return set_err(ctx, FADEHIP_E_UNSUPPORTED, "bam stream: needs the default kernels (FADEHIP_KERNEL unset)");
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -2788,6 +2947,7 @@ int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_ba
     st->stored = (cfg->flags & FADEHIP_BAM_STORED) != 0;
     st->no_output = (cfg->flags & FADEHIP_BAM_NO_OUTPUT) != 0;
     st->clip = (cfg->flags & FADEHIP_BAM_CLIP) != 0;
+    st->extract = (cfg->flags & FADEHIP_BAM_EXTRACT) != 0;
     std::string text;
     std::vector<uint32_t> off((size_t)cfg->n_ref + 1, 0);
     for (int k = 0; k < cfg->n_ref; k++) {
@@ -2855,8 +3015,8 @@ int fadehip_bam_prepare(fadehip_bam_stream *st, size_t call_bytes) {
     const size_t carry_room = 65536;
     for (int q = 0; q < 2 && !rc; q++) {
         fadehip_bam_stream::Set &S = st->set[q];
-        if (!(rc = reserve_roomy(ctx, S.u, call_bytes + carry_room + 256))) rc = reserve_pinned(ctx, S.h_counts, sizeof(bam::ChunkCounts) + 16);
-        if (!rc) rc = reserve_roomy(ctx, S.counts, sizeof(bam::ChunkCounts));
+        if (!(rc = reserve_roomy(ctx, S.u, call_bytes + carry_room + 256))) rc = reserve_pinned(ctx, S.h_counts, st->counts_bytes() + 16);
+        if (!rc) rc = reserve_roomy(ctx, S.counts, st->counts_bytes());
     }
     // (annotated records are a few per cent longer than the call's; the members' bound is the compressor's own)
     const size_t out_est = call_bytes + call_bytes / 8;
@@ -3002,12 +3162,34 @@ int fadehip_bam_back(fadehip_bam_stream *st, const uint8_t **out, size_t *out_by
     } else if (o->ready) {
         (void)hipEventSynchronize(o->ready);
     }
+    if (st->extract) {
+        if (o->xready && hipEventSynchronize(o->xready) != hipSuccess) return bam_fail(st, set_err(ctx, FADEHIP_E_HIP, "bam stream: copying the extract records failed"));
+        st->last_x = o->xbytes ? st->xbuf[k % (FADEHIP_BAM_CHUNKS + 1)].p : nullptr;
+        st->last_xbytes = o->xbytes;
+        st->last_xrecs = o->xrecs;
+        st->have_back = true;
+    }
     {
         std::lock_guard<std::mutex> l(st->mu);
         o->state = 0;
         st->k_back++;
     }
     st->cv.notify_all();
+    return 0;
+}
+
+int fadehip_bam_back_extract(fadehip_bam_stream *st, const uint8_t **recs, size_t *n_bytes, int64_t *n_records) {
+    if (!st) return set_err(nullptr, FADEHIP_E_INVALID, "stream is NULL");
+    fadehip_ctx *ctx = st->ctx;
+    if (!recs || !n_bytes || !n_records) return set_err(ctx, FADEHIP_E_INVALID, "NULL argument");
+    *recs = nullptr;
+    *n_bytes = 0;
+    *n_records = 0;
+    if (!st->extract) return set_err(ctx, FADEHIP_E_STATE, "bam stream: opened without FADEHIP_BAM_EXTRACT");
+    if (!st->have_back) return set_err(ctx, FADEHIP_E_STATE, "bam stream: back_extract comes after a back call");
+    *recs = st->last_x;
+    *n_bytes = st->last_xbytes;
+    *n_records = st->last_xrecs;
     return 0;
 }
 
@@ -3045,14 +3227,17 @@ void fadehip_bam_close(fadehip_bam_stream *st) {
     release(st->names_off);
     for (auto &S : st->set) {
         for (DevBuf *b : {&S.comp, &S.blocks, &S.status, &S.ticket, &S.u, &S.seg, &S.slots, &S.rec_off, &S.info, &S.sent_of, &S.art_of, &S.out_size, &S.blk32,
-                          &S.blk64, &S.counts})
+                          &S.blk64, &S.counts, &S.ex_size, &S.ex_blk})
             release(*b);
         release(S.h_blocks);
         release(S.h_counts);
     }
     for (auto &ob : st->outbuf) release(ob);
+    for (auto &xb : st->xbuf) release(xb);
     for (auto &o : st->ring) {
         release(o.o);
+        release(o.x);
+        if (o.xready) (void)hipEventDestroy(o.xready);
         if (o.ready) (void)hipEventDestroy(o.ready);
     }
     delete st;

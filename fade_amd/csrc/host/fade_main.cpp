@@ -65,6 +65,7 @@ static void print_anno_help() {
             "-b         --bam output bam\n"
             "-u        --ubam output uncompressed bam\n"
             "-c        --clip hard-clip the artifacts in the same pass (what `fade out -c` makes of the annotated file)\n"
+            "        --extract PATH: also write what `fade extract` makes of the annotated file (one mapped record per artifact side), in the same pass\n"
             "          --gpus number of MI355X devices, one process each on its own range of the input (default 1)\n"
             "    --out-shards with --gpus N: every device writes a complete file PREFIX.<k>.bam (.sam), nothing is merged\n"
             "         --batch records per device batch (default 262144)\n"
@@ -81,7 +82,8 @@ struct Opts {
     std::vector<std::string> pos;
     std::string out_shards;  // --out-shards PREFIX (with --gpus N)
     std::string stats_tsv, clip_tsv;  // --stats-tsv PATH, --clip-tsv PATH: the stats.d / noclip.d reports of this run
-    std::string seen;  // one letter per option met: t m w b u c h g(pus) B(atch) s(tats) T(iming) S(hards)
+    std::string extract;  // --extract PATH: `fade extract`'s records of this run's artifact calls, in the output's format
+    std::string seen;  // one letter per option met: t m w b u c h g(pus) B(atch) s(tats) T(iming) S(hards) X (--extract)
 };
 
 // std.getopt with config.bundling: short flags bundle (-bu), values attach (-w100, -w 100, --window-size=100)
@@ -130,6 +132,15 @@ static bool parse_opts(int argc, char **argv, Opts &o, std::string &err) {
                 }
                 if (val.empty()) { err = "Invalid value for option --" + name + ": (empty)"; return false; }
                 (name == "stats-tsv" ? o.stats_tsv : o.clip_tsv) = val;
+            }
+            else if (name == "extract") {
+                o.seen += 'X';
+                if (!has_val) {
+                    if (i + 1 >= argc) { err = "Missing value for argument --" + name; return false; }
+                    val = argv[++i];
+                }
+                if (val.empty()) { err = "Invalid value for option --extract: (empty)"; return false; }
+                o.extract = val;
             }
             else if (name == "bam") { o.seen += 'b'; o.bam = true; }
             else if (name == "ubam") { o.seen += 'u'; o.ubam = true; }
@@ -375,6 +386,47 @@ static void artifact_strings(const R &r, const fadehip_aln &a, const Header &h, 
 
 static void clip_read(Rec &rec, uint32_t rsv, const int64_t *ref_len = nullptr);
 
+// remap.d:46-61 / 67-82: the record `fade extract` makes of one artifact side — a new mapped record on contig tid at the
+// 0-based pos with the alignment's CIGAR, carrying the read's name, its bases reverse-complemented and its qualities
+// reversed; everything else is what a zero-filled bam1_t holds (mapq 0, mate tid 0, mate pos 0, tlen 0), and no aux area
+template <class R>
+static Rec build_extract_rec(const R &r, int tid, int64_t pos, const uint32_t *cig, size_t n_cig) {
+    static const uint8_t comp[16] = {0, 8, 4, 12, 2, 10, 6, 14, 1, 9, 5, 13, 3, 11, 7, 15};
+    const int lq = r.l_seq();
+    const size_t lqn = (size_t)r.l_qname();
+    Rec n;
+    n.d.assign(32 + lqn + 4 * n_cig + ((size_t)lq + 1) / 2 + (size_t)lq, 0);
+    int64_t reflen = 0;
+    for (size_t k = 0; k < n_cig; k++) {
+        const uint32_t op = cig[k] & 15;
+        if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) reflen += cig[k] >> 4;
+    }
+    n.template wr<int32_t>(0, tid);                       // remap.d:49
+    n.template wr<int32_t>(4, (int32_t)pos);              // remap.d:50 (ZB: am holds a 0-based position)
+    n.d[8] = (uint8_t)lqn;
+    n.d[9] = 0;                                  // a fresh bam1_t: mapq 0
+    n.template wr<uint16_t>(10, (uint16_t)reg2bin(pos < 0 ? 0 : pos, (pos < 0 ? 0 : pos) + (reflen > 0 ? reflen : 1)));
+    n.template wr<uint16_t>(12, (uint16_t)n_cig);
+    n.template wr<uint16_t>(14, (uint16_t)((r.flag() & 0x10) ? 0 : 0x10));  // remap.d:51-58
+    n.template wr<int32_t>(16, lq);
+    n.template wr<int32_t>(20, 0);                        // bam_init1 zero-fills: mtid 0, mpos 0, isize 0
+    n.template wr<int32_t>(24, 0);
+    n.template wr<int32_t>(28, 0);
+    memcpy(n.d.data() + 32, r.qname(), lqn);     // remap.d:48
+    size_t off = 32 + lqn;
+    if (n_cig) memcpy(n.d.data() + off, cig, 4 * n_cig);  // remap.d:61
+    off += 4 * n_cig;
+    const uint8_t *sq = r.seq(), *ql = r.qual();
+    for (int j = 0; j < lq; j++) {               // remap.d:59 reverse_complement_sam_record
+        const int code = (sq[j >> 1] >> ((~j & 1) << 2)) & 15;
+        const int k = lq - 1 - j;
+        n.d[off + (size_t)(k >> 1)] |= (uint8_t)(comp[code] << ((~k & 1) << 2));
+    }
+    off += ((size_t)lq + 1) / 2;
+    for (int j = 0; j < lq; j++) n.d[off + (size_t)j] = ql[lq - 1 - j];  // remap.d:60
+    return n;
+}
+
 static void tag_owned_record(Rec &r, uint8_t rs, const fadehip_aln *a, const Header &h) {
     r.aux_update_uint("rs", rs);  // anno.d:63,94
     if (!a) return;
@@ -390,7 +442,9 @@ static void tag_owned_record(Rec &r, uint8_t rs, const fadehip_aln *a, const Hea
 // strings for the few that have them, keeping the reference's tag order rs, am, as, ar, ab
 // clip (`fade annotate -c`): an artifact call is rebuilt as a whole too, tagged, and then hard-clipped by clip_read — with the
 // lengths of the batch's alignment, not of the am text (a record that came in with am:i keeps that tag and is clipped all the same)
-static void apply_tags(Chunk &c, const Header &h, Pool &pool, bool clip = false) {
+// extract (`fade annotate --extract`): `fade extract`'s records of the chunk's artifact calls, in record order, left before
+// right — from the record as it came in and the batch's alignment, likewise never from tags read back
+static void apply_tags(Chunk &c, const Header &h, Pool &pool, bool clip = false, std::vector<Rec> *extract = nullptr) {
     const size_t n = c.n_records();
     std::vector<uint8_t> rs(n, 0);
     for (size_t k = 0; k < c.sent.size(); k++) rs[c.sent[k]] = c.rs_sent[k];
@@ -409,9 +463,16 @@ static void apply_tags(Chunk &c, const Header &h, Pool &pool, bool clip = false)
     o.owned.clear();
     std::vector<std::string> art_str(c.art.size() * 4);
     std::vector<std::vector<std::pair<uint32_t, Rec>>> owned_t(nt);
+    std::vector<std::vector<Rec>> extract_t(extract ? nt : 0);
     pool.parallel_for(nt, [&](size_t t) {
         for (size_t i = n * t / nt; i < n * (t + 1) / nt; i++) {
             const RecView v = c.blk.view(i);
+            if (extract && art_of[i] >= 0 && (rs[i] & 6)) {
+                const fadehip_aln &al = c.art[(size_t)art_of[i]];
+                const size_t n_ops = (size_t)std::min<int>(std::max(al.sw.n_ops, 0), FADEHIP_MAX_OPS);
+                for (int side = 0; side < 2; side++)  // (am names the one alignment on both sides)
+                    if (rs[i] & (2u << side)) extract_t[t].push_back(build_extract_rec(v, v.tid(), al.win_start + al.sw.beg_ref, al.sw.ops, n_ops));
+            }
             bool has_ours = false;
             for (size_t p = v.aux_off(); p + 3 <= v.nbytes();) {
                 const size_t fs = v.aux_field_size(p + 2);
@@ -447,6 +508,11 @@ static void apply_tags(Chunk &c, const Header &h, Pool &pool, bool clip = false)
     }, CPU_TAGS);
     for (auto &v : owned_t)
         for (auto &e : v) o.owned.push_back(std::move(e));
+    if (extract) {
+        extract->clear();
+        for (auto &v : extract_t)  // (the threads' ranges follow one another)
+            for (auto &e : v) extract->push_back(std::move(e));
+    }
     for (size_t i = 0; i < n; i++) o.sfx_off[i + 1] += o.sfx_off[i];
     o.sfx.resize(o.sfx_off[n]);
     pool.parallel_for(nt, [&](size_t t) {
@@ -1390,6 +1456,7 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
             cfg.tail_trim = host_inflate ? 0 : tail_trim;
             cfg.flags = o.ubam ? FADEHIP_BAM_STORED : 0;  // -u: uncompressed BGZF (util.d:65-76, SAMWriterTypes.UBAM)
             if (o.clip) cfg.flags |= FADEHIP_BAM_CLIP;    // -c: the artifact calls leave hard-clipped
+            if (!o.extract.empty()) cfg.flags |= FADEHIP_BAM_EXTRACT;  // --extract: every call leaves its extract records too
             if (fadehip_bam_open(ctx, &cfg, &st)) { create_err = fadehip_last_error(ctx); return 1; }
             const size_t call_bytes = host_inflate ? chunk : std::min<size_t>(chunk * 3, (size_t)1 << 30);
             if (!(getenv("FADE_BAM_PREPARE") && atoi(getenv("FADE_BAM_PREPARE")) == 0) && fadehip_bam_prepare(st, call_bytes)) { create_err = fadehip_last_error(ctx); return 1; }
@@ -1435,7 +1502,7 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
             }
         }
         BoundedQueue<int> q_cfree(NBUF + 1), q_cfull(NBUF + 1), q_free(NBUF + 1), q_full(NBUF + 1), q_done(FADEHIP_BAM_CHUNKS + 1);
-        struct OutRef { const uint8_t *p; size_t n; };
+        struct OutRef { const uint8_t *p; size_t n; const uint8_t *xp = nullptr; size_t xn = 0; };  // (xp, xn: --extract)
         // A call's bytes stay valid during the next back call only (include/fadehip.h: two staging buffers in turn), so the
         // back thread may run at most one call ahead of the call whose bytes the writer still holds: two credits, one taken
         // before each back call and given back when its bytes have been written.
@@ -1451,6 +1518,10 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
             if (stage_err.empty()) stage_err = e;
         };
         std::atomic<bool> abort_all{false};
+        // --extract PATH: the extract file, its writer (made once the device is there) and the writer thread's records
+        struct FileCloser { FILE *f = nullptr; ~FileCloser() { if (f) fclose(f); } } xfile;
+        std::unique_ptr<Writer> xwriter;
+        std::vector<Rec> xrecs;
         StageThreads stages;
         stages.unblock = [&] {
             abort_all = true;
@@ -1645,6 +1716,11 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
             hw.close();
         }
         if (creating.get()) { fprintf(stderr, "[E::fade annotate] cannot open the GPU path: %s\n", create_err.c_str()); return 1; }
+        if (!o.extract.empty()) {  // --extract PATH: the output's format and header, written by the CPU writer
+            xfile.f = fopen(o.extract.c_str(), "wb");
+            if (!xfile.f) { fprintf(stderr, "[E::fade annotate] cannot write %s: %s\n", o.extract.c_str(), strerror(errno)); return 1; }
+            xwriter.reset(new Writer(xfile.f, o.ubam ? OutFmt::UBAM : OutFmt::BAM, out_hdr, &pool));
+        }
         ck_upload.stop();
         // (the FASTA's text is on the device now; giving a genome's worth of pages back takes milliseconds, and the first call
         // is waiting: on a thread of its own)
@@ -1661,7 +1737,12 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
                     const int rc = fadehip_bam_back(st, &p, &n);
                     ck_back.stop();
                     if (rc) throw std::runtime_error(std::string("device: ") + fadehip_last_error(ctx));
-                    q_write.push(OutRef{p, n});
+                    OutRef ref{p, n};
+                    if (xwriter) {  // (the call's extract records live as long as its members: the writer takes both)
+                        int64_t n_x = 0;
+                        if (fadehip_bam_back_extract(st, &ref.xp, &ref.xn, &n_x)) throw std::runtime_error(std::string("device: ") + fadehip_last_error(ctx));
+                    }
+                    q_write.push(ref);
                 }
             } catch (const std::exception &e) {
                 set_err(e.what());
@@ -1685,6 +1766,22 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
             uint64_t at = 0;
             std::vector<std::thread> helpers;
             while (q_write.pop(r)) {
+                if (ok && r.xn) {
+                    // the call's extract records (a few per cent of its bytes): framed here, compressed by the extract file's
+                    // own writer on the pool — on this side of the pipeline, so that the front half never waits for it
+                    try {
+                        xrecs.clear();
+                        for (size_t at_x = 0; at_x + 4 <= r.xn;) {
+                            uint32_t bs;
+                            memcpy(&bs, r.xp + at_x, 4);
+                            if (bs < 32 || at_x + 4 + bs > r.xn) throw std::runtime_error("the device's extract records are not whole");
+                            xrecs.emplace_back();
+                            xrecs.back().d.assign(r.xp + at_x + 4, r.xp + at_x + 4 + bs);
+                            at_x += 4 + (size_t)bs;
+                        }
+                        xwriter->write(xrecs);
+                    } catch (const std::exception &e) { set_err(e.what()); ok = false; abort_all = true; }
+                }
                 if (ok && r.n) {
                     ck_fwrite.start();
                     const long long base = placed_base.load();
@@ -1745,6 +1842,11 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
         for (auto &t : stages.th) t.join();
         stages.unblock = nullptr;
         if (!stage_err.empty()) { fprintf(stderr, "[E::fade annotate] %s\n", stage_err.c_str()); return 1; }
+        if (xwriter) {
+            xwriter->close();
+            xwriter.reset();
+            if (fflush(xfile.f) != 0 || ferror(xfile.f)) { fprintf(stderr, "[E::fade annotate] write error on %s\n", o.extract.c_str()); return 1; }
+        }
         if (placed_base.load() >= 0 && lseek(1, (off_t)((uint64_t)placed_base.load() + placed_bytes.load()), SEEK_SET) < 0) {
             fprintf(stderr, "[E::fade annotate] cannot seek the output: %s\n", strerror(errno));
             return 1;
@@ -1959,6 +2061,15 @@ static int annotate_main(const std::string &cl, const Opts &o) {
         std::unique_ptr<DeviceBgzf> dev_codec;
         if (fmt == OutFmt::BAM && !(getenv("FADE_BGZF_DEVICE") && atoi(getenv("FADE_BGZF_DEVICE")) == 0)) dev_codec.reset(new DeviceBgzf(ctxs[0]));
         Writer writer(stdout, fmt, hdr, &pool, dev_codec.get(), !lane.on || lane.k == 0 || lane.shard, !lane.on || lane.shard);
+        // --extract PATH: the extract records in the output's format, under the output's header (compressed on the host pool)
+        struct FileCloser { FILE *f = nullptr; ~FileCloser() { if (f) fclose(f); } } xfile;
+        std::unique_ptr<Writer> xwriter;
+        std::vector<Rec> xrecs;
+        if (!o.extract.empty()) {
+            xfile.f = fopen(o.extract.c_str(), "wb");
+            if (!xfile.f) { fprintf(stderr, "[E::fade annotate] cannot write %s: %s\n", o.extract.c_str(), strerror(errno)); return 1; }
+            xwriter.reset(new Writer(xfile.f, fmt, hdr, &pool));
+        }
 
         StageThreads wstage;  // declared after the writer it uses: joined before the writer goes away
         wstage.unblock = [&] {
@@ -1971,10 +2082,11 @@ static int annotate_main(const std::string &cl, const Opts &o) {
             try {
                 while (q_out.pop(c)) {
                     ck_tags.start();
-                    apply_tags(*c, hdr, pool, o.clip);
+                    apply_tags(*c, hdr, pool, o.clip, xwriter ? &xrecs : nullptr);
                     if (reports.on()) reports.add(*c, hdr, ctxs[(size_t)c->dev]);
                     ck_tags.stop();
                     ck_write.start();
+                    if (xwriter && !xrecs.empty()) xwriter->write(xrecs);
                     writer.write_block(c->blk, c->bout);
                     ck_write.stop();
                 }
@@ -2084,6 +2196,11 @@ static int annotate_main(const std::string &cl, const Opts &o) {
         }
         if (failed) return 1;
         writer.close();
+        if (xwriter) {
+            xwriter->close();
+            xwriter.reset();
+            if (fflush(xfile.f) != 0 || ferror(xfile.f)) { fprintf(stderr, "[E::fade annotate] write error on %s\n", o.extract.c_str()); return 1; }
+        }
         reports.close();
         if (n_oversize && !lane.on)
             fprintf(stderr, "[W::fade annotate] %lld soft-clipped reads were not re-aligned: read longer than %d bases or window longer than %d\n",
@@ -2216,7 +2333,6 @@ static int extract_main(const std::string &cl, const Opts &o) {
         hdr.add_pg("fade-extract", "fade", FADE_VERSION, cl);  // remap.d:18-26
         const OutFmt fmt = o.bam ? OutFmt::BAM : o.ubam ? OutFmt::UBAM : OutFmt::SAM;
         Writer writer(stdout, fmt, hdr, &pool);
-        static const uint8_t comp[16] = {0, 8, 4, 12, 2, 10, 6, 14, 1, 9, 5, 13, 3, 11, 7, 15};
         std::vector<Rec> in, out;
         for (;;) {
             in.clear();
@@ -2247,39 +2363,7 @@ static int extract_main(const std::string &cl, const Opts &o) {
                     const int64_t pos = std::strtoll(f.c_str() + c1 + 1, nullptr, 10);
                     std::vector<uint32_t> cig;
                     if (!parse_cigar_string(f.substr(c2 + 1), cig)) throw std::runtime_error("malformed am CIGAR: " + am);
-                    const int lq = r.l_seq();
-                    const size_t lqn = (size_t)r.l_qname();
-                    Rec n;
-                    n.d.assign(32 + lqn + 4 * cig.size() + ((size_t)lq + 1) / 2 + (size_t)lq, 0);
-                    int64_t reflen = 0;
-                    for (uint32_t c : cig) {
-                        const uint32_t op = c & 15;
-                        if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) reflen += c >> 4;
-                    }
-                    n.wr<int32_t>(0, tid);                       // remap.d:49
-                    n.wr<int32_t>(4, (int32_t)pos);              // remap.d:50 (ZB: am holds a 0-based position)
-                    n.d[8] = (uint8_t)lqn;
-                    n.d[9] = 0;                                  // a fresh bam1_t: mapq 0
-                    n.wr<uint16_t>(10, (uint16_t)reg2bin(pos < 0 ? 0 : pos, (pos < 0 ? 0 : pos) + (reflen > 0 ? reflen : 1)));
-                    n.wr<uint16_t>(12, (uint16_t)cig.size());
-                    n.wr<uint16_t>(14, (uint16_t)((r.flag() & 0x10) ? 0 : 0x10));  // remap.d:51-58
-                    n.wr<int32_t>(16, lq);
-                    n.wr<int32_t>(20, 0);                        // bam_init1 zero-fills: mtid 0, mpos 0, isize 0
-                    n.wr<int32_t>(24, 0);
-                    n.wr<int32_t>(28, 0);
-                    memcpy(n.d.data() + 32, r.qname(), lqn);     // remap.d:48
-                    size_t off = 32 + lqn;
-                    if (!cig.empty()) memcpy(n.d.data() + off, cig.data(), 4 * cig.size());  // remap.d:61
-                    off += 4 * cig.size();
-                    const uint8_t *sq = r.seq(), *ql = r.qual();
-                    for (int j = 0; j < lq; j++) {               // remap.d:59 reverse_complement_sam_record
-                        const int code = (sq[j >> 1] >> ((~j & 1) << 2)) & 15;
-                        const int k = lq - 1 - j;
-                        n.d[off + (size_t)(k >> 1)] |= (uint8_t)(comp[code] << ((~k & 1) << 2));
-                    }
-                    off += ((size_t)lq + 1) / 2;
-                    for (int j = 0; j < lq; j++) n.d[off + (size_t)j] = ql[lq - 1 - j];  // remap.d:60
-                    out.push_back(std::move(n));
+                    out.push_back(build_extract_rec(r, tid, pos, cig.data(), cig.size()));
                 }
             }
             writer.write(out);
@@ -2575,7 +2659,7 @@ int main(int argc, char **argv) {
             fprintf(stderr, "std.getopt.GetOptException: %s\n", err.c_str());
             return 1;
         }
-        if (!options_allowed(o, "tmwbucgBsTSPQ")) return 1;
+        if (!options_allowed(o, "tmwbucgBsTSPQX")) return 1;
         // app.d:84-89: helpWanted | args.length < 3 (args = prog, "annotate", positionals...)
         if (o.help || o.pos.size() < 2) { print_anno_help(); return 0; }
         if (o.pos.size() < 3) {  // the reference indexes args[2] and dies; say why instead
@@ -2597,10 +2681,23 @@ int main(int argc, char **argv) {
             fprintf(stderr, "[E::fade-annotate] %s describes unclipped records: not with --clip\n", !o.stats_tsv.empty() ? "--stats-tsv" : "--clip-tsv");
             return 1;
         }
+        if (!o.extract.empty()) {  // one file, written in record order by one writer — refused here, before any device is opened
+            if (o.gpus > 1 || !o.out_shards.empty()) {
+                fprintf(stderr, "[E::fade-annotate] --extract goes with one device: not with %s\n", o.gpus > 1 ? "--gpus N > 1" : "--out-shards");
+                return 1;
+            }
+            struct stat sa, sb2;
+            const bool same = o.extract == o.pos[1] || (stat(o.extract.c_str(), &sa) == 0 && stat(o.pos[1].c_str(), &sb2) == 0 && sa.st_dev == sb2.st_dev && sa.st_ino == sb2.st_ino);
+            if (o.extract == "-" || same) {
+                fprintf(stderr, "[E::fade-annotate] --extract PATH is a file of its own: not %s\n", o.extract == "-" ? "the standard output" : "the input");
+                return 1;
+            }
+        }
         if (!o.out_shards.empty() && o.gpus < 2) {
             fprintf(stderr, "[E::fade-annotate] --out-shards PREFIX writes one file per device: it goes with --gpus N (N >= 2)\n");
             return 1;
         }
+        if (!o.extract.empty()) fprintf(stderr, "[W::fade extract] Output SAM/BAM will not be sorted\n");  // remap.d:13
         if (o.clip && !lane_env().on) {  // filter.d:184-185, as `fade out -c` (once: the lanes of --gpus N stay silent)
             fprintf(stderr, "[W::fade-out] Using the -c flag means the output SAM/BAM will not be sorted (regardless of prior sorting)\n");
             fprintf(stderr, "[W::fade-out] You also may need to fix mate information with a tool like Picard FixMateInformation\n");

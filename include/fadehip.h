@@ -155,6 +155,22 @@ int fadehip_sw_stats_batch(fadehip_ctx *ctx, const int32_t scoring[4] /* open, e
 int fadehip_clip_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const int64_t *rec_off, const uint8_t *rs,
                        const int32_t *trim_left, const int32_t *trim_right, uint8_t *out, int64_t out_cap, int64_t *out_off);
 
+/* remap.d:11-87 (`fade extract`) over n BAM records (block_size first, as in a file), concatenated, rec_off holding n + 1
+ * offsets.  Side 2k is the left side of record k and is built when rs[k] has bit 1 (value 2), side 2k + 1 the right one, built
+ * when it has bit 2 (value 4): a new mapped record on contig art_tid[s] at the 0-based art_pos[s] with the CIGAR ops
+ * cig[cig_off[s] .. cig_off[s + 1]) (BAM-encoded), the read's name, its bases reverse-complemented and its qualities
+ * reversed, flag 0x10 exactly when the read has it clear, mapq 0, mate refID 0, mate pos 0, tlen 0, bin over the new span,
+ * no aux.  The entries of a side whose bit is clear are ignored, and out_off[s + 1] == out_off[s] there.  The records go
+ * to out back to back, left before right, in input order; out_off receives 2n + 1 offsets.  A side takes
+ * 36 + l_read_name + 4 n_ops + (l_seq + 1) / 2 + l_seq bytes; more than out_cap in all is FADEHIP_E_INVALID and nothing is
+ * written.  The CIGAR's query length is not held against l_seq (`fade extract` does not either).  The device function is
+ * the one the file path runs under FADEHIP_BAM_EXTRACT; there the fields are the run's own results.  A record whose
+ * block_size, l_read_name, n_cigar_op and l_seq do not fit its bytes, or a built side whose CIGAR offsets step backwards:
+ * FADEHIP_E_INVALID, with the record's index in fadehip_last_error.  Synchronous, on a stream and buffers of its own. */
+int fadehip_extract_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const int64_t *rec_off, const uint8_t *rs,
+                          const int32_t *art_tid /* [2n] */, const int64_t *art_pos /* [2n] */, const int64_t *cig_off /* [2n + 1] */,
+                          const uint32_t *cig, uint8_t *out, int64_t out_cap, int64_t *out_off /* [2n + 1] */);
+
 /* ------------------------------------------------------ Level 2: annotateTask over a batch -- */
 /* Upload the indexed FASTA once (what IndexedFastaFile + fetchSequence serve, analysis.d:63).
  * seqs[c] holds lengths[c] ASCII residues (any case; upper-cased on device as analysis.d:63 does).
@@ -353,7 +369,11 @@ typedef struct fadehip_bam_config {
                                    * FADEHIP_BAM_CLIP: records called artifacts leave hard-clipped (`fade annotate -c`: what
                                    * `fade out -c` would make of the annotated file, in the same pass — by this run's rs and
                                    * alignments, never by tags read back; the five tags describe the unclipped read).  It
-                                   * combines with the other two flags and holds for front and front_raw alike */
+                                   * combines with the other two flags and holds for front and front_raw alike;
+                                   * FADEHIP_BAM_EXTRACT: every call also builds `fade extract`'s records of its artifact calls
+                                   * (`fade annotate --extract`), one per set artifact bit of rs, left before right, in input
+                                   * order, from the record as it came in (with FADEHIP_BAM_CLIP too) and this run's alignment:
+                                   * fadehip_bam_back_extract hands them out.  Combines with the other three */
     const char *const *ref_names; /* [n_ref] NUL-terminated */
     uint32_t first_record;        /* payload bytes of the first member passed to front that precede the first record */
     uint32_t tail_trim;           /* payload bytes at the END of the last member (front's last call) that are not this stream's:
@@ -363,6 +383,7 @@ typedef struct fadehip_bam_config {
 #define FADEHIP_BAM_STORED 1
 #define FADEHIP_BAM_NO_OUTPUT 2
 #define FADEHIP_BAM_CLIP 4
+#define FADEHIP_BAM_EXTRACT 8
 int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_bam_stream **out);
 int fadehip_bam_prepare(fadehip_bam_stream *st, size_t call_bytes);
 int fadehip_bam_front(fadehip_bam_stream *st, const void *members, size_t n_bytes, int last);
@@ -371,6 +392,10 @@ int fadehip_bam_front(fadehip_bam_stream *st, const void *members, size_t n_byte
 int fadehip_bam_front_raw(fadehip_bam_stream *st, const void *payload, size_t n_bytes, int last);
 /* (*out is good during the next back call and no longer: write it, or have it written, before the call after next) */
 int fadehip_bam_back(fadehip_bam_stream *st, const uint8_t **out, size_t *out_bytes);
+/* With FADEHIP_BAM_EXTRACT: the extract records of the call the most recent fadehip_bam_back finished — uncompressed BAM
+ * records (block_size first) back to back, in pinned memory, good as long as that back call's *out; a call without
+ * artifact calls gives 0 bytes, 0 records (and *recs NULL).  Without the flag, or before any back: FADEHIP_E_STATE. */
+int fadehip_bam_back_extract(fadehip_bam_stream *st, const uint8_t **recs, size_t *n_bytes, int64_t *n_records);
 /* totals so far: the eight Stats.parse counters (stats.d:45-54), records, reads beyond the kernels' limits */
 int fadehip_bam_totals(fadehip_bam_stream *st, int64_t stats[8], int64_t *n_records, int64_t *n_oversize);
 void fadehip_bam_close(fadehip_bam_stream *st);
