@@ -144,6 +144,9 @@ int fadehip_clip_batch(fadehip_ctx* ctx, int n, const(ubyte)* recs, const(long)*
 /// reverse-complemented, its qualities reversed; out_off receives 2n + 1 offsets into out_ (a side whose bit is clear takes nothing)
 int fadehip_extract_batch(fadehip_ctx* ctx, int n, const(ubyte)* recs, const(long)* rec_off, const(ubyte)* rs,
         const(int)* art_tid, const(long)* art_pos, const(long)* cig_off, const(uint)* cig, ubyte* out_, long out_cap, long* out_off);
+/// filter.d:209-265 (plain `fade out`) over n BAM records: keep[k] = 1 when record k would be written.  grouped == 0: ejected when
+/// rs[k] & 6; grouped != 0 (name-sorted input): a run of consecutive records with equal names is ejected as a whole when one has rs & 6
+int fadehip_eject_batch(fadehip_ctx* ctx, int n, const(ubyte)* recs, const(long)* rec_off, const(ubyte)* rs, int grouped, ubyte* keep);
 int fadehip_genome_upload(fadehip_ctx* ctx, int n_contigs, const(long)* lengths, const(ubyte*)* seqs);
 int fadehip_annotate_upload(fadehip_ctx* ctx, int slot, const(fadehip_read_batch)* batch);
 int fadehip_annotate_run(fadehip_ctx* ctx, int slot, int floor_len, int window);
@@ -171,7 +174,7 @@ struct fadehip_bam_config {
     int floor_len;               /// --min-length
     int window;                  /// -w
     int n_ref;                   /// contigs of the BAM header
-    int flags;                   /// 1 (FADEHIP_BAM_STORED): uncompressed BGZF out; 2 (FADEHIP_BAM_NO_OUTPUT): back makes no BGZF (measurement); 4 (FADEHIP_BAM_CLIP): hard-clip the artifact calls; 8 (FADEHIP_BAM_EXTRACT): every call also leaves `fade extract`'s records
+    int flags;                   /// 1 (FADEHIP_BAM_STORED): uncompressed BGZF out; 2 (FADEHIP_BAM_NO_OUTPUT): back makes no BGZF (measurement); 4 (FADEHIP_BAM_CLIP): hard-clip the artifact calls; 8 (FADEHIP_BAM_EXTRACT): every call also leaves `fade extract`'s records; 16 (FADEHIP_BAM_EJECT): artifact calls are not written; 32 (FADEHIP_BAM_EJECT_GROUPS): nor the records of their name group
     const(char*)* ref_names;     /// [n_ref]
     uint first_record;           /// payload bytes of the first member passed that precede the first record
     uint tail_trim;              /// payload bytes at the end of the last member that belong to the next reader
@@ -180,6 +183,8 @@ enum FADEHIP_BAM_CHUNKS = 3;
 enum FADEHIP_BAM_STORED = 1;     /// fadehip_bam_config.flags: uncompressed BGZF out (`fade annotate -u`)
 enum FADEHIP_BAM_NO_OUTPUT = 2;  /// ... back releases the annotated records without compressing them (measurement)
 enum FADEHIP_BAM_EXTRACT = 8;    /// ... every call also builds `fade extract`'s records of its artifact calls (`fade annotate --extract`): fadehip_bam_back_extract
+enum FADEHIP_BAM_EJECT = 16;     /// ... artifact calls are not written (`fade annotate --eject`, input not name-sorted), by this run's rs; not with FADEHIP_BAM_CLIP
+enum FADEHIP_BAM_EJECT_GROUPS = 32;  /// ... name-sorted input: nor any record of an artifact call's name group (implies FADEHIP_BAM_EJECT); a group never lies across two calls
 enum FADEHIP_BAM_CLIP = 4;       /// ... artifact calls leave hard-clipped (`fade annotate -c`), by this run's rs and alignments
 int fadehip_bam_open(fadehip_ctx* ctx, const(fadehip_bam_config)* cfg, fadehip_bam_stream** out_);
 int fadehip_bam_prepare(fadehip_bam_stream* st, size_t call_bytes);
@@ -189,4 +194,6 @@ int fadehip_bam_back(fadehip_bam_stream* st, const(ubyte)** out_, size_t* out_by
 /// FADEHIP_BAM_EXTRACT: the extract records (uncompressed BAM records, pinned memory) of the call the most recent back finished
 int fadehip_bam_back_extract(fadehip_bam_stream* st, const(ubyte)** recs, size_t* n_bytes, long* n_records);
 int fadehip_bam_totals(fadehip_bam_stream* st, long* stats8, long* n_records, long* n_oversize);
+/// FADEHIP_BAM_EJECT: records not written, over the calls back has taken
+int fadehip_bam_ejected(fadehip_bam_stream* st, long* n_ejected);
 void fadehip_bam_close(fadehip_bam_stream* st);

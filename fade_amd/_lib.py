@@ -33,8 +33,9 @@ EXPORTS = [
     "fadehip_bgzf_deflate_submit", "fadehip_bgzf_deflate_wait", "fadehip_stats_allreduce_rank", "fadehip_bgzf_inflate",
     "fadehip_bam_open", "fadehip_bam_front", "fadehip_bam_front_raw", "fadehip_bam_back", "fadehip_bam_totals", "fadehip_bam_close",
     "fadehip_bam_prepare", "fadehip_sw_stats_batch", "fadehip_clip_batch", "fadehip_extract_batch", "fadehip_bam_back_extract",
+    "fadehip_eject_batch", "fadehip_bam_ejected",
 ]
-BAM_STORED, BAM_NO_OUTPUT, BAM_CLIP, BAM_EXTRACT = 1, 2, 4, 8  # fadehip_bam_config.flags
+BAM_STORED, BAM_NO_OUTPUT, BAM_CLIP, BAM_EXTRACT, BAM_EJECT, BAM_EJECT_GROUPS = 1, 2, 4, 8, 16, 32  # fadehip_bam_config.flags
 BGZF_BLOCK = 0xff00
 BGZF_LANES = 2
 
@@ -127,6 +128,7 @@ def load():
     L.fadehip_sw_stats_batch.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
     L.fadehip_clip_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, i64, vp]
     L.fadehip_extract_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]
+    L.fadehip_eject_batch.argtypes = [vp, i32, vp, vp, vp, C.c_int, vp]
     L.fadehip_genome_upload.argtypes = [vp, i32, vp, vp]
     L.fadehip_annotate_upload.argtypes = [vp, C.c_int, C.POINTER(ReadBatch)]
     L.fadehip_annotate_run.argtypes = [vp, C.c_int, i32, i32]
@@ -145,6 +147,7 @@ def load():
     L.fadehip_bam_front_raw.argtypes = [vp, vp, C.c_size_t, C.c_int]
     L.fadehip_bam_back.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.fadehip_bam_back_extract.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(i64)]
+    L.fadehip_bam_ejected.argtypes = [vp, C.POINTER(i64)]
     L.fadehip_bam_totals.argtypes = [vp, C.POINTER(i64 * 8), C.POINTER(i64), C.POINTER(i64)]
     L.fadehip_bam_close.argtypes = [vp]
     L.fadehip_bam_close.restype = None

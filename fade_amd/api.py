@@ -16,6 +16,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import ALN_DTYPE, SW_DTYPE, SW_STATS_DTYPE, FadeHipError
+from ._lib import BAM_STORED, BAM_NO_OUTPUT, BAM_CLIP, BAM_EXTRACT, BAM_EJECT, BAM_EJECT_GROUPS  # noqa: F401  (fadehip_bam_config.flags)
 
 CIGAR_OPS = "MIDNSHP=X"
 NT16 = "=ACMGRSVTWYHKDBN"
@@ -151,6 +152,29 @@ class Context:
         cat = np.frombuffer(b"".join(rb), dtype=np.uint8) if off[-1] else np.zeros(0, np.uint8)
         out, out_off = self.clip_batch_packed(cat, off, rs, trim_left, trim_right)
         return [out[out_off[k]:out_off[k + 1]].tobytes() for k in range(len(rb))]
+
+    # ---- filter.d:209-265 (plain `fade out`): the kernels of the file path's eject=..., on records brought here
+    def eject_batch_packed(self, recs, rec_off, rs, grouped):
+        """keep (uint8[n]): 1 where `fade out` would write the record.  grouped: the records are name-sorted, and a run of
+        consecutive records with equal names leaves as a whole when one of them has rs & 6; otherwise record by record."""
+        recs = np.ascontiguousarray(recs, dtype=np.uint8)
+        rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
+        rs = np.ascontiguousarray(rs, dtype=np.uint8)
+        n = len(rec_off) - 1
+        if len(rs) != n:
+            raise ValueError("rs holds one entry per record")
+        keep = np.zeros(n, dtype=np.uint8)
+        self._chk(self._L.fadehip_eject_batch(self._h, n, recs.ctypes.data, rec_off.ctypes.data, rs.ctypes.data, 1 if grouped else 0,
+                                              keep.ctypes.data))
+        return keep
+
+    def eject_batch(self, records, rs, grouped):
+        """Which of the BAM records (bytes, block_size first) plain `fade out` writes, given their rs: a bool array."""
+        rb = [bytes(r) for r in records]
+        off = np.zeros(len(rb) + 1, dtype=np.int64)
+        np.cumsum([len(r) for r in rb], out=off[1:])
+        cat = np.frombuffer(b"".join(rb), dtype=np.uint8) if off[-1] else np.zeros(0, np.uint8)
+        return self.eject_batch_packed(cat, off, rs, grouped).astype(bool)
 
     # ---- remap.d:11-87 (`fade extract`): the device function of the file path's extract=True, on records brought here
     def extract_batch_packed(self, recs, rec_off, rs, art_tid, art_pos, cig_off, cig, out_cap=None):
@@ -382,12 +406,14 @@ class Context:
         self.bgzf_deflate_submit(lane, data)
         return self.bgzf_deflate_wait(lane)
 
-    def bam_stream(self, ref_names, floor_len=5, window=300, first_record=0, stored=False, tail_trim=0, no_output=False, clip=False, extract=False):
+    def bam_stream(self, ref_names, floor_len=5, window=300, first_record=0, stored=False, tail_trim=0, no_output=False, clip=False, extract=False, eject=None):
         """The file path on the device (fadehip_bam_*): BGZF members of a BAM's records in, BGZF members of the annotated
         records out.  ref_names: the BAM header's contigs (the genome must be uploaded).  clip: records called artifacts leave
         hard-clipped (`fade annotate -c`).  extract: every call also builds `fade extract`'s records of its artifact calls
-        (`fade annotate --extract`); BamStream.back_extract() fetches them after each back()."""
-        return BamStream(self, ref_names, floor_len, window, first_record, stored, tail_trim, no_output, clip, extract)
+        (`fade annotate --extract`); BamStream.back_extract() fetches them after each back().  eject: "records" — artifact
+        calls are not written; "groups" — nor any record of their name group, on name-sorted input (`fade annotate --eject`);
+        BamStream.ejected() counts them.  Not with clip."""
+        return BamStream(self, ref_names, floor_len, window, first_record, stored, tail_trim, no_output, clip, extract, eject)
 
     def bgzf_inflate(self, members, out_cap=None):
         """Whole BGZF members (bytes / uint8 array) -> their payloads, inflated on the device (CRC32 and ISIZE checked)."""
@@ -521,11 +547,14 @@ def format_tags(batch, contig_names, rs, aln):
 
 
 class BamStream:
-    def __init__(self, ctx, ref_names, floor_len, window, first_record, stored=False, tail_trim=0, no_output=False, clip=False, extract=False):
+    def __init__(self, ctx, ref_names, floor_len, window, first_record, stored=False, tail_trim=0, no_output=False, clip=False, extract=False, eject=None):
         self._ctx, self._L = ctx, ctx._L
+        if eject not in (None, False, "records", "groups"):
+            raise ValueError('eject is None, "records" or "groups"')
+        ej = BAM_EJECT | BAM_EJECT_GROUPS if eject == "groups" else BAM_EJECT if eject == "records" else 0
         names = [n.encode() if isinstance(n, str) else bytes(n) for n in ref_names]
         arr = (C.c_char_p * max(len(names), 1))(*names)
-        cfg = _lib.BamConfig(floor_len, window, len(names), (_lib.BAM_STORED if stored else 0) | (_lib.BAM_NO_OUTPUT if no_output else 0) | (_lib.BAM_CLIP if clip else 0) | (_lib.BAM_EXTRACT if extract else 0), arr, first_record, tail_trim)
+        cfg = _lib.BamConfig(floor_len, window, len(names), (_lib.BAM_STORED if stored else 0) | (_lib.BAM_NO_OUTPUT if no_output else 0) | (_lib.BAM_CLIP if clip else 0) | (_lib.BAM_EXTRACT if extract else 0) | ej, arr, first_record, tail_trim)
         h = C.c_void_p()
         ctx._chk(self._L.fadehip_bam_open(ctx._h, C.byref(cfg), C.byref(h)))
         self._h = h
@@ -557,6 +586,12 @@ class BamStream:
         p, n, nr = C.c_void_p(), C.c_size_t(0), C.c_int64(0)
         self._ctx._chk(self._L.fadehip_bam_back_extract(self._h, C.byref(p), C.byref(n), C.byref(nr)))
         return (C.string_at(p, n.value) if n.value else b""), int(nr.value)
+
+    def ejected(self):
+        """Records not written (eject=...), over the calls back() has taken."""
+        n = C.c_int64(0)
+        self._ctx._chk(self._L.fadehip_bam_ejected(self._h, C.byref(n)))
+        return int(n.value)
 
     def totals(self):
         st, nr, no = (C.c_int64 * 8)(), C.c_int64(0), C.c_int64(0)

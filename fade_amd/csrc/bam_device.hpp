@@ -49,7 +49,8 @@ struct ChunkCounts {
     uint32_t n_seq;         // their packed sequence bytes
     uint32_t l_seq_min, l_seq_max, span_max, n_long_q;
     uint32_t n_ours;        // records that already carry one of rs / am / as / ar / ab
-    uint32_t pad0, pad1;
+    uint32_t n_ejected;     // records the eject kernels took out of the output (FADEHIP_BAM_EJECT)
+    uint32_t pad1;
     uint64_t out_bytes;     // bytes of the rewritten record stream
     uint64_t pad2;
 };
@@ -1220,6 +1221,170 @@ __global__ __launch_bounds__(256) void extract_batch_write_kernel(ExtractBatchAr
     if (s >= 2u * a.n || !a.out_size[s]) return;
     const RecHdr r = rec_header(a.in + a.in_off[s >> 1]);
     extract_write(r, a.tid[s], a.pos[s], a.cig + a.cig_off[s], (uint32_t)(a.cig_off[s + 1u] - a.cig_off[s]), a.out + a.out_off[s], sl);
+}
+
+// ============================================================================================ eject
+// `fade annotate --eject` (FADEHIP_BAM_EJECT / FADEHIP_BAM_EJECT_GROUPS) / fadehip_eject_batch: filter.d:209-265 (plain
+// `fade out`) in the pass that writes the records.  An artifact call (rs & 6 of THIS run, never an rs tag read back) is
+// not written; in grouped mode neither is any record of its name group — the maximal run of consecutive records with
+// byte-equal names.  These kernels are of their own: a run without the flag launches none of them, and they mark an
+// ejected record the way the kernels of such a run already understand (out_size 0, INFO_BAD, which the rewrite kernel
+// skips by), so those kernels are not touched.
+//
+// Names are equal when l_read_name and all name bytes are: (unaligned) dwords, the last one masked.  The loads reach up to
+// three bytes behind the name — bytes of the record when l_read_name fits block_size, which the callers have checked.
+__device__ __forceinline__ bool same_name(const uint8_t *p, const uint8_t *q) {
+    const uint32_t ln = p[12];
+    if (ln != (uint32_t)q[12]) return false;
+    for (uint32_t k = 0; k < ln; k += 4u) {
+        uint32_t x = ld32(p + 36u + k) ^ ld32(q + 36u + k);
+        if (k + 4u > ln) x &= 0xffffffffu >> (8u * (k + 4u - ln));
+        if (x) return false;
+    }
+    return true;
+}
+
+// Grouped mode, a call that is not the last: a name group must not lie across two calls, so the call gives its last group
+// back — n_records and consumed are lowered to the group's start, and the carry (the bytes behind `consumed`) moves the
+// group into the next call.  One wave, behind bam_frame_compact_kernel: the 64 records in front are compared with the last
+// record's name at a time, by ballot.  A call that is one group gives everything back.  (The layout of these records has
+// not been checked yet: one whose name does not fit its block_size ends the run of equal names and fails the call later.)
+__global__ __launch_bounds__(64) void bam_eject_hold_kernel(FrameArgs a) {
+    ChunkCounts *cc = a.counts;
+    const uint32_t n = min(cc->n_records, a.rec_cap - 1u);
+    if (n == 0 || cc->frame_err) return;
+    const uint32_t lane = threadIdx.x;
+    const uint8_t *last = a.u + a.rec_off[n - 1u];
+    uint32_t start = n - 1u;
+    if (32u + last[12] <= ld32(last)) {
+        for (uint32_t hi = n - 1u; hi > 0u;) {  // records [start, n) carry the last record's name; hi == start
+            bool eq = false;
+            if (lane < hi) {
+                const uint8_t *p = a.u + a.rec_off[hi - 1u - lane];
+                eq = 32u + p[12] <= ld32(p) && same_name(p, last);
+            }
+            const unsigned long long ne = ~__ballot(eq);
+            const uint32_t k = ne ? (uint32_t)__builtin_ctzll(ne) : 64u;
+            hi -= k;
+            start = hi;
+            if (k < 64u) break;
+        }
+    }
+    if (lane == 0) {
+        cc->n_records = start;
+        cc->consumed = a.rec_off[start];
+    }
+}
+
+struct EjectArgs {
+    const uint8_t *u;
+    const uint32_t *off32;     // the file path: rec_off ...
+    const uint64_t *off64;     // ... fadehip_eject_batch: in_off (the one that is not null)
+    uint32_t n;                // records
+    const int32_t *sent_of;    // the file path: rs is per sent record; nullptr: rs is per record
+    const uint8_t *rs;
+    uint32_t *head_of;         // [n]  bit 31: the record is an artifact call; bits 0-30: 1 + index of its group's first record
+    uint32_t *blk_head;        // [blocks of TAG_BLOCK records]  1 + index of the last group start in the block, 0: none
+    uint32_t *blk_carry;       // [blocks]  the same over all blocks in front
+    uint32_t *grp;             // [n]  at a group's first record: != 0 when a record of the group is an artifact call (zeroed)
+    // what the decision goes into: the file path's arrays ...
+    uint32_t *out_size, *info;
+    uint64_t *blk_sums;
+    ChunkCounts *counts;       // n_ejected
+    uint8_t *keep;             // ... or fadehip_eject_batch's answer
+};
+__device__ __forceinline__ const uint8_t *eject_rec(const EjectArgs &a, uint32_t i) { return a.u + (a.off32 ? (uint64_t)a.off32[i] : a.off64[i]); }
+__device__ __forceinline__ bool eject_art(const EjectArgs &a, uint32_t i) {
+    if (!a.sent_of) return (a.rs[i] & 6u) != 0;
+    const int32_t s = a.sent_of[i];
+    return s >= 0 && (a.rs[s] & 6u) != 0;  // (a record that never reached the gate has rs 0)
+}
+
+// Thread per record: is it the first of its name group (its name differs from the record's in front; record 0 is one), is it
+// an artifact call; then a max-scan of (1 + index of a group start) over the block — wave, then the block's four waves —
+// leaves every record the start of its group, or 0 when the group began in a block in front.
+__global__ __launch_bounds__(TAG_BLOCK) void bam_eject_head_kernel(EjectArgs a) {
+    __shared__ uint32_t wmax[TAG_BLOCK / 64];
+    const uint32_t i = blockIdx.x * TAG_BLOCK + threadIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t v = 0;
+    bool art = false;
+    if (i < a.n) {
+        const bool head = i == 0u || !same_name(eject_rec(a, i), eject_rec(a, i - 1u));
+        art = eject_art(a, i);
+        v = head ? i + 1u : 0u;
+    }
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t o = (uint32_t)__shfl_up((int)v, d, 64);
+        if (lane >= d) v = max(v, o);
+    }
+    if (lane == 63) wmax[wave] = v;
+    __syncthreads();
+    for (int w = 0; w < wave; w++) v = max(v, wmax[w]);
+    if (i < a.n) a.head_of[i] = v | (art ? 0x80000000u : 0u);
+    if (threadIdx.x == TAG_BLOCK - 1) a.blk_head[blockIdx.x] = v;  // (threads behind the last record pass the maximum on)
+}
+
+// one block: exclusive max-scan of the blocks' last group starts, as bam_tag_scan_kernel sums the blocks' bytes
+__global__ __launch_bounds__(1024) void bam_eject_scan_kernel(EjectArgs a, uint32_t n_blocks) {
+    __shared__ uint32_t part[1024];
+    const int tid = threadIdx.x;
+    const uint32_t per = (n_blocks + 1023u) / 1024u, lo = (uint32_t)tid * per, hi = min(lo + per, n_blocks);
+    uint32_t m = 0;
+    for (uint32_t k = lo; k < hi; k++) m = max(m, a.blk_head[k]);
+    part[tid] = m;
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t run = 0;
+        for (int k = 0; k < 1024; k++) { const uint32_t t = part[k]; part[k] = run; run = max(run, t); }
+    }
+    __syncthreads();
+    uint32_t at = part[tid];
+    for (uint32_t k = lo; k < hi; k++) { a.blk_carry[k] = at; at = max(at, a.blk_head[k]); }
+}
+
+// thread per record: the group start is final now; an artifact call leaves its mark at the group's first record
+__global__ __launch_bounds__(TAG_BLOCK) void bam_eject_mark_kernel(EjectArgs a) {
+    const uint32_t i = blockIdx.x * TAG_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    const uint32_t w = a.head_of[i];
+    uint32_t h = w & 0x7fffffffu;
+    if (!h) {
+        h = a.blk_carry[blockIdx.x];  // (never 0: record 0 starts a group)
+        a.head_of[i] = w | h;
+    }
+    if (w >> 31) atomicOr(&a.grp[h - 1u], 1u);
+}
+
+// thread per record: the decision, applied.  The file path: an ejected record gets out_size 0 and INFO_BAD, and the block's
+// bytes are summed again — in front of bam_tag_scan_kernel, so that the offsets never hold it; fadehip_eject_batch: keep[].
+__global__ __launch_bounds__(TAG_BLOCK) void bam_eject_apply_kernel(EjectArgs a, int grouped) {
+    __shared__ uint64_t red[TAG_BLOCK / 64];
+    const uint32_t i = blockIdx.x * TAG_BLOCK + threadIdx.x;
+    uint64_t sz = 0;  // bytes, and the number of ejected records above bit 40
+    if (i < a.n) {
+        const bool ej = grouped ? a.grp[(a.head_of[i] & 0x7fffffffu) - 1u] != 0u : eject_art(a, i);
+        if (a.keep) a.keep[i] = ej ? 0 : 1;
+        if (a.out_size) {
+            if (ej) {
+                a.out_size[i] = 0u;
+                a.info[i] |= INFO_BAD;
+                sz = 1ull << 40;
+            } else sz = a.out_size[i];
+        }
+    }
+    if (!a.out_size) return;  // (uniform)
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) sz += (uint64_t)__shfl_xor((long long)sz, m, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sz;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint64_t t = 0;
+        for (int w = 0; w < TAG_BLOCK / 64; w++) t += red[w];
+        a.blk_sums[blockIdx.x] = t & ((1ull << 40) - 1ull);
+        if (t >> 40) atomicAdd(&a.counts->n_ejected, (uint32_t)(t >> 40));
+    }
 }
 
 }  // namespace bam

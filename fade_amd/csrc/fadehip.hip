@@ -200,6 +200,10 @@ struct fadehip_ctx {
     hipStream_t extract_stream = nullptr;
     DevBuf ex_in, ex_meta, ex_size, ex_out;
     std::mutex extract_mu;
+    // fadehip_eject_batch: likewise
+    hipStream_t eject_stream = nullptr;
+    DevBuf ej_in, ej_meta, ej_work;
+    std::mutex eject_mu;
     int n_contigs = 0;
     std::vector<int64_t> h_contig_len;
     std::vector<uint64_t> h_contig_base;
@@ -1467,6 +1471,8 @@ void fadehip_destroy(fadehip_ctx *ctx) {
     if (ctx->clip_stream) (void)hipStreamDestroy(ctx->clip_stream);
     for (DevBuf *b : {&ctx->ex_in, &ctx->ex_meta, &ctx->ex_size, &ctx->ex_out}) release(*b);
     if (ctx->extract_stream) (void)hipStreamDestroy(ctx->extract_stream);
+    for (DevBuf *b : {&ctx->ej_in, &ctx->ej_meta, &ctx->ej_work}) release(*b);
+    if (ctx->eject_stream) (void)hipStreamDestroy(ctx->eject_stream);
     release(ctx->contig_len);
     release(ctx->contig_base);
     if (g_err_ctx == ctx) g_err_ctx = nullptr;
@@ -1833,6 +1839,68 @@ int fadehip_clip_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const i
     hipLaunchKernelGGL(bam::clip_batch_write_kernel, dim3(((unsigned)n + 15u) / 16u), dim3(256), 0, st, a);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(out, a.out, out_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    return 0;
+}
+
+// filter.d:209-265 over records the caller brings: bam_device.hpp's eject kernels, the ones of the file path under
+// FADEHIP_BAM_EJECT / FADEHIP_BAM_EJECT_GROUPS, with the caller's rs in place of a run's results.
+int fadehip_eject_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const int64_t *rec_off, const uint8_t *rs, int grouped, uint8_t *keep) {
+    if (!ctx) return set_err(nullptr, FADEHIP_E_INVALID, "ctx is NULL");
+    if (n < 0 || !rec_off || (n > 0 && (!recs || !rs || !keep))) return set_err(ctx, FADEHIP_E_INVALID, "NULL argument");
+    if (rec_off[0] < 0) return set_err(ctx, FADEHIP_E_INVALID, "offsets must be non-negative and non-decreasing (record 0)");
+    if (n == 0) return 0;
+    // what the kernels dereference through is checked here: block_size against the offsets, the name against block_size
+    for (int32_t k = 0; k < n; k++) {
+        const int64_t len = rec_off[k + 1] - rec_off[k];
+        if (len < 0) return set_err(ctx, FADEHIP_E_INVALID, "offsets must be non-negative and non-decreasing (record %d)", k);
+        const uint8_t *p = recs + rec_off[k];
+        uint32_t bs = 0;
+        if (len >= 36) memcpy(&bs, p, 4);
+        if (len < 36 || len > ((int64_t)1 << 29) || (int64_t)bs + 4 != len || p[12] == 0 || 36 + (int64_t)p[12] > len)
+            return set_err(ctx, FADEHIP_E_INVALID, "record %d is malformed (block_size and l_read_name must fit its %lld bytes)", k, (long long)len);
+    }
+    const size_t in_bytes = (size_t)(rec_off[n] - rec_off[0]);
+    std::vector<uint64_t> off((size_t)n + 1);
+    for (int32_t k = 0; k <= n; k++) off[(size_t)k] = (uint64_t)(rec_off[k] - rec_off[0]);
+    std::lock_guard<std::mutex> lk(ctx->eject_mu);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (!ctx->eject_stream) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->eject_stream, hipStreamNonBlocking));
+    hipStream_t st = ctx->eject_stream;
+    const uint32_t ntb = ((uint32_t)n + bam::TAG_BLOCK - 1) / bam::TAG_BLOCK;
+    // ej_meta: in_off [n + 1] u64 | rs [n] u8 | keep [n] u8;  ej_work: head_of [n] u32 | grp [n] u32 | blk_head [ntb] | blk_carry [ntb]
+    const size_t m_rs = 8 * ((size_t)n + 1), m_keep = m_rs + (size_t)n;
+    int rc;
+    if ((rc = reserve(ctx, ctx->ej_in, in_bytes + 8)) || (rc = reserve(ctx, ctx->ej_meta, m_keep + (size_t)n + 8)) ||
+        (rc = reserve(ctx, ctx->ej_work, 8 * (size_t)n + 8 * (size_t)ntb)))
+        return rc;
+    uint8_t *meta = (uint8_t *)ctx->ej_meta.p;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->ej_in.p, recs + rec_off[0], in_bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(meta, off.data(), m_rs, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(meta + m_rs, rs, (size_t)n, hipMemcpyHostToDevice, st));
+    bam::EjectArgs a;
+    memset(&a, 0, sizeof a);
+    a.u = (const uint8_t *)ctx->ej_in.p;
+    a.off64 = (const uint64_t *)meta;
+    a.n = (uint32_t)n;
+    a.rs = meta + m_rs;
+    a.keep = meta + m_keep;
+    if (grouped) {
+        a.head_of = (uint32_t *)ctx->ej_work.p;
+        a.grp = a.head_of + (size_t)n;
+        a.blk_head = a.grp + (size_t)n;
+        a.blk_carry = a.blk_head + ntb;
+        HIPCHK(ctx, hipMemsetAsync(a.grp, 0, 4 * (size_t)n, st));
+        hipLaunchKernelGGL(bam::bam_eject_head_kernel, dim3(ntb), dim3(bam::TAG_BLOCK), 0, st, a);
+        HIPCHK(ctx, hipGetLastError());
+        hipLaunchKernelGGL(bam::bam_eject_scan_kernel, dim3(1), dim3(1024), 0, st, a, ntb);
+        HIPCHK(ctx, hipGetLastError());
+        hipLaunchKernelGGL(bam::bam_eject_mark_kernel, dim3(ntb), dim3(bam::TAG_BLOCK), 0, st, a);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    hipLaunchKernelGGL(bam::bam_eject_apply_kernel, dim3(ntb), dim3(bam::TAG_BLOCK), 0, st, a, grouped ? 1 : 0);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(keep, a.keep, (size_t)n, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     return 0;
 }
@@ -2471,6 +2539,8 @@ struct fadehip_bam_stream {
     bool clip = false;    // FADEHIP_BAM_CLIP: artifact calls leave hard-clipped (the <true> kernels of bam_device.hpp)
     bool no_output = false;  // FADEHIP_BAM_NO_OUTPUT: back gives the call's device bytes back without making BGZF of them
     bool extract = false;    // FADEHIP_BAM_EXTRACT: every call also leaves `fade extract`'s records of its artifact calls
+    bool eject = false;      // FADEHIP_BAM_EJECT: artifact calls are not written (the eject kernels of bam_device.hpp) ...
+    bool eject_groups = false;  // FADEHIP_BAM_EJECT_GROUPS: ... nor any record of their name group; a group never lies across two calls
     DevBuf names_text, names_off;
     struct Out {
         DevBuf o;
@@ -2497,6 +2567,7 @@ struct fadehip_bam_stream {
         DevBuf u;                             // the call's inflated bytes, the previous call's cut-off record in front
         DevBuf seg, slots, rec_off, info, sent_of, art_of, out_size, blk32, blk64, counts;
         DevBuf ex_size, ex_blk;               // extract: bytes per record, block sums and bases (the tag arrays' counterparts)
+        DevBuf ej_head, ej_blk, ej_grp;       // eject: every record's group start, the blocks' last starts and carries, the groups' marks
         bam::TagArgs xa;                      // extract: ta with the extract stream's sizes, sums, counts and output
         PinBuf h_blocks, h_counts;
         uint64_t k = ~0ull;
@@ -2523,7 +2594,7 @@ struct fadehip_bam_stream {
     std::mutex mu;
     std::condition_variable cv;
     int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int64_t n_records = 0, n_oversize = 0, n_redone = 0;
+    int64_t n_records = 0, n_oversize = 0, n_redone = 0, n_ejected = 0;
     bool failed = false, ended = false, closing = false;
     double t_inflate = 0, t_frame = 0, t_run = 0, t_tags = 0;
 };
@@ -2591,6 +2662,7 @@ int bam_finish_call(fadehip_bam_stream *st, uint64_t k) {
         out->bytes = (size_t)out_bytes;
         std::lock_guard<std::mutex> l(st->mu);
         st->n_records += S.n_rec;
+        st->n_ejected += h_counts->n_ejected;
     }
     if (!out->ready) HIPCHK(ctx, hipEventCreateWithFlags(&out->ready, hipEventDisableTiming | (ctx->blocking_sync ? hipEventBlockingSync : 0)));
     HIPCHK(ctx, hipEventRecord(out->ready, q));
@@ -2661,6 +2733,9 @@ int bam_front_impl(fadehip_bam_stream *st, const uint8_t *members, size_t n_byte
         if (consumed != n_bytes) return set_err(ctx, FADEHIP_E_INVALID, "bam stream: front takes whole BGZF members (%zu of %zu bytes are)", consumed, n_bytes);
     }
     const uint32_t carry = st->prev_len - st->prev_consumed;
+    if (st->eject_groups && (uint64_t)carry + total > (uint64_t)bam::MAX_U && total <= (uint64_t)bam::MAX_U)
+        return set_err(ctx, FADEHIP_E_UNSUPPORTED, "bam stream: a name group is longer than a call can hold (%u bytes carried over, at most %u with the call's own): "
+                       "FADE_BAM_DEVICE=0 takes the host pipeline, which holds a group of any length", carry, bam::MAX_U);
     if ((uint64_t)carry + total > (uint64_t)bam::MAX_U) return set_err(ctx, FADEHIP_E_UNSUPPORTED, "bam stream: %llu inflated bytes in one call (at most %u)", (unsigned long long)total + carry, bam::MAX_U);
     uint32_t u_len = carry + (uint32_t)total;
     if (last && !raw && st->tail_trim) {  // (the bytes behind this stream's last record, in its last member, belong to another reader)
@@ -2733,6 +2808,10 @@ int bam_front_impl(fadehip_bam_stream *st, const uint8_t *members, size_t n_byte
     if (fine) { tr.mark("  resolve enqueued"); (void)hipStreamSynchronize(q); tr.mark("  waited for"); }
     hipLaunchKernelGGL(bam::bam_frame_compact_kernel, dim3(std::max(1u, (n_seg + 3) / 4)), dim3(256), 0, q, fa);
     HIPCHK(ctx, hipGetLastError());
+    if (st->eject_groups && !last) {  // the call's last name group may go on in the next call: it is given back (and carried over)
+        hipLaunchKernelGGL(bam::bam_eject_hold_kernel, dim3(1), dim3(64), 0, q, fa);
+        HIPCHK(ctx, hipGetLastError());
+    }
     // which records go to the device's gate, their sizes: enqueued behind the framing for as many records as the bytes could
     // hold at most (threads beyond the records that are there return at once), so that ONE wait brings back both counts
     const uint32_t nblk_cap = (rec_cap + bam::PACK_BLOCK - 1) / bam::PACK_BLOCK;
@@ -2891,8 +2970,11 @@ int bam_front_impl(fadehip_bam_stream *st, const uint8_t *members, size_t n_byte
         if (st->clip) hipLaunchKernelGGL(bam::bam_tag_size_kernel<true>, dim3(ntb), dim3(bam::TAG_BLOCK), 0, q, ta);
         else hipLaunchKernelGGL(bam::bam_tag_size_kernel<false>, dim3(ntb), dim3(bam::TAG_BLOCK), 0, q, ta);
         HIPCHK(ctx, hipGetLastError());
-        hipLaunchKernelGGL(bam::bam_tag_scan_kernel, dim3(1), dim3(1024), 0, q, ta, ntb);
-        HIPCHK(ctx, hipGetLastError());
+        // (eject: the scan comes behind the eject kernels, which come behind the extract sizes — see below)
+        if (!st->eject) {
+            hipLaunchKernelGGL(bam::bam_tag_scan_kernel, dim3(1), dim3(1024), 0, q, ta, ntb);
+            HIPCHK(ctx, hipGetLastError());
+        }
         if (st->extract) {
             // the extract records' sizes into the same scan, their total into the ChunkCounts behind the call's own: it crosses
             // to the host in the copy below, which back reads anyway
@@ -2907,6 +2989,41 @@ int bam_front_impl(fadehip_bam_stream *st, const uint8_t *members, size_t n_byte
             hipLaunchKernelGGL(bam::bam_extract_size_kernel, dim3(ntb), dim3(bam::TAG_BLOCK), 0, q, xa);
             HIPCHK(ctx, hipGetLastError());
             hipLaunchKernelGGL(bam::bam_tag_scan_kernel, dim3(1), dim3(1024), 0, q, xa, ntb);
+            HIPCHK(ctx, hipGetLastError());
+        }
+        if (st->eject) {
+            // which records leave: out_size 0 and INFO_BAD for them, the blocks' sums again, and only then the scan of the
+            // sums.  Behind the extract sizes, which are taken of every artifact call and look at `info`.
+            bam::EjectArgs ea;
+            memset(&ea, 0, sizeof ea);
+            ea.u = u;
+            ea.off32 = fa.rec_off;
+            ea.n = n_rec;
+            ea.sent_of = pa.sent_of;
+            ea.rs = (const uint8_t *)s.rs.p;
+            ea.out_size = ta.out_size;
+            ea.info = pa.info;
+            ea.blk_sums = ta.blk_sums;
+            ea.counts = d_counts;
+            if (st->eject_groups) {
+                if ((rc = reserve_roomy(ctx, S.ej_head, 4 * (size_t)n_rec)) || (rc = reserve_roomy(ctx, S.ej_blk, 8 * (size_t)ntb)) ||
+                    (rc = reserve_roomy(ctx, S.ej_grp, 4 * (size_t)n_rec)))
+                    return rc;
+                ea.head_of = (uint32_t *)S.ej_head.p;
+                ea.blk_head = (uint32_t *)S.ej_blk.p;
+                ea.blk_carry = ea.blk_head + ntb;
+                ea.grp = (uint32_t *)S.ej_grp.p;
+                HIPCHK(ctx, hipMemsetAsync(ea.grp, 0, 4 * (size_t)n_rec, q));
+                hipLaunchKernelGGL(bam::bam_eject_head_kernel, dim3(ntb), dim3(bam::TAG_BLOCK), 0, q, ea);
+                HIPCHK(ctx, hipGetLastError());
+                hipLaunchKernelGGL(bam::bam_eject_scan_kernel, dim3(1), dim3(1024), 0, q, ea, ntb);
+                HIPCHK(ctx, hipGetLastError());
+                hipLaunchKernelGGL(bam::bam_eject_mark_kernel, dim3(ntb), dim3(bam::TAG_BLOCK), 0, q, ea);
+                HIPCHK(ctx, hipGetLastError());
+            }
+            hipLaunchKernelGGL(bam::bam_eject_apply_kernel, dim3(ntb), dim3(bam::TAG_BLOCK), 0, q, ea, st->eject_groups ? 1 : 0);
+            HIPCHK(ctx, hipGetLastError());
+            hipLaunchKernelGGL(bam::bam_tag_scan_kernel, dim3(1), dim3(1024), 0, q, ta, ntb);
             HIPCHK(ctx, hipGetLastError());
         }
         HIPCHK(ctx, hipMemcpyAsync(h_counts, d_counts, st->counts_bytes(), hipMemcpyDeviceToHost, q));
@@ -2932,8 +3049,10 @@ int bam_front_impl(fadehip_bam_stream *st, const uint8_t *members, size_t n_byte
 
 int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_bam_stream **out) {
     if (!ctx) return set_err(nullptr, FADEHIP_E_INVALID, "ctx is NULL");
-    if (!cfg || !out || cfg->n_ref < 0 || (cfg->n_ref && !cfg->ref_names) || cfg->window < 0 || (cfg->flags & ~(FADEHIP_BAM_STORED | FADEHIP_BAM_NO_OUTPUT | FADEHIP_BAM_CLIP | FADEHIP_BAM_EXTRACT)))
+    if (!cfg || !out || cfg->n_ref < 0 || (cfg->n_ref && !cfg->ref_names) || cfg->window < 0 || (cfg->flags & ~(FADEHIP_BAM_STORED | FADEHIP_BAM_NO_OUTPUT | FADEHIP_BAM_CLIP | FADEHIP_BAM_EXTRACT | FADEHIP_BAM_EJECT | FADEHIP_BAM_EJECT_GROUPS)))
         return set_err(ctx, FADEHIP_E_INVALID, "bam stream: bad configuration");
+    if ((cfg->flags & FADEHIP_BAM_CLIP) && (cfg->flags & (FADEHIP_BAM_EJECT | FADEHIP_BAM_EJECT_GROUPS)))
+        return set_err(ctx, FADEHIP_E_INVALID, "bam stream: FADEHIP_BAM_CLIP and FADEHIP_BAM_EJECT exclude each other (`fade out` clips an artifact or ejects it)");
     if (!ctx->two_pass) return set_err(ctx, FADEHIP_E_UNSUPPORTED, "bam stream: needs the default kernels (FADEHIP_KERNEL unset)");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     fadehip_bam_stream *st = new (std::nothrow) fadehip_bam_stream;
@@ -2948,6 +3067,8 @@ int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_ba
     st->no_output = (cfg->flags & FADEHIP_BAM_NO_OUTPUT) != 0;
     st->clip = (cfg->flags & FADEHIP_BAM_CLIP) != 0;
     st->extract = (cfg->flags & FADEHIP_BAM_EXTRACT) != 0;
+    st->eject_groups = (cfg->flags & FADEHIP_BAM_EJECT_GROUPS) != 0;
+    st->eject = st->eject_groups || (cfg->flags & FADEHIP_BAM_EJECT) != 0;
     std::string text;
     std::vector<uint32_t> off((size_t)cfg->n_ref + 1, 0);
     for (int k = 0; k < cfg->n_ref; k++) {
@@ -3202,6 +3323,14 @@ int fadehip_bam_totals(fadehip_bam_stream *st, int64_t stats[8], int64_t *n_reco
     return 0;
 }
 
+int fadehip_bam_ejected(fadehip_bam_stream *st, int64_t *n_ejected) {
+    if (!st) return set_err(nullptr, FADEHIP_E_INVALID, "stream is NULL");
+    if (!n_ejected) return set_err(st->ctx, FADEHIP_E_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> l(st->mu);
+    *n_ejected = st->n_ejected;
+    return 0;
+}
+
 void fadehip_bam_close(fadehip_bam_stream *st) {
     if (!st) return;
     {
@@ -3227,7 +3356,7 @@ void fadehip_bam_close(fadehip_bam_stream *st) {
     release(st->names_off);
     for (auto &S : st->set) {
         for (DevBuf *b : {&S.comp, &S.blocks, &S.status, &S.ticket, &S.u, &S.seg, &S.slots, &S.rec_off, &S.info, &S.sent_of, &S.art_of, &S.out_size, &S.blk32,
-                          &S.blk64, &S.counts, &S.ex_size, &S.ex_blk})
+                          &S.blk64, &S.counts, &S.ex_size, &S.ex_blk, &S.ej_head, &S.ej_blk, &S.ej_grp})
             release(*b);
         release(S.h_blocks);
         release(S.h_counts);

@@ -66,6 +66,7 @@ static void print_anno_help() {
             "-u        --ubam output uncompressed bam\n"
             "-c        --clip hard-clip the artifacts in the same pass (what `fade out -c` makes of the annotated file)\n"
             "        --extract PATH: also write what `fade extract` makes of the annotated file (one mapped record per artifact side), in the same pass\n"
+            "          --eject drop the artifact reads in the same pass, and on name-sorted input every read that shares their name (what `fade out` makes of the annotated file)\n"
             "          --gpus number of MI355X devices, one process each on its own range of the input (default 1)\n"
             "    --out-shards with --gpus N: every device writes a complete file PREFIX.<k>.bam (.sam), nothing is merged\n"
             "         --batch records per device batch (default 262144)\n"
@@ -79,11 +80,12 @@ static void print_anno_help() {
 struct Opts {
     int threads = 0, floor_len = 5, window = 300, gpus = 1, batch = 262144;
     bool bam = false, ubam = false, help = false, stats = false, timing = false, clip = false;
+    bool eject = false;  // --eject: plain `fade out` (filter.d:209-265) in the same pass
     std::vector<std::string> pos;
     std::string out_shards;  // --out-shards PREFIX (with --gpus N)
     std::string stats_tsv, clip_tsv;  // --stats-tsv PATH, --clip-tsv PATH: the stats.d / noclip.d reports of this run
     std::string extract;  // --extract PATH: `fade extract`'s records of this run's artifact calls, in the output's format
-    std::string seen;  // one letter per option met: t m w b u c h g(pus) B(atch) s(tats) T(iming) S(hards) X (--extract)
+    std::string seen;  // one letter per option met: t m w b u c h g(pus) B(atch) s(tats) T(iming) S(hards) X (--extract) E (--eject)
 };
 
 // std.getopt with config.bundling: short flags bundle (-bu), values attach (-w100, -w 100, --window-size=100)
@@ -147,6 +149,11 @@ static bool parse_opts(int argc, char **argv, Opts &o, std::string &err) {
             else if (name == "stats") { o.seen += 's'; o.stats = true; }
             else if (name == "timing") { o.seen += 'T'; o.timing = true; }
             else if (name == "clip") { o.seen += 'c'; o.clip = true; }
+            else if (name == "eject") {  // (a flag: std.getopt also takes --eject=true / --eject=false)
+                o.seen += 'E';
+                if (has_val && val != "true" && val != "false") { err = "Invalid value for option --eject: " + val; return false; }
+                o.eject = !has_val || val == "true";
+            }
             else if (name == "help") o.help = true;
             else { err = "Unrecognized option --" + name; return false; }
         } else if (a.size() > 1 && a[0] == '-' && a != "-") {
@@ -1333,6 +1340,60 @@ static int annotate_lanes_main(const std::string &cl, const Opts &o, bool *fall_
     return 0;
 }
 
+static int numerically_aware_cmp(std::string a, std::string b);
+
+// `fade annotate --eject`: filter.d:216-220 — the first ten records decide whether the input looks name-sorted (annotate keeps
+// names and order, so these are the names `fade out` would see); the matching line of filter.d:218 / 248 is printed once
+static bool eject_mode_grouped(const std::vector<std::string> &first_names) {
+    bool sorted = true;
+    for (size_t k = 1; k < std::min<size_t>(first_names.size(), 10); k++)
+        if (numerically_aware_cmp(first_names[k], first_names[k - 1]) < 0) sorted = false;
+    if (sorted) fprintf(stderr, "[W::fade-out] Output looks name-sorted, ejecting all reads with same readname if any have an artifact\n");
+    else fprintf(stderr, "[W::fade-out] Output doesn't look name-sorted, ejecting by only reads with an artifact\n");
+    return sorted;
+}
+
+// filter.d:221-265 on the host pipeline's writer side, by the batches' rs (this run's, never an rs tag a record brought):
+// the records of a chunk come in with their tags on, the ones that stay go to `out`.  The mode is decided when ten records
+// have been seen (or the input has ended); in grouped mode the last open group is held across chunks and flushed at the end.
+struct Ejector {
+    int mode = -1;  // -1: not decided yet, 0: record by record, 1: name groups
+    std::vector<std::pair<Rec, bool>> waiting;  // records seen before the decision
+    std::vector<Rec> group;
+    bool group_art = false;
+    void flush_group(std::vector<Rec> &out) {
+        if (!group_art)
+            for (Rec &r : group) out.push_back(std::move(r));
+        group.clear();
+        group_art = false;
+    }
+    void take(Rec &&r, bool art, std::vector<Rec> &out) {
+        if (mode == 0) {
+            if (!art) out.push_back(std::move(r));
+            return;
+        }
+        if (!group.empty() && strcmp(group.back().qname(), r.qname()) != 0) flush_group(out);
+        group.push_back(std::move(r));
+        group_art |= art;
+    }
+    void decide(std::vector<Rec> &out) {
+        std::vector<std::string> names;
+        for (size_t k = 0; k < std::min<size_t>(waiting.size(), 10); k++) names.push_back(waiting[k].first.qname());
+        mode = eject_mode_grouped(names) ? 1 : 0;
+        for (auto &w : waiting) take(std::move(w.first), w.second, out);
+        waiting.clear();
+    }
+    void add(Rec &&r, bool art, std::vector<Rec> &out) {
+        if (mode >= 0) { take(std::move(r), art, out); return; }
+        waiting.emplace_back(std::move(r), art);
+        if (waiting.size() >= 10) decide(out);
+    }
+    void finish(std::vector<Rec> &out) {
+        if (mode < 0) decide(out);
+        flush_group(out);
+    }
+};
+
 // `fade annotate -b in.bam ref.fa` with the whole file path on the device (fadehip_bam_*): this process reads compressed
 // bytes and writes compressed bytes; inflate, framing, annotateTask, the tags and deflate are kernels.  Three threads
 // around the library's two halves: [reader: file -> pinned buffers, cut at BGZF member boundaries] -> [this thread:
@@ -1361,11 +1422,17 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
     Header hdr;
     uint64_t coff = 0;
     uint32_t first_rec = 0;
+    std::vector<std::string> eject_names;  // --eject: the names of the first ten records
     try {
         Reader rd(path, &pool);
         if (!rd.is_bam()) return 1;
         hdr = rd.header();
         const size_t hdr_bytes = rd.bam_header_bytes();
+        if (o.eject) {  // the front of the file is inflated here anyway: on to the tenth record
+            std::vector<Rec> first;
+            rd.read_chunk(first, 10);
+            for (const Rec &r : first) eject_names.push_back(r.qname());
+        }
         uint64_t at = 0, cum = 0;
         if (lane.on) {
             coff = lane.range.coff_start;
@@ -1389,6 +1456,7 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
     *fall_back = false;
     if (o.timing) fprintf(stderr, "[timing] since process start %.3f s (annotate begins; file path on the device)\n", since_process_start());
     if (!lane.on) fprintf(stderr, "[W::fade annotate] Output SAM/BAM will not be sorted (regardless of prior sorting)\n");
+    const bool eject_grouped = o.eject && eject_mode_grouped(eject_names);
     // a lane reads the members in front of coff_end whole and, of the member AT coff_end, the end_rec bytes in front of the next
     // lane's first record
     uint64_t read_end = (uint64_t)sb.st_size;
@@ -1457,6 +1525,7 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
             cfg.flags = o.ubam ? FADEHIP_BAM_STORED : 0;  // -u: uncompressed BGZF (util.d:65-76, SAMWriterTypes.UBAM)
             if (o.clip) cfg.flags |= FADEHIP_BAM_CLIP;    // -c: the artifact calls leave hard-clipped
             if (!o.extract.empty()) cfg.flags |= FADEHIP_BAM_EXTRACT;  // --extract: every call leaves its extract records too
+            if (o.eject) cfg.flags |= eject_grouped ? FADEHIP_BAM_EJECT | FADEHIP_BAM_EJECT_GROUPS : FADEHIP_BAM_EJECT;  // --eject
             if (fadehip_bam_open(ctx, &cfg, &st)) { create_err = fadehip_last_error(ctx); return 1; }
             const size_t call_bytes = host_inflate ? chunk : std::min<size_t>(chunk * 3, (size_t)1 << 30);
             if (!(getenv("FADE_BAM_PREPARE") && atoi(getenv("FADE_BAM_PREPARE")) == 0) && fadehip_bam_prepare(st, call_bytes)) { create_err = fadehip_last_error(ctx); return 1; }
@@ -2071,6 +2140,8 @@ static int annotate_main(const std::string &cl, const Opts &o) {
             xwriter.reset(new Writer(xfile.f, fmt, hdr, &pool));
         }
 
+        Ejector ejector;  // --eject: the writer stage's
+        std::vector<Rec> kept;
         StageThreads wstage;  // declared after the writer it uses: joined before the writer goes away
         wstage.unblock = [&] {
             abort_stages = true;
@@ -2087,8 +2158,32 @@ static int annotate_main(const std::string &cl, const Opts &o) {
                     ck_tags.stop();
                     ck_write.start();
                     if (xwriter && !xrecs.empty()) xwriter->write(xrecs);
-                    writer.write_block(c->blk, c->bout);
+                    if (o.eject) {
+                        // the chunk's records with their tags on, then filter.d:221-265 by the batch's rs
+                        const size_t n = c->n_records();
+                        std::vector<uint8_t> art(n, 0);
+                        for (size_t k = 0; k < c->sent.size(); k++) art[c->sent[k]] = (c->rs_sent[k] & 6) != 0;
+                        std::vector<int32_t> own(n, -1);
+                        for (size_t k = 0; k < c->bout.owned.size(); k++) own[c->bout.owned[k].first] = (int32_t)k;
+                        kept.clear();
+                        for (size_t i = 0; i < n; i++) {
+                            Rec r;
+                            if (own[i] >= 0) r = std::move(c->bout.owned[(size_t)own[i]].second);
+                            else {
+                                const uint8_t *b = c->blk.buf.data() + c->blk.off[i], *sx = c->bout.sfx.data() + c->bout.sfx_off[i];
+                                r.d.assign(b, b + c->blk.len[i]);
+                                r.d.insert(r.d.end(), sx, sx + (c->bout.sfx_off[i + 1] - c->bout.sfx_off[i]));
+                            }
+                            ejector.add(std::move(r), art[i] != 0, kept);
+                        }
+                        writer.write(kept);
+                    } else writer.write_block(c->blk, c->bout);
                     ck_write.stop();
+                }
+                if (o.eject) {  // the group still open, or an input of fewer than ten records
+                    kept.clear();
+                    ejector.finish(kept);
+                    writer.write(kept);
                 }
             } catch (const std::exception &e) {
                 set_stage_err(e.what());
@@ -2659,7 +2754,7 @@ int main(int argc, char **argv) {
             fprintf(stderr, "std.getopt.GetOptException: %s\n", err.c_str());
             return 1;
         }
-        if (!options_allowed(o, "tmwbucgBsTSPQX")) return 1;
+        if (!options_allowed(o, "tmwbucgBsTSPQXE")) return 1;
         // app.d:84-89: helpWanted | args.length < 3 (args = prog, "annotate", positionals...)
         if (o.help || o.pos.size() < 2) { print_anno_help(); return 0; }
         if (o.pos.size() < 3) {  // the reference indexes args[2] and dies; say why instead
@@ -2680,6 +2775,21 @@ int main(int argc, char **argv) {
         if (reports && o.clip) {  // the reports describe the unclipped records
             fprintf(stderr, "[E::fade-annotate] %s describes unclipped records: not with --clip\n", !o.stats_tsv.empty() ? "--stats-tsv" : "--clip-tsv");
             return 1;
+        }
+        if (o.eject) {  // refused here, before any device is opened
+            if (o.clip) {
+                fprintf(stderr, "[E::fade-annotate] --eject drops the artifact reads and --clip keeps them hard-clipped: `fade out` does one or the other\n");
+                return 1;
+            }
+            if (reports) {
+                fprintf(stderr, "[E::fade-annotate] %s describes records that --eject drops from the output: not with --eject\n", !o.stats_tsv.empty() ? "--stats-tsv" : "--clip-tsv");
+                return 1;
+            }
+            if (o.gpus > 1 || !o.out_shards.empty()) {
+                fprintf(stderr, "[E::fade-annotate] --eject goes with one device: not with %s (the devices' ranges of the input would cut through name groups)\n",
+                        o.gpus > 1 ? "--gpus N > 1" : "--out-shards");
+                return 1;
+            }
         }
         if (!o.extract.empty()) {  // one file, written in record order by one writer — refused here, before any device is opened
             if (o.gpus > 1 || !o.out_shards.empty()) {

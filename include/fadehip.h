@@ -171,6 +171,17 @@ int fadehip_extract_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, cons
                           const int32_t *art_tid /* [2n] */, const int64_t *art_pos /* [2n] */, const int64_t *cig_off /* [2n + 1] */,
                           const uint32_t *cig, uint8_t *out, int64_t out_cap, int64_t *out_off /* [2n + 1] */);
 
+/* filter.d:209-265 (plain `fade out`) over n BAM records (block_size first, as in a file), concatenated, rec_off holding
+ * n + 1 offsets: keep[k] = 1 when record k would be written, 0 when it is ejected.  grouped == 0: a record is ejected when
+ * rs[k] & 6.  grouped != 0: the records are taken as name-sorted — maximal runs of consecutive records with equal names
+ * (l_read_name and every name byte) are groups, and a group is ejected as a whole when one of its records has rs & 6; the
+ * work per record does not grow with a group's length.  Whether a file is name-sorted is the caller's to decide (`fade out`
+ * looks at its first ten records).  The kernels are the ones the file path runs under FADEHIP_BAM_EJECT /
+ * FADEHIP_BAM_EJECT_GROUPS; there rs is the run's own result.  A record whose block_size or l_read_name does not fit its
+ * bytes: FADEHIP_E_INVALID, with the record's index in fadehip_last_error.  Synchronous, on a stream and buffers of its own. */
+int fadehip_eject_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const int64_t *rec_off, const uint8_t *rs,
+                        int grouped, uint8_t *keep /* [n] out */);
+
 /* ------------------------------------------------------ Level 2: annotateTask over a batch -- */
 /* Upload the indexed FASTA once (what IndexedFastaFile + fetchSequence serve, analysis.d:63).
  * seqs[c] holds lengths[c] ASCII residues (any case; upper-cased on device as analysis.d:63 does).
@@ -373,7 +384,18 @@ typedef struct fadehip_bam_config {
                                    * FADEHIP_BAM_EXTRACT: every call also builds `fade extract`'s records of its artifact calls
                                    * (`fade annotate --extract`), one per set artifact bit of rs, left before right, in input
                                    * order, from the record as it came in (with FADEHIP_BAM_CLIP too) and this run's alignment:
-                                   * fadehip_bam_back_extract hands them out.  Combines with the other three */
+                                   * fadehip_bam_back_extract hands them out.  Combines with the other three;
+                                   * FADEHIP_BAM_EJECT: records called artifacts are not written (`fade annotate --eject` on input
+                                   * that is not name-sorted: what plain `fade out` would make of the annotated file, in the same
+                                   * pass — by this run's rs, never by an rs tag read back).  FADEHIP_BAM_EJECT_GROUPS (implies
+                                   * FADEHIP_BAM_EJECT): name-sorted input — neither is any record that shares an ejected record's
+                                   * name with it in one run of consecutive records (mates, supplementary and secondary lines).
+                                   * The caller decides which (`fade out`: the first ten names are non-decreasing); a name group
+                                   * is never split between two calls: a call that is not the last gives its last group back to
+                                   * the next (a call that is one group yields nothing), and a group longer than a call can hold
+                                   * is FADEHIP_E_UNSUPPORTED.  Both combine with STORED, NO_OUTPUT and EXTRACT (the extract
+                                   * records are built of the ejected artifact calls all the same); with FADEHIP_BAM_CLIP,
+                                   * fadehip_bam_open returns FADEHIP_E_INVALID.  fadehip_bam_totals is not changed by them */
     const char *const *ref_names; /* [n_ref] NUL-terminated */
     uint32_t first_record;        /* payload bytes of the first member passed to front that precede the first record */
     uint32_t tail_trim;           /* payload bytes at the END of the last member (front's last call) that are not this stream's:
@@ -384,6 +406,8 @@ typedef struct fadehip_bam_config {
 #define FADEHIP_BAM_NO_OUTPUT 2
 #define FADEHIP_BAM_CLIP 4
 #define FADEHIP_BAM_EXTRACT 8
+#define FADEHIP_BAM_EJECT 16
+#define FADEHIP_BAM_EJECT_GROUPS 32
 int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_bam_stream **out);
 int fadehip_bam_prepare(fadehip_bam_stream *st, size_t call_bytes);
 int fadehip_bam_front(fadehip_bam_stream *st, const void *members, size_t n_bytes, int last);
@@ -398,6 +422,8 @@ int fadehip_bam_back(fadehip_bam_stream *st, const uint8_t **out, size_t *out_by
 int fadehip_bam_back_extract(fadehip_bam_stream *st, const uint8_t **recs, size_t *n_bytes, int64_t *n_records);
 /* totals so far: the eight Stats.parse counters (stats.d:45-54), records, reads beyond the kernels' limits */
 int fadehip_bam_totals(fadehip_bam_stream *st, int64_t stats[8], int64_t *n_records, int64_t *n_oversize);
+/* FADEHIP_BAM_EJECT: records not written, over the calls back has taken (0 without the flag) */
+int fadehip_bam_ejected(fadehip_bam_stream *st, int64_t *n_ejected);
 void fadehip_bam_close(fadehip_bam_stream *st);
 
 /* Sum counters over the ranks' devices with one ncclAllReduce (RCCL) — single process, one ctx
