@@ -341,6 +341,41 @@ __device__ __forceinline__ uint32_t block_scan_1024(uint32_t v, uint32_t *tmp16,
     return base + inc - v;
 }
 
+constexpr int TAG_BLOCK = 256;  // records per block of the tag-size, extract and eject kernels
+
+// sum of v over a block of TAG_BLOCK threads: the waves by shuffle, then their sums by thread 0 — which alone gets the total
+__device__ __forceinline__ uint64_t block_sum_256(uint64_t v) {
+    __shared__ uint64_t red[TAG_BLOCK / 64];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += (uint64_t)__shfl_xor((long long)v, m, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    uint64_t t = 0;
+    if (threadIdx.x == 0)
+        for (int w = 0; w < TAG_BLOCK / 64; w++) t += red[w];
+    return t;
+}
+
+// one block of 1024 threads: exclusive scan (sum, or MAX: running maximum) of n_blocks block sums -> base, the total -> *total
+template <class T, bool MAX>
+__device__ __forceinline__ void scan_block_sums(const T *sums, T *base, uint32_t n_blocks, T *total) {
+    __shared__ T part[1024];
+    const int tid = threadIdx.x;
+    const uint32_t per = (n_blocks + 1023u) / 1024u, lo = (uint32_t)tid * per, hi = min(lo + per, n_blocks);
+    T s = 0;
+    for (uint32_t k = lo; k < hi; k++) s = MAX ? max(s, sums[k]) : s + sums[k];
+    part[tid] = s;
+    __syncthreads();
+    if (tid == 0) {
+        T run = 0;
+        for (int k = 0; k < 1024; k++) { const T t = part[k]; part[k] = run; run = MAX ? max(run, t) : run + t; }
+        if (total) *total = run;
+    }
+    __syncthreads();
+    T at = part[tid];
+    for (uint32_t k = lo; k < hi; k++) { base[k] = at; at = MAX ? max(at, sums[k]) : at + sums[k]; }
+}
+
 // thread per record: layout check, anno.d:61-65 (does the record go to the device?), SA, our own tags; block sums
 // (The launch is sized from an ESTIMATE of the records the bytes hold — a bound from the bytes alone would be eight times
 // too many workgroups, each waiting for a wave slot beside the compressor; the grid strides over the blocks of PACK_BLOCK
@@ -866,8 +901,6 @@ struct TagArgs {
     uint64_t out_base;         // bytes of O in front of this batch
     uint8_t *o;
 };
-constexpr int TAG_BLOCK = 256;
-
 __device__ __forceinline__ const fadehip_aln *aln_of(const TagArgs &a, int32_t sent, uint8_t *rs) {
     *rs = 0;
     if (sent < 0) return nullptr;
@@ -878,6 +911,7 @@ __device__ __forceinline__ const fadehip_aln *aln_of(const TagArgs &a, int32_t s
 
 // CLIP (FADEHIP_BAM_CLIP) is a parameter of the kernels themselves, not of a body they share: <false> is, instruction for
 // instruction, the kernel of before the flag existed (a shared body inlined into two kernels was not).
+// (Likewise it keeps its own block sum: with block_sum_256 inlined, <false>'s adds came out with their operands swapped.)
 template <bool CLIP>
 __global__ __launch_bounds__(TAG_BLOCK) void bam_tag_size_kernel(TagArgs a) {
     __shared__ uint64_t red[TAG_BLOCK / 64];
@@ -917,21 +951,7 @@ __global__ __launch_bounds__(TAG_BLOCK) void bam_tag_size_kernel(TagArgs a) {
 }
 
 __global__ __launch_bounds__(1024) void bam_tag_scan_kernel(TagArgs a, uint32_t n_blocks) {
-    __shared__ uint64_t part[1024];
-    const int tid = threadIdx.x;
-    const uint32_t per = (n_blocks + 1023u) / 1024u, lo = (uint32_t)tid * per, hi = min(lo + per, n_blocks);
-    uint64_t s = 0;
-    for (uint32_t k = lo; k < hi; k++) s += a.blk_sums[k];
-    part[tid] = s;
-    __syncthreads();
-    if (tid == 0) {
-        uint64_t run = 0;
-        for (int k = 0; k < 1024; k++) { const uint64_t t = part[k]; part[k] = run; run += t; }
-        a.counts->out_bytes = run;
-    }
-    __syncthreads();
-    uint64_t at = part[tid];
-    for (uint32_t k = lo; k < hi; k++) { a.blk_base[k] = at; at += a.blk_sums[k]; }
+    scan_block_sums<uint64_t, false>(a.blk_sums, a.blk_base, n_blocks, &a.counts->out_bytes);
 }
 
 // Sixteen lanes per record, four records per wavefront at a time: the body moved as (unaligned) dwords by the sixteen, the
@@ -1123,7 +1143,6 @@ __device__ __forceinline__ void extract_write(const RecHdr &r, int32_t tid, int6
 // Thread per record of a TAG_BLOCK block, so that the sizes feed bam_tag_scan_kernel as the tag sizes do and the records
 // come out in input order; a record that is no artifact call costs its thread two index words and nothing of the record.
 __global__ __launch_bounds__(TAG_BLOCK) void bam_extract_size_kernel(TagArgs a) {
-    __shared__ uint64_t red[TAG_BLOCK / 64];
     const uint32_t r1 = min(a.r1_cap, a.counts_in->n_records);
     const uint32_t i = a.r0 + blockIdx.x * TAG_BLOCK + threadIdx.x;
     uint64_t sz = 0;  // bytes, and the number of records above bit 40
@@ -1137,13 +1156,8 @@ __global__ __launch_bounds__(TAG_BLOCK) void bam_extract_size_kernel(TagArgs a) 
         }
         a.out_size[i - a.r0] = (uint32_t)sz;
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) sz += (uint64_t)__shfl_xor((long long)sz, m, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sz;
-    __syncthreads();
+    const uint64_t t = block_sum_256(sz);
     if (threadIdx.x == 0) {
-        uint64_t t = 0;
-        for (int w = 0; w < TAG_BLOCK / 64; w++) t += red[w];
         a.blk_sums[blockIdx.x] = t & ((1ull << 40) - 1ull);
         if (t >> 40) atomicAdd(&a.counts->n_records, (uint32_t)(t >> 40));
     }
@@ -1328,20 +1342,7 @@ __global__ __launch_bounds__(TAG_BLOCK) void bam_eject_head_kernel(EjectArgs a) 
 
 // one block: exclusive max-scan of the blocks' last group starts, as bam_tag_scan_kernel sums the blocks' bytes
 __global__ __launch_bounds__(1024) void bam_eject_scan_kernel(EjectArgs a, uint32_t n_blocks) {
-    __shared__ uint32_t part[1024];
-    const int tid = threadIdx.x;
-    const uint32_t per = (n_blocks + 1023u) / 1024u, lo = (uint32_t)tid * per, hi = min(lo + per, n_blocks);
-    uint32_t m = 0;
-    for (uint32_t k = lo; k < hi; k++) m = max(m, a.blk_head[k]);
-    part[tid] = m;
-    __syncthreads();
-    if (tid == 0) {
-        uint32_t run = 0;
-        for (int k = 0; k < 1024; k++) { const uint32_t t = part[k]; part[k] = run; run = max(run, t); }
-    }
-    __syncthreads();
-    uint32_t at = part[tid];
-    for (uint32_t k = lo; k < hi; k++) { a.blk_carry[k] = at; at = max(at, a.blk_head[k]); }
+    scan_block_sums<uint32_t, true>(a.blk_head, a.blk_carry, n_blocks, nullptr);
 }
 
 // thread per record: the group start is final now; an artifact call leaves its mark at the group's first record
@@ -1360,7 +1361,6 @@ __global__ __launch_bounds__(TAG_BLOCK) void bam_eject_mark_kernel(EjectArgs a) 
 // thread per record: the decision, applied.  The file path: an ejected record gets out_size 0 and INFO_BAD, and the block's
 // bytes are summed again — in front of bam_tag_scan_kernel, so that the offsets never hold it; fadehip_eject_batch: keep[].
 __global__ __launch_bounds__(TAG_BLOCK) void bam_eject_apply_kernel(EjectArgs a, int grouped) {
-    __shared__ uint64_t red[TAG_BLOCK / 64];
     const uint32_t i = blockIdx.x * TAG_BLOCK + threadIdx.x;
     uint64_t sz = 0;  // bytes, and the number of ejected records above bit 40
     if (i < a.n) {
@@ -1375,13 +1375,8 @@ __global__ __launch_bounds__(TAG_BLOCK) void bam_eject_apply_kernel(EjectArgs a,
         }
     }
     if (!a.out_size) return;  // (uniform)
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) sz += (uint64_t)__shfl_xor((long long)sz, m, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sz;
-    __syncthreads();
+    const uint64_t t = block_sum_256(sz);
     if (threadIdx.x == 0) {
-        uint64_t t = 0;
-        for (int w = 0; w < TAG_BLOCK / 64; w++) t += red[w];
         a.blk_sums[blockIdx.x] = t & ((1ull << 40) - 1ull);
         if (t >> 40) atomicAdd(&a.counts->n_ejected, (uint32_t)(t >> 40));
     }

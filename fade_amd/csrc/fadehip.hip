@@ -176,6 +176,14 @@ struct InflateLane {
     PinBuf h_status;
 };
 
+// fadehip_clip_batch, fadehip_extract_batch and fadehip_eject_batch: one stream, made when the first of them is called, and
+// one set of buffers (kept between calls, grow only); a call of any of the three holds mu from its uploads to its last wait
+struct BatchLane {
+    std::mutex mu;
+    hipStream_t stream = nullptr;
+    DevBuf in, meta, work, out;  // the records | offsets, rs and the call's other arrays | sizes, or eject's group arrays | output bytes
+};
+
 }  // namespace
 
 struct fadehip_ctx {
@@ -192,18 +200,7 @@ struct fadehip_ctx {
     hipStream_t stats_stream = nullptr;
     DevBuf st_q, st_r, st_work, st_out, st_scratch;
     std::mutex stats_mu;
-    // fadehip_clip_batch: likewise
-    hipStream_t clip_stream = nullptr;
-    DevBuf cl_in, cl_meta, cl_size, cl_out;
-    std::mutex clip_mu;
-    // fadehip_extract_batch: likewise
-    hipStream_t extract_stream = nullptr;
-    DevBuf ex_in, ex_meta, ex_size, ex_out;
-    std::mutex extract_mu;
-    // fadehip_eject_batch: likewise
-    hipStream_t eject_stream = nullptr;
-    DevBuf ej_in, ej_meta, ej_work;
-    std::mutex eject_mu;
+    BatchLane batch;  // the three record-batch entry points share it: they leave the slots and the stats lane alone, not each other
     int n_contigs = 0;
     std::vector<int64_t> h_contig_len;
     std::vector<uint64_t> h_contig_base;
@@ -1300,6 +1297,105 @@ int launch_inflate(fadehip_ctx *ctx, hipStream_t st, const bgzf::InflateArgs &a)
     return 0;
 }
 
+// ---- the record-batch entry points: fadehip_clip_batch, fadehip_extract_batch, fadehip_eject_batch on ctx->batch
+// What their kernels dereference through, checked on the host record by record: block_size against the offsets and the name
+// against block_size; with `fields`, n_cigar_op and l_seq as well.  extra(k) is what the caller alone checks of record k.
+template <class Extra>
+int check_records(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const int64_t *rec_off, bool fields, Extra extra) {
+    for (int32_t k = 0; k < n; k++) {
+        const int64_t len = rec_off[k + 1] - rec_off[k];
+        if (len < 0) return set_err(ctx, FADEHIP_E_INVALID, "offsets must be non-negative and non-decreasing (record %d)", k);
+        const uint8_t *p = recs + rec_off[k];
+        uint32_t bs = 0, ncig = 0;
+        int32_t lseq = 0;
+        if (len >= 36) {
+            memcpy(&bs, p, 4);
+            memcpy(&lseq, p + 20, 4);
+            ncig = (uint32_t)p[16] | ((uint32_t)p[17] << 8);
+        }
+        const bool whole = len >= 36 && len <= ((int64_t)1 << 29) && (int64_t)bs + 4 == len && p[12] != 0;
+        const bool name_fits = whole && 36 + (int64_t)p[12] <= len;
+        const bool fields_fit = whole && lseq >= 0 && 36ull + p[12] + 4ull * ncig + ((uint64_t)lseq + 1) / 2 + (uint64_t)lseq <= (uint64_t)len;
+        if (fields && !fields_fit)
+            return set_err(ctx, FADEHIP_E_INVALID, "record %d is malformed (block_size, l_read_name, n_cigar_op and l_seq must fit its %lld bytes)", k, (long long)len);
+        if (!fields && !name_fits)
+            return set_err(ctx, FADEHIP_E_INVALID, "record %d is malformed (block_size and l_read_name must fit its %lld bytes)", k, (long long)len);
+        if (const int rc = extra(k)) return rc;
+    }
+    return 0;
+}
+
+// The lane made ready for a call (whose caller holds its lock): stream, buffers, and on the device the records, their offsets
+// from record 0 (`off`, u64 [n + 1], at the start of meta) and rs at meta + m_rs; what lies between is the caller's, copied behind.
+int batch_upload(fadehip_ctx *ctx, BatchLane &L, int32_t n, const uint8_t *recs, const int64_t *rec_off, const uint8_t *rs,
+                 size_t m_rs, size_t meta_bytes, size_t work_bytes, std::vector<uint64_t> &off) {
+    const size_t in_bytes = (size_t)(rec_off[n] - rec_off[0]);
+    off.resize((size_t)n + 1);
+    for (int32_t k = 0; k <= n; k++) off[(size_t)k] = (uint64_t)(rec_off[k] - rec_off[0]);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (!L.stream) HIPCHK(ctx, hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
+    int rc;
+    if ((rc = reserve(ctx, L.in, in_bytes + 8)) || (rc = reserve(ctx, L.meta, meta_bytes)) || (rc = reserve(ctx, L.work, work_bytes))) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(L.in.p, recs + rec_off[0], in_bytes, hipMemcpyHostToDevice, L.stream));
+    HIPCHK(ctx, hipMemcpyAsync(L.meta.p, off.data(), 8 * ((size_t)n + 1), hipMemcpyHostToDevice, L.stream));
+    HIPCHK(ctx, hipMemcpyAsync((uint8_t *)L.meta.p + m_rs, rs, (size_t)n, hipMemcpyHostToDevice, L.stream));
+    return 0;
+}
+
+// Clip and extract behind their uploads: size kernel (a thread per element), the sizes to the host and summed there into
+// off [cnt + 1], the out_cap check, the output reserved, the offsets up to a.out_off, write kernel (sixteen lanes per element),
+// the bytes to `out`.  out_off gets the offsets — with off_first also when out is too small (clip says what it would have
+// taken; extract does not).  No bytes: no second half (extract's rule; clip never gets there, a record leaves with >= 36).
+template <class Args>
+int size_then_write(fadehip_ctx *ctx, BatchLane &L, Args &a, size_t cnt, void (*size_kernel)(Args), void (*write_kernel)(Args),
+                    const char *what, bool off_first, std::vector<uint64_t> &off, uint8_t *out, int64_t out_cap, int64_t *out_off) {
+    hipStream_t st = L.stream;
+    a.out_size = (uint32_t *)L.work.p;
+    a.out = nullptr;
+    hipLaunchKernelGGL(size_kernel, dim3(((unsigned)cnt + 255u) / 256u), dim3(256), 0, st, a);
+    HIPCHK(ctx, hipGetLastError());
+    std::vector<uint32_t> sizes(cnt);
+    HIPCHK(ctx, hipMemcpyAsync(sizes.data(), a.out_size, 4 * cnt, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    uint64_t run = 0;
+    for (size_t q = 0; q < cnt; q++) {
+        off[q] = run;
+        run += sizes[q];
+    }
+    off[cnt] = run;
+    const size_t out_bytes = (size_t)run;
+    const bool fits = (int64_t)out_bytes <= out_cap;
+    if (fits || off_first)
+        for (size_t q = 0; q <= cnt; q++) out_off[q] = (int64_t)off[q];
+    if (!fits) return set_err(ctx, FADEHIP_E_INVALID, "the %s records take %lld bytes, out holds %lld", what, (long long)out_bytes, (long long)out_cap);
+    if (!out_bytes) return 0;
+    if (const int rc = reserve(ctx, L.out, out_bytes + 8)) return rc;
+    HIPCHK(ctx, hipMemcpyAsync((void *)a.out_off, off.data(), 8 * (cnt + 1), hipMemcpyHostToDevice, st));
+    a.out = (uint8_t *)L.out.p;
+    hipLaunchKernelGGL(write_kernel, dim3(((unsigned)cnt + 15u) / 16u), dim3(256), 0, st, a);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(out, a.out, out_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    return 0;
+}
+
+// The eject kernels on a stream, for fadehip_eject_batch and the file path: with `grouped` the groups' marks cleared, every
+// record's group start, the blocks' carries and the marks; then the decision, applied.
+int enqueue_eject(fadehip_ctx *ctx, hipStream_t st, bam::EjectArgs &a, uint32_t ntb, bool grouped) {
+    if (grouped) {
+        HIPCHK(ctx, hipMemsetAsync(a.grp, 0, 4 * (size_t)a.n, st));
+        hipLaunchKernelGGL(bam::bam_eject_head_kernel, dim3(ntb), dim3(bam::TAG_BLOCK), 0, st, a);
+        HIPCHK(ctx, hipGetLastError());
+        hipLaunchKernelGGL(bam::bam_eject_scan_kernel, dim3(1), dim3(1024), 0, st, a, ntb);
+        HIPCHK(ctx, hipGetLastError());
+        hipLaunchKernelGGL(bam::bam_eject_mark_kernel, dim3(ntb), dim3(bam::TAG_BLOCK), 0, st, a);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    hipLaunchKernelGGL(bam::bam_eject_apply_kernel, dim3(ntb), dim3(bam::TAG_BLOCK), 0, st, a, grouped ? 1 : 0);
+    HIPCHK(ctx, hipGetLastError());
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1467,12 +1563,8 @@ void fadehip_destroy(fadehip_ctx *ctx) {
     for (DevBuf *b : {&ctx->l1_q, &ctx->l1_r, &ctx->l1_qn, &ctx->l1_rn, &ctx->l1_bad, &ctx->l1_work, &ctx->l1_aln}) release(*b);
     for (DevBuf *b : {&ctx->st_q, &ctx->st_r, &ctx->st_work, &ctx->st_out, &ctx->st_scratch}) release(*b);
     if (ctx->stats_stream) (void)hipStreamDestroy(ctx->stats_stream);
-    for (DevBuf *b : {&ctx->cl_in, &ctx->cl_meta, &ctx->cl_size, &ctx->cl_out}) release(*b);
-    if (ctx->clip_stream) (void)hipStreamDestroy(ctx->clip_stream);
-    for (DevBuf *b : {&ctx->ex_in, &ctx->ex_meta, &ctx->ex_size, &ctx->ex_out}) release(*b);
-    if (ctx->extract_stream) (void)hipStreamDestroy(ctx->extract_stream);
-    for (DevBuf *b : {&ctx->ej_in, &ctx->ej_meta, &ctx->ej_work}) release(*b);
-    if (ctx->eject_stream) (void)hipStreamDestroy(ctx->eject_stream);
+    for (DevBuf *b : {&ctx->batch.in, &ctx->batch.meta, &ctx->batch.work, &ctx->batch.out}) release(*b);
+    if (ctx->batch.stream) (void)hipStreamDestroy(ctx->batch.stream);
     release(ctx->contig_len);
     release(ctx->contig_base);
     if (g_err_ctx == ctx) g_err_ctx = nullptr;
@@ -1772,75 +1864,27 @@ int fadehip_clip_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const i
     if (rec_off[0] < 0) return set_err(ctx, FADEHIP_E_INVALID, "offsets must be non-negative and non-decreasing (record 0)");
     out_off[0] = 0;
     if (n == 0) return 0;
-    // what the kernels dereference through is checked here: block_size against the offsets, the fields against block_size
-    for (int32_t k = 0; k < n; k++) {
-        const int64_t len = rec_off[k + 1] - rec_off[k];
-        if (len < 0) return set_err(ctx, FADEHIP_E_INVALID, "offsets must be non-negative and non-decreasing (record %d)", k);
-        const uint8_t *p = recs + rec_off[k];
-        uint32_t bs = 0, ncig = 0;
-        int32_t lseq = 0;
-        if (len >= 36) {
-            memcpy(&bs, p, 4);
-            memcpy(&lseq, p + 20, 4);
-            ncig = (uint32_t)p[16] | ((uint32_t)p[17] << 8);
-        }
-        if (len < 36 || len > ((int64_t)1 << 29) || (int64_t)bs + 4 != len || lseq < 0 || p[12] == 0 ||
-            36ull + p[12] + 4ull * ncig + ((uint64_t)lseq + 1) / 2 + (uint64_t)lseq > (uint64_t)len)
-            return set_err(ctx, FADEHIP_E_INVALID, "record %d is malformed (block_size, l_read_name, n_cigar_op and l_seq must fit its %lld bytes)", k, (long long)len);
-        if (trim_left[k] < 0 || trim_right[k] < 0) return set_err(ctx, FADEHIP_E_INVALID, "record %d: negative trim length", k);
-    }
-    const size_t in_bytes = (size_t)(rec_off[n] - rec_off[0]);
-    std::vector<uint64_t> off((size_t)n + 1);
-    for (int32_t k = 0; k <= n; k++) off[(size_t)k] = (uint64_t)(rec_off[k] - rec_off[0]);
-    std::lock_guard<std::mutex> lk(ctx->clip_mu);
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (!ctx->clip_stream) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->clip_stream, hipStreamNonBlocking));
-    hipStream_t st = ctx->clip_stream;
-    // cl_meta: in_off [n + 1] u64 | out_off [n + 1] u64 | trim_l [n] u32 | trim_r [n] u32 | rs [n] u8
-    const size_t m_out = 8 * ((size_t)n + 1), m_tl = 2 * m_out, m_tr = m_tl + 4 * (size_t)n, m_rs = m_tr + 4 * (size_t)n;
+    const auto trims = [&](int32_t k) { return trim_left[k] < 0 || trim_right[k] < 0 ? set_err(ctx, FADEHIP_E_INVALID, "record %d: negative trim length", k) : 0; };
     int rc;
-    if ((rc = reserve(ctx, ctx->cl_in, in_bytes + 8)) || (rc = reserve(ctx, ctx->cl_meta, m_rs + (size_t)n + 8)) ||
-        (rc = reserve(ctx, ctx->cl_size, 4 * (size_t)n)))
-        return rc;
-    uint8_t *meta = (uint8_t *)ctx->cl_meta.p;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->cl_in.p, recs + rec_off[0], in_bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(meta, off.data(), m_out, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(meta + m_tl, trim_left, 4 * (size_t)n, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(meta + m_tr, trim_right, 4 * (size_t)n, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(meta + m_rs, rs, (size_t)n, hipMemcpyHostToDevice, st));
+    if ((rc = check_records(ctx, n, recs, rec_off, true, trims))) return rc;
+    BatchLane &L = ctx->batch;
+    std::lock_guard<std::mutex> lk(L.mu);
+    // meta: in_off [n + 1] u64 | out_off [n + 1] u64 | trim_l [n] u32 | trim_r [n] u32 | rs [n] u8;  work: out_size [n] u32
+    const size_t m_out = 8 * ((size_t)n + 1), m_tl = 2 * m_out, m_tr = m_tl + 4 * (size_t)n, m_rs = m_tr + 4 * (size_t)n;
+    std::vector<uint64_t> off;
+    if ((rc = batch_upload(ctx, L, n, recs, rec_off, rs, m_rs, m_rs + (size_t)n + 8, 4 * (size_t)n, off))) return rc;
+    uint8_t *meta = (uint8_t *)L.meta.p;
+    HIPCHK(ctx, hipMemcpyAsync(meta + m_tl, trim_left, 4 * (size_t)n, hipMemcpyHostToDevice, L.stream));
+    HIPCHK(ctx, hipMemcpyAsync(meta + m_tr, trim_right, 4 * (size_t)n, hipMemcpyHostToDevice, L.stream));
     bam::ClipBatchArgs a;
-    a.in = (const uint8_t *)ctx->cl_in.p;
+    a.in = (const uint8_t *)L.in.p;
     a.in_off = (const uint64_t *)meta;
     a.rs = meta + m_rs;
     a.trim_l = (const uint32_t *)(meta + m_tl);
     a.trim_r = (const uint32_t *)(meta + m_tr);
     a.n = (uint32_t)n;
-    a.out_size = (uint32_t *)ctx->cl_size.p;
     a.out_off = (const uint64_t *)(meta + m_out);
-    a.out = nullptr;
-    hipLaunchKernelGGL(bam::clip_batch_size_kernel, dim3(((unsigned)n + 255u) / 256u), dim3(256), 0, st, a);
-    HIPCHK(ctx, hipGetLastError());
-    std::vector<uint32_t> sizes((size_t)n);
-    HIPCHK(ctx, hipMemcpyAsync(sizes.data(), a.out_size, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    uint64_t run = 0;
-    for (int32_t k = 0; k < n; k++) {
-        off[(size_t)k] = run;
-        run += sizes[(size_t)k];
-        out_off[k + 1] = (int64_t)run;
-    }
-    off[(size_t)n] = run;
-    const size_t out_bytes = (size_t)run;
-    if ((int64_t)out_bytes > out_cap)
-        return set_err(ctx, FADEHIP_E_INVALID, "the clipped records take %lld bytes, out holds %lld", (long long)out_bytes, (long long)out_cap);
-    if ((rc = reserve(ctx, ctx->cl_out, out_bytes + 8))) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(meta + m_out, off.data(), m_out, hipMemcpyHostToDevice, st));
-    a.out = (uint8_t *)ctx->cl_out.p;
-    hipLaunchKernelGGL(bam::clip_batch_write_kernel, dim3(((unsigned)n + 15u) / 16u), dim3(256), 0, st, a);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(out, a.out, out_bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    return 0;
+    return size_then_write(ctx, L, a, (size_t)n, bam::clip_batch_size_kernel, bam::clip_batch_write_kernel, "clipped", true, off, out, out_cap, out_off);
 }
 
 // filter.d:209-265 over records the caller brings: bam_device.hpp's eject kernels, the ones of the file path under
@@ -1850,58 +1894,30 @@ int fadehip_eject_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const 
     if (n < 0 || !rec_off || (n > 0 && (!recs || !rs || !keep))) return set_err(ctx, FADEHIP_E_INVALID, "NULL argument");
     if (rec_off[0] < 0) return set_err(ctx, FADEHIP_E_INVALID, "offsets must be non-negative and non-decreasing (record 0)");
     if (n == 0) return 0;
-    // what the kernels dereference through is checked here: block_size against the offsets, the name against block_size
-    for (int32_t k = 0; k < n; k++) {
-        const int64_t len = rec_off[k + 1] - rec_off[k];
-        if (len < 0) return set_err(ctx, FADEHIP_E_INVALID, "offsets must be non-negative and non-decreasing (record %d)", k);
-        const uint8_t *p = recs + rec_off[k];
-        uint32_t bs = 0;
-        if (len >= 36) memcpy(&bs, p, 4);
-        if (len < 36 || len > ((int64_t)1 << 29) || (int64_t)bs + 4 != len || p[12] == 0 || 36 + (int64_t)p[12] > len)
-            return set_err(ctx, FADEHIP_E_INVALID, "record %d is malformed (block_size and l_read_name must fit its %lld bytes)", k, (long long)len);
-    }
-    const size_t in_bytes = (size_t)(rec_off[n] - rec_off[0]);
-    std::vector<uint64_t> off((size_t)n + 1);
-    for (int32_t k = 0; k <= n; k++) off[(size_t)k] = (uint64_t)(rec_off[k] - rec_off[0]);
-    std::lock_guard<std::mutex> lk(ctx->eject_mu);
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (!ctx->eject_stream) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->eject_stream, hipStreamNonBlocking));
-    hipStream_t st = ctx->eject_stream;
-    const uint32_t ntb = ((uint32_t)n + bam::TAG_BLOCK - 1) / bam::TAG_BLOCK;
-    // ej_meta: in_off [n + 1] u64 | rs [n] u8 | keep [n] u8;  ej_work: head_of [n] u32 | grp [n] u32 | blk_head [ntb] | blk_carry [ntb]
-    const size_t m_rs = 8 * ((size_t)n + 1), m_keep = m_rs + (size_t)n;
     int rc;
-    if ((rc = reserve(ctx, ctx->ej_in, in_bytes + 8)) || (rc = reserve(ctx, ctx->ej_meta, m_keep + (size_t)n + 8)) ||
-        (rc = reserve(ctx, ctx->ej_work, 8 * (size_t)n + 8 * (size_t)ntb)))
-        return rc;
-    uint8_t *meta = (uint8_t *)ctx->ej_meta.p;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->ej_in.p, recs + rec_off[0], in_bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(meta, off.data(), m_rs, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(meta + m_rs, rs, (size_t)n, hipMemcpyHostToDevice, st));
+    if ((rc = check_records(ctx, n, recs, rec_off, false, [](int32_t) { return 0; }))) return rc;
+    BatchLane &L = ctx->batch;
+    std::lock_guard<std::mutex> lk(L.mu);
+    const uint32_t ntb = ((uint32_t)n + bam::TAG_BLOCK - 1) / bam::TAG_BLOCK;
+    // meta: in_off [n + 1] u64 | rs [n] u8 | keep [n] u8;  work: head_of [n] u32 | grp [n] u32 | blk_head [ntb] | blk_carry [ntb]
+    const size_t m_rs = 8 * ((size_t)n + 1), m_keep = m_rs + (size_t)n;
+    std::vector<uint64_t> off;
+    if ((rc = batch_upload(ctx, L, n, recs, rec_off, rs, m_rs, m_keep + (size_t)n + 8, 8 * (size_t)n + 8 * (size_t)ntb, off))) return rc;
+    uint8_t *meta = (uint8_t *)L.meta.p;
     bam::EjectArgs a;
     memset(&a, 0, sizeof a);
-    a.u = (const uint8_t *)ctx->ej_in.p;
+    a.u = (const uint8_t *)L.in.p;
     a.off64 = (const uint64_t *)meta;
     a.n = (uint32_t)n;
     a.rs = meta + m_rs;
     a.keep = meta + m_keep;
-    if (grouped) {
-        a.head_of = (uint32_t *)ctx->ej_work.p;
-        a.grp = a.head_of + (size_t)n;
-        a.blk_head = a.grp + (size_t)n;
-        a.blk_carry = a.blk_head + ntb;
-        HIPCHK(ctx, hipMemsetAsync(a.grp, 0, 4 * (size_t)n, st));
-        hipLaunchKernelGGL(bam::bam_eject_head_kernel, dim3(ntb), dim3(bam::TAG_BLOCK), 0, st, a);
-        HIPCHK(ctx, hipGetLastError());
-        hipLaunchKernelGGL(bam::bam_eject_scan_kernel, dim3(1), dim3(1024), 0, st, a, ntb);
-        HIPCHK(ctx, hipGetLastError());
-        hipLaunchKernelGGL(bam::bam_eject_mark_kernel, dim3(ntb), dim3(bam::TAG_BLOCK), 0, st, a);
-        HIPCHK(ctx, hipGetLastError());
-    }
-    hipLaunchKernelGGL(bam::bam_eject_apply_kernel, dim3(ntb), dim3(bam::TAG_BLOCK), 0, st, a, grouped ? 1 : 0);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(keep, a.keep, (size_t)n, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
+    a.head_of = (uint32_t *)L.work.p;  // (the group arrays: looked at in grouped mode only)
+    a.grp = a.head_of + (size_t)n;
+    a.blk_head = a.grp + (size_t)n;
+    a.blk_carry = a.blk_head + ntb;
+    if ((rc = enqueue_eject(ctx, L.stream, a, ntb, grouped != 0))) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(keep, a.keep, (size_t)n, hipMemcpyDeviceToHost, L.stream));
+    HIPCHK(ctx, hipStreamSynchronize(L.stream));
     return 0;
 }
 
@@ -1916,23 +1932,9 @@ int fadehip_extract_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, cons
     if (rec_off[0] < 0) return set_err(ctx, FADEHIP_E_INVALID, "offsets must be non-negative and non-decreasing (record 0)");
     out_off[0] = 0;
     if (n == 0) return 0;
-    // what the kernels dereference through is checked here: block_size against the offsets, the fields against block_size,
-    // the CIGAR offsets of the sides that are built
+    // beside what check_records checks: the CIGAR offsets of the sides that are built
     int64_t cig_end = 0;
-    for (int32_t k = 0; k < n; k++) {
-        const int64_t len = rec_off[k + 1] - rec_off[k];
-        if (len < 0) return set_err(ctx, FADEHIP_E_INVALID, "offsets must be non-negative and non-decreasing (record %d)", k);
-        const uint8_t *p = recs + rec_off[k];
-        uint32_t bs = 0, ncig = 0;
-        int32_t lseq = 0;
-        if (len >= 36) {
-            memcpy(&bs, p, 4);
-            memcpy(&lseq, p + 20, 4);
-            ncig = (uint32_t)p[16] | ((uint32_t)p[17] << 8);
-        }
-        if (len < 36 || len > ((int64_t)1 << 29) || (int64_t)bs + 4 != len || lseq < 0 || p[12] == 0 ||
-            36ull + p[12] + 4ull * ncig + ((uint64_t)lseq + 1) / 2 + (uint64_t)lseq > (uint64_t)len)
-            return set_err(ctx, FADEHIP_E_INVALID, "record %d is malformed (block_size, l_read_name, n_cigar_op and l_seq must fit its %lld bytes)", k, (long long)len);
+    const auto cigars = [&](int32_t k) {
         for (int side = 0; side < 2; side++) {
             if (!(rs[k] & (2u << side))) continue;
             const int64_t c0 = cig_off[2 * (size_t)k + side], c1 = cig_off[2 * (size_t)k + side + 1];
@@ -1941,31 +1943,26 @@ int fadehip_extract_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, cons
             if (c1 > c0 && !cig) return set_err(ctx, FADEHIP_E_INVALID, "NULL argument");
             cig_end = std::max(cig_end, c1);
         }
-    }
-    const size_t in_bytes = (size_t)(rec_off[n] - rec_off[0]), ns = 2 * (size_t)n;
-    std::vector<uint64_t> off((size_t)n + 1), soff(ns + 1);
-    for (int32_t k = 0; k <= n; k++) off[(size_t)k] = (uint64_t)(rec_off[k] - rec_off[0]);
+        return 0;
+    };
+    int rc;
+    if ((rc = check_records(ctx, n, recs, rec_off, true, cigars))) return rc;
+    const size_t ns = 2 * (size_t)n;
+    std::vector<uint64_t> off, soff(ns + 1);
     for (size_t q = 0; q <= ns; q++) soff[q] = (uint64_t)cig_off[q];  // (of a side that is not built: never read on the device)
-    std::lock_guard<std::mutex> lk(ctx->extract_mu);
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (!ctx->extract_stream) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->extract_stream, hipStreamNonBlocking));
-    hipStream_t st = ctx->extract_stream;
-    // ex_meta: in_off [n + 1] u64 | cig_off [2n + 1] u64 | out_off [2n + 1] u64 | pos [2n] i64 | tid [2n] i32 | cig u32 | rs [n] u8
+    BatchLane &L = ctx->batch;
+    std::lock_guard<std::mutex> lk(L.mu);
+    // meta: in_off [n + 1] u64 | cig_off [2n + 1] u64 | out_off [2n + 1] u64 | pos [2n] i64 | tid [2n] i32 | cig u32 | rs [n] u8;  work: out_size [2n] u32
     const size_t m_coff = 8 * ((size_t)n + 1), m_out = m_coff + 8 * (ns + 1), m_pos = m_out + 8 * (ns + 1), m_tid = m_pos + 8 * ns,
                  m_cig = m_tid + 4 * ns, m_rs = m_cig + 4 * (size_t)cig_end;
-    int rc;
-    if ((rc = reserve(ctx, ctx->ex_in, in_bytes + 8)) || (rc = reserve(ctx, ctx->ex_meta, m_rs + (size_t)n + 8)) || (rc = reserve(ctx, ctx->ex_size, 4 * ns)))
-        return rc;
-    uint8_t *meta = (uint8_t *)ctx->ex_meta.p;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->ex_in.p, recs + rec_off[0], in_bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(meta, off.data(), m_coff, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(meta + m_coff, soff.data(), 8 * (ns + 1), hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(meta + m_pos, art_pos, 8 * ns, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(meta + m_tid, art_tid, 4 * ns, hipMemcpyHostToDevice, st));
-    if (cig_end) HIPCHK(ctx, hipMemcpyAsync(meta + m_cig, cig, 4 * (size_t)cig_end, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(meta + m_rs, rs, (size_t)n, hipMemcpyHostToDevice, st));
+    if ((rc = batch_upload(ctx, L, n, recs, rec_off, rs, m_rs, m_rs + (size_t)n + 8, 4 * ns, off))) return rc;
+    uint8_t *meta = (uint8_t *)L.meta.p;
+    HIPCHK(ctx, hipMemcpyAsync(meta + m_coff, soff.data(), 8 * (ns + 1), hipMemcpyHostToDevice, L.stream));
+    HIPCHK(ctx, hipMemcpyAsync(meta + m_pos, art_pos, 8 * ns, hipMemcpyHostToDevice, L.stream));
+    HIPCHK(ctx, hipMemcpyAsync(meta + m_tid, art_tid, 4 * ns, hipMemcpyHostToDevice, L.stream));
+    if (cig_end) HIPCHK(ctx, hipMemcpyAsync(meta + m_cig, cig, 4 * (size_t)cig_end, hipMemcpyHostToDevice, L.stream));
     bam::ExtractBatchArgs a;
-    a.in = (const uint8_t *)ctx->ex_in.p;
+    a.in = (const uint8_t *)L.in.p;
     a.in_off = (const uint64_t *)meta;
     a.rs = meta + m_rs;
     a.tid = (const int32_t *)(meta + m_tid);
@@ -1973,33 +1970,8 @@ int fadehip_extract_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, cons
     a.cig_off = (const uint64_t *)(meta + m_coff);
     a.cig = (const uint32_t *)(meta + m_cig);
     a.n = (uint32_t)n;
-    a.out_size = (uint32_t *)ctx->ex_size.p;
     a.out_off = (const uint64_t *)(meta + m_out);
-    a.out = nullptr;
-    hipLaunchKernelGGL(bam::extract_batch_size_kernel, dim3(((unsigned)ns + 255u) / 256u), dim3(256), 0, st, a);
-    HIPCHK(ctx, hipGetLastError());
-    std::vector<uint32_t> sizes(ns);
-    HIPCHK(ctx, hipMemcpyAsync(sizes.data(), a.out_size, 4 * ns, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    uint64_t run = 0;
-    for (size_t q = 0; q < ns; q++) {
-        soff[q] = run;
-        run += sizes[q];
-    }
-    soff[ns] = run;
-    const size_t out_bytes = (size_t)run;
-    if ((int64_t)out_bytes > out_cap)
-        return set_err(ctx, FADEHIP_E_INVALID, "the extract records take %lld bytes, out holds %lld", (long long)out_bytes, (long long)out_cap);
-    for (size_t q = 0; q <= ns; q++) out_off[q] = (int64_t)soff[q];
-    if (!out_bytes) return 0;
-    if ((rc = reserve(ctx, ctx->ex_out, out_bytes + 8))) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(meta + m_out, soff.data(), 8 * (ns + 1), hipMemcpyHostToDevice, st));
-    a.out = (uint8_t *)ctx->ex_out.p;
-    hipLaunchKernelGGL(bam::extract_batch_write_kernel, dim3(((unsigned)ns + 15u) / 16u), dim3(256), 0, st, a);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(out, a.out, out_bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    return 0;
+    return size_then_write(ctx, L, a, ns, bam::extract_batch_size_kernel, bam::extract_batch_write_kernel, "extract", false, soff, out, out_cap, out_off);
 }
 
 // ------------------------------------------------------------------------------- level 2
@@ -2573,6 +2545,7 @@ struct fadehip_bam_stream {
         uint64_t k = ~0ull;
         uint32_t n_rec = 0, n_sent = 0, ntb = 0;
         bool pending = false;  // B is enqueued, C is not
+        bam::PackArgs pa;                     // A fills it (u, rec_off, counts, info, sent_of: what B and the tag arguments start from), B the batch arrays
         bam::TagArgs ta;
         Out *out = nullptr;
         std::mutex mu;  // finishing the set's call (front and back may both come to do it; the OTHER set's call is not held up)
@@ -2627,6 +2600,35 @@ struct CallTrace {
     }
 };
 
+// FADEHIP_BAM_EXTRACT, C of call k behind the event the compressor waits for: the extract records of the call's artifact
+// calls, from the untouched input records, and their copy into the pinned buffer back_extract hands out (the total came
+// with the tag sizes)
+int bam_finish_extract(fadehip_bam_stream *st, fadehip_bam_stream::Set &S, uint64_t k, hipStream_t q) {
+    fadehip_ctx *ctx = st->ctx;
+    fadehip_bam_stream::Out *out = S.out;
+    int rc;
+    out->xbytes = 0;
+    out->xrecs = 0;
+    if (S.n_rec) {
+        const bam::ChunkCounts *xc = (const bam::ChunkCounts *)S.h_counts.p + 1;
+        const uint64_t xb = xc->out_bytes;
+        if (xb > ((uint64_t)1 << 31)) return set_err(ctx, FADEHIP_E_UNSUPPORTED, "bam stream: %llu extract bytes in one call (at most 2^31)", (unsigned long long)xb);
+        if (xb) {
+            PinBuf &xh = st->xbuf[k % (FADEHIP_BAM_CHUNKS + 1)];
+            if ((rc = reserve_roomy(ctx, out->x, (size_t)xb + 256)) || (rc = reserve_pinned(ctx, xh, (size_t)xb + (size_t)xb / 4 + 256))) return rc;
+            S.xa.o = (uint8_t *)out->x.p;
+            hipLaunchKernelGGL(bam::bam_extract_write_kernel, dim3(S.ntb), dim3(bam::TAG_BLOCK), 0, q, S.xa);
+            HIPCHK(ctx, hipGetLastError());
+            HIPCHK(ctx, hipMemcpyAsync(xh.p, out->x.p, (size_t)xb, hipMemcpyDeviceToHost, q));
+            out->xbytes = (size_t)xb;
+            out->xrecs = (int64_t)xc->n_records;
+        }
+    }
+    if (!out->xready) HIPCHK(ctx, hipEventCreateWithFlags(&out->xready, hipEventDisableTiming | (ctx->blocking_sync ? hipEventBlockingSync : 0)));
+    HIPCHK(ctx, hipEventRecord(out->xready, q));
+    return 0;
+}
+
 // C of call k (see fadehip_bam_stream): waits for the call's run and tag sizes, sizes the output, enqueues the rewrite.
 // Idempotent; front and back may both arrive here for the same call.
 int bam_finish_call(fadehip_bam_stream *st, uint64_t k) {
@@ -2666,29 +2668,7 @@ int bam_finish_call(fadehip_bam_stream *st, uint64_t k) {
     }
     if (!out->ready) HIPCHK(ctx, hipEventCreateWithFlags(&out->ready, hipEventDisableTiming | (ctx->blocking_sync ? hipEventBlockingSync : 0)));
     HIPCHK(ctx, hipEventRecord(out->ready, q));
-    if (st->extract) {
-        // behind the event the compressor waits for: the extract records of the call's artifact calls, from the untouched
-        // input records, and their copy into the pinned buffer back_extract hands out (the total came with the tag sizes)
-        out->xbytes = 0;
-        out->xrecs = 0;
-        if (S.n_rec) {
-            const bam::ChunkCounts *xc = (const bam::ChunkCounts *)S.h_counts.p + 1;
-            const uint64_t xb = xc->out_bytes;
-            if (xb > ((uint64_t)1 << 31)) return set_err(ctx, FADEHIP_E_UNSUPPORTED, "bam stream: %llu extract bytes in one call (at most 2^31)", (unsigned long long)xb);
-            if (xb) {
-                PinBuf &xh = st->xbuf[k % (FADEHIP_BAM_CHUNKS + 1)];
-                if ((rc = reserve_roomy(ctx, out->x, (size_t)xb + 256)) || (rc = reserve_pinned(ctx, xh, (size_t)xb + (size_t)xb / 4 + 256))) return rc;
-                S.xa.o = (uint8_t *)out->x.p;
-                hipLaunchKernelGGL(bam::bam_extract_write_kernel, dim3(S.ntb), dim3(bam::TAG_BLOCK), 0, q, S.xa);
-                HIPCHK(ctx, hipGetLastError());
-                HIPCHK(ctx, hipMemcpyAsync(xh.p, out->x.p, (size_t)xb, hipMemcpyDeviceToHost, q));
-                out->xbytes = (size_t)xb;
-                out->xrecs = (int64_t)xc->n_records;
-            }
-        }
-        if (!out->xready) HIPCHK(ctx, hipEventCreateWithFlags(&out->xready, hipEventDisableTiming | (ctx->blocking_sync ? hipEventBlockingSync : 0)));
-        HIPCHK(ctx, hipEventRecord(out->xready, q));
-    }
+    if (st->extract && (rc = bam_finish_extract(st, S, k, q))) return rc;
     S.pending = false;
     st->t_tags += now_s() - t0;
     {
@@ -2699,27 +2679,13 @@ int bam_finish_call(fadehip_bam_stream *st, uint64_t k) {
     return 0;
 }
 
-int bam_front_impl(fadehip_bam_stream *st, const uint8_t *members, size_t n_bytes, int last, bool raw) {
+// A of call k (see fadehip_bam_stream) on the slot's stream q, up to and with the wait and the checks of what came back: the
+// call's counts are in S.h_counts then, and S.pa is ready for B
+int bam_front_frame(fadehip_bam_stream *st, fadehip_bam_stream::Set &S, CallTrace &tr, const uint8_t *members, size_t n_bytes, int last, bool raw) {
     fadehip_ctx *ctx = st->ctx;
     const uint64_t k = st->k_front;
-    fadehip_bam_stream::Set &S = st->set[k & 1];
-    Slot &s = ctx->slots[k & 1];
+    hipStream_t q = ctx->slots[k & 1].stream;
     int rc;
-    // the set's previous call must have been finished (back has usually done that long ago)
-    CallTrace tr("front", k);
-    if (ctx->n_contigs == 0) return set_err(ctx, FADEHIP_E_STATE, "fadehip_genome_upload has not been called");
-    if (k >= 2 && (rc = bam_finish_call(st, k - 2))) return rc;
-    tr.mark("finish call k - 2");
-    // every stream is an HSA queue to set up and to give back (tens of ms each): slot 0 works on the ctx's copy stream, which
-    // exists anyway and which the file path does not use otherwise; slot 1 gets a stream of its own when the second call comes
-    if (ctx->split_cus > 0 && !s.stream && !s.h_zb) {
-        ctx->tail_cus_per_xcd = 0;  // (no third set of CUs)
-        s.stream = xcd_slice_stream(ctx, 0, ctx->split_cus);
-    }
-    if (!s.stream && !s.h_zb && (k & 1) == 0 && ctx->copy_stream) s.stream = ctx->copy_stream;
-    if ((rc = ensure_slot(ctx, s))) return rc;
-    tr.mark("slot (stream, events)");
-    hipStream_t q = s.stream;
     const double t0 = now_s();
     // ---- the members, and where their payloads go
     std::vector<bgzf::InflateBlock> blocks;
@@ -2818,7 +2784,7 @@ int bam_front_impl(fadehip_bam_stream *st, const uint8_t *members, size_t n_byte
     if ((rc = reserve_roomy(ctx, S.info, 4 * (size_t)rec_cap)) || (rc = reserve_roomy(ctx, S.sent_of, 4 * (size_t)rec_cap)) ||
         (rc = reserve_roomy(ctx, S.out_size, 4 * (size_t)rec_cap)) || (rc = reserve_roomy(ctx, S.blk32, 24 * (size_t)nblk_cap)))
         return rc;
-    bam::PackArgs pa;
+    bam::PackArgs &pa = S.pa;
     memset(&pa, 0, sizeof pa);
     pa.u = u;
     pa.rec_off = fa.rec_off;
@@ -2864,11 +2830,199 @@ int bam_front_impl(fadehip_bam_stream *st, const uint8_t *members, size_t n_byte
     st->prev_consumed = used;
     st->n_redone += h_counts->n_redone;
     if (n_rec) st->rec_bytes_avg = (double)used / (double)n_rec;
+    return 0;
+}
+
+// B's tail, what anno.d:94-107 adds: which alignment is whose, the sizes of the n_rec records as they leave (ntb blocks of
+// TAG_BLOCK) and, with the flags, of the extract records and less what eject takes out; their scans; the counts to the host
+int bam_enqueue_sizes(fadehip_bam_stream *st, fadehip_bam_stream::Set &S, Slot &s, uint32_t n_rec, uint32_t n_sent, uint32_t ntb) {
+    fadehip_ctx *ctx = st->ctx;
+    hipStream_t q = s.stream;
+    const bam::PackArgs &pa = S.pa;
+    bam::ChunkCounts *d_counts = pa.counts;
+    int rc;
+    if ((rc = reserve_roomy(ctx, S.art_of, 4 * (size_t)std::max(n_sent, 1u)))) return rc;
+    if (n_sent) {
+        HIPCHK(ctx, hipMemsetAsync(S.art_of.p, 0xff, 4 * (size_t)n_sent, q));
+        if (s.out_cap) {
+            hipLaunchKernelGGL(bam::bam_art_index_kernel, dim3((s.out_cap + 255) / 256), dim3(256), 0, q, (const fadehip_aln *)s.aln.p,
+                               (const uint32_t *)(s.d_counters() + 2 * NUM_LISTS + 3), s.out_cap, (int32_t *)S.art_of.p, n_sent);
+            HIPCHK(ctx, hipGetLastError());
+        }
+    }
+    bam::TagArgs &ta = S.ta;
+    memset(&ta, 0, sizeof ta);
+    ta.u = pa.u;
+    ta.rec_off = pa.rec_off;
+    ta.counts_in = d_counts;
+    ta.r0 = 0;
+    ta.r1_cap = n_rec;
+    ta.info = pa.info;
+    ta.sent_of = pa.sent_of;
+    ta.rs = (const uint8_t *)s.rs.p;
+    ta.aln = (const fadehip_aln *)s.aln.p;
+    ta.art_of = (const int32_t *)S.art_of.p;
+    ta.names.text = (const char *)st->names_text.p;
+    ta.names.off = (const uint32_t *)st->names_off.p;
+    ta.names.n = st->n_ref;
+    ta.out_size = (uint32_t *)S.out_size.p;
+    ta.blk_sums = (uint64_t *)S.blk64.p;
+    ta.blk_base = ta.blk_sums + ntb;
+    ta.counts = d_counts;
+    ta.out_base = 0;
+    if (st->clip) hipLaunchKernelGGL(bam::bam_tag_size_kernel<true>, dim3(ntb), dim3(bam::TAG_BLOCK), 0, q, ta);
+    else hipLaunchKernelGGL(bam::bam_tag_size_kernel<false>, dim3(ntb), dim3(bam::TAG_BLOCK), 0, q, ta);
+    HIPCHK(ctx, hipGetLastError());
+    // (eject: the scan comes behind the eject kernels, which come behind the extract sizes — see below)
+    if (!st->eject) {
+        hipLaunchKernelGGL(bam::bam_tag_scan_kernel, dim3(1), dim3(1024), 0, q, ta, ntb);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    if (st->extract) {
+        // the extract records' sizes into the same scan, their total into the ChunkCounts behind the call's own: it crosses
+        // to the host in the copy below, which back reads anyway
+        if ((rc = reserve_roomy(ctx, S.ex_size, 4 * (size_t)n_rec)) || (rc = reserve_roomy(ctx, S.ex_blk, 16 * (size_t)ntb))) return rc;
+        bam::TagArgs &xa = S.xa;
+        xa = ta;
+        xa.out_size = (uint32_t *)S.ex_size.p;
+        xa.blk_sums = (uint64_t *)S.ex_blk.p;
+        xa.blk_base = xa.blk_sums + ntb;
+        xa.counts = d_counts + 1;
+        xa.o = nullptr;
+        hipLaunchKernelGGL(bam::bam_extract_size_kernel, dim3(ntb), dim3(bam::TAG_BLOCK), 0, q, xa);
+        HIPCHK(ctx, hipGetLastError());
+        hipLaunchKernelGGL(bam::bam_tag_scan_kernel, dim3(1), dim3(1024), 0, q, xa, ntb);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    if (st->eject) {
+        // which records leave: out_size 0 and INFO_BAD for them, the blocks' sums again, and only then the scan of the
+        // sums.  Behind the extract sizes, which are taken of every artifact call and look at `info`.
+        bam::EjectArgs ea;
+        memset(&ea, 0, sizeof ea);
+        ea.u = pa.u;
+        ea.off32 = pa.rec_off;
+        ea.n = n_rec;
+        ea.sent_of = pa.sent_of;
+        ea.rs = (const uint8_t *)s.rs.p;
+        ea.out_size = ta.out_size;
+        ea.info = pa.info;
+        ea.blk_sums = ta.blk_sums;
+        ea.counts = d_counts;
+        if (st->eject_groups) {
+            if ((rc = reserve_roomy(ctx, S.ej_head, 4 * (size_t)n_rec)) || (rc = reserve_roomy(ctx, S.ej_blk, 8 * (size_t)ntb)) ||
+                (rc = reserve_roomy(ctx, S.ej_grp, 4 * (size_t)n_rec)))
+                return rc;
+            ea.head_of = (uint32_t *)S.ej_head.p;
+            ea.blk_head = (uint32_t *)S.ej_blk.p;
+            ea.blk_carry = ea.blk_head + ntb;
+            ea.grp = (uint32_t *)S.ej_grp.p;
+        }
+        if ((rc = enqueue_eject(ctx, q, ea, ntb, st->eject_groups))) return rc;
+        hipLaunchKernelGGL(bam::bam_tag_scan_kernel, dim3(1), dim3(1024), 0, q, ta, ntb);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    HIPCHK(ctx, hipMemcpyAsync(S.h_counts.p, d_counts, st->counts_bytes(), hipMemcpyDeviceToHost, q));
+    return 0;
+}
+
+// B of call k: the records that go to the gate packed into the slot's batch arrays, annotateTask on the device (level 2's
+// kernels, results left there), then the sizes
+int bam_front_run(fadehip_bam_stream *st, fadehip_bam_stream::Set &S, Slot &s, CallTrace &tr, uint32_t n_rec) {
+    fadehip_ctx *ctx = st->ctx;
+    hipStream_t q = s.stream;
+    bam::PackArgs &pa = S.pa;
+    const bam::ChunkCounts *h_counts = (const bam::ChunkCounts *)S.h_counts.p;
+    int rc;
+    const uint32_t nblk = (n_rec + bam::PACK_BLOCK - 1) / bam::PACK_BLOCK, ntb = (n_rec + bam::TAG_BLOCK - 1) / bam::TAG_BLOCK;
+    if ((rc = reserve_roomy(ctx, S.blk64, 16 * (size_t)ntb))) return rc;
+    if (h_counts->n_bad_layout)
+        return set_err(ctx, FADEHIP_E_INVALID, "bam stream: call %llu: %u records whose fields do not fit their block_size or whose tags are not whole fields (corrupt BAM)", (unsigned long long)st->k_front, h_counts->n_bad_layout);
+    const uint32_t n_sent = h_counts->n_sent;
+    if ((uint64_t)h_counts->n_seq * 2 >= ((uint64_t)1 << 32)) return set_err(ctx, FADEHIP_E_UNSUPPORTED, "bam stream: packed sequence bytes per call must stay below 2^31");
+    if (s.state == 2) HIPCHK(ctx, hipStreamSynchronize(s.stream));
+    s.state = 0;
+    s.device_only = true;
+    s.next.valid = false;
+    s.have_batch = false;
+    s.cur = 0;
+    s.L = batch_layout(n_sent, h_counts->n_cig, h_counts->n_seq);
+    if ((rc = reserve_roomy(ctx, s.in[0], s.L.total))) return rc;
+    uint8_t *ib = (uint8_t *)s.in[0].p;
+    pa.tid = (int32_t *)(ib + s.L.off[A_TID]);
+    pa.pos = (int32_t *)(ib + s.L.off[A_POS]);
+    pa.lseq = (int32_t *)(ib + s.L.off[A_LSEQ]);
+    pa.cigar_off = (uint32_t *)(ib + s.L.off[A_CIGOFF]);
+    pa.seq_off = (uint32_t *)(ib + s.L.off[A_SEQOFF]);
+    pa.flag = (uint16_t *)(ib + s.L.off[A_FLAG]);
+    pa.has_sa = ib + s.L.off[A_SA];
+    pa.cigar_ops = (uint32_t *)(ib + s.L.off[A_CIG]);
+    pa.seq = ib + s.L.off[A_SEQ];
+    hipLaunchKernelGGL(bam::bam_pack_write_kernel, dim3(nblk), dim3(bam::PACK_BLOCK), 0, q, pa);
+    HIPCHK(ctx, hipGetLastError());
+    tr.mark("pack enqueued");
+    // ---- annotateTask on the device (level 2's kernels), results left there
+    s.n_reads = (int)n_sent;
+    s.n_skipped = (int)(n_rec - n_sent);
+    s.floor_len = st->floor_len;
+    s.window = st->window;
+    memset(s.hist, 0, sizeof s.hist);
+    s.wide.clear();
+    s.wide_all = false;
+    s.out_bound = n_sent;
+    s.max_lq = 0;
+    s.l_seq_lo = 0;  // (the bounds below are counted on the device over these very records)
+    s.l_seq_hi = INT32_MAX;
+    s.span_bound = 1;
+    if (n_sent) {
+        const int lmin = (int)std::min<uint32_t>(h_counts->l_seq_min, (uint32_t)MAX_LONG_QUERY), lmax = (int)std::min<uint32_t>(h_counts->l_seq_max, (uint32_t)MAX_LONG_QUERY);
+        const int c_lo = list_of_len(std::max(lmin, 1)), c_hi = list_of_len(std::max(lmax, 1));
+        for (int c = c_lo; c <= c_hi; c++) s.hist[c] = n_sent;  // any of them may be of any length in between
+        if (h_counts->n_long_q) s.hist[LONG_LIST] = h_counts->n_long_q;  // (the exact number of reads beyond 512 bases)
+        s.max_lq = std::max(lmax, 1);
+        s.span_bound = std::max<int64_t>(h_counts->span_max, 1);
+        s.wide_all = s.span_bound > WIDE_MIN_SPAN;
+    }
+    if (n_sent) {
+        if ((rc = plan_run(ctx, s)) || (rc = enqueue_run(ctx, s))) {
+            (void)hipStreamSynchronize(q);
+            return rc;
+        }
+        s.state = 2;
+    }
+    tr.mark("run planned and enqueued");
+    if ((rc = bam_enqueue_sizes(st, S, s, n_rec, n_sent, ntb))) return rc;
+    S.n_sent = n_sent;
+    S.ntb = ntb;
+    return 0;
+}
+
+int bam_front_impl(fadehip_bam_stream *st, const uint8_t *members, size_t n_bytes, int last, bool raw) {
+    fadehip_ctx *ctx = st->ctx;
+    const uint64_t k = st->k_front;
+    fadehip_bam_stream::Set &S = st->set[k & 1];
+    Slot &s = ctx->slots[k & 1];
+    int rc;
+    // the set's previous call must have been finished (back has usually done that long ago)
+    CallTrace tr("front", k);
+    if (ctx->n_contigs == 0) return set_err(ctx, FADEHIP_E_STATE, "fadehip_genome_upload has not been called");
+    if (k >= 2 && (rc = bam_finish_call(st, k - 2))) return rc;
+    tr.mark("finish call k - 2");
+    // every stream is an HSA queue to set up and to give back (tens of ms each): slot 0 works on the ctx's copy stream, which
+    // exists anyway and which the file path does not use otherwise; slot 1 gets a stream of its own when the second call comes
+    if (ctx->split_cus > 0 && !s.stream && !s.h_zb) {
+        ctx->tail_cus_per_xcd = 0;  // (no third set of CUs)
+        s.stream = xcd_slice_stream(ctx, 0, ctx->split_cus);
+    }
+    if (!s.stream && !s.h_zb && (k & 1) == 0 && ctx->copy_stream) s.stream = ctx->copy_stream;
+    if ((rc = ensure_slot(ctx, s))) return rc;
+    tr.mark("slot (stream, events)");
+    if ((rc = bam_front_frame(st, S, tr, members, n_bytes, last, raw))) return rc;
+    const double t2 = now_s();
+    const uint32_t n_rec = ((const bam::ChunkCounts *)S.h_counts.p)->n_records;
     // ---- a place in the ring
-    fadehip_bam_stream::Out *out;
+    fadehip_bam_stream::Out *out = &st->ring[k % FADEHIP_BAM_CHUNKS];
     {
         std::unique_lock<std::mutex> l(st->mu);
-        out = &st->ring[k % FADEHIP_BAM_CHUNKS];
         st->cv.wait(l, [&] { return out->state == 0 || st->failed || st->closing; });
         if (st->failed || st->closing) return set_err(ctx, FADEHIP_E_STATE, "bam stream: stopped");
     }
@@ -2879,157 +3033,7 @@ int bam_front_impl(fadehip_bam_stream *st, const uint8_t *members, size_t n_byte
     S.n_sent = 0;
     S.ntb = 0;
     S.out = out;
-    if (n_rec) {
-        const uint32_t nblk = (n_rec + bam::PACK_BLOCK - 1) / bam::PACK_BLOCK, ntb = (n_rec + bam::TAG_BLOCK - 1) / bam::TAG_BLOCK;
-        if ((rc = reserve_roomy(ctx, S.blk64, 16 * (size_t)ntb))) return rc;
-        if (h_counts->n_bad_layout)
-            return set_err(ctx, FADEHIP_E_INVALID, "bam stream: call %llu: %u records whose fields do not fit their block_size or whose tags are not whole fields (corrupt BAM)", (unsigned long long)k, h_counts->n_bad_layout);
-        const uint32_t n_sent = h_counts->n_sent;
-        if ((uint64_t)h_counts->n_seq * 2 >= ((uint64_t)1 << 32)) return set_err(ctx, FADEHIP_E_UNSUPPORTED, "bam stream: packed sequence bytes per call must stay below 2^31");
-        if (s.state == 2) HIPCHK(ctx, hipStreamSynchronize(s.stream));
-        s.state = 0;
-        s.device_only = true;
-        s.next.valid = false;
-        s.have_batch = false;
-        s.cur = 0;
-        s.L = batch_layout(n_sent, h_counts->n_cig, h_counts->n_seq);
-        if ((rc = reserve_roomy(ctx, s.in[0], s.L.total))) return rc;
-        uint8_t *ib = (uint8_t *)s.in[0].p;
-        pa.tid = (int32_t *)(ib + s.L.off[A_TID]);
-        pa.pos = (int32_t *)(ib + s.L.off[A_POS]);
-        pa.lseq = (int32_t *)(ib + s.L.off[A_LSEQ]);
-        pa.cigar_off = (uint32_t *)(ib + s.L.off[A_CIGOFF]);
-        pa.seq_off = (uint32_t *)(ib + s.L.off[A_SEQOFF]);
-        pa.flag = (uint16_t *)(ib + s.L.off[A_FLAG]);
-        pa.has_sa = ib + s.L.off[A_SA];
-        pa.cigar_ops = (uint32_t *)(ib + s.L.off[A_CIG]);
-        pa.seq = ib + s.L.off[A_SEQ];
-        hipLaunchKernelGGL(bam::bam_pack_write_kernel, dim3(nblk), dim3(bam::PACK_BLOCK), 0, q, pa);
-        HIPCHK(ctx, hipGetLastError());
-        tr.mark("pack enqueued");
-        // ---- annotateTask on the device (level 2's kernels), results left there
-        s.n_reads = (int)n_sent;
-        s.n_skipped = (int)(n_rec - n_sent);
-        s.floor_len = st->floor_len;
-        s.window = st->window;
-        memset(s.hist, 0, sizeof s.hist);
-        s.wide.clear();
-        s.wide_all = false;
-        s.out_bound = n_sent;
-        s.max_lq = 0;
-        s.l_seq_lo = 0;  // (the bounds below are counted on the device over these very records)
-        s.l_seq_hi = INT32_MAX;
-        s.span_bound = 1;
-        if (n_sent) {
-            const int lmin = (int)std::min<uint32_t>(h_counts->l_seq_min, (uint32_t)MAX_LONG_QUERY), lmax = (int)std::min<uint32_t>(h_counts->l_seq_max, (uint32_t)MAX_LONG_QUERY);
-            const int c_lo = list_of_len(std::max(lmin, 1)), c_hi = list_of_len(std::max(lmax, 1));
-            for (int c = c_lo; c <= c_hi; c++) s.hist[c] = n_sent;  // any of them may be of any length in between
-            if (h_counts->n_long_q) s.hist[LONG_LIST] = h_counts->n_long_q;  // (the exact number of reads beyond 512 bases)
-            s.max_lq = std::max(lmax, 1);
-            s.span_bound = std::max<int64_t>(h_counts->span_max, 1);
-            s.wide_all = s.span_bound > WIDE_MIN_SPAN;
-        }
-        if (n_sent) {
-            if ((rc = plan_run(ctx, s)) || (rc = enqueue_run(ctx, s))) {
-                (void)hipStreamSynchronize(q);
-                return rc;
-            }
-            s.state = 2;
-        }
-        tr.mark("run planned and enqueued");
-        // ---- what anno.d:94-107 adds: sizes, offsets
-        if ((rc = reserve_roomy(ctx, S.art_of, 4 * (size_t)std::max(n_sent, 1u)))) return rc;
-        if (n_sent) {
-            HIPCHK(ctx, hipMemsetAsync(S.art_of.p, 0xff, 4 * (size_t)n_sent, q));
-            if (s.out_cap) {
-                hipLaunchKernelGGL(bam::bam_art_index_kernel, dim3((s.out_cap + 255) / 256), dim3(256), 0, q, (const fadehip_aln *)s.aln.p,
-                                   (const uint32_t *)(s.d_counters() + 2 * NUM_LISTS + 3), s.out_cap, (int32_t *)S.art_of.p, n_sent);
-                HIPCHK(ctx, hipGetLastError());
-            }
-        }
-        bam::TagArgs &ta = S.ta;
-        memset(&ta, 0, sizeof ta);
-        ta.u = u;
-        ta.rec_off = fa.rec_off;
-        ta.counts_in = d_counts;
-        ta.r0 = 0;
-        ta.r1_cap = n_rec;
-        ta.info = pa.info;
-        ta.sent_of = pa.sent_of;
-        ta.rs = (const uint8_t *)s.rs.p;
-        ta.aln = (const fadehip_aln *)s.aln.p;
-        ta.art_of = (const int32_t *)S.art_of.p;
-        ta.names.text = (const char *)st->names_text.p;
-        ta.names.off = (const uint32_t *)st->names_off.p;
-        ta.names.n = st->n_ref;
-        ta.out_size = (uint32_t *)S.out_size.p;
-        ta.blk_sums = (uint64_t *)S.blk64.p;
-        ta.blk_base = ta.blk_sums + ntb;
-        ta.counts = d_counts;
-        ta.out_base = 0;
-        if (st->clip) hipLaunchKernelGGL(bam::bam_tag_size_kernel<true>, dim3(ntb), dim3(bam::TAG_BLOCK), 0, q, ta);
-        else hipLaunchKernelGGL(bam::bam_tag_size_kernel<false>, dim3(ntb), dim3(bam::TAG_BLOCK), 0, q, ta);
-        HIPCHK(ctx, hipGetLastError());
-        // (eject: the scan comes behind the eject kernels, which come behind the extract sizes — see below)
-        if (!st->eject) {
-            hipLaunchKernelGGL(bam::bam_tag_scan_kernel, dim3(1), dim3(1024), 0, q, ta, ntb);
-            HIPCHK(ctx, hipGetLastError());
-        }
-        if (st->extract) {
-            // the extract records' sizes into the same scan, their total into the ChunkCounts behind the call's own: it crosses
-            // to the host in the copy below, which back reads anyway
-            if ((rc = reserve_roomy(ctx, S.ex_size, 4 * (size_t)n_rec)) || (rc = reserve_roomy(ctx, S.ex_blk, 16 * (size_t)ntb))) return rc;
-            bam::TagArgs &xa = S.xa;
-            xa = ta;
-            xa.out_size = (uint32_t *)S.ex_size.p;
-            xa.blk_sums = (uint64_t *)S.ex_blk.p;
-            xa.blk_base = xa.blk_sums + ntb;
-            xa.counts = d_counts + 1;
-            xa.o = nullptr;
-            hipLaunchKernelGGL(bam::bam_extract_size_kernel, dim3(ntb), dim3(bam::TAG_BLOCK), 0, q, xa);
-            HIPCHK(ctx, hipGetLastError());
-            hipLaunchKernelGGL(bam::bam_tag_scan_kernel, dim3(1), dim3(1024), 0, q, xa, ntb);
-            HIPCHK(ctx, hipGetLastError());
-        }
-        if (st->eject) {
-            // which records leave: out_size 0 and INFO_BAD for them, the blocks' sums again, and only then the scan of the
-            // sums.  Behind the extract sizes, which are taken of every artifact call and look at `info`.
-            bam::EjectArgs ea;
-            memset(&ea, 0, sizeof ea);
-            ea.u = u;
-            ea.off32 = fa.rec_off;
-            ea.n = n_rec;
-            ea.sent_of = pa.sent_of;
-            ea.rs = (const uint8_t *)s.rs.p;
-            ea.out_size = ta.out_size;
-            ea.info = pa.info;
-            ea.blk_sums = ta.blk_sums;
-            ea.counts = d_counts;
-            if (st->eject_groups) {
-                if ((rc = reserve_roomy(ctx, S.ej_head, 4 * (size_t)n_rec)) || (rc = reserve_roomy(ctx, S.ej_blk, 8 * (size_t)ntb)) ||
-                    (rc = reserve_roomy(ctx, S.ej_grp, 4 * (size_t)n_rec)))
-                    return rc;
-                ea.head_of = (uint32_t *)S.ej_head.p;
-                ea.blk_head = (uint32_t *)S.ej_blk.p;
-                ea.blk_carry = ea.blk_head + ntb;
-                ea.grp = (uint32_t *)S.ej_grp.p;
-                HIPCHK(ctx, hipMemsetAsync(ea.grp, 0, 4 * (size_t)n_rec, q));
-                hipLaunchKernelGGL(bam::bam_eject_head_kernel, dim3(ntb), dim3(bam::TAG_BLOCK), 0, q, ea);
-                HIPCHK(ctx, hipGetLastError());
-                hipLaunchKernelGGL(bam::bam_eject_scan_kernel, dim3(1), dim3(1024), 0, q, ea, ntb);
-                HIPCHK(ctx, hipGetLastError());
-                hipLaunchKernelGGL(bam::bam_eject_mark_kernel, dim3(ntb), dim3(bam::TAG_BLOCK), 0, q, ea);
-                HIPCHK(ctx, hipGetLastError());
-            }
-            hipLaunchKernelGGL(bam::bam_eject_apply_kernel, dim3(ntb), dim3(bam::TAG_BLOCK), 0, q, ea, st->eject_groups ? 1 : 0);
-            HIPCHK(ctx, hipGetLastError());
-            hipLaunchKernelGGL(bam::bam_tag_scan_kernel, dim3(1), dim3(1024), 0, q, ta, ntb);
-            HIPCHK(ctx, hipGetLastError());
-        }
-        HIPCHK(ctx, hipMemcpyAsync(h_counts, d_counts, st->counts_bytes(), hipMemcpyDeviceToHost, q));
-        S.n_sent = n_sent;
-        S.ntb = ntb;
-    }
+    if (n_rec && (rc = bam_front_run(st, S, s, tr, n_rec))) return rc;
     S.pending = true;
     tr.mark("tag sizes enqueued");
     st->t_run += now_s() - t2;

@@ -151,7 +151,9 @@ int fadehip_sw_stats_batch(fadehip_ctx *ctx, const int32_t scoring[4] /* open, e
  * out_off receives n + 1 offsets; out must hold them (a record grows by at most eight bytes).  The device function is the one
  * the file path runs under FADEHIP_BAM_CLIP; there rs and the lengths are the run's own results.  A record whose
  * block_size, l_read_name, n_cigar_op and l_seq do not fit its bytes: FADEHIP_E_INVALID, with its index in
- * fadehip_last_error.  Synchronous, on a stream and buffers of its own, as fadehip_sw_stats_batch. */
+ * fadehip_last_error.  Synchronous, and apart from the annotate slots as fadehip_sw_stats_batch is; fadehip_clip_batch,
+ * fadehip_extract_batch and fadehip_eject_batch share one stream, one set of buffers and one lock per ctx: calls of any of
+ * the three on one ctx, from whichever threads, run one after the other. */
 int fadehip_clip_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const int64_t *rec_off, const uint8_t *rs,
                        const int32_t *trim_left, const int32_t *trim_right, uint8_t *out, int64_t out_cap, int64_t *out_off);
 
@@ -166,7 +168,8 @@ int fadehip_clip_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const i
  * written.  The CIGAR's query length is not held against l_seq (`fade extract` does not either).  The device function is
  * the one the file path runs under FADEHIP_BAM_EXTRACT; there the fields are the run's own results.  A record whose
  * block_size, l_read_name, n_cigar_op and l_seq do not fit its bytes, or a built side whose CIGAR offsets step backwards:
- * FADEHIP_E_INVALID, with the record's index in fadehip_last_error.  Synchronous, on a stream and buffers of its own. */
+ * FADEHIP_E_INVALID, with the record's index in fadehip_last_error.  Synchronous, on the stream and buffers it shares with
+ * fadehip_clip_batch (see there). */
 int fadehip_extract_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const int64_t *rec_off, const uint8_t *rs,
                           const int32_t *art_tid /* [2n] */, const int64_t *art_pos /* [2n] */, const int64_t *cig_off /* [2n + 1] */,
                           const uint32_t *cig, uint8_t *out, int64_t out_cap, int64_t *out_off /* [2n + 1] */);
@@ -178,7 +181,8 @@ int fadehip_extract_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, cons
  * work per record does not grow with a group's length.  Whether a file is name-sorted is the caller's to decide (`fade out`
  * looks at its first ten records).  The kernels are the ones the file path runs under FADEHIP_BAM_EJECT /
  * FADEHIP_BAM_EJECT_GROUPS; there rs is the run's own result.  A record whose block_size or l_read_name does not fit its
- * bytes: FADEHIP_E_INVALID, with the record's index in fadehip_last_error.  Synchronous, on a stream and buffers of its own. */
+ * bytes: FADEHIP_E_INVALID, with the record's index in fadehip_last_error.  Synchronous, on the stream and buffers it shares
+ * with fadehip_clip_batch (see there). */
 int fadehip_eject_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const int64_t *rec_off, const uint8_t *rs,
                         int grouped, uint8_t *keep /* [n] out */);
 
