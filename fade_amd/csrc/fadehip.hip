@@ -213,7 +213,7 @@ struct fadehip_ctx {
     bool use_packed = true;
     bool two_pass = true;
     int tail_cus_per_xcd = 1;  // FADEHIP_TAIL_CUS: CUs per XCD the score pass leaves alone (0: no CU mask, one stream per slot)
-    int score_g8 = 1;            // the score pass of reads of up to 152 bases in the 160-row class on eight-lane groups (FADEHIP_SCORE_G8=0: sixteen-lane groups; 2: at two waves per SIMD): the score pass of 150-base reads on eight-lane groups (A/B variant)
+    int score_g8 = 1;            // the score pass on eight-lane groups where the batch's reads fit them (g8_kernel; FADEHIP_SCORE_G8=0: sixteen-lane groups only; 2: the 152-row kernel at two waves per SIMD)
     bool blocking_sync = false;  // FADEHIP_BLOCKING_SYNC=1: waits for the device sleep
     int split_cus = 0;  // FADEHIP_BAM_SPLIT=j: the file path's record kernels get j CUs of every XCD, the compressor the others
     bool score_persist = false;  // FADEHIP_SCORE_PERSIST=1: the score pass as a persistent launch (A/B variant)
@@ -422,53 +422,61 @@ int record(fadehip_ctx *ctx, Slot &s, int *idx, hipStream_t on = nullptr) {
     return 0;
 }
 
-template <int C>
-int launch_forward_c(fadehip_ctx *ctx, int cls, const SwArgs &a, int quads, size_t lds, hipStream_t st, bool packed, bool longw) {
-    if constexpr (C >= NUM_CLASSES) {
-        return set_err(ctx, FADEHIP_E_INVALID, "bad class %d", cls);
-    } else {
-        if (cls == C) {
-            constexpr int R = class_rows(C);
-            if (packed && longw)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(sw_pk_kernel<R, 0, true>), dim3(quads), dim3(64), lds, st, a);
-            else if (packed)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(sw_pk_kernel<R, 0>), dim3(quads), dim3(64), lds, st, a);
-            else
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(sw_forward_kernel<R>), dim3(quads), dim3(64), lds, st, a);
-            HIPCHK(ctx, hipGetLastError());
-            return 0;
-        }
-        return launch_forward_c<C + 1>(ctx, cls, a, quads, lds, st, packed, longw);
-    }
-}
-
-// mode 1: score pass, 2: traced re-computation (default rules), 3: traced re-computation with rule switches
-template <int C>
-const void *pk_kernel_ptr(int cls, int mode, bool longw) {
+// The wave kernel of a row class.  mode 0: single pass with full trace (FADEHIP_KERNEL=pk), 1: score pass, 2: traced
+// re-computation (default rules), 3: traced re-computation with rule switches; SW_INT32: the int32 single-pass kernel
+// (FADEHIP_KERNEL=int32).  longw: windows beyond one staged chunk (CH_COLS columns) in this launch (packed kernels only).
+constexpr int SW_INT32 = -1;
+template <int C = 0>
+const void *sw_kernel(int cls, int mode, bool longw) {
     if constexpr (C >= NUM_CLASSES) {
         return nullptr;
     } else {
-        if (cls == C) {
-            constexpr int R = class_rows(C);
-            if (longw) {  // windows beyond one staged chunk (CH_COLS columns) in this launch
-                if (mode == 1) return (const void *)sw_pk_kernel<R, 1, true>;
-                if (mode == 2) return (const void *)sw_pk_kernel<R, 2, true>;
-                return (const void *)sw_pk_kernel<R, 3, true>;
-            }
-            if (mode == 1) return (const void *)sw_pk_kernel<R, 1>;
-            if (mode == 2) return (const void *)sw_pk_kernel<R, 2>;
-            return (const void *)sw_pk_kernel<R, 3>;
+        if (cls != C) return sw_kernel<C + 1>(cls, mode, longw);
+        constexpr int R = class_rows(C);
+        switch (mode) {
+        case SW_INT32: return (const void *)sw_forward_kernel<R>;
+        case 0: return longw ? (const void *)sw_pk_kernel<R, 0, true> : (const void *)sw_pk_kernel<R, 0>;
+        case 1: return longw ? (const void *)sw_pk_kernel<R, 1, true> : (const void *)sw_pk_kernel<R, 1>;
+        case 2: return longw ? (const void *)sw_pk_kernel<R, 2, true> : (const void *)sw_pk_kernel<R, 2>;
+        default: return longw ? (const void *)sw_pk_kernel<R, 3, true> : (const void *)sw_pk_kernel<R, 3>;
         }
-        return pk_kernel_ptr<C + 1>(cls, mode, longw);
     }
 }
 
-int launch_pk_mode(fadehip_ctx *ctx, int cls, int mode, const SwArgs &a, int waves, size_t lds, hipStream_t st, bool longw) {
-    const void *fn = pk_kernel_ptr<0>(cls, mode, longw);
-    if (!fn) return set_err(ctx, FADEHIP_E_INVALID, "bad class %d", cls);
-    SwArgs copy = a;
-    void *args[] = {&copy};
-    HIPCHK(ctx, hipLaunchKernel(fn, dim3((unsigned)waves), dim3(64), args, lds, st));
+// The long list's wave kernel (one alignment per wavefront) at R rows per lane: run_long_wave picks R.
+const void *sw64_kernel(int R) {
+    switch (R) {
+    case 12: return (const void *)sw_forward64_kernel<12>;
+    case 16: return (const void *)sw_forward64_kernel<16>;
+    case 24: return (const void *)sw_forward64_kernel<24>;
+    case 32: return (const void *)sw_forward64_kernel<32>;
+    case 48: return (const void *)sw_forward64_kernel<48>;
+    default: return (const void *)sw_forward64_kernel<64>;
+    }
+}
+
+// The score pass on eight-lane groups, or nullptr where the class keeps its sixteen-lane kernel.  A lane owns R8 rows, a
+// group 8 R8: rows come in steps of 8 instead of 16 (36-base reads: 40 rows instead of 64; 50: 56 / 64; 76: 80 / 96; 100, 101:
+// 104 / 128; 150, 151: 152 / 160), sixteen alignments per wavefront, a skew of 7 steps.  Taken for the batch's top class
+// (a class below it holds reads of any length up to its rows) when every read of the batch fits the rows — the batch's
+// longest read is known on the host — and they are fewer than the sixteen-lane class's.  No snapshots in this geometry
+// (pass 2 re-computes from step 0): the caller asks only for launches that leave none.
+const void *g8_kernel(int score_g8, int cls, int max_lq) {
+    const int rows16 = 16 * class_rows(cls);
+    if (!score_g8 || max_lq > rows16) return nullptr;
+    if (max_lq <= 40 && rows16 > 40) return (const void *)sw_pk_kernel<5, 1, false, 8>;
+    if (max_lq <= 56 && rows16 > 56) return (const void *)sw_pk_kernel<7, 1, false, 8>;
+    if (max_lq <= 80 && rows16 > 80) return (const void *)sw_pk_kernel<10, 1, false, 8>;
+    if (max_lq <= 104 && rows16 > 104) return (const void *)sw_pk_kernel<13, 1, false, 8>;
+    if (max_lq <= 152 && rows16 > 152 && rows16 <= 160)
+        return score_g8 == 2 ? (const void *)sw_pk_kernel<19, 1, false, 8, false, 2> : (const void *)sw_pk_kernel<19, 1, false, 8>;
+    return nullptr;
+}
+
+// every alignment kernel takes one SwArgs by value and runs in blocks of one wavefront
+int launch_sw(fadehip_ctx *ctx, const void *fn, int grid, size_t lds, hipStream_t st, SwArgs a) {
+    void *args[] = {&a};
+    HIPCHK(ctx, hipLaunchKernel(fn, dim3((unsigned)grid), dim3(64), args, lds, st));
     return 0;
 }
 
@@ -479,26 +487,76 @@ int resident_waves(fadehip_ctx *ctx, int cls, int mode, size_t lds, bool longw) 
     auto it = ctx->resident.find(key);
     if (it != ctx->resident.end()) return it->second;
     int per_cu = 0;
-    const void *fn = pk_kernel_ptr<0>(cls, mode, longw);
+    const void *fn = sw_kernel(cls, mode, longw);
     if (!fn || hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64, lds) != hipSuccess || per_cu <= 0) per_cu = 4;
     const int w = per_cu * std::max(ctx->cu_count, 1);
     ctx->resident[key] = w;
     return w;
 }
 
+// One list of a run, as the class runners see it.  The defaults are level 1's (no gate, no per-read status, untimed).
 struct ClassRun {
-    int cls;
-    const Work *work;
-    const Meta *meta;
-    int n_bound;                // items on the list, at most
-    const uint32_t *count_dev;  // where the device keeps the real count
-    int max_lr;                 // longest window, at most
-    const uint8_t *q_nib, *r_nib;
-    fadehip_aln *out;
-    uint8_t *rs;
-    int floor_len, gate;
-    int64_t budget;
+    int cls = 0;
+    const Work *work = nullptr;
+    const Meta *meta = nullptr;
+    int n_bound = 0;                      // items on the list, at most
+    const uint32_t *count_dev = nullptr;  // where the device keeps the real count
+    int max_lr = 0;                       // longest window, at most
+    const uint8_t *q_nib = nullptr, *r_nib = nullptr;
+    fadehip_aln *out = nullptr;
+    uint8_t *rs = nullptr;
+    int floor_len = 0, gate = 0;
+    int64_t budget = 0;
+    bool timed = false;
+};
+
+// The score arguments every wave kernel's launch shares, for items [i0, i0 + n) of the list.
+SwArgs sw_args(const fadehip_ctx *ctx, const Slot &s, const ClassRun &c, int64_t i0, int n) {
+    SwArgs a;
+    memset(&a, 0, sizeof a);
+    a.work = c.work + i0;
+    a.n_items = n;
+    a.q_nib = c.q_nib;
+    a.r_nib = c.r_nib;
+    a.fwd = (Fwd *)s.fwd.p + i0;
+    a.sc = ctx->sc;
+    return a;
+}
+
+// The common traceback for items [i0, i0 + n) of the list.  t holds what differs between the forward kernels (R, packed,
+// the trace and its stride, and count_dev / item_base where n is a bound); everything else is filled in here.
+int launch_traceback(fadehip_ctx *ctx, Slot &s, hipStream_t st, const ClassRun &c, int64_t i0, int n, TbArgs t) {
+    t.work = c.work + i0;
+    t.meta = c.meta ? c.meta + i0 : nullptr;
+    t.fwd = (Fwd *)s.fwd.p + i0;
+    t.n_items = n;
+    t.q_nib = c.q_nib;
+    t.r_nib = c.r_nib;
+    t.sc = ctx->sc;
+    t.out = c.out;
+    t.rs = c.rs;
+    t.stats = (c.rs && c.gate) ? s.d_stats() : nullptr;
+    t.floor_len = c.floor_len;
+    t.gate = c.gate;
+    t.early_out = 0;
+    hipLaunchKernelGGL(traceback_kernel, dim3((n + 63) / 64), dim3(64), 0, st, t);
+    HIPCHK(ctx, hipGetLastError());
+    return 0;
+}
+
+// The three timing events of one chunk of a timed run: 0 before the forward launch, 1 between it and the traceback, 2
+// behind the traceback, which also files the chunk's two spans.  An untimed run records nothing.
+struct ChunkSpans {
     bool timed;
+    int e[3] = {-1, -1, -1};
+    int mark(fadehip_ctx *ctx, Slot &s, int k, hipStream_t on) {
+        if (!timed) return 0;
+        const int rc = record(ctx, s, &e[k], on);
+        if (rc || k < 2) return rc;
+        s.fwd_spans.push_back({e[0], e[1]});
+        s.tb_spans.push_back({e[1], e[2]});
+        return 0;
+    }
 };
 
 // Sizes of the two-pass path for one class list: launch geometry and scratch.  Computed for every class of a run before
@@ -568,10 +626,6 @@ int run_class_two_pass(fadehip_ctx *ctx, Slot &s, hipStream_t st, const ClassRun
     TwoPassPlan p;
     int rc;
     if ((rc = plan_two_pass(ctx, s, c, p))) return rc;
-    const int n_ck = p.n_ck, ref_stride1 = p.ref_stride1, mode2 = p.mode2, total_oct = p.total_oct, p2_waves = p.p2_waves;
-    const uint64_t ck_stride = p.ck_stride, wave_stride = p.wave_stride;
-    const size_t lds1 = p.lds1;
-    const int64_t chunk_oct = p.chunk_oct;
     // (level 2 sized these for all classes before the run's first launch; a buffer that still has to grow here is parked,
     // not freed: earlier launches of this run may be using it)
     if ((rc = reserve_run(ctx, s.trash, s.ckpt, p.ckpt_bytes)) || (rc = reserve_run(ctx, s.trash, s.fwd, p.fwd_bytes)) ||
@@ -579,32 +633,25 @@ int run_class_two_pass(fadehip_ctx *ctx, Slot &s, hipStream_t st, const ClassRun
         return rc;
     s.prof_counts[2] = std::max<int64_t>(s.prof_counts[2], (int64_t)p.trace_bytes);
     uint32_t *const sel_counters = s.d_sel(cls);
-    for (int64_t o0 = 0; o0 < total_oct; o0 += chunk_oct) {
-        const int octs = (int)std::min<int64_t>(chunk_oct, total_oct - o0);
+    const void *const score_fn = sw_kernel(cls, 1, p.longw), *const trace_fn = sw_kernel(cls, p.mode2, p.longw);
+    if (!score_fn || !trace_fn) return set_err(ctx, FADEHIP_E_INVALID, "bad class %d", cls);
+    const void *const g8_fn = !p.longw && p.n_ck == 0 ? g8_kernel(ctx->score_g8, cls, s.max_lq) : nullptr;
+    for (int64_t o0 = 0; o0 < p.total_oct; o0 += p.chunk_oct) {
+        const int octs = (int)std::min<int64_t>(p.chunk_oct, p.total_oct - o0);
         const int i0 = (int)(o0 * 8);
         const int n = std::min(n_items - i0, octs * 8);
         if (!s.sel_fresh[cls]) HIPCHK(ctx, hipMemsetAsync(sel_counters, 0, sizeof(uint32_t) * NUM_BUCKETS, st));
         s.sel_fresh[cls] = false;
-        SwArgs a;
-        memset(&a, 0, sizeof a);
-        a.work = c.work + i0;
-        a.n_items = n;
-        a.q_nib = c.q_nib;
-        a.r_nib = c.r_nib;
-        a.trace = nullptr;
-        a.quad_stride = 0;
-        a.ref_stride = ref_stride1;
-        a.fwd = (Fwd *)s.fwd.p + i0;
-        a.sc = ctx->sc;
-        a.cand = nullptr;
+        SwArgs a = sw_args(ctx, s, c, i0, n);
+        a.ref_stride = p.ref_stride1;
         a.ckpt = (uint32_t *)s.ckpt.p;
-        a.ck_stride = ck_stride;
-        a.n_ck = n_ck;
+        a.ck_stride = p.ck_stride;
+        a.n_ck = p.n_ck;
         a.count_dev = c.count_dev;
         a.item_base = (uint32_t)i0;
         // the selection rides in the score pass's waves
         a.sel.enabled = 1;
-        a.sel.no_ckpt = n_ck == 0 ? 1 : 0;
+        a.sel.no_ckpt = p.n_ck == 0 ? 1 : 0;
         a.sel.meta = c.meta ? c.meta + i0 : nullptr;
         a.sel.floor_len = c.floor_len;
         a.sel.trace_all = ctx->prm.trace_all;
@@ -618,7 +665,6 @@ int run_class_two_pass(fadehip_ctx *ctx, Slot &s, hipStream_t st, const ClassRun
         a.sel.gate = c.gate;
         a.sel.match = getenv("FADEHIP_NO_SHORTCUT") ? 0 : ctx->sc.match;  // read per run: a test flips it on a live ctx
         a.sel.mismatch = ctx->sc.mismatch;
-        int e0 = -1, e1 = -1, e2 = -1;
         // the score pass goes to the slot's CU-masked stream (fork / join by events); its timing events are recorded there
         hipStream_t sst = s.score_stream ? s.score_stream : st;
         if (sst != st) {
@@ -626,46 +672,31 @@ int run_class_two_pass(fadehip_ctx *ctx, Slot &s, hipStream_t st, const ClassRun
             if ((rc = record(ctx, s, &ef, st))) return rc;
             HIPCHK(ctx, hipStreamWaitEvent(sst, s.ev[ef], 0));
         }
-        if (c.timed && (rc = record(ctx, s, &e0, sst))) return rc;
+        ChunkSpans sp{c.timed};
+        if ((rc = sp.mark(ctx, s, 0, sst))) return rc;
+        const void *fn1 = score_fn;
         int waves1 = octs;
+        size_t lds = p.lds1;
         if (ctx->score_persist && class_rows(cls) == 10 && !p.longw && s.tickets_used < (int)Slot::N_TICKETS) {
             // the A/B variant: as many waves as the CUs of the stream hold at once, each drawing octets by ticket
-            const int res = resident_waves(ctx, cls, 1, lds1, p.longw);
+            const int res = resident_waves(ctx, cls, 1, p.lds1, p.longw);
             const int cus = std::max(ctx->cu_count, 1), mine = s.score_stream ? std::max(cus - 8 * ctx->tail_cus_per_xcd, 1) : cus;
+            fn1 = (const void *)sw_pk_kernel<10, 1, false, 16, true>;
             waves1 = std::max(1, std::min(octs, (int)((int64_t)res * mine / cus)));
             a.ticket = s.d_ticket(s.tickets_used++);
-        }
-        // the other A/B variant: eight-lane groups, 19 rows per lane (152 rows for reads of up to 152 bases in the 160-row class),
-        // sixteen alignments per wavefront; no snapshots in this geometry (pass 2 re-computes from step 0)
-        // Eight-lane groups: a lane owns R8 rows of 8 R8 — rows in steps of 8 instead of 16 (36-base reads: 40 rows instead of
-        // 64; 50: 56 / 64; 76: 80 / 96; 100, 101: 104 / 128; 150, 151: 152 / 160), sixteen alignments per wavefront, a skew of 7
-        // steps.  Taken when every read of the batch fits the rows (the batch's longest read is known: s.max_lq) and they are
-        // fewer than the sixteen-lane class's; no snapshots in this geometry (pass 2 re-computes from step 0).
-        const void *g8_fn = nullptr;
-        if (ctx->score_g8 && !p.longw && n_ck == 0 && !a.ticket) {
-            const int rows16 = 16 * class_rows(cls), lq = std::min(s.max_lq, rows16);
-            if (lq <= 40 && rows16 > 40) g8_fn = (const void *)sw_pk_kernel<5, 1, false, 8>;
-            else if (lq <= 56 && rows16 > 56) g8_fn = (const void *)sw_pk_kernel<7, 1, false, 8>;
-            else if (lq <= 80 && rows16 > 80) g8_fn = (const void *)sw_pk_kernel<10, 1, false, 8>;
-            else if (lq <= 104 && rows16 > 104) g8_fn = (const void *)sw_pk_kernel<13, 1, false, 8>;
-            else if (lq <= 152 && rows16 > 152 && rows16 <= 160)
-                g8_fn = ctx->score_g8 == 2 ? (const void *)sw_pk_kernel<19, 1, false, 8, false, 2> : (const void *)sw_pk_kernel<19, 1, false, 8>;
-            // (a class below the batch's top class holds reads of ITS row range only, which the kernel chosen for min(max_lq, rows) covers)
-            if (g8_fn && s.max_lq > rows16) g8_fn = nullptr;  // (not the top class: its reads may be any length up to rows16)
-        }
-        if (g8_fn) {
+        } else if (g8_fn) {  // sixteen alignments per wavefront, two groups' windows in LDS
             if (ctx->debug && o0 == 0) fprintf(stderr, "[fadehip] class of %d rows: score pass on eight-lane groups (longest read of the batch: %d)\n", 16 * class_rows(cls), s.max_lq);
-            SwArgs copy = a;
-            void *args[] = {&copy};
-            HIPCHK(ctx, hipLaunchKernel(g8_fn, dim3((unsigned)((n + 15) / 16)), dim3(64), args, 2 * lds1, sst));
-        } else if (a.ticket) {
-            SwArgs copy = a;
-            void *args[] = {&copy};
-            HIPCHK(ctx, hipLaunchKernel((const void *)sw_pk_kernel<10, 1, false, 16, true>, dim3((unsigned)waves1), dim3(64), args, lds1, sst));
-        } else if ((rc = launch_pk_mode(ctx, cls, 1, a, waves1, lds1, sst, p.longw))) return rc;
-        a.ticket = nullptr;
-        if ((c.timed || sst != st) && (rc = record(ctx, s, &e1, sst))) return rc;
-        if (sst != st) HIPCHK(ctx, hipStreamWaitEvent(st, s.ev[e1], 0));
+            fn1 = g8_fn;
+            waves1 = (n + 15) / 16;
+            lds = 2 * p.lds1;
+        }
+        if ((rc = launch_sw(ctx, fn1, waves1, lds, sst, a))) return rc;
+        if ((rc = sp.mark(ctx, s, 1, sst))) return rc;
+        if (sst != st) {
+            int ej = sp.e[1];  // the join waits for the timing event where there is one
+            if (ej < 0 && (rc = record(ctx, s, &ej, sst))) return rc;
+            HIPCHK(ctx, hipStreamWaitEvent(st, s.ev[ej], 0));
+        }
         // pass 2 + tracebacks + re-traced paths: one persistent launch
         if (s.tickets_used >= (int)Slot::N_TICKETS)
             return set_err(ctx, FADEHIP_E_UNSUPPORTED, "more than %d pass-2 launches in one run (raise trace_bytes)", (int)Slot::N_TICKETS);
@@ -677,7 +708,7 @@ int run_class_two_pass(fadehip_ctx *ctx, Slot &s, hipStream_t st, const ClassRun
         b2.bucket_n = sel_counters;
         b2.cand_total = &s.d_plan()->cand_total;
         b2.trace = (uint32_t *)s.trace.p;
-        b2.quad_stride = wave_stride;
+        b2.quad_stride = p.wave_stride;
         b2.count_dev = nullptr;
         b2.ticket = s.d_ticket(s.tickets_used++);
         b2.meta = c.meta ? c.meta + i0 : nullptr;
@@ -688,12 +719,8 @@ int run_class_two_pass(fadehip_ctx *ctx, Slot &s, hipStream_t st, const ClassRun
         b2.gate = c.gate;
         b2.early_out = (c.gate && c.meta && !ctx->prm.trace_all) ? 1 : 0;
         b2.rerun_total = &s.d_plan()->rerun_total;
-        if ((rc = launch_pk_mode(ctx, cls, mode2, b2, std::min(p2_waves, octs + NUM_BUCKETS), lds1, st, p.longw))) return rc;
-        if (c.timed) {
-            if ((rc = record(ctx, s, &e2))) return rc;
-            s.fwd_spans.push_back({e0, e1});
-            s.tb_spans.push_back({e1, e2});
-        }
+        if ((rc = launch_sw(ctx, trace_fn, std::min(p.p2_waves, octs + NUM_BUCKETS), p.lds1, st, b2))) return rc;
+        if ((rc = sp.mark(ctx, s, 2, st))) return rc;
     }
     return 0;
 }
@@ -719,61 +746,35 @@ int run_class_single(fadehip_ctx *ctx, Slot &s, hipStream_t st, const ClassRun &
     if (rc) return rc;
     rc = reserve_run(ctx, s.trash, s.fwd, (size_t)n_items * sizeof(Fwd));
     if (rc) return rc;
+    const void *const fn = sw_kernel(cls, packed ? 0 : SW_INT32, n_blocks > CH_BLOCKS);
+    if (!fn) return set_err(ctx, FADEHIP_E_INVALID, "bad class %d", cls);
     for (int64_t q0 = 0; q0 < total_quads; q0 += chunk_quads) {
         const int quads = (int)std::min<int64_t>(chunk_quads, total_quads - q0);
         const int i0 = (int)(q0 * per_wave);
         const int n = std::min(n_items - i0, quads * per_wave);
-        SwArgs a;
-        memset(&a, 0, sizeof a);
-        a.work = c.work + i0;
-        a.n_items = n;
-        a.q_nib = c.q_nib;
-        a.r_nib = c.r_nib;
+        SwArgs a = sw_args(ctx, s, c, i0, n);
         a.trace = (uint32_t *)s.trace.p;
         a.quad_stride = quad_stride;
         a.ref_stride = ref_stride;
-        a.fwd = (Fwd *)s.fwd.p + i0;
-        a.sc = ctx->sc;
-        int e0 = -1, e1 = -1, e2 = -1;
-        if (c.timed && (rc = record(ctx, s, &e0))) return rc;
-        rc = launch_forward_c<0>(ctx, cls, a, quads, lds, st, packed, n_blocks > CH_BLOCKS);
-        if (rc) return rc;
-        if (c.timed && (rc = record(ctx, s, &e1))) return rc;
-        TbArgs t;
-        memset(&t, 0, sizeof t);
-        t.work = c.work + i0;
-        t.meta = c.meta ? c.meta + i0 : nullptr;
-        t.fwd = (Fwd *)s.fwd.p + i0;
-        t.n_items = n;
+        ChunkSpans sp{c.timed};
+        if ((rc = sp.mark(ctx, s, 0, st))) return rc;
+        if ((rc = launch_sw(ctx, fn, quads, lds, st, a))) return rc;
+        if ((rc = sp.mark(ctx, s, 1, st))) return rc;
+        TbArgs t = {};  // (count_dev stays null: n is exact here, the host read the counts back)
         t.R = R;
-        t.q_nib = c.q_nib;
-        t.r_nib = c.r_nib;
+        t.packed = packed ? 1 : 0;
         t.trace = (const uint32_t *)s.trace.p;
         t.quad_stride = quad_stride;
-        t.sc = ctx->sc;
-        t.out = c.out;
-        t.rs = c.rs;
-        t.stats = (c.rs && c.gate) ? s.d_stats() : nullptr;
-        t.floor_len = c.floor_len;
-        t.gate = c.gate;
-        t.early_out = 0;
-        t.packed = packed ? 1 : 0;
-        hipLaunchKernelGGL(traceback_kernel, dim3((n + 63) / 64), dim3(64), 0, st, t);
-        HIPCHK(ctx, hipGetLastError());
-        if (c.timed) {
-            if ((rc = record(ctx, s, &e2))) return rc;
-            s.fwd_spans.push_back({e0, e1});
-            s.tb_spans.push_back({e1, e2});
-        }
+        if ((rc = launch_traceback(ctx, s, st, c, i0, n, t))) return rc;
+        if ((rc = sp.mark(ctx, s, 2, st))) return rc;
         s.prof_counts[2] += (int64_t)quads * quad_bytes;
     }
     return 0;
 }
 
-// Queries longer than 512 bases (or windows beyond the wave kernels' LDS): sw_long_kernel (thread per alignment, full
-// trace) + the common traceback.  n_bound / max_lq / max_lr are upper bounds, the live count stays on the device.
 // Long list on the wave kernel with one alignment per wavefront (sw_forward64_kernel): reads of up to 4,096 bases, windows
 // of up to LONG_WAVE_MAX_WINDOW columns, under the default end-cell and gap-tie rules (the kernel's flags are those rules').
+// n_bound / max_lq / max_lr are upper bounds, the live count stays on the device.
 constexpr int LONG_WAVE_MAX_QUERY = 4096, LONG_WAVE_MAX_WINDOW = 65000;
 int run_long_wave(fadehip_ctx *ctx, Slot &s, hipStream_t st, const ClassRun &c, int max_lq) {
     const int n_items = c.n_bound, max_lr = c.max_lr;
@@ -788,66 +789,35 @@ int run_long_wave(fadehip_ctx *ctx, Slot &s, hipStream_t st, const ClassRun &c, 
     if ((rc = reserve_run(ctx, s.trash, s.fwd, (size_t)n_items * sizeof(Fwd))) || (rc = reserve_run(ctx, s.trash, s.trace, (size_t)(chunk * item_bytes)))) return rc;
     for (int64_t i0 = 0; i0 < n_items; i0 += chunk) {
         const int n = (int)std::min<int64_t>(chunk, n_items - i0);
-        SwArgs a;
-        memset(&a, 0, sizeof a);
-        a.work = c.work + i0;
-        a.n_items = n;
-        a.q_nib = c.q_nib;
-        a.r_nib = c.r_nib;
+        SwArgs a = sw_args(ctx, s, c, i0, n);
         a.trace = (uint32_t *)s.trace.p;
         a.quad_stride = quad_stride;
         a.ref_stride = (int32_t)lds;
-        a.fwd = (Fwd *)s.fwd.p + i0;
-        a.sc = ctx->sc;
         a.count_dev = c.count_dev;
         a.item_base = (uint32_t)i0;
-        int e0 = -1, e1 = -1, e2 = -1;
-        if (c.timed && (rc = record(ctx, s, &e0))) return rc;
-        if (R == 12) hipLaunchKernelGGL(HIP_KERNEL_NAME(sw_forward64_kernel<12>), dim3(n), dim3(64), lds, st, a);
-        else if (R == 16) hipLaunchKernelGGL(HIP_KERNEL_NAME(sw_forward64_kernel<16>), dim3(n), dim3(64), lds, st, a);
-        else if (R == 24) hipLaunchKernelGGL(HIP_KERNEL_NAME(sw_forward64_kernel<24>), dim3(n), dim3(64), lds, st, a);
-        else if (R == 32) hipLaunchKernelGGL(HIP_KERNEL_NAME(sw_forward64_kernel<32>), dim3(n), dim3(64), lds, st, a);
-        else if (R == 48) hipLaunchKernelGGL(HIP_KERNEL_NAME(sw_forward64_kernel<48>), dim3(n), dim3(64), lds, st, a);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(sw_forward64_kernel<64>), dim3(n), dim3(64), lds, st, a);
-        HIPCHK(ctx, hipGetLastError());
-        if (c.timed && (rc = record(ctx, s, &e1))) return rc;
-        TbArgs t;
-        memset(&t, 0, sizeof t);
-        t.work = c.work + i0;
-        t.meta = c.meta ? c.meta + i0 : nullptr;
-        t.fwd = (Fwd *)s.fwd.p + i0;
-        t.n_items = n;
+        ChunkSpans sp{c.timed};
+        if ((rc = sp.mark(ctx, s, 0, st))) return rc;
+        if ((rc = launch_sw(ctx, sw64_kernel(R), n, lds, st, a))) return rc;
+        if ((rc = sp.mark(ctx, s, 1, st))) return rc;
+        TbArgs t = {};
         t.R = R;
-        t.q_nib = c.q_nib;
-        t.r_nib = c.r_nib;
+        t.packed = 3;
         t.trace = (const uint32_t *)s.trace.p;
         t.quad_stride = quad_stride;
-        t.sc = ctx->sc;
-        t.out = c.out;
-        t.rs = c.rs;
-        t.stats = (c.rs && c.gate) ? s.d_stats() : nullptr;
-        t.floor_len = c.floor_len;
-        t.gate = c.gate;
-        t.early_out = 0;
-        t.packed = 3;
         t.count_dev = c.count_dev;
         t.item_base = (uint32_t)i0;
-        hipLaunchKernelGGL(traceback_kernel, dim3((n + 63) / 64), dim3(64), 0, st, t);
-        HIPCHK(ctx, hipGetLastError());
-        if (c.timed) {
-            if ((rc = record(ctx, s, &e2))) return rc;
-            s.fwd_spans.push_back({e0, e1});
-            s.tb_spans.push_back({e1, e2});
-        }
+        if ((rc = launch_traceback(ctx, s, st, c, i0, n, t))) return rc;
+        if ((rc = sp.mark(ctx, s, 2, st))) return rc;
         s.prof_counts[2] += (int64_t)n * item_bytes;
     }
     return 0;
 }
 
+// Queries longer than 512 bases (or windows beyond the wave kernels' LDS): what the one-alignment-per-wave kernel holds
+// goes there; sw_long_kernel (thread per alignment, full trace) + the common traceback keep the rest (longer reads, wider
+// windows, the non-default end-cell / gap-tie rules: FADEHIP_LONG_THREAD=1 sends everything to it, for A/B runs).
 int run_long(fadehip_ctx *ctx, Slot &s, hipStream_t st, const ClassRun &c, int max_lq) {
     const int n_items = c.n_bound, max_lr = c.max_lr;
-    // what the one-alignment-per-wave kernel holds goes there; the thread-per-alignment kernel below keeps the rest (longer
-    // reads, wider windows, the non-default end-cell / gap-tie rules: FADEHIP_LONG_THREAD=1 sends everything to it, for A/B runs)
     const uint32_t need_rules = FADEHIP_RULE_END_MIN_REF_THEN_QUERY | FADEHIP_RULE_GAP_TIE_EXTENDS;
     if (max_lq <= LONG_WAVE_MAX_QUERY && max_lr <= LONG_WAVE_MAX_WINDOW && (ctx->sc.rules & need_rules) == need_rules && !getenv("FADEHIP_LONG_THREAD"))
         return run_long_wave(ctx, s, st, c, max_lq);
@@ -880,39 +850,20 @@ int run_long(fadehip_ctx *ctx, Slot &s, hipStream_t st, const ClassRun &c, int m
         a.sc = ctx->sc;
         a.count_dev = c.count_dev;
         a.item_base = (uint32_t)i0;
-        int e0 = -1, e1 = -1, e2 = -1;
-        if (c.timed && (rc = record(ctx, s, &e0))) return rc;
+        ChunkSpans sp{c.timed};
+        if ((rc = sp.mark(ctx, s, 0, st))) return rc;
         hipLaunchKernelGGL(sw_long_kernel, dim3((n + 63) / 64), dim3(64), 0, st, a);
         HIPCHK(ctx, hipGetLastError());
-        if (c.timed && (rc = record(ctx, s, &e1))) return rc;
-        TbArgs t;
-        memset(&t, 0, sizeof t);
-        t.work = c.work + i0;
-        t.meta = c.meta ? c.meta + i0 : nullptr;
-        t.fwd = (Fwd *)s.fwd.p + i0;
-        t.n_items = n;
+        if ((rc = sp.mark(ctx, s, 1, st))) return rc;
+        TbArgs t = {};
         t.R = 1;
-        t.q_nib = c.q_nib;
-        t.r_nib = c.r_nib;
-        t.sc = ctx->sc;
-        t.out = c.out;
-        t.rs = c.rs;
-        t.stats = (c.rs && c.gate) ? s.d_stats() : nullptr;
-        t.floor_len = c.floor_len;
-        t.gate = c.gate;
-        t.early_out = 0;
         t.packed = 2;
         t.ltrace = (const uint8_t *)s.trace.p;
         t.lhalf = lhalf;
         t.count_dev = c.count_dev;
         t.item_base = (uint32_t)i0;
-        hipLaunchKernelGGL(traceback_kernel, dim3((n + 63) / 64), dim3(64), 0, st, t);
-        HIPCHK(ctx, hipGetLastError());
-        if (c.timed) {
-            if ((rc = record(ctx, s, &e2))) return rc;
-            s.fwd_spans.push_back({e0, e1});
-            s.tb_spans.push_back({e1, e2});
-        }
+        if ((rc = launch_traceback(ctx, s, st, c, i0, n, t))) return rc;
+        if ((rc = sp.mark(ctx, s, 2, st))) return rc;
         s.prof_counts[2] += (int64_t)max_lq * lhalf * n;
     }
     return 0;
@@ -1036,6 +987,26 @@ int plan_run(fadehip_ctx *ctx, Slot &s) {
     return 0;
 }
 
+// List c of the slot's level-2 run, at the bounds plan_run left (the caller lowers n_bound where it knows the count).
+ClassRun level2_class_run(const fadehip_ctx *ctx, const Slot &s, int c, int64_t budget) {
+    ClassRun cr;
+    cr.cls = c;
+    cr.work = (const Work *)s.work[c].p;
+    cr.meta = (const Meta *)s.meta[c].p;
+    cr.n_bound = (int)s.bound[c];
+    cr.count_dev = s.d_counters() + c;
+    cr.max_lr = c == LONG_LIST ? s.long_max_lr : std::max(s.wave_lr_bound, 1);
+    cr.q_nib = d_arr<uint8_t>(s, A_SEQ);
+    cr.r_nib = (const uint8_t *)ctx->genome.p;
+    cr.out = (fadehip_aln *)s.aln.p;
+    cr.rs = (uint8_t *)s.rs.p;
+    cr.floor_len = s.floor_len;
+    cr.gate = 1;
+    cr.budget = budget;
+    cr.timed = true;
+    return cr;
+}
+
 // Enqueue one whole run of the slot's uploaded batch on its stream (two-pass path: nothing is read back).
 int enqueue_run(fadehip_ctx *ctx, Slot &s) {
     hipStream_t st = s.stream;
@@ -1068,24 +1039,6 @@ int enqueue_run(fadehip_ctx *ctx, Slot &s) {
     // snapshots only when the slot's previous run had many pass-2 candidates (plan_two_pass); FADEHIP_CKPT=0/1 pins it
     s.use_ckpt = s.last_cand * 32 > std::max<int64_t>(s.last_aln, 1);
     if (const char *kv = getenv("FADEHIP_CKPT")) s.use_ckpt = atoi(kv) != 0;
-    auto class_run = [&](int c) {
-        ClassRun cr;
-        cr.cls = c;
-        cr.work = (const Work *)s.work[c].p;
-        cr.meta = (const Meta *)s.meta[c].p;
-        cr.n_bound = (int)s.bound[c];
-        cr.count_dev = s.d_counters() + c;
-        cr.max_lr = c == LONG_LIST ? s.long_max_lr : std::max(s.wave_lr_bound, 1);
-        cr.q_nib = d_arr<uint8_t>(s, A_SEQ);
-        cr.r_nib = (const uint8_t *)ctx->genome.p;
-        cr.out = (fadehip_aln *)s.aln.p;
-        cr.rs = (uint8_t *)s.rs.p;
-        cr.floor_len = floor_len;
-        cr.gate = 1;
-        cr.budget = budget;
-        cr.timed = true;
-        return cr;
-    };
     if (ctx->two_pass) {
         // the scratch of every class of this run, sized once before the first launch (nothing is re-allocated between
         // kernels already queued; the slot is idle here: run waited for its previous results)
@@ -1093,7 +1046,7 @@ int enqueue_run(fadehip_ctx *ctx, Slot &s) {
         for (int c = 0; c < NUM_CLASSES; c++) {
             if (!s.bound[c]) continue;
             TwoPassPlan p;
-            if ((rc = plan_two_pass(ctx, s, class_run(c), p))) return rc;
+            if ((rc = plan_two_pass(ctx, s, level2_class_run(ctx, s, c, budget), p))) return rc;
             need_ckpt = std::max(need_ckpt, p.ckpt_bytes);
             need_fwd = std::max(need_fwd, p.fwd_bytes);
             need_trace = std::max(need_trace, p.trace_bytes);
@@ -1153,13 +1106,13 @@ int enqueue_run(fadehip_ctx *ctx, Slot &s) {
     }
     for (int c = 0; c < NUM_CLASSES; c++) {
         if (!exact[c]) continue;
-        ClassRun cr = class_run(c);
+        ClassRun cr = level2_class_run(ctx, s, c, budget);
         cr.n_bound = (int)exact[c];
         rc = ctx->two_pass ? run_class_two_pass(ctx, s, st, cr) : run_class_single(ctx, s, st, cr);
         if (rc) return rc;
     }
     if (exact[LONG_LIST]) {
-        ClassRun cr = class_run(LONG_LIST);
+        ClassRun cr = level2_class_run(ctx, s, LONG_LIST, budget);
         cr.n_bound = (int)exact[LONG_LIST];
         if ((rc = run_long(ctx, s, st, cr, std::max(s.long_max_lq, 1)))) return rc;
     }
@@ -1705,21 +1658,16 @@ int fadehip_sw_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *q, const int64_
             // the lists come from the host here: their counts go where the gate leaves them at level 2
             hipLaunchKernelGGL(set_counts_kernel, dim3(1), dim3(1), 0, st, s.d_counters() + c, (uint32_t)lists[c].size());
             HIPCHK(ctx, hipGetLastError());
-            ClassRun cr;
+            ClassRun cr;  // no meta, no rs, no gate, untimed: the defaults
             cr.cls = c;
             cr.work = (const Work *)d_work.p + base;
-            cr.meta = nullptr;
             cr.n_bound = (int)lists[c].size();
             cr.count_dev = s.d_counters() + c;
             cr.max_lr = max_lr[c];
             cr.q_nib = (const uint8_t *)d_qn.p;
             cr.r_nib = (const uint8_t *)d_rn.p;
             cr.out = (fadehip_aln *)d_aln.p;
-            cr.rs = nullptr;
-            cr.floor_len = 0;
-            cr.gate = 0;
             cr.budget = budget;
-            cr.timed = false;
             if (c == LONG_LIST) rc = run_long(ctx, s, st, cr, max_long_lq);
             else rc = ctx->two_pass ? run_class_two_pass(ctx, s, st, cr) : run_class_single(ctx, s, st, cr);
             if (rc) {
