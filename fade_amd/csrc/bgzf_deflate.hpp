@@ -7,11 +7,11 @@
 // Per block (host/selftest/gpu_deflate_model.cpp is the algorithm of the smaller geometry on the CPU, checked with zlib's
 // inflate; it reproduces the device's output byte for byte):
 //   A  matches and the parse over pieces of 64 positions: token bitmap, match bitmap, match records.
-//        0x7f00-byte blocks (bgzf_deflate_body.hpp): the pieces in eight contiguous segments, a wave each — own hash table
+//        0x7f00-byte blocks (bgzf_deflate_g32.hpp): the pieces in eight contiguous segments, a wave each — own hash table
 //        (384 buckets of four 16-bit positions, the KB in front of the segment entered first), candidates = the bucket's four
 //        and the nearest of the distances 1..8, extended side by side in LDS, greedy parse with one step of laziness on
 //        64-bit lane masks; a match cut at its segment's end is lengthened again at the seam.  No wave waits for another.
-//        0xff00-byte blocks (bgzf_deflate_roles.hpp): round 3's pipeline of wave roles — one hasher over ONE table for the
+//        0xff00-byte blocks (bgzf_deflate_g64.hpp): round 3's pipeline of wave roles — one hasher over ONE table for the
 //        whole block, six extenders, one parser, rings between them: every match of the block in reach, half the rate.
 //   B  symbol histograms (8 sub-histograms against same-address LDS atomics), minimum-redundancy code lengths (Moffat &
 //      Katajainen in place), 15-bit limit, canonical codes; the waves that have no part in the code lengths sum the CRC-32
@@ -22,30 +22,18 @@
 // A second kernel scans the block sizes and a third assembles the BGZF members (header, payload, CRC32, ISIZE) into one
 // contiguous byte stream — in pinned host memory: what goes to the file.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include "bgzf_huff.hpp"
-
 // Two geometries.  64: htslib's 0xff00-byte blocks, the block and its tables fill the CU's LDS, one workgroup per CU, the
 // role pipeline — the smallest output (9.8 GB/s of payload).  32: 0x7f00-byte blocks, 80 KB of LDS, two workgroups of eight
 // waves per CU, phase A on per-wave segments (19 GB/s); the output is 0.6 % larger on uniform-quality BAM payload than the
 // other geometry's and 1-2 % larger where qualities run.  fadehip.hip picks per call: 32 while the stream is mostly
 // incompressible bases (ratio above 0.45: there zlib -6 is 2 % behind either), 64 otherwise, so that the output stays
 // below zlib -6's in both regimes (tests/test_gpu_bgzf.py).
-#define FADEHIP_BGZF_GEOM 64
-#define FADEHIP_BGZF_NS bgzf64
-#include "bgzf_deflate_roles.hpp"
-#undef FADEHIP_BGZF_GEOM
-#undef FADEHIP_BGZF_NS
-#define FADEHIP_BGZF_GEOM 32
-#define FADEHIP_BGZF_NS bgzf32
-#include "bgzf_deflate_body.hpp"
-#undef FADEHIP_BGZF_GEOM
-#undef FADEHIP_BGZF_NS
+#include "bgzf_deflate_common.hpp"  // what the two share, and the scan and pack kernels behind either
+#include "bgzf_deflate_g64.hpp"     // namespace bgzf64
+#include "bgzf_deflate_g32.hpp"     // namespace bgzf32
 
 namespace fadehip {
 namespace bgzf {
-using bgzf64::claim_ticket;  // (the inflater draws its tickets the same way)
 
 // Uncompressed BGZF (`fade annotate -u`, what htslib writes at level 0): a member = 18 bytes of header, one stored DEFLATE
 // block (5 bytes + the payload), CRC32, ISIZE.  Sizes are known in advance, so member k of a stream cut into STORE_BLOCK

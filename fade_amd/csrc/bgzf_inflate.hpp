@@ -20,7 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "bgzf_deflate.hpp"
+#include "bgzf_deflate_common.hpp"  // claim_ticket
 #include "bgzf_huff.hpp"
 
 namespace fadehip {

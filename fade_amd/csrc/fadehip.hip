@@ -2267,17 +2267,18 @@ static int bgzf_pick_geom_host(const fadehip_ctx *ctx, const uint8_t *p, size_t 
 // (host_out: pinned memory the members are packed into — the lane's own buffer when NULL.  A member is at most its block's
 // bytes + 5 (stored) + 26 of BGZF framing: the buffer is sized for that, the kernel writes through PCIe, and nothing but
 // the 8-byte total has to be copied afterwards.)
+static size_t bgzf_block_bytes(int geom) { return geom == 32 ? (size_t)bgzf32::BLOCK : (size_t)bgzf64::BLOCK; }
 static size_t bgzf_out_cap(size_t n_bytes, int geom) {
-    const size_t block = geom == 32 ? (size_t)bgzf32::BLOCK : (size_t)bgzf64::BLOCK;
+    const size_t block = bgzf_block_bytes(geom);
     return n_bytes + ((n_bytes + block - 1) / block) * 32 + 64;
 }
 static int bgzf_enqueue(fadehip_ctx *ctx, int lane, const uint8_t *d_src, size_t n_bytes, int geom, PinBuf *host_out = nullptr) {
     BgzfLane &l = ctx->bgzf[lane];
-    const size_t block = geom == 32 ? (size_t)bgzf32::BLOCK : (size_t)bgzf64::BLOCK;
+    const size_t block = bgzf_block_bytes(geom);
     const uint32_t nb = (uint32_t)((n_bytes + block - 1) / block);
     int rc;
     PinBuf &ob = host_out ? *host_out : l.out;
-    if ((rc = reserve(ctx, l.slots, (size_t)nb * bgzf64::SLOT)) || (rc = reserve(ctx, l.meta, (size_t)nb * 8 + 1024)) ||
+    if ((rc = reserve(ctx, l.slots, (size_t)nb * bgzf::SLOT)) || (rc = reserve(ctx, l.meta, (size_t)nb * 8 + 1024)) ||
         (rc = reserve(ctx, l.member_off, (size_t)nb * 8)) || (rc = reserve_pinned(ctx, ob, bgzf_out_cap(n_bytes, geom))))
         return rc;
     l.h_out = ob.p;
@@ -2290,35 +2291,25 @@ static int bgzf_enqueue(fadehip_ctx *ctx, int lane, const uint8_t *d_src, size_t
         HIPCHK(ctx, hipMemsetAsync(prof, 0, 64 + 8 * 72, l.stream));
     }
     const unsigned cus = (unsigned)std::max(ctx->cu_count, 1);
-    auto fill = [&](auto &a) {
-        a.src = d_src;
-        a.n_bytes = n_bytes;
-        a.n_blocks = nb;
-        a.slots = (uint8_t *)l.slots.p;
-        a.out_size = d_size;
-        a.out_crc = d_crc;
-        a.ticket = d_ticket;
-        a.prof = prof;
-    };
-    if (geom == 32) {
-        bgzf32::DeflateArgs a;
-        fill(a);
-        hipLaunchKernelGGL(bgzf32::bgzf_deflate_kernel, dim3(std::min<unsigned>(nb, 2u * cus)), dim3(bgzf32::WG), bgzf32::LDS_BYTES, l.stream, a);
-        HIPCHK(ctx, hipGetLastError());
-        hipLaunchKernelGGL(bgzf32::bgzf_scan_kernel, dim3(1), dim3(1024), 0, l.stream, (const uint32_t *)d_size, nb, (uint64_t *)l.member_off.p, d_total);
-        HIPCHK(ctx, hipGetLastError());
-        hipLaunchKernelGGL(bgzf32::bgzf_pack_kernel, dim3(nb), dim3(256), 0, l.stream, (const uint8_t *)l.slots.p, (const uint32_t *)d_size,
-                           (const uint32_t *)d_crc, (const uint64_t *)l.member_off.p, (uint64_t)n_bytes, nb, l.h_out);
-    } else {
-        bgzf64::DeflateArgs a;
-        fill(a);
-        hipLaunchKernelGGL(bgzf64::bgzf_deflate_kernel, dim3(std::min<unsigned>(nb, cus)), dim3(bgzf64::WG), bgzf64::LDS_BYTES, l.stream, a);
-        HIPCHK(ctx, hipGetLastError());
-        hipLaunchKernelGGL(bgzf64::bgzf_scan_kernel, dim3(1), dim3(1024), 0, l.stream, (const uint32_t *)d_size, nb, (uint64_t *)l.member_off.p, d_total);
-        HIPCHK(ctx, hipGetLastError());
-        hipLaunchKernelGGL(bgzf64::bgzf_pack_kernel, dim3(nb), dim3(256), 0, l.stream, (const uint8_t *)l.slots.p, (const uint32_t *)d_size,
-                           (const uint32_t *)d_crc, (const uint64_t *)l.member_off.p, (uint64_t)n_bytes, nb, l.h_out);
-    }
+    bgzf::DeflateArgs a;
+    a.src = d_src;
+    a.n_bytes = n_bytes;
+    a.n_blocks = nb;
+    a.slots = (uint8_t *)l.slots.p;
+    a.out_size = d_size;
+    a.out_crc = d_crc;
+    a.ticket = d_ticket;
+    a.prof = prof;
+    // the geometries differ in the deflate kernel and its launch (a workgroup per CU, or two) ...
+    if (geom == 32) hipLaunchKernelGGL(bgzf32::bgzf_deflate_kernel, dim3(std::min<unsigned>(nb, 2u * cus)), dim3(bgzf32::WG), bgzf32::LDS_BYTES, l.stream, a);
+    else hipLaunchKernelGGL(bgzf64::bgzf_deflate_kernel, dim3(std::min<unsigned>(nb, cus)), dim3(bgzf64::WG), bgzf64::LDS_BYTES, l.stream, a);
+    HIPCHK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(bgzf::bgzf_scan_kernel, dim3(1), dim3(1024), 0, l.stream, (const uint32_t *)d_size, nb, (uint64_t *)l.member_off.p, d_total);
+    HIPCHK(ctx, hipGetLastError());
+    // ... and in the block size the pack kernel writes ISIZE from
+    const auto pack = geom == 32 ? bgzf::bgzf_pack_kernel<bgzf32::BLOCK> : bgzf::bgzf_pack_kernel<bgzf64::BLOCK>;
+    hipLaunchKernelGGL(pack, dim3(nb), dim3(256), 0, l.stream, (const uint8_t *)l.slots.p, (const uint32_t *)d_size, (const uint32_t *)d_crc,
+                       (const uint64_t *)l.member_off.p, (uint64_t)n_bytes, nb, l.h_out);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(l.h_total, d_total, 8, hipMemcpyDeviceToHost, l.stream));
     HIPCHK(ctx, hipEventRecord(l.done, l.stream));
@@ -2386,7 +2377,7 @@ int fadehip_bgzf_deflate_wait(fadehip_ctx *ctx, int lane, const uint8_t **out, s
                     (double)pr[60] / l.n_blocks, (double)pr[61] / l.n_blocks, (double)pr[62] / l.n_blocks, (double)pr[63] / l.n_blocks, (double)pr[64] / l.n_blocks, (double)pr[65] / l.n_blocks);
         }
     }
-    if (total == 0 || total > (uint64_t)l.n_blocks * bgzf64::SLOT) {
+    if (total == 0 || total > (uint64_t)l.n_blocks * bgzf::SLOT) {
         // a block whose pipeline timed out reports size ~0 and, as its CRC, the wait that gave up (role << 28 | piece)
         std::vector<uint32_t> meta(2 * (size_t)l.n_blocks);
         unsigned bad = 0, why = 0;

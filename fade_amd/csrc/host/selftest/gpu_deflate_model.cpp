@@ -23,7 +23,8 @@ namespace {
 
 constexpr int WG = 256, MIN_MATCH = 4, MAX_MATCH = 258, MAXW = 16;
 int WAYS = 4;
-// the two geometries of bgzf_deflate_body.hpp, and the knobs of phase A (model only: the device's are constants)
+// the geometry of bgzf_deflate_g32.hpp's phase A (main runs the device's, 0x7f00-byte blocks, and the same phase on 0xff00-byte
+// blocks, which the device does not build), and the knobs of phase A (model only: the device's are constants)
 int BLOCK = 0xff00, N_SEG = 8, N_BUCKETS = 512, SEG_CAP = (8192 + 2560) / 8, SEED_PIECES = 16;
 bool SKIP_RUNS = false, SEAM = true;
 int SHORT4 = 32768, SHORT5 = 32768, SHORT6 = 32768, NEAR = 2;
@@ -42,7 +43,7 @@ std::vector<uint8_t> model_deflate(const uint8_t *src, int n, bool lazy) {
     std::vector<uint32_t> match_rec;
     const int n_words = (BLOCK + 31) / 32;
     std::vector<uint32_t> tok((size_t)n_words + 2, 0), mat((size_t)n_words + 2, 0);
-    // ---- phase A (bgzf_deflate_body.hpp phase_a_segment): the block's pieces of 64 positions in N_SEG segments, each with a
+    // ---- phase A (bgzf_deflate_g32.hpp phase_a_segment): the block's pieces of 64 positions in N_SEG segments, each with a
     // hash table of its own (N_BUCKETS x 4 ways, newest first), seeded with the SEED_PIECES pieces in front of it; a
     // position's candidates: the nearest of the distances 1..8 whose four bytes agree, and its bucket's four; greedy parse on
     // 64-position masks with one step of laziness; a match ends with its segment, and the seam gives it back what the next
