@@ -216,6 +216,7 @@ struct fadehip_ctx {
     int score_g8 = 1;            // the score pass on eight-lane groups where the batch's reads fit them (g8_kernel; FADEHIP_SCORE_G8=0: sixteen-lane groups only; 2: the 152-row kernel at two waves per SIMD)
     bool blocking_sync = false;  // FADEHIP_BLOCKING_SYNC=1: waits for the device sleep
     int split_cus = 0;  // FADEHIP_BAM_SPLIT=j: the file path's record kernels get j CUs of every XCD, the compressor the others
+    bool score_frame = true;     // the eight-lane score pass in the column-drift frame where the launch fits it (g8_kernel; FADEHIP_SCORE_FRAME=0: never)
     bool score_persist = false;  // FADEHIP_SCORE_PERSIST=1: the score pass as a persistent launch (A/B variant)
     int p2_waves_fixed = 0;    // FADEHIP_P2_WAVES: waves of the persistent pass-2 launch (0: adaptive, see run_class_two_pass)
     int span_slack = 24;  // FADEHIP_SPAN_SLACK overrides (tests: -1 makes almost every path leave its range)
@@ -461,15 +462,25 @@ const void *sw64_kernel(int R) {
 // (a class below it holds reads of any length up to its rows) when every read of the batch fits the rows — the batch's
 // longest read is known on the host — and they are fewer than the sixteen-lane class's.  No snapshots in this geometry
 // (pass 2 re-computes from step 0): the caller asks only for launches that leave none.
-const void *g8_kernel(int score_g8, int cls, int max_lq) {
-    const int rows16 = 16 * class_rows(cls);
+// The kernel sweeps in the column-drift frame (sw_pk_kernel<..., FRAME>: one packed instruction less per cell) when the
+// context asks for it and the launch's `steps` sweep steps keep every framed value below the f16 infinity (frame_fits, from
+// the scoring and the kernel's rows); *framed says which was taken.
+template <int R8>
+const void *g8_pick(const fadehip_ctx *ctx, int steps, bool *framed) {
+    const ScoreTab &sc = ctx->sc;
+    *framed = ctx->score_frame && frame_fits(std::max(std::max(sc.match, sc.mismatch), 0), sc.open, sc.ext, 8 * R8, steps);
+    return *framed ? (const void *)sw_pk_kernel<R8, 1, false, 8, false, 0, true> : (const void *)sw_pk_kernel<R8, 1, false, 8>;
+}
+const void *g8_kernel(const fadehip_ctx *ctx, int cls, int max_lq, int steps, bool *framed) {
+    const int score_g8 = ctx->score_g8, rows16 = 16 * class_rows(cls);
+    *framed = false;
     if (!score_g8 || max_lq > rows16) return nullptr;
-    if (max_lq <= 40 && rows16 > 40) return (const void *)sw_pk_kernel<5, 1, false, 8>;
-    if (max_lq <= 56 && rows16 > 56) return (const void *)sw_pk_kernel<7, 1, false, 8>;
-    if (max_lq <= 80 && rows16 > 80) return (const void *)sw_pk_kernel<10, 1, false, 8>;
-    if (max_lq <= 104 && rows16 > 104) return (const void *)sw_pk_kernel<13, 1, false, 8>;
+    if (max_lq <= 40 && rows16 > 40) return g8_pick<5>(ctx, steps, framed);
+    if (max_lq <= 56 && rows16 > 56) return g8_pick<7>(ctx, steps, framed);
+    if (max_lq <= 80 && rows16 > 80) return g8_pick<10>(ctx, steps, framed);
+    if (max_lq <= 104 && rows16 > 104) return g8_pick<13>(ctx, steps, framed);
     if (max_lq <= 152 && rows16 > 152 && rows16 <= 160)
-        return score_g8 == 2 ? (const void *)sw_pk_kernel<19, 1, false, 8, false, 2> : (const void *)sw_pk_kernel<19, 1, false, 8>;
+        return score_g8 == 2 ? (const void *)sw_pk_kernel<19, 1, false, 8, false, 2> : g8_pick<19>(ctx, steps, framed);
     return nullptr;
 }
 
@@ -635,7 +646,8 @@ int run_class_two_pass(fadehip_ctx *ctx, Slot &s, hipStream_t st, const ClassRun
     uint32_t *const sel_counters = s.d_sel(cls);
     const void *const score_fn = sw_kernel(cls, 1, p.longw), *const trace_fn = sw_kernel(cls, p.mode2, p.longw);
     if (!score_fn || !trace_fn) return set_err(ctx, FADEHIP_E_INVALID, "bad class %d", cls);
-    const void *const g8_fn = !p.longw && p.n_ck == 0 ? g8_kernel(ctx->score_g8, cls, s.max_lq) : nullptr;
+    bool framed = false;  // (the plan's blocks of four steps cover every window of the class list: what sizes LDS bounds the drift)
+    const void *const g8_fn = !p.longw && p.n_ck == 0 ? g8_kernel(ctx, cls, s.max_lq, 4 * p.n_blocks1, &framed) : nullptr;
     for (int64_t o0 = 0; o0 < p.total_oct; o0 += p.chunk_oct) {
         const int octs = (int)std::min<int64_t>(p.chunk_oct, p.total_oct - o0);
         const int i0 = (int)(o0 * 8);
@@ -685,7 +697,7 @@ int run_class_two_pass(fadehip_ctx *ctx, Slot &s, hipStream_t st, const ClassRun
             waves1 = std::max(1, std::min(octs, (int)((int64_t)res * mine / cus)));
             a.ticket = s.d_ticket(s.tickets_used++);
         } else if (g8_fn) {  // sixteen alignments per wavefront, two groups' windows in LDS
-            if (ctx->debug && o0 == 0) fprintf(stderr, "[fadehip] class of %d rows: score pass on eight-lane groups (longest read of the batch: %d)\n", 16 * class_rows(cls), s.max_lq);
+            if (ctx->debug && o0 == 0) fprintf(stderr, "[fadehip] class of %d rows: score pass on eight-lane groups (longest read of the batch: %d), column-drift frame %s\n", 16 * class_rows(cls), s.max_lq, framed ? "on" : "off");
             fn1 = g8_fn;
             waves1 = (n + 15) / 16;
             lds = 2 * p.lds1;
@@ -1458,6 +1470,7 @@ int fadehip_create(fadehip_ctx **out, int device, const fadehip_params *params) 
     if (const char *kv = getenv("FADEHIP_P2_WAVES")) ctx->p2_waves_fixed = std::max(0, atoi(kv));
     if (const char *kv = getenv("FADEHIP_SCORE_PERSIST")) ctx->score_persist = atoi(kv) != 0;
     if (const char *kv = getenv("FADEHIP_SCORE_G8")) ctx->score_g8 = atoi(kv);
+    if (const char *kv = getenv("FADEHIP_SCORE_FRAME")) ctx->score_frame = atoi(kv) != 0;
     ctx->debug = getenv("FADEHIP_DEBUG") != nullptr;
     uint8_t table[256];
     fill_ascii_table(table);

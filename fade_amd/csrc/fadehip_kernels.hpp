@@ -1316,6 +1316,12 @@ __device__ __forceinline__ uint32_t pk_max3_nonneg(uint32_t a, uint32_t b, uint3
     asm("v_pk_maximum3_f16 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
     return d;
 }
+// the same through the compiler, which fuses the two maxima into one v_pk_maximum3_f16 and, unlike the asm, knows what it schedules
+typedef _Float16 h2v __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t pk_max3_nonneg_c(uint32_t a, uint32_t b, uint32_t c) {
+    const h2v m = __builtin_elementwise_maximum(__builtin_elementwise_maximum(__builtin_bit_cast(h2v, a), __builtin_bit_cast(h2v, b)), __builtin_bit_cast(h2v, c));
+    return __builtin_bit_cast(uint32_t, m);
+}
 __device__ __forceinline__ uint32_t pk_mad4(uint32_t h, uint32_t c) {  // 4*h + c per 16-bit half
     uint32_t d;
     asm("v_pk_mad_u16 %0, %1, 4, %2 op_sel_hi:[1,0,1]" : "=v"(d) : "v"(h), "v"(c));
@@ -1326,6 +1332,14 @@ __device__ __forceinline__ uint32_t pk_mad8(uint32_t h, uint32_t c) {  // 8*h + 
     asm("v_pk_mad_u16 %0, %1, 8, %2 op_sel_hi:[1,0,1]" : "=v"(d) : "v"(h), "s"(c));
     return d;
 }
+template <bool C>  // the framed sweep takes the compiler's, every other kernel keeps the asm (and its code)
+__device__ __forceinline__ uint32_t pk_max3_sel(uint32_t a, uint32_t b, uint32_t c) {
+    if constexpr (C) return pk_max3_nonneg_c(a, b, c);
+    else return pk_max3_nonneg(a, b, c);
+}
+// m*h + c per 16-bit half (mod 2^16), c per lane, through the compiler: with m an opaque register (the caller hides its 8 | 8 << 16,
+// or the product would be rewritten as a shift and an add) this is one v_pk_mad_u16 whose latency the scheduler knows
+__device__ __forceinline__ uint32_t pk_mad_c(uint32_t h, uint32_t m, uint32_t c) { return as_u32(as_u2(h) * as_u2(m) + as_u2(c)); }
 __device__ __forceinline__ uint32_t pk_mul_ffff(uint32_t a) {  // 0/1 per half -> 0x0000/0xffff
     uint32_t d;
     asm("v_pk_mul_lo_u16 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(d) : "v"(a), "s"(0xffffu));
@@ -1369,6 +1383,14 @@ constexpr int PK_SCALE = 8;  // must stay 8: the shifts below are log2(8) and lo
 // (168; R = 16 spills ~100 registers outside its sweep and is still 6 % faster than at 2 waves), 2 beyond (R = 20 / 24:
 // +27 % / +30 % over the unconstrained allocation, which took 256 VGPRs and one wave).  The traced pass is latency-bound:
 // 3 or 4 waves per SIMD (40 / 85 spilled registers) changed nothing measurable, it is left alone.
+// The column-drift frame of the eight-lane score pass (sw_pk_kernel<..., FRAME>) holds for a launch when the largest value
+// it can form stays below the f16 infinity: the highest score of `rows` query rows, the drift of the launch's last step
+// (`steps` sweep steps, lanes starting lg columns apart, one column to the left), the hat offset and one table entry.
+// open >= ext >= 0 keeps floorE = d + 8 open - 8 ext at or above d.
+__host__ __device__ constexpr bool frame_fits(int match, int open, int ext, int rows, int steps, int lg = 8) {
+    return match >= 0 && ext >= 0 && open >= ext && steps >= 0 &&
+           8ll * match * rows + 8ll * ext * ((long long)steps + lg + 1) + 8ll * open + 8 * 15 < 0x7c00;
+}
 __host__ __device__ constexpr int pk_min_waves(int R, int MODE, int LG = 16, int WV = 0) { return WV ? WV : MODE != 1 ? 1 : (LG == 8 ? (R <= 13 ? 4 : 3) : (R <= 10 ? 4 : (R <= 16 ? 3 : 2))); }
 
 // LONGW: the launch may hold windows longer than one staged chunk (CH_COLS columns); the sweep then re-stages at chunk
@@ -1378,11 +1400,27 @@ __host__ __device__ constexpr int pk_min_waves(int R, int MODE, int LG = 16, int
 // (FADEHIP_SCORE_G8, MODE 1 only): eight pairs, sixteen alignments per wavefront, a lane owning R rows of 8 R
 // (19 x 8 = 152 rows for 150-base reads instead of 10 x 16 = 160; the skew is 7 steps instead of 15).  DPP row_shr:1
 // still shifts within 16-lane rows, so lane 8 of a row is given the DP boundary by hand.
+// FRAME (LG = 8, MODE 1 only; FADEHIP_SCORE_FRAME): the sweep in a column-drift frame.  Gap extension along a
+// row costs a subtraction only because E decays by ext per column, so every value of column j is kept with the drift
+// d = 8 ext J added, J = j + LG (a lane starts at column -lig, so J >= 1 wherever a lane sweeps and the column to its left has
+// J >= 0).  Hl, hu, hd, hu_prev hold H + d of their own column; Eh and fu hold E-hat + d - 8 ext and F-hat + d - 8 ext.  Then
+//   E-hat' = max(H_left, E-hat_left - ext)   becomes   En = max3(hl, Eh, floorE)   (the decay is the frame's own)
+//   F-hat' = max(H_up, F-hat_up - ext)       becomes   Fn = max(hu, fu) - 8 ext    (same column: no drift between them)
+//   H = max(0, T-hat - open)                 becomes   H = T - (8 open - 8 ext)    (a plain subtraction)
+// The zero floor of local alignment is the per-lane, per-step constant d, and it enters through E: floorE = d + 8 open - 8 ext
+// is "E >= 0", the free third operand of the max3 that replaces the max.  T >= En >= floorE, so H >= d, which is "H >= 0".
+// Clamping E at 0 changes no H (H = max(0, D, E, F) holds the same floor, and a clamped E clamps again one column on), but the
+// clamped E is not the E pass 2 resumes from: the framed kernel writes no snapshots (the eight-lane geometry never does).
+// The end-cell key stays 8 H_true + tk: v_pk_mad_u16 wraps mod 2^16, so 8 (H + d) + (tk - 8 d mod 2^16) is exact even where
+// 8 (H + d) overflows; the two key constants (even / odd row) are per-lane registers refreshed once per step.  Five
+// instructions per step and lane buy one per cell.  Every operand of v_pk_maximum3_f16 has to stay below 0x7c00, which
+// bounds the columns of a launch: frame_fits() above; the host falls back to the unframed kernel beyond it.
 // PERSIST (FADEHIP_SCORE_PERSIST, MODE 1 only, the other A/B variant): the score pass as a persistent launch whose waves draw
 // octets from a ticket.  Both variants are instantiations of their own: the ordinary score pass keeps its registers.
-template <int R, int MODE, bool LONGW = false, int LG = 16, bool PERSIST = false, int WV = 0>
+template <int R, int MODE, bool LONGW = false, int LG = 16, bool PERSIST = false, int WV = 0, bool FRAME = false>
 __global__ __launch_bounds__(64, pk_min_waves(R, MODE, LG, WV)) void sw_pk_kernel(SwArgs a) {
     static_assert(LG == 16 || (LG == 8 && MODE == 1 && !LONGW), "eight-lane groups exist for the score pass only");
+    static_assert(!FRAME || (LG == 8 && MODE == 1 && !LONGW && !PERSIST), "the column-drift frame exists for the eight-lane score pass only");
     static_assert(!PERSIST || MODE == 1, "the persistent variant is a score pass");
     extern __shared__ __align__(16) uint8_t lds[];
     const int lane = threadIdx.x;
@@ -1625,6 +1663,21 @@ __global__ __launch_bounds__(64, pk_min_waves(R, MODE, LG, WV)) void sw_pk_kerne
     __syncthreads();
     const uint32_t ext8 = (uint32_t)(a.sc.ext * PK_SCALE) * 0x10001u;
     const uint32_t open8 = (uint32_t)(a.sc.open * PK_SCALE) * 0x10001u;
+    // FRAME: fl_h = d of the lane's current column (before the first step: of the column to its left, J = LG - 1 - lig),
+    // fl_e = floorE, kd8 = 8 d mod 2^16 per half; H of the columns before the window is 0, i.e. the drift itself
+    uint32_t fl_h = 0, fl_e = 0, kd8 = 0;
+    const uint32_t oe8 = open8 - ext8, ext64 = ((uint32_t)(a.sc.ext * (8 * PK_SCALE)) & 0xffffu) * 0x10001u;
+    (void)oe8; (void)ext64;
+    uint32_t k8 = (uint32_t)PK_SCALE * 0x10001u;  // the key's multiplier, kept from the optimiser (pk_mad_c)
+    if constexpr (FRAME) {
+        asm("" : "+s"(k8));
+        fl_h = ext8 * (uint32_t)(LG - 1 - lig);
+        fl_e = fl_h + oe8;
+        kd8 = pk_mad_c(fl_h, k8, 0u);
+#pragma unroll
+        for (int r = 0; r < R; r++) Hl[r] = fl_h;
+        hu_out = hu_prev = fl_h;
+    }
     uint32_t *tq = a.trace + trace_off + lane;
     uint32_t *ckw = a.ckpt + (uint64_t)oct * a.ck_stride + lane;
     const uint32_t himask = __builtin_amdgcn_readfirstlane(0xffff0000u);
@@ -1695,10 +1748,16 @@ __global__ __launch_bounds__(64, pk_min_waves(R, MODE, LG, WV)) void sw_pk_kerne
             rc = (uint32_t)__builtin_amdgcn_update_dpp((int)fresh, (int)rc, DPP_ROW_SHR1, 0xf, 0xf, false);
             uint32_t hu = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hu_out, DPP_ROW_SHR1, 0xf, 0xf, true);
             uint32_t fu = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)fu_out, DPP_ROW_SHR1, 0xf, 0xf, true);
+            if constexpr (FRAME) {  // one column on: the drift, the floor of E and the key bias move with the lane
+                fl_h += ext8;
+                fl_e += ext8;
+                kd8 = as_u32(as_u2(kd8) + as_u2(ext64));
+            }
             if constexpr (LG == 8) {  // lane 8 of a DPP row starts a group of its own
                 rc = bfi(lig0m, fresh, rc);
-                hu &= ~lig0m;
-                fu &= ~lig0m;
+                if constexpr (FRAME) hu = bfi(lig0m, fl_h, hu);  // H = 0 above the first row is d exactly (lane 0 of a DPP row too: its fill is 0)
+                else hu &= ~lig0m;
+                fu &= ~lig0m;  // (FRAME: anything <= the true F-hat + d - 8 ext will do, En >= floorE carries the floor)
             }
             uint2 tA, tB;
             if constexpr (FAST) {
@@ -1715,6 +1774,12 @@ __global__ __launch_bounds__(64, pk_min_waves(R, MODE, LG, WV)) void sw_pk_kerne
             const uint32_t tk = (uint32_t)(KW - 1 - (t & (KW - 1))) * 0x10001u;  // MODE 1: position inside the key window
             // PAIRKEY: ... and which row of the pair: 2 * position + (row even), or KW * (row even) + position
             const uint32_t tk_even = end_min_ref ? tk * 2u + 0x10001u : tk + (uint32_t)KW * 0x10001u, tk_odd = end_min_ref ? tk * 2u : tk;
+            uint32_t tkf_even = 0, tkf_odd = 0;  // FRAME: the key constants less 8 d, mod 2^16 per half
+            if constexpr (FRAME) {
+                tkf_even = as_u32(as_u2(tk_even) - as_u2(kd8));
+                tkf_odd = as_u32(as_u2(tk_odd) - as_u2(kd8));
+            }
+            (void)tkf_even; (void)tkf_odd;
             uint32_t kprev = 0;
             uint32_t hd = hu_prev;
             hu_prev = hu;
@@ -1729,12 +1794,21 @@ __global__ __launch_bounds__(64, pk_min_waves(R, MODE, LG, WV)) void sw_pk_kerne
                     Dp = hd + wA + wB;
                 }
                 const uint32_t hl = Hl[r];
-                const uint32_t Ee = as_u32(as_s2(Eh[r]) - as_s2(ext8));
-                const uint32_t En = as_u32(__builtin_elementwise_max(as_s2(hl), as_s2(Ee)));
-                const uint32_t Fe = as_u32(as_s2(fu) - as_s2(ext8));
-                const uint32_t Fn = as_u32(__builtin_elementwise_max(as_s2(hu), as_s2(Fe)));
-                const uint32_t T = pk_max3_nonneg(Dp, En, Fn);  // Dp = H + W' >= 0, En >= H_left >= 0, Fn >= H_up >= 0
-                const uint32_t H = as_u32(__builtin_elementwise_sub_sat(as_u2(T), as_u2(open8)));
+                uint32_t Ee = 0, Fe = 0, En, Fn, T, H;
+                if constexpr (FRAME) {
+                    En = pk_max3_nonneg_c(hl, Eh[r], fl_e);  // hl, Eh and floorE already sit in this column's frame
+                    Fn = as_u32(__builtin_elementwise_max(as_s2(hu), as_s2(fu)) - as_s2(ext8));  // >= d - 8 ext >= 0
+                    T = pk_max3_nonneg_c(Dp, En, Fn);
+                    H = as_u32(as_s2(T) - as_s2(oe8));  // T >= floorE: H >= d, no saturation needed
+                } else {
+                    Ee = as_u32(as_s2(Eh[r]) - as_s2(ext8));
+                    En = as_u32(__builtin_elementwise_max(as_s2(hl), as_s2(Ee)));
+                    Fe = as_u32(as_s2(fu) - as_s2(ext8));
+                    Fn = as_u32(__builtin_elementwise_max(as_s2(hu), as_s2(Fe)));
+                    T = pk_max3_nonneg(Dp, En, Fn);  // Dp = H + W' >= 0, En >= H_left >= 0, Fn >= H_up >= 0
+                    H = as_u32(__builtin_elementwise_sub_sat(as_u2(T), as_u2(open8)));
+                }
+                (void)Ee; (void)Fe;
                 if constexpr (MODE != 1) {
                     // trace nibble: 8*(H!=D) + 4*(H!=F) + 2*(E opened) + 1*(F opened)
                     const uint32_t m1 = pk_min_k<8>(pk_sub(T, Dp));
@@ -1762,9 +1836,15 @@ __global__ __launch_bounds__(64, pk_min_waves(R, MODE, LG, WV)) void sw_pk_kerne
                     bestA[r] = as_u32(__builtin_elementwise_max(as_u2(bestA[r]), as_u2(pk_mad4(H, tk))));
                 }
                 if constexpr (PAIRKEY) {
-                    const uint32_t k = KW == 32 ? pk_mad8(H, (r & 1) ? tk_odd : tk_even) : pk_mad4(H, (r & 1) ? tk_odd : tk_even);
-                    if (r & 1) bestA[r >> 1] = pk_max3_nonneg(bestA[r >> 1], kprev, k);
-                    else if ((R & 1) && r == R - 1) bestA[r >> 1] = pk_max3_nonneg(bestA[r >> 1], k, k);  // (an odd R: the last row has no partner)
+                    uint32_t k;
+                    if constexpr (FRAME) {
+                        static_assert(!FRAME || KW == 32, "the framed key is 8 H + tk");
+                        k = pk_mad_c(H, k8, (r & 1) ? tkf_odd : tkf_even);  // 8 (H + d) + (tk - 8 d) = 8 H_true + tk, mod 2^16
+                    } else {
+                        k = KW == 32 ? pk_mad8(H, (r & 1) ? tk_odd : tk_even) : pk_mad4(H, (r & 1) ? tk_odd : tk_even);
+                    }
+                    if (r & 1) bestA[r >> 1] = pk_max3_sel<FRAME>(bestA[r >> 1], kprev, k);
+                    else if ((R & 1) && r == R - 1) bestA[r >> 1] = pk_max3_sel<FRAME>(bestA[r >> 1], k, k);  // (an odd R: the last row has no partner)
                     else kprev = k;
                 }
                 hd = hl;
@@ -1803,7 +1883,7 @@ __global__ __launch_bounds__(64, pk_min_waves(R, MODE, LG, WV)) void sw_pk_kerne
         // snapshot of the wave state after step 32(k+1)-1
         constexpr int WIN_PER_CK = CK_COLS / KW;
         const int sn = ((int)win + 1) / WIN_PER_CK - 1;
-        if (blk_end == blk0 + GROUP && ((int)win + 1) % WIN_PER_CK == 0 && sn < a.n_ck) {
+        if (!FRAME && blk_end == blk0 + GROUP && ((int)win + 1) % WIN_PER_CK == 0 && sn < a.n_ck) {
             constexpr int CKD = ck_dwords(R);
             uint32_t *cp = ckw + (uint64_t)sn * (CKD * 64);
 #pragma unroll
