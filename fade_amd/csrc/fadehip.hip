@@ -72,6 +72,17 @@ struct Slot {
     // slots (gate, selection, plan, pass 2, traceback) would wait behind it for a slot each.  So the score pass runs
     // on a stream whose CU mask leaves a few CUs (one per XCD by default) to everything else.
     hipStream_t score_stream = nullptr;
+    std::vector<uint32_t> score_mask;  // its CU mask (empty: none)
+    // The early order of a run (enqueue_run): the alignment array leaves for the host right behind the score pass, on the
+    // score stream, while pass 2 and the gather of the entries it wrote (patch_gather_kernel) run on `stream`; the copy is
+    // joined into `stream` before the small copies.  The A/B variants (ctx->early_tail) copy on `stream` and run pass 2 on
+    // this stream instead, forked from the score pass's end and joined back; made when a run first takes that order.
+    hipStream_t tail_stream = nullptr;
+    bool tail_tried = false;
+    bool early = false;        // the run in flight took the early order
+    DevBuf patch;              // PatchHead | PatchEntry [patch_cap]
+    PinBuf h_patch;            // its pinned copy: the head and the first patch_sent entries come with the run
+    uint32_t patch_cap = 0, patch_sent = 0;
     // Two input buffers: while a run works on in[cur], the next batch is uploaded into in[1 - cur] on the copy stream
     // (fadehip_annotate_upload never waits for the run in flight, so H2D leaves the slot's critical path).
     DevBuf in[2];                    // device mirrors of a batch block
@@ -104,16 +115,22 @@ struct Slot {
     //   [0,128) gate counters | [128,512) counters64, one line each | [512 + 48 c, ...) selection counters of class c |
     //   [1024, 1536) stats: STAT_PARTS partial sums of the 8 stats.d counters | [1536, 2560) tickets of the persistent
     //   launches | [2560, ...) PlanOut
+    // Two such blocks, used by alternate runs: a run zeroes the OTHER block behind the copy that ends it, so the next run's
+    // gate follows its upload directly instead of a fill (zb_next_clean: that fill was enqueued and nothing has touched the
+    // block since; otherwise the run fills its own block first, as every run once did).
     DevBuf zblock;
+    size_t zoff = 0;             // the block of the run in flight: 0 or ZB_STRIDE
+    bool zb_next_clean = false;
     static constexpr size_t ZB_COUNTERS = 0, ZB_C64 = 128, ZB_SEL = 512, ZB_SEL_STRIDE = 48, ZB_STATS = 1024,
                             ZB_TICKETS = 1024 + 8 * 8 * STAT_PARTS, N_TICKETS = 256, ZB_PLAN = ZB_TICKETS + 4 * N_TICKETS,
-                            ZB_BYTES = ZB_PLAN + 128;
-    unsigned long long *d_counters64() const { return (unsigned long long *)((uint8_t *)zblock.p + ZB_C64); }
-    unsigned long long *d_stats() const { return (unsigned long long *)((uint8_t *)zblock.p + ZB_STATS); }
-    uint32_t *d_counters() const { return (uint32_t *)((uint8_t *)zblock.p + ZB_COUNTERS); }
-    uint32_t *d_sel(int cls) const { return (uint32_t *)((uint8_t *)zblock.p + ZB_SEL + ZB_SEL_STRIDE * (size_t)cls); }
-    uint32_t *d_ticket(int k) const { return (uint32_t *)((uint8_t *)zblock.p + ZB_TICKETS) + k; }
-    PlanOut *d_plan() const { return (PlanOut *)((uint8_t *)zblock.p + ZB_PLAN); }
+                            ZB_BYTES = ZB_PLAN + 128, ZB_STRIDE = (ZB_BYTES + 255) & ~(size_t)255;
+    uint8_t *zb() const { return (uint8_t *)zblock.p + zoff; }
+    unsigned long long *d_counters64() const { return (unsigned long long *)(zb() + ZB_C64); }
+    unsigned long long *d_stats() const { return (unsigned long long *)(zb() + ZB_STATS); }
+    uint32_t *d_counters() const { return (uint32_t *)(zb() + ZB_COUNTERS); }
+    uint32_t *d_sel(int cls) const { return (uint32_t *)(zb() + ZB_SEL + ZB_SEL_STRIDE * (size_t)cls); }
+    uint32_t *d_ticket(int k) const { return (uint32_t *)(zb() + ZB_TICKETS) + k; }
+    PlanOut *d_plan() const { return (PlanOut *)(zb() + ZB_PLAN); }
     bool sel_fresh[NUM_CLASSES] = {};  // class's selection counters were cleared by the run's memset and not used yet
     int tickets_used = 0;
     DevBuf work[NUM_LISTS], meta[NUM_LISTS];
@@ -219,6 +236,13 @@ struct fadehip_ctx {
     bool score_frame = true;     // the eight-lane score pass in the column-drift frame where the launch fits it (g8_kernel; FADEHIP_SCORE_FRAME=0: never)
     bool score_persist = false;  // FADEHIP_SCORE_PERSIST=1: the score pass as a persistent launch (A/B variant)
     int p2_waves_fixed = 0;    // FADEHIP_P2_WAVES: waves of the persistent pass-2 launch (0: adaptive, see run_class_two_pass)
+    bool early_copy = true;    // FADEHIP_EARLY_COPY=0: no run takes the early order (enqueue_run)
+    // FADEHIP_EARLY_TAIL: what runs beside what in the early order.  0 "score" (default): the copy rides on the slot's
+    // score stream, idle once the score pass has ended, and pass 2 stays on the slot's stream: no stream is added.  1 "masked" /
+    // 2 "plain" (A/B variants, both slower: DESIGN.md §6): the copy on the slot's stream, pass 2 on a tail stream of its
+    // own, on the CUs the score mask leaves free / without a mask.
+    int early_tail = 0;
+    int patch_cap = 4096;      // FADEHIP_PATCH_CAP: entries of a slot's patch list (tests)
     int span_slack = 24;  // FADEHIP_SPAN_SLACK overrides (tests: -1 makes almost every path leave its range)
     bool debug = false;
     BgzfLane bgzf[FADEHIP_BGZF_LANES];
@@ -648,6 +672,8 @@ int run_class_two_pass(fadehip_ctx *ctx, Slot &s, hipStream_t st, const ClassRun
     if (!score_fn || !trace_fn) return set_err(ctx, FADEHIP_E_INVALID, "bad class %d", cls);
     bool framed = false;  // (the plan's blocks of four steps cover every window of the class list: what sizes LDS bounds the drift)
     const void *const g8_fn = !p.longw && p.n_ck == 0 ? g8_kernel(ctx, cls, s.max_lq, 4 * p.n_blocks1, &framed) : nullptr;
+    if (p.total_oct > p.chunk_oct) s.early = false;  // (one patch list per run: a run without snapshots is one chunk anyway)
+    const bool early = s.early;
     for (int64_t o0 = 0; o0 < p.total_oct; o0 += p.chunk_oct) {
         const int octs = (int)std::min<int64_t>(p.chunk_oct, p.total_oct - o0);
         const int i0 = (int)(o0 * 8);
@@ -704,10 +730,23 @@ int run_class_two_pass(fadehip_ctx *ctx, Slot &s, hipStream_t st, const ClassRun
         }
         if ((rc = launch_sw(ctx, fn1, waves1, lds, sst, a))) return rc;
         if ((rc = sp.mark(ctx, s, 1, sst))) return rc;
-        if (sst != st) {
+        hipStream_t p2st = st;  // where pass 2 runs
+        if (sst != st || early) {
             int ej = sp.e[1];  // the join waits for the timing event where there is one
             if (ej < 0 && (rc = record(ctx, s, &ej, sst))) return rc;
-            HIPCHK(ctx, hipStreamWaitEvent(st, s.ev[ej], 0));
+            if (sst != st) HIPCHK(ctx, hipStreamWaitEvent(st, s.ev[ej], 0));
+            if (early) {
+                // Early order: every entry but the candidates' is final here (select_one wrote it), so the array leaves now,
+                // behind the score pass on its stream, and pass 2 runs beside the copy (variants: the copy on the slot's
+                // stream, pass 2 on the tail stream).  The copy may read a candidate's entry while pass 2 writes it: those
+                // entries, and only those, come again in the patch list.
+                if (s.tail_stream) {
+                    p2st = s.tail_stream;
+                    HIPCHK(ctx, hipStreamWaitEvent(p2st, s.ev[ej], 0));
+                }
+                HIPCHK(ctx, hipMemcpyAsync(s.res.p + s.res_aln_off, s.aln.p, sizeof(fadehip_aln) * (size_t)s.out_cap, hipMemcpyDeviceToHost,
+                                           s.tail_stream ? st : sst));
+            }
         }
         // pass 2 + tracebacks + re-traced paths: one persistent launch
         if (s.tickets_used >= (int)Slot::N_TICKETS)
@@ -731,8 +770,28 @@ int run_class_two_pass(fadehip_ctx *ctx, Slot &s, hipStream_t st, const ClassRun
         b2.gate = c.gate;
         b2.early_out = (c.gate && c.meta && !ctx->prm.trace_all) ? 1 : 0;
         b2.rerun_total = &s.d_plan()->rerun_total;
-        if ((rc = launch_sw(ctx, trace_fn, std::min(p.p2_waves, octs + NUM_BUCKETS), p.lds1, st, b2))) return rc;
-        if ((rc = sp.mark(ctx, s, 2, st))) return rc;
+        if ((rc = launch_sw(ctx, trace_fn, std::min(p.p2_waves, octs + NUM_BUCKETS), p.lds1, p2st, b2))) return rc;
+        if ((rc = sp.mark(ctx, s, 2, p2st))) return rc;
+        if (early) {
+            // the entries pass 2 left, gathered for the host; then what ran beside the slot's stream (the copy, or pass 2 and
+            // the gather) joins it again: the slot's stream still completes only when the whole run has
+            PatchArgs pa;
+            pa.cand = b2.cand;
+            pa.cand_cap = b2.cand_cap;
+            pa.bucket_n = sel_counters;
+            pa.work = b2.work;
+            pa.out = c.out;
+            pa.out_cap = s.out_cap;
+            pa.head = (PatchHead *)s.patch.p;
+            pa.list = (PatchEntry *)((uint8_t *)s.patch.p + sizeof(PatchHead));
+            pa.cap = s.patch_cap;
+            const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>(64, (s.patch_sent * (uint32_t)(sizeof(PatchEntry) / 4) + 255) / 256));
+            hipLaunchKernelGGL(patch_gather_kernel, dim3(blocks), dim3(256), 0, p2st, pa);
+            HIPCHK(ctx, hipGetLastError());
+            int et = -1;
+            if ((rc = record(ctx, s, &et, s.tail_stream ? p2st : sst))) return rc;
+            HIPCHK(ctx, hipStreamWaitEvent(st, s.ev[et], 0));
+        }
     }
     return 0;
 }
@@ -924,8 +983,29 @@ int ensure_slot(fadehip_ctx *ctx, Slot &s) {
         if (hipExtStreamCreateWithCUMask(&s.score_stream, (uint32_t)mask.size(), mask.data()) != hipSuccess) {
             (void)hipGetLastError();
             s.score_stream = nullptr;  // no CU masks on this stack: the score pass stays on the slot's stream
+        } else {
+            s.score_mask = mask;
         }
     }
+    return 0;
+}
+
+// The tail stream of a slot's early order where pass 2 leaves the slot's stream (FADEHIP_EARLY_TAIL=masked | plain, or a
+// slot without a score stream), made when a run first takes that order: on the CUs the score mask leaves free, or a plain
+// stream.  One more stream per slot in use, 3 N + 1, which is why the default does without it.
+int ensure_tail(fadehip_ctx *ctx, Slot &s) {
+    if (s.tail_stream || s.tail_tried) return 0;
+    s.tail_tried = true;
+    if (ctx->early_tail == 1 && !s.score_mask.empty()) {
+        std::vector<uint32_t> mask(s.score_mask.size());
+        uint32_t any = 0;
+        for (size_t w = 0; w < mask.size(); w++) any |= (mask[w] = ~s.score_mask[w]);
+        if (any && hipExtStreamCreateWithCUMask(&s.tail_stream, (uint32_t)mask.size(), mask.data()) != hipSuccess) {
+            (void)hipGetLastError();
+            s.tail_stream = nullptr;
+        }
+    }
+    if (!s.tail_stream) HIPCHK(ctx, hipStreamCreateWithFlags(&s.tail_stream, hipStreamNonBlocking));
     return 0;
 }
 
@@ -1038,8 +1118,9 @@ int enqueue_run(fadehip_ctx *ctx, Slot &s) {
     total_bound = std::min(total_bound, s.out_bound);
     s.out_cap = total_bound;
     s.res_aln_off = ((size_t)n + 255) & ~(size_t)255;
+    if (s.zblock.cap < 2 * Slot::ZB_STRIDE) s.zb_next_clean = false, s.zoff = 0;  // (a new allocation)
     if ((rc = rsv(s.rs, (size_t)n)) || (rc = rsv(s.aln, sizeof(fadehip_aln) * (size_t)std::max<uint32_t>(total_bound, 1))) ||
-        (rc = reserve(ctx, s.zblock, Slot::ZB_BYTES)) ||
+        (rc = reserve(ctx, s.zblock, 2 * Slot::ZB_STRIDE)) ||
         (!s.device_only && (rc = reserve_pinned(ctx, s.res, s.res_aln_off + sizeof(fadehip_aln) * (size_t)total_bound))))
         return rc;
     for (int c = 0; c < NUM_LISTS; c++) {
@@ -1068,7 +1149,42 @@ int enqueue_run(fadehip_ctx *ctx, Slot &s) {
             (rc = reserve_run(ctx, s.trash, s.trace, need_trace)) || (rc = reserve_run(ctx, s.trash, s.cand, need_cand)))
             return rc;
     }
-    HIPCHK(ctx, hipMemsetAsync(s.zblock.p, 0, Slot::ZB_BYTES, st));  // every counter of the run in one fill
+    // The order of the run's tail.  Late: pass 2 on the slot's stream, then every copy.  Early: the alignment array is
+    // copied right behind the score pass, on the score stream, pass 2 runs beside that copy, and the entries it wrote
+    // follow in a patch list (run_class_two_pass, finish_run).  Early takes one class list and nothing else to run, results
+    // that go to the host, no snapshots (one chunk), and few candidates in the slot's previous run: at most half the patch
+    // list's capacity (a slot's first run qualifies; a run whose candidates overflow the list all the same is copied again
+    // by finish_run, and the slot's next run is late).
+    {
+        int n_cls = 0;
+        for (int c = 0; c < NUM_CLASSES; c++) n_cls += s.bound[c] ? 1 : 0;
+        const char *why = nullptr;
+        if (!ctx->early_copy) why = "FADEHIP_EARLY_COPY=0";
+        else if (!ctx->two_pass) why = "single-pass kernels";
+        else if (s.device_only) why = "results stay on the device";
+        else if (n_cls != 1) why = "not exactly one class list";
+        else if (s.bound[LONG_LIST]) why = "long list";
+        else if (ctx->prm.trace_all) why = "trace_all";
+        else if (s.last_cand * 2 > ctx->patch_cap) why = "the previous run's candidates exceed half the patch list";
+        else if (s.use_ckpt) why = "snapshots";
+        else if (!total_bound) why = "no alignments";
+        s.early = why == nullptr;
+        if (s.early) {
+            s.patch_cap = (uint32_t)ctx->patch_cap;
+            s.patch_sent = (uint32_t)std::min<int64_t>(s.patch_cap, 2 * s.last_cand + 64);  // entries copied with the run; finish_run fetches the rest
+            const size_t bytes = sizeof(PatchHead) + sizeof(PatchEntry) * (size_t)std::max<uint32_t>(s.patch_cap, 1);
+            if (((ctx->early_tail || !s.score_stream) && (rc = ensure_tail(ctx, s))) || (rc = reserve(ctx, s.patch, bytes)) ||
+                (rc = reserve_pinned(ctx, s.h_patch, bytes)))
+                return rc;
+        }
+        if (ctx->debug)
+            fprintf(stderr, "[fadehip] copy order: %s (%s)\n", s.early ? "early" : "late",
+                    !s.early ? why : !s.tail_stream ? "the copy on the score stream" : ctx->early_tail == 1 && !s.score_mask.empty() ? "pass 2 on the CUs the score mask leaves free" : "pass 2 on a plain stream");
+    }
+    // every counter of the run: the block the slot's previous run zeroed behind its last copy, or one fill here
+    if (s.zb_next_clean) s.zoff ^= Slot::ZB_STRIDE;
+    else HIPCHK(ctx, hipMemsetAsync(s.zb(), 0, Slot::ZB_BYTES, st));
+    s.zb_next_clean = false;
     for (int c = 0; c < NUM_CLASSES; c++) s.sel_fresh[c] = true;
     if ((rc = record(ctx, s, &s.ev_gate0))) return rc;
     GateArgs g;
@@ -1112,7 +1228,7 @@ int enqueue_run(fadehip_ctx *ctx, Slot &s) {
     for (int c = 0; c < NUM_LISTS; c++) exact[c] = s.bound[c];
     if (!ctx->two_pass) {
         // single-pass kernels: their launches take the real counts
-        HIPCHK(ctx, hipMemcpyAsync(s.h_zb, s.zblock.p, 128, hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipMemcpyAsync(s.h_zb, s.zb(), 128, hipMemcpyDeviceToHost, st));
         HIPCHK(ctx, hipStreamSynchronize(st));
         for (int c = 0; c < NUM_LISTS; c++) exact[c] = std::min(s.h_counters()[c], s.bound[c]);
     }
@@ -1130,10 +1246,15 @@ int enqueue_run(fadehip_ctx *ctx, Slot &s) {
     }
     if ((rc = record(ctx, s, &s.ev_end))) return rc;
     // results to the slot's pinned block; the counter block tells the host how many entries of each list are live
-    HIPCHK(ctx, hipMemcpyAsync(s.h_zb, s.zblock.p, Slot::ZB_BYTES, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(s.h_zb, s.zb(), Slot::ZB_BYTES, hipMemcpyDeviceToHost, st));
+    // the next run's counters, zeroed here, off its critical path (the same batch run again takes them as well)
+    HIPCHK(ctx, hipMemsetAsync((uint8_t *)s.zblock.p + (s.zoff ^ Slot::ZB_STRIDE), 0, Slot::ZB_BYTES, st));
+    s.zb_next_clean = true;
     if (s.device_only) return 0;
-    HIPCHK(ctx, hipMemcpyAsync(s.res.p, s.rs.p, (size_t)n, hipMemcpyDeviceToHost, st));
-    if (total_bound)
+    HIPCHK(ctx, hipMemcpyAsync(s.res.p, s.rs.p, (size_t)n, hipMemcpyDeviceToHost, st));  // (pass 2 sets bits in rs: it stays behind it)
+    if (s.early)  // the array left behind the score pass: what pass 2 wrote since comes as the patch list
+        HIPCHK(ctx, hipMemcpyAsync(s.h_patch.p, s.patch.p, sizeof(PatchHead) + sizeof(PatchEntry) * (size_t)s.patch_sent, hipMemcpyDeviceToHost, st));
+    else if (total_bound)
         HIPCHK(ctx, hipMemcpyAsync(s.res.p + s.res_aln_off, s.aln.p, sizeof(fadehip_aln) * (size_t)total_bound, hipMemcpyDeviceToHost, st));
     return 0;
 }
@@ -1163,6 +1284,29 @@ int finish_run(fadehip_ctx *ctx, Slot &s, int slot) {
         if (errbits & 16u) return set_err(ctx, FADEHIP_E_INVALID, "batch has a record whose cigar.alignedLength exceeds ref_span_bound=%lld", (long long)s.span_bound);
         if (errbits & 32u) return set_err(ctx, FADEHIP_E_INVALID, "batch has more records to re-align than its bounds said, or a read outside them (n_with_seq too small, or an l_seq outside l_seq_min / l_seq_max?)");
         return set_err(ctx, FADEHIP_E_INVALID, "batch has a mapped soft-clipped read whose tid is not a contig of the uploaded genome");
+    }
+    if (s.early) {
+        // early order: lay the entries pass 2 wrote over the bulk copy, once, before any view is handed out
+        s.early = false;
+        const PatchHead head = *(const PatchHead *)s.h_patch.p;
+        const PatchEntry *const list = (const PatchEntry *)(s.h_patch.p + sizeof(PatchHead));
+        uint8_t *const h_aln = s.res.p + s.res_aln_off;
+        if (head.overflow || head.n > s.patch_cap) {
+            // more candidates than the list holds: the whole array again (rare; the slot's next run is late, see last_cand)
+            HIPCHK(ctx, hipMemcpyAsync(h_aln, s.aln.p, sizeof(fadehip_aln) * (size_t)s.out_cap, hipMemcpyDeviceToHost, st));
+            HIPCHK(ctx, hipStreamSynchronize(st));
+        } else {
+            if (head.n > s.patch_sent) {  // more than the run's copy was sized for: the rest of the list
+                HIPCHK(ctx, hipMemcpyAsync((void *)(list + s.patch_sent), (const uint8_t *)s.patch.p + sizeof(PatchHead) + sizeof(PatchEntry) * (size_t)s.patch_sent,
+                                           sizeof(PatchEntry) * (size_t)(head.n - s.patch_sent), hipMemcpyDeviceToHost, st));
+                HIPCHK(ctx, hipStreamSynchronize(st));
+            }
+            for (uint32_t k = 0; k < head.n; k++)
+                if (list[k].out < s.out_cap) memcpy(h_aln + sizeof(fadehip_aln) * (size_t)list[k].out, &list[k].e, sizeof(fadehip_aln));
+        }
+        if (ctx->debug)
+            fprintf(stderr, "[fadehip] slot %d: patch list of %u entries (%u sent with the run)%s\n", slot, head.n, s.patch_sent,
+                    head.overflow ? ", overflow: the array was copied again" : "");
     }
     for (int c = 0; c < NUM_CLASSES; c++)  // what pass 2 served: sizes the next run's persistent launch
         if (s.bound[c]) {
@@ -1471,6 +1615,9 @@ int fadehip_create(fadehip_ctx **out, int device, const fadehip_params *params) 
     if (const char *kv = getenv("FADEHIP_SCORE_PERSIST")) ctx->score_persist = atoi(kv) != 0;
     if (const char *kv = getenv("FADEHIP_SCORE_G8")) ctx->score_g8 = atoi(kv);
     if (const char *kv = getenv("FADEHIP_SCORE_FRAME")) ctx->score_frame = atoi(kv) != 0;
+    if (const char *kv = getenv("FADEHIP_EARLY_COPY")) ctx->early_copy = atoi(kv) != 0;
+    if (const char *kv = getenv("FADEHIP_EARLY_TAIL")) ctx->early_tail = strcmp(kv, "masked") == 0 ? 1 : strcmp(kv, "plain") == 0 ? 2 : 0;
+    if (const char *kv = getenv("FADEHIP_PATCH_CAP")) ctx->patch_cap = std::max(0, std::min(atoi(kv), 1 << 20));
     ctx->debug = getenv("FADEHIP_DEBUG") != nullptr;
     uint8_t table[256];
     fill_ascii_table(table);
@@ -1508,6 +1655,9 @@ void fadehip_destroy(fadehip_ctx *ctx) {
         release(s.stage[0]);
         release(s.stage[1]);
         release(s.res);
+        release(s.patch);
+        release(s.h_patch);
+        if (s.tail_stream) (void)hipStreamDestroy(s.tail_stream);
         if (s.ev_copied) (void)hipEventDestroy(s.ev_copied);
         for (hipEvent_t e : s.ev) (void)hipEventDestroy(e);
         if (s.h_zb) (void)hipHostFree(s.h_zb);
@@ -1634,7 +1784,7 @@ int fadehip_sw_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *q, const int64_
     if ((rc = reserve(ctx, d_q, (size_t)q_total + 2)) || (rc = reserve(ctx, d_r, (size_t)r_total + 2)) ||
         (rc = reserve(ctx, d_qn, (size_t)q_total / 2 + 8)) || (rc = reserve(ctx, d_rn, (size_t)r_total / 2 + 8)) ||
         (rc = reserve(ctx, d_bad, 4)) || (rc = reserve(ctx, d_aln, (size_t)n * sizeof(fadehip_aln))) ||
-        (rc = reserve(ctx, d_work, std::max<size_t>(1, n_work) * sizeof(Work))) || (rc = reserve(ctx, s.zblock, Slot::ZB_BYTES)))
+        (rc = reserve(ctx, d_work, std::max<size_t>(1, n_work) * sizeof(Work))) || (rc = reserve(ctx, s.zblock, 2 * Slot::ZB_STRIDE)))
         return rc;
     HIPCHK(ctx, hipMemcpyAsync(d_q.p, q, (size_t)q_total, hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipMemcpyAsync(d_r.p, r, (size_t)r_total, hipMemcpyHostToDevice, st));
@@ -1661,11 +1811,14 @@ int fadehip_sw_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *q, const int64_
         s.fwd_spans.clear();
         s.tb_spans.clear();
         s.tickets_used = 0;
-        HIPCHK(ctx, hipMemsetAsync(s.zblock.p, 0, Slot::ZB_BYTES, st));
+        s.zoff = 0;  // (slot 0's first counter block, filled here: its level-2 runs start over)
+        s.zb_next_clean = false;
+        HIPCHK(ctx, hipMemsetAsync(s.zb(), 0, Slot::ZB_BYTES, st));
         for (int c = 0; c < NUM_CLASSES; c++) s.sel_fresh[c] = true;
         // level 1 wants a CIGAR for every pair: whatever the forced-diagonal shortcut leaves goes to pass 2, with snapshots
         s.use_ckpt = true;
         if (const char *kv = getenv("FADEHIP_CKPT")) s.use_ckpt = atoi(kv) != 0;
+        s.early = false;  // (the results are read back below, behind everything)
         for (int c = 0; c < NUM_LISTS; c++) {
             if (lists[c].empty()) continue;
             // the lists come from the host here: their counts go where the gate leaves them at level 2
@@ -2134,6 +2287,8 @@ int fadehip_annotate_run(fadehip_ctx *ctx, int slot, int32_t floor_len, int32_t 
     }
     if ((rc = plan_run(ctx, s))) return rc;
     if ((rc = enqueue_run(ctx, s))) {
+        if (s.tail_stream) (void)hipStreamSynchronize(s.tail_stream);
+        if (s.score_stream) (void)hipStreamSynchronize(s.score_stream);
         (void)hipStreamSynchronize(s.stream);
         s.state = 0;
         return rc;

@@ -2187,6 +2187,65 @@ struct PlanOut {            // in the slot's counter block, read by the host aft
     unsigned long long rerun_total;  // candidates traced again because their path left the traced steps
 };
 
+// ---------------------------------------------------------------- patch list of an early bulk copy
+// When the alignment array leaves for the host beside pass 2 (enqueue_run's early order), the entries pass 2 wrote follow in
+// a compact list of (entry index, entry) pairs which the host lays over the bulk copy.  Pass 2 writes a.out[w.out] for the
+// candidates on the selection's bucket lists and for nothing else: traceback_path is its only store into the array, it is
+// called for list members only, and every way out of it either stores the member's entry (a complete CIGAR, or n_ops = 0
+// for a path with more than 10 ops, traced to its end or abandoned before step T0) or returns 8, after which the same wave
+// traces the member again from further back until step 0, where no path can leave its steps.  So after pass 2 every list
+// member's entry is final and no other entry has changed since the score pass.
+struct PatchHead {
+    uint32_t n;         // candidates on the lists (entries [0, min(n, cap)) of the list are live)
+    uint32_t overflow;  // n exceeds the list's capacity: the host fetches the whole array again
+    uint32_t pad[2];
+};
+struct PatchEntry {     // 128 bytes
+    uint32_t out;       // entry of the result array (0xffffffff: none, skipped by the host)
+    uint32_t pad;
+    fadehip_aln e;
+};
+static_assert(sizeof(fadehip_aln) % 4 == 0 && sizeof(PatchEntry) == 8 + sizeof(fadehip_aln), "the gather copies dwords");
+struct PatchArgs {
+    const Cand *cand;           // [NUM_BUCKETS][cand_cap], as pass 2 reads it
+    uint32_t cand_cap;
+    const uint32_t *bucket_n;   // [NUM_BUCKETS]
+    const Work *work;
+    const fadehip_aln *out;
+    uint32_t out_cap;
+    PatchHead *head;
+    PatchEntry *list;           // [cap]
+    uint32_t cap;
+};
+
+// a thread per dword of the list: entry p is the (p - first[b])-th candidate of bucket b, buckets in order
+__global__ __launch_bounds__(256) void patch_gather_kernel(PatchArgs a) {
+    constexpr uint32_t ENTRY_DW = sizeof(PatchEntry) / 4;
+    uint32_t first[NUM_BUCKETS + 1];
+    first[0] = 0;
+#pragma unroll
+    for (int b = 0; b < NUM_BUCKETS; b++) first[b + 1] = first[b] + min(a.bucket_n[b], a.cand_cap);  // clamped as pass 2 clamps it
+    const uint32_t total = first[NUM_BUCKETS], live = min(total, a.cap);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        a.head->n = total;
+        a.head->overflow = total > a.cap ? 1u : 0u;
+        a.head->pad[0] = a.head->pad[1] = 0;
+    }
+    uint32_t *const dst = (uint32_t *)a.list;
+    for (uint64_t at = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; at < (uint64_t)live * ENTRY_DW; at += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t p = (uint32_t)(at / ENTRY_DW), d = (uint32_t)(at % ENTRY_DW);
+        int b = 0;
+#pragma unroll
+        for (int k = 1; k < NUM_BUCKETS; k++) b += p >= first[k] ? 1 : 0;
+        const Cand c = a.cand[(uint64_t)b * a.cand_cap + (p - first[b])];
+        const uint32_t o = a.work[c.src].out;
+        uint32_t v;
+        if (o >= a.out_cap) v = d == 0 ? 0xffffffffu : 0u;  // (the gate hands out entries below out_cap only)
+        else v = d == 0 ? o : d == 1 ? 0u : ((const uint32_t *)(a.out + o))[d - 2];
+        dst[at] = v;
+    }
+}
+
 // level 1 builds its class lists on the host: their counts go where the gate would have left them
 __global__ void set_counts_kernel(uint32_t *dst, uint32_t v) { *dst = v; }
 
