@@ -3,6 +3,7 @@
 // match the block holds is in reach — the smallest output, at 9.8 GB/s.  The geometry is taken where the stream compresses
 // well (bgzf_deflate.hpp); where it hardly does, bgzf_deflate_g32.hpp (phase A on per-wave segments, twice the rate) serves.
 // Its phases B to D and its CRC are round 3's too: round 4's faster ones went into the other geometry only.
+// host/selftest/gpu_deflate_model.cpp (phase_a_g64, MODEL_GEOM=64) is this file's algorithm on the CPU, byte for byte.
 #pragma once
 #include "bgzf_deflate_common.hpp"
 
@@ -239,13 +240,18 @@ __device__ __forceinline__ void role_parser(const RoleArgs r) {
         const uint32_t len_next = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)len, 0x130 /* wave_shl:1 */, 0xf, 0xf, false);
         const bool yield = len && lane < 63 && len_next > len;
         const int cb = piece * 64, nv = min(64, n - cb);
-        uint64_t has = __ballot(len != 0 && !yield);
+        int cur = max(carry - cb, 0);
+        const int cur0 = cur;
+        const uint64_t from0 = cur0 >= 64 ? 0ull : (~0ull << cur0);  // positions at or behind cur0
+        // A position below cur0 starts no token, but it may come with a length: its extender ran ahead and read an older `carry`
+        // (a relaxed load) — whether it did is the waves' timing.  Such positions are masked out before the piece's matches are
+        // counted against the list's capacity: the piece at which the list is full, and so the output, is then the same in every run
+        // (every position at or behind cur0 has its length: `carry` only grows, so its extender saw no more than cur0).
+        uint64_t has = __ballot(len != 0 && !yield) & from0;
         if (full || mcount + (uint32_t)__popcll(has) > (uint32_t)MAX_MATCHES) { full = 1; has = 0; }  // the match list is full: literals from here on
         const uint64_t vmask = nv == 64 ? ~0ull : ((1ull << nv) - 1ull);
         // greedy: from `cur`, the next match start at or after it is taken and covers its length; what no match covers is a literal
         uint64_t matmask = 0, covered = 0;
-        int cur = max(carry - cb, 0);
-        const int cur0 = cur;
         while (cur < nv) {
             const uint64_t rem = has & (~0ull << cur);
             if (!rem) break;
@@ -255,7 +261,7 @@ __device__ __forceinline__ void role_parser(const RoleArgs r) {
             covered |= (e >= 64 ? ~0ull : ((1ull << e) - 1ull)) & ~((j == 63) ? ~0ull : ((1ull << (j + 1)) - 1ull));
             cur = e;
         }
-        const uint64_t tokmask = vmask & ~covered & (cur0 >= 64 ? 0ull : (~0ull << cur0));
+        const uint64_t tokmask = vmask & ~covered & from0;
         if (cur < nv) cur = nv;
         if (cb + cur > carry) carry = cb + cur;
         if ((matmask >> lane) & 1ull) {

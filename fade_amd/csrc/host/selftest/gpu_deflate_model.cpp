@@ -1,7 +1,10 @@
 // gpu_deflate_model.cpp — CPU model of the gfx950 BGZF compressor (bgzf_deflate.hpp), phase by phase with the same
 // data structures (per-segment hash tables of 4-way buckets, pieces of 64 positions, token / match bitmaps, the match
 // list, seams; 256 position ranges that each emit their bits at a scanned offset, OR-ing the words they share) and the
-// SAME serial helpers (bgzf_huff.hpp).  It exists so that the format logic is checked against zlib's inflate where there is no GPU:
+// SAME serial helpers (bgzf_huff.hpp).  Both block geometries are restated: bgzf_deflate_g32.hpp's phase A on per-wave segments
+// (model_deflate's own), and bgzf_deflate_g64.hpp's role pipeline as the sequence it stands for (phase_a_g64); what follows
+// phase A is one restatement for both (see model_deflate).  It exists so that the format logic is checked against zlib's
+// inflate where there is no GPU:
 //   every stream inflates to its input, on BAM-like, text, random, constant, tiny and empty-ish inputs;
 //   sizes are printed next to zlib -6 and -1.
 // Build + run: make -C fade_amd/csrc build/gpu_deflate_model && fade_amd/csrc/build/gpu_deflate_model
@@ -35,6 +38,98 @@ inline uint32_t load32(const uint8_t *d, int p) {
     return v;
 }
 inline uint32_t hash4(uint32_t v) { return (((v * 0x9E3779B1u) >> 16) * (uint32_t)N_BUCKETS) >> 16; }
+bool G64 = false;  // phase A as bgzf_deflate_g64.hpp has it (phase_a_g64) instead of bgzf_deflate_g32.hpp's segments
+
+// ---- phase A of bgzf_deflate_g64.hpp (the 0xff00-byte geometry), as the sequence its pipeline of wave roles stands for:
+// ONE hash table for the whole block (2^12 buckets of 4 ways, newest first, its own hash); the hasher walks the pieces of 64
+// positions in order, so a piece's lookups see every earlier piece and none of its own positions, and of two lanes on one
+// bucket the later stays; the extender's candidates are the nearest of the distances 1..8 whose four bytes agree and the
+// bucket's four within 32,768 bytes, extended to min(258, n - p); the parser lets a match yield to a longer one at the next
+// position (never from lane 63), walks greedily from `carry`, and closes the match list at 8192 records.
+// A position below `carry` when its piece is parsed has no length here.  (The device's extenders run ahead of the parser and
+// may have found one — which of them did depends on the waves' timing —, so the parser masks those positions out before it
+// counts the piece's matches against the list's capacity: only then is the piece at which the list is full, and so the
+// output, the same in every run.)
+void phase_a_g64(const std::vector<uint8_t> &data, int n, bool lazy, std::vector<uint32_t> &tok, std::vector<uint32_t> &mat,
+                 std::vector<uint32_t> &match_rec) {
+    constexpr int HASH_BITS = 12, G64_WAYS = 4, MAX_MATCHES = 8192, NEAR64 = 8;
+    auto hash = [](uint32_t v) { return (v * 0x9E3779B1u) >> (32 - HASH_BITS); };
+    std::vector<uint16_t> head((size_t)(1 << HASH_BITS) * G64_WAYS, 0);
+    const int n_pieces = (n + 63) / 64;
+    int carry = 0, mcount = 0;
+    bool full = false;
+    for (int piece = 0; piece < n_pieces; piece++) {
+        const int cb = piece * 64, nv = std::min(64, n - cb);
+        // the hasher: every lane reads its bucket, then every lane writes
+        uint16_t cand[64][G64_WAYS];
+        uint32_t val[64];
+        bool valid[64];
+        for (int l = 0; l < 64; l++) {
+            const int p = cb + l;
+            valid[l] = p + MIN_MATCH <= n;
+            val[l] = valid[l] ? load32(data.data(), p) : 0u;
+            for (int k = 0; k < G64_WAYS; k++) cand[l][k] = valid[l] ? head[(size_t)hash(val[l]) * G64_WAYS + k] : (uint16_t)0;
+        }
+        for (int l = 0; l < 64; l++)
+            if (valid[l]) {
+                uint16_t *bk = &head[(size_t)hash(val[l]) * G64_WAYS];
+                bk[0] = (uint16_t)(cb + l + 1);
+                for (int k = 1; k < G64_WAYS; k++) bk[k] = cand[l][k - 1];
+            }
+        // the extenders
+        uint32_t len[64], dist[64];
+        for (int l = 0; l < 64; l++) {
+            const int p = cb + l;
+            len[l] = dist[l] = 0;
+            if (!valid[l] || p < carry) continue;
+            const int maxlen = std::min(MAX_MATCH, n - p);
+            int cp[1 + G64_WAYS], nc = 0;
+            for (int d = 1; d <= NEAR64 && d <= p; d++)
+                if (load32(data.data(), p - d) == val[l]) { cp[nc++] = p - d; break; }
+            for (int k = 0; k < G64_WAYS; k++)
+                if (cand[l][k]) {
+                    const int c = (int)cand[l][k] - 1;
+                    if (p - c <= 32768 && load32(data.data(), c) == val[l]) cp[nc++] = c;
+                }
+            for (int k = 0; k < nc; k++) {
+                uint32_t ln = 4;
+                while ((int)ln < maxlen && data[(size_t)cp[k] + ln] == data[(size_t)p + ln]) ln++;
+                ln = std::min<uint32_t>(ln, (uint32_t)maxlen);
+                if (ln > len[l]) { len[l] = ln; dist[l] = (uint32_t)(p - cp[k]); }
+            }
+            if (len[l] < (uint32_t)MIN_MATCH) len[l] = 0;
+        }
+        // the parser
+        const int cur0 = std::max(carry - cb, 0);
+        const uint64_t from0 = cur0 >= 64 ? 0ull : (~0ull << cur0), vmask = nv == 64 ? ~0ull : ((1ull << nv) - 1ull);
+        uint64_t has = 0;
+        for (int l = 0; l < 64; l++) {
+            const bool yield = lazy && len[l] && l < 63 && len[l + 1] > len[l];
+            if (len[l] && !yield) has |= 1ull << l;
+        }
+        has &= from0;
+        if (full || mcount + __builtin_popcountll(has) > MAX_MATCHES) { full = true; has = 0; }
+        uint64_t matmask = 0, covered = 0;
+        int cur = cur0;
+        while (cur < nv) {
+            const uint64_t rem = has & (~0ull << cur);
+            if (!rem) break;
+            const int j = __builtin_ctzll(rem), e = j + (int)len[j];
+            matmask |= 1ull << j;
+            covered |= (e >= 64 ? ~0ull : ((1ull << e) - 1ull)) & ~(j == 63 ? ~0ull : ((1ull << (j + 1)) - 1ull));
+            cur = e;
+        }
+        const uint64_t tokmask = vmask & ~covered & from0;
+        carry = std::max(carry, cb + std::max(cur, nv));
+        for (int l = 0; l < 64; l++)
+            if ((matmask >> l) & 1) match_rec.push_back(dist[l] | ((len[l] - 3) << 16));
+        mcount += __builtin_popcountll(matmask);
+        tok[(size_t)(cb >> 5)] = (uint32_t)tokmask;
+        tok[(size_t)(cb >> 5) + 1] = (uint32_t)(tokmask >> 32);
+        mat[(size_t)(cb >> 5)] = (uint32_t)matmask;
+        mat[(size_t)(cb >> 5) + 1] = (uint32_t)(matmask >> 32);
+    }
+}
 
 // returns the raw DEFLATE stream of src[0..n), n <= BLOCK
 std::vector<uint8_t> model_deflate(const uint8_t *src, int n, bool lazy) {
@@ -51,7 +146,12 @@ std::vector<uint8_t> model_deflate(const uint8_t *src, int n, bool lazy) {
     const int n_pieces = (n + 63) / 64, seg_pieces = (n_pieces + N_SEG - 1) / N_SEG;
     struct Seam { int rec, over, seg_end, next_end; };
     std::vector<Seam> seams;
-    for (int w = 0; w < N_SEG; w++) {
+    // (bgzf_deflate_g64.hpp has a phase A of its own.  Its phases B to D are an older writing of the same steps and give the same
+    // bits: symbols ranked by (frequency, symbol), mr_code_lengths and limit_code_lengths to 15 bits on both alphabets, a second
+    // distance code where there is one or none, canonical codes, the header's run-length tokens in cl_rle's order, and the tokens'
+    // bits in position order — how the positions are cut into ranges does not show in the stream.)
+    if (G64) phase_a_g64(data, n, lazy, tok, mat, match_rec);
+    for (int w = 0; !G64 && w < N_SEG; w++) {
         const int first = std::min(w * seg_pieces, n_pieces), end = std::min((w + 1) * seg_pieces, n_pieces);
         const int seg_end = std::min(n, end * 64);
         std::vector<uint16_t> head((size_t)N_BUCKETS * WAYS, 0);
@@ -421,8 +521,14 @@ int main(int argc, char **argv) {
         cases.push_back({"tiny zeros 300", std::vector<uint8_t>(300, 0)});
     }
     int fails = 0;
-    struct Geom { const char *name; int block, buckets, cap; };
-    const Geom geoms[2] = {{"0xff00-byte blocks", 0xff00, 512, (8192 + 2560) / 8}, {"0x7f00-byte blocks", 0x7f00, 384, 2560 / 8}};
+    struct Geom { const char *name; int block, buckets, cap; bool g64; };
+    // the last: the device's own geometry for 0xff00-byte blocks (bgzf_deflate_g64.hpp), where the first runs g32's phase A on them
+    const Geom geoms[3] = {{"0xff00-byte blocks", 0xff00, 512, (8192 + 2560) / 8, false}, {"0x7f00-byte blocks", 0x7f00, 384, 2560 / 8, false},
+                           {"0xff00, role pipeline", 0xff00, 0, 0, true}};
+    // MODEL_GEOM=64|32 (default 32): the device geometry that MODEL_DUMP writes; MODEL_FILES_ONLY=1: only the payload files, only
+    // in that geometry (tests that dump many files)
+    const bool dump64 = getenv("MODEL_GEOM") && atoi(getenv("MODEL_GEOM")) == 64;
+    const bool files_only = getenv("MODEL_FILES_ONLY") && atoi(getenv("MODEL_FILES_ONLY")) != 0;
     // extra payloads from files (experiments: python dumps of tests/test_gpu_bgzf.py's payloads)
     for (int k = 1; k < argc; k++) {
         FILE *f = fopen(argv[k], "rb");
@@ -436,6 +542,9 @@ int main(int argc, char **argv) {
     }
     for (const Geom &g : geoms)
     for (const Case &c : cases) {
+        const bool dumped = g.g64 ? dump64 : (!dump64 && g.block == 0x7f00);  // the geometry MODEL_DUMP is about
+        if (files_only && !(dumped && c.name.rfind("file ", 0) == 0)) continue;
+        G64 = g.g64;
         BLOCK = g.block;
         N_BUCKETS = g.buckets;
         SEG_CAP = g.cap;
@@ -458,9 +567,10 @@ int main(int argc, char **argv) {
             for (size_t o = 0; o < c.data.size(); o += (size_t)BLOCK) {
                 const int n = (int)std::min<size_t>((size_t)BLOCK, c.data.size() - o);
                 const std::vector<uint8_t> z = model_deflate(c.data.data() + o, n, lazy != 0);
-                // MODEL_DUMP=path: the 0x7f00 geometry's raw DEFLATE streams of the payload files, each behind its length
-                // (u32): what tests/test_gpu_bgzf.py holds the device's members to, byte for byte
-                if (getenv("MODEL_DUMP") && g.block == 0x7f00 && c.name.rfind("file ", 0) == 0) {
+                // MODEL_DUMP=path: the raw DEFLATE streams of the payload files in one of the device's geometries (MODEL_GEOM),
+                // each behind its length (u32): what tests/test_gpu_bgzf.py and tests/test_gpu_bgzf_edges.py hold the device's
+                // members to, byte for byte
+                if (getenv("MODEL_DUMP") && dumped && c.name.rfind("file ", 0) == 0) {
                     FILE *df = fopen(getenv("MODEL_DUMP"), "ab");
                     if (df) {
                         const uint32_t zl = (uint32_t)z.size();

@@ -1,7 +1,7 @@
 """The device BGZF compressor's output, pinned byte for byte in BOTH block geometries (fade_amd/csrc/bgzf_deflate.hpp).
-tests/test_gpu_bgzf.py holds the output to zlib (it inflates to the input) and the 0x7f00-byte geometry to the CPU model; the
-0xff00-byte geometry has no model, so a changed byte that still inflates would pass there.  Here the SHA-256 and the length of
-every case's stream are compared with tests/golden/bgzf_device_digests.json, recorded on an MI355X from the commit the file
+tests/test_gpu_bgzf.py and tests/test_gpu_bgzf_edges.py hold the output to zlib (it inflates to the input) and both geometries
+to the CPU model (host/selftest/gpu_deflate_model.cpp), which is the reference.  This file is a regression pin beside it, on
+payloads of plain character at the block boundaries: the SHA-256 and the length of every case's stream are compared with tests/golden/bgzf_device_digests.json, recorded on an MI355X from the commit the file
 names (tools/bgzf_record_digests.py, which builds its payloads through build_cases below and refuses a digest that is not
 the same in three runs).  A change that means to alter the compressor's bytes records the file anew and says so."""
 import hashlib
