@@ -148,6 +148,12 @@ int fadehip_extract_batch(fadehip_ctx* ctx, int n, const(ubyte)* recs, const(lon
 /// rs[k] & 6; grouped != 0 (name-sorted input): a run of consecutive records with equal names is ejected as a whole when one has rs & 6
 int fadehip_eject_batch(fadehip_ctx* ctx, int n, const(ubyte)* recs, const(long)* rec_off, const(ubyte)* rs, int grouped, ubyte* keep);
 int fadehip_genome_upload(fadehip_ctx* ctx, int n_contigs, const(long)* lengths, const(ubyte*)* seqs);
+/// columns 2-5 of a .fai line: bases to take, file offset of the first base (of the uncompressed text), bases and bytes per line
+struct fadehip_fai_entry { long length, offset; int line_bases, line_width; }
+/// the same genome read by the library from the FASTA file (plain or bgzip) through its index: contig c is entries[c]
+int fadehip_genome_upload_fasta(fadehip_ctx* ctx, const(char)* path, int n_contigs, const(fadehip_fai_entry)* entries);
+/// fetchSequence (analysis.d:63) on the uploaded genome: n upper-case letters of contig tid from the 0-based start
+int fadehip_genome_fetch(fadehip_ctx* ctx, int tid, long start, long n, ubyte* out_);
 int fadehip_annotate_upload(fadehip_ctx* ctx, int slot, const(fadehip_read_batch)* batch);
 int fadehip_annotate_run(fadehip_ctx* ctx, int slot, int floor_len, int window);
 int fadehip_annotate_submit(fadehip_ctx* ctx, int slot, const(fadehip_read_batch)* batch,

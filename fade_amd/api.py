@@ -11,6 +11,7 @@ arrays and formats the am/as/ar/ab strings exactly as analysis.d:84-92,108-118 a
 anno.d:94-107 do.  There is no CPU implementation of the alignment here.
 """
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -229,6 +230,28 @@ class Context:
         ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in arrs])
         self._chk(self._L.fadehip_genome_upload(self._h, n, C.cast(lens, C.c_void_p), C.cast(ptrs, C.c_void_p)))
         self.contig_names = [x.decode() if isinstance(x, bytes) else x for x in names]
+
+    def genome_upload_fasta(self, path, names=None):
+        """The genome from an indexed FASTA file (plain or bgzip-compressed): the library reads the file through path + ".fai"
+        and packs it on the device.  names: the contigs to take, in this order (default: every contig, in the index's order)."""
+        from . import fasta_index
+        fai = fasta_index.read_fai(os.fspath(path) + ".fai")
+        if names is None:
+            picked = fai
+        else:
+            by_name = {e.name: e for e in fai}
+            picked = [by_name[n.decode() if isinstance(n, bytes) else n] for n in names]
+        ents = (_lib.FaiEntry * max(len(picked), 1))()
+        for k, e in enumerate(picked):
+            ents[k].length, ents[k].offset, ents[k].line_bases, ents[k].line_width = e.length, e.offset, e.line_bases, e.line_width
+        self._chk(self._L.fadehip_genome_upload_fasta(self._h, os.fsencode(path), len(picked), ents))
+        self.contig_names = [e.name for e in picked]
+
+    def genome_fetch(self, tid, start, n):
+        """n upper-case letters of contig tid from the 0-based start, as the device holds them (fetchSequence, analysis.d:63)."""
+        out = np.empty(max(int(n), 1), dtype=np.uint8)
+        self._chk(self._L.fadehip_genome_fetch(self._h, int(tid), int(start), int(n), out.ctypes.data))
+        return out[:max(int(n), 0)].tobytes()
 
     _ARRAYS = (("tid", np.int32), ("pos", np.int32), ("l_seq", np.int32), ("cigar_off", np.uint32), ("seq_off", np.uint32),
                ("flag", np.uint16), ("has_sa", np.uint8), ("cigar_ops", np.uint32), ("seq_packed", np.uint8))

@@ -12,8 +12,13 @@
 #include "bam_device.hpp"
 #include "sw_stats.hpp"
 #include <rccl/rccl.h>
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <unistd.h>
 #include <algorithm>
+#include <cerrno>
 #include <chrono>
+#include <climits>
 #include <condition_variable>
 #include <cstdarg>
 #include <cstdio>
@@ -2089,9 +2094,9 @@ int fadehip_extract_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, cons
 }
 
 // ------------------------------------------------------------------------------- level 2
-int fadehip_genome_upload(fadehip_ctx *ctx, int32_t n_contigs, const int64_t *lengths, const uint8_t *const *seqs) {
-    if (!ctx) return set_err(nullptr, FADEHIP_E_INVALID, "ctx is NULL");
-    if (n_contigs <= 0 || !lengths || !seqs) return set_err(ctx, FADEHIP_E_INVALID, "bad genome arguments");
+// What every genome upload starts with: the contigs' places in the packed genome (each on a 16-base boundary), the buffers,
+// the genome cleared (pad bases are 0) and the two contig arrays on the device.  ctx->n_contigs is the caller's to set, last.
+static int genome_begin(fadehip_ctx *ctx, int32_t n_contigs, const int64_t *lengths) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
     ctx->h_contig_len.assign(lengths, lengths + n_contigs);
     ctx->h_contig_base.resize(n_contigs);
@@ -2110,6 +2115,15 @@ int fadehip_genome_upload(fadehip_ctx *ctx, int32_t n_contigs, const int64_t *le
     HIPCHK(ctx, hipMemcpyAsync(ctx->contig_len.p, lengths, sizeof(int64_t) * n_contigs, hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipMemcpyAsync(ctx->contig_base.p, ctx->h_contig_base.data(), sizeof(uint64_t) * n_contigs, hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipStreamSynchronize(st));  // (the two host arrays are pageable)
+    return 0;
+}
+
+int fadehip_genome_upload(fadehip_ctx *ctx, int32_t n_contigs, const int64_t *lengths, const uint8_t *const *seqs) {
+    if (!ctx) return set_err(nullptr, FADEHIP_E_INVALID, "ctx is NULL");
+    if (n_contigs <= 0 || !lengths || !seqs) return set_err(ctx, FADEHIP_E_INVALID, "bad genome arguments");
+    int rc;
+    if ((rc = genome_begin(ctx, n_contigs, lengths))) return rc;
+    hipStream_t st = ctx->copy_stream;
     const size_t CH = (size_t)64 << 20;  // staging chunk, even
     DevBuf stage, bad;
     if ((rc = reserve(ctx, stage, CH)) || (rc = reserve(ctx, bad, 4))) {
@@ -2138,6 +2152,326 @@ int fadehip_genome_upload(fadehip_ctx *ctx, int32_t n_contigs, const int64_t *le
     if (e != hipSuccess) return set_err(ctx, FADEHIP_E_HIP, "genome upload failed: %s", hipGetErrorString(e));
     if (h_bad) return set_err(ctx, FADEHIP_E_RESIDUE, "FASTA contains '=' which is not a residue this encoding can represent");
     ctx->n_contigs = n_contigs;
+    return 0;
+}
+
+// ---- fadehip_genome_upload_fasta: the FASTA file through its .fai index, packed on the device
+namespace {
+
+// bases of the entry whose byte lies in front of file position x (the byte of base b is offset + b / lb * lw + b % lb)
+int64_t fai_bases_before(const fadehip_fai_entry &e, int64_t x) {
+    if (e.length == 0 || x <= e.offset) return 0;
+    const int64_t d = x - e.offset, full = d / e.line_width, rem = d % e.line_width;
+    return std::min<int64_t>(full * e.line_bases + std::min<int64_t>(rem, e.line_bases), e.length);
+}
+// 16-base groups of the entry whose LAST byte lies in front of x: the groups the ranges in front of x own
+int64_t fai_groups_before(const fadehip_fai_entry &e, int64_t x) {
+    const int64_t nb = fai_bases_before(e, x);
+    return nb >= e.length ? (e.length + FASTA_GROUP - 1) / FASTA_GROUP : nb / FASTA_GROUP;
+}
+int64_t fai_pos(const fadehip_fai_entry &e, int64_t b) { return e.offset + b / e.line_bases * e.line_width + b % e.line_bases; }
+
+// read fd[off, off + n) into dst: one pread loop per thread, at most four threads (a few MB each at the least)
+bool read_range(int fd, uint8_t *dst, size_t n, int64_t off) {
+    const int nt = (int)std::max<size_t>(1, std::min<size_t>(4, n >> 22));
+    std::vector<char> ok((size_t)nt, 1);
+    auto part = [&](int k) {
+        size_t a = n * (size_t)k / (size_t)nt;
+        const size_t b = n * ((size_t)k + 1) / (size_t)nt;
+        while (a < b) {
+            const ssize_t r = pread(fd, dst + a, b - a, (off_t)(off + (int64_t)a));
+            if (r <= 0) {
+                if (r < 0 && errno == EINTR) continue;
+                ok[(size_t)k] = 0;
+                return;
+            }
+            a += (size_t)r;
+        }
+    };
+    std::vector<std::thread> th;
+    for (int k = 1; k < nt; k++) th.emplace_back(part, k);
+    part(0);
+    for (auto &t : th) t.join();
+    return std::find(ok.begin(), ok.end(), (char)0) == ok.end();
+}
+
+struct FastaUpload {  // what one call holds, given back however it ends
+    int fd = -1;
+    PinBuf chunk[2], pieces[2], tick[2], hblocks[2];
+    hipEvent_t copied[2] = {nullptr, nullptr};
+    DevBuf stage, d_pieces, flags;
+    DevBuf comp[2], blocks[2], status[2], ticket[2], inf[2];  // BGZF: per parity of the call
+    ~FastaUpload() {
+        if (fd >= 0) close(fd);
+        for (int k = 0; k < 2; k++) {
+            release(chunk[k]);
+            release(pieces[k]);
+            release(tick[k]);
+            release(hblocks[k]);
+            if (copied[k]) (void)hipEventDestroy(copied[k]);
+            release(comp[k]);
+            release(blocks[k]);
+            release(status[k]);
+            release(ticket[k]);
+            release(inf[k]);
+        }
+        release(stage);
+        release(d_pieces);
+        release(flags);
+    }
+};
+
+// The pieces of the file range [w0, w1) (every group whose last byte lies in it), into `out`; *lo / *hi: the bytes they read.
+uint64_t fasta_pieces(const fadehip_ctx *ctx, int32_t n, const fadehip_fai_entry *e, const std::vector<int64_t> &end, int64_t w0, int64_t w1,
+                      FastaPiece *out, uint32_t *n_out, int64_t *lo, int64_t *hi) {
+    uint64_t groups = 0;
+    uint32_t np = 0;
+    *lo = INT64_MAX;
+    *hi = 0;
+    for (int32_t c = 0; c < n; c++) {
+        if (e[c].length == 0 || end[(size_t)c] <= w0 || e[c].offset >= w1) continue;
+        const int64_t ga = fai_groups_before(e[c], w0), gb = fai_groups_before(e[c], w1);
+        if (gb <= ga) continue;
+        FastaPiece &p = out[np++];
+        p.src = e[c].offset;  // (file position: the caller takes the staged range's origin off)
+        p.out_byte = ctx->h_contig_base[(size_t)c] / 2;
+        p.length = e[c].length;
+        p.g0 = ga;
+        p.first = groups;
+        p.line_bases = e[c].line_bases;
+        p.line_width = e[c].line_width;
+        p.contig = c;
+        p.pad = 0;
+        groups += (uint64_t)(gb - ga);
+        *lo = std::min(*lo, fai_pos(e[c], ga * FASTA_GROUP));
+        *hi = std::max(*hi, fai_pos(e[c], std::min<int64_t>(gb * FASTA_GROUP, e[c].length) - 1) + 1);
+    }
+    *n_out = np;
+    return groups;
+}
+
+int launch_pack_fasta(fadehip_ctx *ctx, hipStream_t st, const uint8_t *in, uint64_t in_bytes, const FastaPiece *d_pieces, uint32_t np, uint64_t groups,
+                      int *d_flags) {
+    const unsigned grid = (unsigned)std::min<uint64_t>((groups + 255) / 256, (uint64_t)std::max(ctx->cu_count, 1) * 16u);
+    hipLaunchKernelGGL(pack_fasta_kernel, dim3(grid), dim3(256), 0, st, in, in_bytes, d_pieces, np, groups, (uint8_t *)ctx->genome.p, d_flags);
+    HIPCHK(ctx, hipGetLastError());
+    return 0;
+}
+
+}  // namespace
+
+int fadehip_genome_upload_fasta(fadehip_ctx *ctx, const char *path, int32_t n_contigs, const fadehip_fai_entry *entries) {
+    if (!ctx) return set_err(nullptr, FADEHIP_E_INVALID, "ctx is NULL");
+    if (n_contigs <= 0 || !entries || !path) return set_err(ctx, FADEHIP_E_INVALID, "bad genome arguments");
+    size_t CH = (size_t)64 << 20;
+    if (const char *v = getenv("FADEHIP_FASTA_CHUNK")) {
+        const long long w = atoll(v);
+        if (w < 4096) return set_err(ctx, FADEHIP_E_INVALID, "FADEHIP_FASTA_CHUNK=%s: at least 4096 bytes", v);
+        CH = (size_t)w;
+    }
+    FastaUpload u;
+    u.fd = open(path, O_RDONLY | O_CLOEXEC);
+    struct stat sb;
+    if (u.fd < 0 || fstat(u.fd, &sb)) return set_err(ctx, FADEHIP_E_INVALID, "cannot open %s: %s", path, strerror(errno));
+    const int64_t file_size = (int64_t)sb.st_size;
+    uint8_t magic[18] = {0};
+    const ssize_t n_magic = pread(u.fd, magic, sizeof magic, 0);
+    const bool gz = n_magic >= 2 && magic[0] == 0x1f && magic[1] == 0x8b;
+    if (gz) {
+        bool bc = false;
+        if (n_magic == 18 && magic[2] == 8 && (magic[3] & 4)) {
+            const size_t xlen = (size_t)magic[10] | ((size_t)magic[11] << 8);
+            bc = xlen >= 6 && magic[12] == 'B' && magic[13] == 'C' && magic[14] == 2 && magic[15] == 0;
+        }
+        if (!bc) return set_err(ctx, FADEHIP_E_UNSUPPORTED, "%s is gzip without BGZF framing (compress it with bgzip)", path);
+    }
+    // the index: what the kernel divides by and steps with, and where every entry ends (before anything is enqueued)
+    std::vector<int64_t> lens((size_t)n_contigs), end((size_t)n_contigs, 0);
+    int64_t slack = 0, max_end = 0, min_off = INT64_MAX;
+    for (int32_t c = 0; c < n_contigs; c++) {
+        const fadehip_fai_entry &e = entries[c];
+        lens[(size_t)c] = e.length;
+        if (e.length < 0) return set_err(ctx, FADEHIP_E_INVALID, "contig %d has negative length", c);
+        if (e.length == 0) continue;
+        if (e.offset < 0 || e.line_bases <= 0 || e.line_width < e.line_bases)
+            return set_err(ctx, FADEHIP_E_INVALID, "index does not match the FASTA: contig %d has offset %lld, %d bases in a line of %d bytes", c,
+                           (long long)e.offset, e.line_bases, e.line_width);
+        const __int128 last = (__int128)e.offset + (__int128)((e.length - 1) / e.line_bases) * e.line_width + (e.length - 1) % e.line_bases;
+        if (!gz && last >= (__int128)file_size)
+            return set_err(ctx, FADEHIP_E_INVALID, "index does not match the FASTA: contig %d ends beyond the file's %lld bytes", c, (long long)file_size);
+        if (last >= ((__int128)1 << 62)) return set_err(ctx, FADEHIP_E_INVALID, "index does not match the FASTA: contig %d ends beyond any file", c);
+        end[(size_t)c] = (int64_t)last + 1;
+        max_end = std::max(max_end, end[(size_t)c]);
+        min_off = std::min(min_off, e.offset);
+        // a 16-base group crosses at most 1 + 14 / line_bases line ends: the bytes in front of its last one that it reaches back to
+        const int64_t gaps = 1 + 14 / e.line_bases;
+        slack = std::max<int64_t>(slack, FASTA_GROUP - 1 + gaps * (int64_t)(e.line_width - e.line_bases));
+    }
+    if (slack > (int64_t)CH / 2)
+        return set_err(ctx, FADEHIP_E_INVALID, "index does not match the FASTA: line ends of %lld bytes and more do not fit chunks of %zu", (long long)(slack / 15), CH);
+    int rc;
+    if ((rc = genome_begin(ctx, n_contigs, lens.data()))) return rc;
+    hipStream_t st = ctx->copy_stream;
+    if (max_end == 0) {  // nothing but empty contigs
+        ctx->n_contigs = n_contigs;
+        return 0;
+    }
+    const size_t PAD = ((size_t)slack + 63) & ~(size_t)63;  // bytes staged in front of a range
+    if (!gz) CH = std::min(CH, (((size_t)(max_end - min_off) + 4095) & ~(size_t)4095));  // (a small file: small chunks)
+    const size_t read_cap = gz ? std::max<size_t>(CH, 65536 + 1024) : CH + PAD;
+    for (int k = 0; k < 2; k++) {
+        if ((rc = reserve_pinned(ctx, u.chunk[k], read_cap)) || (rc = reserve_pinned(ctx, u.pieces[k], sizeof(FastaPiece) * (size_t)n_contigs)) ||
+            (rc = reserve_pinned(ctx, u.tick[k], 64)))
+            return rc;
+        HIPCHK(ctx, hipEventCreateWithFlags(&u.copied[k], hipEventDisableTiming));
+        memset(u.tick[k].p, 0, 64);
+    }
+    if ((rc = reserve(ctx, u.d_pieces, sizeof(FastaPiece) * (size_t)n_contigs)) || (rc = reserve(ctx, u.flags, 8))) return rc;
+    if (!gz && (rc = reserve(ctx, u.stage, read_cap))) return rc;
+    HIPCHK(ctx, hipMemsetAsync(u.flags.p, 0, 4, st));
+    HIPCHK(ctx, hipMemsetD32Async((hipDeviceptr_t)((int *)u.flags.p + 1), INT_MAX, 1, st));
+    int *d_flags = (int *)u.flags.p;
+    uint32_t call = 0;  // chunks that went to the device so far
+    if (!gz) {
+        for (int64_t w0 = min_off / (int64_t)CH * (int64_t)CH; w0 < max_end;) {
+            const int64_t w1 = w0 + (int64_t)CH;
+            const int par = (int)(call & 1);
+            if (call >= 2) HIPCHK(ctx, hipEventSynchronize(u.copied[par]));  // the chunk's previous bytes have left it
+            FastaPiece *hp = (FastaPiece *)u.pieces[par].p;
+            uint32_t np = 0;
+            int64_t lo, hi;
+            const uint64_t groups = fasta_pieces(ctx, n_contigs, entries, end, w0, w1, hp, &np, &lo, &hi);
+            if (!groups) {  // a range no contig ends a group in: on to the next one that holds a contig's start
+                int64_t next = INT64_MAX;
+                for (int32_t c = 0; c < n_contigs; c++)
+                    if (end[(size_t)c] > w1) next = std::min(next, std::max(entries[c].offset, w1));
+                w0 = next == INT64_MAX ? w1 : std::max(w1, next / (int64_t)CH * (int64_t)CH);
+                continue;
+            }
+            if (hi - lo > (int64_t)read_cap) return set_err(ctx, FADEHIP_E_STATE, "internal: a chunk of %lld bytes", (long long)(hi - lo));
+            for (uint32_t k = 0; k < np; k++) hp[k].src -= lo;
+            if (!read_range(u.fd, u.chunk[par].p, (size_t)(hi - lo), lo)) return set_err(ctx, FADEHIP_E_INVALID, "cannot read %s: %s", path, strerror(errno));
+            HIPCHK(ctx, hipMemcpyAsync(u.stage.p, u.chunk[par].p, (size_t)(hi - lo), hipMemcpyHostToDevice, st));
+            HIPCHK(ctx, hipMemcpyAsync(u.d_pieces.p, hp, sizeof(FastaPiece) * (size_t)np, hipMemcpyHostToDevice, st));
+            HIPCHK(ctx, hipEventRecord(u.copied[par], st));
+            if ((rc = launch_pack_fasta(ctx, st, (const uint8_t *)u.stage.p, (uint64_t)(hi - lo), (const FastaPiece *)u.d_pieces.p, np, groups, d_flags))) return rc;
+            call++;
+            w0 = w1;
+        }
+    } else {
+        // BGZF: compressed bytes cut at member boundaries, inflated into a device buffer that keeps the PAD bytes in front of
+        // the call's range (the end of the call before), the same kernel on the inflated bytes
+        int64_t cpos = 0, u0 = 0;  // file position of the next member, uncompressed position of its first byte
+        size_t n_prev = 0;         // inflated bytes of the call before
+        std::vector<bgzf::InflateBlock> blocks;
+        auto check_tick = [&](int par) -> int {  // (after a wait that covers the parity's last call)
+            const uint32_t *t = (const uint32_t *)u.tick[par].p;
+            if (!t[1]) return 0;
+            const uint32_t nb = t[2];
+            std::vector<uint32_t> stt(nb);
+            HIPCHK(ctx, hipStreamSynchronize(st));
+            HIPCHK(ctx, hipMemcpy(stt.data(), u.status[par].p, 4 * (size_t)nb, hipMemcpyDeviceToHost));
+            for (uint32_t k = 0; k < nb; k++)
+                if (stt[k]) return set_err(ctx, FADEHIP_E_INVALID, "%s: BGZF member %u of a chunk: %s (%u members failed)", path, k, inflate_error_name(stt[k]), t[1]);
+            return set_err(ctx, FADEHIP_E_INVALID, "%s: %u BGZF members failed", path, t[1]);
+        };
+        while (cpos < file_size) {
+            const int par = (int)(call & 1);
+            if (call >= 2) {
+                HIPCHK(ctx, hipEventSynchronize(u.copied[par]));
+                if ((rc = check_tick(par))) return rc;
+            }
+            size_t want = std::min<size_t>(CH, (size_t)(file_size - cpos)), consumed = 0;
+            uint64_t total = 0;
+            std::string msg;
+            for (;;) {
+                if (!read_range(u.fd, u.chunk[par].p, want, cpos)) return set_err(ctx, FADEHIP_E_INVALID, "cannot read %s: %s", path, strerror(errno));
+                blocks.clear();
+                total = 0;
+                if (!scan_bgzf_members(u.chunk[par].p, want, blocks, &consumed, &total, msg)) return set_err(ctx, FADEHIP_E_INVALID, "%s: %s", path, msg.c_str());
+                if (consumed || want >= std::min<size_t>(65536 + 1024, (size_t)(file_size - cpos))) break;
+                want = std::min<size_t>(65536 + 1024, (size_t)(file_size - cpos));  // (a member longer than a small chunk)
+            }
+            if (!consumed) return set_err(ctx, FADEHIP_E_INVALID, "%s ends inside a BGZF member (at byte %lld)", path, (long long)cpos);
+            cpos += (int64_t)consumed;
+            if (!total) continue;  // empty members only
+            const uint32_t nb = (uint32_t)blocks.size();
+            const int64_t u1 = u0 + (int64_t)total;
+            FastaPiece *hp = (FastaPiece *)u.pieces[par].p;
+            uint32_t np = 0;
+            int64_t lo, hi;
+            const uint64_t groups = fasta_pieces(ctx, n_contigs, entries, end, u0, u1, hp, &np, &lo, &hi);
+            const int64_t origin = u0 - (int64_t)PAD;
+            for (uint32_t k = 0; k < np; k++) hp[k].src -= origin;
+            if ((rc = reserve(ctx, u.comp[par], consumed + 1024 + 16)) || (rc = reserve(ctx, u.blocks[par], sizeof(bgzf::InflateBlock) * (size_t)nb)) ||
+                (rc = reserve(ctx, u.status[par], 4 * (size_t)nb)) || (rc = reserve(ctx, u.ticket[par], 64)) ||
+                (rc = reserve_roomy(ctx, u.inf[par], PAD + (size_t)total + 64)) ||
+                (rc = reserve_pinned(ctx, u.hblocks[par], sizeof(bgzf::InflateBlock) * (size_t)nb)))
+                return rc;
+            memcpy(u.hblocks[par].p, blocks.data(), sizeof(bgzf::InflateBlock) * (size_t)nb);
+            HIPCHK(ctx, hipMemcpyAsync(u.comp[par].p, u.chunk[par].p, consumed, hipMemcpyHostToDevice, st));
+            HIPCHK(ctx, hipMemcpyAsync(u.blocks[par].p, u.hblocks[par].p, sizeof(bgzf::InflateBlock) * (size_t)nb, hipMemcpyHostToDevice, st));
+            uint8_t *buf = (uint8_t *)u.inf[par].p;
+            if (call == 0) HIPCHK(ctx, hipMemsetAsync(buf, 0, PAD, st));
+            else HIPCHK(ctx, hipMemcpyAsync(buf, (const uint8_t *)u.inf[par ^ 1].p + n_prev, PAD, hipMemcpyDeviceToDevice, st));
+            bgzf::InflateArgs a;
+            a.comp = (const uint8_t *)u.comp[par].p;
+            a.blocks = (const bgzf::InflateBlock *)u.blocks[par].p;
+            a.n_blocks = nb;
+            a.out = buf + PAD;
+            a.out_shift = nullptr;
+            a.status = (uint32_t *)u.status[par].p;
+            a.ticket = (uint32_t *)u.ticket[par].p;
+            a.check_crc = 1;
+            if ((rc = launch_inflate(ctx, st, a))) return rc;
+            ((uint32_t *)u.tick[par].p)[2] = nb;
+            HIPCHK(ctx, hipMemcpyAsync(u.tick[par].p, u.ticket[par].p, 8, hipMemcpyDeviceToHost, st));
+            if (groups) {
+                HIPCHK(ctx, hipMemcpyAsync(u.d_pieces.p, hp, sizeof(FastaPiece) * (size_t)np, hipMemcpyHostToDevice, st));
+                if ((rc = launch_pack_fasta(ctx, st, buf, (uint64_t)PAD + total, (const FastaPiece *)u.d_pieces.p, np, groups, d_flags))) return rc;
+            }
+            HIPCHK(ctx, hipEventRecord(u.copied[par], st));
+            n_prev = (size_t)total;
+            u0 = u1;
+            call++;
+        }
+        HIPCHK(ctx, hipStreamSynchronize(st));
+        for (int par = 0; par < 2; par++)
+            if ((rc = check_tick(par))) return rc;
+        if (u0 < max_end) {
+            for (int32_t c = 0; c < n_contigs; c++)
+                if (end[(size_t)c] > u0)
+                    return set_err(ctx, FADEHIP_E_INVALID, "index does not match the FASTA: contig %d ends beyond the file's %lld uncompressed bytes", c, (long long)u0);
+        }
+    }
+    int h_flags[2] = {0, INT_MAX};
+    HIPCHK(ctx, hipMemcpyAsync(h_flags, u.flags.p, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    if (h_flags[1] != INT_MAX)
+        return set_err(ctx, FADEHIP_E_INVALID, "index does not match the FASTA: contig %d has a line end, '>' or a control byte where the index puts a base", h_flags[1]);
+    if (h_flags[0]) return set_err(ctx, FADEHIP_E_RESIDUE, "FASTA contains '=' which is not a residue this encoding can represent");
+    ctx->n_contigs = n_contigs;
+    return 0;
+}
+
+int fadehip_genome_fetch(fadehip_ctx *ctx, int32_t tid, int64_t start, int64_t n, uint8_t *out) {
+    if (!ctx) return set_err(nullptr, FADEHIP_E_INVALID, "ctx is NULL");
+    if (ctx->n_contigs == 0) return set_err(ctx, FADEHIP_E_STATE, "no genome has been uploaded");
+    if (tid < 0 || tid >= ctx->n_contigs || (size_t)tid >= ctx->h_contig_len.size()) return set_err(ctx, FADEHIP_E_INVALID, "contig %d of %d", tid, ctx->n_contigs);
+    const int64_t len = ctx->h_contig_len[(size_t)tid];
+    if (start < 0 || n < 0 || start > len || n > len - start || (n && !out))
+        return set_err(ctx, FADEHIP_E_INVALID, "bases [%lld, %lld + %lld) are not inside contig %d of %lld bases", (long long)start, (long long)start, (long long)n, tid, (long long)len);
+    if (n == 0) return 0;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const uint64_t b0 = ctx->h_contig_base[(size_t)tid] + (uint64_t)start, first = b0 / 2, last = (b0 + (uint64_t)n - 1) / 2;
+    std::vector<uint8_t> packed((size_t)(last - first + 1));
+    HIPCHK(ctx, hipMemcpy(packed.data(), (const uint8_t *)ctx->genome.p + first, packed.size(), hipMemcpyDeviceToHost));
+    static const char letters[] = "=ACMGRSVTWYHKDBN";
+    for (int64_t k = 0; k < n; k++) {
+        const uint64_t b = b0 + (uint64_t)k;
+        const uint8_t v = packed[(size_t)(b / 2 - first)];
+        out[k] = (uint8_t)letters[(b & 1) ? (v & 15) : (v >> 4)];
+    }
     return 0;
 }
 

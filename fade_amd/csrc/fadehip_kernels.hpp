@@ -130,6 +130,66 @@ __global__ void pack_ascii_kernel(const uint8_t *__restrict__ in, uint64_t n_bas
     out[(out_base >> 1) + k] = (uint8_t)((c_ascii_code[a0] << 4) | c_ascii_code[a1]);
 }
 
+// ---------------------------------------------------------------- indexed FASTA bytes -> packed 4-bit
+// The part of one contig that a staged range of the file serves (fadehip_genome_upload_fasta).  Work is cut into groups of
+// sixteen bases = eight output bytes: contigs start on sixteen-base boundaries of the packed genome, so every group is one
+// aligned 64-bit word of it, and a group belongs to the range that holds its last byte (the host stages the few bytes in
+// front of the range that such a group reaches back to).
+struct FastaPiece {
+    int64_t src;          // where base 0 of the contig lies, relative to the first staged byte (negative: in front of it)
+    uint64_t out_byte;    // byte of the packed genome that holds base 0 of the contig
+    int64_t length;       // bases taken of the contig
+    int64_t g0;           // the piece's first group
+    uint64_t first;       // number of groups of the launch in front of this piece
+    int32_t line_bases, line_width;  // .fai columns 4 and 5
+    int32_t contig, pad;
+};
+constexpr int FASTA_GROUP = 16;
+
+// One group per thread: ONE division finds the group's line, then the source position steps (a line end adds the width of
+// the terminator).  flags[0] is set when a base is '=' (FADEHIP_E_RESIDUE); flags[1] takes the smallest contig index that has
+// a line terminator, a '>', a control byte or a byte outside the staged range where the index says a base is (a stale
+// index: FADEHIP_E_INVALID).  Nothing outside in[0, in_bytes) is ever read, whatever the index says.
+__global__ __launch_bounds__(256) void pack_fasta_kernel(const uint8_t *__restrict__ in, uint64_t in_bytes, const FastaPiece *__restrict__ pieces,
+                                                         uint32_t n_pieces, uint64_t n_groups, uint8_t *__restrict__ out, int *flags) {
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n_groups; t += (uint64_t)gridDim.x * blockDim.x) {
+        uint32_t lo = 0, hi = n_pieces - 1;  // the last piece that starts at or in front of t
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi + 1) >> 1;
+            if (pieces[mid].first <= t) lo = mid;
+            else hi = mid - 1;
+        }
+        const FastaPiece p = pieces[lo];
+        const int64_t g = p.g0 + (int64_t)(t - p.first), b0 = g * FASTA_GROUP;
+        const int n = (int)(p.length - b0 < FASTA_GROUP ? p.length - b0 : FASTA_GROUP);
+        const int64_t line = b0 / p.line_bases;
+        int64_t col = b0 - line * p.line_bases;
+        int64_t at = p.src + line * p.line_width + col;
+        uint64_t word = 0;
+        bool eq = false, stale = false;
+        for (int k = 0; k < n; k++) {
+            const bool inside = (uint64_t)at < in_bytes;
+            const uint8_t a = inside ? in[at] : 0;
+            stale |= a <= 0x20 || a == '>';
+            eq |= a == '=';
+            word |= (uint64_t)c_ascii_code[a] << (8 * (k >> 1) + ((k & 1) ? 0 : 4));
+            at++;
+            if (++col == p.line_bases) {
+                col = 0;
+                at += p.line_width - p.line_bases;
+            }
+        }
+        uint8_t *o = out + p.out_byte + (uint64_t)g * (FASTA_GROUP / 2);
+        if (n == FASTA_GROUP) {
+            *reinterpret_cast<uint64_t *>(o) = word;
+        } else {
+            for (int j = 0; j < (n + 1) / 2; j++) o[j] = (uint8_t)(word >> (8 * j));
+        }
+        if (eq) flags[0] = 1;
+        if (stale) atomicMin(flags + 1, p.contig);
+    }
+}
+
 struct Cand {           // pass-2 work item: which alignment, and the sweep step its traced re-computation resumes at
     uint32_t src;       // index into the class work list
     uint32_t c0;        // first step T0 (multiple of CK_COLS; 0 = from the start of the sweep)

@@ -28,6 +28,7 @@
 #include <fcntl.h>
 #include <spawn.h>
 #include <sys/stat.h>
+#include <unordered_map>
 #include <sys/wait.h>
 #include <unistd.h>
 
@@ -869,6 +870,84 @@ static double since_process_start() {
     fclose(f);
     return up - (double)start / (double)sysconf(_SC_CLK_TCK);
 }
+
+// The genome of an annotate run (anno.d:23 opens an IndexedFastaFile).  With <fasta>.fai beside the file — unless
+// FADE_FASTA_INDEX=0, or the file is gzip without BGZF framing — prepare() only parses the index and upload() hands the file to
+// the library, which reads it through the index while the device packs it (fadehip_genome_upload_fasta): no residue passes
+// through this program.  In every other case the whole file is read into strings and uploaded from them, as before.  Either
+// way the @SQ names and lengths are held against the FASTA first.
+struct GenomeSource {
+    bool indexed = false;
+    std::string fasta, fai_path;
+    Fasta fa;
+    std::vector<fadehip_fai_entry> entries;
+    std::vector<int64_t> lens;
+    std::vector<const uint8_t *> ptrs;
+    double prepare_s = 0, upload_s = 0;
+    static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+    // 0, or 1 with the reason on stderr (a file that cannot be read throws, as load_fasta does)
+    int prepare(const std::string &path, const std::vector<std::string> &sq_names, const std::vector<int64_t> &sq_lens) {
+        const double t0 = now();
+        fasta = path;
+        fai_path = path + ".fai";
+        Fai fai;
+        const char *sw = getenv("FADE_FASTA_INDEX");
+        indexed = !(sw && strcmp(sw, "0") == 0) && !is_plain_gzip(path) && load_fai(fai_path, fai);
+        if (!indexed) fa = load_fasta(path);  // anno.d:23
+        const std::vector<std::string> &names = indexed ? fai.names : fa.names;
+        lens.resize(sq_names.size());
+        ptrs.assign(sq_names.size(), nullptr);
+        entries.resize(indexed ? sq_names.size() : 0);
+        std::unordered_map<std::string, size_t> by_name;
+        for (size_t q = names.size(); q-- > 0;) by_name[names[q]] = q;  // (the first of equal names, as a linear search finds it)
+        // contigs of the BAM header, in tid order, must be present in the FASTA (fetchSequence by name, analysis.d:63)
+        for (size_t k = 0; k < sq_names.size(); k++) {
+            auto it = by_name.find(sq_names[k]);
+            if (it == by_name.end()) {
+                fprintf(stderr, "[E::fade annotate] reference %s of the BAM header is not in %s\n", sq_names[k].c_str(), path.c_str());
+                return 1;
+            }
+            const size_t q = it->second;
+            // analysis.d:55-59 clamps the window at the header's targetLength; the FASTA may be longer, never shorter
+            const size_t have = indexed ? (size_t)fai.length[q] : fa.seqs[q].size();
+            if ((int64_t)have < sq_lens[k]) {
+                fprintf(stderr, "[E::fade annotate] %s is shorter in the FASTA (%zu) than in the header (%lld)\n", sq_names[k].c_str(), have, (long long)sq_lens[k]);
+                return 1;
+            }
+            lens[k] = sq_lens[k];
+            if (indexed) entries[k] = fadehip_fai_entry{sq_lens[k], fai.offset[q], fai.line_bases[q], fai.line_width[q]};
+            else ptrs[k] = (const uint8_t *)fa.seqs[q].data();
+        }
+        prepare_s += now() - t0;
+        return 0;
+    }
+    int upload(fadehip_ctx *ctx) {
+        const double t0 = now();
+        if (indexed) {
+            if (fadehip_genome_upload_fasta(ctx, fasta.c_str(), (int32_t)entries.size(), entries.data())) {
+                fprintf(stderr, "[E::fade annotate] genome upload through the index %s: %s\n", fai_path.c_str(), fadehip_last_error(ctx));
+                return 1;
+            }
+        } else if (fadehip_genome_upload(ctx, (int)lens.size(), lens.data(), ptrs.data())) {
+            fprintf(stderr, "[E::fade annotate] genome upload: %s\n", fadehip_last_error(ctx));
+            return 1;
+        }
+        upload_s += now() - t0;
+        return 0;
+    }
+    void report() const {
+        long hwm_kb = 0;  // what the host has held at the most so far: the text of the FASTA, or the library's two chunks
+        if (FILE *f = fopen("/proc/self/status", "r")) {
+            char line[256];
+            while (fgets(line, sizeof line, f)) sscanf(line, "VmHWM: %ld", &hwm_kb);
+            fclose(f);
+        }
+        fprintf(stderr, "[timing] genome: %s, %.3f s to read and match, %.3f s to upload; since process start %.3f s (genome resident), host peak %ld MB so far\n",
+                indexed ? "indexed FASTA path (.fai; the library reads the file, the device packs it)" : "whole-file FASTA loader (no index used)", prepare_s,
+                upload_s, since_process_start(), hwm_kb / 1024);
+    }
+};
 
 // ------------------------------------------------------------------ lanes: one process per GPU
 // `fade annotate --gpus N` on a BAM file: N lanes, each a process of its own with its own reader, device and writer, on
@@ -1754,23 +1833,11 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
             q_full.close();
         });
         ck_fasta.start();
-        Fasta fa = load_fasta(o.pos[2]);  // anno.d:23
+        GenomeSource genome;
+        if (genome.prepare(o.pos[2], hdr.names, hdr.lens)) return 1;
         ck_fasta.stop();
         Header out_hdr = hdr;
         out_hdr.add_pg("fade-annotate", "fade", FADE_VERSION, lane.on ? lane.cl : cl);  // anno.d:25-32
-        std::vector<int64_t> lens(hdr.names.size());
-        std::vector<const uint8_t *> ptrs(hdr.names.size());
-        for (size_t k = 0; k < hdr.names.size(); k++) {
-            size_t q = 0;
-            while (q < fa.names.size() && fa.names[q] != hdr.names[k]) q++;
-            if (q == fa.names.size()) { fprintf(stderr, "[E::fade annotate] reference %s of the BAM header is not in %s\n", hdr.names[k].c_str(), o.pos[2].c_str()); return 1; }
-            if ((int64_t)fa.seqs[q].size() < hdr.lens[k]) {
-                fprintf(stderr, "[E::fade annotate] %s is shorter in the FASTA (%zu) than in the header (%lld)\n", hdr.names[k].c_str(), fa.seqs[q].size(), (long long)hdr.lens[k]);
-                return 1;
-            }
-            lens[k] = hdr.lens[k];
-            ptrs[k] = (const uint8_t *)fa.seqs[q].data();
-        }
         ck_upload.start();
         if (ctx_ready.get()) { fprintf(stderr, "[E::fade annotate] cannot open the GPU path: %s\n", create_err.c_str()); return 1; }
         // the buffers the reader has been filling become staging memory now
@@ -1778,7 +1845,8 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
             if (fadehip_host_register(ctx, rb.first, rb.second)) { fprintf(stderr, "[E::fade annotate] %s\n", fadehip_last_error(ctx)); return 1; }
             guard.pinned.push_back(rb.first);
         }
-        if (fadehip_genome_upload(ctx, (int)lens.size(), lens.data(), ptrs.data())) { fprintf(stderr, "[E::fade annotate] genome upload: %s\n", fadehip_last_error(ctx)); return 1; }
+        if (genome.upload(ctx)) return 1;
+        if (o.timing) genome.report();
         // the header goes out through the CPU writer (its members only: no end-of-file block yet; not a byte without a device)
         {
             Writer hw(stdout, o.ubam ? OutFmt::UBAM : OutFmt::BAM, out_hdr, &pool, nullptr, !lane.on || lane.k == 0 || lane.shard, false);
@@ -1793,7 +1861,7 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
         ck_upload.stop();
         // (the FASTA's text is on the device now; giving a genome's worth of pages back takes milliseconds, and the first call
         // is waiting: on a thread of its own)
-        std::thread([seqs = std::move(fa.seqs)]() mutable { seqs.clear(); seqs.shrink_to_fit(); }).detach();
+        std::thread([seqs = std::move(genome.fa.seqs)]() mutable { seqs.clear(); seqs.shrink_to_fit(); }).detach();
         stages.th.emplace_back([&] {  // back: compress, hand to the writer
             int tok;
             try {
@@ -2080,30 +2148,13 @@ static int annotate_main(const std::string &cl, const Opts &o) {
             return 0;
         });
         ck_fasta.start();
-        Fasta fa = load_fasta(o.pos[2]);  // anno.d:23
+        GenomeSource genome;
+        if (genome.prepare(o.pos[2], reader.header().names, reader.header().lens)) return 1;
         ck_fasta.stop();
         Header hdr = reader.header();     // anno.d:24
         hdr.add_pg("fade-annotate", "fade", FADE_VERSION, lane.on ? lane.cl : cl);  // anno.d:25-32
 
-        // contigs of the BAM header, in tid order, must be present in the FASTA (fetchSequence by name, analysis.d:63)
         const Header &h = reader.header();
-        std::vector<int64_t> lens(h.names.size());
-        std::vector<const uint8_t *> ptrs(h.names.size());
-        for (size_t k = 0; k < h.names.size(); k++) {
-            size_t f = 0;
-            while (f < fa.names.size() && fa.names[f] != h.names[k]) f++;
-            if (f == fa.names.size()) {
-                fprintf(stderr, "[E::fade annotate] reference %s of the BAM header is not in %s\n", h.names[k].c_str(), o.pos[2].c_str());
-                return 1;
-            }
-            // analysis.d:55-59 clamps the window at the header's targetLength; the FASTA may be longer, never shorter
-            if ((int64_t)fa.seqs[f].size() < h.lens[k]) {
-                fprintf(stderr, "[E::fade annotate] %s is shorter in the FASTA (%zu) than in the header (%lld)\n", h.names[k].c_str(), fa.seqs[f].size(), (long long)h.lens[k]);
-                return 1;
-            }
-            lens[k] = h.lens[k];
-            ptrs[k] = (const uint8_t *)fa.seqs[f].data();
-        }
         if (h.names.empty()) {
             fprintf(stderr, "[E::fade annotate] input has no @SQ lines\n");
             return 1;
@@ -2119,11 +2170,12 @@ static int annotate_main(const std::string &cl, const Opts &o) {
         }
         for (int d = 0; d < ngpu; d++) {
             blocks[(size_t)d].ctx = ctxs[(size_t)d];
-            if (fadehip_genome_upload(ctxs[(size_t)d], (int)lens.size(), lens.data(), ptrs.data())) return die(ctxs[(size_t)d], "genome upload");
+            if (genome.upload(ctxs[(size_t)d])) return 1;
         }
         ck_upload.stop();
-        fa.seqs.clear();
-        fa.seqs.shrink_to_fit();
+        if (o.timing) genome.report();
+        genome.fa.seqs.clear();
+        genome.fa.seqs.shrink_to_fit();
         // nothing is written to stdout before the GPU path is known to be usable
         const OutFmt fmt = o.bam ? OutFmt::BAM : o.ubam ? OutFmt::UBAM : OutFmt::SAM;  // util.d:65-76
         // BAM output: the BGZF blocks are compressed on the device (FADE_BGZF_DEVICE=0 keeps them on the host pool)

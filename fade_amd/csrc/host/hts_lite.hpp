@@ -1859,4 +1859,58 @@ inline Fasta load_fasta(const std::string &path) {
     return fa;
 }
 
+// <fasta>.fai (samtools faidx): NAME LENGTH OFFSET LINEBASES LINEWIDTH per contig.  With it the FASTA's bytes never pass through
+// the host's hands: the library reads the file and the device finds every base from these five columns.
+struct Fai {
+    std::vector<std::string> names;
+    std::vector<int64_t> length, offset;
+    std::vector<int32_t> line_bases, line_width;
+};
+
+// false: no index at that path.  An index that does not parse throws, naming the file.
+inline bool load_fai(const std::string &path, Fai &fai) {
+    FILE *f = fopen(path.c_str(), "rb");
+    if (!f) return false;
+    std::string text;
+    char buf[1 << 16];
+    size_t n;
+    while ((n = fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, n);
+    fclose(f);
+    size_t at = 0;
+    int line_no = 0;
+    while (at < text.size()) {
+        size_t e = text.find('\n', at);
+        if (e == std::string::npos) e = text.size();
+        std::string line = text.substr(at, e - at);
+        at = e + 1;
+        line_no++;
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line.empty()) continue;
+        const size_t t = line.find('\t');
+        long long len = -1, off = -1, lb = -1, lw = -1;
+        if (t == std::string::npos || t == 0 || sscanf(line.c_str() + t + 1, "%lld\t%lld\t%lld\t%lld", &len, &off, &lb, &lw) != 4 || len < 0 || off < 0 || lb < 0 ||
+            lw < lb || lw > INT32_MAX || (len > 0 && lb == 0))
+            throw std::runtime_error(path + " line " + std::to_string(line_no) + " is not NAME LENGTH OFFSET LINEBASES LINEWIDTH");
+        fai.names.push_back(line.substr(0, t));
+        fai.length.push_back(len);
+        fai.offset.push_back(off);
+        fai.line_bases.push_back((int32_t)lb);
+        fai.line_width.push_back((int32_t)lw);
+    }
+    if (fai.names.empty()) throw std::runtime_error(path + " lists no contigs");
+    return true;
+}
+
+// gzip that is not BGZF (no 'BC' extra subfield in the first member): the indexed path cannot seek or cut it
+inline bool is_plain_gzip(const std::string &path) {
+    FILE *f = fopen(path.c_str(), "rb");
+    if (!f) return false;
+    unsigned char m[18] = {0};
+    const size_t n = fread(m, 1, sizeof m, f);
+    fclose(f);
+    if (n < 2 || m[0] != 0x1f || m[1] != 0x8b) return false;
+    const bool bgzf = n == 18 && m[2] == 8 && (m[3] & 4) && (m[10] | (m[11] << 8)) >= 6 && m[12] == 'B' && m[13] == 'C' && m[14] == 2 && m[15] == 0;
+    return !bgzf;
+}
+
 }  // namespace htsl

@@ -193,6 +193,28 @@ int fadehip_eject_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const 
 int fadehip_genome_upload(fadehip_ctx *ctx, int32_t n_contigs, const int64_t *lengths,
                           const uint8_t *const *seqs);
 
+/* The same genome from the FASTA FILE through its .fai index (what IndexedFastaFile is opened on, anno.d:23): the library
+ * reads the file itself, straight into two pinned staging chunks (at most 4 reading threads; one chunk fills while the device
+ * works on the other), and a kernel turns file bytes into packed bases — the host does work per contig, never per base, and
+ * holds two chunks instead of the text.  Contig c of the genome is entries[c] (columns 2-5 of its .fai line), in the caller's
+ * order whatever the file's; `length` is the number of bases to take and may be less than the contig holds; entries may
+ * overlap or repeat file ranges; length 0 is legal (line_bases may then be 0).  The ctx is left exactly as
+ * fadehip_genome_upload leaves it for the same residues (and on failure).  The file is read front to back once, in chunks of
+ * 64 MB (FADEHIP_FASTA_CHUNK=bytes, at least 4096, read at every call); copies and launches number file bytes / chunk, not
+ * contigs.  An index that does not describe the file — a line terminator, '>' or a control byte where a base should be —
+ * is FADEHIP_E_INVALID ("index does not match the FASTA", with the contig index), as is an entry that ends beyond the file
+ * (found before anything is enqueued); '=' is FADEHIP_E_RESIDUE.
+ * A file that starts with a BGZF member (bgzip) is inflated on the device, .fai offsets being offsets in the uncompressed
+ * text (no .gzi: the file is read front to back); CRC32 / ISIZE failures are FADEHIP_E_INVALID, empty members are legal.
+ * gzip without BGZF framing is FADEHIP_E_UNSUPPORTED.  Synchronous. */
+typedef struct { int64_t length, offset; int32_t line_bases, line_width; } fadehip_fai_entry; /* .fai columns 2-5 */
+int fadehip_genome_upload_fasta(fadehip_ctx *ctx, const char *path, int32_t n_contigs, const fadehip_fai_entry *entries);
+
+/* fetchSequence (analysis.d:63) on the uploaded genome: n letters "=ACMGRSVTWYHKDBN"[code] of contig tid from the 0-based
+ * start (upper case; a byte outside IUPAC reads as '=').  A device-to-host copy of the packed bytes, unpacked on the host.
+ * Synchronous.  A range outside the contig: FADEHIP_E_INVALID; before any upload: FADEHIP_E_STATE. */
+int fadehip_genome_fetch(fadehip_ctx *ctx, int32_t tid, int64_t start, int64_t n, uint8_t *out);
+
 /* BAM-native structure-of-arrays view of n records (what annotateTask reads from a bam1_t). */
 typedef struct {
     int32_t n_reads;
