@@ -147,6 +147,12 @@ int fadehip_extract_batch(fadehip_ctx* ctx, int n, const(ubyte)* recs, const(lon
 /// filter.d:209-265 (plain `fade out`) over n BAM records: keep[k] = 1 when record k would be written.  grouped == 0: ejected when
 /// rs[k] & 6; grouped != 0 (name-sorted input): a run of consecutive records with equal names is ejected as a whole when one has rs & 6
 int fadehip_eject_batch(fadehip_ctx* ctx, int n, const(ubyte)* recs, const(long)* rec_off, const(ubyte)* rs, int grouped, ubyte* keep);
+/// remap.d:31-50, filter.d:24-25,58-59,190-196: rs and am read back out of n BAM records into the arrays the three calls above take.
+/// have[k]: bit 0 an integer rs (rs[k] its low byte), bit 1 an am:Z, bits 2 / 3 its left / right side is "name,pos,cigar"; per such side
+/// s = 2k + side the contig (first of that name in ref_names, or -1), the position and the ops cig[cig_off[s] .. cig_off[s + 1]);
+/// trim_left / trim_right the reference bases those ops take.  More ops than cig_cap: FADEHIP_E_INVALID, nothing written
+int fadehip_tags_batch(fadehip_ctx* ctx, int n, const(ubyte)* recs, const(long)* rec_off, int n_ref, const(char*)* ref_names,
+        ubyte* rs, ubyte* have, int* trim_left, int* trim_right, int* art_tid, long* art_pos, long* cig_off, uint* cig, long cig_cap);
 int fadehip_genome_upload(fadehip_ctx* ctx, int n_contigs, const(long)* lengths, const(ubyte*)* seqs);
 /// columns 2-5 of a .fai line: bases to take, file offset of the first base (of the uncompressed text), bases and bytes per line
 struct fadehip_fai_entry { long length, offset; int line_bases, line_width; }

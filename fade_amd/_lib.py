@@ -33,7 +33,7 @@ EXPORTS = [
     "fadehip_bgzf_deflate_submit", "fadehip_bgzf_deflate_wait", "fadehip_stats_allreduce_rank", "fadehip_bgzf_inflate",
     "fadehip_bam_open", "fadehip_bam_front", "fadehip_bam_front_raw", "fadehip_bam_back", "fadehip_bam_totals", "fadehip_bam_close",
     "fadehip_bam_prepare", "fadehip_sw_stats_batch", "fadehip_clip_batch", "fadehip_extract_batch", "fadehip_bam_back_extract",
-    "fadehip_eject_batch", "fadehip_bam_ejected", "fadehip_genome_upload_fasta", "fadehip_genome_fetch",
+    "fadehip_eject_batch", "fadehip_bam_ejected", "fadehip_genome_upload_fasta", "fadehip_genome_fetch", "fadehip_tags_batch",
 ]
 BAM_STORED, BAM_NO_OUTPUT, BAM_CLIP, BAM_EXTRACT, BAM_EJECT, BAM_EJECT_GROUPS = 1, 2, 4, 8, 16, 32  # fadehip_bam_config.flags
 BGZF_BLOCK = 0xff00
@@ -133,6 +133,7 @@ def load():
     L.fadehip_clip_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, i64, vp]
     L.fadehip_extract_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]
     L.fadehip_eject_batch.argtypes = [vp, i32, vp, vp, vp, C.c_int, vp]
+    L.fadehip_tags_batch.argtypes = [vp, i32, vp, vp, i32, C.POINTER(C.c_char_p), vp, vp, vp, vp, vp, vp, vp, vp, i64]
     L.fadehip_genome_upload.argtypes = [vp, i32, vp, vp]
     L.fadehip_genome_upload_fasta.argtypes = [vp, C.c_char_p, i32, C.POINTER(FaiEntry)]
     L.fadehip_genome_fetch.argtypes = [vp, i32, i64, i64, vp]

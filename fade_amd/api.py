@@ -220,6 +220,37 @@ class Context:
         out, out_off = self.extract_batch_packed(cat, off, rs, tid, pos, cig_off, np.array(cig, dtype=np.uint32))
         return [out[out_off[s]:out_off[s + 1]].tobytes() for s in range(2 * n) if out_off[s + 1] > out_off[s]]
 
+    # ---- remap.d:31-50, filter.d:24-25,58-59,190-196: rs and am read back on the device, in the shapes the three calls above take
+    def tags_batch_packed(self, recs, rec_off, ref_names, cig_cap=None):
+        """rs and am out of BAM records annotated earlier.  Returns a dict: rs, have (uint8[n]; have bit 0 an integer rs, bit 1
+        an am:Z, bits 2 / 3 its left / right side well-formed), trim_left, trim_right (int32[n]), art_tid (int32[2n]), art_pos
+        (int64[2n]), cig_off (int64[2n + 1]) and cig (uint32, BAM-encoded ops) — side 2k is record k's left one, 2k + 1 its
+        right one.  cig_cap: the ops cig may hold (default: as many as the records' bytes could spell)."""
+        recs = np.ascontiguousarray(recs, dtype=np.uint8)
+        rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
+        n = len(rec_off) - 1
+        if cig_cap is None:  # (an op takes at least two bytes of am's text)
+            cig_cap = len(recs) // 2 + 1
+        names = [x.encode() if isinstance(x, str) else bytes(x) for x in ref_names]
+        arr = (C.c_char_p * max(len(names), 1))(*names)
+        o = dict(rs=np.zeros(n, np.uint8), have=np.zeros(n, np.uint8), trim_left=np.zeros(n, np.int32), trim_right=np.zeros(n, np.int32),
+                 art_tid=np.zeros(2 * n, np.int32), art_pos=np.zeros(2 * n, np.int64), cig_off=np.zeros(2 * n + 1, np.int64),
+                 cig=np.zeros(int(cig_cap), np.uint32))
+        self._chk(self._L.fadehip_tags_batch(self._h, n, recs.ctypes.data, rec_off.ctypes.data, len(names), arr, o["rs"].ctypes.data,
+                                             o["have"].ctypes.data, o["trim_left"].ctypes.data, o["trim_right"].ctypes.data,
+                                             o["art_tid"].ctypes.data, o["art_pos"].ctypes.data, o["cig_off"].ctypes.data,
+                                             o["cig"].ctypes.data, int(cig_cap)))
+        o["cig"] = o["cig"][:o["cig_off"][2 * n]]
+        return o
+
+    def tags_batch(self, records, ref_names):
+        """tags_batch_packed over BAM records given as a list of bytes (block_size first); ref_names: the header's contigs."""
+        rb = [bytes(r) for r in records]
+        off = np.zeros(len(rb) + 1, dtype=np.int64)
+        np.cumsum([len(r) for r in rb], out=off[1:])
+        cat = np.frombuffer(b"".join(rb), dtype=np.uint8) if off[-1] else np.zeros(0, np.uint8)
+        return self.tags_batch_packed(cat, off, ref_names)
+
     # ---- level 2: annotateTask over a batch (anno.d:55-110)
     def genome_upload(self, names, seqs):
         """seqs: list of bytes / uint8 arrays (raw FASTA residues)."""

@@ -1382,5 +1382,274 @@ __global__ __launch_bounds__(TAG_BLOCK) void bam_eject_apply_kernel(EjectArgs a,
     }
 }
 
+// ============================================================================================ tags read back
+// fadehip_tags_batch: rs and am out of records that were annotated earlier — by this library, by the reference, or by a
+// tool in between — into the arrays the clip, eject and extract kernels take (remap.d:31-50, filter.d:24-25,58-59,190-196).
+// The first field named rs and the first named am count, as with bam_aux_get.  rs is what tag.to!ubyte makes of an integer
+// field: the low byte of its little-endian value, whatever its width; a field of another type is no rs.  am:Z is
+// "left;right", cut at its first ';' (without one: everything is the left side), a side "name,pos,cigar".
+struct TagsRead {
+    uint32_t am_off, am_len;  // the am:Z string (without its NUL), relative to the record; 0, 0: none
+    uint8_t rs, have;         // have: bit 0 an integer rs, bit 1 an am of type Z
+    bool whole;               // the aux area is whole fields
+};
+__device__ __forceinline__ TagsRead read_tags(const RecHdr &r) {
+    TagsRead t;
+    t.am_off = t.am_len = 0u;
+    t.rs = t.have = 0;
+    t.whole = r.aux_off <= r.end;
+    bool seen_rs = false, seen_am = false;
+    uint32_t q = r.aux_off;
+    while (t.whole && q < r.end) {
+        if (q + 3u > r.end) { t.whole = false; break; }
+        const uint32_t fs = aux_field_size(r.p, q + 2u, r.end);
+        if (!fs) { t.whole = false; break; }
+        const uint8_t a0 = r.p[q], a1 = r.p[q + 1], ty = r.p[q + 2];
+        if (a0 == 'r' && a1 == 's' && !seen_rs) {
+            seen_rs = true;
+            if (ty == 'c' || ty == 'C' || ty == 's' || ty == 'S' || ty == 'i' || ty == 'I') {
+                t.rs = r.p[q + 3];
+                t.have |= 1;
+            }
+        }
+        if (a0 == 'a' && a1 == 'm' && !seen_am) {
+            seen_am = true;
+            if (ty == 'Z') {
+                t.am_off = q + 3u;
+                t.am_len = fs - 2u;
+                t.have |= 2;
+            }
+        }
+        q += 2u + fs;
+    }
+    if (!t.whole) {
+        t.am_off = t.am_len = 0u;
+        t.rs = t.have = 0;
+    }
+    return t;
+}
+
+// the BAM code of a CIGAR letter (MIDNSHP=XB), 0xff for any other byte
+__device__ __forceinline__ uint32_t cigar_op_of(uint32_t c) {
+    switch (c) {
+        case 'M': return 0u;
+        case 'I': return 1u;
+        case 'D': return 2u;
+        case 'N': return 3u;
+        case 'S': return 4u;
+        case 'H': return 5u;
+        case 'P': return 6u;
+        case '=': return 7u;
+        case 'X': return 8u;
+        case 'B': return 9u;
+        default: return 0xffu;
+    }
+}
+// One CIGAR of am, as text: pairs of a count (digits, a value below 2^28) and a letter of MIDNSHP=XB, or nothing at all.
+// Returns whether all n bytes are such pairs; *nops their number, *ref the reference bases they take.
+__device__ __forceinline__ bool am_cigar(const uint8_t *s, uint32_t n, uint32_t *nops, uint64_t *ref) {
+    uint32_t num = 0, k = 0;
+    uint64_t sum = 0;
+    bool digits = false;
+    for (uint32_t j = 0; j < n; j++) {
+        const uint32_t c = s[j];
+        if (c - '0' < 10u) {
+            num = num * 10u + (c - '0');
+            if (num >= (1u << 28)) return false;
+            digits = true;
+            continue;
+        }
+        const uint32_t op = cigar_op_of(c);
+        if (op == 0xffu || !digits) return false;
+        if (FADEHIP_OP_CONSUMES_REF(op)) sum += num;
+        k++;
+        num = 0;
+        digits = false;
+    }
+    *nops = k;
+    *ref = sum;
+    return !digits;
+}
+
+// The contigs' names, as fadehip_tags_batch uploads them: the bytes back to back, their offsets, and for every contig the
+// first one that carries the same name (itself, unless a header names a contig twice).
+struct RefNames {
+    const uint8_t *bytes;
+    const uint32_t *off;    // [n_ref + 1]
+    const int32_t *first;   // [n_ref]
+    int32_t n_ref;
+};
+__device__ __forceinline__ bool name_is(const RefNames &nm, int32_t c, const uint8_t *s, uint32_t n) {
+    const uint32_t o = nm.off[c];
+    if (nm.off[c + 1] - o != n) return false;
+    for (uint32_t j = 0; j < n; j++)
+        if (nm.bytes[o + j] != s[j]) return false;
+    return true;
+}
+// the first contig named s[0 .. n), or -1: the record's own contig is tried first (what annotate writes), then the table
+__device__ __forceinline__ int32_t tid_of_name(const RefNames &nm, int32_t own, const uint8_t *s, uint32_t n) {
+    if (!n) return -1;
+    if (own >= 0 && own < nm.n_ref && name_is(nm, own, s, n)) return nm.first[own];
+    for (int32_t c = 0; c < nm.n_ref; c++)
+        if (name_is(nm, c, s, n)) return c;
+    return -1;
+}
+
+struct AmSide {
+    bool ok;            // "name,pos,cigar", each part as the grammar has it
+    int32_t tid;
+    int64_t pos;
+    uint32_t nops, cig_at;  // ops of the CIGAR; where its text starts, relative to the record
+    int32_t trim;       // the reference bases its ops take, at most INT32_MAX
+};
+// one side of am, s[0 .. n) at offset `at` of the record.  pos is what std.conv.to!long takes: a sign or none, digits, no
+// more, a value of 64 bits.
+__device__ __forceinline__ AmSide am_side(const RecHdr &r, const RefNames &nm, uint32_t at, uint32_t n) {
+    AmSide a;
+    a.ok = false;
+    a.tid = -1;
+    a.pos = 0;
+    a.nops = 0u;
+    a.cig_at = 0u;
+    a.trim = 0;
+    const uint8_t *s = r.p + at;
+    uint32_t c1 = 0;
+    while (c1 < n && s[c1] != ',') c1++;
+    if (c1 >= n) return a;
+    uint32_t c2 = c1 + 1u;
+    while (c2 < n && s[c2] != ',') c2++;
+    if (c2 >= n) return a;
+    uint32_t j = c1 + 1u;
+    const bool neg = s[j] == '-';
+    if (s[j] == '-' || s[j] == '+') j++;  // (s[c2] is the comma: j stays within the side)
+    if (j >= c2) return a;
+    uint64_t mag = 0;
+    for (; j < c2; j++) {
+        const uint32_t d = (uint32_t)s[j] - '0';
+        if (d >= 10u || mag > 922337203685477580ull) return a;
+        mag = mag * 10ull + d;  // (at most 9223372036854775809: no wrap)
+    }
+    if (mag > 0x7fffffffffffffffull + (neg ? 1ull : 0ull)) return a;
+    uint32_t nops;
+    uint64_t ref;
+    if (!am_cigar(s + c2 + 1u, n - c2 - 1u, &nops, &ref)) return a;
+    a.ok = true;
+    a.tid = tid_of_name(nm, r.tid, s, c1);
+    a.pos = neg ? (int64_t)(0ull - mag) : (int64_t)mag;
+    a.nops = nops;
+    a.cig_at = at + c2 + 1u;
+    a.trim = (int32_t)min(ref, (uint64_t)0x7fffffffu);
+    return a;
+}
+
+// exclusive sum of v over a block of TAG_BLOCK threads, the block's total to every thread
+__device__ __forceinline__ uint64_t block_scan_256(uint64_t v, uint64_t *total) {
+    __shared__ uint64_t wsum[TAG_BLOCK / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint64_t inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t o = (uint64_t)__shfl_up((long long)inc, d, 64);
+        if (lane >= d) inc += o;
+    }
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    uint64_t base = 0, tot = 0;
+    for (int w = 0; w < TAG_BLOCK / 64; w++) {
+        const uint64_t t = wsum[w];
+        if (w < wave) base += t;
+        tot += t;
+    }
+    *total = tot;
+    return base + inc - v;
+}
+
+struct TagsArgs {
+    const uint8_t *in;
+    const uint64_t *in_off;   // [n + 1]
+    uint32_t n;
+    RefNames names;
+    uint8_t *rs, *have;       // [n]
+    int32_t *trim_l, *trim_r; // [n]
+    int32_t *tid;             // [2n]
+    int64_t *pos;             // [2n]
+    uint32_t *cnt, *cig_at;   // [2n]  ops of a side; where its CIGAR text starts (count kernel -> write kernel)
+    uint64_t *blk_sums, *blk_base;  // [blocks of TAG_BLOCK records]
+    uint64_t *total;          // ops of the call
+    uint32_t *bad;            // the first record whose aux area is not whole fields (0xffffffff: none)
+    uint64_t *cig_off;        // [2n + 1]
+    uint32_t *cig;            // [*total]
+};
+
+// pass 1, thread per record: everything but the ops — rs, have, both sides' contig, position and trim, their op counts
+__global__ __launch_bounds__(TAG_BLOCK) void tags_count_kernel(TagsArgs a) {
+    const uint32_t i = blockIdx.x * TAG_BLOCK + threadIdx.x;
+    uint64_t ops = 0;
+    if (i < a.n) {
+        const RecHdr r = rec_header(a.in + a.in_off[i]);
+        const TagsRead t = read_tags(r);
+        if (!t.whole) atomicMin(a.bad, i);
+        uint32_t semi = 0;
+        while (semi < t.am_len && r.p[t.am_off + semi] != ';') semi++;
+        uint8_t have = t.have;
+        int32_t trim[2];
+        for (uint32_t side = 0; side < 2u; side++) {
+            AmSide s;
+            if (!(t.have & 2)) s = am_side(r, a.names, 0u, 0u);  // (no text: not well-formed)
+            else if (side == 0u) s = am_side(r, a.names, t.am_off, semi);
+            else s = am_side(r, a.names, t.am_off + min(semi + 1u, t.am_len), t.am_len - min(semi + 1u, t.am_len));
+            if (s.ok) have |= (uint8_t)(4u << side);
+            a.tid[2u * i + side] = s.tid;
+            a.pos[2u * i + side] = s.pos;
+            a.cnt[2u * i + side] = s.nops;
+            a.cig_at[2u * i + side] = s.cig_at;
+            trim[side] = s.trim;
+            ops += s.nops;
+        }
+        a.rs[i] = t.rs;
+        a.have[i] = have;
+        a.trim_l[i] = trim[0];
+        a.trim_r[i] = trim[1];
+    }
+    const uint64_t tot = block_sum_256(ops);
+    if (threadIdx.x == 0) a.blk_sums[blockIdx.x] = tot;
+}
+
+// pass 2, one block: where every block's ops start, and how many there are
+__global__ __launch_bounds__(1024) void tags_scan_kernel(TagsArgs a, uint32_t n_blocks) {
+    scan_block_sums<uint64_t, false>(a.blk_sums, a.blk_base, n_blocks, a.total);
+}
+
+// pass 3, thread per record: the sides' offsets by a scan over the block, then the ops, parsed again from the text
+__global__ __launch_bounds__(TAG_BLOCK) void tags_write_kernel(TagsArgs a) {
+    const uint32_t i = blockIdx.x * TAG_BLOCK + threadIdx.x;
+    uint32_t nl = 0, nr = 0;
+    if (i < a.n) {
+        nl = a.cnt[2u * i];
+        nr = a.cnt[2u * i + 1u];
+    }
+    uint64_t tot;
+    const uint64_t at = a.blk_base[blockIdx.x] + block_scan_256((uint64_t)nl + nr, &tot);
+    if (i >= a.n) return;
+    a.cig_off[2u * i] = at;
+    a.cig_off[2u * i + 1u] = at + nl;
+    if (i + 1u == a.n) a.cig_off[2u * i + 2u] = at + nl + nr;
+    const uint8_t *p = a.in + a.in_off[i];
+    for (uint32_t side = 0; side < 2u; side++) {
+        const uint32_t nops = side ? nr : nl;
+        if (!nops) continue;
+        // the side was found well-formed: its CIGAR text ends where the nops-th op letter stands
+        const uint8_t *s = p + a.cig_at[2u * i + side];
+        uint32_t *dst = a.cig + at + (side ? nl : 0u);
+        uint32_t num = 0, k = 0;
+        for (uint32_t j = 0; k < nops; j++) {
+            const uint32_t c = s[j];
+            if (c - '0' < 10u) { num = num * 10u + (c - '0'); continue; }
+            dst[k++] = (num << 4) | cigar_op_of(c);
+            num = 0;
+        }
+    }
+}
+
 }  // namespace bam
 }  // namespace fadehip

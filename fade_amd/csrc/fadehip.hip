@@ -198,8 +198,9 @@ struct InflateLane {
     PinBuf h_status;
 };
 
-// fadehip_clip_batch, fadehip_extract_batch and fadehip_eject_batch: one stream, made when the first of them is called, and
-// one set of buffers (kept between calls, grow only); a call of any of the three holds mu from its uploads to its last wait
+// fadehip_clip_batch, fadehip_extract_batch, fadehip_eject_batch and fadehip_tags_batch: one stream, made when the first of
+// them is called, and one set of buffers (kept between calls, grow only); a call of any of them holds mu from its uploads to
+// its last wait
 struct BatchLane {
     std::mutex mu;
     hipStream_t stream = nullptr;
@@ -1452,7 +1453,7 @@ int batch_upload(fadehip_ctx *ctx, BatchLane &L, int32_t n, const uint8_t *recs,
     if ((rc = reserve(ctx, L.in, in_bytes + 8)) || (rc = reserve(ctx, L.meta, meta_bytes)) || (rc = reserve(ctx, L.work, work_bytes))) return rc;
     HIPCHK(ctx, hipMemcpyAsync(L.in.p, recs + rec_off[0], in_bytes, hipMemcpyHostToDevice, L.stream));
     HIPCHK(ctx, hipMemcpyAsync(L.meta.p, off.data(), 8 * ((size_t)n + 1), hipMemcpyHostToDevice, L.stream));
-    HIPCHK(ctx, hipMemcpyAsync((uint8_t *)L.meta.p + m_rs, rs, (size_t)n, hipMemcpyHostToDevice, L.stream));
+    if (rs) HIPCHK(ctx, hipMemcpyAsync((uint8_t *)L.meta.p + m_rs, rs, (size_t)n, hipMemcpyHostToDevice, L.stream));  // (fadehip_tags_batch brings none: it makes them)
     return 0;
 }
 
@@ -2091,6 +2092,105 @@ int fadehip_extract_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, cons
     a.n = (uint32_t)n;
     a.out_off = (const uint64_t *)(meta + m_out);
     return size_then_write(ctx, L, a, ns, bam::extract_batch_size_kernel, bam::extract_batch_write_kernel, "extract", false, soff, out, out_cap, out_off);
+}
+
+// remap.d:31-50, filter.d:24-25,58-59,190-196 over records the caller brings: bam_device.hpp's read_tags and am_side fill
+// the arrays the three calls above take.  Count per side, scan, write: a side's ops are as many as its text holds.
+int fadehip_tags_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const int64_t *rec_off, int32_t n_ref, const char *const *ref_names,
+                       uint8_t *rs, uint8_t *have, int32_t *trim_left, int32_t *trim_right, int32_t *art_tid, int64_t *art_pos,
+                       int64_t *cig_off, uint32_t *cig, int64_t cig_cap) {
+    if (!ctx) return set_err(nullptr, FADEHIP_E_INVALID, "ctx is NULL");
+    if (n < 0 || n > (1 << 30) || n_ref < 0 || (n_ref > 0 && !ref_names) || !rec_off || !cig_off ||
+        (n > 0 && (!recs || !rs || !have || !trim_left || !trim_right || !art_tid || !art_pos)) || cig_cap < 0 || (cig_cap > 0 && !cig))
+        return set_err(ctx, FADEHIP_E_INVALID, "NULL argument");
+    if (rec_off[0] < 0) return set_err(ctx, FADEHIP_E_INVALID, "offsets must be non-negative and non-decreasing (record 0)");
+    if (n == 0) {
+        cig_off[0] = 0;
+        return 0;
+    }
+    int rc;
+    if ((rc = check_records(ctx, n, recs, rec_off, true, [](int32_t) { return 0; }))) return rc;
+    // the names back to back, and for every contig the first one of its name
+    std::vector<uint32_t> noff((size_t)n_ref + 1, 0u);
+    std::vector<int32_t> first((size_t)n_ref);
+    std::string nbytes;
+    {
+        std::map<std::string, int32_t> seen;
+        for (int32_t c = 0; c < n_ref; c++) {
+            if (!ref_names[c]) return set_err(ctx, FADEHIP_E_INVALID, "ref_names[%d] is NULL", c);
+            const std::string nm(ref_names[c]);
+            if (nbytes.size() + nm.size() > 0x7fffffffu) return set_err(ctx, FADEHIP_E_INVALID, "the contig names take more than 2^31 bytes");
+            first[(size_t)c] = seen.emplace(nm, c).first->second;
+            nbytes += nm;
+            noff[(size_t)c + 1] = (uint32_t)nbytes.size();
+        }
+    }
+    const size_t ns = 2 * (size_t)n, ntb = ((size_t)n + bam::TAG_BLOCK - 1) / bam::TAG_BLOCK;
+    BatchLane &L = ctx->batch;
+    std::lock_guard<std::mutex> lk(L.mu);
+    // meta: in_off [n + 1] u64 | cig_off [2n + 1] u64 | pos [2n] i64 | tid [2n] i32 | trim_l [n] i32 | trim_r [n] i32 |
+    //       name_off [n_ref + 1] u32 | first [n_ref] i32 | rs [n] u8 | have [n] u8 | name bytes
+    // work: blk_sums [ntb] u64 | blk_base [ntb] u64 | total u64 | bad u32, pad | cnt [2n] u32 | cig_at [2n] u32;  out: the ops
+    const size_t m_coff = 8 * ((size_t)n + 1), m_pos = m_coff + 8 * (ns + 1), m_tid = m_pos + 8 * ns, m_tl = m_tid + 4 * ns,
+                 m_tr = m_tl + 4 * (size_t)n, m_noff = m_tr + 4 * (size_t)n, m_first = m_noff + 4 * ((size_t)n_ref + 1),
+                 m_rs = m_first + 4 * (size_t)n_ref, m_have = m_rs + (size_t)n, m_names = m_have + (size_t)n;
+    const size_t w_base = 8 * ntb, w_tot = 16 * ntb, w_bad = w_tot + 8, w_cnt = w_bad + 8, w_at = w_cnt + 4 * ns;
+    std::vector<uint64_t> off;
+    if ((rc = batch_upload(ctx, L, n, recs, rec_off, nullptr, m_rs, m_names + nbytes.size() + 8, w_at + 4 * ns, off))) return rc;
+    hipStream_t st = L.stream;
+    uint8_t *meta = (uint8_t *)L.meta.p, *work = (uint8_t *)L.work.p;
+    HIPCHK(ctx, hipMemcpyAsync(meta + m_noff, noff.data(), 4 * noff.size(), hipMemcpyHostToDevice, st));
+    if (n_ref) HIPCHK(ctx, hipMemcpyAsync(meta + m_first, first.data(), 4 * (size_t)n_ref, hipMemcpyHostToDevice, st));
+    if (!nbytes.empty()) HIPCHK(ctx, hipMemcpyAsync(meta + m_names, nbytes.data(), nbytes.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemsetAsync(work + w_bad, 0xff, 8, st));
+    bam::TagsArgs a;
+    a.in = (const uint8_t *)L.in.p;
+    a.in_off = (const uint64_t *)meta;
+    a.n = (uint32_t)n;
+    a.names.bytes = meta + m_names;
+    a.names.off = (const uint32_t *)(meta + m_noff);
+    a.names.first = (const int32_t *)(meta + m_first);
+    a.names.n_ref = n_ref;
+    a.rs = meta + m_rs;
+    a.have = meta + m_have;
+    a.trim_l = (int32_t *)(meta + m_tl);
+    a.trim_r = (int32_t *)(meta + m_tr);
+    a.tid = (int32_t *)(meta + m_tid);
+    a.pos = (int64_t *)(meta + m_pos);
+    a.cnt = (uint32_t *)(work + w_cnt);
+    a.cig_at = (uint32_t *)(work + w_at);
+    a.blk_sums = (uint64_t *)work;
+    a.blk_base = (uint64_t *)(work + w_base);
+    a.total = (uint64_t *)(work + w_tot);
+    a.bad = (uint32_t *)(work + w_bad);
+    a.cig_off = (uint64_t *)(meta + m_coff);
+    a.cig = nullptr;
+    hipLaunchKernelGGL(bam::tags_count_kernel, dim3((unsigned)ntb), dim3(bam::TAG_BLOCK), 0, st, a);
+    HIPCHK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(bam::tags_scan_kernel, dim3(1), dim3(1024), 0, st, a, (uint32_t)ntb);
+    HIPCHK(ctx, hipGetLastError());
+    uint64_t tot_bad[2] = {0, 0};  // total | bad (low word)
+    HIPCHK(ctx, hipMemcpyAsync(tot_bad, a.total, 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    const uint32_t bad = (uint32_t)tot_bad[1];
+    if (bad != 0xffffffffu) return set_err(ctx, FADEHIP_E_INVALID, "record %u is malformed (its aux area is not whole fields)", bad);
+    const uint64_t total = tot_bad[0];
+    if (total > (uint64_t)cig_cap)
+        return set_err(ctx, FADEHIP_E_INVALID, "the am tags hold %llu CIGAR ops, cig holds %lld", (unsigned long long)total, (long long)cig_cap);
+    if ((rc = reserve(ctx, L.out, 4 * (size_t)total + 8))) return rc;
+    a.cig = (uint32_t *)L.out.p;
+    hipLaunchKernelGGL(bam::tags_write_kernel, dim3((unsigned)ntb), dim3(bam::TAG_BLOCK), 0, st, a);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(rs, a.rs, (size_t)n, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(have, a.have, (size_t)n, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(trim_left, a.trim_l, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(trim_right, a.trim_r, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(art_tid, a.tid, 4 * ns, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(art_pos, a.pos, 8 * ns, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(cig_off, a.cig_off, 8 * (ns + 1), hipMemcpyDeviceToHost, st));
+    if (total) HIPCHK(ctx, hipMemcpyAsync(cig, a.cig, 4 * (size_t)total, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    return 0;
 }
 
 // ------------------------------------------------------------------------------- level 2

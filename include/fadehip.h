@@ -152,8 +152,8 @@ int fadehip_sw_stats_batch(fadehip_ctx *ctx, const int32_t scoring[4] /* open, e
  * the file path runs under FADEHIP_BAM_CLIP; there rs and the lengths are the run's own results.  A record whose
  * block_size, l_read_name, n_cigar_op and l_seq do not fit its bytes: FADEHIP_E_INVALID, with its index in
  * fadehip_last_error.  Synchronous, and apart from the annotate slots as fadehip_sw_stats_batch is; fadehip_clip_batch,
- * fadehip_extract_batch and fadehip_eject_batch share one stream, one set of buffers and one lock per ctx: calls of any of
- * the three on one ctx, from whichever threads, run one after the other. */
+ * fadehip_extract_batch, fadehip_eject_batch and fadehip_tags_batch share one stream, one set of buffers and one lock per
+ * ctx: calls of any of them on one ctx, from whichever threads, run one after the other. */
 int fadehip_clip_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const int64_t *rec_off, const uint8_t *rs,
                        const int32_t *trim_left, const int32_t *trim_right, uint8_t *out, int64_t out_cap, int64_t *out_off);
 
@@ -185,6 +185,32 @@ int fadehip_extract_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, cons
  * with fadehip_clip_batch (see there). */
 int fadehip_eject_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const int64_t *rec_off, const uint8_t *rs,
                         int grouped, uint8_t *keep /* [n] out */);
+
+/* rs and am read back out of n BAM records (block_size first, as in a file), concatenated, rec_off holding n + 1 offsets:
+ * what `fade extract` and `fade out` parse from a file annotated earlier (remap.d:31-50, filter.d:24-25,58-59,190-196), in
+ * the shapes fadehip_clip_batch, fadehip_eject_batch and fadehip_extract_batch take, so that the calls compose without glue.
+ * The first aux field named rs and the first named am count (bam_aux_get's rule).
+ *   have[k] bit 0: the rs field is an integer (c C s S i I); rs[k] is then the low byte of its value (tag.to!ubyte), else
+ *     0 — an rs of any other type counts as absent.  Bit 1: the am field has type Z.
+ *   am is "left;right", cut at its first ';' (without one the whole string is the left side and the right side is empty).
+ *     have[k] bit 2 (left) / bit 3 (right): the side is well-formed, "name,pos,cigar" — name up to the first comma (may be
+ *     empty), pos what std.conv.to!long accepts (an optional sign, digits, nothing else, a value of 64 bits), cigar zero or
+ *     more pairs of a count (digits, below 2^28) and a letter of MIDNSHP=XB, and nothing behind it.
+ *   For a well-formed side s = 2k + side: art_tid[s] is the first contig of ref_names whose name equals name byte for
+ *     byte, or -1 (also for an empty name); art_pos[s] the position; cig[cig_off[s] .. cig_off[s + 1]) its ops,
+ *     BAM-encoded, as many as the text holds (FADEHIP_MAX_OPS does not apply); trim_left[k] / trim_right[k] the reference
+ *     bases the left / right side's ops take (FADEHIP_OP_CONSUMES_REF), at most INT32_MAX.
+ *   Any other side: art_tid -1, art_pos 0, no ops, trim 0.  A malformed am is never an error here; whether it matters is the
+ *     consumer's to decide.
+ * cig_off receives 2n + 1 offsets.  More ops than cig_cap: FADEHIP_E_INVALID, the number needed is in fadehip_last_error
+ * and nothing is written.  A record whose block_size, l_read_name, n_cigar_op and l_seq do not fit its bytes, or whose aux
+ * area is not whole fields: FADEHIP_E_INVALID, with the record's index in fadehip_last_error.  ref_names (n_ref C strings,
+ * the header's contigs) go up with every call.  Synchronous, on the stream and buffers it shares with fadehip_clip_batch
+ * (see there). */
+int fadehip_tags_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const int64_t *rec_off, int32_t n_ref,
+                       const char *const *ref_names, uint8_t *rs /* [n] */, uint8_t *have /* [n] */, int32_t *trim_left /* [n] */,
+                       int32_t *trim_right /* [n] */, int32_t *art_tid /* [2n] */, int64_t *art_pos /* [2n] */,
+                       int64_t *cig_off /* [2n + 1] */, uint32_t *cig, int64_t cig_cap);
 
 /* ------------------------------------------------------ Level 2: annotateTask over a batch -- */
 /* Upload the indexed FASTA once (what IndexedFastaFile + fetchSequence serve, analysis.d:63).
