@@ -25,7 +25,7 @@
 // Two geometries.  64: htslib's 0xff00-byte blocks, the block and its tables fill the CU's LDS, one workgroup per CU, the
 // role pipeline — the smallest output (9.8 GB/s of payload).  32: 0x7f00-byte blocks, 80 KB of LDS, two workgroups of eight
 // waves per CU, phase A on per-wave segments (19 GB/s); the output is 0.6 % larger on uniform-quality BAM payload than the
-// other geometry's and 1-2 % larger where qualities run.  fadehip.hip picks per call: 32 while the stream is mostly
+// other geometry's and 1-2 % larger where qualities run.  fadehip_bgzf.hip picks per call: 32 while the stream is mostly
 // incompressible bases (ratio above 0.45: there zlib -6 is 2 % behind either), 64 otherwise, so that the output stays
 // below zlib -6's in both regimes (tests/test_gpu_bgzf.py).
 #include "bgzf_deflate_common.hpp"  // what the two share, and the scan and pack kernels behind either

@@ -22,30 +22,10 @@
 
 #include "bgzf_deflate_common.hpp"  // claim_ticket
 #include "bgzf_huff.hpp"
+#include "fadehip_types.hpp"  // InflateBlock, InflateArgs
 
 namespace fadehip {
 namespace bgzf {
-
-struct InflateBlock {  // one per BGZF member, from the host's scan of the member headers and trailers
-    uint64_t src_off;  // first byte of the member's DEFLATE stream in `comp`
-    uint64_t dst_off;  // where its bytes go in `out` (running sum of ISIZE)
-    uint32_t src_len;  // bytes of DEFLATE stream
-    uint32_t isize;    // ISIZE of the trailer
-    uint32_t crc;      // CRC32 of the trailer
-    uint32_t pad;
-};
-static_assert(sizeof(InflateBlock) == 32, "InflateBlock layout");
-
-struct InflateArgs {
-    const uint8_t *comp;         // the members, with at least 1 KB of readable bytes behind the last one
-    const InflateBlock *blocks;
-    uint32_t n_blocks;
-    uint8_t *out;
-    const uint64_t *out_shift;   // device-side: bytes added to every dst_off (bytes carried over in front), or nullptr
-    uint32_t *status;            // [n_blocks] 0 = fine, INF_E_* otherwise
-    uint32_t *ticket;            // [0] ticket, [1] number of failed blocks
-    int check_crc;
-};
 
 enum : uint32_t {
     INF_E_BTYPE = 1, INF_E_STORED = 2, INF_E_HEADER = 3, INF_E_CODE = 4, INF_E_DIST = 5, INF_E_OVERRUN_OUT = 6,

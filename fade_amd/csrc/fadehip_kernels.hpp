@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/fadehip.h"
+#include "fadehip_types.hpp"  // NUM_CLASSES, NUM_LISTS, STAT_PARTS, ScoreTab, PlanOut
 
 namespace fadehip {
 
@@ -55,7 +56,6 @@ constexpr uint64_t CLASS_LUT = make_class_lut();
 constexpr uint64_t COMP_LUT = make_comp_lut();
 constexpr int PAD_CLASS = 6;
 constexpr int C64_STRIDE = 16;  // the three 64-bit batch counters sit 128 bytes apart (one L2 line each)
-constexpr int STAT_PARTS = 8;  // the stats.d counters are kept as this many partial sums (stats[8 * part + k])
 
 __device__ __forceinline__ uint32_t lut4(uint64_t lut, uint32_t code) { return (uint32_t)(lut >> (4 * code)) & 15u; }
 // base b of a packed array: byte b>>1, even base in the high nibble (BAM convention).
@@ -82,7 +82,6 @@ struct Fwd {            // forward pass result per work item
     int32_t score, end_q, end_r, pad;
 };
 
-constexpr int NUM_CLASSES = 10;
 __host__ __device__ constexpr int class_rows(int c) {
     constexpr int t[NUM_CLASSES] = {4, 6, 8, 10, 12, 14, 16, 20, 24, 32};
     return t[c];
@@ -92,9 +91,7 @@ __host__ __device__ inline int class_of_len(int lq) {
         if (16 * class_rows(c) >= lq) return c;
     return -1;
 }
-// Work lists: one per row class of the wave kernels plus one for queries longer than 16 * 32 = 512 bases, which
-// take sw_long_kernel (a thread per alignment; rare in short-read libraries, e.g. merged pairs).
-constexpr int LONG_LIST = NUM_CLASSES, NUM_LISTS = NUM_CLASSES + 1;
+constexpr int LONG_LIST = NUM_CLASSES;  // the last of the NUM_LISTS work lists (fadehip_types.hpp): what no row class takes
 constexpr int MAX_LONG_QUERY = 1 << 15;
 // The wave kernels stage a group's window in LDS 2,048 columns at a time (CH_COLS; 2 bytes per column): a window of any
 // length streams through.  What bounds it is the end-cell key: the score pass keeps the sweep step of a row pair's best
@@ -107,11 +104,6 @@ __host__ __device__ inline int list_of_len(int lq, int64_t lr = 0) {
     return lq <= MAX_LONG_QUERY ? LONG_LIST : -1;
 }
 
-struct ScoreTab {
-    uint32_t prof[8];  // prof[q class] : 8 x 4-bit entries (W + open) indexed by ref class*4
-    int32_t open, ext, match, mismatch;
-    uint32_t rules;    // FADEHIP_RULE_* (include/fadehip.h): the assumptions about libparasail that could not be checked
-};
 __host__ __device__ inline bool rule(uint32_t rules, uint32_t bit) { return (rules & bit) != 0; }
 
 // ---------------------------------------------------------------- ASCII -> packed 4-bit
@@ -2240,12 +2232,6 @@ __global__ void traceback_kernel(TbArgs a) {
     const uint32_t r = traceback_one(a, (int)(blockIdx.x * blockDim.x + threadIdx.x));
     if (a.stats) add_artifact_stats(a.stats, r, blockIdx.x);
 }
-
-// ---------------------------------------------------------------- run totals kept on the device
-struct PlanOut {            // in the slot's counter block, read by the host after the run
-    unsigned long long cand_total;   // candidates traced by pass 2 (all classes)
-    unsigned long long rerun_total;  // candidates traced again because their path left the traced steps
-};
 
 // ---------------------------------------------------------------- patch list of an early bulk copy
 // When the alignment array leaves for the host beside pass 2 (enqueue_run's early order), the entries pass 2 wrote follow in

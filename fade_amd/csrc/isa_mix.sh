@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage: isa_mix.sh <mangled-kernel-prefix> [rows]  — instruction mix of the kernel's innermost (deepest) loop
-S=/root/repo/fade_amd/csrc/build/fadehip-hip-amdgcn-amd-amdhsa-gfx950.s
-awk -v k="^$1" '$0 ~ k && /:/ && !p {p=1} p {print} p && /s_endpgm/ {exit}' $S > /tmp/kern.s
+# (one listing per translation unit: the kernel is in one of them)
+cat "$(dirname "$0")"/build/*-gfx950.s | awk -v k="^$1" '$0 ~ k && /:/ && !p {p=1} p {print} p && /s_endpgm/ {exit}' > /tmp/kern.s
 D=$(grep -o "Inner Loop Header: Depth=[0-9]*" /tmp/kern.s | sort -t= -k2 -n | tail -1)
 A=$(grep -n "$D" /tmp/kern.s | tail -1 | cut -d: -f1)
 [ -z "$A" ] && { echo "loop not found"; exit 1; }

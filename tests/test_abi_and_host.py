@@ -246,8 +246,11 @@ def test_ref_consuming_op_set_has_one_definition():
     hdr = open(os.path.join(ROOT, "include", "fadehip.h")).read()
     mask = int(re.search(r"#define FADEHIP_REF_CONSUMING_OPS (0x[0-9A-Fa-f]+)u", hdr).group(1), 16)
     assert tuple(k for k in range(16) if (mask >> k) & 1) == _lib.REF_CONSUMING_OPS == (0, 2, 3, 7, 8)
-    for path in ("fade_amd/csrc/fadehip_kernels.hpp", "fade_amd/csrc/fadehip.hip"):
-        assert "op == 0 || op == 2 || op == 3" not in open(os.path.join(ROOT, path)).read(), path
+    csrc = os.path.join(ROOT, "fade_amd", "csrc")
+    paths = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".hpp")))
+    assert {"fadehip_kernels.hpp", "fadehip.hip", "fadehip_ctx.hip", "fadehip_bgzf.hip", "fadehip_bam.hip"} <= set(paths)
+    for path in paths:
+        assert "op == 0 || op == 2 || op == 3" not in open(os.path.join(csrc, path)).read(), path
 
 
 def test_header_is_plain_c_and_links_from_c(tmp_path):

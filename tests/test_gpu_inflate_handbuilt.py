@@ -106,7 +106,7 @@ def test_the_three_inflaters_agree_through_the_file_path(tmp_path):
     genome = "".join("ACGT"[k] for k in rng.integers(0, 4, 20000))
     fa.write_text(">chr1\n" + "\n".join(genome[o:o + 70] for o in range(0, len(genome), 70)) + "\n")
     host_message = b"does not inflate to its ISIZE / CRC32"  # hts_lite.hpp's reader and fade_main.cpp's pool
-    envs = {"device": ({"FADE_BAM_INFLATE": "device"}, b"members failed)"),  # fadehip.hip: "bam stream: call .., member ..: <INF_E_*> (.. members failed)"
+    envs = {"device": ({"FADE_BAM_INFLATE": "device"}, b"members failed)"),  # fadehip_bam.hip: "bam stream: call .., member ..: <INF_E_*> (.. members failed)"
             "host pool": ({"FADE_BAM_INFLATE": "host"}, host_message),
             "host pipeline": ({"FADE_BAM_DEVICE": "0"}, host_message)}
 
