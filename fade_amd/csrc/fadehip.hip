@@ -521,13 +521,16 @@ int run_class_single(fadehip_ctx *ctx, Slot &s, hipStream_t st, const ClassRun &
 }
 
 // Long list on the wave kernel with one alignment per wavefront (sw_forward64_kernel): reads of up to 4,096 bases, windows
-// of up to LONG_WAVE_MAX_WINDOW columns, under the default end-cell and gap-tie rules (the kernel's flags are those rules').
+// of up to LONG_WAVE_MAX_WINDOW columns, under the default Appendix A.3 / A.4 rules only: the kernel picks its end cell by
+// END_MIN_REF_THEN_QUERY, opens gaps by GAP_TIE_EXTENDS and writes trace bit 4 as "F < T", which traceback_path reads as
+// "E < T" when HDIR_DIAG_F_E is off (run_long keeps such lists away from here).
 // n_bound / max_lq / max_lr are upper bounds, the live count stays on the device.
 constexpr int LONG_WAVE_MAX_QUERY = 4096, LONG_WAVE_MAX_WINDOW = 65000;
 int run_long_wave(fadehip_ctx *ctx, Slot &s, hipStream_t st, const ClassRun &c, int max_lq) {
     const int n_items = c.n_bound, max_lr = c.max_lr;
     // rows per lane: the smallest of 12 / 16 / 24 / 32 / 48 / 64 that holds the list's longest read (64: 256 VGPRs + 220 AGPRs, one wave per SIMD)
     const int R = max_lq <= 768 ? 12 : max_lq <= 1024 ? 16 : max_lq <= 1536 ? 24 : max_lq <= 2048 ? 32 : max_lq <= 3072 ? 48 : 64;
+    if (ctx->debug) fprintf(stderr, "[fadehip] long list of %d alignments (longest read %d, widest window %d): wave64 R=%d\n", n_items, max_lq, max_lr, R);
     const int n_blocks = (max_lr + 63 + 3) / 4;
     const uint64_t quad_stride = (uint64_t)n_blocks * (R / 2) * 64;  // dwords of trace per alignment
     const size_t lds = (size_t)(((n_blocks * 4) + 15) / 16) * 16;
@@ -563,12 +566,14 @@ int run_long_wave(fadehip_ctx *ctx, Slot &s, hipStream_t st, const ClassRun &c, 
 
 // Queries longer than 512 bases (or windows beyond the wave kernels' LDS): what the one-alignment-per-wave kernel holds
 // goes there; sw_long_kernel (thread per alignment, full trace) + the common traceback keep the rest (longer reads, wider
-// windows, the non-default end-cell / gap-tie rules: FADEHIP_LONG_THREAD=1 sends everything to it, for A/B runs).
+// windows, and any list under a non-default end-cell, gap-tie or traceback-direction rule: sw_long_kernel reads all three
+// switches.  FADEHIP_LONG_THREAD=1 sends everything to it, for A/B runs).  FADEHIP_DEBUG names the runner of each list.
 int run_long(fadehip_ctx *ctx, Slot &s, hipStream_t st, const ClassRun &c, int max_lq) {
     const int n_items = c.n_bound, max_lr = c.max_lr;
-    const uint32_t need_rules = FADEHIP_RULE_END_MIN_REF_THEN_QUERY | FADEHIP_RULE_GAP_TIE_EXTENDS;
+    const uint32_t need_rules = FADEHIP_RULE_END_MIN_REF_THEN_QUERY | FADEHIP_RULE_GAP_TIE_EXTENDS | FADEHIP_RULE_HDIR_DIAG_F_E;
     if (max_lq <= LONG_WAVE_MAX_QUERY && max_lr <= LONG_WAVE_MAX_WINDOW && (ctx->sc.rules & need_rules) == need_rules && !getenv("FADEHIP_LONG_THREAD"))
         return run_long_wave(ctx, s, st, c, max_lq);
+    if (ctx->debug) fprintf(stderr, "[fadehip] long list of %d alignments (longest read %d, widest window %d): thread\n", n_items, max_lq, max_lr);
     const int lhalf = (max_lr + 1) / 2;
     const int64_t per_item = (int64_t)max_lq * lhalf + 8 * (int64_t)max_lr;
     const int64_t chunk = std::min<int64_t>(n_items, c.budget / std::max<int64_t>(per_item, 1));

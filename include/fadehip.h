@@ -87,7 +87,9 @@ typedef struct {
  * not be checked against its source in this environment (DESIGN.md "parity unpinned").  Each
  * assumption is a switch with the same meaning and bit as oracle/fade_oracle.h's FO_RULE_*: should a maintainer find
  * that parasail does the opposite, it is a parameter, not a kernel edit.  Non-default settings run a slower variant of
- * the traced re-computation; the default costs nothing. */
+ * the traced re-computation; the default costs nothing.  With END_MIN_REF_THEN_QUERY, HDIR_DIAG_F_E or GAP_TIE_EXTENDS
+ * off, reads beyond 512 bases and windows beyond 32,000 columns all take the thread-per-alignment kernel (the
+ * one-alignment-per-wavefront kernel carries the default of those three only). */
 enum {
     FADEHIP_RULE_END_MIN_REF_THEN_QUERY = 1u << 0, /* A.3 end cell: max H, ties -> smallest ref index, then smallest query index (off: first in row-major order) */
     FADEHIP_RULE_HDIR_DIAG_F_E = 1u << 1,          /* A.4 traceback priority DIAG > F (query-only) > E (ref-only)  (off: DIAG > E > F) */

@@ -104,6 +104,35 @@ def make_pairs(rng, n, lq_range=(20, 260), lr_range=(30, 900), kinds=("random", 
     return qs, rs
 
 
+def embed_seed_pair(rng, q_s, r_s, lq, col=None, lr=None, n_r=None):
+    """A short pair (q_s, r_s) inside a long one that aligns end to end: q = L + q_s + R with L, R random A,C,G,T and
+    len(q) == lq exactly, r = rand(30) + L + r_s + R + rand(30).  The seed's tie (between the gap directions, or between
+    opening and extending) then sits in the middle of a long path.  col puts r_s at that window column instead (the flank in
+    front of L grows), lr gives the window that many columns (the flank behind R grows), n_r sets len(R)."""
+    if n_r is None:
+        n_r = (lq - len(q_s) + 1) // 2
+    n_l = lq - len(q_s) - n_r
+    assert n_l >= 0 and n_r >= 0, (lq, len(q_s))
+    L, R = rand_seq(rng, n_l), rand_seq(rng, n_r)
+    lead = 30 if col is None else col - n_l
+    tail = 30 if lr is None else lr - (lead + n_l + len(r_s) + n_r)
+    assert lead >= 0 and tail >= 0, (lq, col, lr, lead, tail)
+    q = np.concatenate([L, q_s, R])
+    r = np.concatenate([rand_seq(rng, lead), L, r_s, R, rand_seq(rng, tail)])
+    return np.ascontiguousarray(q), np.ascontiguousarray(r)
+
+
+def end_tie_pair(rng, L, gap, lead=20, tail=20):
+    """Two end cells of the same score for Appendix A.3's rule to choose between: q = A + B with |A| = |B| = L and
+    r = rand(lead) + B + rand(gap) + A + rand(tail), so that row 2L - 1 scores match * L at column lead + L - 1 and row L - 1
+    scores it at column lead + 2L + gap - 1.  A chance extension of either copy breaks the tie: the caller keeps the pair
+    only when the oracle's best score is match * L exactly."""
+    A, B = rand_seq(rng, L), rand_seq(rng, L)
+    q = np.concatenate([A, B])
+    r = np.concatenate([rand_seq(rng, lead), B, rand_seq(rng, gap), A, rand_seq(rng, tail)])
+    return np.ascontiguousarray(q), np.ascontiguousarray(r)
+
+
 def concat(seqs):
     off = np.zeros(len(seqs) + 1, dtype=np.int64)
     np.cumsum([len(s) for s in seqs], out=off[1:])

@@ -1,6 +1,7 @@
 """One-off differential run over RANDOM COMBINATIONS of the rule switches (fadehip_params.rules / FO_RULE_*): the suite
 (tests/test_gpu_rules.py) checks each switch alone and one combination; here every seed draws a 7-bit mask and compares
 level 1 (score, end, begin, CIGAR) and level 2 (rs, am) with the oracle under the same mask.
+Reads beyond 512 bases and windows beyond 900 columns under each switch: tests/test_gpu_rules_long.py.
 GPU box: python tools/rules_fuzz.py [n_seeds]"""
 import os
 import sys
