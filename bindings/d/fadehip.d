@@ -186,7 +186,7 @@ struct fadehip_bam_config {
     int floor_len;               /// --min-length
     int window;                  /// -w
     int n_ref;                   /// contigs of the BAM header
-    int flags;                   /// 1 (FADEHIP_BAM_STORED): uncompressed BGZF out; 2 (FADEHIP_BAM_NO_OUTPUT): back makes no BGZF (measurement); 4 (FADEHIP_BAM_CLIP): hard-clip the artifact calls; 8 (FADEHIP_BAM_EXTRACT): every call also leaves `fade extract`'s records; 16 (FADEHIP_BAM_EJECT): artifact calls are not written; 32 (FADEHIP_BAM_EJECT_GROUPS): nor the records of their name group
+    int flags;                   /// 1 (FADEHIP_BAM_STORED): uncompressed BGZF out; 2 (FADEHIP_BAM_NO_OUTPUT): back makes no BGZF (measurement); 4 (FADEHIP_BAM_CLIP): hard-clip the artifact calls; 8 (FADEHIP_BAM_EXTRACT): every call also leaves `fade extract`'s records; 16 (FADEHIP_BAM_EJECT): artifact calls are not written; 32 (FADEHIP_BAM_EJECT_GROUPS): nor the records of their name group; 64 (FADEHIP_BAM_FROM_TAGS): rs and am come out of the records (annotated earlier), nothing is aligned
     const(char*)* ref_names;     /// [n_ref]
     uint first_record;           /// payload bytes of the first member passed that precede the first record
     uint tail_trim;              /// payload bytes at the end of the last member that belong to the next reader
@@ -197,6 +197,7 @@ enum FADEHIP_BAM_NO_OUTPUT = 2;  /// ... back releases the annotated records wit
 enum FADEHIP_BAM_EXTRACT = 8;    /// ... every call also builds `fade extract`'s records of its artifact calls (`fade annotate --extract`): fadehip_bam_back_extract
 enum FADEHIP_BAM_EJECT = 16;     /// ... artifact calls are not written (`fade annotate --eject`, input not name-sorted), by this run's rs; not with FADEHIP_BAM_CLIP
 enum FADEHIP_BAM_EJECT_GROUPS = 32;  /// ... name-sorted input: nor any record of an artifact call's name group (implies FADEHIP_BAM_EJECT); a group never lies across two calls
+enum FADEHIP_BAM_FROM_TAGS = 64;  /// ... the records were annotated earlier: rs and am are read back out of them on the device and CLIP / EJECT / EJECT_GROUPS / EXTRACT are `fade out -c` / `fade out` / `fade extract`; no genome, floor_len and window ignored; a needed am side that is not well-formed fails the call at its back (FADEHIP_E_INVALID, the record's index in fadehip_last_error)
 enum FADEHIP_BAM_CLIP = 4;       /// ... artifact calls leave hard-clipped (`fade annotate -c`), by this run's rs and alignments
 int fadehip_bam_open(fadehip_ctx* ctx, const(fadehip_bam_config)* cfg, fadehip_bam_stream** out_);
 int fadehip_bam_prepare(fadehip_bam_stream* st, size_t call_bytes);

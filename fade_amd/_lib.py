@@ -35,7 +35,7 @@ EXPORTS = [
     "fadehip_bam_prepare", "fadehip_sw_stats_batch", "fadehip_clip_batch", "fadehip_extract_batch", "fadehip_bam_back_extract",
     "fadehip_eject_batch", "fadehip_bam_ejected", "fadehip_genome_upload_fasta", "fadehip_genome_fetch", "fadehip_tags_batch",
 ]
-BAM_STORED, BAM_NO_OUTPUT, BAM_CLIP, BAM_EXTRACT, BAM_EJECT, BAM_EJECT_GROUPS = 1, 2, 4, 8, 16, 32  # fadehip_bam_config.flags
+BAM_STORED, BAM_NO_OUTPUT, BAM_CLIP, BAM_EXTRACT, BAM_EJECT, BAM_EJECT_GROUPS, BAM_FROM_TAGS = 1, 2, 4, 8, 16, 32, 64  # fadehip_bam_config.flags
 BGZF_BLOCK = 0xff00
 BGZF_LANES = 2
 

@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import ALN_DTYPE, SW_DTYPE, SW_STATS_DTYPE, FadeHipError
-from ._lib import BAM_STORED, BAM_NO_OUTPUT, BAM_CLIP, BAM_EXTRACT, BAM_EJECT, BAM_EJECT_GROUPS  # noqa: F401  (fadehip_bam_config.flags)
+from ._lib import BAM_STORED, BAM_NO_OUTPUT, BAM_CLIP, BAM_EXTRACT, BAM_EJECT, BAM_EJECT_GROUPS, BAM_FROM_TAGS  # noqa: F401  (fadehip_bam_config.flags)
 
 CIGAR_OPS = "MIDNSHP=X"
 NT16 = "=ACMGRSVTWYHKDBN"
@@ -460,14 +460,18 @@ class Context:
         self.bgzf_deflate_submit(lane, data)
         return self.bgzf_deflate_wait(lane)
 
-    def bam_stream(self, ref_names, floor_len=5, window=300, first_record=0, stored=False, tail_trim=0, no_output=False, clip=False, extract=False, eject=None):
+    def bam_stream(self, ref_names, floor_len=5, window=300, first_record=0, stored=False, tail_trim=0, no_output=False, clip=False, extract=False, eject=None, from_tags=False):
         """The file path on the device (fadehip_bam_*): BGZF members of a BAM's records in, BGZF members of the annotated
         records out.  ref_names: the BAM header's contigs (the genome must be uploaded).  clip: records called artifacts leave
         hard-clipped (`fade annotate -c`).  extract: every call also builds `fade extract`'s records of its artifact calls
         (`fade annotate --extract`); BamStream.back_extract() fetches them after each back().  eject: "records" — artifact
         calls are not written; "groups" — nor any record of their name group, on name-sorted input (`fade annotate --eject`);
-        BamStream.ejected() counts them.  Not with clip."""
-        return BamStream(self, ref_names, floor_len, window, first_record, stored, tail_trim, no_output, clip, extract, eject)
+        BamStream.ejected() counts them.  Not with clip.  from_tags: the records were annotated earlier and rs / am come out
+        of the records themselves (FADEHIP_BAM_FROM_TAGS): no genome is needed, floor_len and window are ignored, and clip,
+        eject and extract are `fade out -c`, plain `fade out` and `fade extract` — a record without an integer rs passes
+        clip, is dropped by eject="records" and counts as clean under eject="groups"; a needed am side that is not
+        well-formed fails the call at its back()."""
+        return BamStream(self, ref_names, floor_len, window, first_record, stored, tail_trim, no_output, clip, extract, eject, from_tags)
 
     def bgzf_inflate(self, members, out_cap=None):
         """Whole BGZF members (bytes / uint8 array) -> their payloads, inflated on the device (CRC32 and ISIZE checked)."""
@@ -601,14 +605,14 @@ def format_tags(batch, contig_names, rs, aln):
 
 
 class BamStream:
-    def __init__(self, ctx, ref_names, floor_len, window, first_record, stored=False, tail_trim=0, no_output=False, clip=False, extract=False, eject=None):
+    def __init__(self, ctx, ref_names, floor_len, window, first_record, stored=False, tail_trim=0, no_output=False, clip=False, extract=False, eject=None, from_tags=False):
         self._ctx, self._L = ctx, ctx._L
         if eject not in (None, False, "records", "groups"):
             raise ValueError('eject is None, "records" or "groups"')
         ej = BAM_EJECT | BAM_EJECT_GROUPS if eject == "groups" else BAM_EJECT if eject == "records" else 0
         names = [n.encode() if isinstance(n, str) else bytes(n) for n in ref_names]
         arr = (C.c_char_p * max(len(names), 1))(*names)
-        cfg = _lib.BamConfig(floor_len, window, len(names), (_lib.BAM_STORED if stored else 0) | (_lib.BAM_NO_OUTPUT if no_output else 0) | (_lib.BAM_CLIP if clip else 0) | (_lib.BAM_EXTRACT if extract else 0) | ej, arr, first_record, tail_trim)
+        cfg = _lib.BamConfig(floor_len, window, len(names), (_lib.BAM_STORED if stored else 0) | (_lib.BAM_NO_OUTPUT if no_output else 0) | (_lib.BAM_CLIP if clip else 0) | (_lib.BAM_EXTRACT if extract else 0) | (BAM_FROM_TAGS if from_tags else 0) | ej, arr, first_record, tail_trim)
         h = C.c_void_p()
         ctx._chk(self._L.fadehip_bam_open(ctx._h, C.byref(cfg), C.byref(h)))
         self._h = h

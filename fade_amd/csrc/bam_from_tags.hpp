@@ -1,0 +1,290 @@
+// bam_from_tags.hpp — FADEHIP_BAM_FROM_TAGS: the file path over records that were annotated EARLIER (by this library, by
+// the reference, or by a tool in between), so that `fade out`, `fade out -c` and `fade extract` run on the device without an
+// aligner in the middle.  One stage kernel stands where packing, gate, score pass and pass 2 stand in an annotate run: it
+// reads rs and am back out of every record (read_tags / am_side of bam_device.hpp, the functions of fadehip_tags_batch) and
+// leaves what the kernels behind it need — the record's size as it leaves, the byte the eject kernels decide by, the trims
+// clip_plan takes, the sides extract_write builds records from — and sums stats.d:45-54 on the way.  The eject kernels, the
+// block scans and the device functions of bam_device.hpp are used as they are; the kernels here are of their own, and a run
+// without the flag launches none of them.
+//
+//   CLIP (filter.d:186-207)     a record with an integer rs and rs & 6 is hard-clipped by the reference bases of its am
+//                               sides' CIGARs; only that third field of a needed side has to parse (filter.d:24-25)
+//   EJECT (filter.d:247-265)    written only with an integer rs and !(rs & 6): a record WITHOUT rs gets a byte with an
+//                               artifact bit set for bam_eject_apply_kernel (the counters take the true value)
+//   EJECT_GROUPS (:219-246)     a record without rs counts as clean; its group goes when another record of it is an artifact
+//   EXTRACT (remap.d:29-85)     integer rs, rs & 6 and am:Z: one record per set bit from the side's contig, position and ops
+#pragma once
+#include "bam_device.hpp"
+
+namespace fadehip {
+namespace bam {
+
+enum : uint32_t { FT_CLIP = 1, FT_EJECT_RECORDS = 2, FT_EXTRACT = 4 };
+enum : uint32_t { FT_BAD_CLIP = 1, FT_BAD_SIDE = 2, FT_BAD_OPS = 3 };
+
+// what the stage adds to the counts that cross to the host with a call's ChunkCounts
+struct StageCounts {
+    ChunkCounts ops;               // out_bytes: the ops of the call's extract sides (the total of bam_tag_scan_kernel)
+    unsigned long long stats[8];   // stats.d:45-54 over the call's records
+    unsigned long long bad;        // 0: none; else ((0xffffffff - record) << 8) | FT_BAD_*: the first record that fails the call
+    unsigned long long pad;
+};
+
+struct FromTagsArgs {
+    const uint8_t *u;
+    const uint32_t *rec_off;
+    const ChunkCounts *counts_in;  // n_records
+    uint32_t r1_cap, mode;         // FT_*
+    const uint32_t *info;          // INFO_BAD: the eject kernels took the record out
+    RefNames names;
+    uint8_t *rsb;                  // [n] rs of an integer rs field, else 0 (FT_EJECT_RECORDS: else 2)
+    uint32_t *trim_l, *trim_r;     // [n] FT_CLIP: reference bases of the sides' CIGARs
+    uint32_t *out_size;            // [n] bytes of the record as it leaves
+    uint64_t *blk_sums, *blk_base; // [blocks of TAG_BLOCK records]
+    // FT_EXTRACT
+    uint32_t *x_size;              // [n] bytes of the record's extract records
+    uint64_t *x_blk_sums, *x_blk_base;
+    ChunkCounts *x_counts;         // n_records: extract records of the call
+    int32_t *tid;                  // [2n] per side
+    int64_t *pos;                  // [2n]
+    uint32_t *cnt, *cig_at;        // [2n] ops of a side; where its CIGAR text starts, relative to the record
+    uint64_t *ops_blk_sums, *ops_blk_base;
+    uint64_t *ops_at;              // [n] where the record's ops start in `ops` (left side first)
+    uint32_t *ops;
+    StageCounts *sc;
+    uint8_t *o, *xo;               // the record stream, the extract stream
+};
+
+// filter.d:24-25 / 58-59: all `fade out -c` reads of an am side is its third field — what stands behind the second comma,
+// a CIGAR as am_cigar takes it.  The position between the commas is never looked at (am_side would refuse a side whose
+// position is junk, and cannot say which of the two was wrong).  false: no two commas, or no CIGAR behind them.
+__device__ __forceinline__ bool am_side_trim(const RecHdr &r, uint32_t at, uint32_t n, uint32_t *trim) {
+    const uint8_t *s = r.p + at;
+    uint32_t c = 0, commas = 0;
+    for (; c < n; c++)
+        if (s[c] == ',' && ++commas == 2u) break;
+    if (c >= n) return false;
+    uint32_t nops;
+    uint64_t ref;
+    if (!am_cigar(s + c + 1u, n - c - 1u, &nops, &ref)) return false;
+    *trim = (uint32_t)min(ref, (uint64_t)0x7fffffffu);
+    return true;
+}
+
+// Thread per record, as bam_tag_size_kernel: the stage.  Four block sums in one pass — the seven Stats.parse counters of the
+// records with an integer rs packed nine bits each (a block holds 256 records), the bytes that leave, the extract bytes with
+// the number of extract records above bit 40, the extract ops with the number of records above bit 48.
+__global__ __launch_bounds__(TAG_BLOCK) void bam_tags_stage_kernel(FromTagsArgs a) {
+    __shared__ unsigned long long red[TAG_BLOCK / 64][4];
+    const uint32_t r1 = min(a.r1_cap, a.counts_in->n_records);
+    const uint32_t i = blockIdx.x * TAG_BLOCK + threadIdx.x;
+    unsigned long long v[4] = {0ull, 0ull, 0ull, 0ull};
+    if (i < r1) {
+        const RecHdr r = rec_header(a.u + a.rec_off[i]);
+        const TagsRead t = read_tags(r);
+        const bool has = (t.have & 1) != 0;
+        const uint32_t rs = has ? t.rs : 0u;
+        if (has) {  // stats.d:45-54: clipped, sup, art_sup, art, art_mate, aln_l, aln_r
+            const unsigned long long sc = rs & 1u, al = (rs >> 1) & 1u, ar = (rs >> 2) & 1u, ml = (rs >> 3) & 1u, mr = (rs >> 4) & 1u, su = (rs >> 5) & 1u;
+            v[0] = sc | (su << 9) | (((al | ar) & su) << 18) | ((al | ar) << 27) | (((al & ml) | (ar & mr)) << 36) | (al << 45) | (ar << 54);
+        }
+        uint32_t semi = 0;
+        if ((rs & 6u) && (a.mode & (FT_CLIP | FT_EXTRACT)))
+            while (semi < t.am_len && r.p[t.am_off + semi] != ';') semi++;
+        const uint32_t right = min(semi + 1u, t.am_len);  // (without a ';' the right side is empty)
+        const uint32_t s_at[2] = {t.am_off, t.am_off + right}, s_len[2] = {semi, t.am_len - right};
+        unsigned long long bad = 0;
+        uint32_t sz = r.end;
+        if (a.mode & FT_CLIP) {
+            uint32_t trim[2] = {0u, 0u};
+            for (uint32_t side = 0; side < 2u; side++)
+                if ((rs & (2u << side)) && !((t.have & 2) && am_side_trim(r, s_at[side], s_len[side], &trim[side]))) bad = FT_BAD_CLIP;
+            if ((rs & 6u) && !bad) {
+                const ClipPlan c = clip_plan(r, rs, trim[0], trim[1]);
+                if (c.mode == 2u) sz = c.pre;  // (a reset record has no aux area)
+                else if (c.mode == 1u) sz = c.pre + (r.end - r.aux_off);
+            }
+            a.trim_l[i] = trim[0];
+            a.trim_r[i] = trim[1];
+        }
+        if (a.mode & FT_EXTRACT) {
+            unsigned long long xs = 0;
+            for (uint32_t side = 0; side < 2u; side++) {
+                uint32_t nops = 0;
+                if ((rs & (2u << side)) && (t.have & 2)) {
+                    const AmSide s = am_side(r, a.names, s_at[side], s_len[side]);
+                    if (!s.ok) { if (!bad) bad = FT_BAD_SIDE; }
+                    else if (s.nops > 65535u) { if (!bad) bad = FT_BAD_OPS; }
+                    else {
+                        nops = s.nops;
+                        a.tid[2u * i + side] = s.tid;
+                        a.pos[2u * i + side] = s.pos;
+                        a.cig_at[2u * i + side] = s.cig_at;
+                        xs += (unsigned long long)extract_size(r, nops) | (1ull << 40);
+                    }
+                }
+                a.cnt[2u * i + side] = nops;
+                v[3] += nops;
+            }
+            a.x_size[i] = (uint32_t)xs;
+            v[2] = xs;
+        }
+        if (bad) atomicMax(&a.sc->bad, ((unsigned long long)(0xffffffffu - i) << 8) | bad);
+        a.rsb[i] = (uint8_t)(((a.mode & FT_EJECT_RECORDS) && !has) ? 2u : rs);
+        a.out_size[i] = sz;
+        v[1] = sz;
+        v[3] += 1ull << 48;
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1)
+        for (int k = 0; k < 4; k++) v[k] += (unsigned long long)__shfl_xor((long long)v[k], m, 64);
+    if ((threadIdx.x & 63) == 0)
+        for (int k = 0; k < 4; k++) red[threadIdx.x >> 6][k] = v[k];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long t[4] = {0ull, 0ull, 0ull, 0ull};
+        for (int w = 0; w < TAG_BLOCK / 64; w++)
+            for (int k = 0; k < 4; k++) t[k] += red[w][k];
+        a.blk_sums[blockIdx.x] = t[1];
+        if (a.mode & FT_EXTRACT) {
+            a.x_blk_sums[blockIdx.x] = t[2] & ((1ull << 40) - 1ull);
+            if (t[2] >> 40) atomicAdd(&a.x_counts->n_records, (uint32_t)(t[2] >> 40));
+            a.ops_blk_sums[blockIdx.x] = t[3] & ((1ull << 48) - 1ull);
+        }
+        if (t[3] >> 48) atomicAdd(&a.sc->stats[0], t[3] >> 48);
+        for (int k = 0; k < 7; k++) {
+            const unsigned long long c = (t[0] >> (9 * k)) & 511ull;
+            if (c) atomicAdd(&a.sc->stats[k + 1], c);
+        }
+    }
+}
+
+// FT_EXTRACT, thread per record behind the scan of the ops' block sums: where the record's ops start, and the ops themselves,
+// parsed again from the text the stage found well-formed (as tags_write_kernel does)
+__global__ __launch_bounds__(TAG_BLOCK) void bam_tags_ops_kernel(FromTagsArgs a) {
+    const uint32_t r1 = min(a.r1_cap, a.counts_in->n_records);
+    const uint32_t i = blockIdx.x * TAG_BLOCK + threadIdx.x;
+    uint32_t nl = 0, nr = 0;
+    if (i < r1) {
+        nl = a.cnt[2u * i];
+        nr = a.cnt[2u * i + 1u];
+    }
+    uint64_t tot;
+    const uint64_t at = a.ops_blk_base[blockIdx.x] + block_scan_256((uint64_t)nl + nr, &tot);
+    if (i >= r1) return;
+    a.ops_at[i] = at;
+    const uint8_t *p = a.u + a.rec_off[i];
+    for (uint32_t side = 0; side < 2u; side++) {
+        const uint32_t nops = side ? nr : nl;
+        if (!nops) continue;
+        const uint8_t *s = p + a.cig_at[2u * i + side];
+        uint32_t *dst = a.ops + at + (side ? nl : 0u);
+        uint32_t num = 0, k = 0;
+        for (uint32_t j = 0; k < nops; j++) {
+            const uint32_t c = s[j];
+            if (c - '0' < 10u) { num = num * 10u + (c - '0'); continue; }
+            dst[k++] = (num << 4) | cigar_op_of(c);
+            num = 0;
+        }
+    }
+}
+
+// FT_EXTRACT: the extract records, a block per TAG_BLOCK records as bam_extract_write_kernel — the records that leave some
+// gathered into a list by one scan, the block's sixteen groups of sixteen lanes taking them side by side
+__global__ __launch_bounds__(TAG_BLOCK) void bam_tags_extract_write_kernel(FromTagsArgs a) {
+    __shared__ uint64_t wave_sum[TAG_BLOCK / 64 + 1];
+    __shared__ uint64_t l_off[TAG_BLOCK];
+    __shared__ uint32_t l_rec[TAG_BLOCK];
+    const uint32_t r1 = min(a.r1_cap, a.counts_in->n_records);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t i0 = blockIdx.x * TAG_BLOCK, i = i0 + threadIdx.x;
+    const uint64_t sz = i < r1 ? (uint64_t)a.x_size[i] : 0ull;
+    const uint64_t v = sz | (sz ? 1ull << 40 : 0ull);
+    uint64_t inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t o = (uint64_t)__shfl_up((long long)inc, d, 64);
+        if (lane >= d) inc += o;
+    }
+    if (lane == 63) wave_sum[wave + 1] = inc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        wave_sum[0] = 0;
+        for (int w = 1; w <= TAG_BLOCK / 64; w++) wave_sum[w] += wave_sum[w - 1];
+    }
+    __syncthreads();
+    if (sz) {
+        const uint64_t ex = wave_sum[wave] + inc - v;
+        l_rec[ex >> 40] = threadIdx.x;
+        l_off[ex >> 40] = a.x_blk_base[blockIdx.x] + (ex & ((1ull << 40) - 1ull));
+    }
+    __syncthreads();
+    const uint32_t cnt = (uint32_t)(wave_sum[TAG_BLOCK / 64] >> 40);
+    const uint32_t sl = threadIdx.x & 15u;
+    for (uint32_t g = threadIdx.x >> 4; g < cnt; g += TAG_BLOCK / 16) {
+        const uint32_t ij = i0 + l_rec[g];
+        const RecHdr r = rec_header(a.u + a.rec_off[ij]);
+        const uint32_t rs = a.rsb[ij], nl = a.cnt[2u * ij];
+        uint8_t *dst = a.xo + l_off[g];
+        const uint32_t *ops = a.ops + a.ops_at[ij];
+        if (rs & 2u) {
+            extract_write(r, a.tid[2u * ij], a.pos[2u * ij], ops, nl, dst, sl);
+            dst += extract_size(r, nl);
+        }
+        if (rs & 4u) extract_write(r, a.tid[2u * ij + 1u], a.pos[2u * ij + 1u], ops + nl, a.cnt[2u * ij + 1u], dst, sl);
+    }
+}
+
+// The records as they leave: sixteen lanes per record, four records per wavefront at a time, a block per TAG_BLOCK records
+// (whose base applies), as bam_rewrite_kernel.  A record the eject kernels took out (INFO_BAD) is skipped; with CLIP a record
+// whose plan says so leaves clipped or reset, its aux bytes unchanged; every other record is copied byte for byte.
+template <bool CLIP>
+__global__ __launch_bounds__(REWRITE_WAVES * 64) void bam_tags_write_kernel(FromTagsArgs a) {
+    __shared__ uint64_t off[TAG_BLOCK];
+    __shared__ uint64_t wave_sum[TAG_BLOCK / 64 + 1];
+    const uint32_t r1 = min(a.r1_cap, a.counts_in->n_records);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t i0 = blockIdx.x * TAG_BLOCK;
+    uint64_t sz = 0, inc = 0;
+    if (threadIdx.x < TAG_BLOCK) {
+        const uint32_t i = i0 + threadIdx.x;
+        sz = i < r1 ? (uint64_t)a.out_size[i] : 0ull;
+        inc = sz;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint64_t o = (uint64_t)__shfl_up((long long)inc, d, 64);
+            if (lane >= d) inc += o;
+        }
+        if (lane == 63) wave_sum[wave + 1] = inc;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        wave_sum[0] = 0;
+        for (int w = 1; w <= TAG_BLOCK / 64; w++) wave_sum[w] += wave_sum[w - 1];
+    }
+    __syncthreads();
+    if (threadIdx.x < TAG_BLOCK) off[threadIdx.x] = a.blk_base[blockIdx.x] + wave_sum[wave] + inc - sz;
+    __syncthreads();
+    constexpr int PER_WAVE = TAG_BLOCK / REWRITE_WAVES;
+    static_assert(PER_WAVE % 4 == 0, "four records per wavefront at a time");
+    const uint32_t sub = (uint32_t)lane >> 4, sl = (uint32_t)lane & 15u;
+    for (int j = 0; j < PER_WAVE / 4; j++) {
+        const uint32_t k = (uint32_t)wave * PER_WAVE + 4u * (uint32_t)j + sub, ij = i0 + k;
+        if (ij >= r1) continue;
+        if (a.info[ij] & INFO_BAD) continue;
+        const RecHdr r = rec_header(a.u + a.rec_off[ij]);
+        uint8_t *dst = a.o + off[k];
+        if constexpr (CLIP) {
+            const ClipPlan c = clip_plan(r, a.rsb[ij], a.trim_l[ij], a.trim_r[ij]);
+            if (c.mode) {
+                clip_write_head(r, c, dst, a.out_size[ij] - 4u, sl);
+                if (c.mode == 1u) copy16(dst + c.pre, r.p + r.aux_off, r.end - r.aux_off, sl);
+                continue;
+            }
+        }
+        copy16(dst, r.p, r.end, sl);
+    }
+}
+
+}  // namespace bam
+}  // namespace fadehip

@@ -4,6 +4,7 @@
 // through fadehip_host.hpp.
 #include "fadehip_host.hpp"
 #include "bam_device.hpp"
+#include "bam_from_tags.hpp"
 #include <algorithm>
 #include <chrono>
 #include <condition_variable>
@@ -350,7 +351,9 @@ struct fadehip_bam_stream {
     bool extract = false;    // FADEHIP_BAM_EXTRACT: every call also leaves `fade extract`'s records of its artifact calls
     bool eject = false;      // FADEHIP_BAM_EJECT: artifact calls are not written (the eject kernels of bam_device.hpp) ...
     bool eject_groups = false;  // FADEHIP_BAM_EJECT_GROUPS: ... nor any record of their name group; a group never lies across two calls
+    bool from_tags = false;     // FADEHIP_BAM_FROM_TAGS: rs and am come out of the records (bam_from_tags.hpp), nothing is aligned
     DevBuf names_text, names_off;
+    DevBuf names_first;         // from_tags: for every contig the first one of its name (fadehip_tags_batch's rule)
     struct Out {
         DevBuf o;
         size_t bytes = 0;
@@ -377,6 +380,10 @@ struct fadehip_bam_stream {
         DevBuf seg, slots, rec_off, info, sent_of, art_of, out_size, blk32, blk64, counts;
         DevBuf ex_size, ex_blk;               // extract: bytes per record, block sums and bases (the tag arrays' counterparts)
         DevBuf ej_head, ej_blk, ej_grp;       // eject: every record's group start, the blocks' last starts and carries, the groups' marks
+        // from_tags: the stage's per-record arrays (rs byte, trims), per-side arrays (contig, position, ops, text), the ops'
+        // block sums and bases, where a record's ops start, and the ops themselves (sized in back, when their total is known)
+        DevBuf ft_rec, ft_side, ft_ops_blk, ft_ops_at, ft_ops;
+        bam::FromTagsArgs fa;
         bam::TagArgs xa;                      // extract: ta with the extract stream's sizes, sums, counts and output
         PinBuf h_blocks, h_counts;
         uint64_t k = ~0ull;
@@ -399,8 +406,10 @@ struct fadehip_bam_stream {
     size_t last_xbytes = 0;
     int64_t last_xrecs = 0;
     bool have_back = false;
-    // the counts of a call as they cross to the host: the call's ChunkCounts and, with extract, the extract stream's behind it
-    size_t counts_bytes() const { return sizeof(bam::ChunkCounts) * (extract ? 2u : 1u); }
+    // the counts of a call as they cross to the host: the call's ChunkCounts, with extract the extract stream's behind it,
+    // with from_tags the stage's StageCounts behind those
+    size_t stage_counts_at() const { return sizeof(bam::ChunkCounts) * (extract ? 2u : 1u); }
+    size_t counts_bytes() const { return stage_counts_at() + (from_tags ? sizeof(bam::StageCounts) : 0u); }
     std::mutex mu;
     std::condition_variable cv;
     int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -453,8 +462,20 @@ int bam_finish_extract(fadehip_bam_stream *st, fadehip_bam_stream::Set &S, uint6
         if (xb) {
             PinBuf &xh = st->xbuf[k % (FADEHIP_BAM_CHUNKS + 1)];
             if ((rc = reserve_roomy(ctx, out->x, (size_t)xb + 256)) || (rc = reserve_pinned(ctx, xh, (size_t)xb + (size_t)xb / 4 + 256))) return rc;
-            S.xa.o = (uint8_t *)out->x.p;
-            hipLaunchKernelGGL(bam::bam_extract_write_kernel, dim3(S.ntb), dim3(bam::TAG_BLOCK), 0, q, S.xa);
+            if (st->from_tags) {
+                // the sides' ops, materialised now that their total has crossed with the counts, then the records
+                const uint64_t n_ops = ((const bam::StageCounts *)(S.h_counts.p + st->stage_counts_at()))->ops.out_bytes;
+                if (n_ops > ((uint64_t)1 << 29)) return set_err(ctx, FADEHIP_E_UNSUPPORTED, "bam stream: %llu CIGAR ops in one call's am tags (at most 2^29)", (unsigned long long)n_ops);
+                if ((rc = reserve_roomy(ctx, S.ft_ops, 4 * (size_t)n_ops + 8))) return rc;
+                S.fa.ops = (uint32_t *)S.ft_ops.p;
+                S.fa.xo = (uint8_t *)out->x.p;
+                hipLaunchKernelGGL(bam::bam_tags_ops_kernel, dim3(S.ntb), dim3(bam::TAG_BLOCK), 0, q, S.fa);
+                HIPCHK(ctx, hipGetLastError());
+                hipLaunchKernelGGL(bam::bam_tags_extract_write_kernel, dim3(S.ntb), dim3(bam::TAG_BLOCK), 0, q, S.fa);
+            } else {
+                S.xa.o = (uint8_t *)out->x.p;
+                hipLaunchKernelGGL(bam::bam_extract_write_kernel, dim3(S.ntb), dim3(bam::TAG_BLOCK), 0, q, S.xa);
+            }
             HIPCHK(ctx, hipGetLastError());
             HIPCHK(ctx, hipMemcpyAsync(xh.p, out->x.p, (size_t)xb, hipMemcpyDeviceToHost, q));
             out->xbytes = (size_t)xb;
@@ -481,7 +502,19 @@ int bam_finish_call(fadehip_bam_stream *st, uint64_t k) {
     out->bytes = 0;
     if (S.n_rec) {
         bam::ChunkCounts *h_counts = (bam::ChunkCounts *)S.h_counts.p;
-        if (S.n_sent) {
+        if (st->from_tags) {
+            HIPCHK(ctx, hipStreamSynchronize(q));  // the stage, the eject kernels, the scans, the counts
+            const bam::StageCounts *sc = (const bam::StageCounts *)(S.h_counts.p + st->stage_counts_at());
+            std::lock_guard<std::mutex> l(st->mu);
+            if (sc->bad) {
+                const long long rec = (long long)st->n_records + (long long)(0xffffffffu - (uint32_t)(sc->bad >> 8));
+                const uint32_t kind = (uint32_t)(sc->bad & 0xffu);
+                return set_err(ctx, FADEHIP_E_INVALID, "bam stream: record %lld: malformed am tag (%s)", rec,
+                               kind == bam::FT_BAD_CLIP ? "rs names a side whose CIGAR is missing or does not parse"
+                               : kind == bam::FT_BAD_OPS ? "a side holds more than 65535 CIGAR ops" : "rs names a side that is not name,pos,cigar");
+            }
+            for (int t = 0; t < 8; t++) st->stats[t] += (int64_t)sc->stats[t];
+        } else if (S.n_sent) {
             if ((rc = finish_run(ctx, s, (int)(k & 1)))) return rc;  // waits for the stream: run and sizes
             std::lock_guard<std::mutex> l(st->mu);
             for (int t = 0; t < 8; t++) st->stats[t] += s.stats[t];
@@ -495,7 +528,10 @@ int bam_finish_call(fadehip_bam_stream *st, uint64_t k) {
         if (out_bytes > ((uint64_t)1 << 31)) return set_err(ctx, FADEHIP_E_UNSUPPORTED, "bam stream: %llu output bytes in one call (at most 2^31)", (unsigned long long)out_bytes);
         if ((rc = reserve_roomy(ctx, out->o, (size_t)out_bytes + 256))) return rc;
         S.ta.o = (uint8_t *)out->o.p;
-        if (st->clip) hipLaunchKernelGGL(bam::bam_rewrite_kernel<true>, dim3(S.ntb), dim3(bam::REWRITE_WAVES * 64), 0, q, S.ta);
+        S.fa.o = (uint8_t *)out->o.p;
+        if (st->from_tags && st->clip) hipLaunchKernelGGL(bam::bam_tags_write_kernel<true>, dim3(S.ntb), dim3(bam::REWRITE_WAVES * 64), 0, q, S.fa);
+        else if (st->from_tags) hipLaunchKernelGGL(bam::bam_tags_write_kernel<false>, dim3(S.ntb), dim3(bam::REWRITE_WAVES * 64), 0, q, S.fa);
+        else if (st->clip) hipLaunchKernelGGL(bam::bam_rewrite_kernel<true>, dim3(S.ntb), dim3(bam::REWRITE_WAVES * 64), 0, q, S.ta);
         else hipLaunchKernelGGL(bam::bam_rewrite_kernel<false>, dim3(S.ntb), dim3(bam::REWRITE_WAVES * 64), 0, q, S.ta);
         HIPCHK(ctx, hipGetLastError());
         out->bytes = (size_t)out_bytes;
@@ -817,6 +853,107 @@ int bam_front_run(fadehip_bam_stream *st, fadehip_bam_stream::Set &S, Slot &s, C
     return 0;
 }
 
+// B of call k under FADEHIP_BAM_FROM_TAGS: nothing is packed, gated or aligned — the stage kernel of bam_from_tags.hpp reads
+// rs and am out of the records, then the eject kernels (untouched: sent_of = nullptr, the stage's byte per record), the
+// scans, and the counts to the host, the stage's own behind the call's
+int bam_front_tags(fadehip_bam_stream *st, fadehip_bam_stream::Set &S, Slot &s, uint32_t n_rec) {
+    fadehip_ctx *ctx = st->ctx;
+    hipStream_t q = s.stream;
+    const bam::PackArgs &pa = S.pa;
+    const bam::ChunkCounts *h_counts = (const bam::ChunkCounts *)S.h_counts.p;
+    bam::ChunkCounts *d_counts = pa.counts;
+    int rc;
+    const uint32_t ntb = (n_rec + bam::TAG_BLOCK - 1) / bam::TAG_BLOCK;
+    if (h_counts->n_bad_layout)
+        return set_err(ctx, FADEHIP_E_INVALID, "bam stream: call %llu: %u records whose fields do not fit their block_size or whose tags are not whole fields (corrupt BAM)", (unsigned long long)st->k_front, h_counts->n_bad_layout);
+    const size_t n = n_rec;
+    if ((rc = reserve_roomy(ctx, S.blk64, 16 * (size_t)ntb)) || (rc = reserve_roomy(ctx, S.ft_rec, 9 * n + 16))) return rc;
+    bam::FromTagsArgs &fa = S.fa;
+    memset(&fa, 0, sizeof fa);
+    fa.u = pa.u;
+    fa.rec_off = pa.rec_off;
+    fa.counts_in = d_counts;
+    fa.r1_cap = n_rec;
+    fa.mode = (st->clip ? bam::FT_CLIP : 0u) | (st->eject && !st->eject_groups ? bam::FT_EJECT_RECORDS : 0u) | (st->extract ? bam::FT_EXTRACT : 0u);
+    fa.info = pa.info;
+    fa.names.bytes = (const uint8_t *)st->names_text.p;
+    fa.names.off = (const uint32_t *)st->names_off.p;
+    fa.names.first = (const int32_t *)st->names_first.p;
+    fa.names.n_ref = st->n_ref;
+    fa.trim_l = (uint32_t *)S.ft_rec.p;
+    fa.trim_r = fa.trim_l + n;
+    fa.rsb = (uint8_t *)(fa.trim_r + n);
+    fa.out_size = (uint32_t *)S.out_size.p;
+    fa.blk_sums = (uint64_t *)S.blk64.p;
+    fa.blk_base = fa.blk_sums + ntb;
+    fa.sc = (bam::StageCounts *)((uint8_t *)d_counts + st->stage_counts_at());
+    if (st->extract) {
+        // per side: pos i64 | tid i32 | cnt u32 | cig_at u32
+        if ((rc = reserve_roomy(ctx, S.ex_size, 4 * n)) || (rc = reserve_roomy(ctx, S.ex_blk, 16 * (size_t)ntb)) || (rc = reserve_roomy(ctx, S.ft_side, 40 * n + 16)) ||
+            (rc = reserve_roomy(ctx, S.ft_ops_blk, 16 * (size_t)ntb)) || (rc = reserve_roomy(ctx, S.ft_ops_at, 8 * n)))
+            return rc;
+        fa.x_size = (uint32_t *)S.ex_size.p;
+        fa.x_blk_sums = (uint64_t *)S.ex_blk.p;
+        fa.x_blk_base = fa.x_blk_sums + ntb;
+        fa.x_counts = d_counts + 1;
+        fa.pos = (int64_t *)S.ft_side.p;
+        fa.tid = (int32_t *)(fa.pos + 2 * n);
+        fa.cnt = (uint32_t *)(fa.tid + 2 * n);
+        fa.cig_at = fa.cnt + 2 * n;
+        fa.ops_blk_sums = (uint64_t *)S.ft_ops_blk.p;
+        fa.ops_blk_base = fa.ops_blk_sums + ntb;
+        fa.ops_at = (uint64_t *)S.ft_ops_at.p;
+    }
+    hipLaunchKernelGGL(bam::bam_tags_stage_kernel, dim3(ntb), dim3(bam::TAG_BLOCK), 0, q, fa);
+    HIPCHK(ctx, hipGetLastError());
+    // the scans are bam_tag_scan_kernel's, over TagArgs that name the sums, the bases and where the total goes
+    bam::TagArgs &ta = S.ta;
+    memset(&ta, 0, sizeof ta);
+    ta.blk_sums = fa.blk_sums;
+    ta.blk_base = fa.blk_base;
+    ta.counts = d_counts;
+    if (st->extract) {
+        bam::TagArgs xa = ta;
+        xa.blk_sums = fa.x_blk_sums;
+        xa.blk_base = fa.x_blk_base;
+        xa.counts = d_counts + 1;
+        hipLaunchKernelGGL(bam::bam_tag_scan_kernel, dim3(1), dim3(1024), 0, q, xa, ntb);
+        HIPCHK(ctx, hipGetLastError());
+        xa.blk_sums = fa.ops_blk_sums;
+        xa.blk_base = fa.ops_blk_base;
+        xa.counts = &fa.sc->ops;
+        hipLaunchKernelGGL(bam::bam_tag_scan_kernel, dim3(1), dim3(1024), 0, q, xa, ntb);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    if (st->eject) {
+        bam::EjectArgs ea;
+        memset(&ea, 0, sizeof ea);
+        ea.u = pa.u;
+        ea.off32 = pa.rec_off;
+        ea.n = n_rec;
+        ea.sent_of = nullptr;  // (rs is per record here)
+        ea.rs = fa.rsb;
+        ea.out_size = fa.out_size;
+        ea.info = pa.info;
+        ea.blk_sums = fa.blk_sums;
+        ea.counts = d_counts;
+        if (st->eject_groups) {
+            if ((rc = reserve_roomy(ctx, S.ej_head, 4 * n)) || (rc = reserve_roomy(ctx, S.ej_blk, 8 * (size_t)ntb)) || (rc = reserve_roomy(ctx, S.ej_grp, 4 * n))) return rc;
+            ea.head_of = (uint32_t *)S.ej_head.p;
+            ea.blk_head = (uint32_t *)S.ej_blk.p;
+            ea.blk_carry = ea.blk_head + ntb;
+            ea.grp = (uint32_t *)S.ej_grp.p;
+        }
+        if ((rc = enqueue_eject(ctx, q, ea, ntb, st->eject_groups))) return rc;
+    }
+    hipLaunchKernelGGL(bam::bam_tag_scan_kernel, dim3(1), dim3(1024), 0, q, ta, ntb);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(S.h_counts.p, d_counts, st->counts_bytes(), hipMemcpyDeviceToHost, q));
+    S.n_sent = 0;
+    S.ntb = ntb;
+    return 0;
+}
+
 int bam_front_impl(fadehip_bam_stream *st, const uint8_t *members, size_t n_bytes, int last, bool raw) {
     fadehip_ctx *ctx = st->ctx;
     const uint64_t k = st->k_front;
@@ -825,7 +962,7 @@ int bam_front_impl(fadehip_bam_stream *st, const uint8_t *members, size_t n_byte
     int rc;
     // the set's previous call must have been finished (back has usually done that long ago)
     CallTrace tr("front", k);
-    if (ctx->n_contigs == 0) return set_err(ctx, FADEHIP_E_STATE, "fadehip_genome_upload has not been called");
+    if (ctx->n_contigs == 0 && !st->from_tags) return set_err(ctx, FADEHIP_E_STATE, "fadehip_genome_upload has not been called");
     if (k >= 2 && (rc = bam_finish_call(st, k - 2))) return rc;
     tr.mark("finish call k - 2");
     // every stream is an HSA queue to set up and to give back (tens of ms each): slot 0 works on the ctx's copy stream, which
@@ -854,7 +991,7 @@ int bam_front_impl(fadehip_bam_stream *st, const uint8_t *members, size_t n_byte
     S.n_sent = 0;
     S.ntb = 0;
     S.out = out;
-    if (n_rec && (rc = bam_front_run(st, S, s, tr, n_rec))) return rc;
+    if (n_rec && (rc = st->from_tags ? bam_front_tags(st, S, s, n_rec) : bam_front_run(st, S, s, tr, n_rec))) return rc;
     S.pending = true;
     tr.mark("tag sizes enqueued");
     st->t_run += now_s() - t2;
@@ -874,7 +1011,8 @@ int bam_front_impl(fadehip_bam_stream *st, const uint8_t *members, size_t n_byte
 
 int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_bam_stream **out) {
     if (!ctx) return set_err(nullptr, FADEHIP_E_INVALID, "ctx is NULL");
-    if (!cfg || !out || cfg->n_ref < 0 || (cfg->n_ref && !cfg->ref_names) || cfg->window < 0 || (cfg->flags & ~(FADEHIP_BAM_STORED | FADEHIP_BAM_NO_OUTPUT | FADEHIP_BAM_CLIP | FADEHIP_BAM_EXTRACT | FADEHIP_BAM_EJECT | FADEHIP_BAM_EJECT_GROUPS)))
+    if (!cfg || !out || cfg->n_ref < 0 || (cfg->n_ref && !cfg->ref_names) || (cfg->window < 0 && !(cfg->flags & FADEHIP_BAM_FROM_TAGS)) ||
+        (cfg->flags & ~(FADEHIP_BAM_STORED | FADEHIP_BAM_NO_OUTPUT | FADEHIP_BAM_CLIP | FADEHIP_BAM_EXTRACT | FADEHIP_BAM_EJECT | FADEHIP_BAM_EJECT_GROUPS | FADEHIP_BAM_FROM_TAGS)))
         return set_err(ctx, FADEHIP_E_INVALID, "bam stream: bad configuration");
     if ((cfg->flags & FADEHIP_BAM_CLIP) && (cfg->flags & (FADEHIP_BAM_EJECT | FADEHIP_BAM_EJECT_GROUPS)))
         return set_err(ctx, FADEHIP_E_INVALID, "bam stream: FADEHIP_BAM_CLIP and FADEHIP_BAM_EJECT exclude each other (`fade out` clips an artifact or ejects it)");
@@ -894,6 +1032,7 @@ int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_ba
     st->extract = (cfg->flags & FADEHIP_BAM_EXTRACT) != 0;
     st->eject_groups = (cfg->flags & FADEHIP_BAM_EJECT_GROUPS) != 0;
     st->eject = st->eject_groups || (cfg->flags & FADEHIP_BAM_EJECT) != 0;
+    st->from_tags = (cfg->flags & FADEHIP_BAM_FROM_TAGS) != 0;
     std::string text;
     std::vector<uint32_t> off((size_t)cfg->n_ref + 1, 0);
     for (int k = 0; k < cfg->n_ref; k++) {
@@ -903,6 +1042,17 @@ int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_ba
     }
     off[(size_t)cfg->n_ref] = (uint32_t)text.size();
     int rc;
+    if (st->from_tags) {  // a header that names a contig twice: the first of that name is meant (fadehip_tags_batch's rule)
+        std::vector<int32_t> first((size_t)cfg->n_ref);
+        std::map<std::string, int32_t> seen;
+        for (int32_t k = 0; k < cfg->n_ref; k++) first[(size_t)k] = seen.emplace(cfg->ref_names[k], k).first->second;
+        if ((rc = reserve(ctx, st->names_first, 4 * first.size() + 4))) { fadehip_bam_close(st); return rc; }
+        if (cfg->n_ref && (hipMemcpyAsync(st->names_first.p, first.data(), 4 * first.size(), hipMemcpyHostToDevice, ctx->copy_stream) != hipSuccess ||
+                           hipStreamSynchronize(ctx->copy_stream) != hipSuccess)) {
+            fadehip_bam_close(st);
+            return set_err(ctx, FADEHIP_E_HIP, "bam stream: copying the contig names failed");
+        }
+    }
     if ((rc = reserve(ctx, st->names_text, text.size() + 1)) || (rc = reserve(ctx, st->names_off, 4 * off.size()))) { fadehip_bam_close(st); return rc; }
     // (on the ctx's copy stream: a synchronous hipMemcpy would bring up the null stream, one more queue to set up and to give back)
     if (hipMemcpyAsync(st->names_text.p, text.data(), text.size(), hipMemcpyHostToDevice, ctx->copy_stream) != hipSuccess ||
@@ -1167,9 +1317,10 @@ void fadehip_bam_close(fadehip_bam_stream *st) {
         if (l.stream) (void)hipStreamSynchronize(l.stream);
     release(st->names_text);
     release(st->names_off);
+    release(st->names_first);
     for (auto &S : st->set) {
         for (DevBuf *b : {&S.comp, &S.blocks, &S.status, &S.ticket, &S.u, &S.seg, &S.slots, &S.rec_off, &S.info, &S.sent_of, &S.art_of, &S.out_size, &S.blk32,
-                          &S.blk64, &S.counts, &S.ex_size, &S.ex_blk, &S.ej_head, &S.ej_blk, &S.ej_grp})
+                          &S.blk64, &S.counts, &S.ex_size, &S.ex_blk, &S.ej_head, &S.ej_blk, &S.ej_grp, &S.ft_rec, &S.ft_side, &S.ft_ops_blk, &S.ft_ops_at, &S.ft_ops})
             release(*b);
         release(S.h_blocks);
         release(S.h_counts);

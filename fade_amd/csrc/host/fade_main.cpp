@@ -2447,6 +2447,8 @@ static void print_extract_help() {
             "-t --threads extra threads for parsing the bam file\n"
             "-b     --bam output bam\n"
             "-u    --ubam output uncompressed bam\n"
+            "      --gpus 1: BAM file in, -b or -u out: the records are built on one MI355X (rs and am read back by a kernel)\n"
+            "    --timing print where the run spent its time to stderr\n"
             "-h    --help This help information.\n\n",
             kHeader);
 }
@@ -2534,6 +2536,8 @@ static void print_out_help() {
             "-t --threads extra threads for parsing the bam file\n"
             "-b     --bam output bam\n"
             "-u    --ubam output uncompressed bam\n"
+            "      --gpus 1: BAM file in, -b or -u out: filtering or clipping runs on one MI355X (rs and am read back by a kernel)\n"
+            "    --timing print where the run spent its time to stderr\n"
             "-h    --help This help information.\n\n",
             kHeader);
 }
@@ -2794,6 +2798,323 @@ static int out_main(const std::string &cl, const Opts &o) {
     return 0;
 }
 
+// `fade out [-c] --gpus 1` and `fade extract --gpus 1` on a BAM file with -b or -u: the file path on the device over records
+// that were annotated earlier (FADEHIP_BAM_FROM_TAGS) — rs and am are read back out of the records by a kernel, the clip,
+// eject and extract kernels are those of `fade annotate -c / --eject / --extract`, and this process moves compressed bytes.
+// A reader thread cuts the file at BGZF member boundaries (and, with FADE_BAM_INFLATE=host, inflates the members on the
+// pool); this thread alternates front of call k and back of call k - 1, and writes what back hands out.  SAM or piped
+// input, SAM output and FADE_BAM_DEVICE=0 take the host loop (*fall_back stays set and nothing has been written).
+enum class TagsJob { OUT, EXTRACT };
+static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, bool *fall_back) {
+    *fall_back = true;
+    const char *who = job == TagsJob::EXTRACT ? "fade extract" : "fade out";
+    const std::string &path = o.pos[1];
+    struct stat sb;
+    if (!(o.bam || o.ubam) || path == "-" || stat(path.c_str(), &sb) != 0 || !S_ISREG(sb.st_mode)) return 1;
+    if (getenv("FADE_BAM_DEVICE") && atoi(getenv("FADE_BAM_DEVICE")) == 0) return 1;
+    StageClock ck_total, ck_front, ck_back, ck_write;
+    ck_total.start();
+    const int nthreads = o.threads > 0 ? o.threads : default_threads();
+    const char *inf_env = getenv("FADE_BAM_INFLATE");
+    const bool host_inflate = inf_env ? strcmp(inf_env, "host") == 0 : nthreads >= 8;
+    Pool pool(host_inflate || job == TagsJob::EXTRACT ? nthreads : std::min(nthreads, 4));
+    FILE *f = fopen(path.c_str(), "rb");
+    if (!f) return 1;
+    struct Closer { FILE *f; ~Closer() { fclose(f); } } closer{f};
+    Header hdr;
+    uint64_t coff = 0;
+    uint32_t first_rec = 0;
+    std::vector<std::string> first_names;  // plain `out`: the names of the first ten records
+    try {
+        Reader rd(path, &pool);
+        if (!rd.is_bam()) return 1;
+        hdr = rd.header();
+        const size_t hdr_bytes = rd.bam_header_bytes();
+        if (job == TagsJob::OUT && !o.clip) {  // the front of the file is inflated here anyway: on to the tenth record
+            std::vector<Rec> first;
+            rd.read_chunk(first, 10);
+            for (const Rec &r : first) first_names.push_back(r.qname());
+        }
+        // the member that holds the first record, and the record's offset in its payload
+        uint64_t at = 0, cum = 0;
+        for (;;) {
+            uint8_t h[18], t[4];
+            if (pread(fileno(f), h, 18, (off_t)at) != 18) return 1;
+            if (h[0] != 0x1f || h[1] != 0x8b || !(h[3] & 4) || h[12] != 'B' || h[13] != 'C') return 1;  // (other gzip subfields first: the host loop reads it)
+            const uint32_t bs = (uint32_t)(h[16] | (h[17] << 8)) + 1u;
+            if (pread(fileno(f), t, 4, (off_t)(at + bs - 4)) != 4) return 1;
+            const uint32_t isz = (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
+            if (cum + isz > hdr_bytes || (uint64_t)at + bs >= (uint64_t)sb.st_size) { coff = at; first_rec = (uint32_t)(hdr_bytes - cum); break; }
+            cum += isz;
+            at += bs;
+        }
+        if (first_rec > 65536) return 1;
+    } catch (const std::exception &e) {
+        return 1;  // the host loop reports what is wrong with the file
+    }
+    *fall_back = false;
+    if (o.timing) fprintf(stderr, "[timing] since process start %.3f s (%s begins; file path on the device)\n", since_process_start(), who);
+    bool grouped = false;
+    if (job == TagsJob::EXTRACT) {
+        fprintf(stderr, "[W::fade extract] Output SAM/BAM will not be sorted\n");  // remap.d:13
+    } else if (o.clip) {  // filter.d:184-185
+        fprintf(stderr, "[W::fade-out] Using the -c flag means the output SAM/BAM will not be sorted (regardless of prior sorting)\n");
+        fprintf(stderr, "[W::fade-out] You also may need to fix mate information with a tool like Picard FixMateInformation\n");
+    } else {
+        grouped = eject_mode_grouped(first_names);  // filter.d:216-220, 248
+    }
+    fadehip_ctx *ctx = nullptr;
+    fadehip_bam_stream *st = nullptr;
+    struct Guard {
+        fadehip_ctx *&c;
+        fadehip_bam_stream *&s;
+        std::vector<void *> pinned, owned;
+        ~Guard() {
+            if (s) fadehip_bam_close(s);
+            for (void *p : pinned) fadehip_host_free(c, p);
+            if (c) fadehip_destroy(c);
+            for (void *p : owned) free(p);
+        }
+    } guard{ctx, st, {}, {}};
+    try {
+        fadehip_params prm;
+        fadehip_params_default(&prm);
+        setenv("FADEHIP_TAIL_CUS", "0", 0);
+        setenv("FADEHIP_BLOCKING_SYNC", "1", 0);  // the thread that waits for the device sleeps: the cores are the inflater's
+        const int device = getenv("FADE_DEVICE_MAP") ? atoi(getenv("FADE_DEVICE_MAP")) : 0;
+        const size_t chunk = (size_t)std::max(1, getenv("FADE_BAM_CHUNK_MB") ? atoi(getenv("FADE_BAM_CHUNK_MB")) : host_inflate ? 32 : 128) << 20;
+        // the device is brought up beside the buffers being made and the first members being read
+        std::string create_err;
+        std::future<int> creating = std::async(std::launch::async, [&]() -> int {
+            if (fadehip_create(&ctx, device, &prm)) { create_err = fadehip_last_error(nullptr); return 1; }
+            std::vector<const char *> names;
+            for (auto &n : hdr.names) names.push_back(n.c_str());
+            fadehip_bam_config cfg;
+            memset(&cfg, 0, sizeof cfg);
+            cfg.n_ref = (int32_t)names.size();
+            cfg.ref_names = names.data();
+            cfg.first_record = first_rec;
+            cfg.flags = FADEHIP_BAM_FROM_TAGS | (o.ubam ? FADEHIP_BAM_STORED : 0);
+            if (job == TagsJob::EXTRACT) cfg.flags |= FADEHIP_BAM_EXTRACT | FADEHIP_BAM_NO_OUTPUT;
+            else if (o.clip) cfg.flags |= FADEHIP_BAM_CLIP;
+            else cfg.flags |= grouped ? FADEHIP_BAM_EJECT | FADEHIP_BAM_EJECT_GROUPS : FADEHIP_BAM_EJECT;
+            if (fadehip_bam_open(ctx, &cfg, &st)) { create_err = fadehip_last_error(ctx); return 1; }
+            const size_t call_bytes = host_inflate ? chunk : std::min<size_t>(chunk * 3, (size_t)1 << 30);
+            if (!(getenv("FADE_BAM_PREPARE") && atoi(getenv("FADE_BAM_PREPARE")) == 0) && fadehip_bam_prepare(st, call_bytes)) { create_err = fadehip_last_error(ctx); return 1; }
+            return 0;
+        });
+        struct Joiner { std::future<int> &f; ~Joiner() { if (f.valid()) f.wait(); } } joiner{creating};
+        // ---- the reader: compressed bytes cut at member boundaries; HEAD bytes in front of a buffer take the beginning of a
+        // member that the previous read cut
+        const size_t ccap = host_inflate ? std::max<size_t>(chunk / 2, 1 << 20) : chunk, HEAD = 65536 + 64;
+        constexpr int NBUF = 3;
+        struct In { uint8_t *p = nullptr; size_t n = 0; bool last = false; int buf = -1; };
+        std::vector<std::pair<void *, size_t>> raw_bufs;  // (registered with the ctx once it is there)
+        auto staging = [&](size_t bytes) -> uint8_t * {
+            const size_t al = (size_t)1 << 21, n = (bytes + al - 1) & ~(al - 1);
+            void *q = aligned_alloc(al, n);
+            if (!q) throw std::runtime_error("out of memory");
+            guard.owned.push_back(q);
+            raw_bufs.emplace_back(q, n);
+            return (uint8_t *)q;
+        };
+        uint8_t *bufs[NBUF];
+        std::vector<uint8_t> own_comp;  // host inflate: the compressed bytes never cross PCIe
+        for (int k = 0; k < NBUF; k++) bufs[k] = staging(host_inflate ? chunk + 65536 + 64 : HEAD + ccap + 64);
+        if (host_inflate) own_comp.resize(HEAD + ccap + 64);
+        BoundedQueue<int> q_free(NBUF + 1);
+        BoundedQueue<In> q_full(NBUF + 1);
+        for (int k = 0; k < NBUF; k++) q_free.push(k);
+        std::string stage_err;
+        std::mutex err_m;
+        auto set_err = [&](const std::string &e) {
+            std::lock_guard<std::mutex> l(err_m);
+            if (stage_err.empty()) stage_err = e;
+        };
+        struct Mem { size_t off, size, hl; uint32_t isz; };
+        auto scan_members = [&](const uint8_t *buf, size_t got, std::vector<Mem> &ms) -> size_t {
+            size_t w = 0;
+            ms.clear();
+            while (w + 18 <= got) {
+                const uint8_t *m = buf + w;
+                if (m[0] != 0x1f || m[1] != 0x8b) throw std::runtime_error("not a BGZF member in " + path);
+                const size_t xlen = (size_t)m[10] | ((size_t)m[11] << 8);
+                if (w + 12 + xlen > got) break;
+                size_t bs = 0;
+                for (size_t x = 12; x + 4 <= 12 + xlen;) {
+                    const size_t sl = (size_t)m[x + 2] | ((size_t)m[x + 3] << 8);
+                    if (m[x] == 'B' && m[x + 1] == 'C' && sl == 2 && x + 6 <= 12 + xlen) bs = ((size_t)m[x + 4] | ((size_t)m[x + 5] << 8)) + 1;
+                    x += 4 + sl;
+                }
+                if (bs < 12 + xlen + 10) throw std::runtime_error("BGZF member without a usable BC subfield in " + path);
+                if (w + bs > got) break;
+                uint32_t isz;
+                memcpy(&isz, m + bs - 4, 4);
+                if (isz > 65536) throw std::runtime_error("corrupt BGZF block (ISIZE beyond 64 KiB) in " + path);
+                ms.push_back(Mem{w, bs, 12 + xlen, isz});
+                w += bs;
+            }
+            return w;
+        };
+        StageThreads stages;
+        stages.unblock = [&] { q_free.close(); q_full.close(); };
+        stages.th.emplace_back([&] {
+            try {
+                uint64_t at = coff;
+                std::vector<uint8_t> tail;
+                std::vector<Mem> ms;
+                bool eof = false;
+                while (!eof) {
+                    int k = -1;
+                    if (!host_inflate && !q_free.pop(k)) break;
+                    uint8_t *base = host_inflate ? own_comp.data() : bufs[k];
+                    if (tail.size() > HEAD) throw std::runtime_error("BGZF member larger than 64 KiB in " + path);
+                    uint8_t *cb = base + HEAD - tail.size();
+                    if (!tail.empty()) memcpy(cb, tail.data(), tail.size());
+                    size_t got = 0;
+                    while (got < ccap) {
+                        const ssize_t r = pread(fileno(f), base + HEAD + got, ccap - got, (off_t)at);
+                        if (r < 0) throw std::runtime_error("read error on " + path);
+                        if (r == 0) { eof = true; break; }
+                        got += (size_t)r;
+                        at += (uint64_t)r;
+                    }
+                    const size_t have = tail.size() + got;
+                    const size_t w = scan_members(cb, have, ms);
+                    tail.assign(cb + w, cb + have);
+                    if (eof && !tail.empty()) throw std::runtime_error("the file ends inside a BGZF member: " + path);
+                    if (!host_inflate) {
+                        In in;
+                        in.p = cb; in.n = w; in.last = eof; in.buf = k;
+                        q_full.push(in);
+                        continue;
+                    }
+                    size_t m0 = 0;
+                    do {  // batches of members whose payloads fill a staging buffer
+                        size_t total = 0, m1 = m0;
+                        while (m1 < ms.size() && total + ms[m1].isz <= chunk) total += ms[m1++].isz;
+                        if (!q_free.pop(k)) return;
+                        uint8_t *dst = bufs[k];
+                        std::vector<size_t> ooff(m1 - m0 + 1, 0);
+                        for (size_t j = m0; j < m1; j++) ooff[j - m0 + 1] = ooff[j - m0] + ms[j].isz;
+                        std::atomic<bool> bad{false};
+                        pool.parallel_for(m1 - m0, [&](size_t t) {
+                            static thread_local std::unique_ptr<FastInflate> fi;
+                            if (!fi) fi.reset(new FastInflate());
+                            const Mem &m = ms[m0 + t];
+                            if (m.isz == 0) {  // (an empty member must be one: hts_lite.hpp)
+                                if (m.size < m.hl + 8 || !bgzf_empty_member_ok(cb + m.off + m.hl, m.size - m.hl - 8, cb + m.off + m.size - 8)) bad = true;
+                                return;
+                            }
+                            if (!fi->inflate(cb + m.off + m.hl, m.size - m.hl - 8, dst + ooff[t], m.isz)) { bad = true; return; }
+                            uint32_t crc;  // the member's CRC32 (RFC 1952 trailer), as htslib checks it
+                            memcpy(&crc, cb + m.off + m.size - 8, 4);
+                            if (crc32_fast(0, dst + ooff[t], m.isz) != crc) bad = true;
+                        }, CPU_INFLATE);
+                        if (bad) throw std::runtime_error("BGZF block does not inflate to its ISIZE / CRC32 (corrupt input)");
+                        In in;
+                        in.p = dst; in.n = total; in.last = eof && m1 == ms.size(); in.buf = k;
+                        q_full.push(in);
+                        m0 = m1;
+                    } while (m0 < ms.size());
+                }
+            } catch (const std::exception &e) {
+                set_err(e.what());
+            }
+            q_full.close();
+        });
+        // ---- the header, as the host loop writes it; the records follow from the device (`extract`: through the Writer)
+        Header out_hdr = hdr;
+        out_hdr.add_pg("fade-extract", "fade", FADE_VERSION, cl);  // filter.d:173-180 / remap.d:18-26 (the reference reuses this ID)
+        if (creating.get()) { fprintf(stderr, "[E::%s] cannot open the GPU path: %s\n", who, create_err.c_str()); return 1; }
+        for (auto &rb : raw_bufs) {
+            if (fadehip_host_register(ctx, rb.first, rb.second)) { fprintf(stderr, "[E::%s] %s\n", who, fadehip_last_error(ctx)); return 1; }
+            guard.pinned.push_back(rb.first);
+        }
+        const OutFmt fmt = o.ubam ? OutFmt::UBAM : OutFmt::BAM;
+        std::unique_ptr<Writer> xwriter;
+        if (job == TagsJob::EXTRACT) xwriter.reset(new Writer(stdout, fmt, out_hdr, &pool));
+        else {
+            Writer hw(stdout, fmt, out_hdr, &pool, nullptr, true, false);  // (its members only: no end-of-file block yet)
+            hw.close();
+        }
+        std::vector<Rec> xrecs;
+        auto take_back = [&]() {
+            const uint8_t *p = nullptr;
+            size_t n = 0;
+            ck_back.start();
+            const int rc = fadehip_bam_back(st, &p, &n);
+            ck_back.stop();
+            if (rc) throw std::runtime_error(fadehip_last_error(ctx));
+            ck_write.start();
+            if (xwriter) {
+                const uint8_t *xp = nullptr;
+                size_t xn = 0;
+                int64_t n_x = 0;
+                if (fadehip_bam_back_extract(st, &xp, &xn, &n_x)) throw std::runtime_error(fadehip_last_error(ctx));
+                xrecs.clear();
+                for (size_t at_x = 0; at_x + 4 <= xn;) {
+                    uint32_t bs;
+                    memcpy(&bs, xp + at_x, 4);
+                    if (bs < 32 || at_x + 4 + bs > xn) throw std::runtime_error("the device's extract records are not whole");
+                    xrecs.emplace_back();
+                    xrecs.back().d.assign(xp + at_x + 4, xp + at_x + 4 + bs);
+                    at_x += 4 + (size_t)bs;
+                }
+                if (!xrecs.empty()) xwriter->write(xrecs);
+            } else if (n && fwrite(p, 1, n, stdout) != n) throw std::runtime_error("write error on the output stream");
+            ck_write.stop();
+        };
+        In in;
+        bool waiting = false, ended = false;
+        while (q_full.pop(in)) {
+            ck_front.start();
+            const int rc = host_inflate ? fadehip_bam_front_raw(st, in.p, in.n, in.last ? 1 : 0) : fadehip_bam_front(st, in.p, in.n, in.last ? 1 : 0);
+            ck_front.stop();
+            if (rc) throw std::runtime_error(fadehip_last_error(ctx));
+            q_free.push(in.buf);
+            ended |= in.last;
+            if (waiting) take_back();  // (call k - 1, while call k runs on the device)
+            waiting = true;
+        }
+        if (waiting && stage_err.empty()) take_back();
+        stages.unblock();
+        for (auto &t : stages.th) t.join();
+        stages.unblock = nullptr;
+        if (!stage_err.empty()) { fprintf(stderr, "[E::%s] %s\n", who, stage_err.c_str()); return 1; }
+        if (!ended) { fprintf(stderr, "[E::%s] the input ended before its last call\n", who); return 1; }
+        if (xwriter) xwriter->close();
+        else if (fwrite(BGZF_EOF, 1, sizeof BGZF_EOF, stdout) != sizeof BGZF_EOF) { fprintf(stderr, "[E::%s] write error on the output stream\n", who); return 1; }
+        if (fflush(stdout) != 0 || ferror(stdout)) { fprintf(stderr, "[E::%s] write error on the output stream\n", who); return 1; }
+        int64_t totals[8], n_rec = 0, n_over = 0, n_ej = 0;
+        fadehip_bam_totals(st, totals, &n_rec, &n_over);
+        fadehip_bam_ejected(st, &n_ej);
+        if (job == TagsJob::OUT) {  // filter.d:267
+            OutStats stats;
+            stats.read_count = totals[0]; stats.clipped = totals[1]; stats.sup = totals[2]; stats.art_sup = totals[3];
+            stats.art = totals[4]; stats.art_mate = totals[5]; stats.aln_l = totals[6]; stats.aln_r = totals[7];
+            stats.print();
+        }
+        ck_total.stop();
+        if (o.timing)
+            fprintf(stderr, "[timing] total %.3f s (%s, file path on the device, inflate on the %s): front (%sframe, tags read back) %.3f | back (%s, copy out) %.3f | write %.3f; "
+                            "%lld records, %lld not written\n",
+                    ck_total.t, who, host_inflate ? "host" : "device", host_inflate ? "" : "inflate, ", ck_front.t, job == TagsJob::EXTRACT ? "extract records" : o.ubam ? "store" : "deflate",
+                    ck_back.t, ck_write.t, (long long)n_rec, (long long)n_ej);
+    } catch (const std::exception &e) {
+        fprintf(stderr, "[E::%s] %s\n", who, e.what());
+        return 1;
+    }
+    return 0;
+}
+
+// --gpus for `fade out` / `fade extract`: 1 is the file path on the device where the input and output allow it, more is not built
+static bool tags_gpus_ok(const Opts &o, const char *who) {
+    if (o.seen.find('g') == std::string::npos || o.gpus == 1) return true;
+    fprintf(stderr, "[E::%s] --gpus %d: this subcommand runs on one device (--gpus 1) or on the host (no --gpus)\n", who, o.gpus);
+    return false;
+}
+
 int main(int argc, char **argv) {
     std::string cl;  // app.d:66
     for (int i = 0; i < argc; i++) { if (i) cl += ' '; cl += argv[i]; }
@@ -2912,11 +3233,17 @@ int main(int argc, char **argv) {
             fprintf(stderr, "std.getopt.GetOptException: %s\n", err.c_str());
             return 1;
         }
-        if (!options_allowed(o, "tbu")) return 1;
+        if (!options_allowed(o, "tbugT")) return 1;
         if (o.help || o.pos.size() < 2) { print_extract_help(); return 0; }
+        if (!tags_gpus_ok(o, "fade extract")) return 1;
         if (o.bam && o.ubam) {
             fprintf(stderr, "[E::fade-annotate] Please use only one of the b or u flags\n");  // app.d:149 (sic)
             return 1;
+        }
+        if (o.seen.find('g') != std::string::npos) {  // --gpus 1: the file path on the device, where input and output allow it
+            bool fall_back = true;
+            const int rc = tags_stream_main(cl, o, TagsJob::EXTRACT, &fall_back);
+            if (!fall_back) return rc;
         }
         return extract_main(cl, o);
     }
@@ -2927,11 +3254,17 @@ int main(int argc, char **argv) {
             fprintf(stderr, "std.getopt.GetOptException: %s\n", err.c_str());
             return 1;
         }
-        if (!options_allowed(o, "ctbu")) return 1;
+        if (!options_allowed(o, "ctbugT")) return 1;
         if (o.help || o.pos.size() < 2) { print_out_help(); return 0; }
+        if (!tags_gpus_ok(o, "fade out")) return 1;
         if (o.bam && o.ubam) {
             fprintf(stderr, "[E::fade-annotate] Please use only one of the b or u flags\n");  // app.d:122 (sic)
             return 1;
+        }
+        if (o.seen.find('g') != std::string::npos) {  // --gpus 1: the file path on the device, where input and output allow it
+            bool fall_back = true;
+            const int rc = tags_stream_main(cl, o, TagsJob::OUT, &fall_back);
+            if (!fall_back) return rc;
         }
         return out_main(cl, o);
     }

@@ -415,7 +415,8 @@ int fadehip_bgzf_inflate(fadehip_ctx *ctx, const void *members, size_t n_bytes, 
  * tag of the wrong kind — rs:Z, am:i — is left as it is, as htslib's EINVAL leaves it).  Errors (corrupt member, impossible
  * record, input ending inside a record when last != 0) fail the call and every later one; what the device finds in a
  * call's records after front has returned surfaces at the call's back.  fadehip_bam_totals counts the calls back has taken.
- * The genome must have been uploaded (fadehip_genome_upload) by the first front call; the stream uses the ctx's slots 0 and
+ * The genome must have been uploaded (fadehip_genome_upload) by the first front call — unless the stream was opened with
+ * FADEHIP_BAM_FROM_TAGS, which needs none; the stream uses the ctx's slots 0 and
  * 1 and both BGZF lanes.
  * fadehip_bam_prepare (optional, before the first front call, typically on a thread of its own beside the caller's start-up):
  * makes what the first calls would otherwise make one after the other — the streams of the second slot and of the
@@ -449,7 +450,24 @@ typedef struct fadehip_bam_config {
                                    * the next (a call that is one group yields nothing), and a group longer than a call can hold
                                    * is FADEHIP_E_UNSUPPORTED.  Both combine with STORED, NO_OUTPUT and EXTRACT (the extract
                                    * records are built of the ejected artifact calls all the same); with FADEHIP_BAM_CLIP,
-                                   * fadehip_bam_open returns FADEHIP_E_INVALID.  fadehip_bam_totals is not changed by them */
+                                   * fadehip_bam_open returns FADEHIP_E_INVALID.  fadehip_bam_totals is not changed by them;
+                                   * FADEHIP_BAM_FROM_TAGS: the records were annotated earlier, and rs and am come out of the
+                                   * records themselves (the first field of each name, as fadehip_tags_batch reads them) instead of
+                                   * out of a run of the aligner: `fade out -c` (with CLIP), plain `fade out` (EJECT or
+                                   * EJECT_GROUPS) and `fade extract` (EXTRACT, usually with NO_OUTPUT) as the file path.  No
+                                   * genome is needed, floor_len and window are ignored, no tag is written or updated and the aux
+                                   * bytes pass unchanged.  Alone, every record passes byte for byte.  CLIP: a record with an
+                                   * integer rs and rs & 6 is hard-clipped by the reference bases of its am sides' CIGARs (only the
+                                   * third field of a side whose bit is set has to parse); a record without an integer rs passes.
+                                   * EJECT: a record is written only with an integer rs and !(rs & 6) — one without rs is dropped;
+                                   * EJECT_GROUPS: a record without rs neither ejects its group nor is dropped on its own.
+                                   * EXTRACT: a record takes part with an integer rs, rs & 6 and an am:Z; per set bit one record
+                                   * from that side's contig (-1: unknown or empty name; of two contigs of one name the first),
+                                   * position and ops, at most 65535 of them.  A side that is needed and not well-formed fails
+                                   * the call at its back: FADEHIP_E_INVALID, fadehip_last_error names the record's index in the
+                                   * stream.  fadehip_bam_totals then sums stats.d:45-54 over the rs read back (read_count over
+                                   * every record, the other seven over records with an integer rs), fadehip_bam_ejected counts
+                                   * every record not written */
     const char *const *ref_names; /* [n_ref] NUL-terminated */
     uint32_t first_record;        /* payload bytes of the first member passed to front that precede the first record */
     uint32_t tail_trim;           /* payload bytes at the END of the last member (front's last call) that are not this stream's:
@@ -462,6 +480,7 @@ typedef struct fadehip_bam_config {
 #define FADEHIP_BAM_EXTRACT 8
 #define FADEHIP_BAM_EJECT 16
 #define FADEHIP_BAM_EJECT_GROUPS 32
+#define FADEHIP_BAM_FROM_TAGS 64
 int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_bam_stream **out);
 int fadehip_bam_prepare(fadehip_bam_stream *st, size_t call_bytes);
 int fadehip_bam_front(fadehip_bam_stream *st, const void *members, size_t n_bytes, int last);
