@@ -328,6 +328,10 @@ int plan_two_pass(fadehip_ctx *ctx, const Slot &s, const ClassRun &c, TwoPassPla
     return 0;
 }
 
+// A slot's patch block (Slot::patch, h_patch), what ends a run in the early order: PatchHead | the run's counter block | entries
+constexpr size_t PATCH_ZB_OFF = sizeof(PatchHead), PATCH_LIST_OFF = PATCH_ZB_OFF + Slot::ZB_STRIDE;
+static_assert(PATCH_LIST_OFF % 16 == 0 && Slot::ZB_BYTES % 4 == 0, "the gather copies dwords; entries stay 16-byte aligned");
+
 // Two-pass path for one class list, enqueued without a read-back: pass 1 scores every alignment (and,
 // when the run asks for them, leaves wave snapshots every CK_COLS steps); the selection — inside the score pass's waves —
 // finishes what needs no DP (non-candidates, forced diagonals) and buckets the remaining candidates by the steps to
@@ -423,6 +427,9 @@ int run_class_two_pass(fadehip_ctx *ctx, Slot &s, hipStream_t st, const ClassRun
                 }
                 HIPCHK(ctx, hipMemcpyAsync(s.res.p + s.res_aln_off, s.aln.p, sizeof(fadehip_aln) * (size_t)s.out_cap, hipMemcpyDeviceToHost,
                                            s.tail_stream ? st : sst));
+                // ... and so does rs: select_one wrote every record's byte, pass 2 sets bits in the candidates' only, and a
+                // candidate's final byte comes in its patch entry
+                HIPCHK(ctx, hipMemcpyAsync(s.res.p, c.rs, (size_t)s.n_reads, hipMemcpyDeviceToHost, s.tail_stream ? st : sst));
             }
         }
         // pass 2 + tracebacks + re-traced paths: one persistent launch
@@ -460,8 +467,14 @@ int run_class_two_pass(fadehip_ctx *ctx, Slot &s, hipStream_t st, const ClassRun
             pa.out = c.out;
             pa.out_cap = s.out_cap;
             pa.head = (PatchHead *)s.patch.p;
-            pa.list = (PatchEntry *)((uint8_t *)s.patch.p + sizeof(PatchHead));
+            pa.list = (PatchEntry *)((uint8_t *)s.patch.p + PATCH_LIST_OFF);
             pa.cap = s.patch_cap;
+            pa.rs = c.rs;
+            pa.zb = (const uint32_t *)s.zb();
+            pa.zb_out = (uint32_t *)((uint8_t *)s.patch.p + PATCH_ZB_OFF);
+            pa.zb_next = (uint32_t *)((uint8_t *)s.zblock.p + (s.zoff ^ Slot::ZB_STRIDE));  // the next run's counters, zeroed in passing
+            pa.zb_dwords = (uint32_t)(Slot::ZB_BYTES / 4);
+            s.zb_next_clean = true;
             const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>(64, (s.patch_sent * (uint32_t)(sizeof(PatchEntry) / 4) + 255) / 256));
             hipLaunchKernelGGL(patch_gather_kernel, dim3(blocks), dim3(256), 0, p2st, pa);
             HIPCHK(ctx, hipGetLastError());
@@ -900,7 +913,7 @@ int enqueue_run(fadehip_ctx *ctx, Slot &s) {
         if (s.early) {
             s.patch_cap = (uint32_t)ctx->patch_cap;
             s.patch_sent = (uint32_t)std::min<int64_t>(s.patch_cap, 2 * s.last_cand + 64);  // entries copied with the run; finish_run fetches the rest
-            const size_t bytes = sizeof(PatchHead) + sizeof(PatchEntry) * (size_t)std::max<uint32_t>(s.patch_cap, 1);
+            const size_t bytes = PATCH_LIST_OFF + sizeof(PatchEntry) * (size_t)std::max<uint32_t>(s.patch_cap, 1);
             if (((ctx->early_tail || !s.score_stream) && (rc = ensure_tail(ctx, s))) || (rc = reserve(ctx, s.patch, bytes)) ||
                 (rc = reserve_pinned(ctx, s.h_patch, bytes)))
                 return rc;
@@ -949,7 +962,7 @@ int enqueue_run(fadehip_ctx *ctx, Slot &s) {
     g.stats = s.d_stats();
     g.counters = s.d_counters();
     g.counters64 = s.d_counters64();
-    hipLaunchKernelGGL(gate_kernel, dim3((n + GATE_BLOCK - 1) / GATE_BLOCK), dim3(GATE_BLOCK), 0, st, g);
+    hipLaunchKernelGGL(gate_kernel, dim3((n + GATE_TILE - 1) / GATE_TILE), dim3(GATE_BLOCK), 0, st, g);
     HIPCHK(ctx, hipGetLastError());
     if ((rc = record(ctx, s, &s.ev_gate1))) return rc;
     uint32_t exact[NUM_LISTS];
@@ -973,6 +986,12 @@ int enqueue_run(fadehip_ctx *ctx, Slot &s) {
         if ((rc = run_long(ctx, s, st, cr, std::max(s.long_max_lq, 1)))) return rc;
     }
     if ((rc = record(ctx, s, &s.ev_end))) return rc;
+    if (s.early) {
+        // Early order: the array and rs left behind the score pass, and the gather kernel put the run's counter block in front
+        // of the entries pass 2 wrote and zeroed the other counter block: one copy ends the run.
+        HIPCHK(ctx, hipMemcpyAsync(s.h_patch.p, s.patch.p, PATCH_LIST_OFF + sizeof(PatchEntry) * (size_t)s.patch_sent, hipMemcpyDeviceToHost, st));
+        return 0;
+    }
     // results to the slot's pinned block; the counter block tells the host how many entries of each list are live
     HIPCHK(ctx, hipMemcpyAsync(s.h_zb, s.zb(), Slot::ZB_BYTES, hipMemcpyDeviceToHost, st));
     // the next run's counters, zeroed here, off its critical path (the same batch run again takes them as well)
@@ -980,9 +999,7 @@ int enqueue_run(fadehip_ctx *ctx, Slot &s) {
     s.zb_next_clean = true;
     if (s.device_only) return 0;
     HIPCHK(ctx, hipMemcpyAsync(s.res.p, s.rs.p, (size_t)n, hipMemcpyDeviceToHost, st));  // (pass 2 sets bits in rs: it stays behind it)
-    if (s.early)  // the array left behind the score pass: what pass 2 wrote since comes as the patch list
-        HIPCHK(ctx, hipMemcpyAsync(s.h_patch.p, s.patch.p, sizeof(PatchHead) + sizeof(PatchEntry) * (size_t)s.patch_sent, hipMemcpyDeviceToHost, st));
-    else if (total_bound)
+    if (total_bound)
         HIPCHK(ctx, hipMemcpyAsync(s.res.p + s.res_aln_off, s.aln.p, sizeof(fadehip_aln) * (size_t)total_bound, hipMemcpyDeviceToHost, st));
     return 0;
 }
@@ -1004,6 +1021,7 @@ int finish_run(fadehip_ctx *ctx, Slot &s, int slot) {
     HIPCHK(ctx, hipStreamSynchronize(st));
     for (void *q : s.trash) (void)hipFree(q);  // scratch outgrown while this run was enqueued
     s.trash.clear();
+    if (s.early) memcpy(s.h_zb, s.h_patch.p + PATCH_ZB_OFF, Slot::ZB_BYTES);  // early order: the counter block came in the patch block
     const uint32_t errbits = s.h_counters()[2 * NUM_LISTS];
     if (errbits) {
         s.state = 0;
@@ -1017,20 +1035,24 @@ int finish_run(fadehip_ctx *ctx, Slot &s, int slot) {
         // early order: lay the entries pass 2 wrote over the bulk copy, once, before any view is handed out
         s.early = false;
         const PatchHead head = *(const PatchHead *)s.h_patch.p;
-        const PatchEntry *const list = (const PatchEntry *)(s.h_patch.p + sizeof(PatchHead));
+        const PatchEntry *const list = (const PatchEntry *)(s.h_patch.p + PATCH_LIST_OFF);
         uint8_t *const h_aln = s.res.p + s.res_aln_off;
         if (head.overflow || head.n > s.patch_cap) {
             // more candidates than the list holds: the whole array again (rare; the slot's next run is late, see last_cand)
             HIPCHK(ctx, hipMemcpyAsync(h_aln, s.aln.p, sizeof(fadehip_aln) * (size_t)s.out_cap, hipMemcpyDeviceToHost, st));
+            HIPCHK(ctx, hipMemcpyAsync(s.res.p, s.rs.p, (size_t)n, hipMemcpyDeviceToHost, st));
             HIPCHK(ctx, hipStreamSynchronize(st));
         } else {
             if (head.n > s.patch_sent) {  // more than the run's copy was sized for: the rest of the list
-                HIPCHK(ctx, hipMemcpyAsync((void *)(list + s.patch_sent), (const uint8_t *)s.patch.p + sizeof(PatchHead) + sizeof(PatchEntry) * (size_t)s.patch_sent,
+                HIPCHK(ctx, hipMemcpyAsync((void *)(list + s.patch_sent), (const uint8_t *)s.patch.p + PATCH_LIST_OFF + sizeof(PatchEntry) * (size_t)s.patch_sent,
                                            sizeof(PatchEntry) * (size_t)(head.n - s.patch_sent), hipMemcpyDeviceToHost, st));
                 HIPCHK(ctx, hipStreamSynchronize(st));
             }
             for (uint32_t k = 0; k < head.n; k++)
-                if (list[k].out < s.out_cap) memcpy(h_aln + sizeof(fadehip_aln) * (size_t)list[k].out, &list[k].e, sizeof(fadehip_aln));
+                if (list[k].out < s.out_cap) {
+                    memcpy(h_aln + sizeof(fadehip_aln) * (size_t)list[k].out, &list[k].e, sizeof(fadehip_aln));
+                    if ((uint32_t)list[k].e.read_idx < (uint32_t)n) s.res.p[list[k].e.read_idx] = (uint8_t)list[k].pad;
+                }
         }
         if (ctx->debug)
             fprintf(stderr, "[fadehip] slot %d: patch list of %u entries (%u sent with the run)%s\n", slot, head.n, s.patch_sent,

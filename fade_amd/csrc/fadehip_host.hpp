@@ -41,15 +41,15 @@ struct Slot {
     // on a stream whose CU mask leaves a few CUs (one per XCD by default) to everything else.
     hipStream_t score_stream = nullptr;
     std::vector<uint32_t> score_mask;  // its CU mask (empty: none)
-    // The early order of a run (enqueue_run): the alignment array leaves for the host right behind the score pass, on the
-    // score stream, while pass 2 and the gather of the entries it wrote (patch_gather_kernel) run on `stream`; the copy is
-    // joined into `stream` before the small copies.  The A/B variants (ctx->early_tail) copy on `stream` and run pass 2 on
+    // The early order of a run (enqueue_run): the alignment array and rs leave for the host right behind the score pass, on
+    // the score stream, while pass 2 and the gather of the entries it wrote (patch_gather_kernel) run on `stream`; the copies
+    // are joined into `stream` before the one copy that ends the run (the patch block, which carries the counter block too).  The A/B variants (ctx->early_tail) copy on `stream` and run pass 2 on
     // this stream instead, forked from the score pass's end and joined back; made when a run first takes that order.
     hipStream_t tail_stream = nullptr;
     bool tail_tried = false;
     bool early = false;        // the run in flight took the early order
-    DevBuf patch;              // PatchHead | PatchEntry [patch_cap]
-    PinBuf h_patch;            // its pinned copy: the head and the first patch_sent entries come with the run
+    DevBuf patch;              // PatchHead | the run's counter block (ZB_STRIDE) | PatchEntry [patch_cap]
+    PinBuf h_patch;            // its pinned copy: the head, the counters and the first patch_sent entries come with the run
     uint32_t patch_cap = 0, patch_sent = 0;
     // Two input buffers: while a run works on in[cur], the next batch is uploaded into in[1 - cur] on the copy stream
     // (fadehip_annotate_upload never waits for the run in flight, so H2D leaves the slot's critical path).
@@ -83,8 +83,8 @@ struct Slot {
     //   [0,128) gate counters | [128,512) counters64, one line each | [512 + 48 c, ...) selection counters of class c |
     //   [1024, 1536) stats: STAT_PARTS partial sums of the 8 stats.d counters | [1536, 2560) tickets of the persistent
     //   launches | [2560, ...) PlanOut
-    // Two such blocks, used by alternate runs: a run zeroes the OTHER block behind the copy that ends it, so the next run's
-    // gate follows its upload directly instead of a fill (zb_next_clean: that fill was enqueued and nothing has touched the
+    // Two such blocks, used by alternate runs: a run zeroes the OTHER block (behind the copy that ends it; in the early order
+    // in its gather kernel), so the next run's gate follows its upload directly instead of a fill (zb_next_clean: that fill was enqueued and nothing has touched the
     // block since; otherwise the run fills its own block first, as every run once did).
     DevBuf zblock;
     size_t zoff = 0;             // the block of the run in flight: 0 or ZB_STRIDE
@@ -103,7 +103,7 @@ struct Slot {
     int tickets_used = 0;
     DevBuf work[NUM_LISTS], meta[NUM_LISTS];
     DevBuf lrows;  // sw_long_kernel: previous-row H and F-hat
-    uint8_t *h_zb = nullptr;  // pinned copy of zblock, filled by the D2H that ends a run
+    uint8_t *h_zb = nullptr;  // pinned copy of zblock, filled by the D2H that ends a run (early order: by finish_run, from h_patch)
     const uint32_t *h_counters() const { return (const uint32_t *)(h_zb + ZB_COUNTERS); }
     const unsigned long long *h_counters64() const { return (const unsigned long long *)(h_zb + ZB_C64); }
     const unsigned long long *h_stats() const { return (const unsigned long long *)(h_zb + ZB_STATS); }

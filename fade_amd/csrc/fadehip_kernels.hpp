@@ -227,119 +227,195 @@ struct GateArgs {
     unsigned long long *stats;       // stats.d:45-54: [0] read_count, [1] clipped, [2] sup (the artifact counters come from traceback_kernel)
 };
 
-// A block orders its items by window length (an octet sweeps its longest window).  With every record of a batch sent,
-// one in ten is an item: 1024 records give a block ~100 items to order (256 gave it ~25: 2 % more columns per octet)
-constexpr int GATE_BLOCK = 1024;
+// A block owns a tile of GATE_TILE consecutive records and orders the tile's items by window length (an octet sweeps its
+// longest window).  With every record of a batch sent, one in ten is an item: 1024 records give a block ~100 items to order
+// (256 gave it ~25: 2 % more columns per octet).  A thread takes GATE_QUAD consecutive records of the tile: the fixed
+// fields of a quad come as one load per array, and the dependent loads (cigar_ops, contig_len, contig_base) are issued for
+// the four records together.  (Measured: as fast as a thread per record, alone and on the few CUs it has beside the other
+// slot's score pass -- DESIGN.md §6 "Round 8".)
+constexpr int GATE_TILE = 1024, GATE_QUAD = 4, GATE_BLOCK = GATE_TILE / GATE_QUAD;
+
+// records r0 .. r0 + 3 of one array (r0 a multiple of four): one load where the quad is whole and the array's base is
+// aligned to it, else a load per record below nv (the others read as 0)
+template <typename T>
+__device__ __forceinline__ void gate_load_quad(const T *__restrict__ p, int r0, int nv, bool whole, T (&o)[GATE_QUAD]) {
+    typedef T V __attribute__((ext_vector_type(GATE_QUAD)));
+    if (whole && ((uintptr_t)p & (sizeof(V) - 1)) == 0) {
+        const V v = *reinterpret_cast<const V *>(p + r0);
+#pragma unroll
+        for (int k = 0; k < GATE_QUAD; k++) o[k] = v[k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < GATE_QUAD; k++) o[k] = k < nv ? p[r0 + k] : T(0);
+    }
+}
+// the same for an offset array: entries r0 .. r0 + nv (one more than records)
+__device__ __forceinline__ void gate_load_offsets(const uint32_t *__restrict__ p, int r0, int nv, bool whole, uint32_t (&o)[GATE_QUAD + 1]) {
+    typedef uint32_t V __attribute__((ext_vector_type(GATE_QUAD)));
+    if (whole && ((uintptr_t)p & (sizeof(V) - 1)) == 0) {
+        const V v = *reinterpret_cast<const V *>(p + r0);
+#pragma unroll
+        for (int k = 0; k < GATE_QUAD; k++) o[k] = v[k];
+        o[GATE_QUAD] = p[r0 + GATE_QUAD];
+    } else {
+#pragma unroll
+        for (int k = 0; k <= GATE_QUAD; k++) o[k] = (nv > 0 && k <= nv) ? p[r0 + k] : 0u;
+    }
+}
+
 __global__ __launch_bounds__(GATE_BLOCK) void gate_kernel(GateArgs a) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int tile0 = blockIdx.x * GATE_TILE, r0 = tile0 + GATE_QUAD * (int)threadIdx.x;
+    // a tile cut short by n_reads takes the per-record loads and stores throughout: nothing past n_reads is touched
+    const bool whole = tile0 + GATE_TILE <= a.n_reads;
+    const int nv = whole ? GATE_QUAD : max(0, min(GATE_QUAD, a.n_reads - r0));  // records of this thread
     // per-thread contribution to the batch counters; reduced per wave before touching memory
     unsigned long long cells = 0, seq_bytes = 0, ck_bytes = 0;
-    uint32_t lr_for_max = 0, errbits = 0, st_bits = 0, oversize = 0;
-    int cls = -1;
-    Work w;
-    Meta m;
-    if (i < a.n_reads) {
-        uint32_t c0 = a.cigar_off[i], c1 = a.cigar_off[i + 1];
-        const uint32_t so0 = a.seq_off[i], so1 = a.seq_off[i + 1];
-        const int32_t lq = a.l_seq[i];
-        // the caller's offsets are checked before anything is read through them (upload no longer walks the records
-        // when the caller passes its bounds): a record that fails is skipped and the batch is failed at results
-        bool bad_rec = c0 > c1 || c1 > a.n_cigar_ops || so0 > so1 || so1 > a.n_seq_bytes || lq < 0;
-        if (bad_rec) { errbits |= 64u; c1 = c0; }
+    uint32_t errbits = 0, st_cnt = 0;  // st_cnt: reads | clipped << 10 | sup << 20 of the thread's records
+    int32_t tid[GATE_QUAD], pos[GATE_QUAD], lq[GATE_QUAD];
+    uint16_t flag[GATE_QUAD];
+    uint8_t has_sa[GATE_QUAD];
+    uint32_t co[GATE_QUAD + 1], so[GATE_QUAD + 1];
+    gate_load_offsets(a.cigar_off, r0, nv, whole, co);
+    gate_load_offsets(a.seq_off, r0, nv, whole, so);
+    gate_load_quad(a.l_seq, r0, nv, whole, lq);
+    gate_load_quad(a.flag, r0, nv, whole, flag);
+    gate_load_quad(a.has_sa, r0, nv, whole, has_sa);
+    gate_load_quad(a.tid, r0, nv, whole, tid);
+    gate_load_quad(a.pos, r0, nv, whole, pos);
+    // the caller's offsets are checked before anything is read through them (upload no longer walks the records
+    // when the caller passes its bounds): a record that fails is skipped and the batch is failed at results
+    uint32_t n_ops[GATE_QUAD], max_ops = 0;
+    bool bad_rec[GATE_QUAD], out_of_bounds[GATE_QUAD];
+#pragma unroll
+    for (int k = 0; k < GATE_QUAD; k++) {
+        const bool v = k < nv;
+        bad_rec[k] = v && (co[k] > co[k + 1] || co[k + 1] > a.n_cigar_ops || so[k] > so[k + 1] || so[k + 1] > a.n_seq_bytes || lq[k] < 0);
+        if (bad_rec[k]) errbits |= 64u;
+        n_ops[k] = (v && !bad_rec[k]) ? co[k + 1] - co[k] : 0u;
+        max_ops = max(max_ops, n_ops[k]);
         // the caller's l_seq_min / l_seq_max chose the row classes and score kernels of the run: a record with bases outside
         // them fails the batch, and is never scored by a kernel with fewer rows than its read
-        const bool out_of_bounds = !bad_rec && so1 > so0 && (lq < a.l_seq_lo || lq > a.l_seq_hi);
-        if (out_of_bounds) errbits |= 32u;
-        // anno.d:61: count S ops; util.d:37-62 parse_clips; dhtslib alignedLength (M,D,N,=,X)
-        int n_soft = 0;
-        uint32_t clipL = 0, clipR = 0;
-        int64_t aligned = 0;
-        bool first = true;
-        for (uint32_t k = c0; k < c1; k++) {
-            const uint32_t op = a.cigar_ops[k] & 15u, len = a.cigar_ops[k] >> 4;
-            if (op == 4) n_soft++;
-            if (FADEHIP_OP_CONSUMES_REF(op)) aligned += len;
+        out_of_bounds[k] = v && !bad_rec[k] && so[k + 1] > so[k] && (lq[k] < a.l_seq_lo || lq[k] > a.l_seq_hi);
+        if (out_of_bounds[k]) errbits |= 32u;
+    }
+    // anno.d:61: count S ops; util.d:37-62 parse_clips; dhtslib alignedLength (M,D,N,=,X) -- the four walks side by side, up
+    // to the longest, so that four cigar_ops loads are in flight per step
+    int n_soft[GATE_QUAD];
+    uint32_t clipL[GATE_QUAD], clipR[GATE_QUAD];
+    int64_t aligned[GATE_QUAD];
+    bool first[GATE_QUAD];
+#pragma unroll
+    for (int k = 0; k < GATE_QUAD; k++) { n_soft[k] = 0; clipL[k] = clipR[k] = 0; aligned[k] = 0; first[k] = true; }
+    for (uint32_t j = 0; j < max_ops; j++) {
+        uint32_t c[GATE_QUAD];
+#pragma unroll
+        for (int k = 0; k < GATE_QUAD; k++) c[k] = j < n_ops[k] ? a.cigar_ops[co[k] + j] : 0u;
+#pragma unroll
+        for (int k = 0; k < GATE_QUAD; k++) {
+            if (j >= n_ops[k]) continue;
+            const uint32_t op = c[k] & 15u, len = c[k] >> 4;
+            if (op == 4) n_soft[k]++;
+            if (FADEHIP_OP_CONSUMES_REF(op)) aligned[k] += len;
             if (op == 5) continue;  // util.d:44-45 skips hard clips
             const bool is_sc = (op == 4);
-            if (first && !is_sc) first = false;
-            else if (first && is_sc) clipL = len;
-            else if (is_sc) clipR = len;
+            if (first[k] && !is_sc) first[k] = false;
+            else if (first[k] && is_sc) clipL[k] = len;
+            else if (is_sc) clipR[k] = len;
         }
-        const uint32_t flag = a.flag[i];
-        uint8_t rs = 0;
-        bool want = false;
-        if (!((flag & 4u) || n_soft == 0) && !bad_rec) {          // anno.d:61-65
-            if (clipL != 0 || clipR != 0) rs |= 1;    // anno.d:69-70
-            if (a.has_sa[i]) rs |= 32;                // anno.d:73-74
+    }
+    uint32_t rs4 = 0;
+    bool want[GATE_QUAD];
+#pragma unroll
+    for (int k = 0; k < GATE_QUAD; k++) {
+        uint32_t rs = 0;
+        want[k] = false;
+        if (k < nv && !((flag[k] & 4u) || n_soft[k] == 0) && !bad_rec[k]) {  // anno.d:61-65
+            if (clipL[k] != 0 || clipR[k] != 0) rs |= 1;  // anno.d:69-70
+            if (has_sa[k]) rs |= 32;                      // anno.d:73-74
             // analysis.d:34: only clips strictly longer than the floor are re-aligned
-            want = (clipL != 0 && (int64_t)clipL > a.floor_len) || (clipR != 0 && (int64_t)clipR > a.floor_len);
+            want[k] = (clipL[k] != 0 && (int64_t)clipL[k] > a.floor_len) || (clipR[k] != 0 && (int64_t)clipR[k] > a.floor_len);
         }
-        a.rs[i] = rs;
-        st_bits = 4u | (rs & 1u) | ((rs >> 4) & 2u);  // bit2 read, bit0 clipped, bit1 sup
-        const int32_t tid = a.tid[i];
-        if (out_of_bounds) want = false;
-        if (want && (tid < 0 || tid >= a.n_contigs)) {
+        rs4 |= rs << (8 * k);
+        if (k < nv) st_cnt += 1u | ((rs & 1u) << 10) | ((rs >> 5) << 20);  // read, clipped, sup
+        if (out_of_bounds[k]) want[k] = false;
+        if (want[k] && (tid[k] < 0 || tid[k] >= a.n_contigs)) {
             errbits |= 1u;  // mapped record without a valid contig
-            want = false;
+            want[k] = false;
         }
-        if (want && lq > 0 && so1 - so0 < (uint32_t)(lq + 1) / 2u) {
+        if (want[k] && lq[k] > 0 && so[k + 1] - so[k] < (uint32_t)(lq[k] + 1) / 2u) {
             errbits |= 8u;  // a record that must be re-aligned came without its bases
-            want = false;
+            want[k] = false;
         }
-        if (want && lq > 0) {
-            // analysis.d:45-59
-            const int64_t pos = a.pos[i];
-            int64_t start = pos - a.window;
-            if (start < 0) start = 0;
-            int64_t end = pos + aligned + a.window;
-            if (end > a.contig_len[tid]) end = a.contig_len[tid];
-            const int64_t lr = end - start;
-            if (lr > 0) {
-                cls = list_of_len(lq, lr);
-                // a read or window beyond the kernels' limits is left un-re-aligned (its rs keeps the sc / sup bits) and counted
-                if (cls < 0) oversize = 1u;  // read longer than MAX_LONG_QUERY
-                else if (lr > a.max_ref_len) { oversize = 1u; cls = -1; }  // window longer than max_ref_len
-                else if (cls != LONG_LIST ? lr > a.wave_lr_bound : (lr > a.long_lr_bound || lq > a.long_lq_bound)) {
-                    errbits |= 16u;  // the caller's ref_span_bound was too small
-                    cls = -1;
-                }
-                else {
-                    cells = (unsigned long long)lq * (unsigned long long)lr;
-                    seq_bytes = (unsigned long long)((lq + 1) / 2 + (lr + 1) / 2);
-                    ck_bytes = cls == LONG_LIST ? 0ull : (unsigned long long)lq * (unsigned long long)(lr >> CK_SHIFT) * 4ull;  // H + E-hat, int16 each
-                    lr_for_max = (uint32_t)lr;
-                    w.r_base = a.contig_base[tid] + (uint64_t)start;
-                    w.q_base = so0 * 2u;
-                    w.lq = (uint32_t)lq;
-                    w.lr = (uint32_t)lr;
-                    w.idx = (uint32_t)i;
-                    w.flags = 1u;
-                    w.out = 0;
-                    m.win_start = start;
-                    m.clip_left = (int32_t)clipL;
-                    m.clip_right = (int32_t)clipR;
-                    m.aligned_len = (int32_t)aligned;
-                    m.pad[0] = m.pad[1] = m.pad[2] = 0;
-                }
-            }
+        want[k] = want[k] && lq[k] > 0;
+    }
+    if (whole && ((uintptr_t)a.rs & 3) == 0) *reinterpret_cast<uint32_t *>(a.rs + r0) = rs4;
+    else {
+#pragma unroll
+        for (int k = 0; k < GATE_QUAD; k++)
+            if (k < nv) a.rs[r0 + k] = (uint8_t)(rs4 >> (8 * k));
+    }
+    // the contigs of the wanted records, the loads again side by side
+    int64_t c_len[GATE_QUAD];
+    uint64_t c_base[GATE_QUAD];
+#pragma unroll
+    for (int k = 0; k < GATE_QUAD; k++) {
+        c_len[k] = want[k] ? a.contig_len[tid[k]] : 0;
+        c_base[k] = want[k] ? a.contig_base[tid[k]] : 0;
+    }
+    int cls[GATE_QUAD];
+    uint32_t lr_of[GATE_QUAD];
+    int64_t start_of[GATE_QUAD];
+#pragma unroll
+    for (int k = 0; k < GATE_QUAD; k++) {
+        cls[k] = -1;
+        lr_of[k] = 0;
+        start_of[k] = 0;
+        if (!want[k]) continue;
+        // analysis.d:45-59
+        int64_t start = (int64_t)pos[k] - a.window;
+        if (start < 0) start = 0;
+        int64_t end = (int64_t)pos[k] + aligned[k] + a.window;
+        if (end > c_len[k]) end = c_len[k];
+        const int64_t lr = end - start;
+        if (lr <= 0) continue;
+        int c = list_of_len(lq[k], lr);
+        // a read or window beyond the kernels' limits is left un-re-aligned (its rs keeps the sc / sup bits) and counted
+        bool oversize = false;
+        if (c < 0) oversize = true;  // read longer than MAX_LONG_QUERY
+        else if (lr > a.max_ref_len) { oversize = true; c = -1; }  // window longer than max_ref_len
+        else if (c != LONG_LIST ? lr > a.wave_lr_bound : (lr > a.long_lr_bound || lq[k] > a.long_lq_bound)) {
+            errbits |= 16u;  // the caller's ref_span_bound was too small
+            c = -1;
+        } else {
+            cells += (unsigned long long)lq[k] * (unsigned long long)lr;
+            seq_bytes += (unsigned long long)((lq[k] + 1) / 2 + (lr + 1) / 2);
+            ck_bytes += c == LONG_LIST ? 0ull : (unsigned long long)lq[k] * (unsigned long long)(lr >> CK_SHIFT) * 4ull;  // H + E-hat, int16 each
+            lr_of[k] = (uint32_t)lr;
+            start_of[k] = start;
         }
+        if (oversize) atomicAdd(&a.counters[2 * NUM_LISTS + 2], 1u);  // rare by construction
+        cls[k] = c;
     }
     // block-aggregated append: slots are first reserved in LDS, then one global atomic per block and
     // class (per-lane or even per-wave atomics on one address serialise at ~12 ns each and dominated
     // this kernel)
     __shared__ uint32_t s_cnt[NUM_LISTS], s_base[NUM_LISTS], s_maxlr[NUM_LISTS], s_err, s_items, s_maxlq, s_out_base;
     __shared__ unsigned long long s_cells, s_bytes, s_ck;
-    __shared__ uint32_t s_key[GATE_BLOCK], s_rank[GATE_BLOCK], s_stat[3];
+    __shared__ uint32_t s_key[GATE_TILE], s_rank[GATE_TILE], s_stat[3];
     if (threadIdx.x < NUM_LISTS) { s_cnt[threadIdx.x] = 0; s_maxlr[threadIdx.x] = 0; }
     if (threadIdx.x == 0) { s_err = 0; s_cells = 0; s_bytes = 0; s_ck = 0; s_items = 0; s_maxlq = 0; s_stat[0] = s_stat[1] = s_stat[2] = 0; }
     __syncthreads();
-    uint32_t compact = 0;
-    if (cls >= 0) {
-        atomicAdd(&s_cnt[cls], 1u);
-        atomicMax(&s_maxlr[cls], lr_for_max);
-        if (cls == LONG_LIST) atomicMax(&s_maxlq, w.lq);
-        compact = atomicAdd(&s_items, 1u);
-        s_key[compact] = ((uint32_t)cls << 24) | lr_for_max;  // lr <= 16000
+    uint32_t compact[GATE_QUAD];
+#pragma unroll
+    for (int k = 0; k < GATE_QUAD; k++) {
+        compact[k] = 0;
+        if (cls[k] >= 0) {
+            atomicAdd(&s_cnt[cls[k]], 1u);
+            atomicMax(&s_maxlr[cls[k]], lr_of[k]);
+            if (cls[k] == LONG_LIST) atomicMax(&s_maxlq, (uint32_t)lq[k]);
+            compact[k] = atomicAdd(&s_items, 1u);
+            s_key[compact[k]] = ((uint32_t)cls[k] << 24) | lr_of[k];  // lr <= 16000
+        }
     }
     if (__ballot(cells != 0)) {
         for (int sh = 32; sh >= 1; sh >>= 1) {
@@ -354,14 +430,15 @@ __global__ __launch_bounds__(GATE_BLOCK) void gate_kernel(GateArgs a) {
         }
     }
     if (errbits) atomicOr(&s_err, errbits);
-    if (oversize) atomicAdd(&a.counters[2 * NUM_LISTS + 2], 1u);  // rare by construction
     {
         // stats.d:45-54, the part known here: reads, clipped, supplementary — one LDS add per wave and counter
-        const unsigned long long m_read = __ballot(st_bits & 4u), m_sc = __ballot(st_bits & 1u), m_sup = __ballot(st_bits & 2u);
+        // (three 10-bit fields: a wave has at most 256 records)
+        for (int sh = 32; sh >= 1; sh >>= 1) st_cnt += __shfl_xor(st_cnt, sh, 64);
         if ((threadIdx.x & 63) == 0) {
-            atomicAdd(&s_stat[0], (uint32_t)__popcll(m_read));
-            if (m_sc) atomicAdd(&s_stat[1], (uint32_t)__popcll(m_sc));
-            if (m_sup) atomicAdd(&s_stat[2], (uint32_t)__popcll(m_sup));
+            const uint32_t n_read = st_cnt & 1023u, n_sc = (st_cnt >> 10) & 1023u, n_sup = st_cnt >> 20;
+            if (n_read) atomicAdd(&s_stat[0], n_read);
+            if (n_sc) atomicAdd(&s_stat[1], n_sc);
+            if (n_sup) atomicAdd(&s_stat[2], n_sup);
         }
     }
     __syncthreads();
@@ -385,23 +462,41 @@ __global__ __launch_bounds__(GATE_BLOCK) void gate_kernel(GateArgs a) {
     // a wave sweep max(lr) + 15 steps, so neighbours of equal length waste none (C2: 339 -> 323 columns per
     // octet).  Rank = items of the same class with a longer window (ties by list position); a block holds
     // ~100 items for 10 % clipped reads, and only threads below the item count loop.
-    if (threadIdx.x < s_items) {
-        const uint32_t me = s_key[threadIdx.x];
+    {
         const uint32_t n = s_items;
-        uint32_t r = 0;
-        for (uint32_t k = 0; k < n; k++) {
-            const uint32_t o = s_key[k];
-            r += ((o ^ me) >> 24) == 0 && (o > me || (o == me && k < threadIdx.x));
+        for (uint32_t t = threadIdx.x; t < n; t += GATE_BLOCK) {
+            const uint32_t me = s_key[t];
+            uint32_t r = 0;
+            for (uint32_t k = 0; k < n; k++) {
+                const uint32_t o = s_key[k];
+                r += ((o ^ me) >> 24) == 0 && (o > me || (o == me && k < t));
+            }
+            s_rank[t] = r;
         }
-        s_rank[threadIdx.x] = r;
     }
     __syncthreads();
-    if (cls >= 0) {
-        const uint32_t slot = s_base[cls] + s_rank[compact];
-        w.out = s_out_base + compact;
-        if (slot < a.list_cap[cls] && w.out < a.out_cap) {
-            a.work[cls][slot] = w;
-            a.meta[cls][slot] = m;
+#pragma unroll
+    for (int k = 0; k < GATE_QUAD; k++) {
+        if (cls[k] < 0) continue;
+        const uint32_t slot = s_base[cls[k]] + s_rank[compact[k]];
+        const uint32_t out = s_out_base + compact[k];
+        if (slot < a.list_cap[cls[k]] && out < a.out_cap) {
+            Work w;
+            w.r_base = c_base[k] + (uint64_t)start_of[k];
+            w.q_base = so[k] * 2u;
+            w.lq = (uint32_t)lq[k];
+            w.lr = lr_of[k];
+            w.idx = (uint32_t)(r0 + k);
+            w.flags = 1u;
+            w.out = out;
+            Meta m;
+            m.win_start = start_of[k];
+            m.clip_left = (int32_t)clipL[k];
+            m.clip_right = (int32_t)clipR[k];
+            m.aligned_len = (int32_t)aligned[k];
+            m.pad[0] = m.pad[1] = m.pad[2] = 0;
+            a.work[cls[k]][slot] = w;
+            a.meta[cls[k]][slot] = m;
         } else atomicOr(&a.counters[2 * NUM_LISTS], 32u);  // more items than the host's bound: never written, reported at collect
     }
 }
@@ -2240,7 +2335,12 @@ __global__ void traceback_kernel(TbArgs a) {
 // called for list members only, and every way out of it either stores the member's entry (a complete CIGAR, or n_ops = 0
 // for a path with more than 10 ops, traced to its end or abandoned before step T0) or returns 8, after which the same wave
 // traces the member again from further back until step 0, where no path can leave its steps.  So after pass 2 every list
-// member's entry is final and no other entry has changed since the score pass.
+// member's entry is final and no other entry has changed since the score pass.  The same holds for rs: select_one writes a
+// record's byte in the score pass, pass 2 sets bits in the bytes of list members only, so rs leaves with the array and a
+// member's final byte rides in its patch entry.  The run's counter block, final behind pass 2 as well, comes in the same
+// buffer between the head and the entries: an early run ends with ONE copy to the host.  The gather also zeroes the slot's
+// OTHER counter block for the next run (idle since the slot's previous results returned): a fill kernel of its own beside
+// the other slot's score pass takes 30 - 200 us to find a wave slot, wherever in the run it is enqueued.
 struct PatchHead {
     uint32_t n;         // candidates on the lists (entries [0, min(n, cap)) of the list are live)
     uint32_t overflow;  // n exceeds the list's capacity: the host fetches the whole array again
@@ -2248,7 +2348,7 @@ struct PatchHead {
 };
 struct PatchEntry {     // 128 bytes
     uint32_t out;       // entry of the result array (0xffffffff: none, skipped by the host)
-    uint32_t pad;
+    uint32_t pad;       // rs of the entry's record (e.read_idx) as pass 2 left it
     fadehip_aln e;
 };
 static_assert(sizeof(fadehip_aln) % 4 == 0 && sizeof(PatchEntry) == 8 + sizeof(fadehip_aln), "the gather copies dwords");
@@ -2262,6 +2362,11 @@ struct PatchArgs {
     PatchHead *head;
     PatchEntry *list;           // [cap]
     uint32_t cap;
+    const uint8_t *rs;
+    const uint32_t *zb;         // the run's counter block and where its copy goes (between head and list), in dwords
+    uint32_t *zb_out;
+    uint32_t *zb_next;          // the slot's other counter block: zeroed here
+    uint32_t zb_dwords;
 };
 
 // a thread per dword of the list: entry p is the (p - first[b])-th candidate of bucket b, buckets in order
@@ -2277,6 +2382,11 @@ __global__ __launch_bounds__(256) void patch_gather_kernel(PatchArgs a) {
         a.head->overflow = total > a.cap ? 1u : 0u;
         a.head->pad[0] = a.head->pad[1] = 0;
     }
+    if (blockIdx.x == 0)
+        for (uint32_t d = threadIdx.x; d < a.zb_dwords; d += blockDim.x) {
+            a.zb_out[d] = a.zb[d];
+            a.zb_next[d] = 0;
+        }
     uint32_t *const dst = (uint32_t *)a.list;
     for (uint64_t at = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; at < (uint64_t)live * ENTRY_DW; at += (uint64_t)gridDim.x * blockDim.x) {
         const uint32_t p = (uint32_t)(at / ENTRY_DW), d = (uint32_t)(at % ENTRY_DW);
@@ -2287,7 +2397,7 @@ __global__ __launch_bounds__(256) void patch_gather_kernel(PatchArgs a) {
         const uint32_t o = a.work[c.src].out;
         uint32_t v;
         if (o >= a.out_cap) v = d == 0 ? 0xffffffffu : 0u;  // (the gate hands out entries below out_cap only)
-        else v = d == 0 ? o : d == 1 ? 0u : ((const uint32_t *)(a.out + o))[d - 2];
+        else v = d == 0 ? o : d == 1 ? (uint32_t)a.rs[a.work[c.src].idx] : ((const uint32_t *)(a.out + o))[d - 2];
         dst[at] = v;
     }
 }

@@ -1,6 +1,7 @@
 """Condense a rocprofv3 --kernel-trace --memory-copy-trace run (csv) into a per-stream timeline of the last N ms."""
 import csv
 import glob
+import re
 import sys
 
 d = sys.argv[1]
@@ -10,7 +11,7 @@ mf = glob.glob(d + "/**/*_memory_copy_trace.csv", recursive=True)
 ev = []
 for r in csv.DictReader(open(kf)):
     name = r["Kernel_Name"]
-    short = ("score" if "kernel<" in name and ", 1>" in name else "pass2" if "sw_pk_kernel" in name else
+    short = ("score" if re.search(r"kernel<\d+, 1[,>]", name) else "pass2" if "sw_pk_kernel" in name else
              name.split("(")[0].split("::")[-1][:14])
     ev.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), "K", short, r.get("Stream_Id", "?")))
 if mf:
