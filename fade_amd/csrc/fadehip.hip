@@ -165,16 +165,20 @@ const void *sw64_kernel(int R) {
 // (pass 2 re-computes from step 0): the caller asks only for launches that leave none.
 // The kernel sweeps in the column-drift frame (sw_pk_kernel<..., FRAME>: one packed instruction less per cell) when the
 // context asks for it and the launch's `steps` sweep steps keep every framed value below the f16 infinity (frame_fits, from
-// the scoring and the kernel's rows); *framed says which was taken.
+// the scoring and the kernel's rows).  Three tiers: the frame whose drift follows the row as well (sw_pk_kernel<..., FRAME, DIAG>:
+// one more instruction less per cell; FADEHIP_SCORE_DIAG=0 turns only this one off) where its own bound holds (diag_fits), else the
+// column-drift frame, else the unframed kernel.  *framed: 0 unframed, 1 column drift, 2 row and step drift.
 template <int R8>
-const void *g8_pick(const fadehip_ctx *ctx, int steps, bool *framed) {
+const void *g8_pick(const fadehip_ctx *ctx, int steps, int *framed) {
     const ScoreTab &sc = ctx->sc;
-    *framed = ctx->score_frame && frame_fits(std::max(std::max(sc.match, sc.mismatch), 0), sc.open, sc.ext, 8 * R8, steps);
-    return *framed ? (const void *)sw_pk_kernel<R8, 1, false, 8, false, 0, true> : (const void *)sw_pk_kernel<R8, 1, false, 8>;
+    const int match = std::max(std::max(sc.match, sc.mismatch), 0);
+    *framed = !ctx->score_frame ? 0 : ctx->score_diag && diag_fits(match, sc.open, sc.ext, 8 * R8, steps) ? 2 : frame_fits(match, sc.open, sc.ext, 8 * R8, steps) ? 1 : 0;
+    return *framed == 2 ? (const void *)sw_pk_kernel<R8, 1, false, 8, false, 0, true, true>
+           : *framed ? (const void *)sw_pk_kernel<R8, 1, false, 8, false, 0, true> : (const void *)sw_pk_kernel<R8, 1, false, 8>;
 }
-const void *g8_kernel(const fadehip_ctx *ctx, int cls, int max_lq, int steps, bool *framed) {
+const void *g8_kernel(const fadehip_ctx *ctx, int cls, int max_lq, int steps, int *framed) {
     const int score_g8 = ctx->score_g8, rows16 = 16 * class_rows(cls);
-    *framed = false;
+    *framed = 0;
     if (!score_g8 || max_lq > rows16) return nullptr;
     if (max_lq <= 40 && rows16 > 40) return g8_pick<5>(ctx, steps, framed);
     if (max_lq <= 56 && rows16 > 56) return g8_pick<7>(ctx, steps, framed);
@@ -351,7 +355,7 @@ int run_class_two_pass(fadehip_ctx *ctx, Slot &s, hipStream_t st, const ClassRun
     uint32_t *const sel_counters = s.d_sel(cls);
     const void *const score_fn = sw_kernel(cls, 1, p.longw), *const trace_fn = sw_kernel(cls, p.mode2, p.longw);
     if (!score_fn || !trace_fn) return set_err(ctx, FADEHIP_E_INVALID, "bad class %d", cls);
-    bool framed = false;  // (the plan's blocks of four steps cover every window of the class list: what sizes LDS bounds the drift)
+    int framed = 0;  // (the plan's blocks of four steps cover every window of the class list: what sizes LDS bounds the drift)
     const void *const g8_fn = !p.longw && p.n_ck == 0 ? g8_kernel(ctx, cls, s.max_lq, 4 * p.n_blocks1, &framed) : nullptr;
     if (p.total_oct > p.chunk_oct) s.early = false;  // (one patch list per run: a run without snapshots is one chunk anyway)
     const bool early = s.early;
@@ -404,7 +408,7 @@ int run_class_two_pass(fadehip_ctx *ctx, Slot &s, hipStream_t st, const ClassRun
             waves1 = std::max(1, std::min(octs, (int)((int64_t)res * mine / cus)));
             a.ticket = s.d_ticket(s.tickets_used++);
         } else if (g8_fn) {  // sixteen alignments per wavefront, two groups' windows in LDS
-            if (ctx->debug && o0 == 0) fprintf(stderr, "[fadehip] class of %d rows: score pass on eight-lane groups (longest read of the batch: %d), column-drift frame %s\n", 16 * class_rows(cls), s.max_lq, framed ? "on" : "off");
+            if (ctx->debug && o0 == 0) fprintf(stderr, "[fadehip] class of %d rows: score pass on eight-lane groups (longest read of the batch: %d), column-drift frame %s, row drift %s\n", 16 * class_rows(cls), s.max_lq, framed ? "on" : "off", framed == 2 ? "on" : "off");
             fn1 = g8_fn;
             waves1 = (n + 15) / 16;
             lds = 2 * p.lds1;

@@ -264,6 +264,7 @@ int fadehip_create(fadehip_ctx **out, int device, const fadehip_params *params) 
     if (const char *kv = getenv("FADEHIP_SCORE_PERSIST")) ctx->score_persist = atoi(kv) != 0;
     if (const char *kv = getenv("FADEHIP_SCORE_G8")) ctx->score_g8 = atoi(kv);
     if (const char *kv = getenv("FADEHIP_SCORE_FRAME")) ctx->score_frame = atoi(kv) != 0;
+    if (const char *kv = getenv("FADEHIP_SCORE_DIAG")) ctx->score_diag = atoi(kv) != 0;
     if (const char *kv = getenv("FADEHIP_EARLY_COPY")) ctx->early_copy = atoi(kv) != 0;
     if (const char *kv = getenv("FADEHIP_EARLY_TAIL")) ctx->early_tail = strcmp(kv, "masked") == 0 ? 1 : strcmp(kv, "plain") == 0 ? 2 : 0;
     if (const char *kv = getenv("FADEHIP_PATCH_CAP")) ctx->patch_cap = std::max(0, std::min(atoi(kv), 1 << 20));

@@ -204,6 +204,7 @@ struct fadehip_ctx {
     bool blocking_sync = false;  // FADEHIP_BLOCKING_SYNC=1: waits for the device sleep
     int split_cus = 0;  // FADEHIP_BAM_SPLIT=j: the file path's record kernels get j CUs of every XCD, the compressor the others
     bool score_frame = true;     // the eight-lane score pass in the column-drift frame where the launch fits it (g8_kernel; FADEHIP_SCORE_FRAME=0: never)
+    bool score_diag = true;      // ... with the drift following the row too where that frame's own bound holds (g8_pick; FADEHIP_SCORE_DIAG=0: never)
     bool score_persist = false;  // FADEHIP_SCORE_PERSIST=1: the score pass as a persistent launch (A/B variant)
     int p2_waves_fixed = 0;    // FADEHIP_P2_WAVES: waves of the persistent pass-2 launch (0: adaptive, see run_class_two_pass)
     bool early_copy = true;    // FADEHIP_EARLY_COPY=0: no run takes the early order (enqueue_run)

@@ -1497,6 +1497,11 @@ __device__ __forceinline__ uint32_t bfi(uint32_t mask, uint32_t a, uint32_t b) {
     asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(d) : "v"(mask), "v"(a), "v"(b));
     return d;
 }
+__device__ __forceinline__ uint32_t bfi_s(uint32_t mask, uint32_t a, uint32_t b) {  // the same, a wave-uniform (SGPR)
+    uint32_t d;
+    asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(d) : "v"(mask), "s"(a), "v"(b));
+    return d;
+}
 
 // Window staging: scale * class of the base whose complemented code is x, for the 16 codes: 8 bytes for codes 0-7, 8 for codes 8-15
 __host__ __device__ constexpr uint64_t make_cls_rc(uint32_t scale, int half) {
@@ -1538,6 +1543,18 @@ __host__ __device__ constexpr bool frame_fits(int match, int open, int ext, int 
     return match >= 0 && ext >= 0 && open >= ext && steps >= 0 &&
            8ll * match * rows + 8ll * ext * ((long long)steps + lg + 1) + 8ll * open + 8 * 15 < 0x7c00;
 }
+// The row-and-step drift frame (sw_pk_kernel<..., FRAME, DIAG>, below) holds for a launch when all of these do: the largest
+// max3 operand (the highest score of `rows` rows, the drift D(R - 1, steps), the hat offset, one table entry) and the largest
+// offset key (64 score + 63 + 128 ext per row pair of a lane) stay below the f16 infinity, a table entry 8 (W' + ext) is a
+// byte, and open >= ext >= 0.
+constexpr int DIAG_C0 = 2;  // D(r, t) = 8 ext (t + r + DIAG_C0): every stored H, E and table operand stays non-negative
+__host__ __device__ constexpr bool diag_fits(int match, int open, int ext, int rows, int steps, int lg = 8) {
+    const int R = rows / lg;
+    return match >= 0 && ext >= 0 && open >= ext && steps >= 0 &&
+           8ll * match * rows + 8ll * ext * ((long long)steps + R - 1 + DIAG_C0) + 8ll * open + 8 * (15 + ext) < 0x7c00 &&
+           64ll * match * rows + 63 + 128ll * ext * (R - 1) / 2 < 0x7c00 &&
+           8 * (15 + ext) <= 255;
+}
 __host__ __device__ constexpr int pk_min_waves(int R, int MODE, int LG = 16, int WV = 0) { return WV ? WV : MODE != 1 ? 1 : (LG == 8 ? (R <= 13 ? 4 : 3) : (R <= 10 ? 4 : (R <= 16 ? 3 : 2))); }
 
 // LONGW: the launch may hold windows longer than one staged chunk (CH_COLS columns); the sweep then re-stages at chunk
@@ -1562,10 +1579,23 @@ __host__ __device__ constexpr int pk_min_waves(int R, int MODE, int LG = 16, int
 // 8 (H + d) overflows; the two key constants (even / odd row) are per-lane registers refreshed once per step.  Five
 // instructions per step and lane buy one per cell.  Every operand of v_pk_maximum3_f16 has to stay below 0x7c00, which
 // bounds the columns of a launch: frame_fits() above; the host falls back to the unframed kernel beyond it.
+// DIAG (a FRAME kernel; FADEHIP_SCORE_DIAG): the drift follows the row too.  Every value of lane-local row r at
+// sweep step t carries D(r, t) = 8 ext (t + r + DIAG_C0), which is wave-uniform: within a lane the step and the column differ
+// by a constant, so E's decay stays free, and D(r, t) - 8 ext = D(r - 1, t), so F's decay is free as well:
+//   Fn = max(hu, fu)                     (no subtraction: the row's chain is max -> max3 -> sub)
+//   Dp = hd + 8 (W' + ext)               (D(r, t) - D(r - 1, t - 1) = 2 * 8 ext, T sits at D - 8 ext: the table holds the + 8 ext)
+//   En = max3(hl, Eh, floorE(r + t))     (floorE = D(r, t) + 8 open - 8 ext, a scalar per row and step)
+//   k  = 8 H + C_parity(t)               (two scalars per step; both rows of pair p carry the true key + 128 ext p, a multiple of
+//                                         64 that leaves the key's six low bits alone and comes off GH once after the sweep)
+// hu and fu that arrive from the lane to the left lose (R - 1) 8 ext, in the DPP move itself (v_sub_u32_dpp over both halves:
+// neither value ever falls below (R - 1) 8 ext, so nothing borrows); the first lane of a group takes D(0, t) - 8 ext from a
+// scalar.  The per-step frame upkeep is scalar.
+// diag_fits() above bounds the launch; beyond it the host takes the column-drift frame, then the unframed kernel.
 // PERSIST (FADEHIP_SCORE_PERSIST, MODE 1 only, the other A/B variant): the score pass as a persistent launch whose waves draw
 // octets from a ticket.  Both variants are instantiations of their own: the ordinary score pass keeps its registers.
-template <int R, int MODE, bool LONGW = false, int LG = 16, bool PERSIST = false, int WV = 0, bool FRAME = false>
+template <int R, int MODE, bool LONGW = false, int LG = 16, bool PERSIST = false, int WV = 0, bool FRAME = false, bool DIAG = false>
 __global__ __launch_bounds__(64, pk_min_waves(R, MODE, LG, WV)) void sw_pk_kernel(SwArgs a) {
+    static_assert(!DIAG || FRAME, "the row-and-step drift is a variant of the framed sweep");
     static_assert(LG == 16 || (LG == 8 && MODE == 1 && !LONGW), "eight-lane groups exist for the score pass only");
     static_assert(!FRAME || (LG == 8 && MODE == 1 && !LONGW && !PERSIST), "the column-drift frame exists for the eight-lane score pass only");
     static_assert(!PERSIST || MODE == 1, "the persistent variant is a score pass");
@@ -1592,6 +1622,12 @@ __global__ __launch_bounds__(64, pk_min_waves(R, MODE, LG, WV)) void sw_pk_kerne
         for (int q = 4; q < 7; q++) {
             ahi |= (((a.sc.prof[q] >> (4 * cA)) & 15u) * PK_SCALE) << (8 * (q - 4));
             bhi |= (((a.sc.prof[q] >> (4 * cB)) & 15u) * PK_SCALE) << (8 * (q - 4));
+        }
+        if constexpr (DIAG) {  // entries of real classes hold 8 (W' + ext); a pad row or a pad column keeps its 0
+            const uint32_t e8 = (uint32_t)(a.sc.ext * PK_SCALE);
+            constexpr uint32_t HI_REAL = (1u << (8 * (PAD_CLASS - 4))) - 1u;  // byte mask of the query classes 4 .. PAD_CLASS - 1
+            if (cA != PAD_CLASS) { alo += e8 * 0x01010101u; ahi += e8 * (0x01010101u & HI_REAL); }
+            if (cB != PAD_CLASS) { blo += e8 * 0x01010101u; bhi += e8 * (0x01010101u & HI_REAL); }
         }
         wtab[lane] = make_uint4(alo, blo, ahi, bhi);
     }
@@ -1816,7 +1852,19 @@ __global__ __launch_bounds__(64, pk_min_waves(R, MODE, LG, WV)) void sw_pk_kerne
     const uint32_t oe8 = open8 - ext8, ext64 = ((uint32_t)(a.sc.ext * (8 * PK_SCALE)) & 0xffffu) * 0x10001u;
     (void)oe8; (void)ext64;
     uint32_t k8 = (uint32_t)PK_SCALE * 0x10001u;  // the key's multiplier, kept from the optimiser (pk_mad_c)
-    if constexpr (FRAME) {
+    // DIAG: what the drift of row R - 1, one step back, has over that of row 0.  Kept in a VGPR: with a vector operand the compiler
+    // folds the subtraction into the DPP move of the hand-off (v_sub_u32_dpp), a scalar one costs an instruction of its own
+    uint32_t hand8 = ext8 * (uint32_t)(R - 1);
+    (void)hand8;
+    if constexpr (DIAG) {
+        asm("" : "+v"(k8));  // (the key's constant is the scalar operand here)
+        asm("" : "+v"(hand8));
+#pragma unroll
+        for (int r = 0; r < R; r++) Hl[r] = ext8 * (uint32_t)(r + DIAG_C0 - 1);  // H = 0 left of the window: D(r, -1)
+        hu_out = ext8 * (uint32_t)(R - 1 + DIAG_C0 - 1);
+        hu_prev = ext8 * (uint32_t)(DIAG_C0 - 2);  // D(0, -1) - 8 ext
+        fu_out = hand8;  // F-hat = 0 in row R - 1 (anything at or below the true value will do; this one never borrows in the hand-off)
+    } else if constexpr (FRAME) {
         asm("" : "+s"(k8));
         fl_h = ext8 * (uint32_t)(LG - 1 - lig);
         fl_e = fl_h + oe8;
@@ -1835,6 +1883,9 @@ __global__ __launch_bounds__(64, pk_min_waves(R, MODE, LG, WV)) void sw_pk_kerne
     // hold each row's first column; the paired key ranks (H, even row, position) instead of (H, position, even row)
     const bool end_min_ref = rule(a.sc.rules, FADEHIP_RULE_END_MIN_REF_THEN_QUERY);
     (void)hdir_f_first; (void)tie_flip2; (void)tie_flip1; (void)end_min_ref;
+    // DIAG: the pair key's step constants as scalars, tk_even = dk_mul * position + dk_even, tk_odd = dk_mul * position
+    const uint32_t dk_mul = end_min_ref ? 2u : 1u, dk_even = end_min_ref ? 1u : (uint32_t)KW, e64 = (uint32_t)(a.sc.ext * (8 * PK_SCALE));
+    (void)dk_mul; (void)dk_even; (void)e64;
 
     // The sweep exists twice.  FAST (no N / wildcard in either query of the octet, i.e. nearly always): the four
     // A,C,G,T bytes of the two column rows sit in one register pair, so ONE v_perm_b32 yields both halves of the
@@ -1895,14 +1946,18 @@ __global__ __launch_bounds__(64, pk_min_waves(R, MODE, LG, WV)) void sw_pk_kerne
             rc = (uint32_t)__builtin_amdgcn_update_dpp((int)fresh, (int)rc, DPP_ROW_SHR1, 0xf, 0xf, false);
             uint32_t hu = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hu_out, DPP_ROW_SHR1, 0xf, 0xf, true);
             uint32_t fu = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)fu_out, DPP_ROW_SHR1, 0xf, 0xf, true);
-            if constexpr (FRAME) {  // one column on: the drift, the floor of E and the key bias move with the lane
+            if constexpr (DIAG) {  // from row R - 1 of the step before to above row 0 of this one (no half ever borrows: hu_out, fu_out >= hand8)
+                hu -= hand8;
+                fu -= hand8;
+            } else if constexpr (FRAME) {  // one column on: the drift, the floor of E and the key bias move with the lane
                 fl_h += ext8;
                 fl_e += ext8;
                 kd8 = as_u32(as_u2(kd8) + as_u2(ext64));
             }
             if constexpr (LG == 8) {  // lane 8 of a DPP row starts a group of its own
                 rc = bfi(lig0m, fresh, rc);
-                if constexpr (FRAME) hu = bfi(lig0m, fl_h, hu);  // H = 0 above the first row is d exactly (lane 0 of a DPP row too: its fill is 0)
+                if constexpr (DIAG) hu = bfi_s(lig0m, ext8 * (uint32_t)(t + DIAG_C0 - 1), hu);  // H = 0 above the first row: D(0, t) - 8 ext
+                else if constexpr (FRAME) hu = bfi(lig0m, fl_h, hu);  // H = 0 above the first row is d exactly (lane 0 of a DPP row too: its fill is 0)
                 else hu &= ~lig0m;
                 fu &= ~lig0m;  // (FRAME: anything <= the true F-hat + d - 8 ext will do, En >= floorE carries the floor)
             }
@@ -1922,7 +1977,12 @@ __global__ __launch_bounds__(64, pk_min_waves(R, MODE, LG, WV)) void sw_pk_kerne
             // PAIRKEY: ... and which row of the pair: 2 * position + (row even), or KW * (row even) + position
             const uint32_t tk_even = end_min_ref ? tk * 2u + 0x10001u : tk + (uint32_t)KW * 0x10001u, tk_odd = end_min_ref ? tk * 2u : tk;
             uint32_t tkf_even = 0, tkf_odd = 0;  // FRAME: the key constants less 8 d, mod 2^16 per half
-            if constexpr (FRAME) {
+            if constexpr (DIAG) {  // scalars: C_even(t) = tk_even - 64 ext (t + c0), C_odd(t) = tk_odd - 64 ext (t + c0 + 1), mod 2^16
+                // (the rule as a multiplier and an addend fixed before the sweep: a select here would split the block of four steps)
+                const uint32_t pos = (uint32_t)(KW - 1 - (t & (KW - 1))) * dk_mul;
+                tkf_even = ((pos + dk_even - e64 * (uint32_t)(t + DIAG_C0)) & 0xffffu) * 0x10001u;
+                tkf_odd = ((pos - e64 * (uint32_t)(t + DIAG_C0 + 1)) & 0xffffu) * 0x10001u;
+            } else if constexpr (FRAME) {
                 tkf_even = as_u32(as_u2(tk_even) - as_u2(kd8));
                 tkf_odd = as_u32(as_u2(tk_odd) - as_u2(kd8));
             }
@@ -1942,7 +2002,13 @@ __global__ __launch_bounds__(64, pk_min_waves(R, MODE, LG, WV)) void sw_pk_kerne
                 }
                 const uint32_t hl = Hl[r];
                 uint32_t Ee = 0, Fe = 0, En, Fn, T, H;
-                if constexpr (FRAME) {
+                if constexpr (DIAG) {
+                    const uint32_t fl = oe8 + ext8 * (uint32_t)(t + r + DIAG_C0);  // floorE of row r at step t: a scalar, of r + t only
+                    En = pk_max3_nonneg_c(hl, Eh[r], fl);
+                    Fn = as_u32(__builtin_elementwise_max(as_s2(hu), as_s2(fu)));  // D(r, t) - 8 ext = D(r - 1, t): the frame's own decay
+                    T = pk_max3_nonneg_c(Dp, En, Fn);
+                    H = as_u32(as_s2(T) - as_s2(oe8));  // T >= floorE: H >= D(r, t)
+                } else if constexpr (FRAME) {
                     En = pk_max3_nonneg_c(hl, Eh[r], fl_e);  // hl, Eh and floorE already sit in this column's frame
                     Fn = as_u32(__builtin_elementwise_max(as_s2(hu), as_s2(fu)) - as_s2(ext8));  // >= d - 8 ext >= 0
                     T = pk_max3_nonneg_c(Dp, En, Fn);
@@ -2068,7 +2134,9 @@ __global__ __launch_bounds__(64, pk_min_waves(R, MODE, LG, WV)) void sw_pk_kerne
     if constexpr (PAIRKEY) {
 #pragma unroll
         for (int p2 = 0; p2 < NK; p2++) {
-            const uint32_t gh = bestB[p2], gt = GT[p2];
+            uint32_t gh = bestB[p2];
+            const uint32_t gt = GT[p2];
+            if constexpr (DIAG) gh = pk_sub(gh, (((uint32_t)(a.sc.ext * 128 * p2)) & 0xffffu) * 0x10001u);  // every fold saw the pair's offset keys
             // the key's score field is 64 * score = 8 * H8 (6 low bits) or 32 * score = 4 * H8 (5 low bits)
             constexpr int KS = KLOW - 3, KB = KLOW - 1;  // shift back to H8; bits of the position inside a window
             const uint32_t ha = ((gh & 0xffffu) >> KLOW) << 3, hb = (gh >> (16 + KLOW)) << 3;
