@@ -153,6 +153,15 @@ int fadehip_eject_batch(fadehip_ctx* ctx, int n, const(ubyte)* recs, const(long)
 /// trim_left / trim_right the reference bases those ops take.  More ops than cig_cap: FADEHIP_E_INVALID, nothing written
 int fadehip_tags_batch(fadehip_ctx* ctx, int n, const(ubyte)* recs, const(long)* rec_off, int n_ref, const(char*)* ref_names,
         ubyte* rs, ubyte* have, int* trim_left, int* trim_right, int* art_tid, long* art_pos, long* cig_off, uint* cig, long cig_cap);
+/// A set of read names resident on the device (`fade out --fragments`): exact, growing; records in the shapes fadehip_eject_batch takes.
+/// add_batch: the names of the records with pick[k] != 0 (pick null: every record); contains_batch: hit[k] = 1 when record k's name is
+/// in the set; count: distinct names.  A malformed record: FADEHIP_E_INVALID with its index, the set unchanged.
+struct fadehip_nameset;
+int fadehip_nameset_create(fadehip_ctx* ctx, fadehip_nameset** out_);
+int fadehip_nameset_add_batch(fadehip_nameset* s, int n, const(ubyte)* recs, const(long)* rec_off, const(ubyte)* pick);
+int fadehip_nameset_contains_batch(fadehip_nameset* s, int n, const(ubyte)* recs, const(long)* rec_off, ubyte* hit);
+int fadehip_nameset_count(fadehip_nameset* s, long* n_names);
+void fadehip_nameset_destroy(fadehip_nameset* s);
 int fadehip_genome_upload(fadehip_ctx* ctx, int n_contigs, const(long)* lengths, const(ubyte*)* seqs);
 /// columns 2-5 of a .fai line: bases to take, file offset of the first base (of the uncompressed text), bases and bytes per line
 struct fadehip_fai_entry { long length, offset; int line_bases, line_width; }
@@ -198,8 +207,12 @@ enum FADEHIP_BAM_EXTRACT = 8;    /// ... every call also builds `fade extract`'s
 enum FADEHIP_BAM_EJECT = 16;     /// ... artifact calls are not written (`fade annotate --eject`, input not name-sorted), by this run's rs; not with FADEHIP_BAM_CLIP
 enum FADEHIP_BAM_EJECT_GROUPS = 32;  /// ... name-sorted input: nor any record of an artifact call's name group (implies FADEHIP_BAM_EJECT); a group never lies across two calls
 enum FADEHIP_BAM_FROM_TAGS = 64;  /// ... the records were annotated earlier: rs and am are read back out of them on the device and CLIP / EJECT / EJECT_GROUPS / EXTRACT are `fade out -c` / `fade out` / `fade extract`; no genome, floor_len and window ignored; a needed am side that is not well-formed fails the call at its back (FADEHIP_E_INVALID, the record's index in fadehip_last_error)
+enum FADEHIP_BAM_COLLECT_NAMES = 128;  /// ... with FROM_TAGS: every record with an integer rs and rs & 6 adds its name to the attached set
+enum FADEHIP_BAM_EJECT_NAMED = 256;    /// ... with FROM_TAGS: a record is written exactly when its name is not in the attached set (both: with STORED / NO_OUTPUT only)
 enum FADEHIP_BAM_CLIP = 4;       /// ... artifact calls leave hard-clipped (`fade annotate -c`), by this run's rs and alignments
 int fadehip_bam_open(fadehip_ctx* ctx, const(fadehip_bam_config)* cfg, fadehip_bam_stream** out_);
+/// the set of the same ctx a COLLECT_NAMES stream adds to / an EJECT_NAMED stream looks up in; before the first front call
+int fadehip_bam_use_nameset(fadehip_bam_stream* st, fadehip_nameset* s);
 int fadehip_bam_prepare(fadehip_bam_stream* st, size_t call_bytes);
 int fadehip_bam_front(fadehip_bam_stream* st, const(void)* members, size_t n_bytes, int last);
 int fadehip_bam_front_raw(fadehip_bam_stream* st, const(void)* payload, size_t n_bytes, int last);

@@ -34,8 +34,11 @@ EXPORTS = [
     "fadehip_bam_open", "fadehip_bam_front", "fadehip_bam_front_raw", "fadehip_bam_back", "fadehip_bam_totals", "fadehip_bam_close",
     "fadehip_bam_prepare", "fadehip_sw_stats_batch", "fadehip_clip_batch", "fadehip_extract_batch", "fadehip_bam_back_extract",
     "fadehip_eject_batch", "fadehip_bam_ejected", "fadehip_genome_upload_fasta", "fadehip_genome_fetch", "fadehip_tags_batch",
+    "fadehip_nameset_create", "fadehip_nameset_add_batch", "fadehip_nameset_contains_batch", "fadehip_nameset_count", "fadehip_nameset_destroy",
+    "fadehip_bam_use_nameset",
 ]
 BAM_STORED, BAM_NO_OUTPUT, BAM_CLIP, BAM_EXTRACT, BAM_EJECT, BAM_EJECT_GROUPS, BAM_FROM_TAGS = 1, 2, 4, 8, 16, 32, 64  # fadehip_bam_config.flags
+BAM_COLLECT_NAMES, BAM_EJECT_NAMED = 128, 256
 BGZF_BLOCK = 0xff00
 BGZF_LANES = 2
 
@@ -134,6 +137,13 @@ def load():
     L.fadehip_extract_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]
     L.fadehip_eject_batch.argtypes = [vp, i32, vp, vp, vp, C.c_int, vp]
     L.fadehip_tags_batch.argtypes = [vp, i32, vp, vp, i32, C.POINTER(C.c_char_p), vp, vp, vp, vp, vp, vp, vp, vp, i64]
+    L.fadehip_nameset_create.argtypes = [vp, C.POINTER(vp)]
+    L.fadehip_nameset_add_batch.argtypes = [vp, i32, vp, vp, vp]
+    L.fadehip_nameset_contains_batch.argtypes = [vp, i32, vp, vp, vp]
+    L.fadehip_nameset_count.argtypes = [vp, C.POINTER(i64)]
+    L.fadehip_nameset_destroy.argtypes = [vp]
+    L.fadehip_nameset_destroy.restype = None
+    L.fadehip_bam_use_nameset.argtypes = [vp, vp]
     L.fadehip_genome_upload.argtypes = [vp, i32, vp, vp]
     L.fadehip_genome_upload_fasta.argtypes = [vp, C.c_char_p, i32, C.POINTER(FaiEntry)]
     L.fadehip_genome_fetch.argtypes = [vp, i32, i64, i64, vp]

@@ -177,6 +177,11 @@ class Context:
         cat = np.frombuffer(b"".join(rb), dtype=np.uint8) if off[-1] else np.zeros(0, np.uint8)
         return self.eject_batch_packed(cat, off, rs, grouped).astype(bool)
 
+    # ---- a set of read names on the device (`fade out --fragments`): the kernels of the file path's collect_names= / eject_named=
+    def nameset(self):
+        """An exact, growing set of read names resident on the device (fadehip_nameset_*): NameSet.add / contains / count."""
+        return NameSet(self)
+
     # ---- remap.d:11-87 (`fade extract`): the device function of the file path's extract=True, on records brought here
     def extract_batch_packed(self, recs, rec_off, rs, art_tid, art_pos, cig_off, cig, out_cap=None):
         """Side 2k is the left side of record k (built when rs[k] & 2), side 2k + 1 the right (rs[k] & 4); art_tid and art_pos
@@ -460,7 +465,8 @@ class Context:
         self.bgzf_deflate_submit(lane, data)
         return self.bgzf_deflate_wait(lane)
 
-    def bam_stream(self, ref_names, floor_len=5, window=300, first_record=0, stored=False, tail_trim=0, no_output=False, clip=False, extract=False, eject=None, from_tags=False):
+    def bam_stream(self, ref_names, floor_len=5, window=300, first_record=0, stored=False, tail_trim=0, no_output=False, clip=False, extract=False, eject=None, from_tags=False,
+                   collect_names=None, eject_named=None):
         """The file path on the device (fadehip_bam_*): BGZF members of a BAM's records in, BGZF members of the annotated
         records out.  ref_names: the BAM header's contigs (the genome must be uploaded).  clip: records called artifacts leave
         hard-clipped (`fade annotate -c`).  extract: every call also builds `fade extract`'s records of its artifact calls
@@ -470,8 +476,12 @@ class Context:
         of the records themselves (FADEHIP_BAM_FROM_TAGS): no genome is needed, floor_len and window are ignored, and clip,
         eject and extract are `fade out -c`, plain `fade out` and `fade extract` — a record without an integer rs passes
         clip, is dropped by eject="records" and counts as clean under eject="groups"; a needed am side that is not
-        well-formed fails the call at its back()."""
-        return BamStream(self, ref_names, floor_len, window, first_record, stored, tail_trim, no_output, clip, extract, eject, from_tags)
+        well-formed fails the call at its back().  collect_names / eject_named (a NameSet of this context; with from_tags,
+        stored and no_output only): the two passes of `fade out --fragments` — every record with rs & 6 adds its name to the
+        set / a record is written exactly when its name is not in the set.  True instead of a set sets the flag alone (the
+        first front() then fails: no set is attached)."""
+        return BamStream(self, ref_names, floor_len, window, first_record, stored, tail_trim, no_output, clip, extract, eject, from_tags,
+                         collect_names, eject_named)
 
     def bgzf_inflate(self, members, out_cap=None):
         """Whole BGZF members (bytes / uint8 array) -> their payloads, inflated on the device (CRC32 and ISIZE checked)."""
@@ -605,18 +615,28 @@ def format_tags(batch, contig_names, rs, aln):
 
 
 class BamStream:
-    def __init__(self, ctx, ref_names, floor_len, window, first_record, stored=False, tail_trim=0, no_output=False, clip=False, extract=False, eject=None, from_tags=False):
+    def __init__(self, ctx, ref_names, floor_len, window, first_record, stored=False, tail_trim=0, no_output=False, clip=False, extract=False, eject=None, from_tags=False,
+                 collect_names=None, eject_named=None):
         self._ctx, self._L = ctx, ctx._L
         if eject not in (None, False, "records", "groups"):
             raise ValueError('eject is None, "records" or "groups"')
         ej = BAM_EJECT | BAM_EJECT_GROUPS if eject == "groups" else BAM_EJECT if eject == "records" else 0
         names = [n.encode() if isinstance(n, str) else bytes(n) for n in ref_names]
         arr = (C.c_char_p * max(len(names), 1))(*names)
-        cfg = _lib.BamConfig(floor_len, window, len(names), (_lib.BAM_STORED if stored else 0) | (_lib.BAM_NO_OUTPUT if no_output else 0) | (_lib.BAM_CLIP if clip else 0) | (_lib.BAM_EXTRACT if extract else 0) | (BAM_FROM_TAGS if from_tags else 0) | ej, arr, first_record, tail_trim)
+        cfg = _lib.BamConfig(floor_len, window, len(names), (_lib.BAM_STORED if stored else 0) | (_lib.BAM_NO_OUTPUT if no_output else 0) | (_lib.BAM_CLIP if clip else 0) | (_lib.BAM_EXTRACT if extract else 0) | (BAM_FROM_TAGS if from_tags else 0) | ej |
+                             (_lib.BAM_COLLECT_NAMES if collect_names else 0) | (_lib.BAM_EJECT_NAMED if eject_named else 0), arr, first_record, tail_trim)
         h = C.c_void_p()
         ctx._chk(self._L.fadehip_bam_open(ctx._h, C.byref(cfg), C.byref(h)))
         self._h = h
         self._keep = None
+        self._names = None
+        for ns in (collect_names, eject_named):
+            if isinstance(ns, NameSet):
+                rc = self._L.fadehip_bam_use_nameset(self._h, ns._h)
+                if rc:
+                    self.close()
+                    ctx._chk(rc)
+                self._names = ns  # (the set outlives the stream)
 
     def prepare(self, call_bytes):
         """fadehip_bam_prepare: the streams and buffers of calls of call_bytes inflated bytes, made ahead of the first call."""
@@ -659,6 +679,63 @@ class BamStream:
     def close(self):
         if self._h:
             self._L.fadehip_bam_close(self._h)
+            self._h = None
+
+
+class NameSet:
+    """Context.nameset(): read names on the device.  Records are BAM records (bytes, block_size first) as eject_batch takes."""
+
+    def __init__(self, ctx):
+        self._ctx, self._L = ctx, ctx._L
+        h = C.c_void_p()
+        ctx._chk(self._L.fadehip_nameset_create(ctx._h, C.byref(h)))
+        self._h = h
+
+    @staticmethod
+    def _cat(records):
+        rb = [bytes(r) for r in records]
+        off = np.zeros(len(rb) + 1, dtype=np.int64)
+        np.cumsum([len(r) for r in rb], out=off[1:])
+        return (np.frombuffer(b"".join(rb), dtype=np.uint8) if off[-1] else np.zeros(0, np.uint8)), off
+
+    def add_packed(self, recs, rec_off, pick):
+        """The names of the records with pick[k] != 0 go into the set (pick None: every record)."""
+        recs = np.ascontiguousarray(recs, dtype=np.uint8)
+        rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
+        n = len(rec_off) - 1
+        if pick is not None:
+            pick = np.ascontiguousarray(pick, dtype=np.uint8)
+            if len(pick) != n:
+                raise ValueError("pick holds one entry per record")
+        self._ctx._chk(self._L.fadehip_nameset_add_batch(self._h, n, recs.ctypes.data, rec_off.ctypes.data, pick.ctypes.data if pick is not None else None))
+
+    def add(self, records, pick=None):
+        cat, off = self._cat(records)
+        self.add_packed(cat, off, pick)
+
+    def contains_packed(self, recs, rec_off):
+        recs = np.ascontiguousarray(recs, dtype=np.uint8)
+        rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
+        n = len(rec_off) - 1
+        hit = np.zeros(n, dtype=np.uint8)
+        self._ctx._chk(self._L.fadehip_nameset_contains_batch(self._h, n, recs.ctypes.data, rec_off.ctypes.data, hit.ctypes.data))
+        return hit
+
+    def contains(self, records):
+        """uint8[n]: 1 where the record's name is in the set."""
+        cat, off = self._cat(records)
+        return self.contains_packed(cat, off)
+
+    @property
+    def count(self):
+        """Distinct names in the set."""
+        n = C.c_int64(0)
+        self._ctx._chk(self._L.fadehip_nameset_count(self._h, C.byref(n)))
+        return int(n.value)
+
+    def close(self):
+        if self._h:
+            self._L.fadehip_nameset_destroy(self._h)
             self._h = None
 
 

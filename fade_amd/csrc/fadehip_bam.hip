@@ -5,6 +5,7 @@
 #include "fadehip_host.hpp"
 #include "bam_device.hpp"
 #include "bam_from_tags.hpp"
+#include "bam_names.hpp"
 #include <algorithm>
 #include <chrono>
 #include <condition_variable>
@@ -16,6 +17,21 @@
 
 using namespace fadehip;
 using namespace fadehip::host;
+
+// A set of read names on the device (bam_names.hpp).  The host's part: the buffers, bounds on what the kernels in flight may
+// have added (exact values as of the last wait, plus the bounds of every launch since), and growth.  Every launch that names
+// the set's buffers is enqueued under `mu`, and growth — under `mu` too — begins with a wait for the whole device: so a
+// rehash, or the arena's move to a larger buffer, never runs beside an insert or a look-up of the same set, on whichever
+// stream those were enqueued (the two slots' streams of a file path, the record-batch lane).
+struct fadehip_nameset {
+    fadehip_ctx *ctx = nullptr;
+    std::mutex mu;
+    DevBuf table, arena, ctrl;
+    uint64_t slots = 0;
+    uint64_t count_ub = 0, used_ub = 0;  // bounds on ctrl[NS_COUNT], ctrl[NS_USED] once everything enqueued has run
+    uint32_t hash_bits = 64;
+    PinBuf h_ctrl;
+};
 
 namespace {
 
@@ -116,6 +132,102 @@ int enqueue_eject(fadehip_ctx *ctx, hipStream_t st, bam::EjectArgs &a, uint32_t 
     hipLaunchKernelGGL(bam::bam_eject_apply_kernel, dim3(ntb), dim3(bam::TAG_BLOCK), 0, st, a, grouped ? 1 : 0);
     HIPCHK(ctx, hipGetLastError());
     return 0;
+}
+
+// ---- the name set (bam_names.hpp): what a launch names of it, its growth
+bam::NameSetRef nameset_ref(const fadehip_nameset *s) {
+    bam::NameSetRef r;
+    r.table = (unsigned long long *)s->table.p;
+    r.mask = s->slots - 1;
+    r.arena = (uint8_t *)s->arena.p;
+    r.arena_cap = s->arena.cap;
+    r.ctrl = (unsigned long long *)s->ctrl.p;
+    r.hash_bits = s->hash_bits;
+    return r;
+}
+
+// What the set's kernels have left in ctrl, once nothing of the set runs any more (the caller holds s->mu): waits for the
+// whole device, since the set's kernels may be on any of the ctx's streams.  A raised error flag fails the call.
+int nameset_settle(fadehip_nameset *s, hipStream_t q) {
+    fadehip_ctx *ctx = s->ctx;
+    HIPCHK(ctx, hipDeviceSynchronize());
+    HIPCHK(ctx, hipMemcpyAsync(s->h_ctrl.p, s->ctrl.p, 24, hipMemcpyDeviceToHost, q));
+    HIPCHK(ctx, hipStreamSynchronize(q));
+    const unsigned long long *c = (const unsigned long long *)s->h_ctrl.p;
+    if (c[bam::NS_ERR]) return set_err(ctx, FADEHIP_E_STATE, "nameset: the %s was full during an insert (names may be missing: the set cannot be used)", (c[bam::NS_ERR] & bam::NS_ERR_ARENA) ? "arena" : "table");
+    s->used_ub = c[bam::NS_USED];
+    s->count_ub = c[bam::NS_COUNT];
+    return 0;
+}
+
+// Room for a launch that adds at most n_new names of at most bytes_new arena bytes, made before it is enqueued on q (the
+// caller holds s->mu).  The bounds of the launches so far usually say that there is room; when they do not, the device is
+// waited for, the true numbers are read, and only if those do not leave room either the set grows — to `ahead` launches of
+// this size, so that a file path does not come here with every call.  The insert kernel thus never finds the table (load
+// at most 1/2 after the add) or the arena full.
+int nameset_room(fadehip_nameset *s, hipStream_t q, uint64_t n_new, uint64_t bytes_new, uint64_t ahead) {
+    fadehip_ctx *ctx = s->ctx;
+    const auto fits = [&] { return 2 * (s->count_ub + n_new) <= s->slots && s->used_ub + bytes_new <= (uint64_t)s->arena.cap; };
+    int rc;
+    if (!fits()) {
+        if ((rc = nameset_settle(s, q))) return rc;
+        if (s->used_ub + bytes_new > (uint64_t)s->arena.cap) {  // the arena moves: offsets stay what they are
+            const uint64_t want = s->used_ub + ahead * bytes_new;
+            if (want > bam::NS_OFF_MASK) return set_err(ctx, FADEHIP_E_UNSUPPORTED, "nameset: more than 2^40 bytes of names");
+            DevBuf nb;
+            if ((rc = reserve(ctx, nb, (size_t)want))) return rc;
+            if (s->used_ub && (hipMemcpyAsync(nb.p, s->arena.p, (size_t)s->used_ub, hipMemcpyDeviceToDevice, q) != hipSuccess || hipStreamSynchronize(q) != hipSuccess)) {
+                release(nb);
+                return set_err(ctx, FADEHIP_E_HIP, "nameset: moving the arena failed");
+            }
+            release(s->arena);
+            s->arena = nb;
+        }
+        if (2 * (s->count_ub + n_new) > s->slots) {  // the table is hashed again into a larger one
+            uint64_t slots = s->slots;
+            while (slots < 2 * (s->count_ub + ahead * n_new)) slots <<= 1;
+            if (slots > ((uint64_t)1 << 36)) return set_err(ctx, FADEHIP_E_UNSUPPORTED, "nameset: more than 2^35 names");
+            DevBuf nt;
+            if ((rc = reserve(ctx, nt, 8 * (size_t)slots))) return rc;
+            bam::NameRehashArgs ra;
+            ra.old_table = (const unsigned long long *)s->table.p;
+            ra.old_slots = s->slots;
+            const DevBuf old = s->table;
+            s->table = nt;
+            s->slots = slots;
+            ra.s = nameset_ref(s);
+            hipError_t e = hipMemsetAsync(nt.p, 0, 8 * (size_t)slots, q);
+            if (e == hipSuccess) {
+                hipLaunchKernelGGL(bam::bam_names_rehash_kernel, dim3((unsigned)((ra.old_slots + bam::TAG_BLOCK - 1) / bam::TAG_BLOCK)), dim3(bam::TAG_BLOCK), 0, q, ra);
+                e = hipGetLastError();
+            }
+            if (e == hipSuccess) e = hipMemcpyAsync(s->h_ctrl.p, s->ctrl.p, 24, hipMemcpyDeviceToHost, q);
+            if (e == hipSuccess) e = hipStreamSynchronize(q);
+            if (e != hipSuccess || ((const unsigned long long *)s->h_ctrl.p)[bam::NS_ERR]) {
+                (void)hipStreamSynchronize(q);
+                s->table = old;  // (the old table is whole: the rehash only read it)
+                s->slots = ra.old_slots;
+                release(nt);
+                return set_err(ctx, FADEHIP_E_HIP, "nameset: hashing the table again failed%s%s", e != hipSuccess ? ": " : "", e != hipSuccess ? hipGetErrorString(e) : "");
+            }
+            DevBuf o2 = old;
+            release(o2);
+        }
+    }
+    s->count_ub += n_new;
+    s->used_ub += bytes_new;
+    return 0;
+}
+
+// the arguments the set's kernels take of a record-batch call behind batch_upload
+bam::NameArgs nameset_batch_args(const fadehip_nameset *s, BatchLane &L, int32_t n) {
+    bam::NameArgs a;
+    memset(&a, 0, sizeof a);
+    a.s = nameset_ref(s);
+    a.u = (const uint8_t *)L.in.p;
+    a.off64 = (const uint64_t *)L.meta.p;
+    a.n = (uint32_t)n;
+    return a;
 }
 
 }  // namespace
@@ -341,6 +453,121 @@ int fadehip_tags_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const i
     return 0;
 }
 
+// ---- the name set over records the caller brings: bam_names.hpp's kernels, the ones of the file path under
+// FADEHIP_BAM_COLLECT_NAMES / FADEHIP_BAM_EJECT_NAMED
+int fadehip_nameset_create(fadehip_ctx *ctx, fadehip_nameset **out) {
+    if (!ctx) return set_err(nullptr, FADEHIP_E_INVALID, "ctx is NULL");
+    if (!out) return set_err(ctx, FADEHIP_E_INVALID, "NULL argument");
+    *out = nullptr;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    fadehip_nameset *s = new (std::nothrow) fadehip_nameset;
+    if (!s) return set_err(ctx, FADEHIP_E_NOMEM, "out of memory");
+    s->ctx = ctx;
+    // FADEHIP_NAMESET_SLOTS: the first table's size (at least 16, rounded up to a power of two);
+    // FADEHIP_NAMESET_HASH_BITS: 0 .. 64, the hash is cut to its low bits (0: every name collides with every other)
+    uint64_t want = 65536;
+    if (const char *e = getenv("FADEHIP_NAMESET_SLOTS")) want = (uint64_t)std::max<long long>(16, std::min<long long>(atoll(e), 1ll << 32));
+    s->slots = 16;
+    while (s->slots < want) s->slots <<= 1;
+    if (const char *e = getenv("FADEHIP_NAMESET_HASH_BITS")) s->hash_bits = (uint32_t)std::max(0, std::min(64, atoi(e)));
+    int rc;
+    if ((rc = reserve(ctx, s->table, 8 * (size_t)s->slots)) || (rc = reserve(ctx, s->arena, 65536)) || (rc = reserve(ctx, s->ctrl, 256)) ||
+        (rc = reserve_pinned(ctx, s->h_ctrl, 64))) {
+        fadehip_nameset_destroy(s);
+        return rc;
+    }
+    // (on the ctx's copy stream: the null stream would be one more queue to set up and to give back)
+    if (hipMemsetAsync(s->table.p, 0, 8 * (size_t)s->slots, ctx->copy_stream) != hipSuccess || hipMemsetAsync(s->ctrl.p, 0, 256, ctx->copy_stream) != hipSuccess ||
+        hipStreamSynchronize(ctx->copy_stream) != hipSuccess) {
+        fadehip_nameset_destroy(s);
+        return set_err(ctx, FADEHIP_E_HIP, "nameset: clearing the table failed");
+    }
+    *out = s;
+    return 0;
+}
+
+int fadehip_nameset_add_batch(fadehip_nameset *s, int32_t n, const uint8_t *recs, const int64_t *rec_off, const uint8_t *pick) {
+    if (!s) return set_err(nullptr, FADEHIP_E_INVALID, "nameset is NULL");
+    fadehip_ctx *ctx = s->ctx;
+    if (n < 0 || !rec_off || (n > 0 && !recs)) return set_err(ctx, FADEHIP_E_INVALID, "NULL argument");
+    if (rec_off[0] < 0) return set_err(ctx, FADEHIP_E_INVALID, "offsets must be non-negative and non-decreasing (record 0)");
+    if (n == 0) return 0;
+    int rc;
+    if ((rc = check_records(ctx, n, recs, rec_off, false, [](int32_t) { return 0; }))) return rc;
+    uint64_t n_pick = 0, b_pick = 0;  // the call's bounds: its picked records, and the bytes their entries take at most
+    for (int32_t k = 0; k < n; k++)
+        if (!pick || pick[k]) {
+            n_pick++;
+            b_pick += std::min<uint64_t>(256, (uint64_t)(rec_off[k + 1] - rec_off[k]));
+        }
+    if (!n_pick) return 0;
+    BatchLane &L = ctx->batch;
+    std::lock_guard<std::mutex> lk(L.mu);
+    // meta: in_off [n + 1] u64 | pick [n] u8
+    const size_t m_pick = 8 * ((size_t)n + 1);
+    std::vector<uint64_t> off;
+    if ((rc = batch_upload(ctx, L, n, recs, rec_off, pick, m_pick, m_pick + (size_t)n + 8, 8, off))) return rc;
+    std::lock_guard<std::mutex> sl(s->mu);
+    if ((rc = nameset_room(s, L.stream, n_pick, b_pick, 1))) return rc;
+    bam::NameArgs a = nameset_batch_args(s, L, n);
+    a.pick = pick ? (const uint8_t *)L.meta.p + m_pick : nullptr;
+    a.pick_mask = 0xffu;
+    hipLaunchKernelGGL(bam::bam_names_insert_kernel, dim3(((unsigned)n + bam::TAG_BLOCK - 1) / bam::TAG_BLOCK), dim3(bam::TAG_BLOCK), 0, L.stream, a);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(s->h_ctrl.p, s->ctrl.p, 24, hipMemcpyDeviceToHost, L.stream));
+    HIPCHK(ctx, hipStreamSynchronize(L.stream));
+    if (((const unsigned long long *)s->h_ctrl.p)[bam::NS_ERR]) return set_err(ctx, FADEHIP_E_STATE, "nameset: the table or the arena was full during an insert (names may be missing: the set cannot be used)");
+    return 0;
+}
+
+int fadehip_nameset_contains_batch(fadehip_nameset *s, int32_t n, const uint8_t *recs, const int64_t *rec_off, uint8_t *hit) {
+    if (!s) return set_err(nullptr, FADEHIP_E_INVALID, "nameset is NULL");
+    fadehip_ctx *ctx = s->ctx;
+    if (n < 0 || !rec_off || (n > 0 && (!recs || !hit))) return set_err(ctx, FADEHIP_E_INVALID, "NULL argument");
+    if (rec_off[0] < 0) return set_err(ctx, FADEHIP_E_INVALID, "offsets must be non-negative and non-decreasing (record 0)");
+    if (n == 0) return 0;
+    int rc;
+    if ((rc = check_records(ctx, n, recs, rec_off, false, [](int32_t) { return 0; }))) return rc;
+    BatchLane &L = ctx->batch;
+    std::lock_guard<std::mutex> lk(L.mu);
+    // meta: in_off [n + 1] u64 | hit [n] u8
+    const size_t m_hit = 8 * ((size_t)n + 1);
+    std::vector<uint64_t> off;
+    if ((rc = batch_upload(ctx, L, n, recs, rec_off, nullptr, m_hit, m_hit + (size_t)n + 8, 8, off))) return rc;
+    {
+        std::lock_guard<std::mutex> sl(s->mu);
+        bam::NameArgs a = nameset_batch_args(s, L, n);
+        a.hit = (uint8_t *)L.meta.p + m_hit;
+        hipLaunchKernelGGL(bam::bam_names_lookup_kernel, dim3(((unsigned)n + bam::TAG_BLOCK - 1) / bam::TAG_BLOCK), dim3(bam::TAG_BLOCK), 0, L.stream, a);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    HIPCHK(ctx, hipMemcpyAsync(hit, (const uint8_t *)L.meta.p + m_hit, (size_t)n, hipMemcpyDeviceToHost, L.stream));
+    HIPCHK(ctx, hipStreamSynchronize(L.stream));
+    return 0;
+}
+
+int fadehip_nameset_count(fadehip_nameset *s, int64_t *n_names) {
+    if (!s) return set_err(nullptr, FADEHIP_E_INVALID, "nameset is NULL");
+    fadehip_ctx *ctx = s->ctx;
+    if (!n_names) return set_err(ctx, FADEHIP_E_INVALID, "NULL argument");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    std::lock_guard<std::mutex> sl(s->mu);
+    if (const int rc = nameset_settle(s, ctx->copy_stream)) return rc;
+    *n_names = (int64_t)s->count_ub;
+    return 0;
+}
+
+void fadehip_nameset_destroy(fadehip_nameset *s) {
+    if (!s) return;
+    (void)hipSetDevice(s->ctx->device);
+    (void)hipDeviceSynchronize();
+    release(s->table);
+    release(s->arena);
+    release(s->ctrl);
+    release(s->h_ctrl);
+    delete s;
+}
+
 struct fadehip_bam_stream {
     fadehip_ctx *ctx = nullptr;
     int32_t floor_len = 0, window = 0, n_ref = 0;
@@ -352,6 +579,9 @@ struct fadehip_bam_stream {
     bool eject = false;      // FADEHIP_BAM_EJECT: artifact calls are not written (the eject kernels of bam_device.hpp) ...
     bool eject_groups = false;  // FADEHIP_BAM_EJECT_GROUPS: ... nor any record of their name group; a group never lies across two calls
     bool from_tags = false;     // FADEHIP_BAM_FROM_TAGS: rs and am come out of the records (bam_from_tags.hpp), nothing is aligned
+    bool collect_names = false;  // FADEHIP_BAM_COLLECT_NAMES: from_tags, and every record with rs & 6 adds its name to `names` (bam_names.hpp)
+    bool eject_named = false;    // FADEHIP_BAM_EJECT_NAMED: from_tags, and a record is written exactly when its name is not in `names`
+    fadehip_nameset *names = nullptr;  // fadehip_bam_use_nameset
     DevBuf names_text, names_off;
     DevBuf names_first;         // from_tags: for every contig the first one of its name (fadehip_tags_batch's rule)
     struct Out {
@@ -386,6 +616,7 @@ struct fadehip_bam_stream {
         bam::FromTagsArgs fa;
         bam::TagArgs xa;                      // extract: ta with the extract stream's sizes, sums, counts and output
         PinBuf h_blocks, h_counts;
+        PinBuf h_ns;                          // collect_names / eject_named: the set's ctrl words behind the call's kernels
         uint64_t k = ~0ull;
         uint32_t n_rec = 0, n_sent = 0, ntb = 0;
         bool pending = false;  // B is enqueued, C is not
@@ -513,6 +744,8 @@ int bam_finish_call(fadehip_bam_stream *st, uint64_t k) {
                                kind == bam::FT_BAD_CLIP ? "rs names a side whose CIGAR is missing or does not parse"
                                : kind == bam::FT_BAD_OPS ? "a side holds more than 65535 CIGAR ops" : "rs names a side that is not name,pos,cigar");
             }
+            if (st->names && S.h_ns.p && ((const unsigned long long *)S.h_ns.p)[bam::NS_ERR])
+                return set_err(ctx, FADEHIP_E_STATE, "bam stream: the name set's table or arena was full (names may be missing: the set cannot be used)");
             for (int t = 0; t < 8; t++) st->stats[t] += (int64_t)sc->stats[t];
         } else if (S.n_sent) {
             if ((rc = finish_run(ctx, s, (int)(k & 1)))) return rc;  // waits for the stream: run and sizes
@@ -946,6 +1179,37 @@ int bam_front_tags(fadehip_bam_stream *st, fadehip_bam_stream::Set &S, Slot &s, 
         }
         if ((rc = enqueue_eject(ctx, q, ea, ntb, st->eject_groups))) return rc;
     }
+    if (st->collect_names || st->eject_named) {
+        // Under the set's lock: what the launch names of the set stays as it is until the launch has run (growth waits for
+        // the device under the same lock).  COLLECT: room first, from the call's bounds — at most n_rec names, of at most
+        // min(256 n_rec, the call's record bytes) bytes; the other slot's insert may run beside this one, a rehash never.
+        // EJECT_NAMED: the decision, in front of the scan as bam_eject_apply_kernel's.
+        fadehip_nameset *ns = st->names;
+        if ((rc = reserve_pinned(ctx, S.h_ns, 64))) return rc;
+        std::lock_guard<std::mutex> sl(ns->mu);
+        bam::NameArgs na;
+        memset(&na, 0, sizeof na);
+        na.u = pa.u;
+        na.off32 = pa.rec_off;
+        na.n = n_rec;
+        na.counts_in = d_counts;
+        if (st->collect_names) {
+            if ((rc = nameset_room(ns, q, n, std::min<uint64_t>(256 * (uint64_t)n, h_counts->consumed), 4))) return rc;
+            na.s = nameset_ref(ns);
+            na.pick = fa.rsb;
+            na.pick_mask = 6u;
+            hipLaunchKernelGGL(bam::bam_names_insert_kernel, dim3(ntb), dim3(bam::TAG_BLOCK), 0, q, na);
+        } else {
+            na.s = nameset_ref(ns);
+            na.out_size = fa.out_size;
+            na.info = pa.info;
+            na.blk_sums = fa.blk_sums;
+            na.counts = d_counts;
+            hipLaunchKernelGGL(bam::bam_eject_named_kernel, dim3(ntb), dim3(bam::TAG_BLOCK), 0, q, na);
+        }
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipMemcpyAsync(S.h_ns.p, ns->ctrl.p, 24, hipMemcpyDeviceToHost, q));
+    }
     hipLaunchKernelGGL(bam::bam_tag_scan_kernel, dim3(1), dim3(1024), 0, q, ta, ntb);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(S.h_counts.p, d_counts, st->counts_bytes(), hipMemcpyDeviceToHost, q));
@@ -963,6 +1227,8 @@ int bam_front_impl(fadehip_bam_stream *st, const uint8_t *members, size_t n_byte
     // the set's previous call must have been finished (back has usually done that long ago)
     CallTrace tr("front", k);
     if (ctx->n_contigs == 0 && !st->from_tags) return set_err(ctx, FADEHIP_E_STATE, "fadehip_genome_upload has not been called");
+    if ((st->collect_names || st->eject_named) && !st->names)
+        return set_err(ctx, FADEHIP_E_STATE, "bam stream: opened with FADEHIP_BAM_%s and no name set attached (fadehip_bam_use_nameset)", st->collect_names ? "COLLECT_NAMES" : "EJECT_NAMED");
     if (k >= 2 && (rc = bam_finish_call(st, k - 2))) return rc;
     tr.mark("finish call k - 2");
     // every stream is an HSA queue to set up and to give back (tens of ms each): slot 0 works on the ctx's copy stream, which
@@ -1012,8 +1278,15 @@ int bam_front_impl(fadehip_bam_stream *st, const uint8_t *members, size_t n_byte
 int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_bam_stream **out) {
     if (!ctx) return set_err(nullptr, FADEHIP_E_INVALID, "ctx is NULL");
     if (!cfg || !out || cfg->n_ref < 0 || (cfg->n_ref && !cfg->ref_names) || (cfg->window < 0 && !(cfg->flags & FADEHIP_BAM_FROM_TAGS)) ||
-        (cfg->flags & ~(FADEHIP_BAM_STORED | FADEHIP_BAM_NO_OUTPUT | FADEHIP_BAM_CLIP | FADEHIP_BAM_EXTRACT | FADEHIP_BAM_EJECT | FADEHIP_BAM_EJECT_GROUPS | FADEHIP_BAM_FROM_TAGS)))
+        (cfg->flags & ~(FADEHIP_BAM_STORED | FADEHIP_BAM_NO_OUTPUT | FADEHIP_BAM_CLIP | FADEHIP_BAM_EXTRACT | FADEHIP_BAM_EJECT | FADEHIP_BAM_EJECT_GROUPS | FADEHIP_BAM_FROM_TAGS |
+                        FADEHIP_BAM_COLLECT_NAMES | FADEHIP_BAM_EJECT_NAMED)))
         return set_err(ctx, FADEHIP_E_INVALID, "bam stream: bad configuration");
+    if (cfg->flags & (FADEHIP_BAM_COLLECT_NAMES | FADEHIP_BAM_EJECT_NAMED)) {
+        const int32_t one = cfg->flags & (FADEHIP_BAM_COLLECT_NAMES | FADEHIP_BAM_EJECT_NAMED);
+        if (one == (FADEHIP_BAM_COLLECT_NAMES | FADEHIP_BAM_EJECT_NAMED) || !(cfg->flags & FADEHIP_BAM_FROM_TAGS) ||
+            (cfg->flags & ~(one | FADEHIP_BAM_FROM_TAGS | FADEHIP_BAM_STORED | FADEHIP_BAM_NO_OUTPUT)))
+            return set_err(ctx, FADEHIP_E_INVALID, "bam stream: FADEHIP_BAM_COLLECT_NAMES and FADEHIP_BAM_EJECT_NAMED need FADEHIP_BAM_FROM_TAGS, exclude each other, and combine with STORED and NO_OUTPUT only");
+    }
     if ((cfg->flags & FADEHIP_BAM_CLIP) && (cfg->flags & (FADEHIP_BAM_EJECT | FADEHIP_BAM_EJECT_GROUPS)))
         return set_err(ctx, FADEHIP_E_INVALID, "bam stream: FADEHIP_BAM_CLIP and FADEHIP_BAM_EJECT exclude each other (`fade out` clips an artifact or ejects it)");
     if (!ctx->two_pass) return set_err(ctx, FADEHIP_E_UNSUPPORTED, "bam stream: needs the default kernels (FADEHIP_KERNEL unset)");
@@ -1033,6 +1306,8 @@ int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_ba
     st->eject_groups = (cfg->flags & FADEHIP_BAM_EJECT_GROUPS) != 0;
     st->eject = st->eject_groups || (cfg->flags & FADEHIP_BAM_EJECT) != 0;
     st->from_tags = (cfg->flags & FADEHIP_BAM_FROM_TAGS) != 0;
+    st->collect_names = (cfg->flags & FADEHIP_BAM_COLLECT_NAMES) != 0;
+    st->eject_named = (cfg->flags & FADEHIP_BAM_EJECT_NAMED) != 0;
     std::string text;
     std::vector<uint32_t> off((size_t)cfg->n_ref + 1, 0);
     for (int k = 0; k < cfg->n_ref; k++) {
@@ -1062,6 +1337,17 @@ int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_ba
         return set_err(ctx, FADEHIP_E_HIP, "bam stream: copying the contig names failed");
     }
     *out = st;
+    return 0;
+}
+
+int fadehip_bam_use_nameset(fadehip_bam_stream *st, fadehip_nameset *s) {
+    if (!st) return set_err(nullptr, FADEHIP_E_INVALID, "stream is NULL");
+    fadehip_ctx *ctx = st->ctx;
+    if (!s) return set_err(ctx, FADEHIP_E_INVALID, "nameset is NULL");
+    if (s->ctx != ctx) return set_err(ctx, FADEHIP_E_INVALID, "bam stream: the name set belongs to another ctx");
+    if (!st->collect_names && !st->eject_named) return set_err(ctx, FADEHIP_E_INVALID, "bam stream: opened without FADEHIP_BAM_COLLECT_NAMES or FADEHIP_BAM_EJECT_NAMED");
+    if (st->k_front) return set_err(ctx, FADEHIP_E_STATE, "bam stream: use_nameset comes before the first front call");
+    st->names = s;
     return 0;
 }
 
@@ -1324,6 +1610,7 @@ void fadehip_bam_close(fadehip_bam_stream *st) {
             release(*b);
         release(S.h_blocks);
         release(S.h_counts);
+        release(S.h_ns);
     }
     for (auto &ob : st->outbuf) release(ob);
     for (auto &xb : st->xbuf) release(xb);

@@ -82,11 +82,12 @@ struct Opts {
     int threads = 0, floor_len = 5, window = 300, gpus = 1, batch = 262144;
     bool bam = false, ubam = false, help = false, stats = false, timing = false, clip = false;
     bool eject = false;  // --eject: plain `fade out` (filter.d:209-265) in the same pass
+    bool fragments = false;  // `fade out --fragments`: whole fragments leave, input in any order (a set of names on the device, two passes)
     std::vector<std::string> pos;
     std::string out_shards;  // --out-shards PREFIX (with --gpus N)
     std::string stats_tsv, clip_tsv;  // --stats-tsv PATH, --clip-tsv PATH: the stats.d / noclip.d reports of this run
     std::string extract;  // --extract PATH: `fade extract`'s records of this run's artifact calls, in the output's format
-    std::string seen;  // one letter per option met: t m w b u c h g(pus) B(atch) s(tats) T(iming) S(hards) X (--extract) E (--eject)
+    std::string seen;  // one letter per option met: t m w b u c h g(pus) B(atch) s(tats) T(iming) S(hards) X (--extract) E (--eject) F (--fragments)
 };
 
 // std.getopt with config.bundling: short flags bundle (-bu), values attach (-w100, -w 100, --window-size=100)
@@ -154,6 +155,11 @@ static bool parse_opts(int argc, char **argv, Opts &o, std::string &err) {
                 o.seen += 'E';
                 if (has_val && val != "true" && val != "false") { err = "Invalid value for option --eject: " + val; return false; }
                 o.eject = !has_val || val == "true";
+            }
+            else if (name == "fragments") {  // (a flag, as --eject)
+                o.seen += 'F';
+                if (has_val && val != "true" && val != "false") { err = "Invalid value for option --fragments: " + val; return false; }
+                o.fragments = !has_val || val == "true";
             }
             else if (name == "help") o.help = true;
             else { err = "Unrecognized option --" + name; return false; }
@@ -2537,6 +2543,7 @@ static void print_out_help() {
             "-b     --bam output bam\n"
             "-u    --ubam output uncompressed bam\n"
             "      --gpus 1: BAM file in, -b or -u out: filtering or clipping runs on one MI355X (rs and am read back by a kernel)\n"
+            " --fragments BAM file in, -b or -u out, on one MI355X: eject every read that shares its name with an artifact read, input in any order (two passes over the file)\n"
             "    --timing print where the run spent its time to stderr\n"
             "-h    --help This help information.\n\n",
             kHeader);
@@ -2804,10 +2811,15 @@ static int out_main(const std::string &cl, const Opts &o) {
 // A reader thread cuts the file at BGZF member boundaries (and, with FADE_BAM_INFLATE=host, inflates the members on the
 // pool); this thread alternates front of call k and back of call k - 1, and writes what back hands out.  SAM or piped
 // input, SAM output and FADE_BAM_DEVICE=0 take the host loop (*fall_back stays set and nothing has been written).
-enum class TagsJob { OUT, EXTRACT };
+// `fade out --fragments` (TagsJob::FRAGMENTS) is two runs of that path on one context, the reading loop run twice over the
+// file: the first (FADEHIP_BAM_COLLECT_NAMES | NO_OUTPUT) fills a set of names on the device with the artifact calls' names,
+// the second (FADEHIP_BAM_EJECT_NAMED) writes every record whose name is not in the set.  It has no host loop behind it:
+// where *fall_back stays set, main refuses the run.
+enum class TagsJob { OUT, EXTRACT, FRAGMENTS };
 static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, bool *fall_back) {
     *fall_back = true;
     const char *who = job == TagsJob::EXTRACT ? "fade extract" : "fade out";
+    const bool fragments = job == TagsJob::FRAGMENTS;
     const std::string &path = o.pos[1];
     struct stat sb;
     if (!(o.bam || o.ubam) || path == "-" || stat(path.c_str(), &sb) != 0 || !S_ISREG(sb.st_mode)) return 1;
@@ -2857,6 +2869,8 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
     bool grouped = false;
     if (job == TagsJob::EXTRACT) {
         fprintf(stderr, "[W::fade extract] Output SAM/BAM will not be sorted\n");  // remap.d:13
+    } else if (fragments) {
+        fprintf(stderr, "[W::fade-out] --fragments: ejecting every read that shares its name with an artifact read, input in any order (two passes over the file)\n");
     } else if (o.clip) {  // filter.d:184-185
         fprintf(stderr, "[W::fade-out] Using the -c flag means the output SAM/BAM will not be sorted (regardless of prior sorting)\n");
         fprintf(stderr, "[W::fade-out] You also may need to fix mate information with a tool like Picard FixMateInformation\n");
@@ -2865,17 +2879,20 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
     }
     fadehip_ctx *ctx = nullptr;
     fadehip_bam_stream *st = nullptr;
+    fadehip_nameset *names = nullptr;
     struct Guard {
         fadehip_ctx *&c;
         fadehip_bam_stream *&s;
+        fadehip_nameset *&ns;
         std::vector<void *> pinned, owned;
         ~Guard() {
             if (s) fadehip_bam_close(s);
+            if (ns) fadehip_nameset_destroy(ns);
             for (void *p : pinned) fadehip_host_free(c, p);
             if (c) fadehip_destroy(c);
             for (void *p : owned) free(p);
         }
-    } guard{ctx, st, {}, {}};
+    } guard{ctx, st, names, {}, {}};
     try {
         fadehip_params prm;
         fadehip_params_default(&prm);
@@ -2885,23 +2902,33 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
         const size_t chunk = (size_t)std::max(1, getenv("FADE_BAM_CHUNK_MB") ? atoi(getenv("FADE_BAM_CHUNK_MB")) : host_inflate ? 32 : 128) << 20;
         // the device is brought up beside the buffers being made and the first members being read
         std::string create_err;
-        std::future<int> creating = std::async(std::launch::async, [&]() -> int {
-            if (fadehip_create(&ctx, device, &prm)) { create_err = fadehip_last_error(nullptr); return 1; }
-            std::vector<const char *> names;
-            for (auto &n : hdr.names) names.push_back(n.c_str());
+        // a stream of the file path with `mode` beside FROM_TAGS (--fragments: one per pass, on the same set of names)
+        auto open_stream = [&](int32_t mode) -> int {
+            std::vector<const char *> ref_names;
+            for (auto &n : hdr.names) ref_names.push_back(n.c_str());
             fadehip_bam_config cfg;
             memset(&cfg, 0, sizeof cfg);
-            cfg.n_ref = (int32_t)names.size();
-            cfg.ref_names = names.data();
+            cfg.n_ref = (int32_t)ref_names.size();
+            cfg.ref_names = ref_names.data();
             cfg.first_record = first_rec;
-            cfg.flags = FADEHIP_BAM_FROM_TAGS | (o.ubam ? FADEHIP_BAM_STORED : 0);
-            if (job == TagsJob::EXTRACT) cfg.flags |= FADEHIP_BAM_EXTRACT | FADEHIP_BAM_NO_OUTPUT;
-            else if (o.clip) cfg.flags |= FADEHIP_BAM_CLIP;
-            else cfg.flags |= grouped ? FADEHIP_BAM_EJECT | FADEHIP_BAM_EJECT_GROUPS : FADEHIP_BAM_EJECT;
+            cfg.flags = FADEHIP_BAM_FROM_TAGS | mode;
             if (fadehip_bam_open(ctx, &cfg, &st)) { create_err = fadehip_last_error(ctx); return 1; }
+            if (fragments && fadehip_bam_use_nameset(st, names)) { create_err = fadehip_last_error(ctx); return 1; }
             const size_t call_bytes = host_inflate ? chunk : std::min<size_t>(chunk * 3, (size_t)1 << 30);
             if (!(getenv("FADE_BAM_PREPARE") && atoi(getenv("FADE_BAM_PREPARE")) == 0) && fadehip_bam_prepare(st, call_bytes)) { create_err = fadehip_last_error(ctx); return 1; }
             return 0;
+        };
+        std::future<int> creating = std::async(std::launch::async, [&]() -> int {
+            if (fadehip_create(&ctx, device, &prm)) { create_err = fadehip_last_error(nullptr); return 1; }
+            if (fragments) {
+                if (fadehip_nameset_create(ctx, &names)) { create_err = fadehip_last_error(ctx); return 1; }
+                return open_stream(FADEHIP_BAM_COLLECT_NAMES | FADEHIP_BAM_NO_OUTPUT);
+            }
+            int32_t mode = o.ubam ? FADEHIP_BAM_STORED : 0;
+            if (job == TagsJob::EXTRACT) mode |= FADEHIP_BAM_EXTRACT | FADEHIP_BAM_NO_OUTPUT;
+            else if (o.clip) mode |= FADEHIP_BAM_CLIP;
+            else mode |= grouped ? FADEHIP_BAM_EJECT | FADEHIP_BAM_EJECT_GROUPS : FADEHIP_BAM_EJECT;
+            return open_stream(mode);
         });
         struct Joiner { std::future<int> &f; ~Joiner() { if (f.valid()) f.wait(); } } joiner{creating};
         // ---- the reader: compressed bytes cut at member boundaries; HEAD bytes in front of a buffer take the beginning of a
@@ -2922,9 +2949,9 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
         std::vector<uint8_t> own_comp;  // host inflate: the compressed bytes never cross PCIe
         for (int k = 0; k < NBUF; k++) bufs[k] = staging(host_inflate ? chunk + 65536 + 64 : HEAD + ccap + 64);
         if (host_inflate) own_comp.resize(HEAD + ccap + 64);
-        BoundedQueue<int> q_free(NBUF + 1);
-        BoundedQueue<In> q_full(NBUF + 1);
-        for (int k = 0; k < NBUF; k++) q_free.push(k);
+        // (the queues and the reader thread are made per pass over the file: --fragments makes two)
+        std::unique_ptr<BoundedQueue<int>> q_free_p;
+        std::unique_ptr<BoundedQueue<In>> q_full_p;
         std::string stage_err;
         std::mutex err_m;
         auto set_err = [&](const std::string &e) {
@@ -2956,9 +2983,19 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
             }
             return w;
         };
-        StageThreads stages;
-        stages.unblock = [&] { q_free.close(); q_full.close(); };
-        stages.th.emplace_back([&] {
+        std::unique_ptr<StageThreads> stages_p;
+        auto start_pass = [&] {
+          stages_p.reset();
+          q_free_p.reset(new BoundedQueue<int>(NBUF + 1));
+          q_full_p.reset(new BoundedQueue<In>(NBUF + 1));
+          BoundedQueue<int> &q_free = *q_free_p;
+          BoundedQueue<In> &q_full = *q_full_p;
+          for (int k = 0; k < NBUF; k++) q_free.push(k);
+          stages_p.reset(new StageThreads);
+          stages_p->unblock = [&q_free, &q_full] { q_free.close(); q_full.close(); };
+          stages_p->th.emplace_back([&, qf = q_free_p.get(), qu = q_full_p.get()] {
+            BoundedQueue<int> &q_free = *qf;
+            BoundedQueue<In> &q_full = *qu;
             try {
                 uint64_t at = coff;
                 std::vector<uint8_t> tail;
@@ -3022,7 +3059,9 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
                 set_err(e.what());
             }
             q_full.close();
-        });
+          });
+        };
+        start_pass();
         // ---- the header, as the host loop writes it; the records follow from the device (`extract`: through the Writer)
         Header out_hdr = hdr;
         out_hdr.add_pg("fade-extract", "fade", FADE_VERSION, cl);  // filter.d:173-180 / remap.d:18-26 (the reference reuses this ID)
@@ -3033,11 +3072,6 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
         }
         const OutFmt fmt = o.ubam ? OutFmt::UBAM : OutFmt::BAM;
         std::unique_ptr<Writer> xwriter;
-        if (job == TagsJob::EXTRACT) xwriter.reset(new Writer(stdout, fmt, out_hdr, &pool));
-        else {
-            Writer hw(stdout, fmt, out_hdr, &pool, nullptr, true, false);  // (its members only: no end-of-file block yet)
-            hw.close();
-        }
         std::vector<Rec> xrecs;
         auto take_back = [&]() {
             const uint8_t *p = nullptr;
@@ -3065,6 +3099,11 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
             } else if (n && fwrite(p, 1, n, stdout) != n) throw std::runtime_error("write error on the output stream");
             ck_write.stop();
         };
+        // one pass over the file: front of call k, back of call k - 1, until the reader is through
+        auto run_calls = [&]() -> int {
+        BoundedQueue<int> &q_free = *q_free_p;
+        BoundedQueue<In> &q_full = *q_full_p;
+        StageThreads &stages = *stages_p;
         In in;
         bool waiting = false, ended = false;
         while (q_full.pop(in)) {
@@ -3083,13 +3122,45 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
         stages.unblock = nullptr;
         if (!stage_err.empty()) { fprintf(stderr, "[E::%s] %s\n", who, stage_err.c_str()); return 1; }
         if (!ended) { fprintf(stderr, "[E::%s] the input ended before its last call\n", who); return 1; }
+        return 0;
+        };
+        if (fragments) {  // pass 1: the names of the artifact calls; then the stream of pass 2, and the reader again
+            StageClock ck_pass;
+            ck_pass.start();
+            if (run_calls()) return 1;
+            int64_t n_names = 0, totals1[8], n_rec1 = 0;
+            if (fadehip_nameset_count(names, &n_names)) { fprintf(stderr, "[E::%s] %s\n", who, fadehip_last_error(ctx)); return 1; }
+            fadehip_bam_totals(st, totals1, &n_rec1, nullptr);
+            fadehip_bam_close(st);
+            st = nullptr;
+            ck_pass.stop();
+            if (o.timing)
+                fprintf(stderr, "[timing] pass 1 (names of the artifact calls into the set) %.3f s: front %.3f | back %.3f; %lld records, %lld names collected\n", ck_pass.t, ck_front.t,
+                        ck_back.t, (long long)n_rec1, (long long)n_names);
+            ck_front = StageClock();
+            ck_back = StageClock();
+            ck_write = StageClock();
+            if (open_stream(FADEHIP_BAM_EJECT_NAMED | (o.ubam ? FADEHIP_BAM_STORED : 0))) { fprintf(stderr, "[E::%s] cannot open the GPU path: %s\n", who, create_err.c_str()); return 1; }
+            start_pass();
+        }
+        StageClock ck_pass2;
+        ck_pass2.start();
+        if (job == TagsJob::EXTRACT) xwriter.reset(new Writer(stdout, fmt, out_hdr, &pool));
+        else {
+            Writer hw(stdout, fmt, out_hdr, &pool, nullptr, true, false);  // (its members only: no end-of-file block yet)
+            hw.close();
+        }
+        if (run_calls()) return 1;
         if (xwriter) xwriter->close();
         else if (fwrite(BGZF_EOF, 1, sizeof BGZF_EOF, stdout) != sizeof BGZF_EOF) { fprintf(stderr, "[E::%s] write error on the output stream\n", who); return 1; }
         if (fflush(stdout) != 0 || ferror(stdout)) { fprintf(stderr, "[E::%s] write error on the output stream\n", who); return 1; }
         int64_t totals[8], n_rec = 0, n_over = 0, n_ej = 0;
         fadehip_bam_totals(st, totals, &n_rec, &n_over);
         fadehip_bam_ejected(st, &n_ej);
-        if (job == TagsJob::OUT) {  // filter.d:267
+        ck_pass2.stop();
+        if (fragments && o.timing)
+            fprintf(stderr, "[timing] pass 2 (records whose name is not in the set) %.3f s: front %.3f | back %.3f | write %.3f\n", ck_pass2.t, ck_front.t, ck_back.t, ck_write.t);
+        if (job != TagsJob::EXTRACT) {  // filter.d:267
             OutStats stats;
             stats.read_count = totals[0]; stats.clipped = totals[1]; stats.sup = totals[2]; stats.art_sup = totals[3];
             stats.art = totals[4]; stats.art_mate = totals[5]; stats.aln_l = totals[6]; stats.aln_r = totals[7];
@@ -3254,12 +3325,26 @@ int main(int argc, char **argv) {
             fprintf(stderr, "std.getopt.GetOptException: %s\n", err.c_str());
             return 1;
         }
-        if (!options_allowed(o, "ctbugT")) return 1;
+        if (!options_allowed(o, "ctbugTF")) return 1;
         if (o.help || o.pos.size() < 2) { print_out_help(); return 0; }
         if (!tags_gpus_ok(o, "fade out")) return 1;
         if (o.bam && o.ubam) {
             fprintf(stderr, "[E::fade-annotate] Please use only one of the b or u flags\n");  // app.d:122 (sic)
             return 1;
+        }
+        if (o.fragments) {  // the set of names lives on the device: there is no host loop behind this option
+            const char *why = o.clip ? "-c clips the artifact reads and --fragments ejects them with every read of their name: one or the other"
+                              : !(o.bam || o.ubam) ? "the output is SAM text: --fragments writes BAM (-b) or uncompressed BAM (-u)"
+                              : getenv("FADE_BAM_DEVICE") && atoi(getenv("FADE_BAM_DEVICE")) == 0 ? "FADE_BAM_DEVICE=0 takes the device away, and --fragments runs on it alone (no host loop)"
+                              : nullptr;
+            if (why) {
+                fprintf(stderr, "[E::fade-out] --fragments: %s\n", why);
+                return 1;
+            }
+            bool fall_back = true;
+            const int rc = tags_stream_main(cl, o, TagsJob::FRAGMENTS, &fall_back);
+            if (fall_back) fprintf(stderr, "[E::fade-out] --fragments: the input is read twice, as a BAM file on the device: not SAM text, not a pipe, not %s\n", o.pos[1].c_str());
+            return fall_back ? 1 : rc;
         }
         if (o.seen.find('g') != std::string::npos) {  // --gpus 1: the file path on the device, where input and output allow it
             bool fall_back = true;

@@ -214,6 +214,29 @@ int fadehip_tags_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const i
                        int32_t *trim_right /* [n] */, int32_t *art_tid /* [2n] */, int64_t *art_pos /* [2n] */,
                        int64_t *cig_off /* [2n + 1] */, uint32_t *cig, int64_t cig_cap);
 
+/* A set of read names, resident on the device: what lets `fade out --fragments` eject whole fragments — the artifact read,
+ * its mate, its supplementary and secondary lines — from input in any order, without a sort by name in front and a second
+ * one behind.  Records have the shapes fadehip_eject_batch takes.  Two names are equal when l_read_name and every name byte
+ * are; the set is exact (a hash decides where to look, never whether two names are equal) and grows as names are added.
+ *   add_batch       the names of the records with pick[k] != 0 go into the set (pick NULL: every record); a name that is
+ *                   there already is not added again
+ *   contains_batch  hit[k] = 1 when record k's name is in the set, else 0
+ *   count           distinct names in the set (waits for whatever of the set is still running on the device)
+ * The two batch calls are synchronous, on the stream, the buffers and the lock they share with fadehip_clip_batch (see
+ * there); a file path may use the set at the same time (fadehip_bam_use_nameset).  A record whose block_size or
+ * l_read_name does not fit its bytes: FADEHIP_E_INVALID, with the record's index in fadehip_last_error, and the set is left
+ * as it was before the call.  A NULL set or NULL arrays: FADEHIP_E_INVALID before anything reaches the device.  destroy
+ * comes after every stream that uses the set has been closed, and before fadehip_destroy.
+ * Environment, read at create: FADEHIP_NAMESET_SLOTS=N, the first table's size (default 65536, at least 16, rounded up to a
+ * power of two); FADEHIP_NAMESET_HASH_BITS=N, 0 .. 64 (default 64): the hash is cut to its low N bits before any use — with
+ * 0 every name collides with every other.  Results depend on neither. */
+typedef struct fadehip_nameset fadehip_nameset;
+int fadehip_nameset_create(fadehip_ctx *ctx, fadehip_nameset **out);
+int fadehip_nameset_add_batch(fadehip_nameset *s, int32_t n, const uint8_t *recs, const int64_t *rec_off, const uint8_t *pick /* [n] or NULL */);
+int fadehip_nameset_contains_batch(fadehip_nameset *s, int32_t n, const uint8_t *recs, const int64_t *rec_off, uint8_t *hit /* [n] out */);
+int fadehip_nameset_count(fadehip_nameset *s, int64_t *n_names);
+void fadehip_nameset_destroy(fadehip_nameset *s);
+
 /* ------------------------------------------------------ Level 2: annotateTask over a batch -- */
 /* Upload the indexed FASTA once (what IndexedFastaFile + fetchSequence serve, analysis.d:63).
  * seqs[c] holds lengths[c] ASCII residues (any case; upper-cased on device as analysis.d:63 does).
@@ -467,7 +490,16 @@ typedef struct fadehip_bam_config {
                                    * the call at its back: FADEHIP_E_INVALID, fadehip_last_error names the record's index in the
                                    * stream.  fadehip_bam_totals then sums stats.d:45-54 over the rs read back (read_count over
                                    * every record, the other seven over records with an integer rs), fadehip_bam_ejected counts
-                                   * every record not written */
+                                   * every record not written;
+                                   * FADEHIP_BAM_COLLECT_NAMES / FADEHIP_BAM_EJECT_NAMED: the two passes of `fade out --fragments`
+                                   * over a set of names attached with fadehip_bam_use_nameset.  Both need FROM_TAGS, exclude
+                                   * each other and combine with STORED and NO_OUTPUT only (anything else: FADEHIP_E_INVALID at
+                                   * fadehip_bam_open); without a set attached the first front call fails with FADEHIP_E_STATE.
+                                   * COLLECT_NAMES: every record with an integer rs and rs & 6 adds its name to the set; the
+                                   * records pass as under FROM_TAGS alone.  EJECT_NAMED: a record is written exactly when its
+                                   * name is not in the set — also one without rs (filter.d:221-246's rule for a group, not
+                                   * :254-257's); no name group is held back between calls.  Totals as under FROM_TAGS;
+                                   * fadehip_bam_ejected counts the records not written */
     const char *const *ref_names; /* [n_ref] NUL-terminated */
     uint32_t first_record;        /* payload bytes of the first member passed to front that precede the first record */
     uint32_t tail_trim;           /* payload bytes at the END of the last member (front's last call) that are not this stream's:
@@ -481,7 +513,13 @@ typedef struct fadehip_bam_config {
 #define FADEHIP_BAM_EJECT 16
 #define FADEHIP_BAM_EJECT_GROUPS 32
 #define FADEHIP_BAM_FROM_TAGS 64
+#define FADEHIP_BAM_COLLECT_NAMES 128
+#define FADEHIP_BAM_EJECT_NAMED 256
 int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_bam_stream **out);
+/* The set a stream opened with FADEHIP_BAM_COLLECT_NAMES adds to, or one opened with FADEHIP_BAM_EJECT_NAMED looks names up
+ * in: a set of the same ctx, attached before the first front call (later: FADEHIP_E_STATE).  The set is the caller's and
+ * outlives the stream; it may grow while two calls of the stream are in flight. */
+int fadehip_bam_use_nameset(fadehip_bam_stream *st, fadehip_nameset *s);
 int fadehip_bam_prepare(fadehip_bam_stream *st, size_t call_bytes);
 int fadehip_bam_front(fadehip_bam_stream *st, const void *members, size_t n_bytes, int last);
 /* front for a caller that inflates itself (host cores otherwise idle; the device then spends its time on the rest):
