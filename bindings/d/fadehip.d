@@ -153,6 +153,8 @@ int fadehip_eject_batch(fadehip_ctx* ctx, int n, const(ubyte)* recs, const(long)
 /// trim_left / trim_right the reference bases those ops take.  More ops than cig_cap: FADEHIP_E_INVALID, nothing written
 int fadehip_tags_batch(fadehip_ctx* ctx, int n, const(ubyte)* recs, const(long)* rec_off, int n_ref, const(char*)* ref_names,
         ubyte* rs, ubyte* have, int* trim_left, int* trim_right, int* art_tid, long* art_pos, long* cig_off, uint* cig, long cig_cap);
+/// order[j]: the record that comes j-th in stable coordinate order — by (refID, pos + 1) as unsigned, ties in the order given
+int fadehip_coord_order_batch(fadehip_ctx* ctx, int n, const(ubyte)* recs, const(long)* rec_off, int* order);
 /// A set of read names resident on the device (`fade out --fragments`): exact, growing; records in the shapes fadehip_eject_batch takes.
 /// add_batch: the names of the records with pick[k] != 0 (pick null: every record); contains_batch: hit[k] = 1 when record k's name is
 /// in the set; count: distinct names.  A malformed record: FADEHIP_E_INVALID with its index, the set unchanged.
@@ -209,6 +211,7 @@ enum FADEHIP_BAM_EJECT_GROUPS = 32;  /// ... name-sorted input: nor any record o
 enum FADEHIP_BAM_FROM_TAGS = 64;  /// ... the records were annotated earlier: rs and am are read back out of them on the device and CLIP / EJECT / EJECT_GROUPS / EXTRACT are `fade out -c` / `fade out` / `fade extract`; no genome, floor_len and window ignored; a needed am side that is not well-formed fails the call at its back (FADEHIP_E_INVALID, the record's index in fadehip_last_error)
 enum FADEHIP_BAM_COLLECT_NAMES = 128;  /// ... with FROM_TAGS: every record with an integer rs and rs & 6 adds its name to the attached set
 enum FADEHIP_BAM_EJECT_NAMED = 256;    /// ... with FROM_TAGS: a record is written exactly when its name is not in the attached set (both: with STORED / NO_OUTPUT only)
+enum FADEHIP_BAM_KEEP_SORTED = 512;    /// ... with CLIP (beside it STORED, EXTRACT, FROM_TAGS only), coordinate-sorted input: the records leave in stable order by (refID, pos + 1) as unsigned, a held tail staying on the device between calls
 enum FADEHIP_BAM_CLIP = 4;       /// ... artifact calls leave hard-clipped (`fade annotate -c`), by this run's rs and alignments
 int fadehip_bam_open(fadehip_ctx* ctx, const(fadehip_bam_config)* cfg, fadehip_bam_stream** out_);
 /// the set of the same ctx a COLLECT_NAMES stream adds to / an EJECT_NAMED stream looks up in; before the first front call
@@ -222,4 +225,6 @@ int fadehip_bam_back_extract(fadehip_bam_stream* st, const(ubyte)** recs, size_t
 int fadehip_bam_totals(fadehip_bam_stream* st, long* stats8, long* n_records, long* n_oversize);
 /// FADEHIP_BAM_EJECT: records not written, over the calls back has taken
 int fadehip_bam_ejected(fadehip_bam_stream* st, long* n_ejected);
+/// FADEHIP_BAM_KEEP_SORTED: records and bytes held back behind the most recent finished call
+int fadehip_bam_held(fadehip_bam_stream* st, long* n_records, long* n_bytes);
 void fadehip_bam_close(fadehip_bam_stream* st);

@@ -256,6 +256,17 @@ class Context:
         cat = np.frombuffer(b"".join(rb), dtype=np.uint8) if off[-1] else np.zeros(0, np.uint8)
         return self.tags_batch_packed(cat, off, ref_names)
 
+    def coord_order_batch(self, recs, rec_off):
+        """fadehip_coord_order_batch: the stable coordinate order of BAM records (recs: uint8, concatenated; rec_off: n + 1
+        offsets) by (refID, pos + 1) as unsigned.  Returns int32[n]: order[j] is the record that comes j-th."""
+        recs = np.ascontiguousarray(recs, dtype=np.uint8)
+        rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
+        n = len(rec_off) - 1
+        order = np.zeros(max(n, 0), np.int32)
+        self._chk(self._L.fadehip_coord_order_batch(self._h, n, recs.ctypes.data if recs.nbytes else None, rec_off.ctypes.data,
+                                                    order.ctypes.data if n > 0 else None))
+        return order
+
     # ---- level 2: annotateTask over a batch (anno.d:55-110)
     def genome_upload(self, names, seqs):
         """seqs: list of bytes / uint8 arrays (raw FASTA residues)."""
@@ -466,7 +477,7 @@ class Context:
         return self.bgzf_deflate_wait(lane)
 
     def bam_stream(self, ref_names, floor_len=5, window=300, first_record=0, stored=False, tail_trim=0, no_output=False, clip=False, extract=False, eject=None, from_tags=False,
-                   collect_names=None, eject_named=None):
+                   collect_names=None, eject_named=None, keep_sorted=False):
         """The file path on the device (fadehip_bam_*): BGZF members of a BAM's records in, BGZF members of the annotated
         records out.  ref_names: the BAM header's contigs (the genome must be uploaded).  clip: records called artifacts leave
         hard-clipped (`fade annotate -c`).  extract: every call also builds `fade extract`'s records of its artifact calls
@@ -479,9 +490,11 @@ class Context:
         well-formed fails the call at its back().  collect_names / eject_named (a NameSet of this context; with from_tags,
         stored and no_output only): the two passes of `fade out --fragments` — every record with rs & 6 adds its name to the
         set / a record is written exactly when its name is not in the set.  True instead of a set sets the flag alone (the
-        first front() then fails: no set is attached)."""
+        first front() then fails: no set is attached).  keep_sorted (with clip; beside it stored, extract and from_tags only):
+        coordinate-sorted input leaves in coordinate order — a clipped record at its new position, a reset one at the end —
+        with a small tail held on the device between calls; BamStream.held() counts it."""
         return BamStream(self, ref_names, floor_len, window, first_record, stored, tail_trim, no_output, clip, extract, eject, from_tags,
-                         collect_names, eject_named)
+                         collect_names, eject_named, keep_sorted)
 
     def bgzf_inflate(self, members, out_cap=None):
         """Whole BGZF members (bytes / uint8 array) -> their payloads, inflated on the device (CRC32 and ISIZE checked)."""
@@ -616,7 +629,7 @@ def format_tags(batch, contig_names, rs, aln):
 
 class BamStream:
     def __init__(self, ctx, ref_names, floor_len, window, first_record, stored=False, tail_trim=0, no_output=False, clip=False, extract=False, eject=None, from_tags=False,
-                 collect_names=None, eject_named=None):
+                 collect_names=None, eject_named=None, keep_sorted=False):
         self._ctx, self._L = ctx, ctx._L
         if eject not in (None, False, "records", "groups"):
             raise ValueError('eject is None, "records" or "groups"')
@@ -624,7 +637,7 @@ class BamStream:
         names = [n.encode() if isinstance(n, str) else bytes(n) for n in ref_names]
         arr = (C.c_char_p * max(len(names), 1))(*names)
         cfg = _lib.BamConfig(floor_len, window, len(names), (_lib.BAM_STORED if stored else 0) | (_lib.BAM_NO_OUTPUT if no_output else 0) | (_lib.BAM_CLIP if clip else 0) | (_lib.BAM_EXTRACT if extract else 0) | (BAM_FROM_TAGS if from_tags else 0) | ej |
-                             (_lib.BAM_COLLECT_NAMES if collect_names else 0) | (_lib.BAM_EJECT_NAMED if eject_named else 0), arr, first_record, tail_trim)
+                             (_lib.BAM_COLLECT_NAMES if collect_names else 0) | (_lib.BAM_EJECT_NAMED if eject_named else 0) | (_lib.BAM_KEEP_SORTED if keep_sorted else 0), arr, first_record, tail_trim)
         h = C.c_void_p()
         ctx._chk(self._L.fadehip_bam_open(ctx._h, C.byref(cfg), C.byref(h)))
         self._h = h
@@ -670,6 +683,12 @@ class BamStream:
         n = C.c_int64(0)
         self._ctx._chk(self._L.fadehip_bam_ejected(self._h, C.byref(n)))
         return int(n.value)
+
+    def held(self):
+        """keep_sorted: (records, bytes) held back on the device behind the most recent finished call."""
+        n, b = C.c_int64(0), C.c_int64(0)
+        self._ctx._chk(self._L.fadehip_bam_held(self._h, C.byref(n), C.byref(b)))
+        return int(n.value), int(b.value)
 
     def totals(self):
         st, nr, no = (C.c_int64 * 8)(), C.c_int64(0), C.c_int64(0)

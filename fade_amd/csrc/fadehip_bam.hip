@@ -6,6 +6,7 @@
 #include "bam_device.hpp"
 #include "bam_from_tags.hpp"
 #include "bam_names.hpp"
+#include "bam_resort.hpp"
 #include <algorithm>
 #include <chrono>
 #include <condition_variable>
@@ -581,6 +582,7 @@ struct fadehip_bam_stream {
     bool from_tags = false;     // FADEHIP_BAM_FROM_TAGS: rs and am come out of the records (bam_from_tags.hpp), nothing is aligned
     bool collect_names = false;  // FADEHIP_BAM_COLLECT_NAMES: from_tags, and every record with rs & 6 adds its name to `names` (bam_names.hpp)
     bool eject_named = false;    // FADEHIP_BAM_EJECT_NAMED: from_tags, and a record is written exactly when its name is not in `names`
+    bool keep_sorted = false;    // FADEHIP_BAM_KEEP_SORTED: clip, and the records leave in coordinate order (bam_resort.hpp)
     fadehip_nameset *names = nullptr;  // fadehip_bam_use_nameset
     DevBuf names_text, names_off;
     DevBuf names_first;         // from_tags: for every contig the first one of its name (fadehip_tags_batch's rule)
@@ -617,6 +619,16 @@ struct fadehip_bam_stream {
         bam::TagArgs xa;                      // extract: ta with the extract stream's sizes, sums, counts and output
         PinBuf h_blocks, h_counts;
         PinBuf h_ns;                          // collect_names / eject_named: the set's ctrl words behind the call's kernels
+        // keep_sorted (bam_resort.hpp).  Call k reads what call k - 1 left in the OTHER set — its ctl and final-order arrays in
+        // its front half (behind rs_meta), the bytes of its hold in its back half (behind rs_moved) — and writes only its own
+        // set's, so a call never writes what the call in front of it still reads.
+        DevBuf rs_ctl, rs_arr;                // the call's ResortCtl; the stage's arrays (resort_layout)
+        DevBuf rs_stage, rs_hold;             // the call's records in input order (what the rewrite writes); the records held behind it
+        PinBuf h_rs;                          // the ctl behind the stage
+        hipEvent_t rs_meta = nullptr, rs_moved = nullptr;
+        bam::ResortArgs ra;
+        uint32_t rs_n_rec = 0;                // records of the set's call
+        uint64_t rs_held = 0;                 // records held behind it (known once the call is finished)
         uint64_t k = ~0ull;
         uint32_t n_rec = 0, n_sent = 0, ntb = 0;
         bool pending = false;  // B is enqueued, C is not
@@ -645,6 +657,7 @@ struct fadehip_bam_stream {
     std::condition_variable cv;
     int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int64_t n_records = 0, n_oversize = 0, n_redone = 0, n_ejected = 0;
+    int64_t held_recs = 0, held_bytes = 0;  // keep_sorted: behind the most recent finished call
     bool failed = false, ended = false, closing = false;
     double t_inflate = 0, t_frame = 0, t_run = 0, t_tags = 0;
 };
@@ -676,6 +689,132 @@ struct CallTrace {
         t = n;
     }
 };
+
+// ---- FADEHIP_BAM_KEEP_SORTED and fadehip_coord_order_batch (bam_resort.hpp)
+// The stage's arrays for at most m_cap items, one behind the other from `base` (nullptr: only their size is wanted)
+size_t resort_layout(bam::ResortArgs &a, uint8_t *base, size_t m_cap) {
+    const size_t m = std::max<size_t>(m_cap, 1), tiles = (m + bam::RS_TILE - 1) / bam::RS_TILE, ntb = (m + bam::TAG_BLOCK - 1) / bam::TAG_BLOCK;
+    size_t at = 0;
+    const auto take = [&](size_t bytes) {
+        uint8_t *p = base + at;
+        at += (bytes + 7) & ~(size_t)7;
+        return p;
+    };
+    a.key0 = (uint64_t *)take(8 * m);
+    a.key1 = (uint64_t *)take(8 * m);
+    a.isrc = (uint64_t *)take(8 * m);
+    a.msrc = (uint64_t *)take(8 * m);
+    a.dst = (uint64_t *)take(8 * (m + 1));
+    a.sblk = (uint64_t *)take(16 * ntb);
+    a.idx0 = (uint32_t *)take(4 * m);
+    a.idx1 = (uint32_t *)take(4 * m);
+    a.isize = (uint32_t *)take(4 * m);
+    a.msize = (uint32_t *)take(4 * m);
+    a.hist = (uint32_t *)take(4 * 256 * tiles);
+    a.hist_base = (uint32_t *)take(4 * 256 * tiles);
+    return at;
+}
+
+// the eight passes over at most m_cap items (the kernels take the true number from a.ctl): side 0 holds the final order
+int enqueue_resort_sort(fadehip_ctx *ctx, hipStream_t q, const bam::ResortArgs &a, size_t m_cap) {
+    const unsigned tiles = (unsigned)((std::max<size_t>(m_cap, 1) + bam::RS_TILE - 1) / bam::RS_TILE);
+    for (uint32_t pass = 0; pass < 8; pass++) {
+        hipLaunchKernelGGL(bam::bam_resort_hist_kernel, dim3(tiles), dim3(256), 0, q, a, pass);
+        HIPCHK(ctx, hipGetLastError());
+        hipLaunchKernelGGL(bam::bam_resort_scan_kernel, dim3(1), dim3(1024), 0, q, a);
+        HIPCHK(ctx, hipGetLastError());
+        hipLaunchKernelGGL(bam::bam_resort_scatter_kernel, dim3(tiles), dim3(256), 0, q, a, pass);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    return 0;
+}
+
+// B's last part under FADEHIP_BAM_KEEP_SORTED, behind the sizes and their scan (an empty call comes here too: the last call
+// hands out what is still held): the held-over records and the call's become items, are sorted, cut at W and given their
+// offsets in final order; the ctl goes to the host behind the counts, which back waits for anyway.
+int bam_front_resort(fadehip_bam_stream *st, uint64_t k, uint32_t n_rec, int last) {
+    fadehip_ctx *ctx = st->ctx;
+    fadehip_bam_stream::Set &S = st->set[k & 1], &P = st->set[(k + 1) & 1];
+    hipStream_t q = ctx->slots[k & 1].stream;
+    int rc;
+    // what the previous call may hold at most: call k - 2's hold is known (front has finished that call), call k - 1 adds
+    // at most its own records
+    const uint64_t h_cap64 = k == 0 ? 0 : (k >= 2 ? S.rs_held : 0) + P.rs_n_rec;
+    const uint64_t m_cap = h_cap64 + n_rec;
+    if (m_cap >= ((uint64_t)1 << 31)) return set_err(ctx, FADEHIP_E_UNSUPPORTED, "bam stream: %llu records held and framed in one call (at most 2^31)", (unsigned long long)m_cap);
+    bam::ResortArgs &a = S.ra;
+    memset(&a, 0, sizeof a);
+    if ((rc = reserve_roomy(ctx, S.rs_arr, resort_layout(a, nullptr, (size_t)m_cap))) || (rc = reserve(ctx, S.rs_ctl, 256)) || (rc = reserve_pinned(ctx, S.h_rs, 64))) return rc;
+    resort_layout(a, (uint8_t *)S.rs_arr.p, (size_t)m_cap);
+    a.ctl = (bam::ResortCtl *)S.rs_ctl.p;
+    if (k) {
+        a.prev = (const bam::ResortCtl *)P.rs_ctl.p;
+        a.p_key = P.ra.key0;
+        a.p_dst = P.ra.dst;
+        a.p_size = P.ra.msize;
+        HIPCHK(ctx, hipStreamWaitEvent(q, P.rs_meta, 0));
+    }
+    a.h_cap = (uint32_t)h_cap64;
+    a.n = n_rec;
+    a.last = last ? 1u : 0u;
+    a.u = S.pa.u;
+    a.rec_off = S.pa.rec_off;
+    a.out_size = (const uint32_t *)S.out_size.p;
+    a.blk_base = st->from_tags ? S.fa.blk_base : S.ta.blk_base;
+    hipLaunchKernelGGL(bam::bam_resort_carry_kernel, dim3((unsigned)(h_cap64 / 256 + 1)), dim3(256), 0, q, a);
+    HIPCHK(ctx, hipGetLastError());
+    if (n_rec) {
+        if (st->from_tags) hipLaunchKernelGGL(bam::bam_resort_keys_kernel<true>, dim3(S.ntb), dim3(bam::TAG_BLOCK), 0, q, a, S.ta, S.fa);
+        else hipLaunchKernelGGL(bam::bam_resort_keys_kernel<false>, dim3(S.ntb), dim3(bam::TAG_BLOCK), 0, q, a, S.ta, S.fa);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    if ((rc = enqueue_resort_sort(ctx, q, a, (size_t)m_cap))) return rc;
+    const uint32_t ntb_cap = (uint32_t)((std::max<uint64_t>(m_cap, 1) + bam::TAG_BLOCK - 1) / bam::TAG_BLOCK);
+    hipLaunchKernelGGL(bam::bam_resort_cut_kernel, dim3(ntb_cap), dim3(bam::TAG_BLOCK), 0, q, a);
+    HIPCHK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(bam::bam_resort_offsets_scan_kernel, dim3(1), dim3(1024), 0, q, a, ntb_cap);
+    HIPCHK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(bam::bam_resort_offsets_kernel, dim3(ntb_cap), dim3(bam::TAG_BLOCK), 0, q, a, ntb_cap);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(S.h_rs.p, a.ctl, sizeof(bam::ResortCtl), hipMemcpyDeviceToHost, q));
+    if (!S.rs_meta) HIPCHK(ctx, hipEventCreateWithFlags(&S.rs_meta, hipEventDisableTiming));
+    HIPCHK(ctx, hipEventRecord(S.rs_meta, q));
+    S.rs_n_rec = n_rec;
+    return 0;
+}
+
+// C's last part under FADEHIP_BAM_KEEP_SORTED, behind the rewrite into the staging bytes: every item to its place in the
+// call's output or in the hold the next call reads.  The ctl is on the host (the caller has waited for the stream).
+int bam_finish_resort(fadehip_bam_stream *st, fadehip_bam_stream::Set &S, uint64_t k, hipStream_t q) {
+    fadehip_ctx *ctx = st->ctx;
+    fadehip_bam_stream::Set &P = st->set[(k + 1) & 1];
+    fadehip_bam_stream::Out *out = S.out;
+    const bam::ResortCtl c = *(const bam::ResortCtl *)S.h_rs.p;
+    int rc;
+    if (c.emit_bytes > ((uint64_t)1 << 31)) return set_err(ctx, FADEHIP_E_UNSUPPORTED, "bam stream: %llu output bytes in one call (at most 2^31)", (unsigned long long)c.emit_bytes);
+    const uint64_t hold_bytes = c.total_bytes - c.emit_bytes;
+    // (a buffer that grows is given back first, which waits for the device: the previous call's move, which read this set's
+    // old hold, is through then)
+    if ((rc = reserve_roomy(ctx, out->o, (size_t)c.emit_bytes + 256)) || (rc = reserve_roomy(ctx, S.rs_hold, (size_t)hold_bytes + 256))) return rc;
+    if (k && P.rs_moved) HIPCHK(ctx, hipStreamWaitEvent(q, P.rs_moved, 0));
+    if (c.n_in) {
+        bam::ResortArgs &a = S.ra;
+        a.stage = (const uint8_t *)S.rs_stage.p;
+        a.hold_in = (const uint8_t *)P.rs_hold.p;
+        a.out = (uint8_t *)out->o.p;
+        a.hold_out = (uint8_t *)S.rs_hold.p;
+        hipLaunchKernelGGL(bam::bam_resort_move_kernel, dim3((c.n_in + 15u) / 16u), dim3(256), 0, q, a, c.n_in, c.n_emit, (uint64_t)c.emit_bytes);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    if (!S.rs_moved) HIPCHK(ctx, hipEventCreateWithFlags(&S.rs_moved, hipEventDisableTiming));
+    HIPCHK(ctx, hipEventRecord(S.rs_moved, q));
+    out->bytes = (size_t)c.emit_bytes;
+    S.rs_held = c.n_in - c.n_emit;
+    std::lock_guard<std::mutex> l(st->mu);
+    st->held_recs = (int64_t)S.rs_held;
+    st->held_bytes = (int64_t)hold_bytes;
+    return 0;
+}
 
 // FADEHIP_BAM_EXTRACT, C of call k behind the event the compressor waits for: the extract records of the call's artifact
 // calls, from the untouched input records, and their copy into the pinned buffer back_extract hands out (the total came
@@ -720,7 +859,7 @@ int bam_finish_extract(fadehip_bam_stream *st, fadehip_bam_stream::Set &S, uint6
 
 // C of call k (see fadehip_bam_stream): waits for the call's run and tag sizes, sizes the output, enqueues the rewrite.
 // Idempotent; front and back may both arrive here for the same call.
-int bam_finish_call(fadehip_bam_stream *st, uint64_t k) {
+int bam_finish_one(fadehip_bam_stream *st, uint64_t k) {
     fadehip_ctx *ctx = st->ctx;
     fadehip_bam_stream::Set &S = st->set[k & 1];
     std::lock_guard<std::mutex> pl(S.mu);
@@ -758,10 +897,23 @@ int bam_finish_call(fadehip_bam_stream *st, uint64_t k) {
             st->stats[0] += S.n_rec;
         }
         const uint64_t out_bytes = h_counts->out_bytes;
-        if (out_bytes > ((uint64_t)1 << 31)) return set_err(ctx, FADEHIP_E_UNSUPPORTED, "bam stream: %llu output bytes in one call (at most 2^31)", (unsigned long long)out_bytes);
-        if ((rc = reserve_roomy(ctx, out->o, (size_t)out_bytes + 256))) return rc;
-        S.ta.o = (uint8_t *)out->o.p;
-        S.fa.o = (uint8_t *)out->o.p;
+        if (st->keep_sorted) {
+            // the order check first: nothing of a call that fails it is written.  The rewrite then goes to the staging bytes,
+            // from where the move takes the records; what leaves is sized there
+            const unsigned long long bad = ((const bam::ResortCtl *)S.h_rs.p)->bad;
+            if (bad)
+                return set_err(ctx, FADEHIP_E_INVALID, "bam stream: record %lld: not in coordinate order (--keep-sorted needs coordinate-sorted input)",
+                               (long long)st->n_records + (long long)(0xffffffffu - (uint32_t)(bad >> 8)));
+            if (out_bytes > ((uint64_t)1 << 32)) return set_err(ctx, FADEHIP_E_UNSUPPORTED, "bam stream: %llu bytes of records in one call (at most 2^32)", (unsigned long long)out_bytes);
+            if ((rc = reserve_roomy(ctx, S.rs_stage, (size_t)out_bytes + 256))) return rc;
+            S.ta.o = (uint8_t *)S.rs_stage.p;
+            S.fa.o = (uint8_t *)S.rs_stage.p;
+        } else {
+            if (out_bytes > ((uint64_t)1 << 31)) return set_err(ctx, FADEHIP_E_UNSUPPORTED, "bam stream: %llu output bytes in one call (at most 2^31)", (unsigned long long)out_bytes);
+            if ((rc = reserve_roomy(ctx, out->o, (size_t)out_bytes + 256))) return rc;
+            S.ta.o = (uint8_t *)out->o.p;
+            S.fa.o = (uint8_t *)out->o.p;
+        }
         if (st->from_tags && st->clip) hipLaunchKernelGGL(bam::bam_tags_write_kernel<true>, dim3(S.ntb), dim3(bam::REWRITE_WAVES * 64), 0, q, S.fa);
         else if (st->from_tags) hipLaunchKernelGGL(bam::bam_tags_write_kernel<false>, dim3(S.ntb), dim3(bam::REWRITE_WAVES * 64), 0, q, S.fa);
         else if (st->clip) hipLaunchKernelGGL(bam::bam_rewrite_kernel<true>, dim3(S.ntb), dim3(bam::REWRITE_WAVES * 64), 0, q, S.ta);
@@ -771,7 +923,10 @@ int bam_finish_call(fadehip_bam_stream *st, uint64_t k) {
         std::lock_guard<std::mutex> l(st->mu);
         st->n_records += S.n_rec;
         st->n_ejected += h_counts->n_ejected;
+    } else if (st->keep_sorted) {
+        HIPCHK(ctx, hipStreamSynchronize(q));  // (an empty call: the ctl alone)
     }
+    if (st->keep_sorted && (rc = bam_finish_resort(st, S, k, q))) return rc;
     if (!out->ready) HIPCHK(ctx, hipEventCreateWithFlags(&out->ready, hipEventDisableTiming | (ctx->blocking_sync ? hipEventBlockingSync : 0)));
     HIPCHK(ctx, hipEventRecord(out->ready, q));
     if (st->extract && (rc = bam_finish_extract(st, S, k, q))) return rc;
@@ -783,6 +938,14 @@ int bam_finish_call(fadehip_bam_stream *st, uint64_t k) {
     }
     st->cv.notify_all();
     return 0;
+}
+
+// Under FADEHIP_BAM_KEEP_SORTED call k's move reads the hold that call k - 1's move writes, so the calls are finished in
+// their order (they are anyway: back takes them in order, and front finishes k - 2 before k - 1 exists; this says so).
+int bam_finish_call(fadehip_bam_stream *st, uint64_t k) {
+    int rc;
+    if (st->keep_sorted && k && (rc = bam_finish_one(st, k - 1))) return rc;
+    return bam_finish_one(st, k);
 }
 
 // A of call k (see fadehip_bam_stream) on the slot's stream q, up to and with the wait and the checks of what came back: the
@@ -1258,6 +1421,7 @@ int bam_front_impl(fadehip_bam_stream *st, const uint8_t *members, size_t n_byte
     S.ntb = 0;
     S.out = out;
     if (n_rec && (rc = st->from_tags ? bam_front_tags(st, S, s, n_rec) : bam_front_run(st, S, s, tr, n_rec))) return rc;
+    if (st->keep_sorted && (rc = bam_front_resort(st, k, n_rec, last))) return rc;
     S.pending = true;
     tr.mark("tag sizes enqueued");
     st->t_run += now_s() - t2;
@@ -1279,8 +1443,13 @@ int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_ba
     if (!ctx) return set_err(nullptr, FADEHIP_E_INVALID, "ctx is NULL");
     if (!cfg || !out || cfg->n_ref < 0 || (cfg->n_ref && !cfg->ref_names) || (cfg->window < 0 && !(cfg->flags & FADEHIP_BAM_FROM_TAGS)) ||
         (cfg->flags & ~(FADEHIP_BAM_STORED | FADEHIP_BAM_NO_OUTPUT | FADEHIP_BAM_CLIP | FADEHIP_BAM_EXTRACT | FADEHIP_BAM_EJECT | FADEHIP_BAM_EJECT_GROUPS | FADEHIP_BAM_FROM_TAGS |
-                        FADEHIP_BAM_COLLECT_NAMES | FADEHIP_BAM_EJECT_NAMED)))
+                        FADEHIP_BAM_COLLECT_NAMES | FADEHIP_BAM_EJECT_NAMED | FADEHIP_BAM_KEEP_SORTED)))
         return set_err(ctx, FADEHIP_E_INVALID, "bam stream: bad configuration");
+    if (cfg->flags & FADEHIP_BAM_KEEP_SORTED) {
+        if (!(cfg->flags & FADEHIP_BAM_CLIP)) return set_err(ctx, FADEHIP_E_INVALID, "bam stream: FADEHIP_BAM_KEEP_SORTED needs FADEHIP_BAM_CLIP (without a clip nothing moves)");
+        if (cfg->flags & ~(FADEHIP_BAM_KEEP_SORTED | FADEHIP_BAM_CLIP | FADEHIP_BAM_STORED | FADEHIP_BAM_EXTRACT | FADEHIP_BAM_FROM_TAGS))
+            return set_err(ctx, FADEHIP_E_INVALID, "bam stream: FADEHIP_BAM_KEEP_SORTED combines with CLIP, STORED, EXTRACT and FROM_TAGS only");
+    }
     if (cfg->flags & (FADEHIP_BAM_COLLECT_NAMES | FADEHIP_BAM_EJECT_NAMED)) {
         const int32_t one = cfg->flags & (FADEHIP_BAM_COLLECT_NAMES | FADEHIP_BAM_EJECT_NAMED);
         if (one == (FADEHIP_BAM_COLLECT_NAMES | FADEHIP_BAM_EJECT_NAMED) || !(cfg->flags & FADEHIP_BAM_FROM_TAGS) ||
@@ -1308,6 +1477,7 @@ int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_ba
     st->from_tags = (cfg->flags & FADEHIP_BAM_FROM_TAGS) != 0;
     st->collect_names = (cfg->flags & FADEHIP_BAM_COLLECT_NAMES) != 0;
     st->eject_named = (cfg->flags & FADEHIP_BAM_EJECT_NAMED) != 0;
+    st->keep_sorted = (cfg->flags & FADEHIP_BAM_KEEP_SORTED) != 0;
     std::string text;
     std::vector<uint32_t> off((size_t)cfg->n_ref + 1, 0);
     for (int k = 0; k < cfg->n_ref; k++) {
@@ -1572,6 +1742,48 @@ int fadehip_bam_totals(fadehip_bam_stream *st, int64_t stats[8], int64_t *n_reco
     return 0;
 }
 
+int fadehip_bam_held(fadehip_bam_stream *st, int64_t *n_records, int64_t *n_bytes) {
+    if (!st) return set_err(nullptr, FADEHIP_E_INVALID, "stream is NULL");
+    if (!n_records || !n_bytes) return set_err(st->ctx, FADEHIP_E_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> l(st->mu);
+    *n_records = st->held_recs;
+    *n_bytes = st->held_bytes;
+    return 0;
+}
+
+// The stable coordinate order of records the caller brings, in whatever order they come: bam_resort.hpp's sort, the one of the
+// file path under FADEHIP_BAM_KEEP_SORTED, on the record-batch lane.  order[j] is the record that comes j-th.
+int fadehip_coord_order_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const int64_t *rec_off, int32_t *order) {
+    if (!ctx) return set_err(nullptr, FADEHIP_E_INVALID, "ctx is NULL");
+    if (n < 0 || !rec_off || (n > 0 && (!recs || !order))) return set_err(ctx, FADEHIP_E_INVALID, "NULL argument");
+    if (rec_off[0] < 0) return set_err(ctx, FADEHIP_E_INVALID, "offsets must be non-negative and non-decreasing (record 0)");
+    if (n == 0) return 0;
+    int rc;
+    if ((rc = check_records(ctx, n, recs, rec_off, false, [](int32_t) { return 0; }))) return rc;
+    BatchLane &L = ctx->batch;
+    std::lock_guard<std::mutex> lk(L.mu);
+    // meta: in_off [n + 1] u64 | the ctl;  work: the stage's arrays;  out: order [n] i32
+    bam::ResortArgs a;
+    memset(&a, 0, sizeof a);
+    const size_t m_ctl = 8 * ((size_t)n + 1);
+    std::vector<uint64_t> off;
+    if ((rc = batch_upload(ctx, L, n, recs, rec_off, nullptr, 0, m_ctl + 256, resort_layout(a, nullptr, (size_t)n), off)) || (rc = reserve(ctx, L.out, 4 * (size_t)n + 8))) return rc;
+    resort_layout(a, (uint8_t *)L.work.p, (size_t)n);
+    a.ctl = (bam::ResortCtl *)((uint8_t *)L.meta.p + m_ctl);
+    a.n = (uint32_t)n;
+    a.u = (const uint8_t *)L.in.p;
+    a.rec_off64 = (const uint64_t *)L.meta.p;
+    const unsigned nb = ((unsigned)n + 255u) / 256u;
+    hipLaunchKernelGGL(bam::bam_resort_batch_keys_kernel, dim3(nb), dim3(256), 0, L.stream, a);
+    HIPCHK(ctx, hipGetLastError());
+    if ((rc = enqueue_resort_sort(ctx, L.stream, a, (size_t)n))) return rc;
+    hipLaunchKernelGGL(bam::bam_resort_order_kernel, dim3(nb), dim3(256), 0, L.stream, a, (int32_t *)L.out.p);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(order, L.out.p, 4 * (size_t)n, hipMemcpyDeviceToHost, L.stream));
+    HIPCHK(ctx, hipStreamSynchronize(L.stream));
+    return 0;
+}
+
 int fadehip_bam_ejected(fadehip_bam_stream *st, int64_t *n_ejected) {
     if (!st) return set_err(nullptr, FADEHIP_E_INVALID, "stream is NULL");
     if (!n_ejected) return set_err(st->ctx, FADEHIP_E_INVALID, "NULL argument");
@@ -1611,6 +1823,10 @@ void fadehip_bam_close(fadehip_bam_stream *st) {
         release(S.h_blocks);
         release(S.h_counts);
         release(S.h_ns);
+        for (DevBuf *b : {&S.rs_ctl, &S.rs_arr, &S.rs_stage, &S.rs_hold}) release(*b);  // (records still held, no last call: given back with the rest)
+        release(S.h_rs);
+        if (S.rs_meta) (void)hipEventDestroy(S.rs_meta);
+        if (S.rs_moved) (void)hipEventDestroy(S.rs_moved);
     }
     for (auto &ob : st->outbuf) release(ob);
     for (auto &xb : st->xbuf) release(xb);

@@ -68,6 +68,7 @@ static void print_anno_help() {
             "-c        --clip hard-clip the artifacts in the same pass (what `fade out -c` makes of the annotated file)\n"
             "        --extract PATH: also write what `fade extract` makes of the annotated file (one mapped record per artifact side), in the same pass\n"
             "          --eject drop the artifact reads in the same pass, and on name-sorted input every read that shares their name (what `fade out` makes of the annotated file)\n"
+            "    --keep-sorted with -c, coordinate-sorted BAM file in, -b or -u out, one MI355X: clipped records are written at their new coordinates, so the output stays coordinate-sorted\n"
             "          --gpus number of MI355X devices, one process each on its own range of the input (default 1)\n"
             "    --out-shards with --gpus N: every device writes a complete file PREFIX.<k>.bam (.sam), nothing is merged\n"
             "         --batch records per device batch (default 262144)\n"
@@ -83,11 +84,12 @@ struct Opts {
     bool bam = false, ubam = false, help = false, stats = false, timing = false, clip = false;
     bool eject = false;  // --eject: plain `fade out` (filter.d:209-265) in the same pass
     bool fragments = false;  // `fade out --fragments`: whole fragments leave, input in any order (a set of names on the device, two passes)
+    bool keep_sorted = false;  // --keep-sorted: with -c, the clipped output of coordinate-sorted input stays coordinate-sorted (a tail held on the device)
     std::vector<std::string> pos;
     std::string out_shards;  // --out-shards PREFIX (with --gpus N)
     std::string stats_tsv, clip_tsv;  // --stats-tsv PATH, --clip-tsv PATH: the stats.d / noclip.d reports of this run
     std::string extract;  // --extract PATH: `fade extract`'s records of this run's artifact calls, in the output's format
-    std::string seen;  // one letter per option met: t m w b u c h g(pus) B(atch) s(tats) T(iming) S(hards) X (--extract) E (--eject) F (--fragments)
+    std::string seen;  // one letter per option met: t m w b u c h g(pus) B(atch) s(tats) T(iming) S(hards) X (--extract) E (--eject) F (--fragments) K (--keep-sorted)
 };
 
 // std.getopt with config.bundling: short flags bundle (-bu), values attach (-w100, -w 100, --window-size=100)
@@ -161,6 +163,11 @@ static bool parse_opts(int argc, char **argv, Opts &o, std::string &err) {
                 if (has_val && val != "true" && val != "false") { err = "Invalid value for option --fragments: " + val; return false; }
                 o.fragments = !has_val || val == "true";
             }
+            else if (name == "keep-sorted") {  // (a flag, as --eject)
+                o.seen += 'K';
+                if (has_val && val != "true" && val != "false") { err = "Invalid value for option --keep-sorted: " + val; return false; }
+                o.keep_sorted = !has_val || val == "true";
+            }
             else if (name == "help") o.help = true;
             else { err = "Unrecognized option --" + name; return false; }
         } else if (a.size() > 1 && a[0] == '-' && a != "-") {
@@ -185,6 +192,27 @@ static bool parse_opts(int argc, char **argv, Opts &o, std::string &err) {
         } else o.pos.push_back(a);
     }
     return true;
+}
+
+// --keep-sorted --timing: the largest tail a call left on the device (fadehip_bam_held behind every back call)
+static int64_t g_held_max_recs = 0, g_held_max_bytes = 0;
+static void note_held(const Opts &o, fadehip_bam_stream *st) {
+    int64_t r = 0, b = 0;
+    if (!o.keep_sorted || !o.timing || fadehip_bam_held(st, &r, &b)) return;
+    if (r > g_held_max_recs) g_held_max_recs = r;
+    if (b > g_held_max_bytes) g_held_max_bytes = b;
+}
+static void report_held(const Opts &o) {
+    if (o.keep_sorted && o.timing) fprintf(stderr, "[timing] --keep-sorted: at most %lld records (%lld bytes) held on the device between calls\n", (long long)g_held_max_recs, (long long)g_held_max_bytes);
+}
+
+// What `fade out -c` and `fade annotate -c` say about their output (filter.d:184-185); with --keep-sorted, what holds instead
+static void clip_warnings(const Opts &o) {
+    if (o.keep_sorted)
+        fprintf(stderr, "[W::fade-out] --keep-sorted: clipped records are written at their new coordinates, so coordinate-sorted input stays sorted; reads clipped to nothing go to the end as unmapped records\n");
+    else
+        fprintf(stderr, "[W::fade-out] Using the -c flag means the output SAM/BAM will not be sorted (regardless of prior sorting)\n");
+    fprintf(stderr, "[W::fade-out] You also may need to fix mate information with a tool like Picard FixMateInformation\n");
 }
 
 
@@ -1609,6 +1637,7 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
             cfg.tail_trim = host_inflate ? 0 : tail_trim;
             cfg.flags = o.ubam ? FADEHIP_BAM_STORED : 0;  // -u: uncompressed BGZF (util.d:65-76, SAMWriterTypes.UBAM)
             if (o.clip) cfg.flags |= FADEHIP_BAM_CLIP;    // -c: the artifact calls leave hard-clipped
+            if (o.keep_sorted) cfg.flags |= FADEHIP_BAM_KEEP_SORTED;  // --keep-sorted: ... at their new coordinates
             if (!o.extract.empty()) cfg.flags |= FADEHIP_BAM_EXTRACT;  // --extract: every call leaves its extract records too
             if (o.eject) cfg.flags |= eject_grouped ? FADEHIP_BAM_EJECT | FADEHIP_BAM_EJECT_GROUPS : FADEHIP_BAM_EJECT;  // --eject
             if (fadehip_bam_open(ctx, &cfg, &st)) { create_err = fadehip_last_error(ctx); return 1; }
@@ -1880,6 +1909,7 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
                     const int rc = fadehip_bam_back(st, &p, &n);
                     ck_back.stop();
                     if (rc) throw std::runtime_error(std::string("device: ") + fadehip_last_error(ctx));
+                    note_held(o, st);
                     OutRef ref{p, n};
                     if (xwriter) {  // (the call's extract records live as long as its members: the writer takes both)
                         int64_t n_x = 0;
@@ -1998,6 +2028,7 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
         if (fflush(stdout) != 0 || ferror(stdout)) { fprintf(stderr, "[E::fade annotate] write error on the output stream\n"); return 1; }
         int64_t totals[8], n_rec = 0, n_over = 0;
         fadehip_bam_totals(st, totals, &n_rec, &n_over);
+        report_held(o);
         if (lane.on) {
             // the lane's report for the parent; lanes on distinct devices first sum their counters among themselves (the one
             // collective of the path: ncclAllReduce over xGMI, one rank per process)
@@ -2544,6 +2575,7 @@ static void print_out_help() {
             "-u    --ubam output uncompressed bam\n"
             "      --gpus 1: BAM file in, -b or -u out: filtering or clipping runs on one MI355X (rs and am read back by a kernel)\n"
             " --fragments BAM file in, -b or -u out, on one MI355X: eject every read that shares its name with an artifact read, input in any order (two passes over the file)\n"
+            "--keep-sorted with -c, coordinate-sorted BAM file in, -b or -u out, on one MI355X: clipped records are written at their new coordinates, so the output stays coordinate-sorted\n"
             "    --timing print where the run spent its time to stderr\n"
             "-h    --help This help information.\n\n",
             kHeader);
@@ -2815,6 +2847,7 @@ static int out_main(const std::string &cl, const Opts &o) {
 // file: the first (FADEHIP_BAM_COLLECT_NAMES | NO_OUTPUT) fills a set of names on the device with the artifact calls' names,
 // the second (FADEHIP_BAM_EJECT_NAMED) writes every record whose name is not in the set.  It has no host loop behind it:
 // where *fall_back stays set, main refuses the run.
+
 enum class TagsJob { OUT, EXTRACT, FRAGMENTS };
 static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, bool *fall_back) {
     *fall_back = true;
@@ -2872,8 +2905,7 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
     } else if (fragments) {
         fprintf(stderr, "[W::fade-out] --fragments: ejecting every read that shares its name with an artifact read, input in any order (two passes over the file)\n");
     } else if (o.clip) {  // filter.d:184-185
-        fprintf(stderr, "[W::fade-out] Using the -c flag means the output SAM/BAM will not be sorted (regardless of prior sorting)\n");
-        fprintf(stderr, "[W::fade-out] You also may need to fix mate information with a tool like Picard FixMateInformation\n");
+        clip_warnings(o);
     } else {
         grouped = eject_mode_grouped(first_names);  // filter.d:216-220, 248
     }
@@ -2926,7 +2958,7 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
             }
             int32_t mode = o.ubam ? FADEHIP_BAM_STORED : 0;
             if (job == TagsJob::EXTRACT) mode |= FADEHIP_BAM_EXTRACT | FADEHIP_BAM_NO_OUTPUT;
-            else if (o.clip) mode |= FADEHIP_BAM_CLIP;
+            else if (o.clip) mode |= FADEHIP_BAM_CLIP | (o.keep_sorted ? FADEHIP_BAM_KEEP_SORTED : 0);
             else mode |= grouped ? FADEHIP_BAM_EJECT | FADEHIP_BAM_EJECT_GROUPS : FADEHIP_BAM_EJECT;
             return open_stream(mode);
         });
@@ -3080,6 +3112,7 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
             const int rc = fadehip_bam_back(st, &p, &n);
             ck_back.stop();
             if (rc) throw std::runtime_error(fadehip_last_error(ctx));
+            note_held(o, st);
             ck_write.start();
             if (xwriter) {
                 const uint8_t *xp = nullptr;
@@ -3157,6 +3190,7 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
         int64_t totals[8], n_rec = 0, n_over = 0, n_ej = 0;
         fadehip_bam_totals(st, totals, &n_rec, &n_over);
         fadehip_bam_ejected(st, &n_ej);
+        report_held(o);
         ck_pass2.stop();
         if (fragments && o.timing)
             fprintf(stderr, "[timing] pass 2 (records whose name is not in the set) %.3f s: front %.3f | back %.3f | write %.3f\n", ck_pass2.t, ck_front.t, ck_back.t, ck_write.t);
@@ -3179,6 +3213,29 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
     return 0;
 }
 
+// --keep-sorted (`fade annotate -c`, `fade out -c`): why the option cannot run as the command line stands, or nullptr.  Looks
+// at the options, the environment and the first bytes of the input: no device is opened for it.
+static const char *const kKeepSortedInput = "the input is read as a coordinate-sorted BAM file on the device: not SAM text, not a pipe";
+static const char *keep_sorted_refusal(const Opts &o) {
+    if (!o.clip) return "without -c no record moves: the option goes with -c";
+    if (o.eject) return "--eject drops the artifact reads, and nothing is left to put in order: not with --eject";
+    if (o.fragments) return "--fragments ejects the artifact reads, and nothing is left to put in order: not with --fragments";
+    if (!(o.bam || o.ubam)) return "the output is SAM text: --keep-sorted writes BAM (-b) or uncompressed BAM (-u)";
+    if (o.gpus > 1 || !o.out_shards.empty())
+        return "it goes with one device: the devices of --gpus N > 1 and --out-shards cut the input at BGZF ranges, and the tail one holds back would belong into the next one's range";
+    if (getenv("FADE_BAM_DEVICE") && atoi(getenv("FADE_BAM_DEVICE")) == 0) return "FADE_BAM_DEVICE=0 takes the device away, and the held tail lives on it (no host loop)";
+    const std::string &path = o.pos[1];
+    struct stat sb;
+    uint8_t h[4] = {0, 0, 0, 0};
+    bool bgzf = false;
+    if (path != "-" && stat(path.c_str(), &sb) == 0 && S_ISREG(sb.st_mode))
+        if (FILE *f = fopen(path.c_str(), "rb")) {
+            bgzf = fread(h, 1, 4, f) == 4 && h[0] == 0x1f && h[1] == 0x8b && (h[3] & 4);
+            fclose(f);
+        }
+    return bgzf ? nullptr : kKeepSortedInput;
+}
+
 // --gpus for `fade out` / `fade extract`: 1 is the file path on the device where the input and output allow it, more is not built
 static bool tags_gpus_ok(const Opts &o, const char *who) {
     if (o.seen.find('g') == std::string::npos || o.gpus == 1) return true;
@@ -3198,7 +3255,7 @@ int main(int argc, char **argv) {
             fprintf(stderr, "std.getopt.GetOptException: %s\n", err.c_str());
             return 1;
         }
-        if (!options_allowed(o, "tmwbucgBsTSPQXE")) return 1;
+        if (!options_allowed(o, "tmwbucgBsTSPQXEK")) return 1;
         // app.d:84-89: helpWanted | args.length < 3 (args = prog, "annotate", positionals...)
         if (o.help || o.pos.size() < 2) { print_anno_help(); return 0; }
         if (o.pos.size() < 3) {  // the reference indexes args[2] and dies; say why instead
@@ -3219,6 +3276,12 @@ int main(int argc, char **argv) {
         if (reports && o.clip) {  // the reports describe the unclipped records
             fprintf(stderr, "[E::fade-annotate] %s describes unclipped records: not with --clip\n", !o.stats_tsv.empty() ? "--stats-tsv" : "--clip-tsv");
             return 1;
+        }
+        if (o.keep_sorted) {  // refused here, by name, before any device is opened
+            if (const char *why = keep_sorted_refusal(o)) {
+                fprintf(stderr, "[E::fade-annotate] --keep-sorted: %s\n", why);
+                return 1;
+            }
         }
         if (o.eject) {  // refused here, before any device is opened
             if (o.clip) {
@@ -3252,10 +3315,7 @@ int main(int argc, char **argv) {
             return 1;
         }
         if (!o.extract.empty()) fprintf(stderr, "[W::fade extract] Output SAM/BAM will not be sorted\n");  // remap.d:13
-        if (o.clip && !lane_env().on) {  // filter.d:184-185, as `fade out -c` (once: the lanes of --gpus N stay silent)
-            fprintf(stderr, "[W::fade-out] Using the -c flag means the output SAM/BAM will not be sorted (regardless of prior sorting)\n");
-            fprintf(stderr, "[W::fade-out] You also may need to fix mate information with a tool like Picard FixMateInformation\n");
-        }
+        if (o.clip && !lane_env().on) clip_warnings(o);  // filter.d:184-185, as `fade out -c` (once: the lanes of --gpus N stay silent)
         // --gpus N on a BAM file: one process per GPU, each on its own share of the input (annotate_lanes_main); input that
         // cannot be cut (a pipe, SAM text, a small file) is read by one process that deals batches to the N devices
         if (o.gpus > 1 && !lane_env().on && !(getenv("FADE_LANES") && atoi(getenv("FADE_LANES")) == 0)) {
@@ -3272,6 +3332,10 @@ int main(int argc, char **argv) {
             bool fall_back = true;
             const int src = annotate_stream_main(cl, o, &fall_back);
             if (src == 0 || !fall_back) return src;
+        }
+        if (o.keep_sorted) {  // the tail is held on the device: there is no host loop behind this option
+            fprintf(stderr, "[E::fade-annotate] --keep-sorted: %s\n", kKeepSortedInput);
+            return 1;
         }
         const int rc = annotate_main(cl, o);
         if (o.timing) {
@@ -3325,12 +3389,24 @@ int main(int argc, char **argv) {
             fprintf(stderr, "std.getopt.GetOptException: %s\n", err.c_str());
             return 1;
         }
-        if (!options_allowed(o, "ctbugTF")) return 1;
+        if (!options_allowed(o, "ctbugTFK")) return 1;
         if (o.help || o.pos.size() < 2) { print_out_help(); return 0; }
+        if (o.keep_sorted) {  // refused here, by name, before any device is opened
+            if (const char *why = keep_sorted_refusal(o)) {
+                fprintf(stderr, "[E::fade-out] --keep-sorted: %s\n", why);
+                return 1;
+            }
+        }
         if (!tags_gpus_ok(o, "fade out")) return 1;
         if (o.bam && o.ubam) {
             fprintf(stderr, "[E::fade-annotate] Please use only one of the b or u flags\n");  // app.d:122 (sic)
             return 1;
+        }
+        if (o.keep_sorted) {  // the tail is held on the device: there is no host loop behind this option either (--gpus 1 is implied)
+            bool fall_back = true;
+            const int rc = tags_stream_main(cl, o, TagsJob::OUT, &fall_back);
+            if (fall_back) fprintf(stderr, "[E::fade-out] --keep-sorted: %s\n", kKeepSortedInput);
+            return fall_back ? 1 : rc;
         }
         if (o.fragments) {  // the set of names lives on the device: there is no host loop behind this option
             const char *why = o.clip ? "-c clips the artifact reads and --fragments ejects them with every read of their name: one or the other"

@@ -214,6 +214,14 @@ int fadehip_tags_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const i
                        int32_t *trim_right /* [n] */, int32_t *art_tid /* [2n] */, int64_t *art_pos /* [2n] */,
                        int64_t *cig_off /* [2n + 1] */, uint32_t *cig, int64_t cig_cap);
 
+/* The stable coordinate order of n BAM records (shapes as fadehip_eject_batch takes), whatever order they come in: the key
+ * of a record is (refID as uint32, pos + 1 as uint32) compared as one 64-bit number — refID -1 sorts last, as in samtools —
+ * and records of one key keep the order they came in.  order[j] is the index of the record that comes j-th.  The sort is
+ * the one of the file path under FADEHIP_BAM_KEEP_SORTED; it also puts fadehip_clip_batch's output in order.  NULL
+ * arguments: FADEHIP_E_INVALID before any device call; n = 0 is fine.  A malformed record: FADEHIP_E_INVALID with its
+ * index.  Synchronous, on the stream and buffers it shares with fadehip_clip_batch (see there). */
+int fadehip_coord_order_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const int64_t *rec_off, int32_t *order /* [n] */);
+
 /* A set of read names, resident on the device: what lets `fade out --fragments` eject whole fragments — the artifact read,
  * its mate, its supplementary and secondary lines — from input in any order, without a sort by name in front and a second
  * one behind.  Records have the shapes fadehip_eject_batch takes.  Two names are equal when l_read_name and every name byte
@@ -499,7 +507,16 @@ typedef struct fadehip_bam_config {
                                    * records pass as under FROM_TAGS alone.  EJECT_NAMED: a record is written exactly when its
                                    * name is not in the set — also one without rs (filter.d:221-246's rule for a group, not
                                    * :254-257's); no name group is held back between calls.  Totals as under FROM_TAGS;
-                                   * fadehip_bam_ejected counts the records not written */
+                                   * fadehip_bam_ejected counts the records not written;
+                                   * FADEHIP_BAM_KEEP_SORTED: with CLIP (beside it STORED, EXTRACT and FROM_TAGS only; anything
+                                   * else: FADEHIP_E_INVALID at fadehip_bam_open), for coordinate-sorted input: the records leave
+                                   * in stable order by key — (refID as uint32, pos + 1 as uint32) of the record as it leaves,
+                                   * a reset record as an unmapped one (refID -1, pos -1) — so the stream's output over all its
+                                   * calls is what it writes without the flag, record for record the same bytes, in that order.
+                                   * A call writes the records, held over or its own, whose key is not above the key as it came
+                                   * in of its last record; the others are held on the device until a later call (the last call
+                                   * writes all).  Input keys that decrease fail that call's back: FADEHIP_E_INVALID,
+                                   * fadehip_last_error names the record's index in the stream; nothing of the call is written */
     const char *const *ref_names; /* [n_ref] NUL-terminated */
     uint32_t first_record;        /* payload bytes of the first member passed to front that precede the first record */
     uint32_t tail_trim;           /* payload bytes at the END of the last member (front's last call) that are not this stream's:
@@ -515,6 +532,7 @@ typedef struct fadehip_bam_config {
 #define FADEHIP_BAM_FROM_TAGS 64
 #define FADEHIP_BAM_COLLECT_NAMES 128
 #define FADEHIP_BAM_EJECT_NAMED 256
+#define FADEHIP_BAM_KEEP_SORTED 512
 int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_bam_stream **out);
 /* The set a stream opened with FADEHIP_BAM_COLLECT_NAMES adds to, or one opened with FADEHIP_BAM_EJECT_NAMED looks names up
  * in: a set of the same ctx, attached before the first front call (later: FADEHIP_E_STATE).  The set is the caller's and
@@ -535,6 +553,9 @@ int fadehip_bam_back_extract(fadehip_bam_stream *st, const uint8_t **recs, size_
 int fadehip_bam_totals(fadehip_bam_stream *st, int64_t stats[8], int64_t *n_records, int64_t *n_oversize);
 /* FADEHIP_BAM_EJECT: records not written, over the calls back has taken (0 without the flag) */
 int fadehip_bam_ejected(fadehip_bam_stream *st, int64_t *n_ejected);
+/* FADEHIP_BAM_KEEP_SORTED: the records (and their bytes) held back on the device behind the most recent finished call; 0 / 0
+ * without the flag and behind the last call.  fadehip_bam_close with records still held gives them back unwritten. */
+int fadehip_bam_held(fadehip_bam_stream *st, int64_t *n_records, int64_t *n_bytes);
 void fadehip_bam_close(fadehip_bam_stream *st);
 
 /* Sum counters over the ranks' devices with one ncclAllReduce (RCCL) — single process, one ctx
