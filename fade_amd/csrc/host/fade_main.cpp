@@ -2723,7 +2723,7 @@ static void clip_read(Rec &rec, uint32_t rsv, const int64_t *ref_len) {
         if (to_trim < aligned_len()) {
             while (to_trim) {
                 const uint32_t op = cig[0] & 15;
-                if (q_consuming(op)) { sb++; hard++; }
+                if (q_consuming(op)) { if (sb < se) sb++; hard++; }  // (a CIGAR may claim more bases than l_seq holds: none left, none taken)
                 if (r_consuming(op)) { pos++; to_trim--; }
                 cig[0] -= 16;  // length - 1
                 if ((cig[0] >> 4) == 0) cig.erase(cig.begin());
@@ -2737,7 +2737,7 @@ static void clip_read(Rec &rec, uint32_t rsv, const int64_t *ref_len) {
         if (to_trim < aligned_len()) {
             while (to_trim) {
                 const uint32_t op = cig.back() & 15;
-                if (q_consuming(op)) { se--; hard++; }
+                if (q_consuming(op)) { if (se > sb) se--; hard++; }
                 if (r_consuming(op)) to_trim--;
                 cig.back() -= 16;
                 if ((cig.back() >> 4) == 0) cig.pop_back();

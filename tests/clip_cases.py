@@ -37,7 +37,8 @@ def build_rec(qname, tid, pos, mapq, flag, mtid, mpos, tlen, cigar, seq, qual, a
     packed = bytearray((lq + 1) // 2)
     for k, ch in enumerate(seq):
         packed[k >> 1] |= NT16.index(ch) << (4 if k % 2 == 0 else 0)
-    body = struct.pack("<iiBBHHHiiii", tid, pos, len(name), mapq, reg2bin(p0, p0 + (reflen if reflen > 0 else 1)), len(ops) & 0xffff,
+    # (bin is a 16-bit field: from 997 Mb on a level-14 bin number no longer fits and the field holds its low 16 bits)
+    body = struct.pack("<iiBBHHHiiii", tid, pos, len(name), mapq, reg2bin(p0, p0 + (reflen if reflen > 0 else 1)) & 0xffff, len(ops) & 0xffff,
                        flag, lq, mtid, mpos, tlen)
     body += name + b"".join(struct.pack("<I", (n << 4) | OPS.index(c)) for n, c in ops) + bytes(packed)
     body += bytes(ord(c) - 33 for c in qual[:lq]) + aux

@@ -96,3 +96,51 @@ def test_host_clip_read_agrees_with_pyfilter_on_the_constructed_cases(fade_bin, 
         aux = b"" if new["tags"] == {} else b"rsC" + bytes([c["rs"]]) + b"amZ" + c["rec"]["tags"]["am"][1].encode() + b"\0"
         assert got == cc.to_bam(new, aux), c["name"]
     assert at == len(raw)
+
+
+def _sam_line(rec):
+    """pyfilter's line as SAM writes it: a record without bases has `*` for them and for the qualities."""
+    from oracle import pyfilter
+    f = pyfilter._fmt(rec).split("\t")
+    if f[9] == "":
+        f[9] = f[10] = "*"
+    return "\t".join(f)
+
+
+@pytest.mark.parametrize("family", ["writer", "bins", "random"])
+def test_host_clip_read_agrees_with_pyfilter_on_the_sweep(fade_bin, tmp_path, family):
+    """tests/clip_sweep.py's generated records through `fade out -c` as SAM text and through `fade out -c -b` as bytes.  The
+    SAM reader does not hold l_seq to the CIGAR, so the records with fewer bases than their CIGAR claims go through as well,
+    and so do the unmapped records that carry a CIGAR."""
+    import gzip
+    import clip_sweep as sw
+    cases, exp = sw.cases(family, sam_only=True), sw.expected(family)
+    head = "@HD\tVN:1.6\tSO:unsorted\n" + "".join("@SQ\tSN:%s\tLN:%d\n" % (n, sw.LN) for n in cc.CONTIGS)
+    src = tmp_path / "sweep.sam"
+    src.write_text(head + "".join(_sam_line(c["rec"]) + "\n" for c in cases))
+    p = _run(["out", "-c", str(src)])
+    assert p.returncode == 0, p.stderr.decode()[-2000:]
+    lines = [l for l in p.stdout.decode().splitlines() if not l.startswith("@")]
+    assert len(lines) == len(cases)
+    bad = [(c["name"], a, _sam_line(new)) for c, a, (new, _) in zip(cases, lines, exp) if a != _sam_line(new)]
+    assert not bad, (len(bad), bad[:5])
+    pb = _run(["out", "-c", "-b", str(src)])
+    assert pb.returncode == 0, pb.stderr.decode()[-2000:]
+    raw = gzip.decompress(pb.stdout)
+    at = 8 + int.from_bytes(raw[4:8], "little")
+    n_ref = int.from_bytes(raw[at:at + 4], "little")
+    at += 4
+    for _ in range(n_ref):
+        at += 4 + int.from_bytes(raw[at:at + 4], "little") + 4
+    bad = []
+    for c, (new, _) in zip(cases, exp):
+        bs = int.from_bytes(raw[at:at + 4], "little")
+        got = raw[at:at + 4 + bs]
+        at += 4 + bs
+        aux = b"" if sw.is_reset(c, new) else b"rsC" + bytes([c["rs"]]) + b"amZ" + c["rec"]["tags"]["am"][1].encode() + b"\0"
+        want = cc.to_bam(new, aux)
+        if got != want:
+            d, w = cc.decode_rec(got), cc.decode_rec(want)
+            bad.append((c["name"],) + next(((k, d[k], w[k]) for k in w if d[k] != w[k]), ("bytes", got[:48].hex(), want[:48].hex())))
+    assert not bad, (len(bad), bad[:5])
+    assert at == len(raw)
