@@ -153,6 +153,9 @@ int fadehip_eject_batch(fadehip_ctx* ctx, int n, const(ubyte)* recs, const(long)
 /// trim_left / trim_right the reference bases those ops take.  More ops than cig_cap: FADEHIP_E_INVALID, nothing written
 int fadehip_tags_batch(fadehip_ctx* ctx, int n, const(ubyte)* recs, const(long)* rec_off, int n_ref, const(char*)* ref_names,
         ubyte* rs, ubyte* have, int* trim_left, int* trim_right, int* art_tid, long* art_pos, long* cig_off, uint* cig, long cig_cap);
+/// The rows of `fade stats` (which = FADEHIP_BAM_REPORT_STATS) or `fade stats-clip` (FADEHIP_BAM_REPORT_CLIP) over records annotated earlier, as TSV text written on the device; row_off [2n + 1]: slot 2k is record k's left side, 2k + 1 its right side
+int fadehip_report_batch(fadehip_ctx* ctx, int which, int n, const(ubyte)* recs, const(long)* rec_off, int n_ref, const(char*)* ref_names,
+                         ubyte* out_, long out_cap, long* row_off);
 /// order[j]: the record that comes j-th in stable coordinate order — by (refID, pos + 1) as unsigned, ties in the order given
 int fadehip_coord_order_batch(fadehip_ctx* ctx, int n, const(ubyte)* recs, const(long)* rec_off, int* order);
 /// A set of read names resident on the device (`fade out --fragments`): exact, growing; records in the shapes fadehip_eject_batch takes.
@@ -212,6 +215,8 @@ enum FADEHIP_BAM_FROM_TAGS = 64;  /// ... the records were annotated earlier: rs
 enum FADEHIP_BAM_COLLECT_NAMES = 128;  /// ... with FROM_TAGS: every record with an integer rs and rs & 6 adds its name to the attached set
 enum FADEHIP_BAM_EJECT_NAMED = 256;    /// ... with FROM_TAGS: a record is written exactly when its name is not in the attached set (both: with STORED / NO_OUTPUT only)
 enum FADEHIP_BAM_KEEP_SORTED = 512;    /// ... with CLIP (beside it STORED, EXTRACT, FROM_TAGS only), coordinate-sorted input: the records leave in stable order by (refID, pos + 1) as unsigned, a held tail staying on the device between calls
+enum FADEHIP_BAM_REPORT_STATS = 1024;  /// ... with FROM_TAGS | NO_OUTPUT (beside them STORED only): every call also leaves the rows of `fade stats` over its records (fadehip_bam_back_report); also `which` of fadehip_report_batch
+enum FADEHIP_BAM_REPORT_CLIP = 2048;   /// ... the same for `fade stats-clip`; the two may be set together
 enum FADEHIP_BAM_CLIP = 4;       /// ... artifact calls leave hard-clipped (`fade annotate -c`), by this run's rs and alignments
 int fadehip_bam_open(fadehip_ctx* ctx, const(fadehip_bam_config)* cfg, fadehip_bam_stream** out_);
 /// the set of the same ctx a COLLECT_NAMES stream adds to / an EJECT_NAMED stream looks up in; before the first front call
@@ -222,6 +227,8 @@ int fadehip_bam_front_raw(fadehip_bam_stream* st, const(void)* payload, size_t n
 int fadehip_bam_back(fadehip_bam_stream* st, const(ubyte)** out_, size_t* out_bytes);
 /// FADEHIP_BAM_EXTRACT: the extract records (uncompressed BAM records, pinned memory) of the call the most recent back finished
 int fadehip_bam_back_extract(fadehip_bam_stream* st, const(ubyte)** recs, size_t* n_bytes, long* n_records);
+/// With FADEHIP_BAM_REPORT_STATS / _CLIP (which: one of the two): the report's rows of the call the most recent back finished, TSV lines without a header line, in pinned memory
+int fadehip_bam_back_report(fadehip_bam_stream* st, int which, const(ubyte)** text, size_t* n_bytes, long* n_rows);
 int fadehip_bam_totals(fadehip_bam_stream* st, long* stats8, long* n_records, long* n_oversize);
 /// FADEHIP_BAM_EJECT: records not written, over the calls back has taken
 int fadehip_bam_ejected(fadehip_bam_stream* st, long* n_ejected);

@@ -35,11 +35,13 @@ EXPORTS = [
     "fadehip_bam_prepare", "fadehip_sw_stats_batch", "fadehip_clip_batch", "fadehip_extract_batch", "fadehip_bam_back_extract",
     "fadehip_eject_batch", "fadehip_bam_ejected", "fadehip_genome_upload_fasta", "fadehip_genome_fetch", "fadehip_tags_batch",
     "fadehip_nameset_create", "fadehip_nameset_add_batch", "fadehip_nameset_contains_batch", "fadehip_nameset_count", "fadehip_nameset_destroy",
-    "fadehip_bam_use_nameset", "fadehip_bam_held", "fadehip_coord_order_batch",
+    "fadehip_bam_use_nameset", "fadehip_bam_held", "fadehip_coord_order_batch", "fadehip_report_batch",
+    "fadehip_bam_back_report",
 ]
 BAM_STORED, BAM_NO_OUTPUT, BAM_CLIP, BAM_EXTRACT, BAM_EJECT, BAM_EJECT_GROUPS, BAM_FROM_TAGS = 1, 2, 4, 8, 16, 32, 64  # fadehip_bam_config.flags
 BAM_COLLECT_NAMES, BAM_EJECT_NAMED = 128, 256
 BAM_KEEP_SORTED = 512
+BAM_REPORT_STATS, BAM_REPORT_CLIP = 1024, 2048  # ... and `which` of fadehip_report_batch / fadehip_bam_back_report
 BGZF_BLOCK = 0xff00
 BGZF_LANES = 2
 
@@ -138,6 +140,7 @@ def load():
     L.fadehip_extract_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]
     L.fadehip_eject_batch.argtypes = [vp, i32, vp, vp, vp, C.c_int, vp]
     L.fadehip_tags_batch.argtypes = [vp, i32, vp, vp, i32, C.POINTER(C.c_char_p), vp, vp, vp, vp, vp, vp, vp, vp, i64]
+    L.fadehip_report_batch.argtypes = [vp, i32, i32, vp, vp, i32, C.POINTER(C.c_char_p), vp, i64, vp]
     L.fadehip_nameset_create.argtypes = [vp, C.POINTER(vp)]
     L.fadehip_nameset_add_batch.argtypes = [vp, i32, vp, vp, vp]
     L.fadehip_nameset_contains_batch.argtypes = [vp, i32, vp, vp, vp]
@@ -165,6 +168,7 @@ def load():
     L.fadehip_bam_front_raw.argtypes = [vp, vp, C.c_size_t, C.c_int]
     L.fadehip_bam_back.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.fadehip_bam_back_extract.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(i64)]
+    L.fadehip_bam_back_report.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(i64)]
     L.fadehip_bam_ejected.argtypes = [vp, C.POINTER(i64)]
     L.fadehip_bam_held.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     L.fadehip_coord_order_batch.argtypes = [vp, i32, vp, vp, vp]

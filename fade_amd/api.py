@@ -256,6 +256,36 @@ class Context:
         cat = np.frombuffer(b"".join(rb), dtype=np.uint8) if off[-1] else np.zeros(0, np.uint8)
         return self.tags_batch_packed(cat, off, ref_names)
 
+    # ---- stats.d:75-186, noclip.d:17-73: the rows of `fade stats` / `fade stats-clip` over annotated records, written on the device
+    def report_batch_packed(self, recs, rec_off, ref_names, which, out_cap=None):
+        """fadehip_report_batch: which is "stats" or "clip".  Returns (text, row_off): the TSV rows without a header line as
+        bytes, and int64[2n + 1] offsets into them — slot 2k is record k's left side, 2k + 1 its right side, a slot without a
+        row takes no bytes.  out_cap: the bytes the rows may take (default: a bound from the records' bytes)."""
+        flag = {"stats": _lib.BAM_REPORT_STATS, "clip": _lib.BAM_REPORT_CLIP}[which]
+        recs = np.ascontiguousarray(recs, dtype=np.uint8)
+        rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
+        n = len(rec_off) - 1
+        if out_cap is None:  # (a row's long columns are copies of bytes of its record, at most seven of them)
+            out_cap = 16 * len(recs) + 1024 * max(n, 0) + 1024
+        names = [x.encode() if isinstance(x, str) else bytes(x) for x in ref_names]
+        arr = (C.c_char_p * max(len(names), 1))(*names)
+        out = np.zeros(int(out_cap), np.uint8)
+        row_off = np.zeros(2 * max(n, 0) + 1, np.int64)
+        self._chk(self._L.fadehip_report_batch(self._h, flag, n, recs.ctypes.data if recs.nbytes else None, rec_off.ctypes.data, len(names), arr,
+                                               out.ctypes.data if out_cap else None, int(out_cap), row_off.ctypes.data))
+        return out[:row_off[-1]].tobytes(), row_off
+
+    def report_batch(self, records, ref_names, which):
+        """report_batch_packed over BAM records given as a list of bytes (block_size first).  which: "stats" or "clip" gives
+        the report's rows as bytes; "both" gives the pair (stats, clip), each what the call for it alone gives."""
+        rb = [bytes(r) for r in records]
+        off = np.zeros(len(rb) + 1, dtype=np.int64)
+        np.cumsum([len(r) for r in rb], out=off[1:])
+        cat = np.frombuffer(b"".join(rb), dtype=np.uint8) if off[-1] else np.zeros(0, np.uint8)
+        if which == "both":
+            return tuple(self.report_batch_packed(cat, off, ref_names, w)[0] for w in ("stats", "clip"))
+        return self.report_batch_packed(cat, off, ref_names, which)[0]
+
     def coord_order_batch(self, recs, rec_off):
         """fadehip_coord_order_batch: the stable coordinate order of BAM records (recs: uint8, concatenated; rec_off: n + 1
         offsets) by (refID, pos + 1) as unsigned.  Returns int32[n]: order[j] is the record that comes j-th."""
@@ -477,7 +507,7 @@ class Context:
         return self.bgzf_deflate_wait(lane)
 
     def bam_stream(self, ref_names, floor_len=5, window=300, first_record=0, stored=False, tail_trim=0, no_output=False, clip=False, extract=False, eject=None, from_tags=False,
-                   collect_names=None, eject_named=None, keep_sorted=False):
+                   collect_names=None, eject_named=None, keep_sorted=False, report=None):
         """The file path on the device (fadehip_bam_*): BGZF members of a BAM's records in, BGZF members of the annotated
         records out.  ref_names: the BAM header's contigs (the genome must be uploaded).  clip: records called artifacts leave
         hard-clipped (`fade annotate -c`).  extract: every call also builds `fade extract`'s records of its artifact calls
@@ -492,9 +522,11 @@ class Context:
         set / a record is written exactly when its name is not in the set.  True instead of a set sets the flag alone (the
         first front() then fails: no set is attached).  keep_sorted (with clip; beside it stored, extract and from_tags only):
         coordinate-sorted input leaves in coordinate order — a clipped record at its new position, a reset one at the end —
-        with a small tail held on the device between calls; BamStream.held() counts it."""
+        with a small tail held on the device between calls; BamStream.held() counts it.  report ("stats", "clip" or "both";
+        with from_tags and no_output, beside them stored only): `fade stats` / `fade stats-clip` — every call also leaves the
+        rows of the report(s) over its records; BamStream.report(which) fetches them after each back()."""
         return BamStream(self, ref_names, floor_len, window, first_record, stored, tail_trim, no_output, clip, extract, eject, from_tags,
-                         collect_names, eject_named, keep_sorted)
+                         collect_names, eject_named, keep_sorted, report)
 
     def bgzf_inflate(self, members, out_cap=None):
         """Whole BGZF members (bytes / uint8 array) -> their payloads, inflated on the device (CRC32 and ISIZE checked)."""
@@ -629,15 +661,18 @@ def format_tags(batch, contig_names, rs, aln):
 
 class BamStream:
     def __init__(self, ctx, ref_names, floor_len, window, first_record, stored=False, tail_trim=0, no_output=False, clip=False, extract=False, eject=None, from_tags=False,
-                 collect_names=None, eject_named=None, keep_sorted=False):
+                 collect_names=None, eject_named=None, keep_sorted=False, report=None):
         self._ctx, self._L = ctx, ctx._L
+        if report not in (None, "stats", "clip", "both"):
+            raise ValueError('report is None, "stats", "clip" or "both"')
+        rp = (_lib.BAM_REPORT_STATS if report in ("stats", "both") else 0) | (_lib.BAM_REPORT_CLIP if report in ("clip", "both") else 0)
         if eject not in (None, False, "records", "groups"):
             raise ValueError('eject is None, "records" or "groups"')
         ej = BAM_EJECT | BAM_EJECT_GROUPS if eject == "groups" else BAM_EJECT if eject == "records" else 0
         names = [n.encode() if isinstance(n, str) else bytes(n) for n in ref_names]
         arr = (C.c_char_p * max(len(names), 1))(*names)
         cfg = _lib.BamConfig(floor_len, window, len(names), (_lib.BAM_STORED if stored else 0) | (_lib.BAM_NO_OUTPUT if no_output else 0) | (_lib.BAM_CLIP if clip else 0) | (_lib.BAM_EXTRACT if extract else 0) | (BAM_FROM_TAGS if from_tags else 0) | ej |
-                             (_lib.BAM_COLLECT_NAMES if collect_names else 0) | (_lib.BAM_EJECT_NAMED if eject_named else 0) | (_lib.BAM_KEEP_SORTED if keep_sorted else 0), arr, first_record, tail_trim)
+                             (_lib.BAM_COLLECT_NAMES if collect_names else 0) | (_lib.BAM_EJECT_NAMED if eject_named else 0) | (_lib.BAM_KEEP_SORTED if keep_sorted else 0) | rp, arr, first_record, tail_trim)
         h = C.c_void_p()
         ctx._chk(self._L.fadehip_bam_open(ctx._h, C.byref(cfg), C.byref(h)))
         self._h = h
@@ -676,6 +711,13 @@ class BamStream:
         """The extract records of the call the last back() finished: (uncompressed BAM records as bytes, their number)."""
         p, n, nr = C.c_void_p(), C.c_size_t(0), C.c_int64(0)
         self._ctx._chk(self._L.fadehip_bam_back_extract(self._h, C.byref(p), C.byref(n), C.byref(nr)))
+        return (C.string_at(p, n.value) if n.value else b""), int(nr.value)
+
+    def report(self, which):
+        """The rows ("stats" or "clip") of the call the last back() finished: (TSV lines without a header line as bytes, their number)."""
+        p, n, nr = C.c_void_p(), C.c_size_t(0), C.c_int64(0)
+        flag = {"stats": _lib.BAM_REPORT_STATS, "clip": _lib.BAM_REPORT_CLIP}[which]
+        self._ctx._chk(self._L.fadehip_bam_back_report(self._h, flag, C.byref(p), C.byref(n), C.byref(nr)))
         return (C.string_at(p, n.value) if n.value else b""), int(nr.value)
 
     def ejected(self):

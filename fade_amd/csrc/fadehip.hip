@@ -1099,6 +1099,43 @@ int finish_run(fadehip_ctx *ctx, Slot &s, int slot) {
 
 }  // namespace fadehip::host
 
+namespace fadehip::host {
+
+// The launches of sw_stats_kernel over a work list that lies class behind class (cls_begin [6]: R = 1, 2, 4, 8 rows per lane
+// in one strip, then the multi-strip class), for fadehip_sw_stats_batch and the reports of bam_report.hpp.  Multi-strip
+// pairs: a scratch row of long_max_lr entries per wave, at most 256 MB of them.
+int sw_stats_long_blocks(size_t n_long, int long_max_lr, size_t *row_bytes) {
+    *row_bytes = (size_t)std::max(long_max_lr, 1) * 2 * sizeof(int4);
+    if (!n_long) return 0;
+    const size_t waves = std::max<size_t>(1, std::min<size_t>({n_long, ((size_t)256 << 20) / *row_bytes, (size_t)2048}));
+    return (int)((waves + STATS_WAVES_PER_BLOCK - 1) / STATS_WAVES_PER_BLOCK);
+}
+int enqueue_sw_stats(fadehip_ctx *ctx, hipStream_t st, const StatsWork *d_work, const size_t cls_begin[6], const uint8_t *d_q,
+                     const uint8_t *d_r, fadehip_sw_stats_result *d_out, void *scratch, int long_max_lr, int long_blocks, const StatsScoring &sc) {
+    const dim3 blk(64 * STATS_WAVES_PER_BLOCK);
+    for (int c = 0; c < 5; c++) {
+        const size_t cnt = cls_begin[c + 1] - cls_begin[c];
+        if (!cnt) continue;
+        const StatsWork *wk = d_work + cls_begin[c];
+        if (c == 4) {
+            hipLaunchKernelGGL(sw_stats_kernel<STATS_STRIP_R>, dim3((unsigned)long_blocks), blk, 0, st, wk, (int32_t)cnt, d_q, d_r,
+                               d_out, (int4 *)scratch, std::max(long_max_lr, 1), sc);
+        } else {
+            const unsigned g = (unsigned)std::min<size_t>((cnt + STATS_WAVES_PER_BLOCK - 1) / STATS_WAVES_PER_BLOCK, 16384);
+            switch (c) {
+            case 0: hipLaunchKernelGGL(sw_stats_kernel<1>, dim3(g), blk, 0, st, wk, (int32_t)cnt, d_q, d_r, d_out, (int4 *)nullptr, 0, sc); break;
+            case 1: hipLaunchKernelGGL(sw_stats_kernel<2>, dim3(g), blk, 0, st, wk, (int32_t)cnt, d_q, d_r, d_out, (int4 *)nullptr, 0, sc); break;
+            case 2: hipLaunchKernelGGL(sw_stats_kernel<4>, dim3(g), blk, 0, st, wk, (int32_t)cnt, d_q, d_r, d_out, (int4 *)nullptr, 0, sc); break;
+            default: hipLaunchKernelGGL(sw_stats_kernel<8>, dim3(g), blk, 0, st, wk, (int32_t)cnt, d_q, d_r, d_out, (int4 *)nullptr, 0, sc); break;
+            }
+        }
+        HIPCHK(ctx, hipGetLastError());
+    }
+    return 0;
+}
+
+}  // namespace fadehip::host
+
 extern "C" {
 
 // ------------------------------------------------------------------------------- level 1
@@ -1284,14 +1321,8 @@ int fadehip_sw_stats_batch(fadehip_ctx *ctx, const int32_t scoring[4], int32_t n
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (!ctx->stats_stream) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->stats_stream, hipStreamNonBlocking));
     hipStream_t st = ctx->stats_stream;
-    // multi-strip pairs: a scratch row of long_max_lr entries per wave, at most 256 MB of them
-    const size_t row_bytes = (size_t)std::max(long_max_lr, 1) * 2 * sizeof(int4);
-    const size_t n_long = cls_begin[5] - cls_begin[4];
-    int long_blocks = 0;
-    if (n_long) {
-        const size_t waves = std::max<size_t>(1, std::min<size_t>({n_long, ((size_t)256 << 20) / row_bytes, (size_t)2048}));
-        long_blocks = (int)((waves + STATS_WAVES_PER_BLOCK - 1) / STATS_WAVES_PER_BLOCK);
-    }
+    size_t row_bytes;
+    const int long_blocks = sw_stats_long_blocks(cls_begin[5] - cls_begin[4], long_max_lr, &row_bytes);
     int rc = 0;
     if ((rc = reserve(ctx, ctx->st_q, (size_t)q_total + 1)) || (rc = reserve(ctx, ctx->st_r, (size_t)r_total + 1)) ||
         (rc = reserve(ctx, ctx->st_work, (size_t)n * sizeof(StatsWork))) ||
@@ -1307,28 +1338,10 @@ int fadehip_sw_stats_batch(fadehip_ctx *ctx, const int32_t scoring[4], int32_t n
     sc.match = match;
     sc.mismatch = mismatch;
     sc.rules = ctx->sc.rules;
-    const StatsWork *d_work = (const StatsWork *)ctx->st_work.p;
-    const uint8_t *d_q = (const uint8_t *)ctx->st_q.p, *d_r = (const uint8_t *)ctx->st_r.p;
     fadehip_sw_stats_result *d_out = (fadehip_sw_stats_result *)ctx->st_out.p;
-    const dim3 blk(64 * STATS_WAVES_PER_BLOCK);
-    for (int c = 0; c < 5; c++) {
-        const size_t cnt = cls_begin[c + 1] - cls_begin[c];
-        if (!cnt) continue;
-        const StatsWork *wk = d_work + cls_begin[c];
-        if (c == 4) {
-            hipLaunchKernelGGL(sw_stats_kernel<STATS_STRIP_R>, dim3((unsigned)long_blocks), blk, 0, st, wk, (int32_t)cnt, d_q, d_r,
-                               d_out, (int4 *)ctx->st_scratch.p, std::max(long_max_lr, 1), sc);
-        } else {
-            const unsigned g = (unsigned)std::min<size_t>((cnt + STATS_WAVES_PER_BLOCK - 1) / STATS_WAVES_PER_BLOCK, 16384);
-            switch (c) {
-            case 0: hipLaunchKernelGGL(sw_stats_kernel<1>, dim3(g), blk, 0, st, wk, (int32_t)cnt, d_q, d_r, d_out, (int4 *)nullptr, 0, sc); break;
-            case 1: hipLaunchKernelGGL(sw_stats_kernel<2>, dim3(g), blk, 0, st, wk, (int32_t)cnt, d_q, d_r, d_out, (int4 *)nullptr, 0, sc); break;
-            case 2: hipLaunchKernelGGL(sw_stats_kernel<4>, dim3(g), blk, 0, st, wk, (int32_t)cnt, d_q, d_r, d_out, (int4 *)nullptr, 0, sc); break;
-            default: hipLaunchKernelGGL(sw_stats_kernel<8>, dim3(g), blk, 0, st, wk, (int32_t)cnt, d_q, d_r, d_out, (int4 *)nullptr, 0, sc); break;
-            }
-        }
-        HIPCHK(ctx, hipGetLastError());
-    }
+    if ((rc = enqueue_sw_stats(ctx, st, (const StatsWork *)ctx->st_work.p, cls_begin, (const uint8_t *)ctx->st_q.p, (const uint8_t *)ctx->st_r.p, d_out,
+                               ctx->st_scratch.p, long_max_lr, long_blocks, sc)))
+        return rc;
     HIPCHK(ctx, hipMemcpyAsync(out, d_out, (size_t)n * sizeof(fadehip_sw_stats_result), hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     return 0;

@@ -6,6 +6,7 @@
 #include "bam_device.hpp"
 #include "bam_from_tags.hpp"
 #include "bam_names.hpp"
+#include "bam_report.hpp"
 #include "bam_resort.hpp"
 #include <algorithm>
 #include <chrono>
@@ -13,7 +14,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <new>
+#include <string>
 #include <thread>
 
 using namespace fadehip;
@@ -454,6 +457,164 @@ int fadehip_tags_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const i
     return 0;
 }
 
+// ---- `fade stats` / `fade stats-clip` over records the caller brings (bam_report.hpp)
+namespace {
+
+// what a failed report call says of the record the stage named (RepCtl::bad)
+int report_bad(fadehip_ctx *ctx, unsigned long long bad, long long first_record) {
+    const long long rec = first_record + (long long)(0xffffffffu - (uint32_t)(bad >> 8));
+    const uint32_t kind = (uint32_t)(bad & 0xffu);
+    if (kind == bam::RP_BAD_LONG)
+        return set_err(ctx, FADEHIP_E_UNSUPPORTED, "report: record %lld: a piece of as / ar is longer than %d bytes", rec, FADEHIP_MAX_LONG_QUERY);
+    const char *what = kind == bam::RP_BAD_AUX         ? "its aux area is not whole fields"
+                       : kind == bam::RP_BAD_SIDE      ? "rs names a side of am that is not name,pos,cigar with pos in int32"
+                       : kind == bam::RP_BAD_ART_TAGS  ? "as, ar or ab is absent or not of type Z"
+                       : kind == bam::RP_BAD_PIECE     ? "as or ar has no piece for the side rs names, or the as piece is empty"
+                       : kind == bam::RP_BAD_AB        ? "ab is shorter than the side's piece of as"
+                       : kind == bam::RP_BAD_NO_S      ? "an artifact record without a soft clip"
+                       : kind == bam::RP_BAD_TID       ? "an artifact record whose refID is outside the header"
+                       : kind == bam::RP_BAD_CLIP_EMPTY ? "a soft-clipped record without bases (l_seq 0)"
+                                                        : "a soft clip longer than the read";
+    return set_err(ctx, FADEHIP_E_INVALID, "report: record %lld: %s", rec, what);
+}
+
+// The arrays of a call's reports (`which`: RP_* bits) over n records, one behind the other from `base` (nullptr: only their
+// size is wanted): ctl | per report: row_off [2n + 1] u64 | size [2n] u64 | the rows' descriptors [2n] | (stats) work [2n] | res [2n] |
+// kind [2n] u8, padded
+size_t report_layout(bam::RepArgs &a, uint8_t *base, size_t n, uint32_t which) {
+    const size_t ns = 2 * n;
+    size_t at = 128;
+    auto take = [&](size_t bytes) {
+        uint8_t *p = base ? base + at : nullptr;
+        at += (bytes + 7) & ~(size_t)7;
+        return p;
+    };
+    a.ctl = (bam::RepCtl *)base;
+    for (uint32_t w = 0; w < 2u; w++) {
+        if (!(which & (1u << w))) continue;
+        a.row_off[w] = (uint64_t *)take(8 * (ns + 1));
+        a.size[w] = (uint64_t *)take(8 * ns);
+        if (w == 0u) {
+            a.srow = (bam::StatsRow *)take(ns * sizeof(bam::StatsRow));
+            a.work = (StatsWork *)take(ns * sizeof(StatsWork));
+            a.res = (fadehip_sw_stats_result *)take(ns * sizeof(fadehip_sw_stats_result));
+        } else {
+            a.crow = (bam::ClipRow *)take(ns * sizeof(bam::ClipRow));
+        }
+        a.kind[w] = take(ns);
+    }
+    return at + 8;
+}
+
+// The kernels of one report (w: 0 stats, 1 clip) behind the stage, whose ctl `c` is on the host: the stats sides' pairs and
+// their alignments class by class, the rows' sizes, the scan.  `scratch` holds the multi-strip pairs' rows.
+int enqueue_report_sizes(fadehip_ctx *ctx, hipStream_t st, bam::RepArgs &a, uint32_t w, const bam::RepCtl &c, DevBuf &scratch) {
+    const size_t ns = 2 * (size_t)a.n;
+    if (w == 0u) {
+        size_t cls_begin[6] = {0, 0, 0, 0, 0, 0};
+        for (int k = 0; k < 5; k++) cls_begin[k + 1] = cls_begin[k] + c.cls[k];
+        if (cls_begin[5]) {
+            size_t row_bytes;
+            const int long_blocks = sw_stats_long_blocks(c.cls[4], (int)c.long_max_lr, &row_bytes);
+            int rc;
+            if (long_blocks && (rc = reserve(ctx, scratch, (size_t)long_blocks * STATS_WAVES_PER_BLOCK * row_bytes))) return rc;
+            hipLaunchKernelGGL(bam::report_bucket_kernel, dim3((unsigned)((ns + bam::TAG_BLOCK - 1) / bam::TAG_BLOCK)), dim3(bam::TAG_BLOCK), 0, st, a);
+            HIPCHK(ctx, hipGetLastError());
+            StatsScoring sc;  // stats.d:87
+            sc.open = 3;
+            sc.ext = 8;
+            sc.match = 10;
+            sc.mismatch = -5;
+            sc.rules = ctx->sc.rules;
+            if ((rc = enqueue_sw_stats(ctx, st, a.work, cls_begin, a.base, a.base, a.res, scratch.p, (int)c.long_max_lr, long_blocks, sc))) return rc;
+        }
+    }
+    hipLaunchKernelGGL(bam::report_size_kernel, dim3((unsigned)((ns + 15) / 16)), dim3(256), 0, st, a, w);
+    HIPCHK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(bam::report_scan_kernel, dim3(1), dim3(1024), 0, st, a, w);
+    HIPCHK(ctx, hipGetLastError());
+    return 0;
+}
+
+}  // namespace
+
+int fadehip_report_batch(fadehip_ctx *ctx, int32_t which, int32_t n, const uint8_t *recs, const int64_t *rec_off, int32_t n_ref,
+                         const char *const *ref_names, uint8_t *out, int64_t out_cap, int64_t *row_off) {
+    if (!ctx) return set_err(nullptr, FADEHIP_E_INVALID, "ctx is NULL");
+    if (which != FADEHIP_BAM_REPORT_STATS && which != FADEHIP_BAM_REPORT_CLIP)
+        return set_err(ctx, FADEHIP_E_INVALID, "which must be FADEHIP_BAM_REPORT_STATS or FADEHIP_BAM_REPORT_CLIP");
+    if (n < 0 || n > (1 << 30) || n_ref < 0 || (n_ref > 0 && !ref_names) || !rec_off || !row_off || (n > 0 && !recs) || out_cap < 0 || (out_cap > 0 && !out))
+        return set_err(ctx, FADEHIP_E_INVALID, "NULL argument");
+    if (rec_off[0] < 0) return set_err(ctx, FADEHIP_E_INVALID, "offsets must be non-negative and non-decreasing (record 0)");
+    if (n == 0) {
+        row_off[0] = 0;
+        return 0;
+    }
+    int rc;
+    if ((rc = check_records(ctx, n, recs, rec_off, true, [](int32_t) { return 0; }))) return rc;
+    std::vector<uint32_t> noff((size_t)n_ref + 1, 0u);
+    std::vector<int32_t> first((size_t)n_ref);
+    std::string nbytes;
+    {
+        std::map<std::string, int32_t> seen;
+        for (int32_t c = 0; c < n_ref; c++) {
+            if (!ref_names[c]) return set_err(ctx, FADEHIP_E_INVALID, "ref_names[%d] is NULL", c);
+            const std::string nm(ref_names[c]);
+            if (nbytes.size() + nm.size() > 0x7fffffffu) return set_err(ctx, FADEHIP_E_INVALID, "the contig names take more than 2^31 bytes");
+            first[(size_t)c] = seen.emplace(nm, c).first->second;
+            nbytes += nm;
+            noff[(size_t)c + 1] = (uint32_t)nbytes.size();
+        }
+    }
+    const uint32_t w = which == FADEHIP_BAM_REPORT_STATS ? 0u : 1u;
+    const size_t ns = 2 * (size_t)n, ntb = ((size_t)n + bam::TAG_BLOCK - 1) / bam::TAG_BLOCK;
+    BatchLane &L = ctx->batch;
+    std::lock_guard<std::mutex> lk(L.mu);
+    // meta: in_off [n + 1] u64 | name_off [n_ref + 1] u32 | first [n_ref] i32 | name bytes;  work: report_layout
+    const size_t m_noff = 8 * ((size_t)n + 1), m_first = m_noff + 4 * ((size_t)n_ref + 1), m_names = m_first + 4 * (size_t)n_ref;
+    bam::RepArgs a;
+    memset(&a, 0, sizeof a);
+    a.which = w == 0u ? bam::RP_STATS : bam::RP_CLIP;
+    std::vector<uint64_t> off;
+    if ((rc = batch_upload(ctx, L, n, recs, rec_off, nullptr, 0, m_names + nbytes.size() + 8, report_layout(a, nullptr, (size_t)n, a.which), off))) return rc;
+    hipStream_t st = L.stream;
+    uint8_t *meta = (uint8_t *)L.meta.p, *work = (uint8_t *)L.work.p;
+    HIPCHK(ctx, hipMemcpyAsync(meta + m_noff, noff.data(), 4 * noff.size(), hipMemcpyHostToDevice, st));
+    if (n_ref) HIPCHK(ctx, hipMemcpyAsync(meta + m_first, first.data(), 4 * (size_t)n_ref, hipMemcpyHostToDevice, st));
+    if (!nbytes.empty()) HIPCHK(ctx, hipMemcpyAsync(meta + m_names, nbytes.data(), nbytes.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemsetAsync(work, 0, 128, st));
+    report_layout(a, work, (size_t)n, a.which);
+    a.base = (const uint8_t *)L.in.p;
+    a.off64 = (const uint64_t *)meta;
+    a.n = (uint32_t)n;
+    a.names.bytes = meta + m_names;
+    a.names.off = (const uint32_t *)(meta + m_noff);
+    a.names.first = (const int32_t *)(meta + m_first);
+    a.names.n_ref = n_ref;
+    hipLaunchKernelGGL(bam::report_stage_kernel, dim3((unsigned)ntb), dim3(bam::TAG_BLOCK), 0, st, a);
+    HIPCHK(ctx, hipGetLastError());
+    bam::RepCtl c;
+    HIPCHK(ctx, hipMemcpyAsync(&c, a.ctl, sizeof c, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));  // wait 1: what fails the call, the stats sides per class
+    if (c.bad) return report_bad(ctx, c.bad, 0);
+    if ((rc = enqueue_report_sizes(ctx, st, a, w, c, L.scratch))) return rc;
+    std::vector<uint64_t> roff(ns + 1);
+    HIPCHK(ctx, hipMemcpyAsync(roff.data(), a.row_off[w], 8 * (ns + 1), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));  // wait 2: the rows' offsets
+    const uint64_t total = roff[ns];
+    if (total > (uint64_t)out_cap)
+        return set_err(ctx, FADEHIP_E_INVALID, "the report's rows take %llu bytes, out holds %lld", (unsigned long long)total, (long long)out_cap);
+    for (size_t q = 0; q <= ns; q++) row_off[q] = (int64_t)roff[q];
+    if (!total) return 0;
+    if ((rc = reserve(ctx, L.out, (size_t)total + 8))) return rc;
+    a.out[w] = (uint8_t *)L.out.p;
+    hipLaunchKernelGGL(bam::report_write_kernel, dim3((unsigned)((ns + 15) / 16)), dim3(256), 0, st, a, w);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(out, a.out[w], (size_t)total, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));  // wait 3: the rows
+    return 0;
+}
+
 // ---- the name set over records the caller brings: bam_names.hpp's kernels, the ones of the file path under
 // FADEHIP_BAM_COLLECT_NAMES / FADEHIP_BAM_EJECT_NAMED
 int fadehip_nameset_create(fadehip_ctx *ctx, fadehip_nameset **out) {
@@ -583,6 +744,7 @@ struct fadehip_bam_stream {
     bool collect_names = false;  // FADEHIP_BAM_COLLECT_NAMES: from_tags, and every record with rs & 6 adds its name to `names` (bam_names.hpp)
     bool eject_named = false;    // FADEHIP_BAM_EJECT_NAMED: from_tags, and a record is written exactly when its name is not in `names`
     bool keep_sorted = false;    // FADEHIP_BAM_KEEP_SORTED: clip, and the records leave in coordinate order (bam_resort.hpp)
+    uint32_t report = 0;         // FADEHIP_BAM_REPORT_STATS / _CLIP as bam::RP_*: from_tags, and every call leaves the reports' rows (bam_report.hpp)
     fadehip_nameset *names = nullptr;  // fadehip_bam_use_nameset
     DevBuf names_text, names_off;
     DevBuf names_first;         // from_tags: for every contig the first one of its name (fadehip_tags_batch's rule)
@@ -595,6 +757,11 @@ struct fadehip_bam_stream {
         size_t xbytes = 0;
         int64_t xrecs = 0;
         hipEvent_t xready = nullptr;
+        // report: the call's rows on the device per report (stats, clip), their bytes and number, and the event behind their copies
+        DevBuf r[2];
+        size_t rbytes[2] = {0, 0};
+        int64_t rrows[2] = {0, 0};
+        hipEvent_t rready = nullptr;
         int state = 0;  // 0 free, 1 its call's kernels are enqueued up to the tag sizes (to be finished), 2 finished: waiting for back
     } ring[FADEHIP_BAM_CHUNKS];
     // The front half, two calls in flight.  Call k lives in set k & 1 and on the ctx's slot k & 1 (a stream each):
@@ -616,6 +783,9 @@ struct fadehip_bam_stream {
         // block sums and bases, where a record's ops start, and the ops themselves (sized in back, when their total is known)
         DevBuf ft_rec, ft_side, ft_ops_blk, ft_ops_at, ft_ops;
         bam::FromTagsArgs fa;
+        DevBuf rp, rp_scratch;                // report: the arrays of report_layout; sw_stats_kernel's rows of its multi-strip pairs
+        PinBuf h_rp;                          // the RepCtl behind the stage, then behind the scans
+        bam::RepArgs rpa;
         bam::TagArgs xa;                      // extract: ta with the extract stream's sizes, sums, counts and output
         PinBuf h_blocks, h_counts;
         PinBuf h_ns;                          // collect_names / eject_named: the set's ctrl words behind the call's kernels
@@ -645,6 +815,10 @@ struct fadehip_bam_stream {
     // extract: the extract records of call k, pinned, k % (FADEHIP_BAM_CHUNKS + 1) — one more than the ring, because the copy is
     // enqueued when the call is finished, which front may do one back call before the compressor of that ring place starts
     PinBuf xbuf[FADEHIP_BAM_CHUNKS + 1];
+    PinBuf rbuf[2][FADEHIP_BAM_CHUNKS + 1];  // report: the rows of call k per report, pinned, as xbuf
+    const uint8_t *last_r[2] = {nullptr, nullptr};  // fadehip_bam_back_report: what the most recent back finished
+    size_t last_rbytes[2] = {0, 0};
+    int64_t last_rrows[2] = {0, 0};
     const uint8_t *last_x = nullptr;        // fadehip_bam_back_extract: what the most recent back finished
     size_t last_xbytes = 0;
     int64_t last_xrecs = 0;
@@ -857,6 +1031,44 @@ int bam_finish_extract(fadehip_bam_stream *st, fadehip_bam_stream::Set &S, uint6
     return 0;
 }
 
+// FADEHIP_BAM_REPORT_*, C of call k: the stage's ctl has crossed with the counts (what fails the call has been looked at); the
+// stats sides' alignments class by class, the rows' sizes and the scans — then the ONE wait a report call adds to a
+// FROM_TAGS | EXTRACT | NO_OUTPUT call, for the reports' bytes, which size the buffers the rows are written and copied into
+int bam_finish_report(fadehip_bam_stream *st, fadehip_bam_stream::Set &S, uint64_t k, hipStream_t q) {
+    fadehip_ctx *ctx = st->ctx;
+    fadehip_bam_stream::Out *out = S.out;
+    int rc;
+    for (uint32_t w = 0; w < 2u; w++) {
+        out->rbytes[w] = 0;
+        out->rrows[w] = 0;
+    }
+    if (S.n_rec) {
+        const bam::RepCtl c = *(const bam::RepCtl *)S.h_rp.p;
+        const size_t ns = 2 * (size_t)S.n_rec;
+        for (uint32_t w = 0; w < 2u; w++)
+            if ((st->report & (1u << w)) && c.rows[w] && (rc = enqueue_report_sizes(ctx, q, S.rpa, w, c, S.rp_scratch))) return rc;
+        HIPCHK(ctx, hipMemcpyAsync(S.h_rp.p, S.rpa.ctl, sizeof(bam::RepCtl), hipMemcpyDeviceToHost, q));
+        HIPCHK(ctx, hipStreamSynchronize(q));
+        const bam::RepCtl *t = (const bam::RepCtl *)S.h_rp.p;
+        for (uint32_t w = 0; w < 2u; w++) {
+            const uint64_t rb = t->total[w];
+            if (!(st->report & (1u << w)) || !c.rows[w] || !rb) continue;
+            if (rb > ((uint64_t)1 << 31)) return set_err(ctx, FADEHIP_E_UNSUPPORTED, "bam stream: %llu report bytes in one call (at most 2^31)", (unsigned long long)rb);
+            PinBuf &rh = st->rbuf[w][k % (FADEHIP_BAM_CHUNKS + 1)];
+            if ((rc = reserve_roomy(ctx, out->r[w], (size_t)rb + 256)) || (rc = reserve_pinned(ctx, rh, (size_t)rb + (size_t)rb / 4 + 256))) return rc;
+            S.rpa.out[w] = (uint8_t *)out->r[w].p;
+            hipLaunchKernelGGL(bam::report_write_kernel, dim3((unsigned)((ns + 15) / 16)), dim3(256), 0, q, S.rpa, w);
+            HIPCHK(ctx, hipGetLastError());
+            HIPCHK(ctx, hipMemcpyAsync(rh.p, out->r[w].p, (size_t)rb, hipMemcpyDeviceToHost, q));
+            out->rbytes[w] = (size_t)rb;
+            out->rrows[w] = (int64_t)c.rows[w];
+        }
+    }
+    if (!out->rready) HIPCHK(ctx, hipEventCreateWithFlags(&out->rready, hipEventDisableTiming | (ctx->blocking_sync ? hipEventBlockingSync : 0)));
+    HIPCHK(ctx, hipEventRecord(out->rready, q));
+    return 0;
+}
+
 // C of call k (see fadehip_bam_stream): waits for the call's run and tag sizes, sizes the output, enqueues the rewrite.
 // Idempotent; front and back may both arrive here for the same call.
 int bam_finish_one(fadehip_bam_stream *st, uint64_t k) {
@@ -883,6 +1095,7 @@ int bam_finish_one(fadehip_bam_stream *st, uint64_t k) {
                                kind == bam::FT_BAD_CLIP ? "rs names a side whose CIGAR is missing or does not parse"
                                : kind == bam::FT_BAD_OPS ? "a side holds more than 65535 CIGAR ops" : "rs names a side that is not name,pos,cigar");
             }
+            if (st->report && ((const bam::RepCtl *)S.h_rp.p)->bad) return report_bad(ctx, ((const bam::RepCtl *)S.h_rp.p)->bad, (long long)st->n_records);
             if (st->names && S.h_ns.p && ((const unsigned long long *)S.h_ns.p)[bam::NS_ERR])
                 return set_err(ctx, FADEHIP_E_STATE, "bam stream: the name set's table or arena was full (names may be missing: the set cannot be used)");
             for (int t = 0; t < 8; t++) st->stats[t] += (int64_t)sc->stats[t];
@@ -930,6 +1143,7 @@ int bam_finish_one(fadehip_bam_stream *st, uint64_t k) {
     if (!out->ready) HIPCHK(ctx, hipEventCreateWithFlags(&out->ready, hipEventDisableTiming | (ctx->blocking_sync ? hipEventBlockingSync : 0)));
     HIPCHK(ctx, hipEventRecord(out->ready, q));
     if (st->extract && (rc = bam_finish_extract(st, S, k, q))) return rc;
+    if (st->report && (rc = bam_finish_report(st, S, k, q))) return rc;
     S.pending = false;
     st->t_tags += now_s() - t0;
     {
@@ -1375,6 +1589,21 @@ int bam_front_tags(fadehip_bam_stream *st, fadehip_bam_stream::Set &S, Slot &s, 
     }
     hipLaunchKernelGGL(bam::bam_tag_scan_kernel, dim3(1), dim3(1024), 0, q, ta, ntb);
     HIPCHK(ctx, hipGetLastError());
+    if (st->report) {  // the reports' stage (bam_report.hpp); its ctl crosses with the counts
+        bam::RepArgs &ra = S.rpa;
+        memset(&ra, 0, sizeof ra);
+        if ((rc = reserve_roomy(ctx, S.rp, report_layout(ra, nullptr, n, st->report))) || (rc = reserve_pinned(ctx, S.h_rp, 128))) return rc;
+        report_layout(ra, (uint8_t *)S.rp.p, n, st->report);
+        ra.base = pa.u;
+        ra.off32 = pa.rec_off;
+        ra.n = n_rec;
+        ra.which = st->report;
+        ra.names = fa.names;
+        HIPCHK(ctx, hipMemsetAsync(ra.ctl, 0, 128, q));
+        hipLaunchKernelGGL(bam::report_stage_kernel, dim3(ntb), dim3(bam::TAG_BLOCK), 0, q, ra);
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipMemcpyAsync(S.h_rp.p, ra.ctl, sizeof(bam::RepCtl), hipMemcpyDeviceToHost, q));
+    }
     HIPCHK(ctx, hipMemcpyAsync(S.h_counts.p, d_counts, st->counts_bytes(), hipMemcpyDeviceToHost, q));
     S.n_sent = 0;
     S.ntb = ntb;
@@ -1443,8 +1672,13 @@ int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_ba
     if (!ctx) return set_err(nullptr, FADEHIP_E_INVALID, "ctx is NULL");
     if (!cfg || !out || cfg->n_ref < 0 || (cfg->n_ref && !cfg->ref_names) || (cfg->window < 0 && !(cfg->flags & FADEHIP_BAM_FROM_TAGS)) ||
         (cfg->flags & ~(FADEHIP_BAM_STORED | FADEHIP_BAM_NO_OUTPUT | FADEHIP_BAM_CLIP | FADEHIP_BAM_EXTRACT | FADEHIP_BAM_EJECT | FADEHIP_BAM_EJECT_GROUPS | FADEHIP_BAM_FROM_TAGS |
-                        FADEHIP_BAM_COLLECT_NAMES | FADEHIP_BAM_EJECT_NAMED | FADEHIP_BAM_KEEP_SORTED)))
+                        FADEHIP_BAM_COLLECT_NAMES | FADEHIP_BAM_EJECT_NAMED | FADEHIP_BAM_KEEP_SORTED | FADEHIP_BAM_REPORT_STATS | FADEHIP_BAM_REPORT_CLIP)))
         return set_err(ctx, FADEHIP_E_INVALID, "bam stream: bad configuration");
+    if (cfg->flags & (FADEHIP_BAM_REPORT_STATS | FADEHIP_BAM_REPORT_CLIP)) {
+        const int32_t need = FADEHIP_BAM_FROM_TAGS | FADEHIP_BAM_NO_OUTPUT;
+        if ((cfg->flags & need) != need || (cfg->flags & ~(need | FADEHIP_BAM_STORED | FADEHIP_BAM_REPORT_STATS | FADEHIP_BAM_REPORT_CLIP)))
+            return set_err(ctx, FADEHIP_E_INVALID, "bam stream: FADEHIP_BAM_REPORT_STATS and FADEHIP_BAM_REPORT_CLIP need FADEHIP_BAM_FROM_TAGS | FADEHIP_BAM_NO_OUTPUT and combine with STORED only");
+    }
     if (cfg->flags & FADEHIP_BAM_KEEP_SORTED) {
         if (!(cfg->flags & FADEHIP_BAM_CLIP)) return set_err(ctx, FADEHIP_E_INVALID, "bam stream: FADEHIP_BAM_KEEP_SORTED needs FADEHIP_BAM_CLIP (without a clip nothing moves)");
         if (cfg->flags & ~(FADEHIP_BAM_KEEP_SORTED | FADEHIP_BAM_CLIP | FADEHIP_BAM_STORED | FADEHIP_BAM_EXTRACT | FADEHIP_BAM_FROM_TAGS))
@@ -1478,6 +1712,7 @@ int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_ba
     st->collect_names = (cfg->flags & FADEHIP_BAM_COLLECT_NAMES) != 0;
     st->eject_named = (cfg->flags & FADEHIP_BAM_EJECT_NAMED) != 0;
     st->keep_sorted = (cfg->flags & FADEHIP_BAM_KEEP_SORTED) != 0;
+    st->report = ((cfg->flags & FADEHIP_BAM_REPORT_STATS) ? bam::RP_STATS : 0u) | ((cfg->flags & FADEHIP_BAM_REPORT_CLIP) ? bam::RP_CLIP : 0u);
     std::string text;
     std::vector<uint32_t> off((size_t)cfg->n_ref + 1, 0);
     for (int k = 0; k < cfg->n_ref; k++) {
@@ -1709,6 +1944,15 @@ int fadehip_bam_back(fadehip_bam_stream *st, const uint8_t **out, size_t *out_by
         st->last_xrecs = o->xrecs;
         st->have_back = true;
     }
+    if (st->report) {
+        if (o->rready && hipEventSynchronize(o->rready) != hipSuccess) return bam_fail(st, set_err(ctx, FADEHIP_E_HIP, "bam stream: copying the reports' rows failed"));
+        for (uint32_t w = 0; w < 2u; w++) {
+            st->last_r[w] = o->rbytes[w] ? st->rbuf[w][k % (FADEHIP_BAM_CHUNKS + 1)].p : nullptr;
+            st->last_rbytes[w] = o->rbytes[w];
+            st->last_rrows[w] = o->rrows[w];
+        }
+        st->have_back = true;
+    }
     {
         std::lock_guard<std::mutex> l(st->mu);
         o->state = 0;
@@ -1730,6 +1974,22 @@ int fadehip_bam_back_extract(fadehip_bam_stream *st, const uint8_t **recs, size_
     *recs = st->last_x;
     *n_bytes = st->last_xbytes;
     *n_records = st->last_xrecs;
+    return 0;
+}
+
+int fadehip_bam_back_report(fadehip_bam_stream *st, int32_t which, const uint8_t **text, size_t *n_bytes, int64_t *n_rows) {
+    if (!st) return set_err(nullptr, FADEHIP_E_INVALID, "stream is NULL");
+    fadehip_ctx *ctx = st->ctx;
+    if (!text || !n_bytes || !n_rows || (which != FADEHIP_BAM_REPORT_STATS && which != FADEHIP_BAM_REPORT_CLIP)) return set_err(ctx, FADEHIP_E_INVALID, "NULL argument, or which is not one report");
+    *text = nullptr;
+    *n_bytes = 0;
+    *n_rows = 0;
+    const uint32_t w = which == FADEHIP_BAM_REPORT_STATS ? 0u : 1u;
+    if (!(st->report & (1u << w))) return set_err(ctx, FADEHIP_E_STATE, "bam stream: opened without that FADEHIP_BAM_REPORT flag");
+    if (!st->have_back) return set_err(ctx, FADEHIP_E_STATE, "bam stream: back_report comes after a back call");
+    *text = st->last_r[w];
+    *n_bytes = st->last_rbytes[w];
+    *n_rows = st->last_rrows[w];
     return 0;
 }
 
@@ -1823,6 +2083,9 @@ void fadehip_bam_close(fadehip_bam_stream *st) {
         release(S.h_blocks);
         release(S.h_counts);
         release(S.h_ns);
+        release(S.rp);
+        release(S.rp_scratch);
+        release(S.h_rp);
         for (DevBuf *b : {&S.rs_ctl, &S.rs_arr, &S.rs_stage, &S.rs_hold}) release(*b);  // (records still held, no last call: given back with the rest)
         release(S.h_rs);
         if (S.rs_meta) (void)hipEventDestroy(S.rs_meta);
@@ -1830,10 +2093,15 @@ void fadehip_bam_close(fadehip_bam_stream *st) {
     }
     for (auto &ob : st->outbuf) release(ob);
     for (auto &xb : st->xbuf) release(xb);
+    for (auto &rw : st->rbuf)
+        for (auto &rb : rw) release(rb);
     for (auto &o : st->ring) {
         release(o.o);
         release(o.x);
+        release(o.r[0]);
+        release(o.r[1]);
         if (o.xready) (void)hipEventDestroy(o.xready);
+        if (o.rready) (void)hipEventDestroy(o.rready);
         if (o.ready) (void)hipEventDestroy(o.ready);
     }
     delete st;

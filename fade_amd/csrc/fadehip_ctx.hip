@@ -322,7 +322,7 @@ void fadehip_destroy(fadehip_ctx *ctx) {
     for (DevBuf *b : {&ctx->l1_q, &ctx->l1_r, &ctx->l1_qn, &ctx->l1_rn, &ctx->l1_bad, &ctx->l1_work, &ctx->l1_aln}) release(*b);
     for (DevBuf *b : {&ctx->st_q, &ctx->st_r, &ctx->st_work, &ctx->st_out, &ctx->st_scratch}) release(*b);
     if (ctx->stats_stream) (void)hipStreamDestroy(ctx->stats_stream);
-    for (DevBuf *b : {&ctx->batch.in, &ctx->batch.meta, &ctx->batch.work, &ctx->batch.out}) release(*b);
+    for (DevBuf *b : {&ctx->batch.in, &ctx->batch.meta, &ctx->batch.work, &ctx->batch.out, &ctx->batch.scratch}) release(*b);
     if (ctx->batch.stream) (void)hipStreamDestroy(ctx->batch.stream);
     release(ctx->contig_len);
     release(ctx->contig_base);

@@ -14,6 +14,8 @@
 #include "fadehip_types.hpp"
 
 namespace fadehip {
+struct StatsWork;     // sw_stats.hpp
+struct StatsScoring;
 namespace host __attribute__((visibility("hidden"))) {
 
 struct DevBuf {
@@ -168,6 +170,7 @@ struct BatchLane {
     std::mutex mu;
     hipStream_t stream = nullptr;
     DevBuf in, meta, work, out;  // the records | offsets, rs and the call's other arrays | sizes, or eject's group arrays | output bytes
+    DevBuf scratch;              // fadehip_report_batch: sw_stats_kernel's rows of its multi-strip pairs
 };
 
 }  // namespace host
@@ -254,6 +257,9 @@ void bound_counted_batch(Slot &s, uint32_t n_sent, uint32_t l_seq_min, uint32_t 
 int plan_run(fadehip_ctx *ctx, Slot &s);
 int enqueue_run(fadehip_ctx *ctx, Slot &s);
 int finish_run(fadehip_ctx *ctx, Slot &s, int slot);
+int sw_stats_long_blocks(size_t n_long, int long_max_lr, size_t *row_bytes);
+int enqueue_sw_stats(fadehip_ctx *ctx, hipStream_t st, const StatsWork *d_work, const size_t cls_begin[6], const uint8_t *d_q, const uint8_t *d_r,
+                     fadehip_sw_stats_result *d_out, void *scratch, int long_max_lr, int long_blocks, const StatsScoring &sc);
 
 // ---- fadehip_bgzf.hip: the inflater and the compressor lanes
 bool scan_bgzf_members(const uint8_t *p, size_t n, std::vector<bgzf::InflateBlock> &blocks, size_t *consumed, uint64_t *total_out, std::string &msg);

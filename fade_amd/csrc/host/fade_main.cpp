@@ -2490,6 +2490,18 @@ static void print_extract_help() {
             kHeader);
 }
 
+static void print_report_help(bool stats) {
+    fprintf(stderr,
+            "%s\n%s\n"
+            "usage: fade %s --gpus 1 [options] <annotated BAM> [out.tsv]\n\n"
+            "-t --threads extra threads for parsing the bam file\n"
+            "      --gpus 1: the report's rows are written on one MI355X (the tags read back, the inverted repeats aligned, the text formatted by kernels)\n"
+            "    --timing print where the run spent its time to stderr\n"
+            "-h    --help This help information.\n\n",
+            kHeader, stats ? "stats: reports extended information about artifact reads (used after annotate)" : "stats-clip: reports extended information about all soft-clipped reads (used after annotate)",
+            stats ? "stats" : "stats-clip");
+}
+
 static bool parse_cigar_string(const std::string &s, std::vector<uint32_t> &ops) {
     uint64_t num = 0;
     bool have = false;
@@ -2848,14 +2860,18 @@ static int out_main(const std::string &cl, const Opts &o) {
 // the second (FADEHIP_BAM_EJECT_NAMED) writes every record whose name is not in the set.  It has no host loop behind it:
 // where *fall_back stays set, main refuses the run.
 
-enum class TagsJob { OUT, EXTRACT, FRAGMENTS };
+// `fade stats --gpus 1` / `fade stats-clip --gpus 1` (TagsJob::STATS / STATS_CLIP) are the same reading loop over a stream
+// with FADEHIP_BAM_REPORT_STATS / _CLIP | NO_OUTPUT: the host writes the header line, then what fadehip_bam_back_report hands
+// out, to stdout or to the file named behind the input (app.d:168-176).  No host loop behind them either.
+enum class TagsJob { OUT, EXTRACT, FRAGMENTS, STATS, STATS_CLIP };
 static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, bool *fall_back) {
     *fall_back = true;
-    const char *who = job == TagsJob::EXTRACT ? "fade extract" : "fade out";
+    const bool report = job == TagsJob::STATS || job == TagsJob::STATS_CLIP;
+    const char *who = job == TagsJob::EXTRACT ? "fade extract" : job == TagsJob::STATS ? "fade stats" : job == TagsJob::STATS_CLIP ? "fade stats-clip" : "fade out";
     const bool fragments = job == TagsJob::FRAGMENTS;
     const std::string &path = o.pos[1];
     struct stat sb;
-    if (!(o.bam || o.ubam) || path == "-" || stat(path.c_str(), &sb) != 0 || !S_ISREG(sb.st_mode)) return 1;
+    if (!(o.bam || o.ubam || report) || path == "-" || stat(path.c_str(), &sb) != 0 || !S_ISREG(sb.st_mode)) return 1;
     if (getenv("FADE_BAM_DEVICE") && atoi(getenv("FADE_BAM_DEVICE")) == 0) return 1;
     StageClock ck_total, ck_front, ck_back, ck_write;
     ck_total.start();
@@ -2900,7 +2916,14 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
     *fall_back = false;
     if (o.timing) fprintf(stderr, "[timing] since process start %.3f s (%s begins; file path on the device)\n", since_process_start(), who);
     bool grouped = false;
-    if (job == TagsJob::EXTRACT) {
+    FILE *rep_out = stdout;  // the report: stdout, or the file named behind the input
+    struct RepCloser { FILE *&f; ~RepCloser() { if (f && f != stdout) fclose(f); } } rep_closer{rep_out};
+    if (report) {
+        if (o.pos.size() > 2 && !(rep_out = fopen(o.pos[2].c_str(), "wb"))) {
+            fprintf(stderr, "[E::%s] cannot open %s for writing: %s\n", who, o.pos[2].c_str(), strerror(errno));
+            return 1;
+        }
+    } else if (job == TagsJob::EXTRACT) {
         fprintf(stderr, "[W::fade extract] Output SAM/BAM will not be sorted\n");  // remap.d:13
     } else if (fragments) {
         fprintf(stderr, "[W::fade-out] --fragments: ejecting every read that shares its name with an artifact read, input in any order (two passes over the file)\n");
@@ -2956,6 +2979,7 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
                 if (fadehip_nameset_create(ctx, &names)) { create_err = fadehip_last_error(ctx); return 1; }
                 return open_stream(FADEHIP_BAM_COLLECT_NAMES | FADEHIP_BAM_NO_OUTPUT);
             }
+            if (report) return open_stream(FADEHIP_BAM_NO_OUTPUT | (job == TagsJob::STATS ? FADEHIP_BAM_REPORT_STATS : FADEHIP_BAM_REPORT_CLIP));
             int32_t mode = o.ubam ? FADEHIP_BAM_STORED : 0;
             if (job == TagsJob::EXTRACT) mode |= FADEHIP_BAM_EXTRACT | FADEHIP_BAM_NO_OUTPUT;
             else if (o.clip) mode |= FADEHIP_BAM_CLIP | (o.keep_sorted ? FADEHIP_BAM_KEEP_SORTED : 0);
@@ -3114,7 +3138,13 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
             if (rc) throw std::runtime_error(fadehip_last_error(ctx));
             note_held(o, st);
             ck_write.start();
-            if (xwriter) {
+            if (report) {
+                const uint8_t *tp = nullptr;
+                size_t tn = 0;
+                int64_t n_rows = 0;
+                if (fadehip_bam_back_report(st, job == TagsJob::STATS ? FADEHIP_BAM_REPORT_STATS : FADEHIP_BAM_REPORT_CLIP, &tp, &tn, &n_rows)) throw std::runtime_error(fadehip_last_error(ctx));
+                if (tn && fwrite(tp, 1, tn, rep_out) != tn) throw std::runtime_error("write error on the report");
+            } else if (xwriter) {
                 const uint8_t *xp = nullptr;
                 size_t xn = 0;
                 int64_t n_x = 0;
@@ -3178,13 +3208,19 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
         }
         StageClock ck_pass2;
         ck_pass2.start();
-        if (job == TagsJob::EXTRACT) xwriter.reset(new Writer(stdout, fmt, out_hdr, &pool));
+        if (report) {
+            fputs(job == TagsJob::STATS ? "qname\trname\tpos\tcigar\tart_start\tart_end\taln_rname\taln_start\taln_end\tart_cigar\tstemloop\tstemloop_rc\t"
+                                          "predicted_inverted_repeat\tIR_identity\tavgbq\tart_avgbq\tart_bq\tIR_bq\tflagbinary\tflag\tstrand\n"
+                                        : "qname\tsc_q_scores\tsc_seq\tsc_avg_bq\tavg_bq\tart_status\n", rep_out);
+        } else if (job == TagsJob::EXTRACT) xwriter.reset(new Writer(stdout, fmt, out_hdr, &pool));
         else {
             Writer hw(stdout, fmt, out_hdr, &pool, nullptr, true, false);  // (its members only: no end-of-file block yet)
             hw.close();
         }
         if (run_calls()) return 1;
-        if (xwriter) xwriter->close();
+        if (report) {
+            if (fflush(rep_out) != 0 || ferror(rep_out)) { fprintf(stderr, "[E::%s] write error on the report\n", who); return 1; }
+        } else if (xwriter) xwriter->close();
         else if (fwrite(BGZF_EOF, 1, sizeof BGZF_EOF, stdout) != sizeof BGZF_EOF) { fprintf(stderr, "[E::%s] write error on the output stream\n", who); return 1; }
         if (fflush(stdout) != 0 || ferror(stdout)) { fprintf(stderr, "[E::%s] write error on the output stream\n", who); return 1; }
         int64_t totals[8], n_rec = 0, n_over = 0, n_ej = 0;
@@ -3194,7 +3230,7 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
         ck_pass2.stop();
         if (fragments && o.timing)
             fprintf(stderr, "[timing] pass 2 (records whose name is not in the set) %.3f s: front %.3f | back %.3f | write %.3f\n", ck_pass2.t, ck_front.t, ck_back.t, ck_write.t);
-        if (job != TagsJob::EXTRACT) {  // filter.d:267
+        if (job != TagsJob::EXTRACT && !report) {  // filter.d:267
             OutStats stats;
             stats.read_count = totals[0]; stats.clipped = totals[1]; stats.sup = totals[2]; stats.art_sup = totals[3];
             stats.art = totals[4]; stats.art_mate = totals[5]; stats.aln_l = totals[6]; stats.aln_r = totals[7];
@@ -3204,7 +3240,7 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
         if (o.timing)
             fprintf(stderr, "[timing] total %.3f s (%s, file path on the device, inflate on the %s): front (%sframe, tags read back) %.3f | back (%s, copy out) %.3f | write %.3f; "
                             "%lld records, %lld not written\n",
-                    ck_total.t, who, host_inflate ? "host" : "device", host_inflate ? "" : "inflate, ", ck_front.t, job == TagsJob::EXTRACT ? "extract records" : o.ubam ? "store" : "deflate",
+                    ck_total.t, who, host_inflate ? "host" : "device", host_inflate ? "" : "inflate, ", ck_front.t, report ? "report rows" : job == TagsJob::EXTRACT ? "extract records" : o.ubam ? "store" : "deflate",
                     ck_back.t, ck_write.t, (long long)n_rec, (long long)n_ej);
     } catch (const std::exception &e) {
         fprintf(stderr, "[E::%s] %s\n", who, e.what());
@@ -3429,10 +3465,32 @@ int main(int argc, char **argv) {
         }
         return out_main(cl, o);
     }
-    if (sub == "stats" || sub == "stats-clip") {
-        fprintf(stderr, "[E::fade] %s is outside the MI355X annotate hot path; run the reference fade for it, or write its report "
-                        "during the run: fade annotate %s PATH\n", sub.c_str(), sub == "stats" ? "--stats-tsv" : "--clip-tsv");
-        return 1;
+    if (sub == "stats" || sub == "stats-clip") {  // app.d:154-209
+        Opts o;
+        std::string err;
+        const bool with_gpus = parse_opts(argc, argv, o, err) && o.seen.find('g') != std::string::npos;
+        if (!with_gpus) {
+            fprintf(stderr, "[E::fade] %s is outside the MI355X annotate hot path; run the reference fade for it, or write its report "
+                            "during the run: fade annotate %s PATH.  On an annotated BAM file one MI355X writes it: fade %s --gpus 1 <annotated BAM> [out.tsv]\n",
+                    sub.c_str(), sub == "stats" ? "--stats-tsv" : "--clip-tsv", sub.c_str());
+            return 1;
+        }
+        const std::string who = "fade " + sub;
+        if (!options_allowed(o, "tgT")) return 1;
+        if (o.help || o.pos.size() < 2 || o.pos.size() > 3) { print_report_help(sub == "stats"); return o.pos.size() > 3 ? 1 : 0; }
+        if (o.gpus != 1) {
+            fprintf(stderr, "[E::%s] --gpus %d: the report is written on one device (--gpus 1)\n", who.c_str(), o.gpus);
+            return 1;
+        }
+        // the rows are written on the device alone: there is no host loop behind the option
+        if (getenv("FADE_BAM_DEVICE") && atoi(getenv("FADE_BAM_DEVICE")) == 0) {
+            fprintf(stderr, "[E::%s] --gpus 1: FADE_BAM_DEVICE=0 takes the device away, and the report is written on it alone (no host loop)\n", who.c_str());
+            return 1;
+        }
+        bool fall_back = true;
+        const int rc = tags_stream_main(cl, o, sub == "stats" ? TagsJob::STATS : TagsJob::STATS_CLIP, &fall_back);
+        if (fall_back) fprintf(stderr, "[E::%s] --gpus 1: the input is read as an annotated BAM file on the device: not SAM text, not a pipe, not %s\n", who.c_str(), o.pos[1].c_str());
+        return fall_back ? 1 : rc;
     }
     if (sub == "-h" || sub == "--help") { print_full_help(); return 0; }
     fprintf(stderr, "[E::fade] %s is not a fade subcommand\n", sub.c_str());  // app.d:218-220

@@ -214,6 +214,34 @@ int fadehip_tags_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const i
                        int32_t *trim_right /* [n] */, int32_t *art_tid /* [2n] */, int64_t *art_pos /* [2n] */,
                        int64_t *cig_off /* [2n + 1] */, uint32_t *cig, int64_t cig_cap);
 
+/* The rows of `fade stats` (stats.d:75-186; which = FADEHIP_BAM_REPORT_STATS) or `fade stats-clip` (noclip.d:17-73; which =
+ * FADEHIP_BAM_REPORT_CLIP) over n BAM records that were annotated earlier (shapes and ref_names as fadehip_tags_batch takes),
+ * as TSV text without the header line, written on the device.  Slot 2k is the left side of record k, slot 2k + 1 its right
+ * side; row_off receives 2n + 1 offsets into out, a slot without a row taking no bytes, so the rows stand in input order,
+ * left before right.  rs counts only as an integer field, the first of its name, by its low byte.
+ *   stats: a record takes part with an integer rs, rs & 6 and an am:Z (any other record is skipped); one row of 21 columns
+ *     per set bit.  art_start / art_end come from the first (left) or last (right) S op anywhere in the CIGAR and the
+ *     aligned length; the am side is "name,pos,cigar" as fadehip_tags_batch has it, cut at am's first ';', pos within
+ *     int32, aln_end = pos + the reference bases of the side's CIGAR; as / ar are cut at ';' (piece 0 left, piece 1 right),
+ *     ab's first (left) or last (right) bytes, as many as the as piece has, are the side's qualities; the predicted repeat
+ *     is the as piece up to the end of parasail's sw_stats alignment {3, 8, 10, -5} (under the ctx's rules) of its first
+ *     round(0.75 length) bytes against the ar piece.  The call fails with FADEHIP_E_INVALID and the record's index in
+ *     fadehip_last_error where the reference would die of a range or conversion error: a needed am side that is not
+ *     well-formed or whose pos is outside int32; as / ar / ab absent or not Z; no piece 1 where the right side is needed; an
+ *     empty as piece; ab shorter than the piece; no S op; refID outside ref_names.  A piece longer than
+ *     FADEHIP_MAX_LONG_QUERY: FADEHIP_E_UNSUPPORTED.
+ *   stats-clip: a record takes part with an integer rs and rs & 1; one row of 6 columns per clip parse_clips finds (util.d:
+ *     37-62, with its quirk: leading S ops all count as the left clip, the last one wins).  Qualities + 33 in byte
+ *     arithmetic (0xff gives a space), bases from =ACMGRSVTWYHKDBN.  FADEHIP_E_INVALID with the record's index: a clip on a
+ *     record with l_seq 0, or one longer than l_seq.
+ * The float columns are "%g" of float(num) / float(den): nan, inf, else six significant digits.  A record whose fields do not
+ * fit its bytes or whose aux area is not whole fields: FADEHIP_E_INVALID with its index.  More than out_cap bytes:
+ * FADEHIP_E_INVALID, the number needed is in fadehip_last_error; a call that fails writes nothing.  Synchronous, on the stream
+ * and buffers it shares with fadehip_clip_batch (see there).  (The two constants are fadehip_bam_config.flags bits, defined
+ * with them below: there they ask the file path for the same rows.) */
+int fadehip_report_batch(fadehip_ctx *ctx, int32_t which, int32_t n, const uint8_t *recs, const int64_t *rec_off, int32_t n_ref,
+                         const char *const *ref_names, uint8_t *out, int64_t out_cap, int64_t *row_off /* [2n + 1] */);
+
 /* The stable coordinate order of n BAM records (shapes as fadehip_eject_batch takes), whatever order they come in: the key
  * of a record is (refID as uint32, pos + 1 as uint32) compared as one 64-bit number — refID -1 sorts last, as in samtools —
  * and records of one key keep the order they came in.  order[j] is the index of the record that comes j-th.  The sort is
@@ -516,7 +544,13 @@ typedef struct fadehip_bam_config {
                                    * A call writes the records, held over or its own, whose key is not above the key as it came
                                    * in of its last record; the others are held on the device until a later call (the last call
                                    * writes all).  Input keys that decrease fail that call's back: FADEHIP_E_INVALID,
-                                   * fadehip_last_error names the record's index in the stream; nothing of the call is written */
+                                   * fadehip_last_error names the record's index in the stream; nothing of the call is written;
+                                   * FADEHIP_BAM_REPORT_STATS / FADEHIP_BAM_REPORT_CLIP: `fade stats` / `fade stats-clip` as the file
+                                   * path — every call also leaves the rows of the report(s) over its records, by the rules and the
+                                   * kernels of fadehip_report_batch: fadehip_bam_back_report hands them out.  Valid only with
+                                   * FROM_TAGS | NO_OUTPUT; beside them STORED alone may stand (and is ignored), anything else is
+                                   * FADEHIP_E_INVALID at fadehip_bam_open; the two may be set together.  What fadehip_report_batch
+                                   * fails on fails the call at its back, fadehip_last_error naming the record's index in the stream */
     const char *const *ref_names; /* [n_ref] NUL-terminated */
     uint32_t first_record;        /* payload bytes of the first member passed to front that precede the first record */
     uint32_t tail_trim;           /* payload bytes at the END of the last member (front's last call) that are not this stream's:
@@ -533,6 +567,8 @@ typedef struct fadehip_bam_config {
 #define FADEHIP_BAM_COLLECT_NAMES 128
 #define FADEHIP_BAM_EJECT_NAMED 256
 #define FADEHIP_BAM_KEEP_SORTED 512
+#define FADEHIP_BAM_REPORT_STATS 1024
+#define FADEHIP_BAM_REPORT_CLIP 2048
 int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_bam_stream **out);
 /* The set a stream opened with FADEHIP_BAM_COLLECT_NAMES adds to, or one opened with FADEHIP_BAM_EJECT_NAMED looks names up
  * in: a set of the same ctx, attached before the first front call (later: FADEHIP_E_STATE).  The set is the caller's and
@@ -549,6 +585,11 @@ int fadehip_bam_back(fadehip_bam_stream *st, const uint8_t **out, size_t *out_by
  * records (block_size first) back to back, in pinned memory, good as long as that back call's *out; a call without
  * artifact calls gives 0 bytes, 0 records (and *recs NULL).  Without the flag, or before any back: FADEHIP_E_STATE. */
 int fadehip_bam_back_extract(fadehip_bam_stream *st, const uint8_t **recs, size_t *n_bytes, int64_t *n_records);
+/* With FADEHIP_BAM_REPORT_STATS / _CLIP (which: one of the two): the report's rows of the call the most recent fadehip_bam_back
+ * finished — TSV lines without a header line, in input record order, the left side before the right, so that the calls of a
+ * stream give the report one piece behind the other — in pinned memory, good as long as that back call's *out; a call
+ * without rows gives 0 bytes, 0 rows (and *text NULL).  Without that flag, or before any back: FADEHIP_E_STATE. */
+int fadehip_bam_back_report(fadehip_bam_stream *st, int32_t which, const uint8_t **text, size_t *n_bytes, int64_t *n_rows);
 /* totals so far: the eight Stats.parse counters (stats.d:45-54), records, reads beyond the kernels' limits */
 int fadehip_bam_totals(fadehip_bam_stream *st, int64_t stats[8], int64_t *n_records, int64_t *n_oversize);
 /* FADEHIP_BAM_EJECT: records not written, over the calls back has taken (0 without the flag) */
