@@ -158,6 +158,28 @@ int fadehip_report_batch(fadehip_ctx* ctx, int which, int n, const(ubyte)* recs,
                          ubyte* out_, long out_cap, long* row_off);
 /// order[j]: the record that comes j-th in stable coordinate order — by (refID, pos + 1) as unsigned, ties in the order given
 int fadehip_coord_order_batch(fadehip_ctx* ctx, int n, const(ubyte)* recs, const(long)* rec_off, int* order);
+/// The .bai entries of coordinate-sorted records (include/fadehip.h states the rule): chunks are runs of one (refID, bin), linear
+/// entries the 16 kb windows a mapped record newly reaches, refs runs of one refID (-1 included); offsets are BGZF virtual offsets
+struct fadehip_index_chunk { int tid; uint bin; ulong beg, end; }
+struct fadehip_index_linear { int tid; uint window; ulong off; }
+struct fadehip_index_ref { int tid; int reserved; ulong off_beg, off_end, n_mapped, n_unmapped; }
+struct fadehip_index_call
+{
+    const(fadehip_index_chunk)* chunks;
+    const(fadehip_index_linear)* linear;
+    const(fadehip_index_ref)* refs;
+    long n_chunks, n_linear, n_refs, n_records;
+    ulong first_key, last_key;
+}
+/// ... of n records the caller brings at the virtual offsets voff [n + 1]; *out_ points into memory of the ctx
+int fadehip_index_batch(fadehip_ctx* ctx, int n, const(ubyte)* recs, const(long)* rec_off, const(ulong)* voff, fadehip_index_call* out_);
+/// The host's part: the calls' entries, rebased by the file offset of each call's first member, become one .bai
+struct fadehip_bai;
+fadehip_bai* fadehip_bai_create(int n_ref);
+int fadehip_bai_add(fadehip_bai* b, ulong base_file_offset, const(fadehip_index_call)* call);
+int fadehip_bai_finish(fadehip_bai* b, const(ubyte)** bytes, size_t* n);
+const(char)* fadehip_bai_error(const(fadehip_bai)* b);
+void fadehip_bai_destroy(fadehip_bai* b);
 /// A set of read names resident on the device (`fade out --fragments`): exact, growing; records in the shapes fadehip_eject_batch takes.
 /// add_batch: the names of the records with pick[k] != 0 (pick null: every record); contains_batch: hit[k] = 1 when record k's name is
 /// in the set; count: distinct names.  A malformed record: FADEHIP_E_INVALID with its index, the set unchanged.
@@ -217,6 +239,7 @@ enum FADEHIP_BAM_EJECT_NAMED = 256;    /// ... with FROM_TAGS: a record is writt
 enum FADEHIP_BAM_KEEP_SORTED = 512;    /// ... with CLIP (beside it STORED, EXTRACT, FROM_TAGS only), coordinate-sorted input: the records leave in stable order by (refID, pos + 1) as unsigned, a held tail staying on the device between calls
 enum FADEHIP_BAM_REPORT_STATS = 1024;  /// ... with FROM_TAGS | NO_OUTPUT (beside them STORED only): every call also leaves the rows of `fade stats` over its records (fadehip_bam_back_report); also `which` of fadehip_report_batch
 enum FADEHIP_BAM_REPORT_CLIP = 2048;   /// ... the same for `fade stats-clip`; the two may be set together
+enum FADEHIP_BAM_INDEX = 4096;         /// ... beside every flag that writes output: every call also leaves the .bai entries of the records it writes (fadehip_bam_back_index)
 enum FADEHIP_BAM_CLIP = 4;       /// ... artifact calls leave hard-clipped (`fade annotate -c`), by this run's rs and alignments
 int fadehip_bam_open(fadehip_ctx* ctx, const(fadehip_bam_config)* cfg, fadehip_bam_stream** out_);
 /// the set of the same ctx a COLLECT_NAMES stream adds to / an EJECT_NAMED stream looks up in; before the first front call
@@ -229,6 +252,8 @@ int fadehip_bam_back(fadehip_bam_stream* st, const(ubyte)** out_, size_t* out_by
 int fadehip_bam_back_extract(fadehip_bam_stream* st, const(ubyte)** recs, size_t* n_bytes, long* n_records);
 /// With FADEHIP_BAM_REPORT_STATS / _CLIP (which: one of the two): the report's rows of the call the most recent back finished, TSV lines without a header line, in pinned memory
 int fadehip_bam_back_report(fadehip_bam_stream* st, int which, const(ubyte)** text, size_t* n_bytes, long* n_rows);
+/// With FADEHIP_BAM_INDEX: the .bai entries of the call the most recent back finished, relative to its first member, in pinned memory
+int fadehip_bam_back_index(fadehip_bam_stream* st, fadehip_index_call* out_);
 int fadehip_bam_totals(fadehip_bam_stream* st, long* stats8, long* n_records, long* n_oversize);
 /// FADEHIP_BAM_EJECT: records not written, over the calls back has taken
 int fadehip_bam_ejected(fadehip_bam_stream* st, long* n_ejected);

@@ -37,11 +37,14 @@ EXPORTS = [
     "fadehip_nameset_create", "fadehip_nameset_add_batch", "fadehip_nameset_contains_batch", "fadehip_nameset_count", "fadehip_nameset_destroy",
     "fadehip_bam_use_nameset", "fadehip_bam_held", "fadehip_coord_order_batch", "fadehip_report_batch",
     "fadehip_bam_back_report",
+    "fadehip_index_batch", "fadehip_bam_back_index", "fadehip_bai_create", "fadehip_bai_add", "fadehip_bai_finish", "fadehip_bai_error",
+    "fadehip_bai_destroy",
 ]
 BAM_STORED, BAM_NO_OUTPUT, BAM_CLIP, BAM_EXTRACT, BAM_EJECT, BAM_EJECT_GROUPS, BAM_FROM_TAGS = 1, 2, 4, 8, 16, 32, 64  # fadehip_bam_config.flags
 BAM_COLLECT_NAMES, BAM_EJECT_NAMED = 128, 256
 BAM_KEEP_SORTED = 512
 BAM_REPORT_STATS, BAM_REPORT_CLIP = 1024, 2048  # ... and `which` of fadehip_report_batch / fadehip_bam_back_report
+BAM_INDEX = 4096  # every call leaves the .bai entries of the records it writes (fadehip_bam_back_index)
 BGZF_BLOCK = 0xff00
 BGZF_LANES = 2
 
@@ -98,6 +101,19 @@ class BamConfig(C.Structure):
 
 class FaiEntry(C.Structure):  # fadehip_fai_entry: columns 2-5 of a .fai line
     _fields_ = [("length", C.c_int64), ("offset", C.c_int64), ("line_bases", C.c_int32), ("line_width", C.c_int32)]
+
+
+class IndexCall(C.Structure):  # fadehip_index_call: the .bai entries of one call (or of one fadehip_index_batch)
+    _fields_ = [("chunks", C.c_void_p), ("linear", C.c_void_p), ("refs", C.c_void_p), ("n_chunks", C.c_int64),
+                ("n_linear", C.c_int64), ("n_refs", C.c_int64), ("n_records", C.c_int64), ("first_key", C.c_uint64),
+                ("last_key", C.c_uint64)]
+
+
+INDEX_CHUNK_DTYPE = np.dtype([("tid", "<i4"), ("bin", "<u4"), ("beg", "<u8"), ("end", "<u8")])
+INDEX_LINEAR_DTYPE = np.dtype([("tid", "<i4"), ("window", "<u4"), ("off", "<u8")])
+INDEX_REF_DTYPE = np.dtype([("tid", "<i4"), ("reserved", "<i4"), ("off_beg", "<u8"), ("off_end", "<u8"), ("n_mapped", "<u8"),
+                            ("n_unmapped", "<u8")])
+assert (INDEX_CHUNK_DTYPE.itemsize, INDEX_LINEAR_DTYPE.itemsize, INDEX_REF_DTYPE.itemsize) == (24, 16, 40)
 
 
 class FadeHipError(RuntimeError):
@@ -172,6 +188,16 @@ def load():
     L.fadehip_bam_ejected.argtypes = [vp, C.POINTER(i64)]
     L.fadehip_bam_held.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     L.fadehip_coord_order_batch.argtypes = [vp, i32, vp, vp, vp]
+    L.fadehip_index_batch.argtypes = [vp, i32, vp, vp, vp, C.POINTER(IndexCall)]
+    L.fadehip_bam_back_index.argtypes = [vp, C.POINTER(IndexCall)]
+    L.fadehip_bai_create.argtypes = [i32]
+    L.fadehip_bai_create.restype = vp
+    L.fadehip_bai_add.argtypes = [vp, C.c_uint64, C.POINTER(IndexCall)]
+    L.fadehip_bai_finish.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.fadehip_bai_error.argtypes = [vp]
+    L.fadehip_bai_error.restype = C.c_char_p
+    L.fadehip_bai_destroy.argtypes = [vp]
+    L.fadehip_bai_destroy.restype = None
     L.fadehip_bam_totals.argtypes = [vp, C.POINTER(i64 * 8), C.POINTER(i64), C.POINTER(i64)]
     L.fadehip_bam_close.argtypes = [vp]
     L.fadehip_bam_close.restype = None

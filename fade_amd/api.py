@@ -297,6 +297,20 @@ class Context:
                                                     order.ctypes.data if n > 0 else None))
         return order
 
+    def index_batch(self, recs, rec_off, voff):
+        """fadehip_index_batch: the .bai entries of coordinate-sorted BAM records (recs: uint8, concatenated; rec_off: n + 1
+        offsets) at the virtual offsets voff (n + 1: record k lies in voff[k] .. voff[k + 1]).  Returns the call's entries as
+        index_call_dict gives them.  Keys that step back: FadeHipError -1; a record ending beyond 2^29: -5."""
+        recs = np.ascontiguousarray(recs, dtype=np.uint8)
+        rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
+        voff = np.ascontiguousarray(voff, dtype=np.uint64)
+        n = len(rec_off) - 1
+        if len(voff) != n + 1:
+            raise ValueError("voff holds n + 1 virtual offsets")
+        c = _lib.IndexCall()
+        self._chk(self._L.fadehip_index_batch(self._h, n, recs.ctypes.data if recs.nbytes else None, rec_off.ctypes.data, voff.ctypes.data, C.byref(c)))
+        return index_call_dict(c)
+
     # ---- level 2: annotateTask over a batch (anno.d:55-110)
     def genome_upload(self, names, seqs):
         """seqs: list of bytes / uint8 arrays (raw FASTA residues)."""
@@ -507,7 +521,7 @@ class Context:
         return self.bgzf_deflate_wait(lane)
 
     def bam_stream(self, ref_names, floor_len=5, window=300, first_record=0, stored=False, tail_trim=0, no_output=False, clip=False, extract=False, eject=None, from_tags=False,
-                   collect_names=None, eject_named=None, keep_sorted=False, report=None):
+                   collect_names=None, eject_named=None, keep_sorted=False, report=None, index=False):
         """The file path on the device (fadehip_bam_*): BGZF members of a BAM's records in, BGZF members of the annotated
         records out.  ref_names: the BAM header's contigs (the genome must be uploaded).  clip: records called artifacts leave
         hard-clipped (`fade annotate -c`).  extract: every call also builds `fade extract`'s records of its artifact calls
@@ -524,9 +538,12 @@ class Context:
         coordinate-sorted input leaves in coordinate order — a clipped record at its new position, a reset one at the end —
         with a small tail held on the device between calls; BamStream.held() counts it.  report ("stats", "clip" or "both";
         with from_tags and no_output, beside them stored only): `fade stats` / `fade stats-clip` — every call also leaves the
-        rows of the report(s) over its records; BamStream.report(which) fetches them after each back()."""
+        rows of the report(s) over its records; BamStream.report(which) fetches them after each back().  index (beside every
+        mode that writes output; not with no_output, report or collect_names): every call also leaves the .bai entries of the
+        records it writes, at virtual offsets relative to the call's first member; BamStream.back_index() fetches them after
+        each back(), BaiBuilder makes the file of them."""
         return BamStream(self, ref_names, floor_len, window, first_record, stored, tail_trim, no_output, clip, extract, eject, from_tags,
-                         collect_names, eject_named, keep_sorted, report)
+                         collect_names, eject_named, keep_sorted, report, index)
 
     def bgzf_inflate(self, members, out_cap=None):
         """Whole BGZF members (bytes / uint8 array) -> their payloads, inflated on the device (CRC32 and ISIZE checked)."""
@@ -548,6 +565,55 @@ class Context:
         self._chk(self._L.fadehip_last_run_profile(self._h, slot, C.byref(ms), C.byref(cnt)))
         return dict(gate_ms=ms[0], forward_ms=ms[1], traceback_ms=ms[2], total_ms=ms[3], alignments=cnt[0],
                     cells=cnt[1], trace_bytes=cnt[2], algorithmic_bytes=cnt[3], snapshot_bytes=cnt[4], candidates=cnt[5])
+
+
+def index_call_dict(c):
+    """A fadehip_index_call copied out of the library's memory: chunks [(tid, bin, beg, end)], linear [(tid, window, off)],
+    refs [(tid, off_beg, off_end, n_mapped, n_unmapped)] as lists of int tuples, n (records), first_key, last_key."""
+    def arr(p, n, dt):
+        return np.frombuffer(C.string_at(p, n * dt.itemsize), dtype=dt) if n else np.zeros(0, dt)
+    ch = arr(c.chunks, c.n_chunks, _lib.INDEX_CHUNK_DTYPE)
+    li = arr(c.linear, c.n_linear, _lib.INDEX_LINEAR_DTYPE)
+    rf = arr(c.refs, c.n_refs, _lib.INDEX_REF_DTYPE)
+    return dict(chunks=[(int(x["tid"]), int(x["bin"]), int(x["beg"]), int(x["end"])) for x in ch],
+                linear=[(int(x["tid"]), int(x["window"]), int(x["off"])) for x in li],
+                refs=[(int(x["tid"]), int(x["off_beg"]), int(x["off_end"]), int(x["n_mapped"]), int(x["n_unmapped"])) for x in rf],
+                n=int(c.n_records), first_key=int(c.first_key), last_key=int(c.last_key))
+
+
+class BaiBuilder:
+    """fadehip_bai_*: a .bai out of the calls' index entries (BamStream.back_index(), Context.index_batch()), on the host.
+    add(base_file_offset, call) in stream order — call as index_call_dict gives it —, finish() the file's bytes."""
+
+    def __init__(self, n_ref):
+        self._L = _lib.load()
+        self._h = self._L.fadehip_bai_create(int(n_ref))
+        if not self._h:
+            raise FadeHipError(-1, "fadehip_bai_create failed")
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise FadeHipError(rc, self._L.fadehip_bai_error(self._h).decode())
+
+    def add(self, base_file_offset, call):
+        ch = np.array(call["chunks"], dtype=_lib.INDEX_CHUNK_DTYPE) if call["chunks"] else np.zeros(0, _lib.INDEX_CHUNK_DTYPE)
+        li = np.array(call["linear"], dtype=_lib.INDEX_LINEAR_DTYPE) if call["linear"] else np.zeros(0, _lib.INDEX_LINEAR_DTYPE)
+        rf = np.zeros(len(call["refs"]), _lib.INDEX_REF_DTYPE)
+        for k, (tid, u, v, nm, nu) in enumerate(call["refs"]):
+            rf[k] = (tid, 0, u, v, nm, nu)
+        c = _lib.IndexCall(ch.ctypes.data if len(ch) else None, li.ctypes.data if len(li) else None, rf.ctypes.data if len(rf) else None,
+                           len(ch), len(li), len(rf), call["n"], call["first_key"], call["last_key"])
+        self._chk(self._L.fadehip_bai_add(self._h, int(base_file_offset), C.byref(c)))
+
+    def finish(self):
+        p, n = C.c_void_p(), C.c_size_t(0)
+        self._chk(self._L.fadehip_bai_finish(self._h, C.byref(p), C.byref(n)))
+        return C.string_at(p, n.value)
+
+    def close(self):
+        if self._h:
+            self._L.fadehip_bai_destroy(self._h)
+            self._h = None
 
 
 class PinnedBatch:
@@ -661,7 +727,7 @@ def format_tags(batch, contig_names, rs, aln):
 
 class BamStream:
     def __init__(self, ctx, ref_names, floor_len, window, first_record, stored=False, tail_trim=0, no_output=False, clip=False, extract=False, eject=None, from_tags=False,
-                 collect_names=None, eject_named=None, keep_sorted=False, report=None):
+                 collect_names=None, eject_named=None, keep_sorted=False, report=None, index=False):
         self._ctx, self._L = ctx, ctx._L
         if report not in (None, "stats", "clip", "both"):
             raise ValueError('report is None, "stats", "clip" or "both"')
@@ -672,7 +738,7 @@ class BamStream:
         names = [n.encode() if isinstance(n, str) else bytes(n) for n in ref_names]
         arr = (C.c_char_p * max(len(names), 1))(*names)
         cfg = _lib.BamConfig(floor_len, window, len(names), (_lib.BAM_STORED if stored else 0) | (_lib.BAM_NO_OUTPUT if no_output else 0) | (_lib.BAM_CLIP if clip else 0) | (_lib.BAM_EXTRACT if extract else 0) | (BAM_FROM_TAGS if from_tags else 0) | ej |
-                             (_lib.BAM_COLLECT_NAMES if collect_names else 0) | (_lib.BAM_EJECT_NAMED if eject_named else 0) | (_lib.BAM_KEEP_SORTED if keep_sorted else 0) | rp, arr, first_record, tail_trim)
+                             (_lib.BAM_COLLECT_NAMES if collect_names else 0) | (_lib.BAM_EJECT_NAMED if eject_named else 0) | (_lib.BAM_KEEP_SORTED if keep_sorted else 0) | rp | (_lib.BAM_INDEX if index else 0), arr, first_record, tail_trim)
         h = C.c_void_p()
         ctx._chk(self._L.fadehip_bam_open(ctx._h, C.byref(cfg), C.byref(h)))
         self._h = h
@@ -719,6 +785,12 @@ class BamStream:
         flag = {"stats": _lib.BAM_REPORT_STATS, "clip": _lib.BAM_REPORT_CLIP}[which]
         self._ctx._chk(self._L.fadehip_bam_back_report(self._h, flag, C.byref(p), C.byref(n), C.byref(nr)))
         return (C.string_at(p, n.value) if n.value else b""), int(nr.value)
+
+    def back_index(self):
+        """index=True: the .bai entries of the call the last back() finished, as index_call_dict gives them."""
+        c = _lib.IndexCall()
+        self._ctx._chk(self._L.fadehip_bam_back_index(self._h, C.byref(c)))
+        return index_call_dict(c)
 
     def ejected(self):
         """Records not written (eject=...), over the calls back() has taken."""

@@ -8,6 +8,8 @@
 #include "bam_names.hpp"
 #include "bam_report.hpp"
 #include "bam_resort.hpp"
+#include "bam_index.hpp"
+#include "host/bai_build.hpp"
 #include <algorithm>
 #include <chrono>
 #include <condition_variable>
@@ -745,6 +747,7 @@ struct fadehip_bam_stream {
     bool eject_named = false;    // FADEHIP_BAM_EJECT_NAMED: from_tags, and a record is written exactly when its name is not in `names`
     bool keep_sorted = false;    // FADEHIP_BAM_KEEP_SORTED: clip, and the records leave in coordinate order (bam_resort.hpp)
     uint32_t report = 0;         // FADEHIP_BAM_REPORT_STATS / _CLIP as bam::RP_*: from_tags, and every call leaves the reports' rows (bam_report.hpp)
+    bool index = false;          // FADEHIP_BAM_INDEX: every call leaves the .bai entries of the records it wrote (bam_index.hpp)
     fadehip_nameset *names = nullptr;  // fadehip_bam_use_nameset
     DevBuf names_text, names_off;
     DevBuf names_first;         // from_tags: for every contig the first one of its name (fadehip_tags_batch's rule)
@@ -762,6 +765,13 @@ struct fadehip_bam_stream {
         size_t rbytes[2] = {0, 0};
         int64_t rrows[2] = {0, 0};
         hipEvent_t rready = nullptr;
+        // index (bam_index.hpp): where the call's records lie in o (made when the call is finished, on its slot's stream), the
+        // stage's arrays and ctl, its arguments (the arrays it writes are pinned memory of the stream), the records it was
+        // launched for at most (0: no stage — the call wrote nothing), and the event behind it
+        DevBuf ix_at, ix_work, ix_ctl;
+        bam::IndexArgs ixa;
+        uint32_t ix_n_cap = 0;
+        hipEvent_t iready = nullptr;
         int state = 0;  // 0 free, 1 its call's kernels are enqueued up to the tag sizes (to be finished), 2 finished: waiting for back
     } ring[FADEHIP_BAM_CHUNKS];
     // The front half, two calls in flight.  Call k lives in set k & 1 and on the ctx's slot k & 1 (a stream each):
@@ -823,6 +833,13 @@ struct fadehip_bam_stream {
     size_t last_xbytes = 0;
     int64_t last_xrecs = 0;
     bool have_back = false;
+    // index: the entries of call k, pinned, k % FADEHIP_BAM_CHUNKS (the write kernel stores them there itself; they are good as
+    // long as the call's members); what fadehip_bam_back_index hands out; the records and the last key of the calls so far
+    PinBuf ixbuf[FADEHIP_BAM_CHUNKS];
+    fadehip_index_call last_ix = {};
+    bool have_ix = false, ix_have_key = false;
+    int64_t ix_records = 0;
+    uint64_t ix_last_key = 0;
     // the counts of a call as they cross to the host: the call's ChunkCounts, with extract the extract stream's behind it,
     // with from_tags the stage's StageCounts behind those
     size_t stage_counts_at() const { return sizeof(bam::ChunkCounts) * (extract ? 2u : 1u); }
@@ -900,6 +917,189 @@ int enqueue_resort_sort(fadehip_ctx *ctx, hipStream_t q, const bam::ResortArgs &
         hipLaunchKernelGGL(bam::bam_resort_scatter_kernel, dim3(tiles), dim3(256), 0, q, a, pass);
         HIPCHK(ctx, hipGetLastError());
     }
+    return 0;
+}
+
+// ---- FADEHIP_BAM_INDEX and fadehip_index_batch (bam_index.hpp)
+// The stage's arrays for at most n_cap records, one behind the other from `base` (nullptr: only their size is wanted)
+size_t index_layout(bam::IndexArgs &a, uint8_t *base, size_t n_cap) {
+    const size_t n = std::max<size_t>(n_cap, 1), nb = (n + bam::TAG_BLOCK - 1) / bam::TAG_BLOCK;
+    size_t at = 0;
+    const auto take = [&](size_t bytes) {
+        uint8_t *p = base + at;
+        at += (bytes + 7) & ~(size_t)7;
+        return p;
+    };
+    a.uo = (uint64_t *)take(8 * (n + 1));
+    a.blk_max = (uint64_t *)take(8 * nb);
+    a.blk_carry = (uint64_t *)take(8 * nb);
+    a.blk_sums = (uint64_t *)take(32 * nb);
+    a.blk_base = (uint64_t *)take(32 * nb);
+    a.cum = (uint64_t *)take(16 * n);
+    a.rec = (bam::IndexRec *)take(sizeof(bam::IndexRec) * n);
+    return at;
+}
+
+// where the three arrays the stage writes lie in one block from `base`: n_cap chunks, n_cap reference runs, cap_linear entries
+size_t index_out_layout(bam::IndexArgs &a, uint8_t *base, size_t n_cap, size_t cap_linear) {
+    a.chunks = (fadehip_index_chunk *)base;
+    a.refs = (fadehip_index_ref *)(base + sizeof(fadehip_index_chunk) * n_cap);
+    a.linear = (fadehip_index_linear *)(base + (sizeof(fadehip_index_chunk) + sizeof(fadehip_index_ref)) * n_cap);
+    a.cap_linear = (uint32_t)cap_linear;
+    return (sizeof(fadehip_index_chunk) + sizeof(fadehip_index_ref)) * n_cap + sizeof(fadehip_index_linear) * cap_linear;
+}
+
+// the stage up to its counts (a.n > 0): the ctl cleared, keys, the running maximum, heads and counts, their sums
+int enqueue_index_counts(fadehip_ctx *ctx, hipStream_t q, const bam::IndexArgs &a) {
+    const unsigned nb = (a.n + bam::TAG_BLOCK - 1u) / bam::TAG_BLOCK;
+    HIPCHK(ctx, hipMemsetAsync(a.ctl, 0, sizeof(bam::IndexCtl), q));
+    HIPCHK(ctx, hipMemsetAsync(&a.ctl->bad_order, 0xff, 8, q));  // (bad_order and bad_span: IX_NONE)
+    hipLaunchKernelGGL(bam::bam_index_key_kernel, dim3(nb), dim3(bam::TAG_BLOCK), 0, q, a);
+    HIPCHK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(bam::bam_index_max_scan_kernel, dim3(1), dim3(1024), 0, q, a, nb);
+    HIPCHK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(bam::bam_index_count_kernel, dim3(nb), dim3(bam::TAG_BLOCK), 0, q, a, nb);
+    HIPCHK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(bam::bam_index_sum_scan_kernel, dim3(1), dim3(1024), 0, q, a, nb);
+    HIPCHK(ctx, hipGetLastError());
+    return 0;
+}
+
+// ... and behind them the three arrays (a.chunks, a.refs and a.linear are set)
+int enqueue_index_write(fadehip_ctx *ctx, hipStream_t q, const bam::IndexArgs &a) {
+    const unsigned nb = (a.n + bam::TAG_BLOCK - 1u) / bam::TAG_BLOCK;
+    hipLaunchKernelGGL(bam::bam_index_write_kernel, dim3(nb), dim3(bam::TAG_BLOCK), 0, q, a, nb);
+    HIPCHK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(bam::bam_index_refs_kernel, dim3((a.n + 255u) / 256u), dim3(256), 0, q, a, a.n);
+    HIPCHK(ctx, hipGetLastError());
+    return 0;
+}
+
+// what the stage's flags fail a call with: the lower record of the two, the order first; `first` is record 0's index in the stream
+int index_bad(fadehip_ctx *ctx, const bam::IndexCtl &c, long long first, const char *who) {
+    if (c.bad_order != bam::IX_NONE && c.bad_order <= c.bad_span)
+        return set_err(ctx, FADEHIP_E_INVALID, "%s: record %lld: not in coordinate order (--write-index needs coordinate-sorted output)", who, first + (long long)c.bad_order);
+    if (c.bad_span != bam::IX_NONE)
+        return set_err(ctx, FADEHIP_E_UNSUPPORTED, "%s: record %lld: ends beyond 2^29 on its reference (a BAI index cannot hold it)", who, first + (long long)c.bad_span);
+    return 0;
+}
+
+// C's part under FADEHIP_BAM_INDEX, behind the rewrite or the move on the slot's stream and in front of the event the
+// compressor waits for: where every record the call writes lies in its output, dense and in the order it leaves — the set's
+// arrays are the next call's to overwrite once this one is finished, so the offsets move to the ring place here.
+int bam_finish_index(fadehip_bam_stream *st, fadehip_bam_stream::Set &S, hipStream_t q) {
+    fadehip_ctx *ctx = st->ctx;
+    fadehip_bam_stream::Out *out = S.out;
+    int rc;
+    out->ix_n_cap = 0;
+    bam::IndexArgs &a = out->ixa;
+    memset(&a, 0, sizeof a);
+    if (!out->bytes) return 0;
+    if ((rc = reserve(ctx, out->ix_ctl, 256))) return rc;
+    if (st->keep_sorted) {
+        const bam::ResortCtl c = *(const bam::ResortCtl *)S.h_rs.p;
+        if ((rc = reserve_roomy(ctx, out->ix_at, 8 * ((size_t)c.n_emit + 1)))) return rc;
+        HIPCHK(ctx, hipMemcpyAsync(out->ix_at.p, S.ra.dst, 8 * ((size_t)c.n_emit + 1), hipMemcpyDeviceToDevice, q));
+        a.n = c.n_emit;
+    } else {
+        const uint32_t n = S.n_rec, ntb = (n + bam::TAG_BLOCK - 1u) / bam::TAG_BLOCK;
+        if ((rc = reserve_roomy(ctx, out->ix_at, 8 * ((size_t)n + 1) + 8 * (size_t)ntb + 8))) return rc;
+        bam::IndexAtArgs g;
+        g.out_size = (const uint32_t *)S.out_size.p;
+        g.blk_base = st->from_tags ? S.fa.blk_base : S.ta.blk_base;
+        g.n = n;
+        g.at = (uint64_t *)out->ix_at.p;
+        g.cnt = (uint32_t *)(g.at + n + 1);
+        g.cnt_base = g.cnt + ntb;
+        g.n_out = (uint32_t *)((uint8_t *)out->ix_ctl.p + 128);
+        hipLaunchKernelGGL(bam::bam_index_present_kernel, dim3(ntb), dim3(bam::TAG_BLOCK), 0, q, g);
+        HIPCHK(ctx, hipGetLastError());
+        hipLaunchKernelGGL(bam::bam_index_present_scan_kernel, dim3(1), dim3(1024), 0, q, g, ntb);
+        HIPCHK(ctx, hipGetLastError());
+        hipLaunchKernelGGL(bam::bam_index_at_kernel, dim3(ntb), dim3(bam::TAG_BLOCK), 0, q, g);
+        HIPCHK(ctx, hipGetLastError());
+        a.n = n;
+        a.n_ptr = g.n_out;
+    }
+    out->ix_n_cap = a.n;
+    return 0;
+}
+
+// The back half's part, on the compressor lane's stream behind the scan that fixes member_off[] (or the stored members,
+// whose offsets the host knows): the stage, writing its arrays and — in one small copy behind them — its ctl into the pinned
+// block of the call's ring place.  Room for one linear entry per record and 65536 more; a call that needs more (known when
+// back has waited) has its arrays written again into a larger block.
+size_t index_pinned_bytes(size_t n_cap, size_t cap_linear) {
+    bam::IndexArgs t;
+    return 128 + index_out_layout(t, nullptr, n_cap, cap_linear);
+}
+int bam_enqueue_index(fadehip_bam_stream *st, uint64_t k, int lane) {
+    fadehip_ctx *ctx = st->ctx;
+    fadehip_bam_stream::Out *o = &st->ring[k % FADEHIP_BAM_CHUNKS];
+    if (!o->ix_n_cap) return 0;
+    hipStream_t q = ctx->bgzf[lane].stream;
+    bam::IndexArgs &a = o->ixa;
+    const size_t n = o->ix_n_cap, cap_linear = n + 65536;
+    PinBuf &pb = st->ixbuf[k % FADEHIP_BAM_CHUNKS];
+    int rc;
+    if ((rc = reserve_roomy(ctx, o->ix_work, index_layout(a, nullptr, n))) || (rc = reserve_pinned(ctx, pb, index_pinned_bytes(n, cap_linear)))) return rc;
+    index_layout(a, (uint8_t *)o->ix_work.p, n);
+    index_out_layout(a, pb.p + 128, n, cap_linear);
+    a.ctl = (bam::IndexCtl *)o->ix_ctl.p;
+    a.u = (const uint8_t *)o->o.p;
+    a.at = (const uint64_t *)o->ix_at.p;
+    const BgzfGeometry g = bgzf_lane_geometry(ctx, lane, st->stored);
+    a.block = g.block;
+    a.member_off = g.member_off;
+    a.behind_ptr = g.behind_ptr;
+    a.member_stride = g.member_stride;
+    a.behind = g.behind;
+    if ((rc = enqueue_index_counts(ctx, q, a)) || (rc = enqueue_index_write(ctx, q, a))) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(pb.p, a.ctl, sizeof(bam::IndexCtl), hipMemcpyDeviceToHost, q));
+    if (!o->iready) HIPCHK(ctx, hipEventCreateWithFlags(&o->iready, hipEventDisableTiming | (ctx->blocking_sync ? hipEventBlockingSync : 0)));
+    HIPCHK(ctx, hipEventRecord(o->iready, q));
+    return 0;
+}
+
+// back has waited for the call's members: its index entries.  Fails the call on what the stage flagged and on keys that step
+// back between two calls; fills st->last_ix.
+int bam_take_index(fadehip_bam_stream *st, uint64_t k, int lane) {
+    fadehip_ctx *ctx = st->ctx;
+    fadehip_bam_stream::Out *o = &st->ring[k % FADEHIP_BAM_CHUNKS];
+    fadehip_index_call &r = st->last_ix;
+    memset(&r, 0, sizeof r);
+    st->have_ix = true;
+    if (!o->ix_n_cap) return 0;
+    PinBuf &pb = st->ixbuf[k % FADEHIP_BAM_CHUNKS];
+    HIPCHK(ctx, hipEventSynchronize(o->iready));
+    bam::IndexCtl c = *(const bam::IndexCtl *)pb.p;
+    int rc;
+    if ((rc = index_bad(ctx, c, (long long)st->ix_records, "bam stream"))) return rc;
+    if (c.n && st->ix_have_key && c.first_key < st->ix_last_key)
+        return set_err(ctx, FADEHIP_E_INVALID, "bam stream: record %lld: not in coordinate order (--write-index needs coordinate-sorted output)", (long long)st->ix_records);
+    if (c.n_linear > o->ixa.cap_linear) {
+        // (a call whose records reach more windows than it has records + 65536: the arrays once more, with room for all)
+        if (c.n_linear >> 31) return set_err(ctx, FADEHIP_E_UNSUPPORTED, "bam stream: %llu linear index entries in one call (at most 2^31)", (unsigned long long)c.n_linear);
+        hipStream_t q = ctx->bgzf[lane].stream;
+        if ((rc = reserve_pinned(ctx, pb, index_pinned_bytes(o->ix_n_cap, (size_t)c.n_linear)))) return rc;
+        index_out_layout(o->ixa, pb.p + 128, o->ix_n_cap, (size_t)c.n_linear);
+        if ((rc = enqueue_index_write(ctx, q, o->ixa))) return rc;
+        HIPCHK(ctx, hipStreamSynchronize(q));
+    }
+    r.chunks = o->ixa.chunks;
+    r.linear = o->ixa.linear;
+    r.refs = o->ixa.refs;
+    r.n_chunks = (int64_t)c.n_chunks;
+    r.n_linear = (int64_t)c.n_linear;
+    r.n_refs = (int64_t)c.n_refs;
+    r.n_records = (int64_t)c.n;
+    r.first_key = c.first_key;
+    r.last_key = c.last_key;
+    if (c.n) {
+        st->ix_last_key = c.last_key;
+        st->ix_have_key = true;
+    }
+    st->ix_records += (int64_t)c.n;
     return 0;
 }
 
@@ -1140,6 +1340,7 @@ int bam_finish_one(fadehip_bam_stream *st, uint64_t k) {
         HIPCHK(ctx, hipStreamSynchronize(q));  // (an empty call: the ctl alone)
     }
     if (st->keep_sorted && (rc = bam_finish_resort(st, S, k, q))) return rc;
+    if (st->index && (rc = bam_finish_index(st, S, q))) return rc;
     if (!out->ready) HIPCHK(ctx, hipEventCreateWithFlags(&out->ready, hipEventDisableTiming | (ctx->blocking_sync ? hipEventBlockingSync : 0)));
     HIPCHK(ctx, hipEventRecord(out->ready, q));
     if (st->extract && (rc = bam_finish_extract(st, S, k, q))) return rc;
@@ -1672,8 +1873,19 @@ int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_ba
     if (!ctx) return set_err(nullptr, FADEHIP_E_INVALID, "ctx is NULL");
     if (!cfg || !out || cfg->n_ref < 0 || (cfg->n_ref && !cfg->ref_names) || (cfg->window < 0 && !(cfg->flags & FADEHIP_BAM_FROM_TAGS)) ||
         (cfg->flags & ~(FADEHIP_BAM_STORED | FADEHIP_BAM_NO_OUTPUT | FADEHIP_BAM_CLIP | FADEHIP_BAM_EXTRACT | FADEHIP_BAM_EJECT | FADEHIP_BAM_EJECT_GROUPS | FADEHIP_BAM_FROM_TAGS |
-                        FADEHIP_BAM_COLLECT_NAMES | FADEHIP_BAM_EJECT_NAMED | FADEHIP_BAM_KEEP_SORTED | FADEHIP_BAM_REPORT_STATS | FADEHIP_BAM_REPORT_CLIP)))
+                        FADEHIP_BAM_COLLECT_NAMES | FADEHIP_BAM_EJECT_NAMED | FADEHIP_BAM_KEEP_SORTED | FADEHIP_BAM_REPORT_STATS | FADEHIP_BAM_REPORT_CLIP | FADEHIP_BAM_INDEX)))
         return set_err(ctx, FADEHIP_E_INVALID, "bam stream: bad configuration");
+    // the index describes records that are written: a stream that writes none has nothing to index.  It stands beside every
+    // flag that writes output, and the checks below look at the flags without it
+    const int32_t all_flags = cfg->flags;
+    if (all_flags & FADEHIP_BAM_INDEX) {
+        const char *no = (all_flags & FADEHIP_BAM_NO_OUTPUT) ? "FADEHIP_BAM_NO_OUTPUT" : (all_flags & FADEHIP_BAM_REPORT_STATS) ? "FADEHIP_BAM_REPORT_STATS"
+                         : (all_flags & FADEHIP_BAM_REPORT_CLIP) ? "FADEHIP_BAM_REPORT_CLIP" : (all_flags & FADEHIP_BAM_COLLECT_NAMES) ? "FADEHIP_BAM_COLLECT_NAMES" : nullptr;
+        if (no) return set_err(ctx, FADEHIP_E_INVALID, "bam stream: FADEHIP_BAM_INDEX does not combine with %s (the index is of the records a stream writes)", no);
+    }
+    fadehip_bam_config cfg_plain = *cfg;
+    cfg_plain.flags &= ~FADEHIP_BAM_INDEX;
+    cfg = &cfg_plain;
     if (cfg->flags & (FADEHIP_BAM_REPORT_STATS | FADEHIP_BAM_REPORT_CLIP)) {
         const int32_t need = FADEHIP_BAM_FROM_TAGS | FADEHIP_BAM_NO_OUTPUT;
         if ((cfg->flags & need) != need || (cfg->flags & ~(need | FADEHIP_BAM_STORED | FADEHIP_BAM_REPORT_STATS | FADEHIP_BAM_REPORT_CLIP)))
@@ -1713,6 +1925,7 @@ int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_ba
     st->eject_named = (cfg->flags & FADEHIP_BAM_EJECT_NAMED) != 0;
     st->keep_sorted = (cfg->flags & FADEHIP_BAM_KEEP_SORTED) != 0;
     st->report = ((cfg->flags & FADEHIP_BAM_REPORT_STATS) ? bam::RP_STATS : 0u) | ((cfg->flags & FADEHIP_BAM_REPORT_CLIP) ? bam::RP_CLIP : 0u);
+    st->index = (all_flags & FADEHIP_BAM_INDEX) != 0;
     std::string text;
     std::vector<uint32_t> off((size_t)cfg->n_ref + 1, 0);
     for (int k = 0; k < cfg->n_ref; k++) {
@@ -1890,9 +2103,10 @@ static int bam_submit_back(fadehip_bam_stream *st, uint64_t k) {
     BgzfLane &l = ctx->bgzf[lane];
     if (hipStreamWaitEvent(l.stream, o->ready, 0) != hipSuccess) return set_err(ctx, FADEHIP_E_HIP, "bam stream: hipStreamWaitEvent failed");
     PinBuf &ob = st->outbuf[k % FADEHIP_BAM_CHUNKS];
-    if (st->stored) return bgzf_store_enqueue(ctx, lane, (const uint8_t *)o->o.p, o->bytes, ob);
-    rc = bgzf_enqueue(ctx, lane, (const uint8_t *)o->o.p, o->bytes, bgzf_pick_geom(ctx), &ob);
+    if (st->stored) rc = bgzf_store_enqueue(ctx, lane, (const uint8_t *)o->o.p, o->bytes, ob);
+    else rc = bgzf_enqueue(ctx, lane, (const uint8_t *)o->o.p, o->bytes, bgzf_pick_geom(ctx), &ob);
     tr.mark("compressor enqueued");
+    if (!rc && st->index) rc = bam_enqueue_index(st, k, lane);
     return rc;
 }
 
@@ -1936,6 +2150,11 @@ int fadehip_bam_back(fadehip_bam_stream *st, const uint8_t **out, size_t *out_by
         } else if ((rc = fadehip_bgzf_deflate_wait(ctx, lane, out, out_bytes))) return bam_fail(st, rc);
     } else if (o->ready) {
         (void)hipEventSynchronize(o->ready);
+    }
+    if (st->index && (rc = bam_take_index(st, k, (int)(k & 1)))) {
+        *out = nullptr;  // (nothing of a call that fails is handed out)
+        *out_bytes = 0;
+        return bam_fail(st, rc);
     }
     if (st->extract) {
         if (o->xready && hipEventSynchronize(o->xready) != hipSuccess) return bam_fail(st, set_err(ctx, FADEHIP_E_HIP, "bam stream: copying the extract records failed"));
@@ -2044,6 +2263,111 @@ int fadehip_coord_order_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, 
     return 0;
 }
 
+int fadehip_bam_back_index(fadehip_bam_stream *st, fadehip_index_call *out) {
+    if (!st) return set_err(nullptr, FADEHIP_E_INVALID, "stream is NULL");
+    fadehip_ctx *ctx = st->ctx;
+    if (!out) return set_err(ctx, FADEHIP_E_INVALID, "NULL argument");
+    memset(out, 0, sizeof *out);
+    if (!st->index) return set_err(ctx, FADEHIP_E_STATE, "bam stream: opened without FADEHIP_BAM_INDEX");
+    if (!st->have_ix) return set_err(ctx, FADEHIP_E_STATE, "bam stream: back_index comes after a back call");
+    *out = st->last_ix;
+    return 0;
+}
+
+// The index entries of records the caller brings, at virtual offsets the caller brings: bam_index.hpp's kernels, the ones of
+// the file path under FADEHIP_BAM_INDEX, on the record-batch lane.
+int fadehip_index_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const int64_t *rec_off, const uint64_t *voff, fadehip_index_call *out) {
+    if (!ctx) return set_err(nullptr, FADEHIP_E_INVALID, "ctx is NULL");
+    if (n < 0 || !rec_off || !voff || !out || (n > 0 && !recs)) return set_err(ctx, FADEHIP_E_INVALID, "NULL argument");
+    memset(out, 0, sizeof *out);
+    if (rec_off[0] < 0) return set_err(ctx, FADEHIP_E_INVALID, "offsets must be non-negative and non-decreasing (record 0)");
+    if (n == 0) return 0;
+    int rc;
+    if ((rc = check_records(ctx, n, recs, rec_off, true, [](int32_t) { return 0; }))) return rc;
+    BatchLane &L = ctx->batch;
+    std::lock_guard<std::mutex> lk(L.mu);
+    // meta: in_off [n + 1] u64 | voff [n + 1] u64 | the ctl;  work: the stage's arrays;  out: chunks | refs | linear
+    bam::IndexArgs a;
+    memset(&a, 0, sizeof a);
+    const size_t m_voff = 8 * ((size_t)n + 1), m_ctl = 2 * m_voff;
+    std::vector<uint64_t> off;
+    if ((rc = batch_upload(ctx, L, n, recs, rec_off, nullptr, 0, m_ctl + 256, index_layout(a, nullptr, (size_t)n), off))) return rc;
+    HIPCHK(ctx, hipMemcpyAsync((uint8_t *)L.meta.p + m_voff, voff, m_voff, hipMemcpyHostToDevice, L.stream));
+    index_layout(a, (uint8_t *)L.work.p, (size_t)n);
+    a.ctl = (bam::IndexCtl *)((uint8_t *)L.meta.p + m_ctl);
+    a.u = (const uint8_t *)L.in.p;
+    a.at = (const uint64_t *)L.meta.p;
+    a.n = (uint32_t)n;
+    a.voff = (const uint64_t *)((uint8_t *)L.meta.p + m_voff);
+    if ((rc = enqueue_index_counts(ctx, L.stream, a))) return rc;
+    bam::IndexCtl c;
+    HIPCHK(ctx, hipMemcpyAsync(&c, a.ctl, sizeof c, hipMemcpyDeviceToHost, L.stream));
+    HIPCHK(ctx, hipStreamSynchronize(L.stream));
+    if ((rc = index_bad(ctx, c, 0, "index batch"))) return rc;
+    if (c.n_linear >> 31) return set_err(ctx, FADEHIP_E_UNSUPPORTED, "index batch: %llu linear index entries (at most 2^31)", (unsigned long long)c.n_linear);
+    const size_t out_bytes = index_out_layout(a, nullptr, (size_t)n, (size_t)c.n_linear);
+    if ((rc = reserve(ctx, L.out, out_bytes + 8))) return rc;
+    index_out_layout(a, (uint8_t *)L.out.p, (size_t)n, (size_t)c.n_linear);
+    if ((rc = enqueue_index_write(ctx, L.stream, a))) return rc;
+    L.index_host.resize(out_bytes + 8);
+    HIPCHK(ctx, hipMemcpyAsync(L.index_host.data(), L.out.p, out_bytes, hipMemcpyDeviceToHost, L.stream));
+    HIPCHK(ctx, hipStreamSynchronize(L.stream));
+    bam::IndexArgs h;
+    index_out_layout(h, L.index_host.data(), (size_t)n, (size_t)c.n_linear);
+    out->chunks = h.chunks;
+    out->linear = h.linear;
+    out->refs = h.refs;
+    out->n_chunks = (int64_t)c.n_chunks;
+    out->n_linear = (int64_t)c.n_linear;
+    out->n_refs = (int64_t)c.n_refs;
+    out->n_records = (int64_t)c.n;
+    out->first_key = c.first_key;
+    out->last_key = c.last_key;
+    return 0;
+}
+
+// ---- the host's part of the index (host/bai_build.hpp); no device is involved
+struct fadehip_bai {
+    fadehip::bai::Builder b;
+    explicit fadehip_bai(int32_t n_ref) : b(n_ref) {}
+};
+static thread_local std::string g_bai_null_err;
+
+fadehip_bai *fadehip_bai_create(int32_t n_ref) {
+    if (n_ref < 0) return nullptr;
+    try {
+        return new fadehip_bai(n_ref);
+    } catch (...) {
+        return nullptr;
+    }
+}
+int fadehip_bai_add(fadehip_bai *b, uint64_t base_file_offset, const fadehip_index_call *call) {
+    if (!b) {
+        g_bai_null_err = "bai: builder is NULL";
+        return FADEHIP_E_INVALID;
+    }
+    try {
+        return b->b.add(base_file_offset, call);
+    } catch (...) {
+        b->b.err = "bai: out of memory";
+        return FADEHIP_E_NOMEM;
+    }
+}
+int fadehip_bai_finish(fadehip_bai *b, const uint8_t **bytes, size_t *n) {
+    if (!b) {
+        g_bai_null_err = "bai: builder is NULL";
+        return FADEHIP_E_INVALID;
+    }
+    try {
+        return b->b.finish(bytes, n);
+    } catch (...) {
+        b->b.err = "bai: out of memory";
+        return FADEHIP_E_NOMEM;
+    }
+}
+const char *fadehip_bai_error(const fadehip_bai *b) { return b ? b->b.err.c_str() : g_bai_null_err.c_str(); }
+void fadehip_bai_destroy(fadehip_bai *b) { delete b; }
+
 int fadehip_bam_ejected(fadehip_bam_stream *st, int64_t *n_ejected) {
     if (!st) return set_err(nullptr, FADEHIP_E_INVALID, "stream is NULL");
     if (!n_ejected) return set_err(st->ctx, FADEHIP_E_INVALID, "NULL argument");
@@ -2093,6 +2417,7 @@ void fadehip_bam_close(fadehip_bam_stream *st) {
     }
     for (auto &ob : st->outbuf) release(ob);
     for (auto &xb : st->xbuf) release(xb);
+    for (auto &ib : st->ixbuf) release(ib);
     for (auto &rw : st->rbuf)
         for (auto &rb : rw) release(rb);
     for (auto &o : st->ring) {
@@ -2100,6 +2425,8 @@ void fadehip_bam_close(fadehip_bam_stream *st) {
         release(o.x);
         release(o.r[0]);
         release(o.r[1]);
+        for (DevBuf *b : {&o.ix_at, &o.ix_work, &o.ix_ctl}) release(*b);
+        if (o.iready) (void)hipEventDestroy(o.iready);
         if (o.xready) (void)hipEventDestroy(o.xready);
         if (o.rready) (void)hipEventDestroy(o.rready);
         if (o.ready) (void)hipEventDestroy(o.ready);

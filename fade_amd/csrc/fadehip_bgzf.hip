@@ -209,6 +209,26 @@ int bgzf_store_enqueue(fadehip_ctx *ctx, int lane, const uint8_t *d_src, size_t 
     return 0;
 }
 
+// Where the members of the lane's submission in flight lie, for a kernel enqueued behind it on the lane's stream (the index
+// stage of the file path): the block size, and the members' offsets — the scan kernel's member_off[] and total on the
+// device, or, for stored members, what the host knows already.
+BgzfGeometry bgzf_lane_geometry(const fadehip_ctx *ctx, int lane, bool stored) {
+    const BgzfLane &l = ctx->bgzf[lane];
+    BgzfGeometry g;
+    if (stored) {
+        const uint64_t nb = (l.n_bytes + bgzf::STORE_BLOCK - 1) / bgzf::STORE_BLOCK;
+        g.block = bgzf::STORE_BLOCK;
+        g.member_stride = bgzf::STORE_MEMBER;
+        g.behind = l.n_bytes + nb * (uint64_t)(bgzf::STORE_MEMBER - bgzf::STORE_BLOCK);
+        return g;
+    }
+    const uint32_t *d_ticket = (const uint32_t *)l.meta.p + 2 * (size_t)l.n_blocks;
+    g.block = (uint32_t)bgzf_block_bytes(l.geom);
+    g.member_off = (const uint64_t *)l.member_off.p;
+    g.behind_ptr = (const uint64_t *)(((uintptr_t)(d_ticket + 2) + 7) & ~(uintptr_t)7);  // (d_total of bgzf_enqueue)
+    return g;
+}
+
 }  // namespace fadehip::host
 
 extern "C" {

@@ -171,6 +171,7 @@ struct BatchLane {
     hipStream_t stream = nullptr;
     DevBuf in, meta, work, out;  // the records | offsets, rs and the call's other arrays | sizes, or eject's group arrays | output bytes
     DevBuf scratch;              // fadehip_report_batch: sw_stats_kernel's rows of its multi-strip pairs
+    std::vector<uint8_t> index_host;  // fadehip_index_batch: the arrays *out points into, until the lane's next call
 };
 
 }  // namespace host
@@ -271,6 +272,13 @@ size_t bgzf_out_cap(size_t n_bytes, int geom);
 int bgzf_enqueue(fadehip_ctx *ctx, int lane, const uint8_t *d_src, size_t n_bytes, int geom, PinBuf *host_out = nullptr);
 size_t bgzf_store_cap(size_t n_bytes);
 int bgzf_store_enqueue(fadehip_ctx *ctx, int lane, const uint8_t *d_src, size_t n_bytes, PinBuf &ob);
+struct BgzfGeometry {
+    uint32_t block = 0;                    // uncompressed bytes per member (the last may hold fewer)
+    const uint64_t *member_off = nullptr;  // device: member k's offset among the call's members; nullptr: k * member_stride
+    const uint64_t *behind_ptr = nullptr;  // device: the members' total; nullptr: `behind`
+    uint64_t member_stride = 0, behind = 0;
+};
+BgzfGeometry bgzf_lane_geometry(const fadehip_ctx *ctx, int lane, bool stored);
 
 }  // namespace host
 }  // namespace fadehip

@@ -69,6 +69,7 @@ static void print_anno_help() {
             "        --extract PATH: also write what `fade extract` makes of the annotated file (one mapped record per artifact side), in the same pass\n"
             "          --eject drop the artifact reads in the same pass, and on name-sorted input every read that shares their name (what `fade out` makes of the annotated file)\n"
             "    --keep-sorted with -c, coordinate-sorted BAM file in, -b or -u out, one MI355X: clipped records are written at their new coordinates, so the output stays coordinate-sorted\n"
+            "    --write-index PATH: also write the BAM index (.bai) of the output, made in the same pass (coordinate-sorted output, BAM file in, -b or -u out, one MI355X)\n"
             "          --gpus number of MI355X devices, one process each on its own range of the input (default 1)\n"
             "    --out-shards with --gpus N: every device writes a complete file PREFIX.<k>.bam (.sam), nothing is merged\n"
             "         --batch records per device batch (default 262144)\n"
@@ -88,6 +89,7 @@ struct Opts {
     std::vector<std::string> pos;
     std::string out_shards;  // --out-shards PREFIX (with --gpus N)
     std::string stats_tsv, clip_tsv;  // --stats-tsv PATH, --clip-tsv PATH: the stats.d / noclip.d reports of this run
+    std::string write_index;  // --write-index PATH: the .bai of the BAM on stdout, made on the device in the same pass
     std::string extract;  // --extract PATH: `fade extract`'s records of this run's artifact calls, in the output's format
     std::string seen;  // one letter per option met: t m w b u c h g(pus) B(atch) s(tats) T(iming) S(hards) X (--extract) E (--eject) F (--fragments) K (--keep-sorted)
 };
@@ -148,6 +150,15 @@ static bool parse_opts(int argc, char **argv, Opts &o, std::string &err) {
                 if (val.empty()) { err = "Invalid value for option --extract: (empty)"; return false; }
                 o.extract = val;
             }
+            else if (name == "write-index") {
+                o.seen += 'I';
+                if (!has_val) {
+                    if (i + 1 >= argc) { err = "Missing value for argument --" + name; return false; }
+                    val = argv[++i];
+                }
+                if (val.empty()) { err = "Invalid value for option --write-index: (empty)"; return false; }
+                o.write_index = val;
+            }
             else if (name == "bam") { o.seen += 'b'; o.bam = true; }
             else if (name == "ubam") { o.seen += 'u'; o.ubam = true; }
             else if (name == "stats") { o.seen += 's'; o.stats = true; }
@@ -205,6 +216,58 @@ static void note_held(const Opts &o, fadehip_bam_stream *st) {
 static void report_held(const Opts &o) {
     if (o.keep_sorted && o.timing) fprintf(stderr, "[timing] --keep-sorted: at most %lld records (%lld bytes) held on the device between calls\n", (long long)g_held_max_recs, (long long)g_held_max_bytes);
 }
+
+// --write-index PATH: the .bai of the BAM that goes to stdout.  Every call of the file path leaves its index entries at
+// offsets relative to its first member (fadehip_bam_back_index); the driver knows where that member lies in the output — the
+// header members it wrote, then the bytes of the calls before — so stdout may be a pipe.  PATH is written behind the
+// end-of-file marker.
+struct IndexSink {
+    fadehip_bai *b = nullptr;
+    uint64_t at = 0;  // file offset of the next call's first member
+    std::string path;
+    ~IndexSink() { if (b) fadehip_bai_destroy(b); }
+    bool on() const { return b != nullptr; }
+    void open(const std::string &p, size_t n_ref) {
+        path = p;
+        if (!(b = fadehip_bai_create((int32_t)n_ref))) throw std::runtime_error("out of memory");
+    }
+    // the header's members through `write` into memory first, so that their size is known whatever stdout is
+    template <class WriteHeader>
+    void header(WriteHeader write) {
+        char *mp = nullptr;
+        size_t mn = 0;
+        FILE *mf = open_memstream(&mp, &mn);
+        if (!mf) throw std::runtime_error("out of memory");
+        try {
+            write(mf);
+        } catch (...) {
+            fclose(mf);
+            free(mp);
+            throw;
+        }
+        fclose(mf);
+        const bool ok = fwrite(mp, 1, mn, stdout) == mn;
+        free(mp);
+        if (!ok) throw std::runtime_error("write error on the output stream");
+        at = mn;
+    }
+    // behind a back call that gave n bytes of members
+    void call(fadehip_bam_stream *st, fadehip_ctx *ctx, size_t n) {
+        fadehip_index_call c;
+        if (fadehip_bam_back_index(st, &c)) throw std::runtime_error(fadehip_last_error(ctx));
+        if (fadehip_bai_add(b, at, &c)) throw std::runtime_error(fadehip_bai_error(b));
+        at += n;
+    }
+    void write() {
+        const uint8_t *p = nullptr;
+        size_t n = 0;
+        if (fadehip_bai_finish(b, &p, &n)) throw std::runtime_error(fadehip_bai_error(b));
+        FILE *f = fopen(path.c_str(), "wb");
+        if (!f) throw std::runtime_error("cannot write " + path + ": " + strerror(errno));
+        const bool ok = fwrite(p, 1, n, f) == n;
+        if (fclose(f) != 0 || !ok) throw std::runtime_error("write error on " + path);
+    }
+};
 
 // What `fade out -c` and `fade annotate -c` say about their output (filter.d:184-185); with --keep-sorted, what holds instead
 static void clip_warnings(const Opts &o) {
@@ -1640,6 +1703,7 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
             if (o.keep_sorted) cfg.flags |= FADEHIP_BAM_KEEP_SORTED;  // --keep-sorted: ... at their new coordinates
             if (!o.extract.empty()) cfg.flags |= FADEHIP_BAM_EXTRACT;  // --extract: every call leaves its extract records too
             if (o.eject) cfg.flags |= eject_grouped ? FADEHIP_BAM_EJECT | FADEHIP_BAM_EJECT_GROUPS : FADEHIP_BAM_EJECT;  // --eject
+            if (!o.write_index.empty()) cfg.flags |= FADEHIP_BAM_INDEX;  // --write-index: every call leaves its .bai entries too
             if (fadehip_bam_open(ctx, &cfg, &st)) { create_err = fadehip_last_error(ctx); return 1; }
             const size_t call_bytes = host_inflate ? chunk : std::min<size_t>(chunk * 3, (size_t)1 << 30);
             if (!(getenv("FADE_BAM_PREPARE") && atoi(getenv("FADE_BAM_PREPARE")) == 0) && fadehip_bam_prepare(st, call_bytes)) { create_err = fadehip_last_error(ctx); return 1; }
@@ -1705,6 +1769,7 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
         struct FileCloser { FILE *f = nullptr; ~FileCloser() { if (f) fclose(f); } } xfile;
         std::unique_ptr<Writer> xwriter;
         std::vector<Rec> xrecs;
+        IndexSink index;  // --write-index (the back thread adds every call's entries)
         StageThreads stages;
         stages.unblock = [&] {
             abort_all = true;
@@ -1883,7 +1948,13 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
         if (genome.upload(ctx)) return 1;
         if (o.timing) genome.report();
         // the header goes out through the CPU writer (its members only: no end-of-file block yet; not a byte without a device)
-        {
+        if (!o.write_index.empty()) {
+            index.open(o.write_index, hdr.names.size());
+            index.header([&](FILE *to) {
+                Writer hw(to, o.ubam ? OutFmt::UBAM : OutFmt::BAM, out_hdr, &pool, nullptr, true, false);
+                hw.close();
+            });
+        } else {
             Writer hw(stdout, o.ubam ? OutFmt::UBAM : OutFmt::BAM, out_hdr, &pool, nullptr, !lane.on || lane.k == 0 || lane.shard, false);
             hw.close();
         }
@@ -1910,6 +1981,7 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
                     ck_back.stop();
                     if (rc) throw std::runtime_error(std::string("device: ") + fadehip_last_error(ctx));
                     note_held(o, st);
+                    if (index.on()) index.call(st, ctx, n);  // (the entries live as long as the call's members: taken here)
                     OutRef ref{p, n};
                     if (xwriter) {  // (the call's extract records live as long as its members: the writer takes both)
                         int64_t n_x = 0;
@@ -2026,6 +2098,7 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
         }
         if ((!lane.on || lane.shard) && fwrite(BGZF_EOF, 1, sizeof BGZF_EOF, stdout) != sizeof BGZF_EOF) { fprintf(stderr, "[E::fade annotate] write error on the output stream\n"); return 1; }
         if (fflush(stdout) != 0 || ferror(stdout)) { fprintf(stderr, "[E::fade annotate] write error on the output stream\n"); return 1; }
+        if (index.on()) index.write();
         int64_t totals[8], n_rec = 0, n_over = 0;
         fadehip_bam_totals(st, totals, &n_rec, &n_over);
         report_held(o);
@@ -2588,6 +2661,7 @@ static void print_out_help() {
             "      --gpus 1: BAM file in, -b or -u out: filtering or clipping runs on one MI355X (rs and am read back by a kernel)\n"
             " --fragments BAM file in, -b or -u out, on one MI355X: eject every read that shares its name with an artifact read, input in any order (two passes over the file)\n"
             "--keep-sorted with -c, coordinate-sorted BAM file in, -b or -u out, on one MI355X: clipped records are written at their new coordinates, so the output stays coordinate-sorted\n"
+            "--write-index PATH: also write the BAM index (.bai) of the output, made in the same pass (coordinate-sorted output, BAM file in, -b or -u out, on one MI355X)\n"
             "    --timing print where the run spent its time to stderr\n"
             "-h    --help This help information.\n\n",
             kHeader);
@@ -2984,6 +3058,7 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
             if (job == TagsJob::EXTRACT) mode |= FADEHIP_BAM_EXTRACT | FADEHIP_BAM_NO_OUTPUT;
             else if (o.clip) mode |= FADEHIP_BAM_CLIP | (o.keep_sorted ? FADEHIP_BAM_KEEP_SORTED : 0);
             else mode |= grouped ? FADEHIP_BAM_EJECT | FADEHIP_BAM_EJECT_GROUPS : FADEHIP_BAM_EJECT;
+            if (!o.write_index.empty()) mode |= FADEHIP_BAM_INDEX;
             return open_stream(mode);
         });
         struct Joiner { std::future<int> &f; ~Joiner() { if (f.valid()) f.wait(); } } joiner{creating};
@@ -3129,6 +3204,7 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
         const OutFmt fmt = o.ubam ? OutFmt::UBAM : OutFmt::BAM;
         std::unique_ptr<Writer> xwriter;
         std::vector<Rec> xrecs;
+        IndexSink index;  // --write-index (`fade out`; with --fragments the second pass, which writes the output)
         auto take_back = [&]() {
             const uint8_t *p = nullptr;
             size_t n = 0;
@@ -3137,6 +3213,7 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
             ck_back.stop();
             if (rc) throw std::runtime_error(fadehip_last_error(ctx));
             note_held(o, st);
+            if (index.on()) index.call(st, ctx, n);
             ck_write.start();
             if (report) {
                 const uint8_t *tp = nullptr;
@@ -3203,7 +3280,7 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
             ck_front = StageClock();
             ck_back = StageClock();
             ck_write = StageClock();
-            if (open_stream(FADEHIP_BAM_EJECT_NAMED | (o.ubam ? FADEHIP_BAM_STORED : 0))) { fprintf(stderr, "[E::%s] cannot open the GPU path: %s\n", who, create_err.c_str()); return 1; }
+            if (open_stream(FADEHIP_BAM_EJECT_NAMED | (o.ubam ? FADEHIP_BAM_STORED : 0) | (o.write_index.empty() ? 0 : FADEHIP_BAM_INDEX))) { fprintf(stderr, "[E::%s] cannot open the GPU path: %s\n", who, create_err.c_str()); return 1; }
             start_pass();
         }
         StageClock ck_pass2;
@@ -3213,7 +3290,13 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
                                           "predicted_inverted_repeat\tIR_identity\tavgbq\tart_avgbq\tart_bq\tIR_bq\tflagbinary\tflag\tstrand\n"
                                         : "qname\tsc_q_scores\tsc_seq\tsc_avg_bq\tavg_bq\tart_status\n", rep_out);
         } else if (job == TagsJob::EXTRACT) xwriter.reset(new Writer(stdout, fmt, out_hdr, &pool));
-        else {
+        else if (!o.write_index.empty()) {
+            index.open(o.write_index, hdr.names.size());
+            index.header([&](FILE *to) {
+                Writer hw(to, fmt, out_hdr, &pool, nullptr, true, false);
+                hw.close();
+            });
+        } else {
             Writer hw(stdout, fmt, out_hdr, &pool, nullptr, true, false);  // (its members only: no end-of-file block yet)
             hw.close();
         }
@@ -3223,6 +3306,7 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
         } else if (xwriter) xwriter->close();
         else if (fwrite(BGZF_EOF, 1, sizeof BGZF_EOF, stdout) != sizeof BGZF_EOF) { fprintf(stderr, "[E::%s] write error on the output stream\n", who); return 1; }
         if (fflush(stdout) != 0 || ferror(stdout)) { fprintf(stderr, "[E::%s] write error on the output stream\n", who); return 1; }
+        if (index.on()) index.write();
         int64_t totals[8], n_rec = 0, n_over = 0, n_ej = 0;
         fadehip_bam_totals(st, totals, &n_rec, &n_over);
         fadehip_bam_ejected(st, &n_ej);
@@ -3272,6 +3356,31 @@ static const char *keep_sorted_refusal(const Opts &o) {
     return bgzf ? nullptr : kKeepSortedInput;
 }
 
+// --write-index PATH (`fade annotate`, `fade out`): why the option cannot run as the command line stands, or "".  The entries
+// are made on the device in the pass that writes the output: there is no host loop behind the option.  Looks at the options,
+// the environment and the first bytes of the input: no device is opened for it.
+static const char *const kWriteIndexInput = "the input is read as a BAM file on the device: not SAM text, not a pipe";
+static std::string write_index_refusal(const Opts &o, bool reports) {
+    if (!(o.bam || o.ubam)) return "the output is SAM text: an index is of BAM (-b) or uncompressed BAM (-u)";
+    if (o.gpus > 1) return "it goes with one device: not with --gpus N > 1 (the devices' indexes are not merged)";
+    if (!o.out_shards.empty()) return "it goes with one device and one output: not with --out-shards";
+    if (getenv("FADE_BAM_DEVICE") && atoi(getenv("FADE_BAM_DEVICE")) == 0) return "FADE_BAM_DEVICE=0 takes the device away, and the index is made on it (no host loop)";
+    if (reports) return std::string("the run with ") + (!o.stats_tsv.empty() ? "--stats-tsv" : "--clip-tsv") + " does not take the file path on the device: not with it";
+    const std::string &path = o.pos[1];
+    struct stat sb, sa;
+    if (o.write_index == "-") return "PATH is a file of its own: not the standard output";
+    if (o.write_index == path || (stat(o.write_index.c_str(), &sa) == 0 && stat(path.c_str(), &sb) == 0 && sa.st_dev == sb.st_dev && sa.st_ino == sb.st_ino))
+        return "PATH is a file of its own: not the input";
+    uint8_t h[4] = {0, 0, 0, 0};
+    bool bgzf = false;
+    if (path != "-" && stat(path.c_str(), &sb) == 0 && S_ISREG(sb.st_mode))
+        if (FILE *f = fopen(path.c_str(), "rb")) {
+            bgzf = fread(h, 1, 4, f) == 4 && h[0] == 0x1f && h[1] == 0x8b && (h[3] & 4);
+            fclose(f);
+        }
+    return bgzf ? "" : kWriteIndexInput;
+}
+
 // --gpus for `fade out` / `fade extract`: 1 is the file path on the device where the input and output allow it, more is not built
 static bool tags_gpus_ok(const Opts &o, const char *who) {
     if (o.seen.find('g') == std::string::npos || o.gpus == 1) return true;
@@ -3291,7 +3400,7 @@ int main(int argc, char **argv) {
             fprintf(stderr, "std.getopt.GetOptException: %s\n", err.c_str());
             return 1;
         }
-        if (!options_allowed(o, "tmwbucgBsTSPQXEK")) return 1;
+        if (!options_allowed(o, "tmwbucgBsTSPQXEKI")) return 1;
         // app.d:84-89: helpWanted | args.length < 3 (args = prog, "annotate", positionals...)
         if (o.help || o.pos.size() < 2) { print_anno_help(); return 0; }
         if (o.pos.size() < 3) {  // the reference indexes args[2] and dies; say why instead
@@ -3316,6 +3425,13 @@ int main(int argc, char **argv) {
         if (o.keep_sorted) {  // refused here, by name, before any device is opened
             if (const char *why = keep_sorted_refusal(o)) {
                 fprintf(stderr, "[E::fade-annotate] --keep-sorted: %s\n", why);
+                return 1;
+            }
+        }
+        if (!o.write_index.empty()) {  // refused here, by name, before any device is opened
+            const std::string why = write_index_refusal(o, reports);
+            if (!why.empty()) {
+                fprintf(stderr, "[E::fade-annotate] --write-index: %s\n", why.c_str());
                 return 1;
             }
         }
@@ -3373,6 +3489,10 @@ int main(int argc, char **argv) {
             fprintf(stderr, "[E::fade-annotate] --keep-sorted: %s\n", kKeepSortedInput);
             return 1;
         }
+        if (!o.write_index.empty()) {  // nor behind this one
+            fprintf(stderr, "[E::fade-annotate] --write-index: %s\n", kWriteIndexInput);
+            return 1;
+        }
         const int rc = annotate_main(cl, o);
         if (o.timing) {
             long rss_kb = 0, hwm_kb = 0;
@@ -3425,11 +3545,18 @@ int main(int argc, char **argv) {
             fprintf(stderr, "std.getopt.GetOptException: %s\n", err.c_str());
             return 1;
         }
-        if (!options_allowed(o, "ctbugTFK")) return 1;
+        if (!options_allowed(o, "ctbugTFKI")) return 1;
         if (o.help || o.pos.size() < 2) { print_out_help(); return 0; }
         if (o.keep_sorted) {  // refused here, by name, before any device is opened
             if (const char *why = keep_sorted_refusal(o)) {
                 fprintf(stderr, "[E::fade-out] --keep-sorted: %s\n", why);
+                return 1;
+            }
+        }
+        if (!o.write_index.empty()) {  // refused here, by name, before any device is opened
+            const std::string why = write_index_refusal(o, false);
+            if (!why.empty()) {
+                fprintf(stderr, "[E::fade-out] --write-index: %s\n", why.c_str());
                 return 1;
             }
         }
@@ -3456,6 +3583,12 @@ int main(int argc, char **argv) {
             bool fall_back = true;
             const int rc = tags_stream_main(cl, o, TagsJob::FRAGMENTS, &fall_back);
             if (fall_back) fprintf(stderr, "[E::fade-out] --fragments: the input is read twice, as a BAM file on the device: not SAM text, not a pipe, not %s\n", o.pos[1].c_str());
+            return fall_back ? 1 : rc;
+        }
+        if (!o.write_index.empty()) {  // the entries are made on the device: no host loop behind this option either (--gpus 1 is implied)
+            bool fall_back = true;
+            const int rc = tags_stream_main(cl, o, TagsJob::OUT, &fall_back);
+            if (fall_back) fprintf(stderr, "[E::fade-out] --write-index: %s\n", kWriteIndexInput);
             return fall_back ? 1 : rc;
         }
         if (o.seen.find('g') != std::string::npos) {  // --gpus 1: the file path on the device, where input and output allow it

@@ -250,6 +250,54 @@ int fadehip_report_batch(fadehip_ctx *ctx, int32_t which, int32_t n, const uint8
  * index.  Synchronous, on the stream and buffers it shares with fadehip_clip_batch (see there). */
 int fadehip_coord_order_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const int64_t *rec_off, int32_t *order /* [n] */);
 
+/* The BAM index (.bai, SAM specification 5.2) of coordinate-sorted records, built where they are written.
+ * The rule, which tests/bai_model.py states in Python:
+ *   span     beg = max(pos, 0), end = beg + max(reflen, 1); reflen over FADEHIP_REF_CONSUMING_OPS, 0 for a record with flag 4;
+ *            bin = reg2bin(beg, end), never the record's bin field.  refID >= 0 with end > 2^29: FADEHIP_E_UNSUPPORTED (BAI
+ *            cannot hold it), fadehip_last_error names the record
+ *   order    the key (refID as uint32, pos + 1 as uint32) must not decrease: else FADEHIP_E_INVALID, naming the record
+ *   chunks   every maximal run of consecutive records of one (refID >= 0, bin): (offset of its first record, offset behind
+ *            its last)
+ *   linear   per record with flag 4 clear, the 16 kb windows beg >> 14 .. (end - 1) >> 14 that no earlier such record of its
+ *            refID in the call reaches: (refID, window, the record's offset)
+ *   refs     every maximal run of one refID, -1 included: its first offset, the offset behind it, its records by flag 4
+ * Offsets are BGZF virtual offsets relative to the call: fadehip_bai_add rebases them.  The arrays are dense and in stream
+ * order.  htslib's folding of sparse deep bins into their parents is not done; byte equality with `samtools index` is not
+ * claimed. */
+typedef struct { int32_t tid; uint32_t bin; uint64_t beg, end; } fadehip_index_chunk;
+typedef struct { int32_t tid; uint32_t window; uint64_t off; } fadehip_index_linear;
+typedef struct { int32_t tid; int32_t reserved; uint64_t off_beg, off_end, n_mapped, n_unmapped; } fadehip_index_ref;
+typedef struct {
+    const fadehip_index_chunk *chunks;
+    const fadehip_index_linear *linear;
+    const fadehip_index_ref *refs;
+    int64_t n_chunks, n_linear, n_refs;
+    int64_t n_records;               /* records the call wrote */
+    uint64_t first_key, last_key;    /* of its first and last record (0 without records) */
+} fadehip_index_call;
+
+/* The index entries of n BAM records the caller brings (shapes as fadehip_eject_batch takes; n_cigar_op must fit too) with
+ * virtual offsets the caller brings: voff[k] is where record k starts, voff[k + 1] where it ends.  The kernels are the ones
+ * the file path runs under FADEHIP_BAM_INDEX.  *out points into memory of the ctx, good until the next record-batch call on
+ * it.  NULL arguments: FADEHIP_E_INVALID before any device call; n = 0 gives empty arrays.  Synchronous, on the stream and
+ * buffers it shares with fadehip_clip_batch (see there). */
+int fadehip_index_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const int64_t *rec_off, const uint64_t *voff /* [n + 1] */,
+                        fadehip_index_call *out);
+
+/* The host's part: a .bai out of the calls' entries, in stream order.  No device is involved (a NULL builder or argument:
+ * FADEHIP_E_INVALID; fadehip_bai_error has the message).
+ *   add     offsets + (base_file_offset << 16); chunks, first-writer-wins linear entries and reference runs appended per
+ *           reference; first_key below the previous call's last_key: FADEHIP_E_INVALID (the builder is left unchanged)
+ *   finish  within a bin, in file order, a chunk merges into the one before when prev.end >> 16 >= next.beg >> 16; a window
+ *           without an entry takes the next higher window's; pseudo-bin 37450 per reference with records; n_no_coor.
+ *           *bytes is the builder's, good until it is destroyed or added to */
+typedef struct fadehip_bai fadehip_bai;
+fadehip_bai *fadehip_bai_create(int32_t n_ref);
+int fadehip_bai_add(fadehip_bai *b, uint64_t base_file_offset, const fadehip_index_call *call);
+int fadehip_bai_finish(fadehip_bai *b, const uint8_t **bytes, size_t *n);
+const char *fadehip_bai_error(const fadehip_bai *b); /* never NULL; b may be NULL */
+void fadehip_bai_destroy(fadehip_bai *b);
+
 /* A set of read names, resident on the device: what lets `fade out --fragments` eject whole fragments — the artifact read,
  * its mate, its supplementary and secondary lines — from input in any order, without a sort by name in front and a second
  * one behind.  Records have the shapes fadehip_eject_batch takes.  Two names are equal when l_read_name and every name byte
@@ -550,7 +598,17 @@ typedef struct fadehip_bam_config {
                                    * kernels of fadehip_report_batch: fadehip_bam_back_report hands them out.  Valid only with
                                    * FROM_TAGS | NO_OUTPUT; beside them STORED alone may stand (and is ignored), anything else is
                                    * FADEHIP_E_INVALID at fadehip_bam_open; the two may be set together.  What fadehip_report_batch
-                                   * fails on fails the call at its back, fadehip_last_error naming the record's index in the stream */
+                                   * fails on fails the call at its back, fadehip_last_error naming the record's index in the stream;
+                                   * FADEHIP_BAM_INDEX: every call also leaves the .bai entries (fadehip_index_call, by the rule and
+                                   * the kernels of fadehip_index_batch) of the records it writes, as they leave — clipped, in
+                                   * KEEP_SORTED's order, without the ejected ones — at virtual offsets relative to the call's
+                                   * first member: fadehip_bam_back_index hands them out, fadehip_bai_add takes them.  It stands
+                                   * beside every flag that writes output (STORED, CLIP, KEEP_SORTED, EXTRACT, EJECT,
+                                   * EJECT_GROUPS, FROM_TAGS, EJECT_NAMED) and changes no output byte; with NO_OUTPUT, REPORT_* or
+                                   * COLLECT_NAMES fadehip_bam_open returns FADEHIP_E_INVALID and names the flag.  Records that
+                                   * leave with a key below the key in front (within a call or between two) fail that call's
+                                   * back: FADEHIP_E_INVALID, "record N: not in coordinate order", N counting the records the
+                                   * stream has written; a record that ends beyond 2^29: FADEHIP_E_UNSUPPORTED */
     const char *const *ref_names; /* [n_ref] NUL-terminated */
     uint32_t first_record;        /* payload bytes of the first member passed to front that precede the first record */
     uint32_t tail_trim;           /* payload bytes at the END of the last member (front's last call) that are not this stream's:
@@ -569,6 +627,7 @@ typedef struct fadehip_bam_config {
 #define FADEHIP_BAM_KEEP_SORTED 512
 #define FADEHIP_BAM_REPORT_STATS 1024
 #define FADEHIP_BAM_REPORT_CLIP 2048
+#define FADEHIP_BAM_INDEX 4096
 int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_bam_stream **out);
 /* The set a stream opened with FADEHIP_BAM_COLLECT_NAMES adds to, or one opened with FADEHIP_BAM_EJECT_NAMED looks names up
  * in: a set of the same ctx, attached before the first front call (later: FADEHIP_E_STATE).  The set is the caller's and
@@ -590,6 +649,10 @@ int fadehip_bam_back_extract(fadehip_bam_stream *st, const uint8_t **recs, size_
  * stream give the report one piece behind the other — in pinned memory, good as long as that back call's *out; a call
  * without rows gives 0 bytes, 0 rows (and *text NULL).  Without that flag, or before any back: FADEHIP_E_STATE. */
 int fadehip_bam_back_report(fadehip_bam_stream *st, int32_t which, const uint8_t **text, size_t *n_bytes, int64_t *n_rows);
+/* With FADEHIP_BAM_INDEX: the index entries of the call the most recent fadehip_bam_back finished, in pinned memory, good as
+ * long as that back call's *out; a call that wrote nothing gives empty arrays.  Without the flag, or before any back:
+ * FADEHIP_E_STATE. */
+int fadehip_bam_back_index(fadehip_bam_stream *st, fadehip_index_call *out);
 /* totals so far: the eight Stats.parse counters (stats.d:45-54), records, reads beyond the kernels' limits */
 int fadehip_bam_totals(fadehip_bam_stream *st, int64_t stats[8], int64_t *n_records, int64_t *n_oversize);
 /* FADEHIP_BAM_EJECT: records not written, over the calls back has taken (0 without the flag) */
