@@ -189,6 +189,14 @@ int fadehip_nameset_add_batch(fadehip_nameset* s, int n, const(ubyte)* recs, con
 int fadehip_nameset_contains_batch(fadehip_nameset* s, int n, const(ubyte)* recs, const(long)* rec_off, ubyte* hit);
 int fadehip_nameset_count(fadehip_nameset* s, long* n_names);
 void fadehip_nameset_destroy(fadehip_nameset* s);
+struct fadehip_mateset;
+int fadehip_mateset_create(fadehip_ctx* ctx, fadehip_mateset** out_);
+int fadehip_mateset_add_batch(fadehip_mateset* s, int n, const(ubyte)* recs, const(long)* rec_off, const(ubyte)* rs,
+                              const(int)* trim_left, const(int)* trim_right, const(ubyte)* pick);
+int fadehip_mates_fix_batch(fadehip_mateset* s, int n, const(ubyte)* recs, const(long)* rec_off, const(ubyte)* rs,
+                            const(int)* trim_left, const(int)* trim_right, ubyte* out_, long out_cap, long* out_off, ubyte* fixed);
+int fadehip_mateset_count(fadehip_mateset* s, long* n_entries, long* n_ambiguous);
+void fadehip_mateset_destroy(fadehip_mateset* s);
 int fadehip_genome_upload(fadehip_ctx* ctx, int n_contigs, const(long)* lengths, const(ubyte*)* seqs);
 /// columns 2-5 of a .fai line: bases to take, file offset of the first base (of the uncompressed text), bases and bytes per line
 struct fadehip_fai_entry { long length, offset; int line_bases, line_width; }
@@ -239,11 +247,15 @@ enum FADEHIP_BAM_EJECT_NAMED = 256;    /// ... with FROM_TAGS: a record is writt
 enum FADEHIP_BAM_KEEP_SORTED = 512;    /// ... with CLIP (beside it STORED, EXTRACT, FROM_TAGS only), coordinate-sorted input: the records leave in stable order by (refID, pos + 1) as unsigned, a held tail staying on the device between calls
 enum FADEHIP_BAM_REPORT_STATS = 1024;  /// ... with FROM_TAGS | NO_OUTPUT (beside them STORED only): every call also leaves the rows of `fade stats` over its records (fadehip_bam_back_report); also `which` of fadehip_report_batch
 enum FADEHIP_BAM_REPORT_CLIP = 2048;   /// ... the same for `fade stats-clip`; the two may be set together
+enum FADEHIP_BAM_COLLECT_MATES = 8192; /// ... with FROM_TAGS | CLIP | NO_OUTPUT (beside them STORED only): every primary paired-end record whose name is in the name set stores its placement as it leaves in the mate set
+enum FADEHIP_BAM_FIX_MATES = 16384;    /// ... with FROM_TAGS | CLIP (beside them STORED, KEEP_SORTED, INDEX only): every record's mate fields follow the placement the mate set holds for its mate
 enum FADEHIP_BAM_INDEX = 4096;         /// ... beside every flag that writes output: every call also leaves the .bai entries of the records it writes (fadehip_bam_back_index)
 enum FADEHIP_BAM_CLIP = 4;       /// ... artifact calls leave hard-clipped (`fade annotate -c`), by this run's rs and alignments
 int fadehip_bam_open(fadehip_ctx* ctx, const(fadehip_bam_config)* cfg, fadehip_bam_stream** out_);
 /// the set of the same ctx a COLLECT_NAMES stream adds to / an EJECT_NAMED stream looks up in; before the first front call
 int fadehip_bam_use_nameset(fadehip_bam_stream* st, fadehip_nameset* s);
+int fadehip_bam_use_mateset(fadehip_bam_stream* st, fadehip_mateset* s);
+int fadehip_bam_mates(fadehip_bam_stream* st, long* n_fixed, long* n_ambiguous);
 int fadehip_bam_prepare(fadehip_bam_stream* st, size_t call_bytes);
 int fadehip_bam_front(fadehip_bam_stream* st, const(void)* members, size_t n_bytes, int last);
 int fadehip_bam_front_raw(fadehip_bam_stream* st, const(void)* payload, size_t n_bytes, int last);

@@ -39,12 +39,15 @@ EXPORTS = [
     "fadehip_bam_back_report",
     "fadehip_index_batch", "fadehip_bam_back_index", "fadehip_bai_create", "fadehip_bai_add", "fadehip_bai_finish", "fadehip_bai_error",
     "fadehip_bai_destroy",
+    "fadehip_mateset_create", "fadehip_mateset_add_batch", "fadehip_mates_fix_batch", "fadehip_mateset_count", "fadehip_mateset_destroy",
+    "fadehip_bam_use_mateset", "fadehip_bam_mates",
 ]
 BAM_STORED, BAM_NO_OUTPUT, BAM_CLIP, BAM_EXTRACT, BAM_EJECT, BAM_EJECT_GROUPS, BAM_FROM_TAGS = 1, 2, 4, 8, 16, 32, 64  # fadehip_bam_config.flags
 BAM_COLLECT_NAMES, BAM_EJECT_NAMED = 128, 256
 BAM_KEEP_SORTED = 512
 BAM_REPORT_STATS, BAM_REPORT_CLIP = 1024, 2048  # ... and `which` of fadehip_report_batch / fadehip_bam_back_report
 BAM_INDEX = 4096  # every call leaves the .bai entries of the records it writes (fadehip_bam_back_index)
+BAM_COLLECT_MATES, BAM_FIX_MATES = 8192, 16384  # mate fields that follow the hard clip: a MateSet attached (fadehip_bam_use_mateset)
 BGZF_BLOCK = 0xff00
 BGZF_LANES = 2
 
@@ -164,6 +167,14 @@ def load():
     L.fadehip_nameset_destroy.argtypes = [vp]
     L.fadehip_nameset_destroy.restype = None
     L.fadehip_bam_use_nameset.argtypes = [vp, vp]
+    L.fadehip_mateset_create.argtypes = [vp, C.POINTER(vp)]
+    L.fadehip_mateset_add_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
+    L.fadehip_mates_fix_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, i64, vp, vp]
+    L.fadehip_mateset_count.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
+    L.fadehip_mateset_destroy.argtypes = [vp]
+    L.fadehip_mateset_destroy.restype = None
+    L.fadehip_bam_use_mateset.argtypes = [vp, vp]
+    L.fadehip_bam_mates.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     L.fadehip_genome_upload.argtypes = [vp, i32, vp, vp]
     L.fadehip_genome_upload_fasta.argtypes = [vp, C.c_char_p, i32, C.POINTER(FaiEntry)]
     L.fadehip_genome_fetch.argtypes = [vp, i32, i64, i64, vp]

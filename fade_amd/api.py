@@ -12,6 +12,7 @@ anno.d:94-107 do.  There is no CPU implementation of the alignment here.
 """
 import ctypes as C
 import os
+import re
 
 import numpy as np
 
@@ -181,6 +182,12 @@ class Context:
     def nameset(self):
         """An exact, growing set of read names resident on the device (fadehip_nameset_*): NameSet.add / contains / count."""
         return NameSet(self)
+
+    # ---- mate fields that follow the hard clip: a map from (name, segment) to the record's placement as it leaves
+    def mateset(self):
+        """A map resident on the device from (read name, segment) to where `fade out -c` leaves that record
+        (fadehip_mateset_*): MateSet.add_batch / fix_batch / count."""
+        return MateSet(self)
 
     # ---- remap.d:11-87 (`fade extract`): the device function of the file path's extract=True, on records brought here
     def extract_batch_packed(self, recs, rec_off, rs, art_tid, art_pos, cig_off, cig, out_cap=None):
@@ -521,7 +528,7 @@ class Context:
         return self.bgzf_deflate_wait(lane)
 
     def bam_stream(self, ref_names, floor_len=5, window=300, first_record=0, stored=False, tail_trim=0, no_output=False, clip=False, extract=False, eject=None, from_tags=False,
-                   collect_names=None, eject_named=None, keep_sorted=False, report=None, index=False):
+                   collect_names=None, eject_named=None, keep_sorted=False, report=None, index=False, collect_mates=None, fix_mates=False, mateset=None):
         """The file path on the device (fadehip_bam_*): BGZF members of a BAM's records in, BGZF members of the annotated
         records out.  ref_names: the BAM header's contigs (the genome must be uploaded).  clip: records called artifacts leave
         hard-clipped (`fade annotate -c`).  extract: every call also builds `fade extract`'s records of its artifact calls
@@ -541,9 +548,14 @@ class Context:
         rows of the report(s) over its records; BamStream.report(which) fetches them after each back().  index (beside every
         mode that writes output; not with no_output, report or collect_names): every call also leaves the .bai entries of the
         records it writes, at virtual offsets relative to the call's first member; BamStream.back_index() fetches them after
-        each back(), BaiBuilder makes the file of them."""
+        each back(), BaiBuilder makes the file of them.  collect_mates / fix_mates, with mateset a MateSet of this context:
+        mate fields that follow the hard clip, in two passes behind one with collect_names.  collect_mates (that pass's
+        NameSet; with from_tags, clip and no_output, beside them stored only): every primary paired-end record whose name is
+        in the NameSet stores its placement as it leaves in the MateSet.  fix_mates (with from_tags and clip; beside them
+        stored, keep_sorted and index only): every record's mate fields are set from the MateSet; BamStream.mates() counts.
+        True for collect_mates, or no mateset, sets the flag alone (the first front() then fails)."""
         return BamStream(self, ref_names, floor_len, window, first_record, stored, tail_trim, no_output, clip, extract, eject, from_tags,
-                         collect_names, eject_named, keep_sorted, report, index)
+                         collect_names, eject_named, keep_sorted, report, index, collect_mates, fix_mates, mateset)
 
     def bgzf_inflate(self, members, out_cap=None):
         """Whole BGZF members (bytes / uint8 array) -> their payloads, inflated on the device (CRC32 and ISIZE checked)."""
@@ -727,7 +739,7 @@ def format_tags(batch, contig_names, rs, aln):
 
 class BamStream:
     def __init__(self, ctx, ref_names, floor_len, window, first_record, stored=False, tail_trim=0, no_output=False, clip=False, extract=False, eject=None, from_tags=False,
-                 collect_names=None, eject_named=None, keep_sorted=False, report=None, index=False):
+                 collect_names=None, eject_named=None, keep_sorted=False, report=None, index=False, collect_mates=None, fix_mates=False, mateset=None):
         self._ctx, self._L = ctx, ctx._L
         if report not in (None, "stats", "clip", "both"):
             raise ValueError('report is None, "stats", "clip" or "both"')
@@ -738,19 +750,27 @@ class BamStream:
         names = [n.encode() if isinstance(n, str) else bytes(n) for n in ref_names]
         arr = (C.c_char_p * max(len(names), 1))(*names)
         cfg = _lib.BamConfig(floor_len, window, len(names), (_lib.BAM_STORED if stored else 0) | (_lib.BAM_NO_OUTPUT if no_output else 0) | (_lib.BAM_CLIP if clip else 0) | (_lib.BAM_EXTRACT if extract else 0) | (BAM_FROM_TAGS if from_tags else 0) | ej |
-                             (_lib.BAM_COLLECT_NAMES if collect_names else 0) | (_lib.BAM_EJECT_NAMED if eject_named else 0) | (_lib.BAM_KEEP_SORTED if keep_sorted else 0) | rp | (_lib.BAM_INDEX if index else 0), arr, first_record, tail_trim)
+                             (_lib.BAM_COLLECT_NAMES if collect_names else 0) | (_lib.BAM_EJECT_NAMED if eject_named else 0) | (_lib.BAM_KEEP_SORTED if keep_sorted else 0) | rp | (_lib.BAM_INDEX if index else 0) |
+                             (_lib.BAM_COLLECT_MATES if collect_mates else 0) | (_lib.BAM_FIX_MATES if fix_mates else 0), arr, first_record, tail_trim)
         h = C.c_void_p()
         ctx._chk(self._L.fadehip_bam_open(ctx._h, C.byref(cfg), C.byref(h)))
         self._h = h
         self._keep = None
         self._names = None
-        for ns in (collect_names, eject_named):
+        for ns in (collect_names, eject_named, collect_mates):
             if isinstance(ns, NameSet):
                 rc = self._L.fadehip_bam_use_nameset(self._h, ns._h)
                 if rc:
                     self.close()
                     ctx._chk(rc)
                 self._names = ns  # (the set outlives the stream)
+        self._mates = None
+        if isinstance(mateset, MateSet):
+            rc = self._L.fadehip_bam_use_mateset(self._h, mateset._h)
+            if rc:
+                self.close()
+                ctx._chk(rc)
+            self._mates = mateset
 
     def prepare(self, call_bytes):
         """fadehip_bam_prepare: the streams and buffers of calls of call_bytes inflated bytes, made ahead of the first call."""
@@ -797,6 +817,12 @@ class BamStream:
         n = C.c_int64(0)
         self._ctx._chk(self._L.fadehip_bam_ejected(self._h, C.byref(n)))
         return int(n.value)
+
+    def mates(self):
+        """fix_mates: (records fixed, records left alone because their mate's key is ambiguous) over the calls finished so far."""
+        n, amb = C.c_int64(0), C.c_int64(0)
+        self._ctx._chk(self._L.fadehip_bam_mates(self._h, C.byref(n), C.byref(amb)))
+        return int(n.value), int(amb.value)
 
     def held(self):
         """keep_sorted: (records, bytes) held back on the device behind the most recent finished call."""
@@ -869,6 +895,76 @@ class NameSet:
     def close(self):
         if self._h:
             self._L.fadehip_nameset_destroy(self._h)
+            self._h = None
+
+
+class MateSet:
+    """Context.mateset(): placements of clipped records on the device, and the mate fields set from them.  Records are BAM
+    records (bytes, block_size first); rs, trim_left and trim_right are what Context.clip_batch takes."""
+
+    def __init__(self, ctx):
+        self._ctx, self._L = ctx, ctx._L
+        h = C.c_void_p()
+        ctx._chk(self._L.fadehip_mateset_create(ctx._h, C.byref(h)))
+        self._h = h
+
+    @staticmethod
+    def _arrays(records, rs, trim_left, trim_right):
+        cat, off = NameSet._cat(records)
+        rs = np.ascontiguousarray(rs, dtype=np.uint8)
+        tl = np.ascontiguousarray(trim_left, dtype=np.int32)
+        tr = np.ascontiguousarray(trim_right, dtype=np.int32)
+        if not (len(rs) == len(tl) == len(tr) == len(off) - 1):
+            raise ValueError("rs, trim_left and trim_right hold one entry per record")
+        return cat, off, rs, tl, tr
+
+    def add_batch(self, records, rs, trim_left, trim_right, pick=None):
+        """Every primary paired-end record with pick[k] != 0 (pick None: every one) stores its placement as it leaves."""
+        cat, off, rs, tl, tr = self._arrays(records, rs, trim_left, trim_right)
+        if pick is not None:
+            pick = np.ascontiguousarray(pick, dtype=np.uint8)
+            if len(pick) != len(off) - 1:
+                raise ValueError("pick holds one entry per record")
+        self._ctx._chk(self._L.fadehip_mateset_add_batch(self._h, len(off) - 1, cat.ctypes.data, off.ctypes.data, rs.ctypes.data, tl.ctypes.data,
+                                                         tr.ctypes.data, pick.ctypes.data if pick is not None else None))
+
+    def fix_batch(self, records, rs, trim_left, trim_right, out_cap=None):
+        """The records clipped as Context.clip_batch clips them, their mate fields set from the map: (list of bytes,
+        uint8[n] with 0 untouched, 1 fixed, 2 the mate's key is ambiguous).  out_cap None: room for the clipped records and
+        64 bytes of a longer MC value each; a call that needs more says how much and is made again with that."""
+        cat, off, rs, tl, tr = self._arrays(records, rs, trim_left, trim_right)
+        n = len(off) - 1
+        out_off = np.zeros(n + 1, dtype=np.int64)
+        fixed = np.zeros(n, dtype=np.uint8)
+
+        def call(cap):
+            out = np.zeros(cap, dtype=np.uint8)
+            self._ctx._chk(self._L.fadehip_mates_fix_batch(self._h, n, cat.ctypes.data, off.ctypes.data, rs.ctypes.data, tl.ctypes.data, tr.ctypes.data,
+                                                           out.ctypes.data, cap, out_off.ctypes.data, fixed.ctypes.data))
+            return out
+
+        if out_cap is not None:
+            out = call(out_cap)
+        else:
+            try:
+                out = call(len(cat) + 72 * n + 8)
+            except FadeHipError as e:
+                need = re.search(r"records take (\d+) bytes", str(e))
+                if e.code != -1 or not need:
+                    raise
+                out = call(int(need.group(1)))
+        return [out[out_off[k]:out_off[k + 1]].tobytes() for k in range(n)], fixed
+
+    @property
+    def count(self):
+        """(keys in the map, how many of them are ambiguous)."""
+        n, amb = C.c_int64(0), C.c_int64(0)
+        self._ctx._chk(self._L.fadehip_mateset_count(self._h, C.byref(n), C.byref(amb)))
+        return int(n.value), int(amb.value)
+
+    def close(self):
+        if self._h:
+            self._L.fadehip_mateset_destroy(self._h)
             self._h = None
 
 

@@ -758,6 +758,15 @@ __device__ __forceinline__ void copy16(uint8_t *to, const uint8_t *from, uint32_
     if (sl < n - whole) to[whole + sl] = from[whole + sl];
 }
 
+// op j of a clipped record's new CIGAR (c.mode == 1, j < c.ncig): the new H ops around the surviving ones, the first and
+// the last of those less what the walk ate of them
+__device__ __forceinline__ uint32_t clip_op(const RecHdr &r, const ClipPlan &c, uint32_t j) {
+    const uint32_t idx = c.cf + j - c.has_l;
+    if (c.has_l && j == 0u) return (c.hard_l << 4) | 5u;
+    if (idx >= c.ce) return (c.hard_r << 4) | 5u;
+    return ld32(r.p + r.cig_off + 4u * idx) - (((idx == c.cf ? c.eat_f : 0u) + (idx + 1u == c.ce ? c.eat_b : 0u)) << 4);
+}
+
 // The clipped (or reset) record up to its aux area, by the record's sixteen lanes: the fixed fields a dword per lane, the
 // name, the new CIGAR an op per lane, the bases — shifted by a nibble when an odd number of them went at the front — and
 // the qualities.  bs_out = the record's block_size as it leaves.
@@ -774,12 +783,7 @@ __device__ __forceinline__ void clip_write_head(const RecHdr &r, const ClipPlan 
     copy16(dst + 36u, r.p + 36u, r.lname, sl);
     uint8_t *oc = dst + 36u + r.lname;
     for (uint32_t j = sl; j < c.ncig; j += 16u) {
-        uint32_t v;
-        const uint32_t idx = c.cf + j - c.has_l;
-        if (c.has_l && j == 0u) v = (c.hard_l << 4) | 5u;
-        else if (idx >= c.ce) v = (c.hard_r << 4) | 5u;
-        else v = ld32(r.p + r.cig_off + 4u * idx) - (((idx == c.cf ? c.eat_f : 0u) + (idx + 1u == c.ce ? c.eat_b : 0u)) << 4);
-        *reinterpret_cast<u32u *>(oc + 4u * j) = v;
+        *reinterpret_cast<u32u *>(oc + 4u * j) = clip_op(r, c, j);
     }
     uint8_t *os = oc + 4u * c.ncig;
     const uint8_t *s = r.p + r.seq_off + (c.sb >> 1);

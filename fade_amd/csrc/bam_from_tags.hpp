@@ -15,6 +15,7 @@
 //   EXTRACT (remap.d:29-85)     integer rs, rs & 6 and am:Z: one record per set bit from the side's contig, position and ops
 #pragma once
 #include "bam_device.hpp"
+#include "bam_mates.hpp"
 
 namespace fadehip {
 namespace bam {
@@ -27,7 +28,7 @@ struct StageCounts {
     ChunkCounts ops;               // out_bytes: the ops of the call's extract sides (the total of bam_tag_scan_kernel)
     unsigned long long stats[8];   // stats.d:45-54 over the call's records
     unsigned long long bad;        // 0: none; else ((0xffffffff - record) << 8) | FT_BAD_*: the first record that fails the call
-    unsigned long long pad;
+    unsigned long long mates;      // FADEHIP_BAM_FIX_MATES: records fixed | records whose mate's key is ambiguous << 32
 };
 
 struct FromTagsArgs {
@@ -53,6 +54,9 @@ struct FromTagsArgs {
     uint32_t *ops;
     StageCounts *sc;
     uint8_t *o, *xo;               // the record stream, the extract stream
+    // FADEHIP_BAM_FIX_MATES (bam_mates.hpp): the mate map as it is when the write kernel is launched, bam_mates_plan_kernel's plans
+    NameSetRef ms;
+    const MateFix *fix;            // [n]
 };
 
 // filter.d:24-25 / 58-59: all `fade out -c` reads of an am side is its third field — what stands behind the second comma,
@@ -237,8 +241,9 @@ __global__ __launch_bounds__(TAG_BLOCK) void bam_tags_extract_write_kernel(FromT
 
 // The records as they leave: sixteen lanes per record, four records per wavefront at a time, a block per TAG_BLOCK records
 // (whose base applies), as bam_rewrite_kernel.  A record the eject kernels took out (INFO_BAD) is skipped; with CLIP a record
-// whose plan says so leaves clipped or reset, its aux bytes unchanged; every other record is copied byte for byte.
-template <bool CLIP>
+// whose plan says so leaves clipped or reset, its aux bytes unchanged; every other record is copied byte for byte.  With
+// MATES (and CLIP) every record goes through mate_write, which patches the mate fields and MC of the records the plan fixed.
+template <bool CLIP, bool MATES = false>
 __global__ __launch_bounds__(REWRITE_WAVES * 64) void bam_tags_write_kernel(FromTagsArgs a) {
     __shared__ uint64_t off[TAG_BLOCK];
     __shared__ uint64_t wave_sum[TAG_BLOCK / 64 + 1];
@@ -274,6 +279,11 @@ __global__ __launch_bounds__(REWRITE_WAVES * 64) void bam_tags_write_kernel(From
         if (a.info[ij] & INFO_BAD) continue;
         const RecHdr r = rec_header(a.u + a.rec_off[ij]);
         uint8_t *dst = a.o + off[k];
+        if constexpr (MATES) {
+            static_assert(CLIP, "the mate fields follow a clip");
+            mate_write(a.ms, r, clip_plan(r, a.rsb[ij], a.trim_l[ij], a.trim_r[ij]), a.fix[ij], a.out_size[ij], dst, sl);
+            continue;
+        }
         if constexpr (CLIP) {
             const ClipPlan c = clip_plan(r, a.rsb[ij], a.trim_l[ij], a.trim_r[ij]);
             if (c.mode) {

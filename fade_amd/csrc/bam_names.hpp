@@ -54,6 +54,7 @@ struct NameRehashArgs {
     const unsigned long long *old_table;
     uint64_t old_slots;
     NameSetRef s;  // the new table
+    uint32_t key_extra;  // key bytes behind the name: 0 for names, 1 for the mate map's segment byte (bam_mates.hpp)
 };
 
 __device__ __forceinline__ const uint8_t *name_rec(const NameArgs &a, uint32_t i) { return a.u + (a.off32 ? (uint64_t)a.off32[i] : a.off64[i]); }
@@ -202,7 +203,7 @@ __global__ __launch_bounds__(TAG_BLOCK) void bam_eject_named_kernel(NameArgs a) 
     }
 }
 
-// Thread per slot of the old table: a used slot hashes its name again from the arena and claims an empty slot of the new
+// Thread per slot of the old table: a used slot hashes its key again from the arena and claims an empty slot of the new
 // table (no duplicates can occur).  Runs alone: nothing else of the set is in flight (see fadehip_bam.hip).
 __global__ __launch_bounds__(TAG_BLOCK) void bam_names_rehash_kernel(NameRehashArgs a) {
     const uint64_t k = (uint64_t)blockIdx.x * TAG_BLOCK + threadIdx.x;
@@ -210,7 +211,7 @@ __global__ __launch_bounds__(TAG_BLOCK) void bam_names_rehash_kernel(NameRehashA
     const unsigned long long cur = a.old_table[k];
     if (!cur) return;
     const uint32_t *e = reinterpret_cast<const uint32_t *>(a.s.arena + ((cur & NS_OFF_MASK) - 1ull));
-    const uint32_t L = 1u + (e[0] & 0xffu);
+    const uint32_t L = 1u + (e[0] & 0xffu) + a.key_extra;
     uint64_t h = NS_HASH_SEED;
     for (uint32_t j = 0; 4u * j < L; j++) h = name_hash_step(h, e[j]);
     h = name_hash_end(h, a.s.hash_bits);

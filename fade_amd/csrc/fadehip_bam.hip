@@ -6,6 +6,7 @@
 #include "bam_device.hpp"
 #include "bam_from_tags.hpp"
 #include "bam_names.hpp"
+#include "bam_mates.hpp"
 #include "bam_report.hpp"
 #include "bam_resort.hpp"
 #include "bam_index.hpp"
@@ -37,6 +38,14 @@ struct fadehip_nameset {
     uint64_t count_ub = 0, used_ub = 0;  // bounds on ctrl[NS_COUNT], ctrl[NS_USED] once everything enqueued has run
     uint32_t hash_bits = 64;
     PinBuf h_ctrl;
+    // a name set; the mate map (bam_mates.hpp) is the same buffers with one more key byte and a fourth counter
+    uint32_t key_extra = 0;
+    const char *what = "nameset";
+};
+
+// The mate map of fadehip_mateset_* / fadehip_mates_fix_batch: the name set's host part as it is, over bam_mates.hpp's entries.
+struct fadehip_mateset {
+    fadehip_nameset core;
 };
 
 namespace {
@@ -157,10 +166,10 @@ bam::NameSetRef nameset_ref(const fadehip_nameset *s) {
 int nameset_settle(fadehip_nameset *s, hipStream_t q) {
     fadehip_ctx *ctx = s->ctx;
     HIPCHK(ctx, hipDeviceSynchronize());
-    HIPCHK(ctx, hipMemcpyAsync(s->h_ctrl.p, s->ctrl.p, 24, hipMemcpyDeviceToHost, q));
+    HIPCHK(ctx, hipMemcpyAsync(s->h_ctrl.p, s->ctrl.p, 32, hipMemcpyDeviceToHost, q));
     HIPCHK(ctx, hipStreamSynchronize(q));
     const unsigned long long *c = (const unsigned long long *)s->h_ctrl.p;
-    if (c[bam::NS_ERR]) return set_err(ctx, FADEHIP_E_STATE, "nameset: the %s was full during an insert (names may be missing: the set cannot be used)", (c[bam::NS_ERR] & bam::NS_ERR_ARENA) ? "arena" : "table");
+    if (c[bam::NS_ERR]) return set_err(ctx, FADEHIP_E_STATE, "%s: the %s was full during an insert (names may be missing: the set cannot be used)", s->what, (c[bam::NS_ERR] & bam::NS_ERR_ARENA) ? "arena" : "table");
     s->used_ub = c[bam::NS_USED];
     s->count_ub = c[bam::NS_COUNT];
     return 0;
@@ -179,12 +188,12 @@ int nameset_room(fadehip_nameset *s, hipStream_t q, uint64_t n_new, uint64_t byt
         if ((rc = nameset_settle(s, q))) return rc;
         if (s->used_ub + bytes_new > (uint64_t)s->arena.cap) {  // the arena moves: offsets stay what they are
             const uint64_t want = s->used_ub + ahead * bytes_new;
-            if (want > bam::NS_OFF_MASK) return set_err(ctx, FADEHIP_E_UNSUPPORTED, "nameset: more than 2^40 bytes of names");
+            if (want > bam::NS_OFF_MASK) return set_err(ctx, FADEHIP_E_UNSUPPORTED, "%s: more than 2^40 bytes of names", s->what);
             DevBuf nb;
             if ((rc = reserve(ctx, nb, (size_t)want))) return rc;
             if (s->used_ub && (hipMemcpyAsync(nb.p, s->arena.p, (size_t)s->used_ub, hipMemcpyDeviceToDevice, q) != hipSuccess || hipStreamSynchronize(q) != hipSuccess)) {
                 release(nb);
-                return set_err(ctx, FADEHIP_E_HIP, "nameset: moving the arena failed");
+                return set_err(ctx, FADEHIP_E_HIP, "%s: moving the arena failed", s->what);
             }
             release(s->arena);
             s->arena = nb;
@@ -192,7 +201,7 @@ int nameset_room(fadehip_nameset *s, hipStream_t q, uint64_t n_new, uint64_t byt
         if (2 * (s->count_ub + n_new) > s->slots) {  // the table is hashed again into a larger one
             uint64_t slots = s->slots;
             while (slots < 2 * (s->count_ub + ahead * n_new)) slots <<= 1;
-            if (slots > ((uint64_t)1 << 36)) return set_err(ctx, FADEHIP_E_UNSUPPORTED, "nameset: more than 2^35 names");
+            if (slots > ((uint64_t)1 << 36)) return set_err(ctx, FADEHIP_E_UNSUPPORTED, "%s: more than 2^35 names", s->what);
             DevBuf nt;
             if ((rc = reserve(ctx, nt, 8 * (size_t)slots))) return rc;
             bam::NameRehashArgs ra;
@@ -202,6 +211,7 @@ int nameset_room(fadehip_nameset *s, hipStream_t q, uint64_t n_new, uint64_t byt
             s->table = nt;
             s->slots = slots;
             ra.s = nameset_ref(s);
+            ra.key_extra = s->key_extra;
             hipError_t e = hipMemsetAsync(nt.p, 0, 8 * (size_t)slots, q);
             if (e == hipSuccess) {
                 hipLaunchKernelGGL(bam::bam_names_rehash_kernel, dim3((unsigned)((ra.old_slots + bam::TAG_BLOCK - 1) / bam::TAG_BLOCK)), dim3(bam::TAG_BLOCK), 0, q, ra);
@@ -214,7 +224,7 @@ int nameset_room(fadehip_nameset *s, hipStream_t q, uint64_t n_new, uint64_t byt
                 s->table = old;  // (the old table is whole: the rehash only read it)
                 s->slots = ra.old_slots;
                 release(nt);
-                return set_err(ctx, FADEHIP_E_HIP, "nameset: hashing the table again failed%s%s", e != hipSuccess ? ": " : "", e != hipSuccess ? hipGetErrorString(e) : "");
+                return set_err(ctx, FADEHIP_E_HIP, "%s: hashing the table again failed%s%s", s->what, e != hipSuccess ? ": " : "", e != hipSuccess ? hipGetErrorString(e) : "");
             }
             DevBuf o2 = old;
             release(o2);
@@ -223,6 +233,35 @@ int nameset_room(fadehip_nameset *s, hipStream_t q, uint64_t n_new, uint64_t byt
     s->count_ub += n_new;
     s->used_ub += bytes_new;
     return 0;
+}
+
+// A new set's buffers, cleared.  env_slots: the first table's size (at least 16, rounded up to a power of two); env_bits:
+// 0 .. 64, the hash is cut to its low bits (0: every key collides with every other).
+int nameset_init(fadehip_ctx *ctx, fadehip_nameset *s, const char *env_slots, const char *env_bits) {
+    s->ctx = ctx;
+    uint64_t want = 65536;
+    if (const char *e = getenv(env_slots)) want = (uint64_t)std::max<long long>(16, std::min<long long>(atoll(e), 1ll << 32));
+    s->slots = 16;
+    while (s->slots < want) s->slots <<= 1;
+    if (const char *e = getenv(env_bits)) s->hash_bits = (uint32_t)std::max(0, std::min(64, atoi(e)));
+    int rc;
+    if ((rc = reserve(ctx, s->table, 8 * (size_t)s->slots)) || (rc = reserve(ctx, s->arena, 65536)) || (rc = reserve(ctx, s->ctrl, 256)) ||
+        (rc = reserve_pinned(ctx, s->h_ctrl, 64)))
+        return rc;
+    // (on the ctx's copy stream: the null stream would be one more queue to set up and to give back)
+    if (hipMemsetAsync(s->table.p, 0, 8 * (size_t)s->slots, ctx->copy_stream) != hipSuccess || hipMemsetAsync(s->ctrl.p, 0, 256, ctx->copy_stream) != hipSuccess ||
+        hipStreamSynchronize(ctx->copy_stream) != hipSuccess)
+        return set_err(ctx, FADEHIP_E_HIP, "%s: clearing the table failed", s->what);
+    return 0;
+}
+
+void nameset_release(fadehip_nameset *s) {
+    (void)hipSetDevice(s->ctx->device);
+    (void)hipDeviceSynchronize();
+    release(s->table);
+    release(s->arena);
+    release(s->ctrl);
+    release(s->h_ctrl);
 }
 
 // the arguments the set's kernels take of a record-batch call behind batch_upload
@@ -626,25 +665,9 @@ int fadehip_nameset_create(fadehip_ctx *ctx, fadehip_nameset **out) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
     fadehip_nameset *s = new (std::nothrow) fadehip_nameset;
     if (!s) return set_err(ctx, FADEHIP_E_NOMEM, "out of memory");
-    s->ctx = ctx;
-    // FADEHIP_NAMESET_SLOTS: the first table's size (at least 16, rounded up to a power of two);
-    // FADEHIP_NAMESET_HASH_BITS: 0 .. 64, the hash is cut to its low bits (0: every name collides with every other)
-    uint64_t want = 65536;
-    if (const char *e = getenv("FADEHIP_NAMESET_SLOTS")) want = (uint64_t)std::max<long long>(16, std::min<long long>(atoll(e), 1ll << 32));
-    s->slots = 16;
-    while (s->slots < want) s->slots <<= 1;
-    if (const char *e = getenv("FADEHIP_NAMESET_HASH_BITS")) s->hash_bits = (uint32_t)std::max(0, std::min(64, atoi(e)));
-    int rc;
-    if ((rc = reserve(ctx, s->table, 8 * (size_t)s->slots)) || (rc = reserve(ctx, s->arena, 65536)) || (rc = reserve(ctx, s->ctrl, 256)) ||
-        (rc = reserve_pinned(ctx, s->h_ctrl, 64))) {
+    if (const int rc = nameset_init(ctx, s, "FADEHIP_NAMESET_SLOTS", "FADEHIP_NAMESET_HASH_BITS")) {
         fadehip_nameset_destroy(s);
         return rc;
-    }
-    // (on the ctx's copy stream: the null stream would be one more queue to set up and to give back)
-    if (hipMemsetAsync(s->table.p, 0, 8 * (size_t)s->slots, ctx->copy_stream) != hipSuccess || hipMemsetAsync(s->ctrl.p, 0, 256, ctx->copy_stream) != hipSuccess ||
-        hipStreamSynchronize(ctx->copy_stream) != hipSuccess) {
-        fadehip_nameset_destroy(s);
-        return set_err(ctx, FADEHIP_E_HIP, "nameset: clearing the table failed");
     }
     *out = s;
     return 0;
@@ -723,13 +746,148 @@ int fadehip_nameset_count(fadehip_nameset *s, int64_t *n_names) {
 
 void fadehip_nameset_destroy(fadehip_nameset *s) {
     if (!s) return;
-    (void)hipSetDevice(s->ctx->device);
-    (void)hipDeviceSynchronize();
-    release(s->table);
-    release(s->arena);
-    release(s->ctrl);
-    release(s->h_ctrl);
+    nameset_release(s);
     delete s;
+}
+
+// ---- the mate map over records the caller brings (bam_mates.hpp): placements in, mate fields out
+int fadehip_mateset_create(fadehip_ctx *ctx, fadehip_mateset **out) {
+    if (!ctx) return set_err(nullptr, FADEHIP_E_INVALID, "ctx is NULL");
+    if (!out) return set_err(ctx, FADEHIP_E_INVALID, "NULL argument");
+    *out = nullptr;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    fadehip_mateset *m = new (std::nothrow) fadehip_mateset;
+    if (!m) return set_err(ctx, FADEHIP_E_NOMEM, "out of memory");
+    m->core.key_extra = 1;
+    m->core.what = "mateset";
+    if (const int rc = nameset_init(ctx, &m->core, "FADEHIP_MATESET_SLOTS", "FADEHIP_MATESET_HASH_BITS")) {
+        fadehip_mateset_destroy(m);
+        return rc;
+    }
+    *out = m;
+    return 0;
+}
+
+int fadehip_mateset_add_batch(fadehip_mateset *m, int32_t n, const uint8_t *recs, const int64_t *rec_off, const uint8_t *rs,
+                              const int32_t *trim_left, const int32_t *trim_right, const uint8_t *pick) {
+    if (!m) return set_err(nullptr, FADEHIP_E_INVALID, "mateset is NULL");
+    fadehip_nameset *s = &m->core;
+    fadehip_ctx *ctx = s->ctx;
+    if (n < 0 || !rec_off || (n > 0 && (!recs || !rs || !trim_left || !trim_right))) return set_err(ctx, FADEHIP_E_INVALID, "NULL argument");
+    if (rec_off[0] < 0) return set_err(ctx, FADEHIP_E_INVALID, "offsets must be non-negative and non-decreasing (record 0)");
+    if (n == 0) return 0;
+    // the call's bounds: the records that insert, and the bytes their entries take at most (bam_mates.hpp's header)
+    uint64_t n_pick = 0, b_pick = 0;
+    const auto bounds = [&](int32_t k) {
+        if (trim_left[k] < 0 || trim_right[k] < 0) return set_err(ctx, FADEHIP_E_INVALID, "record %d: negative trim length", k);
+        const uint8_t *p = recs + rec_off[k];
+        const uint32_t flag = (uint32_t)p[18] | ((uint32_t)p[19] << 8), ncig = (uint32_t)p[16] | ((uint32_t)p[17] << 8), seg = flag & 0xC0u;
+        if ((pick && !pick[k]) || !(flag & 1u) || (seg != 0x40u && seg != 0x80u) || (flag & 0x900u)) return 0;
+        n_pick++;
+        b_pick += bam::MATE_KEY_BYTES_MAX + 4ull * bam::MV_DWORDS + 11ull * (ncig + 2ull) + 3ull;
+        return 0;
+    };
+    int rc;
+    if ((rc = check_records(ctx, n, recs, rec_off, true, bounds))) return rc;
+    if (!n_pick) return 0;
+    BatchLane &L = ctx->batch;
+    std::lock_guard<std::mutex> lk(L.mu);
+    // meta: in_off [n + 1] u64 | trim_l [n] u32 | trim_r [n] u32 | rs [n] u8 | pick [n] u8
+    const size_t m_tl = 8 * ((size_t)n + 1), m_tr = m_tl + 4 * (size_t)n, m_rs = m_tr + 4 * (size_t)n, m_pick = m_rs + (size_t)n;
+    std::vector<uint64_t> off;
+    if ((rc = batch_upload(ctx, L, n, recs, rec_off, rs, m_rs, m_pick + (size_t)n + 8, 8, off))) return rc;
+    uint8_t *meta = (uint8_t *)L.meta.p;
+    HIPCHK(ctx, hipMemcpyAsync(meta + m_tl, trim_left, 4 * (size_t)n, hipMemcpyHostToDevice, L.stream));
+    HIPCHK(ctx, hipMemcpyAsync(meta + m_tr, trim_right, 4 * (size_t)n, hipMemcpyHostToDevice, L.stream));
+    if (pick) HIPCHK(ctx, hipMemcpyAsync(meta + m_pick, pick, (size_t)n, hipMemcpyHostToDevice, L.stream));
+    std::lock_guard<std::mutex> sl(s->mu);
+    if ((rc = nameset_room(s, L.stream, n_pick, b_pick, 1))) return rc;
+    bam::MateArgs a;
+    memset(&a, 0, sizeof a);
+    a.s = nameset_ref(s);
+    a.u = (const uint8_t *)L.in.p;
+    a.off64 = (const uint64_t *)meta;
+    a.n = (uint32_t)n;
+    a.rs = meta + m_rs;
+    a.trim_l = (const uint32_t *)(meta + m_tl);
+    a.trim_r = (const uint32_t *)(meta + m_tr);
+    a.pick = pick ? meta + m_pick : nullptr;
+    hipLaunchKernelGGL(bam::bam_mates_insert_kernel, dim3(((unsigned)n + bam::TAG_BLOCK - 1) / bam::TAG_BLOCK), dim3(bam::TAG_BLOCK), 0, L.stream, a);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(s->h_ctrl.p, s->ctrl.p, 32, hipMemcpyDeviceToHost, L.stream));
+    HIPCHK(ctx, hipStreamSynchronize(L.stream));
+    if (((const unsigned long long *)s->h_ctrl.p)[bam::NS_ERR]) return set_err(ctx, FADEHIP_E_STATE, "mateset: the table or the arena was full during an insert (placements may be missing: the set cannot be used)");
+    return 0;
+}
+
+// fadehip_clip_batch, then the rule: the plan kernel in the place of the size kernel, the write kernel patching what it planned.
+int fadehip_mates_fix_batch(fadehip_mateset *m, int32_t n, const uint8_t *recs, const int64_t *rec_off, const uint8_t *rs,
+                            const int32_t *trim_left, const int32_t *trim_right, uint8_t *out, int64_t out_cap, int64_t *out_off, uint8_t *fixed) {
+    if (!m) return set_err(nullptr, FADEHIP_E_INVALID, "mateset is NULL");
+    fadehip_nameset *s = &m->core;
+    fadehip_ctx *ctx = s->ctx;
+    if (n < 0 || !rec_off || !out_off || (n > 0 && (!recs || !rs || !trim_left || !trim_right || !fixed)) || out_cap < 0 || (out_cap > 0 && !out))
+        return set_err(ctx, FADEHIP_E_INVALID, "NULL argument");
+    if (rec_off[0] < 0) return set_err(ctx, FADEHIP_E_INVALID, "offsets must be non-negative and non-decreasing (record 0)");
+    if (n == 0) {
+        out_off[0] = 0;
+        return 0;
+    }
+    const auto trims = [&](int32_t k) { return trim_left[k] < 0 || trim_right[k] < 0 ? set_err(ctx, FADEHIP_E_INVALID, "record %d: negative trim length", k) : 0; };
+    int rc;
+    if ((rc = check_records(ctx, n, recs, rec_off, true, trims))) return rc;
+    BatchLane &L = ctx->batch;
+    std::lock_guard<std::mutex> lk(L.mu);
+    // meta: in_off [n + 1] u64 | out_off [n + 1] u64 | fix [n] MateFix | trim_l [n] u32 | trim_r [n] u32 | rs [n] u8;  work: out_size [n] u32
+    static_assert(sizeof(bam::MateFix) % 8 == 0, "the fix array keeps what lies behind it aligned");
+    const size_t m_out = 8 * ((size_t)n + 1), m_fix = 2 * m_out, m_tl = m_fix + sizeof(bam::MateFix) * (size_t)n, m_tr = m_tl + 4 * (size_t)n, m_rs = m_tr + 4 * (size_t)n;
+    std::vector<uint64_t> off;
+    if ((rc = batch_upload(ctx, L, n, recs, rec_off, rs, m_rs, m_rs + (size_t)n + 8, 4 * (size_t)n, off))) return rc;
+    uint8_t *meta = (uint8_t *)L.meta.p;
+    HIPCHK(ctx, hipMemcpyAsync(meta + m_tl, trim_left, 4 * (size_t)n, hipMemcpyHostToDevice, L.stream));
+    HIPCHK(ctx, hipMemcpyAsync(meta + m_tr, trim_right, 4 * (size_t)n, hipMemcpyHostToDevice, L.stream));
+    // (the set's lock is held to the end of the call: its buffers must not move under the two kernels)
+    std::lock_guard<std::mutex> sl(s->mu);
+    bam::MateArgs a;
+    memset(&a, 0, sizeof a);
+    a.s = nameset_ref(s);
+    a.u = (const uint8_t *)L.in.p;
+    a.off64 = (const uint64_t *)meta;
+    a.n = (uint32_t)n;
+    a.rs = meta + m_rs;
+    a.trim_l = (const uint32_t *)(meta + m_tl);
+    a.trim_r = (const uint32_t *)(meta + m_tr);
+    a.fix = (bam::MateFix *)(meta + m_fix);
+    a.out_off = (const uint64_t *)(meta + m_out);
+    std::vector<int64_t> ooff((size_t)n + 1);
+    if ((rc = size_then_write(ctx, L, a, (size_t)n, bam::mates_batch_plan_kernel, bam::mates_batch_write_kernel, "fixed", false, off, out, out_cap, ooff.data()))) return rc;
+    std::vector<bam::MateFix> fix((size_t)n);
+    HIPCHK(ctx, hipMemcpyAsync(fix.data(), a.fix, sizeof(bam::MateFix) * (size_t)n, hipMemcpyDeviceToHost, L.stream));
+    HIPCHK(ctx, hipMemcpyAsync(s->h_ctrl.p, s->ctrl.p, 32, hipMemcpyDeviceToHost, L.stream));
+    HIPCHK(ctx, hipStreamSynchronize(L.stream));
+    if (((const unsigned long long *)s->h_ctrl.p)[bam::NS_ERR]) return set_err(ctx, FADEHIP_E_STATE, "mateset: a look-up came round the whole table (the set cannot be used)");
+    for (int32_t k = 0; k < n; k++) fixed[k] = (uint8_t)fix[(size_t)k].state;
+    for (int32_t k = 0; k <= n; k++) out_off[k] = ooff[(size_t)k];
+    return 0;
+}
+
+int fadehip_mateset_count(fadehip_mateset *m, int64_t *n_entries, int64_t *n_ambiguous) {
+    if (!m) return set_err(nullptr, FADEHIP_E_INVALID, "mateset is NULL");
+    fadehip_nameset *s = &m->core;
+    fadehip_ctx *ctx = s->ctx;
+    if (!n_entries || !n_ambiguous) return set_err(ctx, FADEHIP_E_INVALID, "NULL argument");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    std::lock_guard<std::mutex> sl(s->mu);
+    if (const int rc = nameset_settle(s, ctx->copy_stream)) return rc;
+    *n_entries = (int64_t)s->count_ub;
+    *n_ambiguous = (int64_t)((const unsigned long long *)s->h_ctrl.p)[bam::MS_AMBIG];
+    return 0;
+}
+
+void fadehip_mateset_destroy(fadehip_mateset *m) {
+    if (!m) return;
+    nameset_release(&m->core);
+    delete m;
 }
 
 struct fadehip_bam_stream {
@@ -748,7 +906,10 @@ struct fadehip_bam_stream {
     bool keep_sorted = false;    // FADEHIP_BAM_KEEP_SORTED: clip, and the records leave in coordinate order (bam_resort.hpp)
     uint32_t report = 0;         // FADEHIP_BAM_REPORT_STATS / _CLIP as bam::RP_*: from_tags, and every call leaves the reports' rows (bam_report.hpp)
     bool index = false;          // FADEHIP_BAM_INDEX: every call leaves the .bai entries of the records it wrote (bam_index.hpp)
+    bool collect_mates = false;  // FADEHIP_BAM_COLLECT_MATES: from_tags and clip, and every primary paired-end record whose name is in `names` stores its placement in `mates` (bam_mates.hpp)
+    bool fix_mates = false;      // FADEHIP_BAM_FIX_MATES: from_tags and clip, and every record's mate fields follow the placement `mates` holds for its mate
     fadehip_nameset *names = nullptr;  // fadehip_bam_use_nameset
+    fadehip_mateset *mates = nullptr;  // fadehip_bam_use_mateset
     DevBuf names_text, names_off;
     DevBuf names_first;         // from_tags: for every contig the first one of its name (fadehip_tags_batch's rule)
     struct Out {
@@ -798,7 +959,8 @@ struct fadehip_bam_stream {
         bam::RepArgs rpa;
         bam::TagArgs xa;                      // extract: ta with the extract stream's sizes, sums, counts and output
         PinBuf h_blocks, h_counts;
-        PinBuf h_ns;                          // collect_names / eject_named: the set's ctrl words behind the call's kernels
+        PinBuf h_ns;                          // collect_names / eject_named: the set's ctrl words behind the call's kernels; the mate map's at + 32
+        DevBuf mt_hit, mt_fix;                // collect_mates: the name look-up's byte per record; fix_mates: the plan per record
         // keep_sorted (bam_resort.hpp).  Call k reads what call k - 1 left in the OTHER set — its ctl and final-order arrays in
         // its front half (behind rs_meta), the bytes of its hold in its back half (behind rs_moved) — and writes only its own
         // set's, so a call never writes what the call in front of it still reads.
@@ -848,6 +1010,7 @@ struct fadehip_bam_stream {
     std::condition_variable cv;
     int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int64_t n_records = 0, n_oversize = 0, n_redone = 0, n_ejected = 0;
+    int64_t n_fixed = 0, n_mate_ambiguous = 0;  // fix_mates
     int64_t held_recs = 0, held_bytes = 0;  // keep_sorted: behind the most recent finished call
     bool failed = false, ended = false, closing = false;
     double t_inflate = 0, t_frame = 0, t_run = 0, t_tags = 0;
@@ -1298,7 +1461,11 @@ int bam_finish_one(fadehip_bam_stream *st, uint64_t k) {
             if (st->report && ((const bam::RepCtl *)S.h_rp.p)->bad) return report_bad(ctx, ((const bam::RepCtl *)S.h_rp.p)->bad, (long long)st->n_records);
             if (st->names && S.h_ns.p && ((const unsigned long long *)S.h_ns.p)[bam::NS_ERR])
                 return set_err(ctx, FADEHIP_E_STATE, "bam stream: the name set's table or arena was full (names may be missing: the set cannot be used)");
+            if (st->mates && S.h_ns.p && ((const unsigned long long *)S.h_ns.p)[4 + bam::NS_ERR])
+                return set_err(ctx, FADEHIP_E_STATE, "bam stream: the mate set's table or arena was full (placements may be missing: the set cannot be used)");
             for (int t = 0; t < 8; t++) st->stats[t] += (int64_t)sc->stats[t];
+            st->n_fixed += (int64_t)(sc->mates & 0xffffffffull);
+            st->n_mate_ambiguous += (int64_t)(sc->mates >> 32);
         } else if (S.n_sent) {
             if ((rc = finish_run(ctx, s, (int)(k & 1)))) return rc;  // waits for the stream: run and sizes
             std::lock_guard<std::mutex> l(st->mu);
@@ -1327,7 +1494,13 @@ int bam_finish_one(fadehip_bam_stream *st, uint64_t k) {
             S.ta.o = (uint8_t *)out->o.p;
             S.fa.o = (uint8_t *)out->o.p;
         }
-        if (st->from_tags && st->clip) hipLaunchKernelGGL(bam::bam_tags_write_kernel<true>, dim3(S.ntb), dim3(bam::REWRITE_WAVES * 64), 0, q, S.fa);
+        if (st->fix_mates) {  // (under the set's lock: the arena may have moved since the plan, and must not move before this launch has run)
+            fadehip_nameset *ms = &st->mates->core;
+            std::lock_guard<std::mutex> ml(ms->mu);
+            S.fa.ms = nameset_ref(ms);
+            S.fa.fix = (const bam::MateFix *)S.mt_fix.p;
+            hipLaunchKernelGGL((bam::bam_tags_write_kernel<true, true>), dim3(S.ntb), dim3(bam::REWRITE_WAVES * 64), 0, q, S.fa);
+        } else if (st->from_tags && st->clip) hipLaunchKernelGGL(bam::bam_tags_write_kernel<true>, dim3(S.ntb), dim3(bam::REWRITE_WAVES * 64), 0, q, S.fa);
         else if (st->from_tags) hipLaunchKernelGGL(bam::bam_tags_write_kernel<false>, dim3(S.ntb), dim3(bam::REWRITE_WAVES * 64), 0, q, S.fa);
         else if (st->clip) hipLaunchKernelGGL(bam::bam_rewrite_kernel<true>, dim3(S.ntb), dim3(bam::REWRITE_WAVES * 64), 0, q, S.ta);
         else hipLaunchKernelGGL(bam::bam_rewrite_kernel<false>, dim3(S.ntb), dim3(bam::REWRITE_WAVES * 64), 0, q, S.ta);
@@ -1788,6 +1961,57 @@ int bam_front_tags(fadehip_bam_stream *st, fadehip_bam_stream::Set &S, Slot &s, 
         HIPCHK(ctx, hipGetLastError());
         HIPCHK(ctx, hipMemcpyAsync(S.h_ns.p, ns->ctrl.p, 24, hipMemcpyDeviceToHost, q));
     }
+    if (st->collect_mates || st->fix_mates) {
+        // Under the sets' locks, as above (the name set's first).  COLLECT_MATES: the name look-up, room in the map from the
+        // call's bounds — at most n_rec entries of at most key 260 + fixed 24 + padding 3 + two H ops 22 bytes and 11 bytes for
+        // each of the call's CIGAR ops, of which there are at most a quarter of its record bytes — then the insert.
+        // FIX_MATES: the plan, in front of the scan.  The write kernel gets the map as it is when IT is launched (bam_finish_call).
+        fadehip_nameset *ms = &st->mates->core;
+        if ((rc = reserve_pinned(ctx, S.h_ns, 64))) return rc;
+        bam::MateArgs ma;
+        memset(&ma, 0, sizeof ma);
+        ma.u = pa.u;
+        ma.off32 = pa.rec_off;
+        ma.n = n_rec;
+        ma.counts_in = d_counts;
+        ma.rs = fa.rsb;
+        ma.trim_l = fa.trim_l;
+        ma.trim_r = fa.trim_r;
+        if (st->collect_mates) {
+            fadehip_nameset *ns = st->names;
+            if ((rc = reserve_roomy(ctx, S.mt_hit, n + 8))) return rc;
+            std::lock_guard<std::mutex> nl(ns->mu);
+            std::lock_guard<std::mutex> ml(ms->mu);
+            bam::NameArgs na;
+            memset(&na, 0, sizeof na);
+            na.s = nameset_ref(ns);
+            na.u = pa.u;
+            na.off32 = pa.rec_off;
+            na.n = n_rec;
+            na.counts_in = d_counts;
+            na.hit = (uint8_t *)S.mt_hit.p;
+            hipLaunchKernelGGL(bam::bam_names_lookup_kernel, dim3(ntb), dim3(bam::TAG_BLOCK), 0, q, na);
+            HIPCHK(ctx, hipGetLastError());
+            if ((rc = nameset_room(ms, q, n, 312 * (uint64_t)n + 3 * (uint64_t)h_counts->consumed, 4))) return rc;
+            ma.s = nameset_ref(ms);
+            ma.pick = na.hit;
+            hipLaunchKernelGGL(bam::bam_mates_insert_kernel, dim3(ntb), dim3(bam::TAG_BLOCK), 0, q, ma);
+            HIPCHK(ctx, hipGetLastError());
+            HIPCHK(ctx, hipMemcpyAsync(S.h_ns.p, ns->ctrl.p, 32, hipMemcpyDeviceToHost, q));
+        } else {
+            if ((rc = reserve_roomy(ctx, S.mt_fix, sizeof(bam::MateFix) * n + 8))) return rc;
+            std::lock_guard<std::mutex> ml(ms->mu);
+            ma.s = nameset_ref(ms);
+            ma.info = pa.info;
+            ma.fix = (bam::MateFix *)S.mt_fix.p;
+            ma.out_size = fa.out_size;
+            ma.blk_sums = fa.blk_sums;
+            ma.n_mates = &fa.sc->mates;
+            hipLaunchKernelGGL(bam::bam_mates_plan_kernel, dim3(ntb), dim3(bam::TAG_BLOCK), 0, q, ma);
+            HIPCHK(ctx, hipGetLastError());
+        }
+        HIPCHK(ctx, hipMemcpyAsync(S.h_ns.p + 32, ms->ctrl.p, 32, hipMemcpyDeviceToHost, q));
+    }
     hipLaunchKernelGGL(bam::bam_tag_scan_kernel, dim3(1), dim3(1024), 0, q, ta, ntb);
     HIPCHK(ctx, hipGetLastError());
     if (st->report) {  // the reports' stage (bam_report.hpp); its ctl crosses with the counts
@@ -1820,8 +2044,11 @@ int bam_front_impl(fadehip_bam_stream *st, const uint8_t *members, size_t n_byte
     // the set's previous call must have been finished (back has usually done that long ago)
     CallTrace tr("front", k);
     if (ctx->n_contigs == 0 && !st->from_tags) return set_err(ctx, FADEHIP_E_STATE, "fadehip_genome_upload has not been called");
-    if ((st->collect_names || st->eject_named) && !st->names)
-        return set_err(ctx, FADEHIP_E_STATE, "bam stream: opened with FADEHIP_BAM_%s and no name set attached (fadehip_bam_use_nameset)", st->collect_names ? "COLLECT_NAMES" : "EJECT_NAMED");
+    if ((st->collect_names || st->eject_named || st->collect_mates) && !st->names)
+        return set_err(ctx, FADEHIP_E_STATE, "bam stream: opened with FADEHIP_BAM_%s and no name set attached (fadehip_bam_use_nameset)",
+                       st->collect_names ? "COLLECT_NAMES" : st->eject_named ? "EJECT_NAMED" : "COLLECT_MATES");
+    if ((st->collect_mates || st->fix_mates) && !st->mates)
+        return set_err(ctx, FADEHIP_E_STATE, "bam stream: opened with FADEHIP_BAM_%s and no mate set attached (fadehip_bam_use_mateset)", st->collect_mates ? "COLLECT_MATES" : "FIX_MATES");
     if (k >= 2 && (rc = bam_finish_call(st, k - 2))) return rc;
     tr.mark("finish call k - 2");
     // every stream is an HSA queue to set up and to give back (tens of ms each): slot 0 works on the ctx's copy stream, which
@@ -1873,7 +2100,8 @@ int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_ba
     if (!ctx) return set_err(nullptr, FADEHIP_E_INVALID, "ctx is NULL");
     if (!cfg || !out || cfg->n_ref < 0 || (cfg->n_ref && !cfg->ref_names) || (cfg->window < 0 && !(cfg->flags & FADEHIP_BAM_FROM_TAGS)) ||
         (cfg->flags & ~(FADEHIP_BAM_STORED | FADEHIP_BAM_NO_OUTPUT | FADEHIP_BAM_CLIP | FADEHIP_BAM_EXTRACT | FADEHIP_BAM_EJECT | FADEHIP_BAM_EJECT_GROUPS | FADEHIP_BAM_FROM_TAGS |
-                        FADEHIP_BAM_COLLECT_NAMES | FADEHIP_BAM_EJECT_NAMED | FADEHIP_BAM_KEEP_SORTED | FADEHIP_BAM_REPORT_STATS | FADEHIP_BAM_REPORT_CLIP | FADEHIP_BAM_INDEX)))
+                        FADEHIP_BAM_COLLECT_NAMES | FADEHIP_BAM_EJECT_NAMED | FADEHIP_BAM_KEEP_SORTED | FADEHIP_BAM_REPORT_STATS | FADEHIP_BAM_REPORT_CLIP | FADEHIP_BAM_INDEX |
+                        FADEHIP_BAM_COLLECT_MATES | FADEHIP_BAM_FIX_MATES)))
         return set_err(ctx, FADEHIP_E_INVALID, "bam stream: bad configuration");
     // the index describes records that are written: a stream that writes none has nothing to index.  It stands beside every
     // flag that writes output, and the checks below look at the flags without it
@@ -1891,10 +2119,20 @@ int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_ba
         if ((cfg->flags & need) != need || (cfg->flags & ~(need | FADEHIP_BAM_STORED | FADEHIP_BAM_REPORT_STATS | FADEHIP_BAM_REPORT_CLIP)))
             return set_err(ctx, FADEHIP_E_INVALID, "bam stream: FADEHIP_BAM_REPORT_STATS and FADEHIP_BAM_REPORT_CLIP need FADEHIP_BAM_FROM_TAGS | FADEHIP_BAM_NO_OUTPUT and combine with STORED only");
     }
+    if (cfg->flags & FADEHIP_BAM_COLLECT_MATES) {
+        const int32_t need = FADEHIP_BAM_FROM_TAGS | FADEHIP_BAM_CLIP | FADEHIP_BAM_NO_OUTPUT;
+        if ((cfg->flags & need) != need || (cfg->flags & ~(need | FADEHIP_BAM_COLLECT_MATES | FADEHIP_BAM_STORED)))
+            return set_err(ctx, FADEHIP_E_INVALID, "bam stream: FADEHIP_BAM_COLLECT_MATES needs FADEHIP_BAM_FROM_TAGS | FADEHIP_BAM_CLIP | FADEHIP_BAM_NO_OUTPUT and combines with STORED only");
+    }
+    if (cfg->flags & FADEHIP_BAM_FIX_MATES) {
+        const int32_t need = FADEHIP_BAM_FROM_TAGS | FADEHIP_BAM_CLIP;
+        if ((cfg->flags & need) != need || (cfg->flags & ~(need | FADEHIP_BAM_FIX_MATES | FADEHIP_BAM_STORED | FADEHIP_BAM_KEEP_SORTED)))
+            return set_err(ctx, FADEHIP_E_INVALID, "bam stream: FADEHIP_BAM_FIX_MATES needs FADEHIP_BAM_FROM_TAGS | FADEHIP_BAM_CLIP and combines with STORED, KEEP_SORTED and INDEX only");
+    }
     if (cfg->flags & FADEHIP_BAM_KEEP_SORTED) {
         if (!(cfg->flags & FADEHIP_BAM_CLIP)) return set_err(ctx, FADEHIP_E_INVALID, "bam stream: FADEHIP_BAM_KEEP_SORTED needs FADEHIP_BAM_CLIP (without a clip nothing moves)");
-        if (cfg->flags & ~(FADEHIP_BAM_KEEP_SORTED | FADEHIP_BAM_CLIP | FADEHIP_BAM_STORED | FADEHIP_BAM_EXTRACT | FADEHIP_BAM_FROM_TAGS))
-            return set_err(ctx, FADEHIP_E_INVALID, "bam stream: FADEHIP_BAM_KEEP_SORTED combines with CLIP, STORED, EXTRACT and FROM_TAGS only");
+        if (cfg->flags & ~(FADEHIP_BAM_KEEP_SORTED | FADEHIP_BAM_CLIP | FADEHIP_BAM_STORED | FADEHIP_BAM_EXTRACT | FADEHIP_BAM_FROM_TAGS | FADEHIP_BAM_FIX_MATES))
+            return set_err(ctx, FADEHIP_E_INVALID, "bam stream: FADEHIP_BAM_KEEP_SORTED combines with CLIP, STORED, EXTRACT, FROM_TAGS and FIX_MATES only");
     }
     if (cfg->flags & (FADEHIP_BAM_COLLECT_NAMES | FADEHIP_BAM_EJECT_NAMED)) {
         const int32_t one = cfg->flags & (FADEHIP_BAM_COLLECT_NAMES | FADEHIP_BAM_EJECT_NAMED);
@@ -1924,6 +2162,8 @@ int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_ba
     st->collect_names = (cfg->flags & FADEHIP_BAM_COLLECT_NAMES) != 0;
     st->eject_named = (cfg->flags & FADEHIP_BAM_EJECT_NAMED) != 0;
     st->keep_sorted = (cfg->flags & FADEHIP_BAM_KEEP_SORTED) != 0;
+    st->collect_mates = (cfg->flags & FADEHIP_BAM_COLLECT_MATES) != 0;
+    st->fix_mates = (cfg->flags & FADEHIP_BAM_FIX_MATES) != 0;
     st->report = ((cfg->flags & FADEHIP_BAM_REPORT_STATS) ? bam::RP_STATS : 0u) | ((cfg->flags & FADEHIP_BAM_REPORT_CLIP) ? bam::RP_CLIP : 0u);
     st->index = (all_flags & FADEHIP_BAM_INDEX) != 0;
     std::string text;
@@ -1963,9 +2203,30 @@ int fadehip_bam_use_nameset(fadehip_bam_stream *st, fadehip_nameset *s) {
     fadehip_ctx *ctx = st->ctx;
     if (!s) return set_err(ctx, FADEHIP_E_INVALID, "nameset is NULL");
     if (s->ctx != ctx) return set_err(ctx, FADEHIP_E_INVALID, "bam stream: the name set belongs to another ctx");
-    if (!st->collect_names && !st->eject_named) return set_err(ctx, FADEHIP_E_INVALID, "bam stream: opened without FADEHIP_BAM_COLLECT_NAMES or FADEHIP_BAM_EJECT_NAMED");
+    if (!st->collect_names && !st->eject_named && !st->collect_mates)
+        return set_err(ctx, FADEHIP_E_INVALID, "bam stream: opened without FADEHIP_BAM_COLLECT_NAMES, FADEHIP_BAM_EJECT_NAMED or FADEHIP_BAM_COLLECT_MATES");
     if (st->k_front) return set_err(ctx, FADEHIP_E_STATE, "bam stream: use_nameset comes before the first front call");
     st->names = s;
+    return 0;
+}
+
+int fadehip_bam_use_mateset(fadehip_bam_stream *st, fadehip_mateset *m) {
+    if (!st) return set_err(nullptr, FADEHIP_E_INVALID, "stream is NULL");
+    fadehip_ctx *ctx = st->ctx;
+    if (!m) return set_err(ctx, FADEHIP_E_INVALID, "mateset is NULL");
+    if (m->core.ctx != ctx) return set_err(ctx, FADEHIP_E_INVALID, "bam stream: the mate set belongs to another ctx");
+    if (!st->collect_mates && !st->fix_mates) return set_err(ctx, FADEHIP_E_INVALID, "bam stream: opened without FADEHIP_BAM_COLLECT_MATES or FADEHIP_BAM_FIX_MATES");
+    if (st->k_front) return set_err(ctx, FADEHIP_E_STATE, "bam stream: use_mateset comes before the first front call");
+    st->mates = m;
+    return 0;
+}
+
+int fadehip_bam_mates(fadehip_bam_stream *st, int64_t *n_fixed, int64_t *n_ambiguous) {
+    if (!st) return set_err(nullptr, FADEHIP_E_INVALID, "stream is NULL");
+    if (!n_fixed || !n_ambiguous) return set_err(st->ctx, FADEHIP_E_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> l(st->mu);
+    *n_fixed = st->n_fixed;
+    *n_ambiguous = st->n_mate_ambiguous;
     return 0;
 }
 
@@ -2407,6 +2668,8 @@ void fadehip_bam_close(fadehip_bam_stream *st) {
         release(S.h_blocks);
         release(S.h_counts);
         release(S.h_ns);
+        release(S.mt_hit);
+        release(S.mt_fix);
         release(S.rp);
         release(S.rp_scratch);
         release(S.h_rp);

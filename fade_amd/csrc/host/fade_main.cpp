@@ -85,6 +85,7 @@ struct Opts {
     bool bam = false, ubam = false, help = false, stats = false, timing = false, clip = false;
     bool eject = false;  // --eject: plain `fade out` (filter.d:209-265) in the same pass
     bool fragments = false;  // `fade out --fragments`: whole fragments leave, input in any order (a set of names on the device, two passes)
+    bool fix_mates = false;  // `fade out -c --fix-mates`: mate fields follow the clip (names, placements, write: three passes on the device)
     bool keep_sorted = false;  // --keep-sorted: with -c, the clipped output of coordinate-sorted input stays coordinate-sorted (a tail held on the device)
     std::vector<std::string> pos;
     std::string out_shards;  // --out-shards PREFIX (with --gpus N)
@@ -173,6 +174,11 @@ static bool parse_opts(int argc, char **argv, Opts &o, std::string &err) {
                 o.seen += 'F';
                 if (has_val && val != "true" && val != "false") { err = "Invalid value for option --fragments: " + val; return false; }
                 o.fragments = !has_val || val == "true";
+            }
+            else if (name == "fix-mates") {  // (a flag, as --eject)
+                o.seen += 'M';
+                if (has_val && val != "true" && val != "false") { err = "Invalid value for option --fix-mates: " + val; return false; }
+                o.fix_mates = !has_val || val == "true";
             }
             else if (name == "keep-sorted") {  // (a flag, as --eject)
                 o.seen += 'K';
@@ -270,12 +276,16 @@ struct IndexSink {
 };
 
 // What `fade out -c` and `fade annotate -c` say about their output (filter.d:184-185); with --keep-sorted, what holds instead
+static const char *const kFixMatesLine =
+    "[W::fade-out] --fix-mates: mate fields (next position, template length, mate strand and unmapped flags, MC) follow the clip: three passes over the file "
+    "(names of the artifact reads, placements of their fragments, write)\n";
 static void clip_warnings(const Opts &o) {
     if (o.keep_sorted)
         fprintf(stderr, "[W::fade-out] --keep-sorted: clipped records are written at their new coordinates, so coordinate-sorted input stays sorted; reads clipped to nothing go to the end as unmapped records\n");
     else
         fprintf(stderr, "[W::fade-out] Using the -c flag means the output SAM/BAM will not be sorted (regardless of prior sorting)\n");
-    fprintf(stderr, "[W::fade-out] You also may need to fix mate information with a tool like Picard FixMateInformation\n");
+    if (o.fix_mates) fputs(kFixMatesLine, stderr);
+    else fprintf(stderr, "[W::fade-out] You also may need to fix mate information with a tool like Picard FixMateInformation\n");
 }
 
 
@@ -2660,6 +2670,7 @@ static void print_out_help() {
             "-u    --ubam output uncompressed bam\n"
             "      --gpus 1: BAM file in, -b or -u out: filtering or clipping runs on one MI355X (rs and am read back by a kernel)\n"
             " --fragments BAM file in, -b or -u out, on one MI355X: eject every read that shares its name with an artifact read, input in any order (two passes over the file)\n"
+            " --fix-mates with -c, BAM file in, -b or -u out, on one MI355X: every read's mate fields (next position, template length, flags 0x8 / 0x20, MC) follow the clip of its mate (three passes over the file)\n"
             "--keep-sorted with -c, coordinate-sorted BAM file in, -b or -u out, on one MI355X: clipped records are written at their new coordinates, so the output stays coordinate-sorted\n"
             "--write-index PATH: also write the BAM index (.bai) of the output, made in the same pass (coordinate-sorted output, BAM file in, -b or -u out, on one MI355X)\n"
             "    --timing print where the run spent its time to stderr\n"
@@ -2937,12 +2948,15 @@ static int out_main(const std::string &cl, const Opts &o) {
 // `fade stats --gpus 1` / `fade stats-clip --gpus 1` (TagsJob::STATS / STATS_CLIP) are the same reading loop over a stream
 // with FADEHIP_BAM_REPORT_STATS / _CLIP | NO_OUTPUT: the host writes the header line, then what fadehip_bam_back_report hands
 // out, to stdout or to the file named behind the input (app.d:168-176).  No host loop behind them either.
-enum class TagsJob { OUT, EXTRACT, FRAGMENTS, STATS, STATS_CLIP };
+// `fade out -c --fix-mates` (TagsJob::FIX_MATES) is three: the names as under --fragments, then (FADEHIP_BAM_COLLECT_MATES |
+// CLIP | NO_OUTPUT) the placement of every primary paired-end read of those names into a mate map on the device, then
+// (FADEHIP_BAM_FIX_MATES | CLIP, with --keep-sorted and --write-index as asked) the output.  No host loop behind it either.
+enum class TagsJob { OUT, EXTRACT, FRAGMENTS, FIX_MATES, STATS, STATS_CLIP };
 static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, bool *fall_back) {
     *fall_back = true;
     const bool report = job == TagsJob::STATS || job == TagsJob::STATS_CLIP;
     const char *who = job == TagsJob::EXTRACT ? "fade extract" : job == TagsJob::STATS ? "fade stats" : job == TagsJob::STATS_CLIP ? "fade stats-clip" : "fade out";
-    const bool fragments = job == TagsJob::FRAGMENTS;
+    const bool fragments = job == TagsJob::FRAGMENTS, fix_mates = job == TagsJob::FIX_MATES;
     const std::string &path = o.pos[1];
     struct stat sb;
     if (!(o.bam || o.ubam || report) || path == "-" || stat(path.c_str(), &sb) != 0 || !S_ISREG(sb.st_mode)) return 1;
@@ -3001,7 +3015,7 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
         fprintf(stderr, "[W::fade extract] Output SAM/BAM will not be sorted\n");  // remap.d:13
     } else if (fragments) {
         fprintf(stderr, "[W::fade-out] --fragments: ejecting every read that shares its name with an artifact read, input in any order (two passes over the file)\n");
-    } else if (o.clip) {  // filter.d:184-185
+    } else if (o.clip) {  // filter.d:184-185 (--fix-mates: its own line in the place of the second)
         clip_warnings(o);
     } else {
         grouped = eject_mode_grouped(first_names);  // filter.d:216-220, 248
@@ -3009,19 +3023,22 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
     fadehip_ctx *ctx = nullptr;
     fadehip_bam_stream *st = nullptr;
     fadehip_nameset *names = nullptr;
+    fadehip_mateset *mates = nullptr;
     struct Guard {
         fadehip_ctx *&c;
         fadehip_bam_stream *&s;
         fadehip_nameset *&ns;
+        fadehip_mateset *&ms;
         std::vector<void *> pinned, owned;
         ~Guard() {
             if (s) fadehip_bam_close(s);
             if (ns) fadehip_nameset_destroy(ns);
+            if (ms) fadehip_mateset_destroy(ms);
             for (void *p : pinned) fadehip_host_free(c, p);
             if (c) fadehip_destroy(c);
             for (void *p : owned) free(p);
         }
-    } guard{ctx, st, names, {}, {}};
+    } guard{ctx, st, names, mates, {}, {}};
     try {
         fadehip_params prm;
         fadehip_params_default(&prm);
@@ -3042,15 +3059,17 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
             cfg.first_record = first_rec;
             cfg.flags = FADEHIP_BAM_FROM_TAGS | mode;
             if (fadehip_bam_open(ctx, &cfg, &st)) { create_err = fadehip_last_error(ctx); return 1; }
-            if (fragments && fadehip_bam_use_nameset(st, names)) { create_err = fadehip_last_error(ctx); return 1; }
+            if ((mode & (FADEHIP_BAM_COLLECT_NAMES | FADEHIP_BAM_EJECT_NAMED | FADEHIP_BAM_COLLECT_MATES)) && fadehip_bam_use_nameset(st, names)) { create_err = fadehip_last_error(ctx); return 1; }
+            if ((mode & (FADEHIP_BAM_COLLECT_MATES | FADEHIP_BAM_FIX_MATES)) && fadehip_bam_use_mateset(st, mates)) { create_err = fadehip_last_error(ctx); return 1; }
             const size_t call_bytes = host_inflate ? chunk : std::min<size_t>(chunk * 3, (size_t)1 << 30);
             if (!(getenv("FADE_BAM_PREPARE") && atoi(getenv("FADE_BAM_PREPARE")) == 0) && fadehip_bam_prepare(st, call_bytes)) { create_err = fadehip_last_error(ctx); return 1; }
             return 0;
         };
         std::future<int> creating = std::async(std::launch::async, [&]() -> int {
             if (fadehip_create(&ctx, device, &prm)) { create_err = fadehip_last_error(nullptr); return 1; }
-            if (fragments) {
+            if (fragments || fix_mates) {
                 if (fadehip_nameset_create(ctx, &names)) { create_err = fadehip_last_error(ctx); return 1; }
+                if (fix_mates && fadehip_mateset_create(ctx, &mates)) { create_err = fadehip_last_error(ctx); return 1; }
                 return open_stream(FADEHIP_BAM_COLLECT_NAMES | FADEHIP_BAM_NO_OUTPUT);
             }
             if (report) return open_stream(FADEHIP_BAM_NO_OUTPUT | (job == TagsJob::STATS ? FADEHIP_BAM_REPORT_STATS : FADEHIP_BAM_REPORT_CLIP));
@@ -3264,7 +3283,7 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
         if (!ended) { fprintf(stderr, "[E::%s] the input ended before its last call\n", who); return 1; }
         return 0;
         };
-        if (fragments) {  // pass 1: the names of the artifact calls; then the stream of pass 2, and the reader again
+        if (fragments || fix_mates) {  // pass 1: the names of the artifact calls; then the stream of pass 2, and the reader again
             StageClock ck_pass;
             ck_pass.start();
             if (run_calls()) return 1;
@@ -3280,7 +3299,33 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
             ck_front = StageClock();
             ck_back = StageClock();
             ck_write = StageClock();
-            if (open_stream(FADEHIP_BAM_EJECT_NAMED | (o.ubam ? FADEHIP_BAM_STORED : 0) | (o.write_index.empty() ? 0 : FADEHIP_BAM_INDEX))) { fprintf(stderr, "[E::%s] cannot open the GPU path: %s\n", who, create_err.c_str()); return 1; }
+            if (open_stream(fix_mates ? FADEHIP_BAM_COLLECT_MATES | FADEHIP_BAM_CLIP | FADEHIP_BAM_NO_OUTPUT
+                                      : FADEHIP_BAM_EJECT_NAMED | (o.ubam ? FADEHIP_BAM_STORED : 0) | (o.write_index.empty() ? 0 : FADEHIP_BAM_INDEX))) {
+                fprintf(stderr, "[E::%s] cannot open the GPU path: %s\n", who, create_err.c_str());
+                return 1;
+            }
+            start_pass();
+        }
+        if (fix_mates) {  // pass 2: the placements of those names' primary paired-end reads; then the stream of pass 3
+            StageClock ck_pass;
+            ck_pass.start();
+            if (run_calls()) return 1;
+            int64_t n_entries = 0, n_amb = 0;
+            if (fadehip_mateset_count(mates, &n_entries, &n_amb)) { fprintf(stderr, "[E::%s] %s\n", who, fadehip_last_error(ctx)); return 1; }
+            fadehip_bam_close(st);
+            st = nullptr;
+            ck_pass.stop();
+            if (o.timing)
+                fprintf(stderr, "[timing] pass 2 (placements of the reads of those names into the mate map) %.3f s: front %.3f | back %.3f; %lld placements stored, %lld of them ambiguous\n",
+                        ck_pass.t, ck_front.t, ck_back.t, (long long)n_entries, (long long)n_amb);
+            ck_front = StageClock();
+            ck_back = StageClock();
+            ck_write = StageClock();
+            if (open_stream(FADEHIP_BAM_FIX_MATES | FADEHIP_BAM_CLIP | (o.ubam ? FADEHIP_BAM_STORED : 0) | (o.keep_sorted ? FADEHIP_BAM_KEEP_SORTED : 0) |
+                            (o.write_index.empty() ? 0 : FADEHIP_BAM_INDEX))) {
+                fprintf(stderr, "[E::%s] cannot open the GPU path: %s\n", who, create_err.c_str());
+                return 1;
+            }
             start_pass();
         }
         StageClock ck_pass2;
@@ -3314,6 +3359,12 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
         ck_pass2.stop();
         if (fragments && o.timing)
             fprintf(stderr, "[timing] pass 2 (records whose name is not in the set) %.3f s: front %.3f | back %.3f | write %.3f\n", ck_pass2.t, ck_front.t, ck_back.t, ck_write.t);
+        if (fix_mates && o.timing) {
+            int64_t n_fixed = 0, n_amb = 0;
+            fadehip_bam_mates(st, &n_fixed, &n_amb);
+            fprintf(stderr, "[timing] pass 3 (clip, mate fields from the map, write) %.3f s: front %.3f | back %.3f | write %.3f; %lld records fixed, %lld left alone (mate ambiguous)\n", ck_pass2.t,
+                    ck_front.t, ck_back.t, ck_write.t, (long long)n_fixed, (long long)n_amb);
+        }
         if (job != TagsJob::EXTRACT && !report) {  // filter.d:267
             OutStats stats;
             stats.read_count = totals[0]; stats.clipped = totals[1]; stats.sup = totals[2]; stats.art_sup = totals[3];
@@ -3545,8 +3596,20 @@ int main(int argc, char **argv) {
             fprintf(stderr, "std.getopt.GetOptException: %s\n", err.c_str());
             return 1;
         }
-        if (!options_allowed(o, "ctbugTFKI")) return 1;
+        if (!options_allowed(o, "ctbugTFKIM")) return 1;
         if (o.help || o.pos.size() < 2) { print_out_help(); return 0; }
+        if (o.fix_mates) {  // refused here, by name, before any device is opened: the map lives on one device, and there is no host loop
+            const char *why = !o.clip ? "without -c no record moves and no mate field goes stale: the option goes with -c"
+                              : o.fragments ? "--fragments ejects the artifact reads with every read of their name, and no mate is left to fix: not with --fragments"
+                              : !(o.bam || o.ubam) ? "the output is SAM text: --fix-mates writes BAM (-b) or uncompressed BAM (-u)"
+                              : o.seen.find('g') != std::string::npos && o.gpus != 1 ? "it goes with one device (--gpus 1): the mate map lives on it"
+                              : getenv("FADE_BAM_DEVICE") && atoi(getenv("FADE_BAM_DEVICE")) == 0 ? "FADE_BAM_DEVICE=0 takes the device away, and --fix-mates runs on it alone (no host loop)"
+                              : nullptr;
+            if (why) {
+                fprintf(stderr, "[E::fade-out] --fix-mates: %s\n", why);
+                return 1;
+            }
+        }
         if (o.keep_sorted) {  // refused here, by name, before any device is opened
             if (const char *why = keep_sorted_refusal(o)) {
                 fprintf(stderr, "[E::fade-out] --keep-sorted: %s\n", why);
@@ -3564,6 +3627,12 @@ int main(int argc, char **argv) {
         if (o.bam && o.ubam) {
             fprintf(stderr, "[E::fade-annotate] Please use only one of the b or u flags\n");  // app.d:122 (sic)
             return 1;
+        }
+        if (o.fix_mates) {
+            bool fall_back = true;
+            const int rc = tags_stream_main(cl, o, TagsJob::FIX_MATES, &fall_back);
+            if (fall_back) fprintf(stderr, "[E::fade-out] --fix-mates: the input is read three times, as a BAM file on the device: not SAM text, not a pipe, not %s\n", o.pos[1].c_str());
+            return fall_back ? 1 : rc;
         }
         if (o.keep_sorted) {  // the tail is held on the device: there is no host loop behind this option either (--gpus 1 is implied)
             bool fall_back = true;

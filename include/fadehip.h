@@ -321,6 +321,44 @@ int fadehip_nameset_contains_batch(fadehip_nameset *s, int32_t n, const uint8_t 
 int fadehip_nameset_count(fadehip_nameset *s, int64_t *n_names);
 void fadehip_nameset_destroy(fadehip_nameset *s);
 
+/* A map, resident on the device, from (read name, segment) to where that record ends up once `fade out -c` has clipped
+ * it — and the call that lets every record's mate fields follow: after a hard clip the mate's next_pos, tlen, flag 0x20 and
+ * MC:Z describe a record that no longer exists, and the mate of a reset record points at nothing.
+ * A record is paired-end when flag & 0x1 is set and exactly one of 0x40 / 0x80 is; its key is l_read_name, the name bytes
+ * and flag & 0xC0; its mate's key is the same name with the other segment.  "As it leaves" is the record as
+ * fadehip_clip_batch writes it for the same rs, trim_left and trim_right.
+ *   add_batch   every primary (flag & 0x900 == 0) paired-end record with pick[k] != 0 (pick NULL: every such record)
+ *               stores its placement as it leaves under its key: reset / unmapped / mapped, refID, pos, strand, the 5' end
+ *               (pos, or for a reverse record pos + max(1, reference bases of the leaving CIGAR) - 1) and the leaving
+ *               CIGAR as SAM text.  A second insert under a key the map holds marks the entry ambiguous, whatever the two
+ *               placements are and whichever came first.
+ *   fix_batch   writes every record as fadehip_clip_batch does (same out / out_off shapes); then a record that leaves
+ *               paired-end and whose mate's key is in the map and not ambiguous gets its mate fields from the mate's
+ *               placement V — V reset: flag |= 0x8, flag &= ~0x22, next_refID / next_pos its own refID / pos, tlen 0, the
+ *               first MC:Z field removed; otherwise next_refID / next_pos V's, 0x20 V's strand, 0x8 exactly when V is
+ *               unmapped, tlen 0 when either is unmapped, a refID is negative or the two differ, else with
+ *               d = V's 5' end - its own: d + 1 when d >= 0, d - 1 otherwise; the value of the first MC:Z field replaced in
+ *               place by V's CIGAR text (the field removed when V is unmapped or has no ops; none is added; an MC of
+ *               another type and a second MC:Z stay).  Its own refID, pos, bin, mapq and every other aux byte never
+ *               change.  fixed[k]: 0 untouched, 1 fixed, 2 the mate's key is ambiguous (the record leaves as
+ *               fadehip_clip_batch writes it).  An output of more than out_cap bytes: FADEHIP_E_INVALID with the number
+ *               needed in fadehip_last_error, and nothing is written to out, out_off or fixed.
+ *   count       keys in the map, and how many of them are ambiguous.
+ * The calls are synchronous, on the stream, the buffers and the lock they share with fadehip_clip_batch.  A malformed
+ * record (block_size, l_read_name, n_cigar_op, l_seq against its bytes) or a negative trim: FADEHIP_E_INVALID with the
+ * record's index, the map left as it was.  A NULL map or NULL arrays: FADEHIP_E_INVALID before anything reaches the device.
+ * Environment, read at create: FADEHIP_MATESET_SLOTS and FADEHIP_MATESET_HASH_BITS, as the name set's two.  Results depend
+ * on neither.  tests/mates_model.py states the rule in plain Python. */
+typedef struct fadehip_mateset fadehip_mateset;
+int fadehip_mateset_create(fadehip_ctx *ctx, fadehip_mateset **out);
+int fadehip_mateset_add_batch(fadehip_mateset *s, int32_t n, const uint8_t *recs, const int64_t *rec_off, const uint8_t *rs,
+                              const int32_t *trim_left, const int32_t *trim_right, const uint8_t *pick /* [n] or NULL */);
+int fadehip_mates_fix_batch(fadehip_mateset *s, int32_t n, const uint8_t *recs, const int64_t *rec_off, const uint8_t *rs,
+                            const int32_t *trim_left, const int32_t *trim_right, uint8_t *out, int64_t out_cap,
+                            int64_t *out_off /* [n + 1] out */, uint8_t *fixed /* [n] out */);
+int fadehip_mateset_count(fadehip_mateset *s, int64_t *n_entries, int64_t *n_ambiguous);
+void fadehip_mateset_destroy(fadehip_mateset *s);
+
 /* ------------------------------------------------------ Level 2: annotateTask over a batch -- */
 /* Upload the indexed FASTA once (what IndexedFastaFile + fetchSequence serve, analysis.d:63).
  * seqs[c] holds lengths[c] ASCII residues (any case; upper-cased on device as analysis.d:63 does).
@@ -608,7 +646,18 @@ typedef struct fadehip_bam_config {
                                    * COLLECT_NAMES fadehip_bam_open returns FADEHIP_E_INVALID and names the flag.  Records that
                                    * leave with a key below the key in front (within a call or between two) fail that call's
                                    * back: FADEHIP_E_INVALID, "record N: not in coordinate order", N counting the records the
-                                   * stream has written; a record that ends beyond 2^29: FADEHIP_E_UNSUPPORTED */
+                                   * stream has written; a record that ends beyond 2^29: FADEHIP_E_UNSUPPORTED;
+                                   * FADEHIP_BAM_COLLECT_MATES / FADEHIP_BAM_FIX_MATES: mate fields that follow the hard clip, the
+                                   * rule of fadehip_mates_fix_batch over a file, in passes behind one of COLLECT_NAMES on the same
+                                   * name set.  COLLECT_MATES (needs FROM_TAGS | CLIP | NO_OUTPUT, beside them STORED alone; a name
+                                   * set and a mate set attached): every primary paired-end record whose name is in the name set
+                                   * stores its placement as it leaves in the mate set.  FIX_MATES (needs FROM_TAGS | CLIP; beside
+                                   * them STORED, KEEP_SORTED and INDEX only; a mate set attached): every record is clipped as under
+                                   * CLIP alone, then its mate fields are set from the mate set; fadehip_bam_mates counts.  A
+                                   * record's own refID, pos and bin never change, so KEEP_SORTED's order and INDEX's entries are
+                                   * those of CLIP alone, but for the bytes MC gains or loses.  Any other combination:
+                                   * FADEHIP_E_INVALID at fadehip_bam_open, naming the flag; without the sets attached the first
+                                   * front call fails with FADEHIP_E_STATE */
     const char *const *ref_names; /* [n_ref] NUL-terminated */
     uint32_t first_record;        /* payload bytes of the first member passed to front that precede the first record */
     uint32_t tail_trim;           /* payload bytes at the END of the last member (front's last call) that are not this stream's:
@@ -628,11 +677,19 @@ typedef struct fadehip_bam_config {
 #define FADEHIP_BAM_REPORT_STATS 1024
 #define FADEHIP_BAM_REPORT_CLIP 2048
 #define FADEHIP_BAM_INDEX 4096
+#define FADEHIP_BAM_COLLECT_MATES 8192
+#define FADEHIP_BAM_FIX_MATES 16384
 int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_bam_stream **out);
 /* The set a stream opened with FADEHIP_BAM_COLLECT_NAMES adds to, or one opened with FADEHIP_BAM_EJECT_NAMED looks names up
  * in: a set of the same ctx, attached before the first front call (later: FADEHIP_E_STATE).  The set is the caller's and
  * outlives the stream; it may grow while two calls of the stream are in flight. */
 int fadehip_bam_use_nameset(fadehip_bam_stream *st, fadehip_nameset *s);
+/* The mate map a stream opened with FADEHIP_BAM_COLLECT_MATES stores placements in, or one opened with
+ * FADEHIP_BAM_FIX_MATES sets mate fields from: a map of the same ctx, attached before the first front call (later:
+ * FADEHIP_E_STATE).  The map is the caller's and outlives the stream.  fadehip_bam_mates: the records fixed and the records
+ * left alone because their mate's key is ambiguous, over the calls finished so far. */
+int fadehip_bam_use_mateset(fadehip_bam_stream *st, fadehip_mateset *s);
+int fadehip_bam_mates(fadehip_bam_stream *st, int64_t *n_fixed, int64_t *n_ambiguous);
 int fadehip_bam_prepare(fadehip_bam_stream *st, size_t call_bytes);
 int fadehip_bam_front(fadehip_bam_stream *st, const void *members, size_t n_bytes, int last);
 /* front for a caller that inflates itself (host cores otherwise idle; the device then spends its time on the rest):
