@@ -197,6 +197,18 @@ int fadehip_mates_fix_batch(fadehip_mateset* s, int n, const(ubyte)* recs, const
                             const(int)* trim_left, const(int)* trim_right, ubyte* out_, long out_cap, long* out_off, ubyte* fixed);
 int fadehip_mateset_count(fadehip_mateset* s, long* n_entries, long* n_ambiguous);
 void fadehip_mateset_destroy(fadehip_mateset* s);
+/// A store of BAM records on the device: added in any order (add_batch, or a FADEHIP_BAM_STORE_EXTRACT stream), sorted once by
+/// (refID, pos + 1) as unsigned with ties in the order added, drained in that order (fadehip.h, DESIGN.md 3.8l)
+struct fadehip_recstore;
+enum FADEHIP_RECSTORE_RAW = 1;     /// fadehip_recstore_drain's flags: the records back to back, no codec
+enum FADEHIP_RECSTORE_STORED = 2;  /// ... stored BGZF members (0: members from the device compressor)
+enum FADEHIP_RECSTORE_INDEX = 4;   /// ... beside 0 or STORED: *idx also gets the drained records' .bai entries, relative to the drain's first member
+int fadehip_recstore_create(fadehip_ctx* ctx, fadehip_recstore** out_);
+int fadehip_recstore_add_batch(fadehip_recstore* s, int n, const(ubyte)* recs, const(long)* rec_off, const(ubyte)* pick);
+int fadehip_recstore_count(fadehip_recstore* s, long* n_records, long* n_bytes);
+int fadehip_recstore_sort(fadehip_recstore* s);
+int fadehip_recstore_drain(fadehip_recstore* s, int flags, ulong max_payload, const(ubyte)** out_, size_t* out_bytes, long* n_records, fadehip_index_call* idx);
+void fadehip_recstore_destroy(fadehip_recstore* s);
 int fadehip_genome_upload(fadehip_ctx* ctx, int n_contigs, const(long)* lengths, const(ubyte*)* seqs);
 /// columns 2-5 of a .fai line: bases to take, file offset of the first base (of the uncompressed text), bases and bytes per line
 struct fadehip_fai_entry { long length, offset; int line_bases, line_width; }
@@ -250,12 +262,15 @@ enum FADEHIP_BAM_REPORT_CLIP = 2048;   /// ... the same for `fade stats-clip`; t
 enum FADEHIP_BAM_COLLECT_MATES = 8192; /// ... with FROM_TAGS | CLIP | NO_OUTPUT (beside them STORED only): every primary paired-end record whose name is in the name set stores its placement as it leaves in the mate set
 enum FADEHIP_BAM_FIX_MATES = 16384;    /// ... with FROM_TAGS | CLIP (beside them STORED, KEEP_SORTED, INDEX only): every record's mate fields follow the placement the mate set holds for its mate
 enum FADEHIP_BAM_INDEX = 4096;         /// ... beside every flag that writes output: every call also leaves the .bai entries of the records it writes (fadehip_bam_back_index)
+enum FADEHIP_BAM_STORE_EXTRACT = 32768;  /// ... with EXTRACT: the calls' extract records go into the attached record store and stay on the device (fadehip_bam_use_recstore); fadehip_bam_back_extract gives 0 bytes and the records added
 enum FADEHIP_BAM_CLIP = 4;       /// ... artifact calls leave hard-clipped (`fade annotate -c`), by this run's rs and alignments
 int fadehip_bam_open(fadehip_ctx* ctx, const(fadehip_bam_config)* cfg, fadehip_bam_stream** out_);
 /// the set of the same ctx a COLLECT_NAMES stream adds to / an EJECT_NAMED stream looks up in; before the first front call
 int fadehip_bam_use_nameset(fadehip_bam_stream* st, fadehip_nameset* s);
 int fadehip_bam_use_mateset(fadehip_bam_stream* st, fadehip_mateset* s);
 int fadehip_bam_mates(fadehip_bam_stream* st, long* n_fixed, long* n_ambiguous);
+/// the store of the same ctx a STORE_EXTRACT stream appends its extract records to; before the first front call
+int fadehip_bam_use_recstore(fadehip_bam_stream* st, fadehip_recstore* s);
 int fadehip_bam_prepare(fadehip_bam_stream* st, size_t call_bytes);
 int fadehip_bam_front(fadehip_bam_stream* st, const(void)* members, size_t n_bytes, int last);
 int fadehip_bam_front_raw(fadehip_bam_stream* st, const(void)* payload, size_t n_bytes, int last);

@@ -41,6 +41,8 @@ EXPORTS = [
     "fadehip_bai_destroy",
     "fadehip_mateset_create", "fadehip_mateset_add_batch", "fadehip_mates_fix_batch", "fadehip_mateset_count", "fadehip_mateset_destroy",
     "fadehip_bam_use_mateset", "fadehip_bam_mates",
+    "fadehip_recstore_create", "fadehip_recstore_add_batch", "fadehip_recstore_count", "fadehip_recstore_sort", "fadehip_recstore_drain",
+    "fadehip_recstore_destroy", "fadehip_bam_use_recstore",
 ]
 BAM_STORED, BAM_NO_OUTPUT, BAM_CLIP, BAM_EXTRACT, BAM_EJECT, BAM_EJECT_GROUPS, BAM_FROM_TAGS = 1, 2, 4, 8, 16, 32, 64  # fadehip_bam_config.flags
 BAM_COLLECT_NAMES, BAM_EJECT_NAMED = 128, 256
@@ -48,6 +50,8 @@ BAM_KEEP_SORTED = 512
 BAM_REPORT_STATS, BAM_REPORT_CLIP = 1024, 2048  # ... and `which` of fadehip_report_batch / fadehip_bam_back_report
 BAM_INDEX = 4096  # every call leaves the .bai entries of the records it writes (fadehip_bam_back_index)
 BAM_COLLECT_MATES, BAM_FIX_MATES = 8192, 16384  # mate fields that follow the hard clip: a MateSet attached (fadehip_bam_use_mateset)
+BAM_STORE_EXTRACT = 32768  # with BAM_EXTRACT: the extract records go into a RecStore attached (fadehip_bam_use_recstore), not to the host
+RECSTORE_RAW, RECSTORE_STORED, RECSTORE_INDEX = 1, 2, 4  # fadehip_recstore_drain's flags
 BGZF_BLOCK = 0xff00
 BGZF_LANES = 2
 
@@ -174,6 +178,14 @@ def load():
     L.fadehip_mateset_destroy.argtypes = [vp]
     L.fadehip_mateset_destroy.restype = None
     L.fadehip_bam_use_mateset.argtypes = [vp, vp]
+    L.fadehip_recstore_create.argtypes = [vp, C.POINTER(vp)]
+    L.fadehip_recstore_add_batch.argtypes = [vp, i32, vp, vp, vp]
+    L.fadehip_recstore_count.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
+    L.fadehip_recstore_sort.argtypes = [vp]
+    L.fadehip_recstore_drain.argtypes = [vp, i32, C.c_uint64, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(i64), C.POINTER(IndexCall)]
+    L.fadehip_recstore_destroy.argtypes = [vp]
+    L.fadehip_recstore_destroy.restype = None
+    L.fadehip_bam_use_recstore.argtypes = [vp, vp]
     L.fadehip_bam_mates.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     L.fadehip_genome_upload.argtypes = [vp, i32, vp, vp]
     L.fadehip_genome_upload_fasta.argtypes = [vp, C.c_char_p, i32, C.POINTER(FaiEntry)]

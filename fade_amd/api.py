@@ -184,6 +184,10 @@ class Context:
         return NameSet(self)
 
     # ---- mate fields that follow the hard clip: a map from (name, segment) to the record's placement as it leaves
+    def recstore(self):
+        """A store of BAM records on this context's device (fadehip_recstore_*): see RecStore."""
+        return RecStore(self)
+
     def mateset(self):
         """A map resident on the device from (read name, segment) to where `fade out -c` leaves that record
         (fadehip_mateset_*): MateSet.add_batch / fix_batch / count."""
@@ -528,7 +532,7 @@ class Context:
         return self.bgzf_deflate_wait(lane)
 
     def bam_stream(self, ref_names, floor_len=5, window=300, first_record=0, stored=False, tail_trim=0, no_output=False, clip=False, extract=False, eject=None, from_tags=False,
-                   collect_names=None, eject_named=None, keep_sorted=False, report=None, index=False, collect_mates=None, fix_mates=False, mateset=None):
+                   collect_names=None, eject_named=None, keep_sorted=False, report=None, index=False, collect_mates=None, fix_mates=False, mateset=None, recstore=None):
         """The file path on the device (fadehip_bam_*): BGZF members of a BAM's records in, BGZF members of the annotated
         records out.  ref_names: the BAM header's contigs (the genome must be uploaded).  clip: records called artifacts leave
         hard-clipped (`fade annotate -c`).  extract: every call also builds `fade extract`'s records of its artifact calls
@@ -553,9 +557,13 @@ class Context:
         NameSet; with from_tags, clip and no_output, beside them stored only): every primary paired-end record whose name is
         in the NameSet stores its placement as it leaves in the MateSet.  fix_mates (with from_tags and clip; beside them
         stored, keep_sorted and index only): every record's mate fields are set from the MateSet; BamStream.mates() counts.
-        True for collect_mates, or no mateset, sets the flag alone (the first front() then fails)."""
+        True for collect_mates, or no mateset, sets the flag alone (the first front() then fails).  recstore (a RecStore of
+        this context; with extract, wherever extract stands): the calls' extract records stay on the device, appended to the
+        store in stream order — back_extract() then gives no bytes and the number of records the call added — to be sorted
+        and drained once the stream has ended (`fade extract --sorted`, `fade annotate --extract-sorted`).  True instead of a
+        store sets the flag alone (the first front() then fails)."""
         return BamStream(self, ref_names, floor_len, window, first_record, stored, tail_trim, no_output, clip, extract, eject, from_tags,
-                         collect_names, eject_named, keep_sorted, report, index, collect_mates, fix_mates, mateset)
+                         collect_names, eject_named, keep_sorted, report, index, collect_mates, fix_mates, mateset, recstore)
 
     def bgzf_inflate(self, members, out_cap=None):
         """Whole BGZF members (bytes / uint8 array) -> their payloads, inflated on the device (CRC32 and ISIZE checked)."""
@@ -739,7 +747,7 @@ def format_tags(batch, contig_names, rs, aln):
 
 class BamStream:
     def __init__(self, ctx, ref_names, floor_len, window, first_record, stored=False, tail_trim=0, no_output=False, clip=False, extract=False, eject=None, from_tags=False,
-                 collect_names=None, eject_named=None, keep_sorted=False, report=None, index=False, collect_mates=None, fix_mates=False, mateset=None):
+                 collect_names=None, eject_named=None, keep_sorted=False, report=None, index=False, collect_mates=None, fix_mates=False, mateset=None, recstore=None):
         self._ctx, self._L = ctx, ctx._L
         if report not in (None, "stats", "clip", "both"):
             raise ValueError('report is None, "stats", "clip" or "both"')
@@ -751,7 +759,7 @@ class BamStream:
         arr = (C.c_char_p * max(len(names), 1))(*names)
         cfg = _lib.BamConfig(floor_len, window, len(names), (_lib.BAM_STORED if stored else 0) | (_lib.BAM_NO_OUTPUT if no_output else 0) | (_lib.BAM_CLIP if clip else 0) | (_lib.BAM_EXTRACT if extract else 0) | (BAM_FROM_TAGS if from_tags else 0) | ej |
                              (_lib.BAM_COLLECT_NAMES if collect_names else 0) | (_lib.BAM_EJECT_NAMED if eject_named else 0) | (_lib.BAM_KEEP_SORTED if keep_sorted else 0) | rp | (_lib.BAM_INDEX if index else 0) |
-                             (_lib.BAM_COLLECT_MATES if collect_mates else 0) | (_lib.BAM_FIX_MATES if fix_mates else 0), arr, first_record, tail_trim)
+                             (_lib.BAM_COLLECT_MATES if collect_mates else 0) | (_lib.BAM_FIX_MATES if fix_mates else 0) | (_lib.BAM_STORE_EXTRACT if recstore else 0), arr, first_record, tail_trim)
         h = C.c_void_p()
         ctx._chk(self._L.fadehip_bam_open(ctx._h, C.byref(cfg), C.byref(h)))
         self._h = h
@@ -771,6 +779,13 @@ class BamStream:
                 self.close()
                 ctx._chk(rc)
             self._mates = mateset
+        self._recstore = None
+        if isinstance(recstore, RecStore):
+            rc = self._L.fadehip_bam_use_recstore(self._h, recstore._h)
+            if rc:
+                self.close()
+                ctx._chk(rc)
+            self._recstore = recstore  # (the store outlives the stream)
 
     def prepare(self, call_bytes):
         """fadehip_bam_prepare: the streams and buffers of calls of call_bytes inflated bytes, made ahead of the first call."""
@@ -895,6 +910,58 @@ class NameSet:
     def close(self):
         if self._h:
             self._L.fadehip_nameset_destroy(self._h)
+            self._h = None
+
+
+class RecStore:
+    """Context.recstore(): BAM records (bytes, block_size first) collected on the device in any order, sorted once by
+    coordinate — (refID as uint32, pos + 1 as uint32), ties in the order added — and drained in that order.  add_batch() and
+    streams opened with recstore=... append; sort() closes the store; drain() hands out the next run of records."""
+
+    def __init__(self, ctx):
+        self._ctx, self._L = ctx, ctx._L
+        h = C.c_void_p()
+        ctx._chk(self._L.fadehip_recstore_create(ctx._h, C.byref(h)))
+        self._h = h
+
+    def add_packed(self, recs, rec_off, pick=None):
+        recs = np.ascontiguousarray(recs, dtype=np.uint8)
+        rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
+        n = len(rec_off) - 1
+        if pick is not None:
+            pick = np.ascontiguousarray(pick, dtype=np.uint8)
+            if len(pick) != n:
+                raise ValueError("pick holds one entry per record")
+        self._ctx._chk(self._L.fadehip_recstore_add_batch(self._h, n, recs.ctypes.data, rec_off.ctypes.data, pick.ctypes.data if pick is not None else None))
+
+    def add_batch(self, records, pick=None):
+        """The records with pick[k] != 0 (pick None: every record) are appended, in the order they come."""
+        cat, off = NameSet._cat(records)
+        self.add_packed(cat, off, pick)
+
+    def count(self):
+        """(records, bytes) added so far."""
+        n, b = C.c_int64(0), C.c_int64(0)
+        self._ctx._chk(self._L.fadehip_recstore_count(self._h, C.byref(n), C.byref(b)))
+        return int(n.value), int(b.value)
+
+    def sort(self):
+        self._ctx._chk(self._L.fadehip_recstore_sort(self._h))
+
+    def drain(self, max_payload, raw=False, stored=False, index=False):
+        """The next maximal run of records, in final order, of at most max_payload bytes (at least one record): (bytes,
+        records) — the records back to back with raw, else BGZF members (stored: uncompressed ones) —, and with index a
+        third item, the run's .bai entries as index_call_dict gives them.  0 records: the store is drained."""
+        p, n, nr = C.c_void_p(), C.c_size_t(0), C.c_int64(0)
+        c = _lib.IndexCall()
+        flags = (_lib.RECSTORE_RAW if raw else 0) | (_lib.RECSTORE_STORED if stored else 0) | (_lib.RECSTORE_INDEX if index else 0)
+        self._ctx._chk(self._L.fadehip_recstore_drain(self._h, flags, int(max_payload), C.byref(p), C.byref(n), C.byref(nr), C.byref(c) if index else None))
+        out = C.string_at(p, n.value) if n.value else b""
+        return (out, int(nr.value), index_call_dict(c)) if index else (out, int(nr.value))
+
+    def close(self):
+        if self._h:
+            self._L.fadehip_recstore_destroy(self._h)
             self._h = None
 
 

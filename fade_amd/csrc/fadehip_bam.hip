@@ -10,7 +10,9 @@
 #include "bam_report.hpp"
 #include "bam_resort.hpp"
 #include "bam_index.hpp"
+#include "bam_recstore.hpp"
 #include "host/bai_build.hpp"
+#include "host/recstore_host.hpp"
 #include <algorithm>
 #include <chrono>
 #include <condition_variable>
@@ -46,6 +48,29 @@ struct fadehip_nameset {
 // The mate map of fadehip_mateset_* / fadehip_mates_fix_batch: the name set's host part as it is, over bam_mates.hpp's entries.
 struct fadehip_mateset {
     fadehip_nameset core;
+};
+
+// A store of records on the device (bam_recstore.hpp).  The host's part: the arena and the item arrays with what has been
+// handed out of them — exact numbers, since every call's byte range and item range are reserved here, in call order, before
+// anything of the call is launched — growth, the sort's arrays, and the drain's cursor and buffers.  As with the name set,
+// every launch that names the store's buffers is enqueued under `mu`, and growth begins with a wait for the whole device.
+struct fadehip_recstore {
+    fadehip_ctx *ctx = nullptr;
+    std::mutex mu;
+    DevBuf arena, key, off, size;
+    uint64_t first_bytes = 0;         // FADEHIP_RECSTORE_BYTES: the first arena
+    uint64_t used = 0, n_items = 0;   // arena bytes and items handed out
+    uint64_t item_cap = 0;
+    bool sorted = false;              // fadehip_recstore_sort has run: nothing is added any more
+    DevBuf sort_arr;                  // the sort's arrays (recstore_sort_layout) and its ctl
+    bam::ResortArgs ra;
+    std::vector<uint64_t> h_dst;      // [n_items + 1] the records' offsets in final order
+    uint64_t cursor = 0;              // records drained so far
+    DevBuf stage, at, app;            // a drain's bytes and offsets; add_batch's sizes, bases and counts
+    DevBuf ix_work, ix_ctl, ix_out;
+    bam::IndexCtl ixc;                // a drain's index ctl as it crosses (a member: the copy may outlive a call that fails)
+    PinBuf h_out;                     // what a drain hands out: the raw records or the members
+    std::vector<uint8_t> h_ix;        // the arrays *idx points into, until the next drain
 };
 
 namespace {
@@ -910,6 +935,8 @@ struct fadehip_bam_stream {
     bool fix_mates = false;      // FADEHIP_BAM_FIX_MATES: from_tags and clip, and every record's mate fields follow the placement `mates` holds for its mate
     fadehip_nameset *names = nullptr;  // fadehip_bam_use_nameset
     fadehip_mateset *mates = nullptr;  // fadehip_bam_use_mateset
+    bool store_extract = false;  // FADEHIP_BAM_STORE_EXTRACT: extract, and the calls' extract records stay on the device, in `recstore` (bam_recstore.hpp)
+    fadehip_recstore *recstore = nullptr;  // fadehip_bam_use_recstore
     DevBuf names_text, names_off;
     DevBuf names_first;         // from_tags: for every contig the first one of its name (fadehip_tags_batch's rule)
     struct Out {
@@ -949,6 +976,7 @@ struct fadehip_bam_stream {
         DevBuf u;                             // the call's inflated bytes, the previous call's cut-off record in front
         DevBuf seg, slots, rec_off, info, sent_of, art_of, out_size, blk32, blk64, counts;
         DevBuf ex_size, ex_blk;               // extract: bytes per record, block sums and bases (the tag arrays' counterparts)
+        DevBuf rx_cnt;                        // store_extract: the append kernels' item counts per block, and their bases
         DevBuf ej_head, ej_blk, ej_grp;       // eject: every record's group start, the blocks' last starts and carries, the groups' marks
         // from_tags: the stage's per-record arrays (rs byte, trims), per-side arrays (contig, position, ops, text), the ops'
         // block sums and bases, where a record's ops start, and the ops themselves (sized in back, when their total is known)
@@ -1353,6 +1381,95 @@ int bam_finish_resort(fadehip_bam_stream *st, fadehip_bam_stream::Set &S, uint64
     return 0;
 }
 
+// ---- the record store (bam_recstore.hpp): what a launch names of it, its growth, a call's items
+// The sort's item numbers are uint32 (bam_resort.hpp's idx arrays and its kernels' j); the launches here are sized in int32.
+constexpr uint64_t RECSTORE_MAX_ITEMS = ((uint64_t)1 << 31) - 1;
+constexpr uint64_t RECSTORE_DEFAULT_BYTES = (uint64_t)64 << 20;
+constexpr uint64_t RECSTORE_MAX_DRAIN = (uint64_t)1 << 30;  // bytes of one drain at most (the compressor takes 2^31 a call)
+
+bam::RecStoreRef recstore_ref(const fadehip_recstore *s) {
+    bam::RecStoreRef r;
+    r.arena = (uint8_t *)s->arena.p;
+    r.key = (uint64_t *)s->key.p;
+    r.off = (uint64_t *)s->off.p;
+    r.size = (uint32_t *)s->size.p;
+    return r;
+}
+
+int recstore_alloc(fadehip_ctx *ctx, DevBuf &b, size_t bytes) {
+    b.p = nullptr;
+    b.cap = 0;
+    const size_t want = (std::max<size_t>(bytes, 256) + 255) & ~(size_t)255;
+    if (hipMalloc(&b.p, want) != hipSuccess) {
+        (void)hipGetLastError();
+        b.p = nullptr;
+        return set_err(ctx, FADEHIP_E_NOMEM, "recstore: allocating %zu bytes on the device failed (the sorted extract holds every extract record on the device)", want);
+    }
+    b.cap = want;
+    return 0;
+}
+
+// a larger buffer with the first `keep` bytes of the old one (the caller holds s->mu and has waited for the device)
+int recstore_regrow(fadehip_ctx *ctx, hipStream_t q, DevBuf &b, size_t keep, size_t want) {
+    DevBuf nb;
+    if (const int rc = recstore_alloc(ctx, nb, want)) return rc;
+    if (keep && (hipMemcpyAsync(nb.p, b.p, keep, hipMemcpyDeviceToDevice, q) != hipSuccess || hipStreamSynchronize(q) != hipSuccess)) {
+        release(nb);
+        return set_err(ctx, FADEHIP_E_HIP, "recstore: moving the records to a larger buffer failed");
+    }
+    release(b);
+    b = nb;
+    return 0;
+}
+
+// Room for a call that adds bytes_new bytes and items_new items, made before anything of it is enqueued on q (the caller
+// holds s->mu).  Where there is none the device is waited for — the store's kernels may be on any of the ctx's streams — and
+// the arena, or the item arrays, move to buffers of twice the size (or what the call needs, if that is more).
+int recstore_room(fadehip_recstore *s, hipStream_t q, uint64_t bytes_new, uint64_t items_new) {
+    fadehip_ctx *ctx = s->ctx;
+    if (s->sorted) return set_err(ctx, FADEHIP_E_STATE, "recstore: the store has been sorted, nothing can be added to it any more");
+    if (s->n_items + items_new > RECSTORE_MAX_ITEMS)
+        return set_err(ctx, FADEHIP_E_UNSUPPORTED, "recstore: more than %llu records (the sort numbers its items in 32 bits)", (unsigned long long)RECSTORE_MAX_ITEMS);
+    const bool grow_arena = s->used + bytes_new + 8 > (uint64_t)s->arena.cap, grow_items = s->n_items + items_new > s->item_cap;
+    if (!grow_arena && !grow_items) return 0;
+    HIPCHK(ctx, hipDeviceSynchronize());
+    int rc;
+    if (grow_arena && (rc = recstore_regrow(ctx, q, s->arena, (size_t)s->used, (size_t)std::max<uint64_t>(2 * (uint64_t)s->arena.cap, s->used + bytes_new + 8)))) return rc;
+    if (grow_items) {
+        const uint64_t cap = std::max<uint64_t>(std::max<uint64_t>(2 * s->item_cap, s->n_items + items_new), 1024);
+        if ((rc = recstore_regrow(ctx, q, s->key, 8 * (size_t)s->n_items, 8 * (size_t)cap)) || (rc = recstore_regrow(ctx, q, s->off, 8 * (size_t)s->n_items, 8 * (size_t)cap)) ||
+            (rc = recstore_regrow(ctx, q, s->size, 4 * (size_t)s->n_items, 4 * (size_t)cap)))
+            return rc;  // (an array that has grown already stays grown: it holds what it held)
+        s->item_cap = cap;
+    }
+    return 0;
+}
+
+// The items of a call's n_slots slots, behind the kernel that wrote their records at arena + base (bam_recstore.hpp); cnt:
+// 2 x blocks u32 of the caller's.  Enqueued under s->mu.
+int enqueue_recstore_append(fadehip_recstore *s, hipStream_t q, uint64_t base, uint64_t item0, uint32_t n_slots, uint32_t n_items, const uint32_t *x_size,
+                            const uint64_t *blk_base, uint32_t *cnt) {
+    fadehip_ctx *ctx = s->ctx;
+    const uint32_t ntb = (n_slots + bam::TAG_BLOCK - 1u) / bam::TAG_BLOCK;
+    bam::RecAppendArgs a;
+    a.s = recstore_ref(s);
+    a.base = base;
+    a.item0 = item0;
+    a.n = n_slots;
+    a.n_items = n_items;
+    a.x_size = x_size;
+    a.blk_base = blk_base;
+    a.cnt_sums = cnt;
+    a.cnt_base = cnt + ntb;
+    hipLaunchKernelGGL(bam::recstore_count_kernel, dim3(ntb), dim3(bam::TAG_BLOCK), 0, q, a);
+    HIPCHK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(bam::recstore_count_scan_kernel, dim3(1), dim3(1024), 0, q, a, ntb);
+    HIPCHK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(bam::recstore_append_kernel, dim3(ntb), dim3(bam::TAG_BLOCK), 0, q, a);
+    HIPCHK(ctx, hipGetLastError());
+    return 0;
+}
+
 // FADEHIP_BAM_EXTRACT, C of call k behind the event the compressor waits for: the extract records of the call's artifact
 // calls, from the untouched input records, and their copy into the pinned buffer back_extract hands out (the total came
 // with the tag sizes)
@@ -1366,7 +1483,38 @@ int bam_finish_extract(fadehip_bam_stream *st, fadehip_bam_stream::Set &S, uint6
         const bam::ChunkCounts *xc = (const bam::ChunkCounts *)S.h_counts.p + 1;
         const uint64_t xb = xc->out_bytes;
         if (xb > ((uint64_t)1 << 31)) return set_err(ctx, FADEHIP_E_UNSUPPORTED, "bam stream: %llu extract bytes in one call (at most 2^31)", (unsigned long long)xb);
-        if (xb) {
+        if (xb && st->store_extract) {
+            // FADEHIP_BAM_STORE_EXTRACT: the call's bytes and items are reserved here, in call order (bam_finish_call) and with
+            // numbers that have crossed to the host; the write kernels then put the records at the arena's reserved place, and
+            // the append kernels behind them make the items.  All under the store's lock: the arena must not move before
+            // these launches have run.
+            fadehip_recstore *rs = st->recstore;
+            const uint32_t n_x = xc->n_records;
+            std::lock_guard<std::mutex> sl(rs->mu);
+            if ((rc = recstore_room(rs, q, xb, n_x)) || (rc = reserve_roomy(ctx, S.rx_cnt, 8 * (size_t)S.ntb + 8))) return rc;
+            uint8_t *at = (uint8_t *)rs->arena.p + rs->used;
+            const uint64_t *blk_base;
+            if (st->from_tags) {
+                const uint64_t n_ops = ((const bam::StageCounts *)(S.h_counts.p + st->stage_counts_at()))->ops.out_bytes;
+                if (n_ops > ((uint64_t)1 << 29)) return set_err(ctx, FADEHIP_E_UNSUPPORTED, "bam stream: %llu CIGAR ops in one call's am tags (at most 2^29)", (unsigned long long)n_ops);
+                if ((rc = reserve_roomy(ctx, S.ft_ops, 4 * (size_t)n_ops + 8))) return rc;
+                S.fa.ops = (uint32_t *)S.ft_ops.p;
+                S.fa.xo = at;
+                blk_base = S.fa.x_blk_base;
+                hipLaunchKernelGGL(bam::bam_tags_ops_kernel, dim3(S.ntb), dim3(bam::TAG_BLOCK), 0, q, S.fa);
+                HIPCHK(ctx, hipGetLastError());
+                hipLaunchKernelGGL(bam::bam_tags_extract_write_kernel, dim3(S.ntb), dim3(bam::TAG_BLOCK), 0, q, S.fa);
+            } else {
+                S.xa.o = at;
+                blk_base = S.xa.blk_base;
+                hipLaunchKernelGGL(bam::bam_extract_write_kernel, dim3(S.ntb), dim3(bam::TAG_BLOCK), 0, q, S.xa);
+            }
+            HIPCHK(ctx, hipGetLastError());
+            if ((rc = enqueue_recstore_append(rs, q, rs->used, rs->n_items, S.n_rec, n_x, (const uint32_t *)S.ex_size.p, blk_base, (uint32_t *)S.rx_cnt.p))) return rc;
+            rs->used += xb;
+            rs->n_items += n_x;
+            out->xrecs = (int64_t)n_x;
+        } else if (xb) {
             PinBuf &xh = st->xbuf[k % (FADEHIP_BAM_CHUNKS + 1)];
             if ((rc = reserve_roomy(ctx, out->x, (size_t)xb + 256)) || (rc = reserve_pinned(ctx, xh, (size_t)xb + (size_t)xb / 4 + 256))) return rc;
             if (st->from_tags) {
@@ -1532,7 +1680,7 @@ int bam_finish_one(fadehip_bam_stream *st, uint64_t k) {
 // their order (they are anyway: back takes them in order, and front finishes k - 2 before k - 1 exists; this says so).
 int bam_finish_call(fadehip_bam_stream *st, uint64_t k) {
     int rc;
-    if (st->keep_sorted && k && (rc = bam_finish_one(st, k - 1))) return rc;
+    if ((st->keep_sorted || st->store_extract) && k && (rc = bam_finish_one(st, k - 1))) return rc;  // (store_extract: a call's place in the store is handed out when it is finished)
     return bam_finish_one(st, k);
 }
 
@@ -2047,6 +2195,8 @@ int bam_front_impl(fadehip_bam_stream *st, const uint8_t *members, size_t n_byte
     if ((st->collect_names || st->eject_named || st->collect_mates) && !st->names)
         return set_err(ctx, FADEHIP_E_STATE, "bam stream: opened with FADEHIP_BAM_%s and no name set attached (fadehip_bam_use_nameset)",
                        st->collect_names ? "COLLECT_NAMES" : st->eject_named ? "EJECT_NAMED" : "COLLECT_MATES");
+    if (st->store_extract && !st->recstore)
+        return set_err(ctx, FADEHIP_E_STATE, "bam stream: opened with FADEHIP_BAM_STORE_EXTRACT and no record store attached (fadehip_bam_use_recstore)");
     if ((st->collect_mates || st->fix_mates) && !st->mates)
         return set_err(ctx, FADEHIP_E_STATE, "bam stream: opened with FADEHIP_BAM_%s and no mate set attached (fadehip_bam_use_mateset)", st->collect_mates ? "COLLECT_MATES" : "FIX_MATES");
     if (k >= 2 && (rc = bam_finish_call(st, k - 2))) return rc;
@@ -2101,8 +2251,10 @@ int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_ba
     if (!cfg || !out || cfg->n_ref < 0 || (cfg->n_ref && !cfg->ref_names) || (cfg->window < 0 && !(cfg->flags & FADEHIP_BAM_FROM_TAGS)) ||
         (cfg->flags & ~(FADEHIP_BAM_STORED | FADEHIP_BAM_NO_OUTPUT | FADEHIP_BAM_CLIP | FADEHIP_BAM_EXTRACT | FADEHIP_BAM_EJECT | FADEHIP_BAM_EJECT_GROUPS | FADEHIP_BAM_FROM_TAGS |
                         FADEHIP_BAM_COLLECT_NAMES | FADEHIP_BAM_EJECT_NAMED | FADEHIP_BAM_KEEP_SORTED | FADEHIP_BAM_REPORT_STATS | FADEHIP_BAM_REPORT_CLIP | FADEHIP_BAM_INDEX |
-                        FADEHIP_BAM_COLLECT_MATES | FADEHIP_BAM_FIX_MATES)))
+                        FADEHIP_BAM_COLLECT_MATES | FADEHIP_BAM_FIX_MATES | FADEHIP_BAM_STORE_EXTRACT)))
         return set_err(ctx, FADEHIP_E_INVALID, "bam stream: bad configuration");
+    if ((cfg->flags & FADEHIP_BAM_STORE_EXTRACT) && !(cfg->flags & FADEHIP_BAM_EXTRACT))
+        return set_err(ctx, FADEHIP_E_INVALID, "bam stream: FADEHIP_BAM_STORE_EXTRACT needs FADEHIP_BAM_EXTRACT (it says where the extract records go)");
     // the index describes records that are written: a stream that writes none has nothing to index.  It stands beside every
     // flag that writes output, and the checks below look at the flags without it
     const int32_t all_flags = cfg->flags;
@@ -2111,8 +2263,9 @@ int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_ba
                          : (all_flags & FADEHIP_BAM_REPORT_CLIP) ? "FADEHIP_BAM_REPORT_CLIP" : (all_flags & FADEHIP_BAM_COLLECT_NAMES) ? "FADEHIP_BAM_COLLECT_NAMES" : nullptr;
         if (no) return set_err(ctx, FADEHIP_E_INVALID, "bam stream: FADEHIP_BAM_INDEX does not combine with %s (the index is of the records a stream writes)", no);
     }
+    // (STORE_EXTRACT only says where EXTRACT's records go: it stands wherever EXTRACT does)
     fadehip_bam_config cfg_plain = *cfg;
-    cfg_plain.flags &= ~FADEHIP_BAM_INDEX;
+    cfg_plain.flags &= ~(FADEHIP_BAM_INDEX | FADEHIP_BAM_STORE_EXTRACT);
     cfg = &cfg_plain;
     if (cfg->flags & (FADEHIP_BAM_REPORT_STATS | FADEHIP_BAM_REPORT_CLIP)) {
         const int32_t need = FADEHIP_BAM_FROM_TAGS | FADEHIP_BAM_NO_OUTPUT;
@@ -2166,6 +2319,7 @@ int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_ba
     st->fix_mates = (cfg->flags & FADEHIP_BAM_FIX_MATES) != 0;
     st->report = ((cfg->flags & FADEHIP_BAM_REPORT_STATS) ? bam::RP_STATS : 0u) | ((cfg->flags & FADEHIP_BAM_REPORT_CLIP) ? bam::RP_CLIP : 0u);
     st->index = (all_flags & FADEHIP_BAM_INDEX) != 0;
+    st->store_extract = (all_flags & FADEHIP_BAM_STORE_EXTRACT) != 0;
     std::string text;
     std::vector<uint32_t> off((size_t)cfg->n_ref + 1, 0);
     for (int k = 0; k < cfg->n_ref; k++) {
@@ -2218,6 +2372,17 @@ int fadehip_bam_use_mateset(fadehip_bam_stream *st, fadehip_mateset *m) {
     if (!st->collect_mates && !st->fix_mates) return set_err(ctx, FADEHIP_E_INVALID, "bam stream: opened without FADEHIP_BAM_COLLECT_MATES or FADEHIP_BAM_FIX_MATES");
     if (st->k_front) return set_err(ctx, FADEHIP_E_STATE, "bam stream: use_mateset comes before the first front call");
     st->mates = m;
+    return 0;
+}
+
+int fadehip_bam_use_recstore(fadehip_bam_stream *st, fadehip_recstore *s) {
+    if (!st) return set_err(nullptr, FADEHIP_E_INVALID, "stream is NULL");
+    fadehip_ctx *ctx = st->ctx;
+    if (!s) return set_err(ctx, FADEHIP_E_INVALID, "recstore is NULL");
+    if (s->ctx != ctx) return set_err(ctx, FADEHIP_E_INVALID, "bam stream: the record store belongs to another ctx");
+    if (!st->store_extract) return set_err(ctx, FADEHIP_E_INVALID, "bam stream: opened without FADEHIP_BAM_STORE_EXTRACT");
+    if (st->k_front) return set_err(ctx, FADEHIP_E_STATE, "bam stream: use_recstore comes before the first front call");
+    st->recstore = s;
     return 0;
 }
 
@@ -2629,6 +2794,268 @@ int fadehip_bai_finish(fadehip_bai *b, const uint8_t **bytes, size_t *n) {
 const char *fadehip_bai_error(const fadehip_bai *b) { return b ? b->b.err.c_str() : g_bai_null_err.c_str(); }
 void fadehip_bai_destroy(fadehip_bai *b) { delete b; }
 
+// ---- the record store over records the caller brings, its sort and its drains (bam_recstore.hpp)
+int fadehip_recstore_create(fadehip_ctx *ctx, fadehip_recstore **out) {
+    if (!ctx) return set_err(nullptr, FADEHIP_E_INVALID, "ctx is NULL");
+    if (!out) return set_err(ctx, FADEHIP_E_INVALID, "NULL argument");
+    *out = nullptr;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    fadehip_recstore *s = new (std::nothrow) fadehip_recstore;
+    if (!s) return set_err(ctx, FADEHIP_E_NOMEM, "out of memory");
+    s->ctx = ctx;
+    s->first_bytes = RECSTORE_DEFAULT_BYTES;
+    if (const char *e = getenv("FADEHIP_RECSTORE_BYTES")) s->first_bytes = (uint64_t)std::max<long long>(256, std::min<long long>(atoll(e), 1ll << 40));
+    memset(&s->ra, 0, sizeof s->ra);
+    if (const int rc = recstore_alloc(ctx, s->arena, (size_t)s->first_bytes)) {
+        fadehip_recstore_destroy(s);
+        return rc;
+    }
+    *out = s;
+    return 0;
+}
+
+void fadehip_recstore_destroy(fadehip_recstore *s) {
+    if (!s) return;
+    (void)hipSetDevice(s->ctx->device);
+    (void)hipDeviceSynchronize();
+    for (DevBuf *b : {&s->arena, &s->key, &s->off, &s->size, &s->sort_arr, &s->stage, &s->at, &s->app, &s->ix_work, &s->ix_ctl, &s->ix_out}) release(*b);
+    release(s->h_out);
+    delete s;
+}
+
+int fadehip_recstore_add_batch(fadehip_recstore *s, int32_t n, const uint8_t *recs, const int64_t *rec_off, const uint8_t *pick) {
+    if (!s) return set_err(nullptr, FADEHIP_E_INVALID, "recstore is NULL");
+    fadehip_ctx *ctx = s->ctx;
+    if (n < 0 || !rec_off || (n > 0 && !recs)) return set_err(ctx, FADEHIP_E_INVALID, "NULL argument");
+    if (rec_off[0] < 0) return set_err(ctx, FADEHIP_E_INVALID, "offsets must be non-negative and non-decreasing (record 0)");
+    int rc;
+    if ((rc = check_records(ctx, n, recs, rec_off, true, [](int32_t) { return 0; }))) return rc;
+    // the picked records as slots of one record each: their sizes, the blocks' bases, and the runs of neighbours to copy
+    const size_t ntb = ((size_t)n + bam::TAG_BLOCK - 1) / bam::TAG_BLOCK;
+    std::vector<uint32_t> x_size((size_t)n);
+    std::vector<uint64_t> blk_base(ntb + 1);
+    uint64_t bytes = 0, n_pick = 0;
+    for (int32_t k = 0; k < n; k++) {
+        if (k % bam::TAG_BLOCK == 0) blk_base[(size_t)k / bam::TAG_BLOCK] = bytes;
+        const bool in = !pick || pick[k];
+        x_size[(size_t)k] = in ? (uint32_t)(rec_off[k + 1] - rec_off[k]) : 0u;
+        bytes += x_size[(size_t)k];
+        n_pick += in;
+    }
+    BatchLane &L = ctx->batch;
+    std::lock_guard<std::mutex> lk(L.mu);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (!L.stream) HIPCHK(ctx, hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
+    std::lock_guard<std::mutex> sl(s->mu);
+    if (s->sorted) return set_err(ctx, FADEHIP_E_STATE, "recstore: the store has been sorted, nothing can be added to it any more");
+    if (!n_pick) return 0;
+    // app: x_size [n] u32 | blk_base [blocks] u64 | counts [2 blocks] u32
+    const size_t a_base = (4 * (size_t)n + 7) & ~(size_t)7, a_cnt = a_base + 8 * ntb;
+    if ((rc = recstore_room(s, L.stream, bytes, n_pick)) || (rc = reserve_roomy(ctx, s->app, a_cnt + 8 * ntb + 8))) return rc;
+    uint8_t *at = (uint8_t *)s->arena.p + s->used;
+    for (int32_t k = 0; k < n;) {
+        if (!x_size[(size_t)k]) { k++; continue; }
+        int32_t e = k;
+        while (e < n && x_size[(size_t)e]) e++;
+        const size_t run = (size_t)(rec_off[e] - rec_off[k]);
+        HIPCHK(ctx, hipMemcpyAsync(at, recs + rec_off[k], run, hipMemcpyHostToDevice, L.stream));
+        at += run;
+        k = e;
+    }
+    HIPCHK(ctx, hipMemcpyAsync(s->app.p, x_size.data(), 4 * (size_t)n, hipMemcpyHostToDevice, L.stream));
+    HIPCHK(ctx, hipMemcpyAsync((uint8_t *)s->app.p + a_base, blk_base.data(), 8 * ntb, hipMemcpyHostToDevice, L.stream));
+    rc = enqueue_recstore_append(s, L.stream, s->used, s->n_items, (uint32_t)n, (uint32_t)n_pick, (const uint32_t *)s->app.p, (const uint64_t *)((uint8_t *)s->app.p + a_base),
+                                 (uint32_t *)((uint8_t *)s->app.p + a_cnt));
+    const hipError_t e = hipStreamSynchronize(L.stream);  // (the vectors go out of scope)
+    if (rc) return rc;
+    HIPCHK(ctx, e);
+    s->used += bytes;
+    s->n_items += n_pick;
+    return 0;
+}
+
+int fadehip_recstore_count(fadehip_recstore *s, int64_t *n_records, int64_t *n_bytes) {
+    if (!s) return set_err(nullptr, FADEHIP_E_INVALID, "recstore is NULL");
+    if (!n_records || !n_bytes) return set_err(s->ctx, FADEHIP_E_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> sl(s->mu);
+    *n_records = (int64_t)s->n_items;
+    *n_bytes = (int64_t)s->used;
+    return 0;
+}
+
+// the sort's arrays for n items, one behind the other from `base` (nullptr: only their size is wanted); key0, isrc and isize
+// are the store's own item arrays
+static size_t recstore_sort_layout(bam::ResortArgs &a, uint8_t *base, size_t n) {
+    const size_t m = std::max<size_t>(n, 1), tiles = (m + bam::RS_TILE - 1) / bam::RS_TILE, ntb = (m + bam::TAG_BLOCK - 1) / bam::TAG_BLOCK;
+    size_t at = 0;
+    const auto take = [&](size_t bytes) {
+        uint8_t *p = base + at;
+        at += (bytes + 7) & ~(size_t)7;
+        return p;
+    };
+    a.ctl = (bam::ResortCtl *)take(256);
+    a.key1 = (uint64_t *)take(8 * m);
+    a.msrc = (uint64_t *)take(8 * m);
+    a.dst = (uint64_t *)take(8 * (m + 1));
+    a.sblk = (uint64_t *)take(16 * ntb);
+    a.idx0 = (uint32_t *)take(4 * m);
+    a.idx1 = (uint32_t *)take(4 * m);
+    a.msize = (uint32_t *)take(4 * m);
+    a.hist = (uint32_t *)take(4 * 256 * tiles);
+    a.hist_base = (uint32_t *)take(4 * 256 * tiles);
+    return at;
+}
+
+int fadehip_recstore_sort(fadehip_recstore *s) {
+    if (!s) return set_err(nullptr, FADEHIP_E_INVALID, "recstore is NULL");
+    fadehip_ctx *ctx = s->ctx;
+    BatchLane &L = ctx->batch;
+    std::lock_guard<std::mutex> lk(L.mu);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (!L.stream) HIPCHK(ctx, hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
+    std::lock_guard<std::mutex> sl(s->mu);
+    if (s->sorted) return set_err(ctx, FADEHIP_E_STATE, "recstore: the store has been sorted already");
+    HIPCHK(ctx, hipDeviceSynchronize());  // the streams' appends may be on any of the ctx's streams
+    const size_t n = (size_t)s->n_items;
+    std::vector<uint64_t> dst(n + 1, 0);
+    if (n) {
+        bam::ResortArgs &a = s->ra;
+        memset(&a, 0, sizeof a);
+        int rc;
+        if ((rc = recstore_alloc(ctx, s->sort_arr, recstore_sort_layout(a, nullptr, n)))) return rc;
+        recstore_sort_layout(a, (uint8_t *)s->sort_arr.p, n);
+        a.key0 = (uint64_t *)s->key.p;
+        a.isrc = (uint64_t *)s->off.p;
+        a.isize = (uint32_t *)s->size.p;
+        const unsigned nb = (unsigned)((n + 255) / 256);
+        hipLaunchKernelGGL(bam::recstore_sort_begin_kernel, dim3(nb), dim3(256), 0, L.stream, a, (uint32_t)n);
+        HIPCHK(ctx, hipGetLastError());
+        if ((rc = enqueue_resort_sort(ctx, L.stream, a, n))) return rc;
+        // (bam_resort.hpp's kernels behind the eighth pass: W is all ones, so the cut lets every record leave)
+        hipLaunchKernelGGL(bam::bam_resort_cut_kernel, dim3(nb), dim3(bam::TAG_BLOCK), 0, L.stream, a);
+        HIPCHK(ctx, hipGetLastError());
+        hipLaunchKernelGGL(bam::bam_resort_offsets_scan_kernel, dim3(1), dim3(1024), 0, L.stream, a, nb);
+        HIPCHK(ctx, hipGetLastError());
+        hipLaunchKernelGGL(bam::bam_resort_offsets_kernel, dim3(nb), dim3(bam::TAG_BLOCK), 0, L.stream, a, nb);
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipMemcpyAsync(dst.data(), a.dst, 8 * (n + 1), hipMemcpyDeviceToHost, L.stream));
+        HIPCHK(ctx, hipStreamSynchronize(L.stream));
+        if (dst[n] != s->used) return set_err(ctx, FADEHIP_E_STATE, "internal: recstore: the sorted records take %llu bytes, the arena holds %llu", (unsigned long long)dst[n], (unsigned long long)s->used);
+    }
+    s->h_dst.swap(dst);
+    s->cursor = 0;
+    s->sorted = true;
+    return 0;
+}
+
+int fadehip_recstore_drain(fadehip_recstore *s, int32_t flags, uint64_t max_payload, const uint8_t **out, size_t *out_bytes, int64_t *n_records, fadehip_index_call *idx) {
+    if (!s) return set_err(nullptr, FADEHIP_E_INVALID, "recstore is NULL");
+    fadehip_ctx *ctx = s->ctx;
+    const bool raw = (flags & FADEHIP_RECSTORE_RAW) != 0, stored = (flags & FADEHIP_RECSTORE_STORED) != 0, index = (flags & FADEHIP_RECSTORE_INDEX) != 0;
+    if (!out || !out_bytes || !n_records || (index && !idx)) return set_err(ctx, FADEHIP_E_INVALID, "NULL argument");
+    *out = nullptr;
+    *out_bytes = 0;
+    *n_records = 0;
+    if (idx) memset(idx, 0, sizeof *idx);
+    if (flags & ~(FADEHIP_RECSTORE_RAW | FADEHIP_RECSTORE_STORED | FADEHIP_RECSTORE_INDEX)) return set_err(ctx, FADEHIP_E_INVALID, "recstore: unknown drain flags");
+    if (raw && (stored || index))
+        return set_err(ctx, FADEHIP_E_INVALID, "recstore: FADEHIP_RECSTORE_RAW does not combine with %s (raw records have no members to store or to index)", index ? "FADEHIP_RECSTORE_INDEX" : "FADEHIP_RECSTORE_STORED");
+    std::lock_guard<std::mutex> sl(s->mu);
+    if (!s->sorted) return set_err(ctx, FADEHIP_E_STATE, "recstore: drain comes after fadehip_recstore_sort");
+    const size_t n_all = (size_t)s->n_items, j0 = (size_t)s->cursor;
+    if (j0 >= n_all) return 0;
+    const size_t j1 = recstore::drain_cut(s->h_dst.data(), n_all, j0, std::min<uint64_t>(max_payload, RECSTORE_MAX_DRAIN));
+    const size_t n = j1 - j0, bytes = (size_t)(s->h_dst[j1] - s->h_dst[j0]);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc;
+    const int lane = 0;
+    if ((rc = bgzf_lane_ready(ctx, lane))) return rc;  // (RAW too: the lane's stream is the drain's)
+    hipStream_t q = ctx->bgzf[lane].stream;
+    if ((rc = reserve_roomy(ctx, s->stage, bytes + 256)) || (rc = reserve_roomy(ctx, s->at, 8 * (n + 1)))) return rc;
+    bam::RecGatherArgs g;
+    g.arena = (const uint8_t *)s->arena.p;
+    g.msrc = s->ra.msrc;
+    g.dst = s->ra.dst;
+    g.msize = s->ra.msize;
+    g.j0 = (uint32_t)j0;
+    g.n = (uint32_t)n;
+    g.out = (uint8_t *)s->stage.p;
+    g.at = (uint64_t *)s->at.p;
+    hipLaunchKernelGGL(bam::recstore_gather_kernel, dim3((unsigned)((n + 15) / 16)), dim3(256), 0, q, g);
+    HIPCHK(ctx, hipGetLastError());
+    if (raw) {
+        if ((rc = reserve_pinned(ctx, s->h_out, bytes + 8))) return rc;
+        HIPCHK(ctx, hipMemcpyAsync(s->h_out.p, s->stage.p, bytes, hipMemcpyDeviceToHost, q));
+        HIPCHK(ctx, hipStreamSynchronize(q));
+        *out = s->h_out.p;
+        *out_bytes = bytes;
+    } else {
+        BgzfLane &l = ctx->bgzf[lane];
+        if (stored) rc = bgzf_store_enqueue(ctx, lane, (const uint8_t *)s->stage.p, bytes, s->h_out);
+        else rc = bgzf_enqueue(ctx, lane, (const uint8_t *)s->stage.p, bytes, bgzf_pick_geom(ctx), &s->h_out);
+        if (rc) return rc;
+        // the index stage behind the compressor's scan on the lane's stream, as the file path's (bam_enqueue_index); its
+        // counts first, then arrays of exactly their size (fadehip_index_batch's two steps)
+        bam::IndexArgs a;
+        memset(&a, 0, sizeof a);
+        bam::IndexCtl &c = s->ixc;
+        memset(&c, 0, sizeof c);
+        if (index) {
+            if ((rc = reserve_roomy(ctx, s->ix_work, index_layout(a, nullptr, n))) || (rc = reserve(ctx, s->ix_ctl, 256))) return rc;
+            index_layout(a, (uint8_t *)s->ix_work.p, n);
+            a.ctl = (bam::IndexCtl *)s->ix_ctl.p;
+            a.u = (const uint8_t *)s->stage.p;
+            a.at = (const uint64_t *)s->at.p;
+            a.n = (uint32_t)n;
+            const BgzfGeometry geo = bgzf_lane_geometry(ctx, lane, stored);
+            a.block = geo.block;
+            a.member_off = geo.member_off;
+            a.behind_ptr = geo.behind_ptr;
+            a.member_stride = geo.member_stride;
+            a.behind = geo.behind;
+            if ((rc = enqueue_index_counts(ctx, q, a))) return rc;
+            HIPCHK(ctx, hipMemcpyAsync(&c, a.ctl, sizeof c, hipMemcpyDeviceToHost, q));
+        }
+        if (stored) {
+            HIPCHK(ctx, hipEventSynchronize(l.done));
+            l.state = 0;
+            *out = l.h_out;
+            *out_bytes = (size_t)*l.h_total;
+        } else if ((rc = fadehip_bgzf_deflate_wait(ctx, lane, out, out_bytes))) return rc;
+        if (index) {
+            const auto fail = [&](int code) {
+                *out = nullptr;  // (nothing of a drain that fails is handed out, and the cursor stays)
+                *out_bytes = 0;
+                return code;
+            };
+            if (hipStreamSynchronize(q) != hipSuccess) return fail(set_err(ctx, FADEHIP_E_HIP, "recstore: the index stage failed"));
+            if ((rc = index_bad(ctx, c, (long long)j0, "recstore drain"))) return fail(rc);
+            if (c.n_linear >> 31) return fail(set_err(ctx, FADEHIP_E_UNSUPPORTED, "recstore drain: %llu linear index entries (at most 2^31)", (unsigned long long)c.n_linear));
+            const size_t ix_bytes = index_out_layout(a, nullptr, n, (size_t)c.n_linear);
+            if ((rc = reserve_roomy(ctx, s->ix_out, ix_bytes + 8))) return fail(rc);
+            index_out_layout(a, (uint8_t *)s->ix_out.p, n, (size_t)c.n_linear);
+            if ((rc = enqueue_index_write(ctx, q, a))) return fail(rc);
+            s->h_ix.resize(ix_bytes + 8);
+            if (hipMemcpyAsync(s->h_ix.data(), s->ix_out.p, ix_bytes, hipMemcpyDeviceToHost, q) != hipSuccess || hipStreamSynchronize(q) != hipSuccess)
+                return fail(set_err(ctx, FADEHIP_E_HIP, "recstore: copying the index entries failed"));
+            bam::IndexArgs h;
+            index_out_layout(h, s->h_ix.data(), n, (size_t)c.n_linear);
+            idx->chunks = h.chunks;
+            idx->linear = h.linear;
+            idx->refs = h.refs;
+            idx->n_chunks = (int64_t)c.n_chunks;
+            idx->n_linear = (int64_t)c.n_linear;
+            idx->n_refs = (int64_t)c.n_refs;
+            idx->n_records = (int64_t)c.n;
+            idx->first_key = c.first_key;
+            idx->last_key = c.last_key;
+        }
+    }
+    *n_records = (int64_t)n;
+    s->cursor = j1;
+    return 0;
+}
+
 int fadehip_bam_ejected(fadehip_bam_stream *st, int64_t *n_ejected) {
     if (!st) return set_err(nullptr, FADEHIP_E_INVALID, "stream is NULL");
     if (!n_ejected) return set_err(st->ctx, FADEHIP_E_INVALID, "NULL argument");
@@ -2663,7 +3090,7 @@ void fadehip_bam_close(fadehip_bam_stream *st) {
     release(st->names_first);
     for (auto &S : st->set) {
         for (DevBuf *b : {&S.comp, &S.blocks, &S.status, &S.ticket, &S.u, &S.seg, &S.slots, &S.rec_off, &S.info, &S.sent_of, &S.art_of, &S.out_size, &S.blk32,
-                          &S.blk64, &S.counts, &S.ex_size, &S.ex_blk, &S.ej_head, &S.ej_blk, &S.ej_grp, &S.ft_rec, &S.ft_side, &S.ft_ops_blk, &S.ft_ops_at, &S.ft_ops})
+                          &S.blk64, &S.counts, &S.ex_size, &S.ex_blk, &S.rx_cnt, &S.ej_head, &S.ej_blk, &S.ej_grp, &S.ft_rec, &S.ft_side, &S.ft_ops_blk, &S.ft_ops_at, &S.ft_ops})
             release(*b);
         release(S.h_blocks);
         release(S.h_counts);

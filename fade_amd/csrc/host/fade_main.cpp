@@ -13,6 +13,7 @@
 // There is no CPU alignment path in this program.
 #include <memory>
 #include "hts_lite.hpp"
+#include "recstore_host.hpp"
 #include "../../../include/fadehip.h"
 
 #include <atomic>
@@ -67,6 +68,7 @@ static void print_anno_help() {
             "-u        --ubam output uncompressed bam\n"
             "-c        --clip hard-clip the artifacts in the same pass (what `fade out -c` makes of the annotated file)\n"
             "        --extract PATH: also write what `fade extract` makes of the annotated file (one mapped record per artifact side), in the same pass\n"
+            " --extract-sorted with --extract PATH, BAM file in, -b or -u out, one MI355X: PATH is written in coordinate order (@HD SO:coordinate), and its index PATH.bai beside it\n"
             "          --eject drop the artifact reads in the same pass, and on name-sorted input every read that shares their name (what `fade out` makes of the annotated file)\n"
             "    --keep-sorted with -c, coordinate-sorted BAM file in, -b or -u out, one MI355X: clipped records are written at their new coordinates, so the output stays coordinate-sorted\n"
             "    --write-index PATH: also write the BAM index (.bai) of the output, made in the same pass (coordinate-sorted output, BAM file in, -b or -u out, one MI355X)\n"
@@ -92,7 +94,9 @@ struct Opts {
     std::string stats_tsv, clip_tsv;  // --stats-tsv PATH, --clip-tsv PATH: the stats.d / noclip.d reports of this run
     std::string write_index;  // --write-index PATH: the .bai of the BAM on stdout, made on the device in the same pass
     std::string extract;  // --extract PATH: `fade extract`'s records of this run's artifact calls, in the output's format
-    std::string seen;  // one letter per option met: t m w b u c h g(pus) B(atch) s(tats) T(iming) S(hards) X (--extract) E (--eject) F (--fragments) K (--keep-sorted)
+    bool sorted = false;  // `fade extract --sorted`: the records leave in coordinate order (a store of records on the device, sorted once at the end)
+    bool extract_sorted = false;  // `fade annotate --extract PATH --extract-sorted`: PATH is written in coordinate order, PATH.bai beside it
+    std::string seen;  // one letter per option met: t m w b u c h g(pus) B(atch) s(tats) T(iming) S(hards) X (--extract) E (--eject) F (--fragments) K (--keep-sorted) O (--sorted) Y (--extract-sorted)
 };
 
 // std.getopt with config.bundling: short flags bundle (-bu), values attach (-w100, -w 100, --window-size=100)
@@ -185,6 +189,11 @@ static bool parse_opts(int argc, char **argv, Opts &o, std::string &err) {
                 if (has_val && val != "true" && val != "false") { err = "Invalid value for option --keep-sorted: " + val; return false; }
                 o.keep_sorted = !has_val || val == "true";
             }
+            else if (name == "sorted" || name == "extract-sorted") {  // (flags, as --eject)
+                o.seen += name == "sorted" ? 'O' : 'Y';
+                if (has_val && val != "true" && val != "false") { err = "Invalid value for option --" + name + ": " + val; return false; }
+                (name == "sorted" ? o.sorted : o.extract_sorted) = !has_val || val == "true";
+            }
             else if (name == "help") o.help = true;
             else { err = "Unrecognized option --" + name; return false; }
         } else if (a.size() > 1 && a[0] == '-' && a != "-") {
@@ -274,6 +283,60 @@ struct IndexSink {
         if (fclose(f) != 0 || !ok) throw std::runtime_error("write error on " + path);
     }
 };
+
+// `fade extract --sorted`, `fade annotate --extract-sorted`: the run's extract records are in a record store on the device
+// (fadehip_recstore_*).  Written here to `out`: the header's members — @HD with SO:coordinate, otherwise the header the
+// unsorted file gets —, then the store's drains in coordinate order, members straight from the device compressor, then the
+// end-of-file marker; with bai_path the .bai of it, from the header's size and every drain's entries, as IndexSink makes one.
+// `out` may be a pipe.  Returns the records written.
+static int64_t write_sorted_store(fadehip_ctx *ctx, fadehip_recstore *rs, FILE *out, bool stored, Header hdr, Pool *pool, const std::string &bai_path) {
+    hdr.text = fadehip::recstore::header_sorted(hdr.text);
+    char *mp = nullptr;
+    size_t mn = 0;
+    FILE *mf = open_memstream(&mp, &mn);
+    if (!mf) throw std::runtime_error("out of memory");
+    try {
+        Writer hw(mf, stored ? OutFmt::UBAM : OutFmt::BAM, hdr, pool, nullptr, true, false);
+        hw.close();
+    } catch (...) {
+        fclose(mf);
+        free(mp);
+        throw;
+    }
+    fclose(mf);
+    const bool ok = fwrite(mp, 1, mn, out) == mn;
+    free(mp);
+    if (!ok) throw std::runtime_error("write error on the sorted extract");
+    uint64_t at = mn;
+    struct Bai { fadehip_bai *b = nullptr; ~Bai() { if (b) fadehip_bai_destroy(b); } } bai;
+    if (!bai_path.empty() && !(bai.b = fadehip_bai_create((int32_t)hdr.names.size()))) throw std::runtime_error("out of memory");
+    if (fadehip_recstore_sort(rs)) throw std::runtime_error(fadehip_last_error(ctx));
+    const int32_t flags = (stored ? FADEHIP_RECSTORE_STORED : 0) | (bai.b ? FADEHIP_RECSTORE_INDEX : 0);
+    int64_t total = 0;
+    for (;;) {
+        const uint8_t *p = nullptr;
+        size_t n = 0;
+        int64_t n_rec = 0;
+        fadehip_index_call c;
+        if (fadehip_recstore_drain(rs, flags, (uint64_t)64 << 20, &p, &n, &n_rec, bai.b ? &c : nullptr)) throw std::runtime_error(fadehip_last_error(ctx));
+        if (!n_rec) break;
+        if (fwrite(p, 1, n, out) != n) throw std::runtime_error("write error on the sorted extract");
+        if (bai.b && fadehip_bai_add(bai.b, at, &c)) throw std::runtime_error(fadehip_bai_error(bai.b));
+        at += n;
+        total += n_rec;
+    }
+    if (fwrite(BGZF_EOF, 1, sizeof BGZF_EOF, out) != sizeof BGZF_EOF || fflush(out) != 0 || ferror(out)) throw std::runtime_error("write error on the sorted extract");
+    if (bai.b) {
+        const uint8_t *p = nullptr;
+        size_t n = 0;
+        if (fadehip_bai_finish(bai.b, &p, &n)) throw std::runtime_error(fadehip_bai_error(bai.b));
+        FILE *f = fopen(bai_path.c_str(), "wb");
+        if (!f) throw std::runtime_error("cannot write " + bai_path + ": " + strerror(errno));
+        const bool wrote = fwrite(p, 1, n, f) == n;
+        if (fclose(f) != 0 || !wrote) throw std::runtime_error("write error on " + bai_path);
+    }
+    return total;
+}
 
 // What `fade out -c` and `fade annotate -c` say about their output (filter.d:184-185); with --keep-sorted, what holds instead
 static const char *const kFixMatesLine =
@@ -1666,17 +1729,20 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
     }
     fadehip_ctx *ctx = nullptr;
     fadehip_bam_stream *st = nullptr;
+    fadehip_recstore *store = nullptr;  // --extract-sorted: the run's extract records, on the device
     struct Guard {
         fadehip_ctx *&c;
         fadehip_bam_stream *&s;
+        fadehip_recstore *&rs;
         std::vector<void *> pinned, owned;  // registered with the ctx; allocated here
         ~Guard() {
             if (s) fadehip_bam_close(s);
+            if (rs) fadehip_recstore_destroy(rs);
             for (void *p : pinned) fadehip_host_free(c, p);
             fadehip_destroy(c);
             for (void *p : owned) free(p);
         }
-    } guard{ctx, st, {}, {}};
+    } guard{ctx, st, store, {}, {}};
     try {
         fadehip_params prm;
         fadehip_params_default(&prm);
@@ -1714,7 +1780,12 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
             if (!o.extract.empty()) cfg.flags |= FADEHIP_BAM_EXTRACT;  // --extract: every call leaves its extract records too
             if (o.eject) cfg.flags |= eject_grouped ? FADEHIP_BAM_EJECT | FADEHIP_BAM_EJECT_GROUPS : FADEHIP_BAM_EJECT;  // --eject
             if (!o.write_index.empty()) cfg.flags |= FADEHIP_BAM_INDEX;  // --write-index: every call leaves its .bai entries too
+            if (o.extract_sorted) {  // --extract-sorted: ... and they stay on the device, in a store, until the main output is finished
+                cfg.flags |= FADEHIP_BAM_STORE_EXTRACT;
+                if (fadehip_recstore_create(ctx, &store)) { create_err = fadehip_last_error(ctx); return 1; }
+            }
             if (fadehip_bam_open(ctx, &cfg, &st)) { create_err = fadehip_last_error(ctx); return 1; }
+            if (store && fadehip_bam_use_recstore(st, store)) { create_err = fadehip_last_error(ctx); return 1; }
             const size_t call_bytes = host_inflate ? chunk : std::min<size_t>(chunk * 3, (size_t)1 << 30);
             if (!(getenv("FADE_BAM_PREPARE") && atoi(getenv("FADE_BAM_PREPARE")) == 0) && fadehip_bam_prepare(st, call_bytes)) { create_err = fadehip_last_error(ctx); return 1; }
             return 0;
@@ -1972,7 +2043,7 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
         if (!o.extract.empty()) {  // --extract PATH: the output's format and header, written by the CPU writer
             xfile.f = fopen(o.extract.c_str(), "wb");
             if (!xfile.f) { fprintf(stderr, "[E::fade annotate] cannot write %s: %s\n", o.extract.c_str(), strerror(errno)); return 1; }
-            xwriter.reset(new Writer(xfile.f, o.ubam ? OutFmt::UBAM : OutFmt::BAM, out_hdr, &pool));
+            if (!store) xwriter.reset(new Writer(xfile.f, o.ubam ? OutFmt::UBAM : OutFmt::BAM, out_hdr, &pool));  // (--extract-sorted: written once the main output is finished)
         }
         ck_upload.stop();
         // (the FASTA's text is on the device now; giving a genome's worth of pages back takes milliseconds, and the first call
@@ -2109,6 +2180,13 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
         if ((!lane.on || lane.shard) && fwrite(BGZF_EOF, 1, sizeof BGZF_EOF, stdout) != sizeof BGZF_EOF) { fprintf(stderr, "[E::fade annotate] write error on the output stream\n"); return 1; }
         if (fflush(stdout) != 0 || ferror(stdout)) { fprintf(stderr, "[E::fade annotate] write error on the output stream\n"); return 1; }
         if (index.on()) index.write();
+        if (store) {  // --extract-sorted: PATH in coordinate order and PATH.bai beside it, behind the finished main output
+            StageClock ck_sorted;
+            ck_sorted.start();
+            const int64_t n_sorted = write_sorted_store(ctx, store, xfile.f, o.ubam, out_hdr, &pool, o.extract + ".bai");
+            ck_sorted.stop();
+            if (o.timing) fprintf(stderr, "[timing] --extract-sorted: %lld records sorted on the device and written in coordinate order in %.3f s\n", (long long)n_sorted, ck_sorted.t);
+        }
         int64_t totals[8], n_rec = 0, n_over = 0;
         fadehip_bam_totals(st, totals, &n_rec, &n_over);
         report_held(o);
@@ -2568,6 +2646,8 @@ static void print_extract_help() {
             "-b     --bam output bam\n"
             "-u    --ubam output uncompressed bam\n"
             "      --gpus 1: BAM file in, -b or -u out: the records are built on one MI355X (rs and am read back by a kernel)\n"
+            "    --sorted with --gpus 1: the records are kept on the MI355X, sorted once by coordinate and written in that order (@HD SO:coordinate)\n"
+            "--write-index PATH: with --sorted, also write the BAM index (.bai) of the output, made in the same pass\n"
             "    --timing print where the run spent its time to stderr\n"
             "-h    --help This help information.\n\n",
             kHeader);
@@ -3012,7 +3092,7 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
             return 1;
         }
     } else if (job == TagsJob::EXTRACT) {
-        fprintf(stderr, "[W::fade extract] Output SAM/BAM will not be sorted\n");  // remap.d:13
+        if (!o.sorted) fprintf(stderr, "[W::fade extract] Output SAM/BAM will not be sorted\n");  // remap.d:13 (--sorted: it will be)
     } else if (fragments) {
         fprintf(stderr, "[W::fade-out] --fragments: ejecting every read that shares its name with an artifact read, input in any order (two passes over the file)\n");
     } else if (o.clip) {  // filter.d:184-185 (--fix-mates: its own line in the place of the second)
@@ -3024,21 +3104,24 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
     fadehip_bam_stream *st = nullptr;
     fadehip_nameset *names = nullptr;
     fadehip_mateset *mates = nullptr;
+    fadehip_recstore *store = nullptr;  // `fade extract --sorted`: the run's extract records, on the device
     struct Guard {
         fadehip_ctx *&c;
         fadehip_bam_stream *&s;
         fadehip_nameset *&ns;
         fadehip_mateset *&ms;
+        fadehip_recstore *&rs;
         std::vector<void *> pinned, owned;
         ~Guard() {
             if (s) fadehip_bam_close(s);
             if (ns) fadehip_nameset_destroy(ns);
             if (ms) fadehip_mateset_destroy(ms);
+            if (rs) fadehip_recstore_destroy(rs);
             for (void *p : pinned) fadehip_host_free(c, p);
             if (c) fadehip_destroy(c);
             for (void *p : owned) free(p);
         }
-    } guard{ctx, st, names, mates, {}, {}};
+    } guard{ctx, st, names, mates, store, {}, {}};
     try {
         fadehip_params prm;
         fadehip_params_default(&prm);
@@ -3061,6 +3144,7 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
             if (fadehip_bam_open(ctx, &cfg, &st)) { create_err = fadehip_last_error(ctx); return 1; }
             if ((mode & (FADEHIP_BAM_COLLECT_NAMES | FADEHIP_BAM_EJECT_NAMED | FADEHIP_BAM_COLLECT_MATES)) && fadehip_bam_use_nameset(st, names)) { create_err = fadehip_last_error(ctx); return 1; }
             if ((mode & (FADEHIP_BAM_COLLECT_MATES | FADEHIP_BAM_FIX_MATES)) && fadehip_bam_use_mateset(st, mates)) { create_err = fadehip_last_error(ctx); return 1; }
+            if ((mode & FADEHIP_BAM_STORE_EXTRACT) && fadehip_bam_use_recstore(st, store)) { create_err = fadehip_last_error(ctx); return 1; }
             const size_t call_bytes = host_inflate ? chunk : std::min<size_t>(chunk * 3, (size_t)1 << 30);
             if (!(getenv("FADE_BAM_PREPARE") && atoi(getenv("FADE_BAM_PREPARE")) == 0) && fadehip_bam_prepare(st, call_bytes)) { create_err = fadehip_last_error(ctx); return 1; }
             return 0;
@@ -3075,6 +3159,11 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
             if (report) return open_stream(FADEHIP_BAM_NO_OUTPUT | (job == TagsJob::STATS ? FADEHIP_BAM_REPORT_STATS : FADEHIP_BAM_REPORT_CLIP));
             int32_t mode = o.ubam ? FADEHIP_BAM_STORED : 0;
             if (job == TagsJob::EXTRACT) mode |= FADEHIP_BAM_EXTRACT | FADEHIP_BAM_NO_OUTPUT;
+            if (job == TagsJob::EXTRACT && o.sorted) {  // the records stay on the device until the input is through
+                if (fadehip_recstore_create(ctx, &store)) { create_err = fadehip_last_error(ctx); return 1; }
+                mode |= FADEHIP_BAM_STORE_EXTRACT;
+                return open_stream(mode);  // (--write-index is of the sorted records: the drains make its entries, not the stream)
+            }
             else if (o.clip) mode |= FADEHIP_BAM_CLIP | (o.keep_sorted ? FADEHIP_BAM_KEEP_SORTED : 0);
             else mode |= grouped ? FADEHIP_BAM_EJECT | FADEHIP_BAM_EJECT_GROUPS : FADEHIP_BAM_EJECT;
             if (!o.write_index.empty()) mode |= FADEHIP_BAM_INDEX;
@@ -3334,6 +3423,8 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
             fputs(job == TagsJob::STATS ? "qname\trname\tpos\tcigar\tart_start\tart_end\taln_rname\taln_start\taln_end\tart_cigar\tstemloop\tstemloop_rc\t"
                                           "predicted_inverted_repeat\tIR_identity\tavgbq\tart_avgbq\tart_bq\tIR_bq\tflagbinary\tflag\tstrand\n"
                                         : "qname\tsc_q_scores\tsc_seq\tsc_avg_bq\tavg_bq\tart_status\n", rep_out);
+        } else if (job == TagsJob::EXTRACT && o.sorted) {
+            // (nothing is written while the input streams through: header, records and marker follow the sort)
         } else if (job == TagsJob::EXTRACT) xwriter.reset(new Writer(stdout, fmt, out_hdr, &pool));
         else if (!o.write_index.empty()) {
             index.open(o.write_index, hdr.names.size());
@@ -3349,7 +3440,13 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
         if (report) {
             if (fflush(rep_out) != 0 || ferror(rep_out)) { fprintf(stderr, "[E::%s] write error on the report\n", who); return 1; }
         } else if (xwriter) xwriter->close();
-        else if (fwrite(BGZF_EOF, 1, sizeof BGZF_EOF, stdout) != sizeof BGZF_EOF) { fprintf(stderr, "[E::%s] write error on the output stream\n", who); return 1; }
+        else if (store) {
+            StageClock ck_sorted;
+            ck_sorted.start();
+            const int64_t n_sorted = write_sorted_store(ctx, store, stdout, o.ubam, out_hdr, &pool, o.write_index);
+            ck_sorted.stop();
+            if (o.timing) fprintf(stderr, "[timing] --sorted: %lld records sorted on the device and written in coordinate order in %.3f s\n", (long long)n_sorted, ck_sorted.t);
+        } else if (fwrite(BGZF_EOF, 1, sizeof BGZF_EOF, stdout) != sizeof BGZF_EOF) { fprintf(stderr, "[E::%s] write error on the output stream\n", who); return 1; }
         if (fflush(stdout) != 0 || ferror(stdout)) { fprintf(stderr, "[E::%s] write error on the output stream\n", who); return 1; }
         if (index.on()) index.write();
         int64_t totals[8], n_rec = 0, n_over = 0, n_ej = 0;
@@ -3432,6 +3529,28 @@ static std::string write_index_refusal(const Opts &o, bool reports) {
     return bgzf ? "" : kWriteIndexInput;
 }
 
+// --sorted (`fade extract`) and --extract-sorted (`fade annotate`): why the option cannot run as the command line stands, or
+// "".  The records are kept, sorted and compressed on one device: there is no host loop behind either option.  Looks at the
+// options, the environment and the first bytes of the input: no device is opened for it.  `first`: a reason the caller has.
+static const char *const kSortedExtractInput = "the input is read as a BAM file on the device: not SAM text, not a pipe";
+static std::string sorted_extract_refusal(const Opts &o, const std::string &first) {
+    if (!first.empty()) return first;
+    if (o.gpus > 1) return "it goes with one device: not with --gpus N > 1 (the store of records lives on one device)";
+    if (!o.out_shards.empty()) return "it goes with one device and one output: not with --out-shards";
+    if (!(o.bam || o.ubam)) return "the output is SAM text: the sorted extract is BAM (-b) or uncompressed BAM (-u)";
+    if (getenv("FADE_BAM_DEVICE") && atoi(getenv("FADE_BAM_DEVICE")) == 0) return "FADE_BAM_DEVICE=0 takes the device away, and the records are kept and sorted on it (no host loop)";
+    const std::string &path = o.pos[1];
+    struct stat sb;
+    uint8_t h[4] = {0, 0, 0, 0};
+    bool bgzf = false;
+    if (path != "-" && stat(path.c_str(), &sb) == 0 && S_ISREG(sb.st_mode))
+        if (FILE *f = fopen(path.c_str(), "rb")) {
+            bgzf = fread(h, 1, 4, f) == 4 && h[0] == 0x1f && h[1] == 0x8b && (h[3] & 4);
+            fclose(f);
+        }
+    return bgzf ? "" : kSortedExtractInput;
+}
+
 // --gpus for `fade out` / `fade extract`: 1 is the file path on the device where the input and output allow it, more is not built
 static bool tags_gpus_ok(const Opts &o, const char *who) {
     if (o.seen.find('g') == std::string::npos || o.gpus == 1) return true;
@@ -3451,7 +3570,7 @@ int main(int argc, char **argv) {
             fprintf(stderr, "std.getopt.GetOptException: %s\n", err.c_str());
             return 1;
         }
-        if (!options_allowed(o, "tmwbucgBsTSPQXEKI")) return 1;
+        if (!options_allowed(o, "tmwbucgBsTSPQXEKIY")) return 1;
         // app.d:84-89: helpWanted | args.length < 3 (args = prog, "annotate", positionals...)
         if (o.help || o.pos.size() < 2) { print_anno_help(); return 0; }
         if (o.pos.size() < 3) {  // the reference indexes args[2] and dies; say why instead
@@ -3513,11 +3632,19 @@ int main(int argc, char **argv) {
                 return 1;
             }
         }
+        if (o.extract_sorted) {  // the store lives on one device: there is no host loop behind the option — refused here, by name
+            const std::string why = sorted_extract_refusal(o, o.extract.empty() ? "it says how the --extract file is written: the option goes with --extract PATH"
+                                                              : reports ? std::string("the run with ") + (!o.stats_tsv.empty() ? "--stats-tsv" : "--clip-tsv") + " does not take the file path on the device: not with it" : "");
+            if (!why.empty()) {
+                fprintf(stderr, "[E::fade-annotate] --extract-sorted: %s\n", why.c_str());
+                return 1;
+            }
+        }
         if (!o.out_shards.empty() && o.gpus < 2) {
             fprintf(stderr, "[E::fade-annotate] --out-shards PREFIX writes one file per device: it goes with --gpus N (N >= 2)\n");
             return 1;
         }
-        if (!o.extract.empty()) fprintf(stderr, "[W::fade extract] Output SAM/BAM will not be sorted\n");  // remap.d:13
+        if (!o.extract.empty() && !o.extract_sorted) fprintf(stderr, "[W::fade extract] Output SAM/BAM will not be sorted\n");  // remap.d:13
         if (o.clip && !lane_env().on) clip_warnings(o);  // filter.d:184-185, as `fade out -c` (once: the lanes of --gpus N stay silent)
         // --gpus N on a BAM file: one process per GPU, each on its own share of the input (annotate_lanes_main); input that
         // cannot be cut (a pipe, SAM text, a small file) is read by one process that deals batches to the N devices
@@ -3542,6 +3669,10 @@ int main(int argc, char **argv) {
         }
         if (!o.write_index.empty()) {  // nor behind this one
             fprintf(stderr, "[E::fade-annotate] --write-index: %s\n", kWriteIndexInput);
+            return 1;
+        }
+        if (o.extract_sorted) {  // nor behind this one
+            fprintf(stderr, "[E::fade-annotate] --extract-sorted: %s\n", kSortedExtractInput);
             return 1;
         }
         const int rc = annotate_main(cl, o);
@@ -3575,12 +3706,43 @@ int main(int argc, char **argv) {
             fprintf(stderr, "std.getopt.GetOptException: %s\n", err.c_str());
             return 1;
         }
-        if (!options_allowed(o, "tbugT")) return 1;
+        if (!options_allowed(o, "tbugTOIS")) return 1;
         if (o.help || o.pos.size() < 2) { print_extract_help(); return 0; }
+        if (!o.write_index.empty() && !o.sorted) {  // refused here, by name, before any device is opened
+            // (in std.getopt's words, as before --sorted existed: without it this subcommand has no such option)
+            fprintf(stderr, "std.getopt.GetOptException: Unrecognized option --write-index without --sorted\n"
+                            "[E::fade extract] --write-index: the extract records leave in the order of the input's reads, and an index is of coordinate-sorted records: the option goes with --sorted\n");
+            return 1;
+        }
+        if (!o.out_shards.empty()) {
+            fprintf(stderr, "[E::fade extract] --out-shards: this subcommand writes one output%s\n", o.sorted ? " (--sorted puts the whole run's records in one order: not with --out-shards)" : "");
+            return 1;
+        }
+        if (o.sorted) {  // the store lives on one device: there is no host loop behind the option
+            const std::string why = sorted_extract_refusal(o, o.seen.find('g') == std::string::npos ? "it goes with --gpus 1 (the records are kept and sorted on the device; there is no host loop)" : "");
+            if (!why.empty()) {
+                fprintf(stderr, "[E::fade extract] --sorted: %s\n", why.c_str());
+                return 1;
+            }
+            if (!o.write_index.empty()) {
+                struct stat sa, sb2;
+                const bool same = o.write_index == o.pos[1] || (stat(o.write_index.c_str(), &sa) == 0 && stat(o.pos[1].c_str(), &sb2) == 0 && sa.st_dev == sb2.st_dev && sa.st_ino == sb2.st_ino);
+                if (o.write_index == "-" || same) {
+                    fprintf(stderr, "[E::fade extract] --write-index: PATH is a file of its own: not %s\n", o.write_index == "-" ? "the standard output" : "the input");
+                    return 1;
+                }
+            }
+        }
         if (!tags_gpus_ok(o, "fade extract")) return 1;
         if (o.bam && o.ubam) {
             fprintf(stderr, "[E::fade-annotate] Please use only one of the b or u flags\n");  // app.d:149 (sic)
             return 1;
+        }
+        if (o.sorted) {
+            bool fall_back = true;
+            const int rc = tags_stream_main(cl, o, TagsJob::EXTRACT, &fall_back);
+            if (fall_back) fprintf(stderr, "[E::fade extract] --sorted: %s\n", kSortedExtractInput);
+            return fall_back ? 1 : rc;
         }
         if (o.seen.find('g') != std::string::npos) {  // --gpus 1: the file path on the device, where input and output allow it
             bool fall_back = true;

@@ -359,6 +359,50 @@ int fadehip_mates_fix_batch(fadehip_mateset *s, int32_t n, const uint8_t *recs, 
 int fadehip_mateset_count(fadehip_mateset *s, int64_t *n_entries, int64_t *n_ambiguous);
 void fadehip_mateset_destroy(fadehip_mateset *s);
 
+/* A store of BAM records, resident on the device: what lets `fade extract --sorted` and `fade annotate --extract-sorted`
+ * write their extract records in coordinate order with a .bai, without a `samtools sort` and `samtools index` behind them.
+ * An extract record lies at its artifact alignment, so the output order has nothing to do with the input's: the store
+ * collects the records of a whole run, sorts them once, and hands them out in order (tests/recstore_model.py
+ * states the rule in plain Python).
+ *   add_batch  the records with pick[k] != 0 (pick NULL: every record) are appended, in the order they come; shapes as
+ *              fadehip_eject_batch takes (n_cigar_op and l_seq must fit too).  A malformed record: FADEHIP_E_INVALID with
+ *              its index, the store left as it was.  A stream opened with FADEHIP_BAM_STORE_EXTRACT appends its calls'
+ *              extract records to the same store, call by call in stream order.
+ *   count      records and their bytes, as added so far
+ *   sort       closes the store for adding (a later add, or a stream that appends: FADEHIP_E_STATE) and puts the records in
+ *              the order of fadehip_coord_order_batch: by (refID as uint32) << 32 | (pos + 1 as uint32) — refID -1 last —
+ *              and, within one key, in the order they were added.  Waits for whatever still appends on the device.
+ *   drain      after sort (before: FADEHIP_E_STATE): hands out the next maximal run of records, in final order, whose bytes
+ *              total at most max_payload (and at most 2^30) — always at least one record, never a part of one; *n_records 0:
+ *              the store is drained.  flags:
+ *                FADEHIP_RECSTORE_RAW     *out: the records back to back, no codec
+ *                0                        *out: BGZF members from the device compressor, ready for the file
+ *                FADEHIP_RECSTORE_STORED  *out: stored members, as FADEHIP_BAM_STORED makes them
+ *                FADEHIP_RECSTORE_INDEX   beside 0 or STORED (with RAW: FADEHIP_E_INVALID): *idx also gets the drained
+ *                                         records' index entries, by the rule and the kernels of fadehip_index_batch, at
+ *                                         virtual offsets relative to the drain's first member — fadehip_bai_add rebases
+ *                                         them as it does a stream's calls.  A record that ends beyond 2^29:
+ *                                         FADEHIP_E_UNSUPPORTED naming the record (its number in final order); that drain
+ *                                         hands out nothing and the store stays where it was.
+ *              *out is pinned memory of the store and *idx points into memory of the store, both good until its next drain.
+ * The calls are synchronous; add_batch and sort take the lock fadehip_clip_batch takes, drain uses compressor lane 0 (no
+ * stream of the ctx may be using it).  The store grows as records come: the arena and the per-record arrays double, after a
+ * wait for the device, with a copy on the device.  A device allocation that fails is FADEHIP_E_NOMEM; more than 2^31 - 1
+ * records is FADEHIP_E_UNSUPPORTED.  destroy comes after every stream that uses the store has been closed, and before
+ * fadehip_destroy.  Environment, read at create: FADEHIP_RECSTORE_BYTES=N, the first arena's size (default 64 MiB, at least
+ * 256).  Results do not depend on it. */
+typedef struct fadehip_recstore fadehip_recstore;
+#define FADEHIP_RECSTORE_RAW 1
+#define FADEHIP_RECSTORE_STORED 2
+#define FADEHIP_RECSTORE_INDEX 4
+int fadehip_recstore_create(fadehip_ctx *ctx, fadehip_recstore **out);
+int fadehip_recstore_add_batch(fadehip_recstore *s, int32_t n, const uint8_t *recs, const int64_t *rec_off, const uint8_t *pick /* [n] or NULL */);
+int fadehip_recstore_count(fadehip_recstore *s, int64_t *n_records, int64_t *n_bytes);
+int fadehip_recstore_sort(fadehip_recstore *s);
+int fadehip_recstore_drain(fadehip_recstore *s, int32_t flags, uint64_t max_payload, const uint8_t **out, size_t *out_bytes, int64_t *n_records,
+                           fadehip_index_call *idx /* NULL without FADEHIP_RECSTORE_INDEX */);
+void fadehip_recstore_destroy(fadehip_recstore *s);
+
 /* ------------------------------------------------------ Level 2: annotateTask over a batch -- */
 /* Upload the indexed FASTA once (what IndexedFastaFile + fetchSequence serve, analysis.d:63).
  * seqs[c] holds lengths[c] ASCII residues (any case; upper-cased on device as analysis.d:63 does).
@@ -657,7 +701,13 @@ typedef struct fadehip_bam_config {
                                    * record's own refID, pos and bin never change, so KEEP_SORTED's order and INDEX's entries are
                                    * those of CLIP alone, but for the bytes MC gains or loses.  Any other combination:
                                    * FADEHIP_E_INVALID at fadehip_bam_open, naming the flag; without the sets attached the first
-                                   * front call fails with FADEHIP_E_STATE */
+                                   * front call fails with FADEHIP_E_STATE;
+                                   * FADEHIP_BAM_STORE_EXTRACT: needs EXTRACT (without it: FADEHIP_E_INVALID at fadehip_bam_open,
+                                   * naming the flag) and stands wherever EXTRACT does.  The calls' extract records are written
+                                   * into the record store attached with fadehip_bam_use_recstore (none attached: the first front
+                                   * call fails with FADEHIP_E_STATE), in stream order, and stay on the device: no copy to the
+                                   * host is made, and fadehip_bam_back_extract gives 0 bytes and the number of records the call
+                                   * added.  No other output byte changes.  A store that has been sorted: FADEHIP_E_STATE */
     const char *const *ref_names; /* [n_ref] NUL-terminated */
     uint32_t first_record;        /* payload bytes of the first member passed to front that precede the first record */
     uint32_t tail_trim;           /* payload bytes at the END of the last member (front's last call) that are not this stream's:
@@ -679,6 +729,7 @@ typedef struct fadehip_bam_config {
 #define FADEHIP_BAM_INDEX 4096
 #define FADEHIP_BAM_COLLECT_MATES 8192
 #define FADEHIP_BAM_FIX_MATES 16384
+#define FADEHIP_BAM_STORE_EXTRACT 32768
 int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_bam_stream **out);
 /* The set a stream opened with FADEHIP_BAM_COLLECT_NAMES adds to, or one opened with FADEHIP_BAM_EJECT_NAMED looks names up
  * in: a set of the same ctx, attached before the first front call (later: FADEHIP_E_STATE).  The set is the caller's and
@@ -690,6 +741,10 @@ int fadehip_bam_use_nameset(fadehip_bam_stream *st, fadehip_nameset *s);
  * left alone because their mate's key is ambiguous, over the calls finished so far. */
 int fadehip_bam_use_mateset(fadehip_bam_stream *st, fadehip_mateset *s);
 int fadehip_bam_mates(fadehip_bam_stream *st, int64_t *n_fixed, int64_t *n_ambiguous);
+/* The record store a stream opened with FADEHIP_BAM_STORE_EXTRACT appends its extract records to: a store of the same ctx,
+ * attached before the first front call (later: FADEHIP_E_STATE).  The store is the caller's and outlives the stream; it is
+ * sorted and drained after the stream's last back call. */
+int fadehip_bam_use_recstore(fadehip_bam_stream *st, fadehip_recstore *s);
 int fadehip_bam_prepare(fadehip_bam_stream *st, size_t call_bytes);
 int fadehip_bam_front(fadehip_bam_stream *st, const void *members, size_t n_bytes, int last);
 /* front for a caller that inflates itself (host cores otherwise idle; the device then spends its time on the rest):
