@@ -14,6 +14,7 @@
 #include <memory>
 #include "hts_lite.hpp"
 #include "recstore_host.hpp"
+#include "bgzf_feed.hpp"
 #include "../../../include/fadehip.h"
 
 #include <atomic>
@@ -990,6 +991,30 @@ struct StageThreads {
     }
 };
 
+// The staging buffers of the file-path drivers: ordinary memory while the ctx is still being made (the reader fills them
+// meanwhile), registered with it once it is there.  A driver's Guard gives them back (unpin) before it destroys the ctx;
+// the memory itself goes when this does, so it is declared in front of the Guard.
+struct Staging {
+    std::vector<std::pair<void *, size_t>> raw;  // allocated here
+    std::vector<void *> pinned;                  // ... and registered with the ctx
+    uint8_t *alloc(size_t bytes) {
+        const size_t al = (size_t)1 << 21, n = (bytes + al - 1) & ~(al - 1);
+        void *q = aligned_alloc(al, n);
+        if (!q) throw std::runtime_error("out of memory");
+        raw.emplace_back(q, n);
+        return (uint8_t *)q;
+    }
+    bool pin(fadehip_ctx *c) {  // false: fadehip_last_error(c) says why
+        for (auto &rb : raw) {
+            if (fadehip_host_register(c, rb.first, rb.second)) return false;
+            pinned.push_back(rb.first);
+        }
+        return true;
+    }
+    void unpin(fadehip_ctx *c) { for (void *p : pinned) fadehip_host_free(c, p); }
+    ~Staging() { for (auto &rb : raw) free(rb.first); }
+};
+
 // Threads when -t is not given: the CPUs this process may actually use — its affinity mask and, in a container, the
 // cgroup's CPU quota (a 16-CPU share of a 256-thread host must not get 255 threads) — at most 64.
 static int default_threads(int cap = 64) {
@@ -1186,20 +1211,18 @@ static int annotate_lanes_main(const std::string &cl, const Opts &o, bool *fall_
     std::vector<uint32_t> bsz;
     {
         uint64_t at = 0;
-        uint8_t h[18];
-        while (pread(fileno(f), h, 18, (off_t)at) == 18) {
-            if (h[0] != 0x1f || h[1] != 0x8b || !(h[3] & 4) || h[12] != 'B' || h[13] != 'C') return 1;  // not BGZF: one lane reads it
-            const uint32_t bs = (uint32_t)(h[16] | (h[17] << 8)) + 1u;
+        uint32_t bs;
+        for (MemberAt r; (r = bgzf_member_at(fileno(f), at, &bs, nullptr)) != MemberAt::NO_HEADER; at += bs) {
+            if (r == MemberAt::NOT_BGZF) return 1;  // not BGZF: one lane reads it
             boff.push_back(at);
             bsz.push_back(bs);
-            at += bs;
         }
     }
     if (boff.size() < (size_t)(8 * n_lanes)) return 1;  // too small to be worth cutting
     auto isize_of = [&](size_t b) -> uint32_t {
-        uint8_t t[4] = {0, 0, 0, 0};
-        if (pread(fileno(f), t, 4, (off_t)(boff[b] + bsz[b] - 4)) != 4) return 0;
-        return (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
+        uint32_t bs, isz = 0;  // (0 where the trailer cannot be read)
+        bgzf_member_at(fileno(f), boff[b], &bs, &isz);
+        return isz;
     };
     auto inflate_blocks = [&](size_t b0, size_t nb, std::vector<uint8_t> &out, std::vector<size_t> &start) -> bool {
         out.clear();
@@ -1243,13 +1266,14 @@ static int annotate_lanes_main(const std::string &cl, const Opts &o, bool *fall_
     // must end exactly there.
     std::vector<LaneRange> lr((size_t)n_lanes);
     {
-        size_t b = 0;
-        uint64_t cum = 0;
-        while (b < boff.size() && cum + isize_of(b) <= hdr_bytes) cum += isize_of(b++);
-        if (b >= boff.size()) return 1;
+        uint64_t coff = 0;
+        uint32_t first_rec = 0, bs, isz;
+        if (!locate_first_record(fileno(f), (uint64_t)sb.st_size, hdr_bytes, &coff, &first_rec)) return 1;
+        // (where the header fills every member the single-lane drivers start at the last one; here no member is left for a lane)
+        if (bgzf_member_at(fileno(f), coff, &bs, &isz) != MemberAt::OK || first_rec >= isz) return 1;
         lr[0].on = true;
-        lr[0].coff_start = boff[b];
-        lr[0].first_rec = hdr_bytes - cum;
+        lr[0].coff_start = coff;
+        lr[0].first_rec = first_rec;
     }
     for (int k = 1; k < n_lanes; k++) {
         bool found = false;
@@ -1682,23 +1706,13 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
             rd.read_chunk(first, 10);
             for (const Rec &r : first) eject_names.push_back(r.qname());
         }
-        uint64_t at = 0, cum = 0;
         if (lane.on) {
             coff = lane.range.coff_start;
             first_rec = (uint32_t)lane.range.first_rec;
+            if (first_rec > 65536) return 1;
+        } else if (!locate_first_record(fileno(f), (uint64_t)sb.st_size, hdr_bytes, &coff, &first_rec)) {
+            return 1;  // (other gzip subfields first, say: the host path reads it)
         }
-        while (!lane.on) {
-            uint8_t h[18], t[4];
-            if (pread(fileno(f), h, 18, (off_t)at) != 18) return 1;
-            if (h[0] != 0x1f || h[1] != 0x8b || !(h[3] & 4) || h[12] != 'B' || h[13] != 'C') return 1;  // (other gzip subfields first: the host path reads it)
-            const uint32_t bs = (uint32_t)(h[16] | (h[17] << 8)) + 1u;
-            if (pread(fileno(f), t, 4, (off_t)(at + bs - 4)) != 4) return 1;
-            const uint32_t isz = (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
-            if (cum + isz > hdr_bytes || (uint64_t)at + bs >= (uint64_t)sb.st_size) { coff = at; first_rec = (uint32_t)(hdr_bytes - cum); break; }
-            cum += isz;
-            at += bs;
-        }
-        if (first_rec > 65536) return 1;
     } catch (const std::exception &e) {
         return 1;  // the host path reports what is wrong with the file
     }
@@ -1714,15 +1728,13 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
     if (limited) {
         read_end = lane.range.coff_end;
         if (lane.range.end_rec > 0) {
-            uint8_t h[18];
-            if (pread(fileno(f), h, 18, (off_t)lane.range.coff_end) != 18 || h[12] != 'B' || h[13] != 'C') { fprintf(stderr, "[E::fade annotate] lane range ends at no BGZF member\n"); return 1; }
-            const uint64_t bsz = (uint64_t)(h[16] | (h[17] << 8)) + 1u;
+            uint32_t bsz, isz;
+            const MemberAt r = bgzf_member_at(fileno(f), lane.range.coff_end, &bsz, &isz);
+            if (r == MemberAt::NO_HEADER || r == MemberAt::NOT_BGZF) fprintf(stderr, "[E::fade annotate] lane range ends at no BGZF member\n");
+            if (r != MemberAt::OK) return 1;
             read_end += bsz;
             // a lane's last member is cut where the next lane's first record starts: by this process when it inflates, by the
             // library (tail_trim) when the device does
-            uint8_t t[4];
-            if (pread(fileno(f), t, 4, (off_t)(read_end - 4)) != 4) return 1;
-            const uint32_t isz = (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
             if (lane.range.end_rec > isz) { fprintf(stderr, "[E::fade annotate] lane range ends beyond its last block\n"); return 1; }
             tail_trim = isz - (uint32_t)lane.range.end_rec;
         }
@@ -1730,19 +1742,19 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
     fadehip_ctx *ctx = nullptr;
     fadehip_bam_stream *st = nullptr;
     fadehip_recstore *store = nullptr;  // --extract-sorted: the run's extract records, on the device
+    Staging staging;
     struct Guard {
         fadehip_ctx *&c;
         fadehip_bam_stream *&s;
         fadehip_recstore *&rs;
-        std::vector<void *> pinned, owned;  // registered with the ctx; allocated here
+        Staging &stg;
         ~Guard() {
             if (s) fadehip_bam_close(s);
             if (rs) fadehip_recstore_destroy(rs);
-            for (void *p : pinned) fadehip_host_free(c, p);
+            stg.unpin(c);
             fadehip_destroy(c);
-            for (void *p : owned) free(p);
         }
-    } guard{ctx, st, store, {}, {}};
+    } guard{ctx, st, store, staging};
     try {
         fadehip_params prm;
         fadehip_params_default(&prm);
@@ -1799,16 +1811,6 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
         struct In { uint8_t *p = nullptr, *pin = nullptr; size_t n = 0; bool last = false, compressed = false; int cbuf = -1; };
         CBuf cbufs[NBUF];
         In bufs[NBUF];
-        // (ordinary memory for now — the ctx is still being made; registered with it once it is there)
-        std::vector<std::pair<void *, size_t>> raw_bufs;
-        auto pinned = [&](size_t bytes) -> uint8_t * {
-            const size_t al = (size_t)1 << 21, n = (bytes + al - 1) & ~(al - 1);
-            void *q = aligned_alloc(al, n);
-            if (!q) throw std::runtime_error("out of memory");
-            guard.owned.push_back(q);
-            raw_bufs.emplace_back(q, n);
-            return (uint8_t *)q;
-        };
         // FADE_BAM_DEVICE_SHARE=n: with the pool inflating, every n-th call's members go to the device as they are (inflated by
         // the kernel of FADE_BAM_INFLATE=device): the cores are the bottleneck of a file-to-file run once the device's half is
         // fast, and the device has time to spare for a share of the inflating.  0: none.
@@ -1819,14 +1821,14 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
         // was measured and is slower than pread into a buffer: the pool inflates 20-30 % slower out of the mapping.)
         for (int k = 0; k < NBUF; k++) {
             if (host_inflate) {
-                if (dev_share) cbufs[k].p = pinned(HEAD + ccap + 64);  // (some of its members cross PCIe as they are)
+                if (dev_share) cbufs[k].p = staging.alloc(HEAD + ccap + 64);  // (some of its members cross PCIe as they are)
                 else {
                     cbufs[k].own.resize(HEAD + ccap + 64);
                     cbufs[k].p = cbufs[k].own.data();
                 }
-                bufs[k].pin = bufs[k].p = pinned(chunk + 65536 + 64);
+                bufs[k].pin = bufs[k].p = staging.alloc(chunk + 65536 + 64);
             } else {
-                cbufs[k].p = pinned(HEAD + ccap + 64);  // (handed to front as they are: pinned)
+                cbufs[k].p = staging.alloc(HEAD + ccap + 64);  // (handed to front as they are: pinned)
             }
         }
         BoundedQueue<int> q_cfree(NBUF + 1), q_cfull(NBUF + 1), q_free(NBUF + 1), q_full(NBUF + 1), q_done(FADEHIP_BAM_CHUNKS + 1);
@@ -1856,32 +1858,6 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
             abort_all = true;
             q_cfree.close(); q_cfull.close(); q_free.close(); q_full.close(); q_done.close(); q_write.close(); q_credit.close();
         };
-        // the members of buf[0, got): (offset, size, header length); stops in front of one that is not whole
-        struct Mem { size_t off, size, hl; uint32_t isz; };
-        auto scan_members = [&](const uint8_t *buf, size_t got, std::vector<Mem> &ms) -> size_t {
-            size_t w = 0;
-            ms.clear();
-            while (w + 18 <= got) {
-                const uint8_t *m = buf + w;
-                if (m[0] != 0x1f || m[1] != 0x8b) throw std::runtime_error("not a BGZF member in " + path);
-                const size_t xlen = (size_t)m[10] | ((size_t)m[11] << 8);
-                if (w + 12 + xlen > got) break;
-                size_t bs = 0;
-                for (size_t x = 12; x + 4 <= 12 + xlen;) {
-                    const size_t sl = (size_t)m[x + 2] | ((size_t)m[x + 3] << 8);
-                    if (m[x] == 'B' && m[x + 1] == 'C' && sl == 2 && x + 6 <= 12 + xlen) bs = ((size_t)m[x + 4] | ((size_t)m[x + 5] << 8)) + 1;
-                    x += 4 + sl;
-                }
-                if (bs < 12 + xlen + 10) throw std::runtime_error("BGZF member without a usable BC subfield in " + path);
-                if (w + bs > got) break;
-                uint32_t isz;
-                memcpy(&isz, m + bs - 4, 4);
-                if (isz > 65536) throw std::runtime_error("corrupt BGZF block (ISIZE beyond 64 KiB) in " + path);
-                ms.push_back(Mem{w, bs, 12 + xlen, isz});
-                w += bs;
-            }
-            return w;
-        };
         stages.th.emplace_back([&] {  // file reader
             try {
                 uint64_t at = coff;
@@ -1890,18 +1866,9 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
                 while (!eof && !abort_all && q_cfree.pop(k)) {
                     CBuf &c = cbufs[k];
                     ck_fread.start();
-                    size_t got = 0;
                     c.off = at;
-                    while (got < ccap) {
-                        const size_t want = (size_t)std::min<uint64_t>(ccap - got, read_end - at);
-                        const ssize_t r = want ? pread(fileno(f), c.p + HEAD + got, want, (off_t)at) : 0;
-                        if (r < 0) throw std::runtime_error("read error on " + path);
-                        if (r == 0) { eof = true; break; }
-                        got += (size_t)r;
-                        at += (uint64_t)r;
-                    }
+                    c.n = read_fill(fileno(f), c.p + HEAD, ccap, &at, read_end, &eof, path);
                     ck_fread.stop();
-                    c.n = got;
                     c.eof = eof;
                     q_cfull.push(k);
                 }
@@ -1912,26 +1879,21 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
         });
         stages.th.emplace_back([&] {  // members: cut (and, in host mode, inflated on the pool) into the calls' buffers
             try {
-                std::vector<uint8_t> tail;
+                MemberCutter cutter;
                 std::vector<Mem> ms;
                 int ck;
                 bool ended = false;
                 unsigned batch_no = 0;
                 while (!ended && !abort_all && q_cfull.pop(ck)) {
                     CBuf &c = cbufs[ck];
-                    if (tail.size() > HEAD) throw std::runtime_error("BGZF member larger than 64 KiB in " + path);
-                    uint8_t *cb = c.p + HEAD - tail.size();
-                    if (!tail.empty()) memcpy(cb, tail.data(), tail.size());
-                    const size_t got = tail.size() + c.n;
-                    const uint64_t cb_off = c.off - tail.size();  // file offset of cb[0]
-                    const size_t w = scan_members(cb, got, ms);
-                    tail.assign(cb + w, cb + got);
-                    if (c.eof && !tail.empty()) throw std::runtime_error("the file ends inside a BGZF member: " + path);
+                    const uint64_t cb_off = c.off - cutter.tail.size();  // file offset of cb[0]
+                    const MemberCutter::Cut cut = cutter.cut(c.p, HEAD, c.n, c.eof, ms, path);
+                    uint8_t *const cb = cut.cb;
                     ended = c.eof;
                     if (!host_inflate) {
                         // the compressed bytes go to the device as they lie; the buffer comes back when front is done with it
                         In in;
-                        in.p = cb; in.n = w; in.last = ended; in.cbuf = ck;
+                        in.p = cb; in.n = cut.w; in.last = ended; in.cbuf = ck;
                         int slot;
                         if (!q_free.pop(slot)) break;
                         bufs[slot] = in;
@@ -1942,8 +1904,8 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
                     size_t m0 = 0;
                     cbuf_refs[ck] = 1;  // (this thread's own hold on the compressed bytes)
                     do {
-                        size_t total = 0, m1 = m0;
-                        while (m1 < ms.size() && total + ms[m1].isz <= chunk) total += ms[m1++].isz;
+                        size_t total = 0;
+                        const size_t m1 = take_batch(ms, m0, chunk, &total);
                         int slot;
                         if (!q_free.pop(slot)) { ended = true; break; }
                         In &b = bufs[slot];
@@ -1961,38 +1923,10 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
                             m0 = m1;
                             continue;
                         }
-                        std::vector<size_t> ooff(m1 - m0 + 1, 0);
-                        for (size_t j = m0; j < m1; j++) ooff[j - m0 + 1] = ooff[j - m0] + ms[j].isz;
-                        std::atomic<bool> bad{false};
                         ck_inflate.start();
-                        pool.parallel_for((m1 - m0 + 1) / 2, [&](size_t t) {
-                            static thread_local std::unique_ptr<FastInflate> fi[2];
-                            if (!fi[0]) { fi[0].reset(new FastInflate()); fi[1].reset(new FastInflate()); }
-                            const uint8_t *src[2] = {nullptr, nullptr};
-                            size_t slen[2] = {0, 0}, jj[2] = {0, 0};
-                            int n = 0;
-                            for (size_t j = m0 + 2 * t; j < std::min(m1, m0 + 2 * t + 2); j++) {
-                                if (ms[j].isz == 0) {  // (an empty member must be one: hts_lite.hpp)
-                                    if (ms[j].size < ms[j].hl + 8 || !bgzf_empty_member_ok(cb + ms[j].off + ms[j].hl, ms[j].size - ms[j].hl - 8, cb + ms[j].off + ms[j].size - 8)) bad = true;
-                                    continue;
-                                }
-                                src[n] = cb + ms[j].off + ms[j].hl;
-                                slen[n] = ms[j].size - ms[j].hl - 8;
-                                jj[n++] = j;
-                            }
-                            if (n == 2) {
-                                if (!FastInflate::inflate2(*fi[0], src[0], slen[0], b.p + ooff[jj[0] - m0], ms[jj[0]].isz, *fi[1], src[1], slen[1], b.p + ooff[jj[1] - m0], ms[jj[1]].isz)) bad = true;
-                            } else if (n == 1) {
-                                if (!fi[0]->inflate(src[0], slen[0], b.p + ooff[jj[0] - m0], ms[jj[0]].isz)) bad = true;
-                            }
-                            for (int q = 0; q < n; q++) {  // the members' CRC32 (RFC 1952 trailer), as htslib checks it
-                                uint32_t crc;
-                                memcpy(&crc, cb + ms[jj[q]].off + ms[jj[q]].size - 8, 4);
-                                if (crc32_fast(0, b.p + ooff[jj[q] - m0], ms[jj[q]].isz) != crc) bad = true;
-                            }
-                        }, CPU_INFLATE);
+                        const bool inflated = inflate_batch(pool, cb, ms, m0, m1, b.p);
                         ck_inflate.stop();
-                        if (bad) throw std::runtime_error("BGZF block does not inflate to its ISIZE / CRC32 (corrupt input)");
+                        if (!inflated) throw std::runtime_error("BGZF block does not inflate to its ISIZE / CRC32 (corrupt input)");
                         // a lane's last member: only the bytes in front of the next lane's first record are this lane's
                         if (limited && m1 == ms.size() && m1 > m0 && cb_off + ms[m1 - 1].off == lane.range.coff_end) {
                             if (lane.range.end_rec > ms[m1 - 1].isz) throw std::runtime_error("lane range ends beyond its last block");
@@ -2022,10 +1956,7 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
         ck_upload.start();
         if (ctx_ready.get()) { fprintf(stderr, "[E::fade annotate] cannot open the GPU path: %s\n", create_err.c_str()); return 1; }
         // the buffers the reader has been filling become staging memory now
-        for (auto &rb : raw_bufs) {
-            if (fadehip_host_register(ctx, rb.first, rb.second)) { fprintf(stderr, "[E::fade annotate] %s\n", fadehip_last_error(ctx)); return 1; }
-            guard.pinned.push_back(rb.first);
-        }
+        if (!staging.pin(ctx)) { fprintf(stderr, "[E::fade annotate] %s\n", fadehip_last_error(ctx)); return 1; }
         if (genome.upload(ctx)) return 1;
         if (o.timing) genome.report();
         // the header goes out through the CPU writer (its members only: no end-of-file block yet; not a byte without a device)
@@ -2096,15 +2027,7 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
                     // the call's extract records (a few per cent of its bytes): framed here, compressed by the extract file's
                     // own writer on the pool — on this side of the pipeline, so that the front half never waits for it
                     try {
-                        xrecs.clear();
-                        for (size_t at_x = 0; at_x + 4 <= r.xn;) {
-                            uint32_t bs;
-                            memcpy(&bs, r.xp + at_x, 4);
-                            if (bs < 32 || at_x + 4 + bs > r.xn) throw std::runtime_error("the device's extract records are not whole");
-                            xrecs.emplace_back();
-                            xrecs.back().d.assign(r.xp + at_x + 4, r.xp + at_x + 4 + bs);
-                            at_x += 4 + (size_t)bs;
-                        }
+                        split_extract_records(r.xp, r.xn, xrecs);
                         xwriter->write(xrecs);
                     } catch (const std::exception &e) { set_err(e.what()); ok = false; abort_all = true; }
                 }
@@ -3065,19 +2988,7 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
             for (const Rec &r : first) first_names.push_back(r.qname());
         }
         // the member that holds the first record, and the record's offset in its payload
-        uint64_t at = 0, cum = 0;
-        for (;;) {
-            uint8_t h[18], t[4];
-            if (pread(fileno(f), h, 18, (off_t)at) != 18) return 1;
-            if (h[0] != 0x1f || h[1] != 0x8b || !(h[3] & 4) || h[12] != 'B' || h[13] != 'C') return 1;  // (other gzip subfields first: the host loop reads it)
-            const uint32_t bs = (uint32_t)(h[16] | (h[17] << 8)) + 1u;
-            if (pread(fileno(f), t, 4, (off_t)(at + bs - 4)) != 4) return 1;
-            const uint32_t isz = (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
-            if (cum + isz > hdr_bytes || (uint64_t)at + bs >= (uint64_t)sb.st_size) { coff = at; first_rec = (uint32_t)(hdr_bytes - cum); break; }
-            cum += isz;
-            at += bs;
-        }
-        if (first_rec > 65536) return 1;
+        if (!locate_first_record(fileno(f), (uint64_t)sb.st_size, hdr_bytes, &coff, &first_rec)) return 1;  // (other gzip subfields first, say: the host loop reads it)
     } catch (const std::exception &e) {
         return 1;  // the host loop reports what is wrong with the file
     }
@@ -3105,23 +3016,23 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
     fadehip_nameset *names = nullptr;
     fadehip_mateset *mates = nullptr;
     fadehip_recstore *store = nullptr;  // `fade extract --sorted`: the run's extract records, on the device
+    Staging staging;
     struct Guard {
         fadehip_ctx *&c;
         fadehip_bam_stream *&s;
         fadehip_nameset *&ns;
         fadehip_mateset *&ms;
         fadehip_recstore *&rs;
-        std::vector<void *> pinned, owned;
+        Staging &stg;
         ~Guard() {
             if (s) fadehip_bam_close(s);
             if (ns) fadehip_nameset_destroy(ns);
             if (ms) fadehip_mateset_destroy(ms);
             if (rs) fadehip_recstore_destroy(rs);
-            for (void *p : pinned) fadehip_host_free(c, p);
+            stg.unpin(c);
             if (c) fadehip_destroy(c);
-            for (void *p : owned) free(p);
         }
-    } guard{ctx, st, names, mates, store, {}, {}};
+    } guard{ctx, st, names, mates, store, staging};
     try {
         fadehip_params prm;
         fadehip_params_default(&prm);
@@ -3175,18 +3086,9 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
         const size_t ccap = host_inflate ? std::max<size_t>(chunk / 2, 1 << 20) : chunk, HEAD = 65536 + 64;
         constexpr int NBUF = 3;
         struct In { uint8_t *p = nullptr; size_t n = 0; bool last = false; int buf = -1; };
-        std::vector<std::pair<void *, size_t>> raw_bufs;  // (registered with the ctx once it is there)
-        auto staging = [&](size_t bytes) -> uint8_t * {
-            const size_t al = (size_t)1 << 21, n = (bytes + al - 1) & ~(al - 1);
-            void *q = aligned_alloc(al, n);
-            if (!q) throw std::runtime_error("out of memory");
-            guard.owned.push_back(q);
-            raw_bufs.emplace_back(q, n);
-            return (uint8_t *)q;
-        };
         uint8_t *bufs[NBUF];
         std::vector<uint8_t> own_comp;  // host inflate: the compressed bytes never cross PCIe
-        for (int k = 0; k < NBUF; k++) bufs[k] = staging(host_inflate ? chunk + 65536 + 64 : HEAD + ccap + 64);
+        for (int k = 0; k < NBUF; k++) bufs[k] = staging.alloc(host_inflate ? chunk + 65536 + 64 : HEAD + ccap + 64);
         if (host_inflate) own_comp.resize(HEAD + ccap + 64);
         // (the queues and the reader thread are made per pass over the file: --fragments makes two)
         std::unique_ptr<BoundedQueue<int>> q_free_p;
@@ -3196,31 +3098,6 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
         auto set_err = [&](const std::string &e) {
             std::lock_guard<std::mutex> l(err_m);
             if (stage_err.empty()) stage_err = e;
-        };
-        struct Mem { size_t off, size, hl; uint32_t isz; };
-        auto scan_members = [&](const uint8_t *buf, size_t got, std::vector<Mem> &ms) -> size_t {
-            size_t w = 0;
-            ms.clear();
-            while (w + 18 <= got) {
-                const uint8_t *m = buf + w;
-                if (m[0] != 0x1f || m[1] != 0x8b) throw std::runtime_error("not a BGZF member in " + path);
-                const size_t xlen = (size_t)m[10] | ((size_t)m[11] << 8);
-                if (w + 12 + xlen > got) break;
-                size_t bs = 0;
-                for (size_t x = 12; x + 4 <= 12 + xlen;) {
-                    const size_t sl = (size_t)m[x + 2] | ((size_t)m[x + 3] << 8);
-                    if (m[x] == 'B' && m[x + 1] == 'C' && sl == 2 && x + 6 <= 12 + xlen) bs = ((size_t)m[x + 4] | ((size_t)m[x + 5] << 8)) + 1;
-                    x += 4 + sl;
-                }
-                if (bs < 12 + xlen + 10) throw std::runtime_error("BGZF member without a usable BC subfield in " + path);
-                if (w + bs > got) break;
-                uint32_t isz;
-                memcpy(&isz, m + bs - 4, 4);
-                if (isz > 65536) throw std::runtime_error("corrupt BGZF block (ISIZE beyond 64 KiB) in " + path);
-                ms.push_back(Mem{w, bs, 12 + xlen, isz});
-                w += bs;
-            }
-            return w;
         };
         std::unique_ptr<StageThreads> stages_p;
         auto start_pass = [&] {
@@ -3237,57 +3114,28 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
             BoundedQueue<In> &q_full = *qu;
             try {
                 uint64_t at = coff;
-                std::vector<uint8_t> tail;
+                MemberCutter cutter;
                 std::vector<Mem> ms;
                 bool eof = false;
                 while (!eof) {
                     int k = -1;
                     if (!host_inflate && !q_free.pop(k)) break;
                     uint8_t *base = host_inflate ? own_comp.data() : bufs[k];
-                    if (tail.size() > HEAD) throw std::runtime_error("BGZF member larger than 64 KiB in " + path);
-                    uint8_t *cb = base + HEAD - tail.size();
-                    if (!tail.empty()) memcpy(cb, tail.data(), tail.size());
-                    size_t got = 0;
-                    while (got < ccap) {
-                        const ssize_t r = pread(fileno(f), base + HEAD + got, ccap - got, (off_t)at);
-                        if (r < 0) throw std::runtime_error("read error on " + path);
-                        if (r == 0) { eof = true; break; }
-                        got += (size_t)r;
-                        at += (uint64_t)r;
-                    }
-                    const size_t have = tail.size() + got;
-                    const size_t w = scan_members(cb, have, ms);
-                    tail.assign(cb + w, cb + have);
-                    if (eof && !tail.empty()) throw std::runtime_error("the file ends inside a BGZF member: " + path);
+                    const size_t got = read_fill(fileno(f), base + HEAD, ccap, &at, UINT64_MAX, &eof, path);
+                    const MemberCutter::Cut cut = cutter.cut(base, HEAD, got, eof, ms, path);
                     if (!host_inflate) {
                         In in;
-                        in.p = cb; in.n = w; in.last = eof; in.buf = k;
+                        in.p = cut.cb; in.n = cut.w; in.last = eof; in.buf = k;
                         q_full.push(in);
                         continue;
                     }
                     size_t m0 = 0;
                     do {  // batches of members whose payloads fill a staging buffer
-                        size_t total = 0, m1 = m0;
-                        while (m1 < ms.size() && total + ms[m1].isz <= chunk) total += ms[m1++].isz;
+                        size_t total = 0;
+                        const size_t m1 = take_batch(ms, m0, chunk, &total);
                         if (!q_free.pop(k)) return;
                         uint8_t *dst = bufs[k];
-                        std::vector<size_t> ooff(m1 - m0 + 1, 0);
-                        for (size_t j = m0; j < m1; j++) ooff[j - m0 + 1] = ooff[j - m0] + ms[j].isz;
-                        std::atomic<bool> bad{false};
-                        pool.parallel_for(m1 - m0, [&](size_t t) {
-                            static thread_local std::unique_ptr<FastInflate> fi;
-                            if (!fi) fi.reset(new FastInflate());
-                            const Mem &m = ms[m0 + t];
-                            if (m.isz == 0) {  // (an empty member must be one: hts_lite.hpp)
-                                if (m.size < m.hl + 8 || !bgzf_empty_member_ok(cb + m.off + m.hl, m.size - m.hl - 8, cb + m.off + m.size - 8)) bad = true;
-                                return;
-                            }
-                            if (!fi->inflate(cb + m.off + m.hl, m.size - m.hl - 8, dst + ooff[t], m.isz)) { bad = true; return; }
-                            uint32_t crc;  // the member's CRC32 (RFC 1952 trailer), as htslib checks it
-                            memcpy(&crc, cb + m.off + m.size - 8, 4);
-                            if (crc32_fast(0, dst + ooff[t], m.isz) != crc) bad = true;
-                        }, CPU_INFLATE);
-                        if (bad) throw std::runtime_error("BGZF block does not inflate to its ISIZE / CRC32 (corrupt input)");
+                        if (!inflate_batch(pool, cut.cb, ms, m0, m1, dst)) throw std::runtime_error("BGZF block does not inflate to its ISIZE / CRC32 (corrupt input)");
                         In in;
                         in.p = dst; in.n = total; in.last = eof && m1 == ms.size(); in.buf = k;
                         q_full.push(in);
@@ -3305,10 +3153,7 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
         Header out_hdr = hdr;
         out_hdr.add_pg("fade-extract", "fade", FADE_VERSION, cl);  // filter.d:173-180 / remap.d:18-26 (the reference reuses this ID)
         if (creating.get()) { fprintf(stderr, "[E::%s] cannot open the GPU path: %s\n", who, create_err.c_str()); return 1; }
-        for (auto &rb : raw_bufs) {
-            if (fadehip_host_register(ctx, rb.first, rb.second)) { fprintf(stderr, "[E::%s] %s\n", who, fadehip_last_error(ctx)); return 1; }
-            guard.pinned.push_back(rb.first);
-        }
+        if (!staging.pin(ctx)) { fprintf(stderr, "[E::%s] %s\n", who, fadehip_last_error(ctx)); return 1; }
         const OutFmt fmt = o.ubam ? OutFmt::UBAM : OutFmt::BAM;
         std::unique_ptr<Writer> xwriter;
         std::vector<Rec> xrecs;
@@ -3334,15 +3179,7 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
                 size_t xn = 0;
                 int64_t n_x = 0;
                 if (fadehip_bam_back_extract(st, &xp, &xn, &n_x)) throw std::runtime_error(fadehip_last_error(ctx));
-                xrecs.clear();
-                for (size_t at_x = 0; at_x + 4 <= xn;) {
-                    uint32_t bs;
-                    memcpy(&bs, xp + at_x, 4);
-                    if (bs < 32 || at_x + 4 + bs > xn) throw std::runtime_error("the device's extract records are not whole");
-                    xrecs.emplace_back();
-                    xrecs.back().d.assign(xp + at_x + 4, xp + at_x + 4 + bs);
-                    at_x += 4 + (size_t)bs;
-                }
+                split_extract_records(xp, xn, xrecs);
                 if (!xrecs.empty()) xwriter->write(xrecs);
             } else if (n && fwrite(p, 1, n, stdout) != n) throw std::runtime_error("write error on the output stream");
             ck_write.stop();
