@@ -209,6 +209,24 @@ int fadehip_recstore_count(fadehip_recstore* s, long* n_records, long* n_bytes);
 int fadehip_recstore_sort(fadehip_recstore* s);
 int fadehip_recstore_drain(fadehip_recstore* s, int flags, ulong max_payload, const(ubyte)** out_, size_t* out_bytes, long* n_records, fadehip_index_call* idx);
 void fadehip_recstore_destroy(fadehip_recstore* s);
+
+/// A set of genomic intervals on the device and the overlap query over it (what `bedtools subtract -A` against a RepeatMasker
+/// BED decides): intervals (chrom, start, end), chrom an index into the names given at create, 0-based half-open,
+/// 0 <= start < end <= 2^31 - 1, added in any order and sealed once; a query (chrom, qs, qe) of longs, which may be negative,
+/// hits iff qs < qe and an interval of that chrom shares a base with it.  A bad interval fails its add by index and adds nothing;
+/// load_bed is create + add in pieces + seal over a plain-text BED file (names in order of first appearance).
+struct fadehip_intervals;
+int fadehip_intervals_create(fadehip_ctx* ctx, int n_chrom, const(char*)* chrom_names, fadehip_intervals** out_);
+int fadehip_intervals_add(fadehip_intervals* s, long n, const(int)* chrom, const(long)* start, const(long)* end);
+int fadehip_intervals_seal(fadehip_intervals* s);
+int fadehip_intervals_count(fadehip_intervals* s, long* n_intervals, int* n_chrom);
+int fadehip_intervals_overlap_batch(fadehip_intervals* s, long n, const(int)* chrom, const(long)* start, const(long)* end, ubyte* hit);
+int fadehip_intervals_load_bed(fadehip_ctx* ctx, const(char)* path, fadehip_intervals** out_);
+void fadehip_intervals_destroy(fadehip_intervals* s);
+/// fadehip_report_batch's stats rows with two more columns, read_rpm and art_rpm: 1 where (rname, art_start, art_end) /
+/// (aln_rname, aln_start, aln_end), as the row prints them, overlap an interval of the sealed set
+int fadehip_report_batch_repeats(fadehip_ctx* ctx, int n, const(ubyte)* recs, const(long)* rec_off, int n_ref, const(char*)* ref_names,
+                                 fadehip_intervals* intervals, ubyte* out_, long out_cap, long* row_off);
 int fadehip_genome_upload(fadehip_ctx* ctx, int n_contigs, const(long)* lengths, const(ubyte*)* seqs);
 /// columns 2-5 of a .fai line: bases to take, file offset of the first base (of the uncompressed text), bases and bytes per line
 struct fadehip_fai_entry { long length, offset; int line_bases, line_width; }
@@ -271,6 +289,9 @@ int fadehip_bam_use_mateset(fadehip_bam_stream* st, fadehip_mateset* s);
 int fadehip_bam_mates(fadehip_bam_stream* st, long* n_fixed, long* n_ambiguous);
 /// the store of the same ctx a STORE_EXTRACT stream appends its extract records to; before the first front call
 int fadehip_bam_use_recstore(fadehip_bam_stream* st, fadehip_recstore* s);
+enum FADEHIP_BAM_REPORT_REPEATS = 65536;  /// ... with REPORT_STATS: the stats rows gain read_rpm and art_rpm against the attached set of intervals (fadehip_bam_use_intervals)
+/// the sealed set of the same ctx a REPORT_REPEATS stream queries; before the first front call
+int fadehip_bam_use_intervals(fadehip_bam_stream* st, fadehip_intervals* s);
 int fadehip_bam_prepare(fadehip_bam_stream* st, size_t call_bytes);
 int fadehip_bam_front(fadehip_bam_stream* st, const(void)* members, size_t n_bytes, int last);
 int fadehip_bam_front_raw(fadehip_bam_stream* st, const(void)* payload, size_t n_bytes, int last);

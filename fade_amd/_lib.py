@@ -43,6 +43,8 @@ EXPORTS = [
     "fadehip_bam_use_mateset", "fadehip_bam_mates",
     "fadehip_recstore_create", "fadehip_recstore_add_batch", "fadehip_recstore_count", "fadehip_recstore_sort", "fadehip_recstore_drain",
     "fadehip_recstore_destroy", "fadehip_bam_use_recstore",
+    "fadehip_intervals_create", "fadehip_intervals_add", "fadehip_intervals_seal", "fadehip_intervals_count", "fadehip_intervals_overlap_batch",
+    "fadehip_intervals_load_bed", "fadehip_intervals_destroy", "fadehip_report_batch_repeats", "fadehip_bam_use_intervals",
 ]
 BAM_STORED, BAM_NO_OUTPUT, BAM_CLIP, BAM_EXTRACT, BAM_EJECT, BAM_EJECT_GROUPS, BAM_FROM_TAGS = 1, 2, 4, 8, 16, 32, 64  # fadehip_bam_config.flags
 BAM_COLLECT_NAMES, BAM_EJECT_NAMED = 128, 256
@@ -51,6 +53,7 @@ BAM_REPORT_STATS, BAM_REPORT_CLIP = 1024, 2048  # ... and `which` of fadehip_rep
 BAM_INDEX = 4096  # every call leaves the .bai entries of the records it writes (fadehip_bam_back_index)
 BAM_COLLECT_MATES, BAM_FIX_MATES = 8192, 16384  # mate fields that follow the hard clip: a MateSet attached (fadehip_bam_use_mateset)
 BAM_STORE_EXTRACT = 32768  # with BAM_EXTRACT: the extract records go into a RecStore attached (fadehip_bam_use_recstore), not to the host
+BAM_REPORT_REPEATS = 65536  # with BAM_REPORT_STATS: the rows gain read_rpm and art_rpm against an IntervalSet attached (fadehip_bam_use_intervals)
 RECSTORE_RAW, RECSTORE_STORED, RECSTORE_INDEX = 1, 2, 4  # fadehip_recstore_drain's flags
 BGZF_BLOCK = 0xff00
 BGZF_LANES = 2
@@ -186,6 +189,16 @@ def load():
     L.fadehip_recstore_destroy.argtypes = [vp]
     L.fadehip_recstore_destroy.restype = None
     L.fadehip_bam_use_recstore.argtypes = [vp, vp]
+    L.fadehip_intervals_create.argtypes = [vp, i32, C.POINTER(C.c_char_p), C.POINTER(vp)]
+    L.fadehip_intervals_add.argtypes = [vp, i64, vp, vp, vp]
+    L.fadehip_intervals_seal.argtypes = [vp]
+    L.fadehip_intervals_count.argtypes = [vp, C.POINTER(i64), C.POINTER(i32)]
+    L.fadehip_intervals_overlap_batch.argtypes = [vp, i64, vp, vp, vp, vp]
+    L.fadehip_intervals_load_bed.argtypes = [vp, C.c_char_p, C.POINTER(vp)]
+    L.fadehip_intervals_destroy.argtypes = [vp]
+    L.fadehip_intervals_destroy.restype = None
+    L.fadehip_report_batch_repeats.argtypes = [vp, i32, vp, vp, i32, C.POINTER(C.c_char_p), vp, vp, i64, vp]
+    L.fadehip_bam_use_intervals.argtypes = [vp, vp]
     L.fadehip_bam_mates.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     L.fadehip_genome_upload.argtypes = [vp, i32, vp, vp]
     L.fadehip_genome_upload_fasta.argtypes = [vp, C.c_char_p, i32, C.POINTER(FaiEntry)]

@@ -188,6 +188,15 @@ class Context:
         """A store of BAM records on this context's device (fadehip_recstore_*): see RecStore."""
         return RecStore(self)
 
+    def intervalset(self, names):
+        """A set of genomic intervals resident on the device over the contigs `names` (fadehip_intervals_*):
+        IntervalSet.add / seal / overlaps / count."""
+        return IntervalSet(self, names)
+
+    def load_bed(self, path):
+        """A sealed IntervalSet of a BED file (fadehip_intervals_load_bed): plain text, names in order of first appearance."""
+        return IntervalSet(self, None, bed=path)
+
     def mateset(self):
         """A map resident on the device from (read name, segment) to where `fade out -c` leaves that record
         (fadehip_mateset_*): MateSet.add_batch / fix_batch / count."""
@@ -268,11 +277,14 @@ class Context:
         return self.tags_batch_packed(cat, off, ref_names)
 
     # ---- stats.d:75-186, noclip.d:17-73: the rows of `fade stats` / `fade stats-clip` over annotated records, written on the device
-    def report_batch_packed(self, recs, rec_off, ref_names, which, out_cap=None):
+    def report_batch_packed(self, recs, rec_off, ref_names, which, out_cap=None, repeats=None):
         """fadehip_report_batch: which is "stats" or "clip".  Returns (text, row_off): the TSV rows without a header line as
         bytes, and int64[2n + 1] offsets into them — slot 2k is record k's left side, 2k + 1 its right side, a slot without a
-        row takes no bytes.  out_cap: the bytes the rows may take (default: a bound from the records' bytes)."""
+        row takes no bytes.  out_cap: the bytes the rows may take (default: a bound from the records' bytes).  repeats (a sealed
+        IntervalSet; with "stats"): fadehip_report_batch_repeats — every row gains read_rpm and art_rpm."""
         flag = {"stats": _lib.BAM_REPORT_STATS, "clip": _lib.BAM_REPORT_CLIP}[which]
+        if repeats is not None and which != "stats":
+            raise ValueError('repeats goes with which="stats"')
         recs = np.ascontiguousarray(recs, dtype=np.uint8)
         rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
         n = len(rec_off) - 1
@@ -282,20 +294,25 @@ class Context:
         arr = (C.c_char_p * max(len(names), 1))(*names)
         out = np.zeros(int(out_cap), np.uint8)
         row_off = np.zeros(2 * max(n, 0) + 1, np.int64)
-        self._chk(self._L.fadehip_report_batch(self._h, flag, n, recs.ctypes.data if recs.nbytes else None, rec_off.ctypes.data, len(names), arr,
-                                               out.ctypes.data if out_cap else None, int(out_cap), row_off.ctypes.data))
+        if repeats is not None:
+            self._chk(self._L.fadehip_report_batch_repeats(self._h, n, recs.ctypes.data if recs.nbytes else None, rec_off.ctypes.data, len(names), arr, repeats._h,
+                                                           out.ctypes.data if out_cap else None, int(out_cap), row_off.ctypes.data))
+        else:
+            self._chk(self._L.fadehip_report_batch(self._h, flag, n, recs.ctypes.data if recs.nbytes else None, rec_off.ctypes.data, len(names), arr,
+                                                   out.ctypes.data if out_cap else None, int(out_cap), row_off.ctypes.data))
         return out[:row_off[-1]].tobytes(), row_off
 
-    def report_batch(self, records, ref_names, which):
+    def report_batch(self, records, ref_names, which, repeats=None):
         """report_batch_packed over BAM records given as a list of bytes (block_size first).  which: "stats" or "clip" gives
-        the report's rows as bytes; "both" gives the pair (stats, clip), each what the call for it alone gives."""
+        the report's rows as bytes; "both" gives the pair (stats, clip), each what the call for it alone gives.  repeats (a
+        sealed IntervalSet): the stats rows gain read_rpm and art_rpm; the clip rows stay as they are."""
         rb = [bytes(r) for r in records]
         off = np.zeros(len(rb) + 1, dtype=np.int64)
         np.cumsum([len(r) for r in rb], out=off[1:])
         cat = np.frombuffer(b"".join(rb), dtype=np.uint8) if off[-1] else np.zeros(0, np.uint8)
         if which == "both":
-            return tuple(self.report_batch_packed(cat, off, ref_names, w)[0] for w in ("stats", "clip"))
-        return self.report_batch_packed(cat, off, ref_names, which)[0]
+            return tuple(self.report_batch_packed(cat, off, ref_names, w, repeats=repeats if w == "stats" else None)[0] for w in ("stats", "clip"))
+        return self.report_batch_packed(cat, off, ref_names, which, repeats=repeats)[0]
 
     def coord_order_batch(self, recs, rec_off):
         """fadehip_coord_order_batch: the stable coordinate order of BAM records (recs: uint8, concatenated; rec_off: n + 1
@@ -532,7 +549,7 @@ class Context:
         return self.bgzf_deflate_wait(lane)
 
     def bam_stream(self, ref_names, floor_len=5, window=300, first_record=0, stored=False, tail_trim=0, no_output=False, clip=False, extract=False, eject=None, from_tags=False,
-                   collect_names=None, eject_named=None, keep_sorted=False, report=None, index=False, collect_mates=None, fix_mates=False, mateset=None, recstore=None):
+                   collect_names=None, eject_named=None, keep_sorted=False, report=None, index=False, collect_mates=None, fix_mates=False, mateset=None, recstore=None, repeats=None):
         """The file path on the device (fadehip_bam_*): BGZF members of a BAM's records in, BGZF members of the annotated
         records out.  ref_names: the BAM header's contigs (the genome must be uploaded).  clip: records called artifacts leave
         hard-clipped (`fade annotate -c`).  extract: every call also builds `fade extract`'s records of its artifact calls
@@ -561,9 +578,11 @@ class Context:
         this context; with extract, wherever extract stands): the calls' extract records stay on the device, appended to the
         store in stream order — back_extract() then gives no bytes and the number of records the call added — to be sorted
         and drained once the stream has ended (`fade extract --sorted`, `fade annotate --extract-sorted`).  True instead of a
-        store sets the flag alone (the first front() then fails)."""
+        store sets the flag alone (the first front() then fails).  repeats (a sealed IntervalSet of this context; with
+        report "stats" or "both"): the stats rows gain read_rpm and art_rpm (`fade stats --repeats`).  True instead of a set
+        sets the flag alone (the first front() then fails)."""
         return BamStream(self, ref_names, floor_len, window, first_record, stored, tail_trim, no_output, clip, extract, eject, from_tags,
-                         collect_names, eject_named, keep_sorted, report, index, collect_mates, fix_mates, mateset, recstore)
+                         collect_names, eject_named, keep_sorted, report, index, collect_mates, fix_mates, mateset, recstore, repeats)
 
     def bgzf_inflate(self, members, out_cap=None):
         """Whole BGZF members (bytes / uint8 array) -> their payloads, inflated on the device (CRC32 and ISIZE checked)."""
@@ -747,7 +766,7 @@ def format_tags(batch, contig_names, rs, aln):
 
 class BamStream:
     def __init__(self, ctx, ref_names, floor_len, window, first_record, stored=False, tail_trim=0, no_output=False, clip=False, extract=False, eject=None, from_tags=False,
-                 collect_names=None, eject_named=None, keep_sorted=False, report=None, index=False, collect_mates=None, fix_mates=False, mateset=None, recstore=None):
+                 collect_names=None, eject_named=None, keep_sorted=False, report=None, index=False, collect_mates=None, fix_mates=False, mateset=None, recstore=None, repeats=None):
         self._ctx, self._L = ctx, ctx._L
         if report not in (None, "stats", "clip", "both"):
             raise ValueError('report is None, "stats", "clip" or "both"')
@@ -759,7 +778,8 @@ class BamStream:
         arr = (C.c_char_p * max(len(names), 1))(*names)
         cfg = _lib.BamConfig(floor_len, window, len(names), (_lib.BAM_STORED if stored else 0) | (_lib.BAM_NO_OUTPUT if no_output else 0) | (_lib.BAM_CLIP if clip else 0) | (_lib.BAM_EXTRACT if extract else 0) | (BAM_FROM_TAGS if from_tags else 0) | ej |
                              (_lib.BAM_COLLECT_NAMES if collect_names else 0) | (_lib.BAM_EJECT_NAMED if eject_named else 0) | (_lib.BAM_KEEP_SORTED if keep_sorted else 0) | rp | (_lib.BAM_INDEX if index else 0) |
-                             (_lib.BAM_COLLECT_MATES if collect_mates else 0) | (_lib.BAM_FIX_MATES if fix_mates else 0) | (_lib.BAM_STORE_EXTRACT if recstore else 0), arr, first_record, tail_trim)
+                             (_lib.BAM_COLLECT_MATES if collect_mates else 0) | (_lib.BAM_FIX_MATES if fix_mates else 0) | (_lib.BAM_STORE_EXTRACT if recstore else 0) |
+                             (_lib.BAM_REPORT_REPEATS if repeats else 0), arr, first_record, tail_trim)
         h = C.c_void_p()
         ctx._chk(self._L.fadehip_bam_open(ctx._h, C.byref(cfg), C.byref(h)))
         self._h = h
@@ -786,6 +806,13 @@ class BamStream:
                 self.close()
                 ctx._chk(rc)
             self._recstore = recstore  # (the store outlives the stream)
+        self._repeats = None
+        if isinstance(repeats, IntervalSet):
+            rc = self._L.fadehip_bam_use_intervals(self._h, repeats._h)
+            if rc:
+                self.close()
+                ctx._chk(rc)
+            self._repeats = repeats  # (the set outlives the stream)
 
     def prepare(self, call_bytes):
         """fadehip_bam_prepare: the streams and buffers of calls of call_bytes inflated bytes, made ahead of the first call."""
@@ -962,6 +989,58 @@ class RecStore:
     def close(self):
         if self._h:
             self._L.fadehip_recstore_destroy(self._h)
+            self._h = None
+
+
+class IntervalSet:
+    """Context.intervalset(names) / Context.load_bed(path): genomic intervals on the device (fadehip_intervals_*).  An interval
+    is (chrom, start, end): chrom an index into names, start and end 0-based half-open, 0 <= start < end <= 2^31 - 1.  add()
+    any number of times, in any order; seal() sorts once; overlaps() then answers queries — 1 where the set holds an interval
+    of the query's chrom that shares at least one base with [start, end)."""
+
+    def __init__(self, ctx, names, bed=None):
+        self._ctx, self._L = ctx, ctx._L
+        h = C.c_void_p()
+        if bed is not None:
+            ctx._chk(self._L.fadehip_intervals_load_bed(ctx._h, os.fsencode(bed), C.byref(h)))
+        else:
+            nb = [x.encode() if isinstance(x, str) else bytes(x) for x in names]
+            arr = (C.c_char_p * max(len(nb), 1))(*nb)
+            ctx._chk(self._L.fadehip_intervals_create(ctx._h, len(nb), arr, C.byref(h)))
+        self._h = h
+
+    @staticmethod
+    def _arrays(chrom, start, end):
+        chrom = np.ascontiguousarray(chrom, dtype=np.int32)
+        start = np.ascontiguousarray(start, dtype=np.int64)
+        end = np.ascontiguousarray(end, dtype=np.int64)
+        if not len(chrom) == len(start) == len(end):
+            raise ValueError("chrom, start and end hold one entry each per interval")
+        return chrom, start, end
+
+    def add(self, chrom, start, end):
+        chrom, start, end = self._arrays(chrom, start, end)
+        self._ctx._chk(self._L.fadehip_intervals_add(self._h, len(chrom), chrom.ctypes.data, start.ctypes.data, end.ctypes.data))
+
+    def seal(self):
+        self._ctx._chk(self._L.fadehip_intervals_seal(self._h))
+
+    def overlaps(self, chrom, start, end):
+        """uint8[n]: 1 where the query (chrom[k], start[k], end[k]) hits.  start and end are int64 and may be negative."""
+        chrom, start, end = self._arrays(chrom, start, end)
+        hit = np.zeros(len(chrom), dtype=np.uint8)
+        self._ctx._chk(self._L.fadehip_intervals_overlap_batch(self._h, len(chrom), chrom.ctypes.data, start.ctypes.data, end.ctypes.data, hit.ctypes.data))
+        return hit
+
+    def count(self):
+        """(intervals, contig names) of the set."""
+        n, c = C.c_int64(0), C.c_int32(0)
+        self._ctx._chk(self._L.fadehip_intervals_count(self._h, C.byref(n), C.byref(c)))
+        return int(n.value), int(c.value)
+
+    def close(self):
+        if self._h:
+            self._L.fadehip_intervals_destroy(self._h)
             self._h = None
 
 

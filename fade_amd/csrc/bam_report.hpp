@@ -11,6 +11,7 @@
 //                         descriptor per row, the stats sides counted by the five row classes of fadehip_sw_stats_batch
 //   report_bucket_kernel  thread per slot: the stats sides' StatsWork, class behind class
 //   sw_stats_kernel<R>    (sw_stats.hpp, unchanged) one launch per class that has sides
+//   report_repeats_kernel (bam_intervals.hpp; only with a set of intervals attached) thread per slot: the two repeat-overlap bits
 //   report_size_kernel    sixteen lanes per slot: the sums of the qualities and ab bytes, the row's exact bytes
 //   report_scan_kernel    one block: the rows' offsets in slot order, their total (scan_block_sums)
 //   report_write_kernel   sixteen lanes per slot: the row
@@ -293,7 +294,9 @@ __device__ __forceinline__ uint64_t sum16(uint64_t v) {
     return v;
 }
 
-__device__ __forceinline__ void stats_row(const RepArgs &a, const RecHdr &r, const StatsRow &w, const fadehip_sw_stats_result &res, RowSink &s) {
+// RPM: the row ends with the two repeat-overlap columns (bam_intervals.hpp), bit 0 and bit 1 of `rpm`; <false> is the row as it was
+template <bool RPM>
+__device__ __forceinline__ void stats_row(const RepArgs &a, const RecHdr &r, const StatsRow &w, const fadehip_sw_stats_result &res, RowSink &s, uint32_t rpm) {
     s.bytes(r.p + 36u, r.lname - 1u);
     s.put('\t');
     s.bytes(a.names.bytes + a.names.off[r.tid], a.names.off[r.tid + 1] - a.names.off[r.tid]);
@@ -340,6 +343,12 @@ __device__ __forceinline__ void stats_row(const RepArgs &a, const RecHdr &r, con
     s.dec(w.rs);
     s.put('\t');
     s.put((r.flag & 16u) ? '+' : '-');
+    if constexpr (RPM) {
+        s.put('\t');
+        s.put((uint8_t)('0' + (rpm & 1u)));
+        s.put('\t');
+        s.put((uint8_t)('0' + ((rpm >> 1) & 1u)));
+    }
     s.put('\n');
 }
 
@@ -367,8 +376,10 @@ __device__ __forceinline__ void clip_row(const RecHdr &r, const ClipRow &c, uint
     s.put('\n');
 }
 
-// sixteen lanes per slot: the qualities and the ab bytes summed where they are read, then the row counted
-__global__ __launch_bounds__(256) void report_size_kernel(RepArgs a, uint32_t w) {
+// sixteen lanes per slot: the qualities and the ab bytes summed where they are read, then the row counted.  <true>: a stats
+// row carries the two columns of rpm [2n] (report_repeats_kernel's); <false> never looks at rpm
+template <bool RPM>
+__global__ __launch_bounds__(256) void report_size_kernel(RepArgs a, uint32_t w, const uint8_t *rpm) {
     const size_t ns = 2 * (size_t)a.n, s = (size_t)blockIdx.x * 16u + (threadIdx.x >> 4);
     const uint32_t sl = threadIdx.x & 15u;
     const bool on = s < ns && a.kind[w][s];
@@ -406,7 +417,7 @@ __global__ __launch_bounds__(256) void report_size_kernel(RepArgs a, uint32_t w)
         StatsRow v = row;
         v.qsum = qs;
         v.bsum = (uint32_t)ps;
-        stats_row(a, r, v, a.res[s], sink);
+        stats_row<RPM>(a, r, v, a.res[s], sink, RPM ? (uint32_t)rpm[s] : 0u);
     } else {
         ClipRow &row = a.crow[s];
         if (sl == 0u) {
@@ -429,7 +440,8 @@ __global__ __launch_bounds__(1024) void report_scan_kernel(RepArgs a, uint32_t w
     if (threadIdx.x == 0) off[ns] = a.ctl->total[w];
 }
 
-__global__ __launch_bounds__(256) void report_write_kernel(RepArgs a, uint32_t w) {
+template <bool RPM>
+__global__ __launch_bounds__(256) void report_write_kernel(RepArgs a, uint32_t w, const uint8_t *rpm) {
     const size_t ns = 2 * (size_t)a.n, s = (size_t)blockIdx.x * 16u + (threadIdx.x >> 4);
     if (s >= ns || !a.kind[w][s]) return;
     const RecHdr r = rec_header(rep_rec(a, (uint32_t)(s >> 1)));
@@ -437,7 +449,7 @@ __global__ __launch_bounds__(256) void report_write_kernel(RepArgs a, uint32_t w
     sink.d = a.out[w] + a.row_off[w][s];
     sink.n = 0;
     sink.sl = threadIdx.x & 15u;
-    if (w == 0u) stats_row(a, r, a.srow[s], a.res[s], sink);
+    if (w == 0u) stats_row<RPM>(a, r, a.srow[s], a.res[s], sink, RPM ? (uint32_t)rpm[s] : 0u);
     else clip_row(r, a.crow[s], (uint32_t)(s & 1u), sink);
 }
 

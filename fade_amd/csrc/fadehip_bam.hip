@@ -11,8 +11,10 @@
 #include "bam_resort.hpp"
 #include "bam_index.hpp"
 #include "bam_recstore.hpp"
+#include "bam_intervals.hpp"
 #include "host/bai_build.hpp"
 #include "host/recstore_host.hpp"
+#include "host/bed_lite.hpp"
 #include <algorithm>
 #include <chrono>
 #include <condition_variable>
@@ -71,6 +73,23 @@ struct fadehip_recstore {
     bam::IndexCtl ixc;                // a drain's index ctl as it crosses (a member: the copy may outlive a call that fails)
     PinBuf h_out;                     // what a drain hands out: the raw records or the members
     std::vector<uint8_t> h_ix;        // the arrays *idx points into, until the next drain
+};
+
+// A set of intervals on the device (bam_intervals.hpp).  The host's part: the contigs' names and their ids, the raw items
+// as add brought them (exact numbers: a call's items count only once its key kernel has found no bad interval), growth, and
+// behind seal the three sealed arrays and the names on the device — from then on nothing of the set changes, so the kernels
+// that read it (the overlap query, the report's on any stream) take no lock.
+struct fadehip_intervals {
+    fadehip_ctx *ctx = nullptr;
+    std::mutex mu;
+    std::vector<std::string> names;
+    std::map<std::string, int32_t> ids;
+    DevBuf key, end32, idx;            // the raw items
+    uint64_t first_cap = 0, cap = 0, n = 0;  // FADEHIP_INTERVALS_CAP; items the arrays hold; items added
+    bool sealed = false;
+    DevBuf start, maxend, chrom_first;  // sealed
+    DevBuf name_bytes, name_off;        // sealed: the names as report_repeats_kernel looks them up
+    DevBuf stage;                       // a call's arrays on the device (add, overlap_batch)
 };
 
 namespace {
@@ -546,8 +565,8 @@ int report_bad(fadehip_ctx *ctx, unsigned long long bad, long long first_record)
 
 // The arrays of a call's reports (`which`: RP_* bits) over n records, one behind the other from `base` (nullptr: only their
 // size is wanted): ctl | per report: row_off [2n + 1] u64 | size [2n] u64 | the rows' descriptors [2n] | (stats) work [2n] | res [2n] |
-// kind [2n] u8, padded
-size_t report_layout(bam::RepArgs &a, uint8_t *base, size_t n, uint32_t which) {
+// kind [2n] u8, padded; with `rpm` (a set of intervals attached) the stats report's repeat bits [2n] u8 behind its kind
+size_t report_layout(bam::RepArgs &a, uint8_t *base, size_t n, uint32_t which, uint8_t **rpm = nullptr) {
     const size_t ns = 2 * n;
     size_t at = 128;
     auto take = [&](size_t bytes) {
@@ -568,13 +587,15 @@ size_t report_layout(bam::RepArgs &a, uint8_t *base, size_t n, uint32_t which) {
             a.crow = (bam::ClipRow *)take(ns * sizeof(bam::ClipRow));
         }
         a.kind[w] = take(ns);
+        if (w == 0u && rpm) *rpm = take(ns);
     }
     return at + 8;
 }
 
 // The kernels of one report (w: 0 stats, 1 clip) behind the stage, whose ctl `c` is on the host: the stats sides' pairs and
-// their alignments class by class, the rows' sizes, the scan.  `scratch` holds the multi-strip pairs' rows.
-int enqueue_report_sizes(fadehip_ctx *ctx, hipStream_t st, bam::RepArgs &a, uint32_t w, const bam::RepCtl &c, DevBuf &scratch) {
+// their alignments class by class, the rows' sizes, the scan.  `scratch` holds the multi-strip pairs' rows.  With rpm (the
+// repeat bits report_repeats_kernel left) the stats rows are sized with their two more columns.
+int enqueue_report_sizes(fadehip_ctx *ctx, hipStream_t st, bam::RepArgs &a, uint32_t w, const bam::RepCtl &c, DevBuf &scratch, const uint8_t *rpm = nullptr) {
     const size_t ns = 2 * (size_t)a.n;
     if (w == 0u) {
         size_t cls_begin[6] = {0, 0, 0, 0, 0, 0};
@@ -595,18 +616,52 @@ int enqueue_report_sizes(fadehip_ctx *ctx, hipStream_t st, bam::RepArgs &a, uint
             if ((rc = enqueue_sw_stats(ctx, st, a.work, cls_begin, a.base, a.base, a.res, scratch.p, (int)c.long_max_lr, long_blocks, sc))) return rc;
         }
     }
-    hipLaunchKernelGGL(bam::report_size_kernel, dim3((unsigned)((ns + 15) / 16)), dim3(256), 0, st, a, w);
+    if (rpm && w == 0u) hipLaunchKernelGGL((bam::report_size_kernel<true>), dim3((unsigned)((ns + 15) / 16)), dim3(256), 0, st, a, w, rpm);
+    else hipLaunchKernelGGL((bam::report_size_kernel<false>), dim3((unsigned)((ns + 15) / 16)), dim3(256), 0, st, a, w, (const uint8_t *)nullptr);
     HIPCHK(ctx, hipGetLastError());
     hipLaunchKernelGGL(bam::report_scan_kernel, dim3(1), dim3(1024), 0, st, a, w);
     HIPCHK(ctx, hipGetLastError());
     return 0;
 }
 
-}  // namespace
+// the sealed set as the kernels read it
+bam::IvSetRef intervals_ref(const fadehip_intervals *s) {
+    bam::IvSetRef r;
+    r.start = (const uint32_t *)s->start.p;
+    r.maxend = (const uint64_t *)s->maxend.p;
+    r.chrom_first = (const uint32_t *)s->chrom_first.p;
+    r.n = (uint32_t)s->n;
+    r.n_chrom = (int32_t)s->names.size();
+    return r;
+}
 
-int fadehip_report_batch(fadehip_ctx *ctx, int32_t which, int32_t n, const uint8_t *recs, const int64_t *rec_off, int32_t n_ref,
-                         const char *const *ref_names, uint8_t *out, int64_t out_cap, int64_t *row_off) {
-    if (!ctx) return set_err(nullptr, FADEHIP_E_INVALID, "ctx is NULL");
+// ref_chrom: for every contig of a header the set's chrom id of that name, by its bytes, or -1
+std::vector<int32_t> intervals_ref_chrom(const fadehip_intervals *s, int32_t n_ref, const char *const *ref_names) {
+    std::vector<int32_t> rc((size_t)n_ref + 1, -1);
+    for (int32_t c = 0; c < n_ref; c++) {
+        const auto it = s->ids.find(ref_names[c]);
+        if (it != s->ids.end()) rc[(size_t)c] = it->second;
+    }
+    return rc;
+}
+
+// report_repeats_kernel behind the stage: the two bits of every slot into rpm
+int enqueue_report_repeats(fadehip_ctx *ctx, hipStream_t st, const bam::RepArgs &a, const fadehip_intervals *iv, const int32_t *d_ref_chrom, uint8_t *rpm) {
+    bam::RepeatArgs q;
+    q.s = intervals_ref(iv);
+    q.ref_chrom = d_ref_chrom;
+    q.name_bytes = (const uint8_t *)iv->name_bytes.p;
+    q.name_off = (const uint32_t *)iv->name_off.p;
+    q.rpm = rpm;
+    const size_t ns = 2 * (size_t)a.n;
+    hipLaunchKernelGGL(bam::report_repeats_kernel, dim3((unsigned)((ns + bam::TAG_BLOCK - 1) / bam::TAG_BLOCK)), dim3(bam::TAG_BLOCK), 0, st, a, q);
+    HIPCHK(ctx, hipGetLastError());
+    return 0;
+}
+
+// fadehip_report_batch, and with a set of intervals fadehip_report_batch_repeats
+int report_batch_impl(fadehip_ctx *ctx, int32_t which, int32_t n, const uint8_t *recs, const int64_t *rec_off, int32_t n_ref, const char *const *ref_names,
+                      fadehip_intervals *iv, uint8_t *out, int64_t out_cap, int64_t *row_off) {
     if (which != FADEHIP_BAM_REPORT_STATS && which != FADEHIP_BAM_REPORT_CLIP)
         return set_err(ctx, FADEHIP_E_INVALID, "which must be FADEHIP_BAM_REPORT_STATS or FADEHIP_BAM_REPORT_CLIP");
     if (n < 0 || n > (1 << 30) || n_ref < 0 || (n_ref > 0 && !ref_names) || !rec_off || !row_off || (n > 0 && !recs) || out_cap < 0 || (out_cap > 0 && !out))
@@ -637,19 +692,22 @@ int fadehip_report_batch(fadehip_ctx *ctx, int32_t which, int32_t n, const uint8
     BatchLane &L = ctx->batch;
     std::lock_guard<std::mutex> lk(L.mu);
     // meta: in_off [n + 1] u64 | name_off [n_ref + 1] u32 | first [n_ref] i32 | name bytes;  work: report_layout
+    // (with a set: ref_chrom [n_ref] i32 behind the name bytes, and the repeat bits in work)
     const size_t m_noff = 8 * ((size_t)n + 1), m_first = m_noff + 4 * ((size_t)n_ref + 1), m_names = m_first + 4 * (size_t)n_ref;
+    const size_t m_refc = (m_names + nbytes.size() + 7) & ~(size_t)7, m_end = iv ? m_refc + 4 * ((size_t)n_ref + 1) : m_names + nbytes.size();
     bam::RepArgs a;
     memset(&a, 0, sizeof a);
     a.which = w == 0u ? bam::RP_STATS : bam::RP_CLIP;
+    uint8_t *rpm = nullptr;
     std::vector<uint64_t> off;
-    if ((rc = batch_upload(ctx, L, n, recs, rec_off, nullptr, 0, m_names + nbytes.size() + 8, report_layout(a, nullptr, (size_t)n, a.which), off))) return rc;
+    if ((rc = batch_upload(ctx, L, n, recs, rec_off, nullptr, 0, m_end + 8, report_layout(a, nullptr, (size_t)n, a.which, iv ? &rpm : nullptr), off))) return rc;
     hipStream_t st = L.stream;
     uint8_t *meta = (uint8_t *)L.meta.p, *work = (uint8_t *)L.work.p;
     HIPCHK(ctx, hipMemcpyAsync(meta + m_noff, noff.data(), 4 * noff.size(), hipMemcpyHostToDevice, st));
     if (n_ref) HIPCHK(ctx, hipMemcpyAsync(meta + m_first, first.data(), 4 * (size_t)n_ref, hipMemcpyHostToDevice, st));
     if (!nbytes.empty()) HIPCHK(ctx, hipMemcpyAsync(meta + m_names, nbytes.data(), nbytes.size(), hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipMemsetAsync(work, 0, 128, st));
-    report_layout(a, work, (size_t)n, a.which);
+    report_layout(a, work, (size_t)n, a.which, iv ? &rpm : nullptr);
     a.base = (const uint8_t *)L.in.p;
     a.off64 = (const uint64_t *)meta;
     a.n = (uint32_t)n;
@@ -659,11 +717,17 @@ int fadehip_report_batch(fadehip_ctx *ctx, int32_t which, int32_t n, const uint8
     a.names.n_ref = n_ref;
     hipLaunchKernelGGL(bam::report_stage_kernel, dim3((unsigned)ntb), dim3(bam::TAG_BLOCK), 0, st, a);
     HIPCHK(ctx, hipGetLastError());
+    std::vector<int32_t> refc;  // (lives to the first wait)
+    if (iv) {
+        refc = intervals_ref_chrom(iv, n_ref, ref_names);
+        HIPCHK(ctx, hipMemcpyAsync(meta + m_refc, refc.data(), 4 * refc.size(), hipMemcpyHostToDevice, st));
+        if ((rc = enqueue_report_repeats(ctx, st, a, iv, (const int32_t *)(meta + m_refc), rpm))) return rc;
+    }
     bam::RepCtl c;
     HIPCHK(ctx, hipMemcpyAsync(&c, a.ctl, sizeof c, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));  // wait 1: what fails the call, the stats sides per class
     if (c.bad) return report_bad(ctx, c.bad, 0);
-    if ((rc = enqueue_report_sizes(ctx, st, a, w, c, L.scratch))) return rc;
+    if ((rc = enqueue_report_sizes(ctx, st, a, w, c, L.scratch, rpm))) return rc;
     std::vector<uint64_t> roff(ns + 1);
     HIPCHK(ctx, hipMemcpyAsync(roff.data(), a.row_off[w], 8 * (ns + 1), hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));  // wait 2: the rows' offsets
@@ -674,11 +738,29 @@ int fadehip_report_batch(fadehip_ctx *ctx, int32_t which, int32_t n, const uint8
     if (!total) return 0;
     if ((rc = reserve(ctx, L.out, (size_t)total + 8))) return rc;
     a.out[w] = (uint8_t *)L.out.p;
-    hipLaunchKernelGGL(bam::report_write_kernel, dim3((unsigned)((ns + 15) / 16)), dim3(256), 0, st, a, w);
+    if (rpm) hipLaunchKernelGGL((bam::report_write_kernel<true>), dim3((unsigned)((ns + 15) / 16)), dim3(256), 0, st, a, w, (const uint8_t *)rpm);
+    else hipLaunchKernelGGL((bam::report_write_kernel<false>), dim3((unsigned)((ns + 15) / 16)), dim3(256), 0, st, a, w, (const uint8_t *)nullptr);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(out, a.out[w], (size_t)total, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));  // wait 3: the rows
     return 0;
+}
+
+}  // namespace
+
+int fadehip_report_batch(fadehip_ctx *ctx, int32_t which, int32_t n, const uint8_t *recs, const int64_t *rec_off, int32_t n_ref,
+                         const char *const *ref_names, uint8_t *out, int64_t out_cap, int64_t *row_off) {
+    if (!ctx) return set_err(nullptr, FADEHIP_E_INVALID, "ctx is NULL");
+    return report_batch_impl(ctx, which, n, recs, rec_off, n_ref, ref_names, nullptr, out, out_cap, row_off);
+}
+
+int fadehip_report_batch_repeats(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const int64_t *rec_off, int32_t n_ref, const char *const *ref_names,
+                                 fadehip_intervals *iv, uint8_t *out, int64_t out_cap, int64_t *row_off) {
+    if (!ctx) return set_err(nullptr, FADEHIP_E_INVALID, "ctx is NULL");
+    if (!iv) return set_err(ctx, FADEHIP_E_INVALID, "intervals is NULL");
+    if (iv->ctx != ctx) return set_err(ctx, FADEHIP_E_INVALID, "report: the set of intervals belongs to another ctx");
+    if (!iv->sealed) return set_err(ctx, FADEHIP_E_INVALID, "report: the set of intervals has not been sealed (fadehip_intervals_seal)");
+    return report_batch_impl(ctx, FADEHIP_BAM_REPORT_STATS, n, recs, rec_off, n_ref, ref_names, iv, out, out_cap, row_off);
 }
 
 // ---- the name set over records the caller brings: bam_names.hpp's kernels, the ones of the file path under
@@ -937,6 +1019,10 @@ struct fadehip_bam_stream {
     fadehip_mateset *mates = nullptr;  // fadehip_bam_use_mateset
     bool store_extract = false;  // FADEHIP_BAM_STORE_EXTRACT: extract, and the calls' extract records stay on the device, in `recstore` (bam_recstore.hpp)
     fadehip_recstore *recstore = nullptr;  // fadehip_bam_use_recstore
+    bool repeats = false;        // FADEHIP_BAM_REPORT_REPEATS: the stats rows gain read_rpm and art_rpm (bam_intervals.hpp)
+    fadehip_intervals *intervals = nullptr;  // fadehip_bam_use_intervals
+    std::vector<std::string> ref_names_h;    // the header's contigs as the caller named them (ref_chrom is made of them)
+    DevBuf ref_chrom;            // repeats: the set's chrom id of every contig of the header
     DevBuf names_text, names_off;
     DevBuf names_first;         // from_tags: for every contig the first one of its name (fadehip_tags_batch's rule)
     struct Out {
@@ -985,6 +1071,7 @@ struct fadehip_bam_stream {
         DevBuf rp, rp_scratch;                // report: the arrays of report_layout; sw_stats_kernel's rows of its multi-strip pairs
         PinBuf h_rp;                          // the RepCtl behind the stage, then behind the scans
         bam::RepArgs rpa;
+        uint8_t *rpm = nullptr;               // report with a set of intervals attached: the stats slots' repeat bits (in rp)
         bam::TagArgs xa;                      // extract: ta with the extract stream's sizes, sums, counts and output
         PinBuf h_blocks, h_counts;
         PinBuf h_ns;                          // collect_names / eject_named: the set's ctrl words behind the call's kernels; the mate map's at + 32
@@ -1557,7 +1644,7 @@ int bam_finish_report(fadehip_bam_stream *st, fadehip_bam_stream::Set &S, uint64
         const bam::RepCtl c = *(const bam::RepCtl *)S.h_rp.p;
         const size_t ns = 2 * (size_t)S.n_rec;
         for (uint32_t w = 0; w < 2u; w++)
-            if ((st->report & (1u << w)) && c.rows[w] && (rc = enqueue_report_sizes(ctx, q, S.rpa, w, c, S.rp_scratch))) return rc;
+            if ((st->report & (1u << w)) && c.rows[w] && (rc = enqueue_report_sizes(ctx, q, S.rpa, w, c, S.rp_scratch, S.rpm))) return rc;
         HIPCHK(ctx, hipMemcpyAsync(S.h_rp.p, S.rpa.ctl, sizeof(bam::RepCtl), hipMemcpyDeviceToHost, q));
         HIPCHK(ctx, hipStreamSynchronize(q));
         const bam::RepCtl *t = (const bam::RepCtl *)S.h_rp.p;
@@ -1568,7 +1655,8 @@ int bam_finish_report(fadehip_bam_stream *st, fadehip_bam_stream::Set &S, uint64
             PinBuf &rh = st->rbuf[w][k % (FADEHIP_BAM_CHUNKS + 1)];
             if ((rc = reserve_roomy(ctx, out->r[w], (size_t)rb + 256)) || (rc = reserve_pinned(ctx, rh, (size_t)rb + (size_t)rb / 4 + 256))) return rc;
             S.rpa.out[w] = (uint8_t *)out->r[w].p;
-            hipLaunchKernelGGL(bam::report_write_kernel, dim3((unsigned)((ns + 15) / 16)), dim3(256), 0, q, S.rpa, w);
+            if (S.rpm && w == 0u) hipLaunchKernelGGL((bam::report_write_kernel<true>), dim3((unsigned)((ns + 15) / 16)), dim3(256), 0, q, S.rpa, w, (const uint8_t *)S.rpm);
+            else hipLaunchKernelGGL((bam::report_write_kernel<false>), dim3((unsigned)((ns + 15) / 16)), dim3(256), 0, q, S.rpa, w, (const uint8_t *)nullptr);
             HIPCHK(ctx, hipGetLastError());
             HIPCHK(ctx, hipMemcpyAsync(rh.p, out->r[w].p, (size_t)rb, hipMemcpyDeviceToHost, q));
             out->rbytes[w] = (size_t)rb;
@@ -2165,8 +2253,10 @@ int bam_front_tags(fadehip_bam_stream *st, fadehip_bam_stream::Set &S, Slot &s, 
     if (st->report) {  // the reports' stage (bam_report.hpp); its ctl crosses with the counts
         bam::RepArgs &ra = S.rpa;
         memset(&ra, 0, sizeof ra);
-        if ((rc = reserve_roomy(ctx, S.rp, report_layout(ra, nullptr, n, st->report))) || (rc = reserve_pinned(ctx, S.h_rp, 128))) return rc;
-        report_layout(ra, (uint8_t *)S.rp.p, n, st->report);
+        S.rpm = nullptr;
+        uint8_t **rpm = st->repeats ? &S.rpm : nullptr;
+        if ((rc = reserve_roomy(ctx, S.rp, report_layout(ra, nullptr, n, st->report, rpm))) || (rc = reserve_pinned(ctx, S.h_rp, 128))) return rc;
+        report_layout(ra, (uint8_t *)S.rp.p, n, st->report, rpm);
         ra.base = pa.u;
         ra.off32 = pa.rec_off;
         ra.n = n_rec;
@@ -2175,6 +2265,7 @@ int bam_front_tags(fadehip_bam_stream *st, fadehip_bam_stream::Set &S, Slot &s, 
         HIPCHK(ctx, hipMemsetAsync(ra.ctl, 0, 128, q));
         hipLaunchKernelGGL(bam::report_stage_kernel, dim3(ntb), dim3(bam::TAG_BLOCK), 0, q, ra);
         HIPCHK(ctx, hipGetLastError());
+        if (st->repeats && (rc = enqueue_report_repeats(ctx, q, ra, st->intervals, (const int32_t *)st->ref_chrom.p, S.rpm))) return rc;
         HIPCHK(ctx, hipMemcpyAsync(S.h_rp.p, ra.ctl, sizeof(bam::RepCtl), hipMemcpyDeviceToHost, q));
     }
     HIPCHK(ctx, hipMemcpyAsync(S.h_counts.p, d_counts, st->counts_bytes(), hipMemcpyDeviceToHost, q));
@@ -2195,6 +2286,8 @@ int bam_front_impl(fadehip_bam_stream *st, const uint8_t *members, size_t n_byte
     if ((st->collect_names || st->eject_named || st->collect_mates) && !st->names)
         return set_err(ctx, FADEHIP_E_STATE, "bam stream: opened with FADEHIP_BAM_%s and no name set attached (fadehip_bam_use_nameset)",
                        st->collect_names ? "COLLECT_NAMES" : st->eject_named ? "EJECT_NAMED" : "COLLECT_MATES");
+    if (st->repeats && !st->intervals)
+        return set_err(ctx, FADEHIP_E_STATE, "bam stream: opened with FADEHIP_BAM_REPORT_REPEATS and no set of intervals attached (fadehip_bam_use_intervals)");
     if (st->store_extract && !st->recstore)
         return set_err(ctx, FADEHIP_E_STATE, "bam stream: opened with FADEHIP_BAM_STORE_EXTRACT and no record store attached (fadehip_bam_use_recstore)");
     if ((st->collect_mates || st->fix_mates) && !st->mates)
@@ -2251,8 +2344,10 @@ int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_ba
     if (!cfg || !out || cfg->n_ref < 0 || (cfg->n_ref && !cfg->ref_names) || (cfg->window < 0 && !(cfg->flags & FADEHIP_BAM_FROM_TAGS)) ||
         (cfg->flags & ~(FADEHIP_BAM_STORED | FADEHIP_BAM_NO_OUTPUT | FADEHIP_BAM_CLIP | FADEHIP_BAM_EXTRACT | FADEHIP_BAM_EJECT | FADEHIP_BAM_EJECT_GROUPS | FADEHIP_BAM_FROM_TAGS |
                         FADEHIP_BAM_COLLECT_NAMES | FADEHIP_BAM_EJECT_NAMED | FADEHIP_BAM_KEEP_SORTED | FADEHIP_BAM_REPORT_STATS | FADEHIP_BAM_REPORT_CLIP | FADEHIP_BAM_INDEX |
-                        FADEHIP_BAM_COLLECT_MATES | FADEHIP_BAM_FIX_MATES | FADEHIP_BAM_STORE_EXTRACT)))
+                        FADEHIP_BAM_COLLECT_MATES | FADEHIP_BAM_FIX_MATES | FADEHIP_BAM_STORE_EXTRACT | FADEHIP_BAM_REPORT_REPEATS)))
         return set_err(ctx, FADEHIP_E_INVALID, "bam stream: bad configuration");
+    if ((cfg->flags & FADEHIP_BAM_REPORT_REPEATS) && !(cfg->flags & FADEHIP_BAM_REPORT_STATS))
+        return set_err(ctx, FADEHIP_E_INVALID, "bam stream: FADEHIP_BAM_REPORT_REPEATS needs FADEHIP_BAM_REPORT_STATS (it adds two columns to that report's rows)");
     if ((cfg->flags & FADEHIP_BAM_STORE_EXTRACT) && !(cfg->flags & FADEHIP_BAM_EXTRACT))
         return set_err(ctx, FADEHIP_E_INVALID, "bam stream: FADEHIP_BAM_STORE_EXTRACT needs FADEHIP_BAM_EXTRACT (it says where the extract records go)");
     // the index describes records that are written: a stream that writes none has nothing to index.  It stands beside every
@@ -2265,7 +2360,7 @@ int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_ba
     }
     // (STORE_EXTRACT only says where EXTRACT's records go: it stands wherever EXTRACT does)
     fadehip_bam_config cfg_plain = *cfg;
-    cfg_plain.flags &= ~(FADEHIP_BAM_INDEX | FADEHIP_BAM_STORE_EXTRACT);
+    cfg_plain.flags &= ~(FADEHIP_BAM_INDEX | FADEHIP_BAM_STORE_EXTRACT | FADEHIP_BAM_REPORT_REPEATS);  // (REPORT_REPEATS stands wherever REPORT_STATS does)
     cfg = &cfg_plain;
     if (cfg->flags & (FADEHIP_BAM_REPORT_STATS | FADEHIP_BAM_REPORT_CLIP)) {
         const int32_t need = FADEHIP_BAM_FROM_TAGS | FADEHIP_BAM_NO_OUTPUT;
@@ -2320,10 +2415,12 @@ int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_ba
     st->report = ((cfg->flags & FADEHIP_BAM_REPORT_STATS) ? bam::RP_STATS : 0u) | ((cfg->flags & FADEHIP_BAM_REPORT_CLIP) ? bam::RP_CLIP : 0u);
     st->index = (all_flags & FADEHIP_BAM_INDEX) != 0;
     st->store_extract = (all_flags & FADEHIP_BAM_STORE_EXTRACT) != 0;
+    st->repeats = (all_flags & FADEHIP_BAM_REPORT_REPEATS) != 0;
     std::string text;
     std::vector<uint32_t> off((size_t)cfg->n_ref + 1, 0);
     for (int k = 0; k < cfg->n_ref; k++) {
         if (!cfg->ref_names[k]) { delete st; return set_err(ctx, FADEHIP_E_INVALID, "bam stream: ref_names[%d] is NULL", k); }
+        if (st->repeats) st->ref_names_h.push_back(cfg->ref_names[k]);
         off[(size_t)k] = (uint32_t)text.size();
         text += cfg->ref_names[k];
     }
@@ -2383,6 +2480,25 @@ int fadehip_bam_use_recstore(fadehip_bam_stream *st, fadehip_recstore *s) {
     if (!st->store_extract) return set_err(ctx, FADEHIP_E_INVALID, "bam stream: opened without FADEHIP_BAM_STORE_EXTRACT");
     if (st->k_front) return set_err(ctx, FADEHIP_E_STATE, "bam stream: use_recstore comes before the first front call");
     st->recstore = s;
+    return 0;
+}
+
+int fadehip_bam_use_intervals(fadehip_bam_stream *st, fadehip_intervals *s) {
+    if (!st) return set_err(nullptr, FADEHIP_E_INVALID, "stream is NULL");
+    fadehip_ctx *ctx = st->ctx;
+    if (!s) return set_err(ctx, FADEHIP_E_INVALID, "intervals is NULL");
+    if (s->ctx != ctx) return set_err(ctx, FADEHIP_E_INVALID, "bam stream: the set of intervals belongs to another ctx");
+    if (!st->repeats) return set_err(ctx, FADEHIP_E_INVALID, "bam stream: opened without FADEHIP_BAM_REPORT_REPEATS");
+    if (st->k_front) return set_err(ctx, FADEHIP_E_STATE, "bam stream: use_intervals comes before the first front call");
+    if (!s->sealed) return set_err(ctx, FADEHIP_E_INVALID, "bam stream: the set of intervals has not been sealed (fadehip_intervals_seal)");
+    std::vector<const char *> names;
+    for (const std::string &nm : st->ref_names_h) names.push_back(nm.c_str());
+    const std::vector<int32_t> refc = intervals_ref_chrom(s, (int32_t)names.size(), names.data());
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (const int rc = reserve(ctx, st->ref_chrom, 4 * refc.size())) return rc;
+    if (hipMemcpyAsync(st->ref_chrom.p, refc.data(), 4 * refc.size(), hipMemcpyHostToDevice, ctx->copy_stream) != hipSuccess || hipStreamSynchronize(ctx->copy_stream) != hipSuccess)
+        return set_err(ctx, FADEHIP_E_HIP, "bam stream: copying the contigs' chrom ids failed");
+    st->intervals = s;
     return 0;
 }
 
@@ -3088,6 +3204,7 @@ void fadehip_bam_close(fadehip_bam_stream *st) {
     release(st->names_text);
     release(st->names_off);
     release(st->names_first);
+    release(st->ref_chrom);
     for (auto &S : st->set) {
         for (DevBuf *b : {&S.comp, &S.blocks, &S.status, &S.ticket, &S.u, &S.seg, &S.slots, &S.rec_off, &S.info, &S.sent_of, &S.art_of, &S.out_size, &S.blk32,
                           &S.blk64, &S.counts, &S.ex_size, &S.ex_blk, &S.rx_cnt, &S.ej_head, &S.ej_blk, &S.ej_grp, &S.ft_rec, &S.ft_side, &S.ft_ops_blk, &S.ft_ops_at, &S.ft_ops})
@@ -3122,6 +3239,332 @@ void fadehip_bam_close(fadehip_bam_stream *st) {
         if (o.ready) (void)hipEventDestroy(o.ready);
     }
     delete st;
+}
+
+// ---- the set of intervals (bam_intervals.hpp): fadehip_intervals_*
+namespace {
+
+constexpr uint64_t INTERVALS_DEFAULT_CAP = (uint64_t)1 << 20;
+constexpr uint64_t INTERVALS_MAX = ((uint64_t)1 << 31) - 1;  // the sort numbers its items in 32 bits
+constexpr int64_t INTERVALS_CALL = (int64_t)1 << 22;         // intervals (or queries) of one upload and launch
+
+int intervals_alloc(fadehip_ctx *ctx, DevBuf &b, size_t bytes) {
+    b.p = nullptr;
+    b.cap = 0;
+    const size_t want = (std::max<size_t>(bytes, 256) + 255) & ~(size_t)255;
+    if (hipMalloc(&b.p, want) != hipSuccess) {
+        (void)hipGetLastError();
+        b.p = nullptr;
+        return set_err(ctx, FADEHIP_E_NOMEM, "intervals: allocating %zu bytes on the device failed", want);
+    }
+    b.cap = want;
+    return 0;
+}
+
+// a larger array with the first `keep` bytes of the old one (the caller holds s->mu and the lane's lock, and has waited for the lane's stream)
+int intervals_regrow(fadehip_ctx *ctx, hipStream_t q, DevBuf &b, size_t keep, size_t want) {
+    DevBuf nb;
+    if (const int rc = intervals_alloc(ctx, nb, want)) return rc;
+    if (keep && (hipMemcpyAsync(nb.p, b.p, keep, hipMemcpyDeviceToDevice, q) != hipSuccess || hipStreamSynchronize(q) != hipSuccess)) {
+        release(nb);
+        return set_err(ctx, FADEHIP_E_HIP, "intervals: moving the items to a larger buffer failed");
+    }
+    release(b);
+    b = nb;
+    return 0;
+}
+
+int intervals_room(fadehip_intervals *s, hipStream_t q, uint64_t n_new) {
+    fadehip_ctx *ctx = s->ctx;
+    if (s->n + n_new > INTERVALS_MAX) return set_err(ctx, FADEHIP_E_UNSUPPORTED, "intervals: more than %llu intervals (the sort numbers its items in 32 bits)", (unsigned long long)INTERVALS_MAX);
+    if (s->n + n_new <= s->cap) return 0;
+    const uint64_t cap = std::max<uint64_t>(std::max<uint64_t>(2 * s->cap, s->n + n_new), s->first_cap);
+    int rc;
+    if ((rc = intervals_regrow(ctx, q, s->key, 8 * (size_t)s->n, 8 * (size_t)cap)) || (rc = intervals_regrow(ctx, q, s->end32, 4 * (size_t)s->n, 4 * (size_t)cap)) ||
+        (rc = intervals_regrow(ctx, q, s->idx, 4 * (size_t)s->n, 4 * (size_t)cap)))
+        return rc;  // (an array that has grown already stays grown: it holds what it held)
+    s->cap = cap;
+    return 0;
+}
+
+int intervals_new(fadehip_ctx *ctx, fadehip_intervals **out) {
+    *out = nullptr;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    fadehip_intervals *s = new (std::nothrow) fadehip_intervals;
+    if (!s) return set_err(ctx, FADEHIP_E_NOMEM, "out of memory");
+    s->ctx = ctx;
+    s->first_cap = INTERVALS_DEFAULT_CAP;
+    if (const char *e = getenv("FADEHIP_INTERVALS_CAP")) s->first_cap = (uint64_t)std::max<long long>(16, std::min<long long>(atoll(e), (long long)INTERVALS_MAX));
+    *out = s;
+    return 0;
+}
+
+// a name the set does not hold yet gets the next id (before seal; create's and the BED loader's)
+int intervals_name(fadehip_intervals *s, const std::string &nm) {
+    if (nm.empty()) return set_err(s->ctx, FADEHIP_E_INVALID, "intervals: chrom_names[%zu] is empty", s->names.size());
+    if (!s->ids.emplace(nm, (int32_t)s->names.size()).second) return set_err(s->ctx, FADEHIP_E_INVALID, "intervals: chrom_names[%zu] names \"%s\" a second time", s->names.size(), nm.c_str());
+    s->names.push_back(nm);
+    return 0;
+}
+
+// add, under the lane's lock and the set's
+int intervals_add_locked(fadehip_intervals *s, BatchLane &L, int64_t n, const int32_t *chrom, const int64_t *start, const int64_t *end) {
+    fadehip_ctx *ctx = s->ctx;
+    int rc;
+    if ((rc = intervals_room(s, L.stream, (uint64_t)n))) return rc;
+    for (int64_t c0 = 0; c0 < n; c0 += INTERVALS_CALL) {
+        const size_t m = (size_t)std::min<int64_t>(INTERVALS_CALL, n - c0);
+        // stage: ctl | start [m] i64 | end [m] i64 | chrom [m] i32
+        if ((rc = reserve_roomy(ctx, s->stage, 16 + 20 * m + 8))) return rc;
+        uint8_t *sp = (uint8_t *)s->stage.p;
+        bam::IvAddArgs a;
+        a.ctl = (bam::IvCtl *)sp;
+        a.start = (const int64_t *)(sp + 16);
+        a.end = (const int64_t *)(sp + 16 + 8 * m);
+        a.chrom = (const int32_t *)(sp + 16 + 16 * m);
+        a.n = (uint32_t)m;
+        a.item0 = (uint32_t)(s->n + (uint64_t)c0);
+        a.n_chrom = (int32_t)s->names.size();
+        a.key = (uint64_t *)s->key.p;
+        a.end32 = (uint32_t *)s->end32.p;
+        a.idx = (uint32_t *)s->idx.p;
+        HIPCHK(ctx, hipMemsetAsync(sp, 0, 16, L.stream));
+        HIPCHK(ctx, hipMemcpyAsync((void *)a.start, start + c0, 8 * m, hipMemcpyHostToDevice, L.stream));
+        HIPCHK(ctx, hipMemcpyAsync((void *)a.end, end + c0, 8 * m, hipMemcpyHostToDevice, L.stream));
+        HIPCHK(ctx, hipMemcpyAsync((void *)a.chrom, chrom + c0, 4 * m, hipMemcpyHostToDevice, L.stream));
+        hipLaunchKernelGGL(bam::intervals_key_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, L.stream, a);
+        HIPCHK(ctx, hipGetLastError());
+        bam::IvCtl c;
+        HIPCHK(ctx, hipMemcpyAsync(&c, a.ctl, sizeof c, hipMemcpyDeviceToHost, L.stream));
+        HIPCHK(ctx, hipStreamSynchronize(L.stream));
+        if (c.bad) {  // (the items written so far lie beyond s->n, which stays: nothing has been added)
+            const long long k = (long long)c0 + (long long)(0xffffffffu - (uint32_t)(c.bad >> 8));
+            if (chrom[k] < 0 || chrom[k] >= a.n_chrom)
+                return set_err(ctx, FADEHIP_E_INVALID, "intervals: interval %lld: chrom %d is outside the set's %d contigs", k, chrom[k], a.n_chrom);
+            return set_err(ctx, FADEHIP_E_INVALID, "intervals: interval %lld: start %lld, end %lld (0 <= start < end <= 2^31 - 1 is required)", k, (long long)start[k], (long long)end[k]);
+        }
+    }
+    s->n += (uint64_t)n;
+    return 0;
+}
+
+int intervals_seal_locked(fadehip_intervals *s, BatchLane &L) {
+    fadehip_ctx *ctx = s->ctx;
+    const size_t n = (size_t)s->n, n_chrom = s->names.size();
+    hipStream_t q = L.stream;
+    int rc;
+    std::vector<uint32_t> noff(n_chrom + 1, 0);
+    std::string nbytes;
+    for (size_t c = 0; c < n_chrom; c++) {
+        nbytes += s->names[c];
+        noff[c + 1] = (uint32_t)nbytes.size();
+    }
+    if ((rc = intervals_alloc(ctx, s->start, 4 * n + 8)) || (rc = intervals_alloc(ctx, s->maxend, 8 * n + 8)) || (rc = intervals_alloc(ctx, s->chrom_first, 4 * (n_chrom + 1))) ||
+        (rc = intervals_alloc(ctx, s->name_bytes, nbytes.size() + 8)) || (rc = intervals_alloc(ctx, s->name_off, 4 * noff.size())))
+        return rc;
+    HIPCHK(ctx, hipMemcpyAsync(s->name_off.p, noff.data(), 4 * noff.size(), hipMemcpyHostToDevice, q));
+    if (!nbytes.empty()) HIPCHK(ctx, hipMemcpyAsync(s->name_bytes.p, nbytes.data(), nbytes.size(), hipMemcpyHostToDevice, q));
+    HIPCHK(ctx, hipMemsetAsync(s->chrom_first.p, 0, 4 * (n_chrom + 1), q));
+    DevBuf sort_arr, blk;
+    bam::ResortCtl rc0;
+    // (whichever way this function is left: nothing enqueued still reads what goes out of scope with it)
+    struct Free { hipStream_t q; DevBuf &a, &b; ~Free() { (void)hipStreamSynchronize(q); release(a); release(b); } } free_them{q, sort_arr, blk};
+    if (n) {
+        bam::ResortArgs ra;
+        memset(&ra, 0, sizeof ra);
+        if ((rc = intervals_alloc(ctx, sort_arr, recstore_sort_layout(ra, nullptr, n)))) return rc;
+        recstore_sort_layout(ra, (uint8_t *)sort_arr.p, n);
+        ra.key0 = (uint64_t *)s->key.p;  // (the layout's msrc, dst, sblk and msize stay unused: the cut and the offsets are the records')
+        memset(&rc0, 0, sizeof rc0);
+        rc0.W = ~0ull;
+        rc0.n_in = (uint32_t)n;
+        HIPCHK(ctx, hipMemcpyAsync(ra.ctl, &rc0, sizeof rc0, hipMemcpyHostToDevice, q));
+        HIPCHK(ctx, hipMemcpyAsync(ra.idx0, s->idx.p, 4 * n, hipMemcpyDeviceToDevice, q));
+        if ((rc = enqueue_resort_sort(ctx, q, ra, n))) return rc;
+        const unsigned nb = (unsigned)((n + 255) / 256);
+        if ((rc = intervals_alloc(ctx, blk, 16 * (size_t)nb))) return rc;
+        bam::IvSealArgs a;
+        a.key = ra.key0;
+        a.idx = ra.idx0;
+        a.end32 = (const uint32_t *)s->end32.p;
+        a.n = (uint32_t)n;
+        a.n_chrom = (int32_t)n_chrom;
+        a.start = (uint32_t *)s->start.p;
+        a.maxend = (uint64_t *)s->maxend.p;
+        a.blk_max = (uint64_t *)blk.p;
+        a.blk_carry = a.blk_max + nb;
+        a.chrom_first = (uint32_t *)s->chrom_first.p;
+        hipLaunchKernelGGL(bam::intervals_gather_kernel, dim3(nb), dim3(256), 0, q, a);
+        HIPCHK(ctx, hipGetLastError());
+        hipLaunchKernelGGL(bam::intervals_block_max_kernel, dim3(nb), dim3(256), 0, q, a);
+        HIPCHK(ctx, hipGetLastError());
+        hipLaunchKernelGGL(bam::intervals_max_scan_kernel, dim3(1), dim3(1024), 0, q, a, (uint32_t)nb);
+        HIPCHK(ctx, hipGetLastError());
+        hipLaunchKernelGGL(bam::intervals_max_apply_kernel, dim3(nb), dim3(256), 0, q, a);
+        HIPCHK(ctx, hipGetLastError());
+        hipLaunchKernelGGL(bam::intervals_chrom_first_kernel, dim3((unsigned)((n_chrom + 1 + 255) / 256)), dim3(256), 0, q, a);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    HIPCHK(ctx, hipStreamSynchronize(q));  // (the names' vectors go out of scope; the raw items are given back)
+    for (DevBuf *b : {&s->key, &s->end32, &s->idx, &s->stage}) release(*b);
+    s->cap = 0;
+    s->sealed = true;
+    return 0;
+}
+
+// the lane made ready for a call of the set's
+int intervals_lane(fadehip_ctx *ctx, BatchLane &L) {
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (!L.stream) HIPCHK(ctx, hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
+    return 0;
+}
+
+}  // namespace
+
+int fadehip_intervals_create(fadehip_ctx *ctx, int32_t n_chrom, const char *const *chrom_names, fadehip_intervals **out) {
+    if (!ctx) return set_err(nullptr, FADEHIP_E_INVALID, "ctx is NULL");
+    if (!out || n_chrom < 0 || (n_chrom > 0 && !chrom_names)) return set_err(ctx, FADEHIP_E_INVALID, "NULL argument");
+    fadehip_intervals *s = nullptr;
+    int rc;
+    if ((rc = intervals_new(ctx, &s))) return rc;
+    for (int32_t c = 0; c < n_chrom && !rc; c++) rc = chrom_names[c] ? intervals_name(s, chrom_names[c]) : set_err(ctx, FADEHIP_E_INVALID, "intervals: chrom_names[%d] is NULL", c);
+    if (rc) {
+        fadehip_intervals_destroy(s);
+        return rc;
+    }
+    *out = s;
+    return 0;
+}
+
+int fadehip_intervals_add(fadehip_intervals *s, int64_t n, const int32_t *chrom, const int64_t *start, const int64_t *end) {
+    if (!s) return set_err(nullptr, FADEHIP_E_INVALID, "intervals is NULL");
+    fadehip_ctx *ctx = s->ctx;
+    if (n < 0 || (n > 0 && (!chrom || !start || !end))) return set_err(ctx, FADEHIP_E_INVALID, "NULL argument");
+    BatchLane &L = ctx->batch;
+    std::lock_guard<std::mutex> lk(L.mu);
+    int rc;
+    if ((rc = intervals_lane(ctx, L))) return rc;
+    std::lock_guard<std::mutex> sl(s->mu);
+    if (s->sealed) return set_err(ctx, FADEHIP_E_STATE, "intervals: the set has been sealed, nothing can be added to it any more");
+    if (n == 0) return 0;
+    return intervals_add_locked(s, L, n, chrom, start, end);
+}
+
+int fadehip_intervals_seal(fadehip_intervals *s) {
+    if (!s) return set_err(nullptr, FADEHIP_E_INVALID, "intervals is NULL");
+    fadehip_ctx *ctx = s->ctx;
+    BatchLane &L = ctx->batch;
+    std::lock_guard<std::mutex> lk(L.mu);
+    int rc;
+    if ((rc = intervals_lane(ctx, L))) return rc;
+    std::lock_guard<std::mutex> sl(s->mu);
+    if (s->sealed) return set_err(ctx, FADEHIP_E_STATE, "intervals: the set has been sealed already");
+    return intervals_seal_locked(s, L);
+}
+
+int fadehip_intervals_count(fadehip_intervals *s, int64_t *n_intervals, int32_t *n_chrom) {
+    if (!s) return set_err(nullptr, FADEHIP_E_INVALID, "intervals is NULL");
+    if (!n_intervals || !n_chrom) return set_err(s->ctx, FADEHIP_E_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> sl(s->mu);
+    *n_intervals = (int64_t)s->n;
+    *n_chrom = (int32_t)s->names.size();
+    return 0;
+}
+
+int fadehip_intervals_overlap_batch(fadehip_intervals *s, int64_t n, const int32_t *chrom, const int64_t *start, const int64_t *end, uint8_t *hit) {
+    if (!s) return set_err(nullptr, FADEHIP_E_INVALID, "intervals is NULL");
+    fadehip_ctx *ctx = s->ctx;
+    if (n < 0 || (n > 0 && (!chrom || !start || !end || !hit))) return set_err(ctx, FADEHIP_E_INVALID, "NULL argument");
+    BatchLane &L = ctx->batch;
+    std::lock_guard<std::mutex> lk(L.mu);
+    int rc;
+    if ((rc = intervals_lane(ctx, L))) return rc;
+    std::lock_guard<std::mutex> sl(s->mu);
+    if (!s->sealed) return set_err(ctx, FADEHIP_E_INVALID, "intervals: a query comes after fadehip_intervals_seal");
+    for (int64_t c0 = 0; c0 < n; c0 += INTERVALS_CALL) {
+        const size_t m = (size_t)std::min<int64_t>(INTERVALS_CALL, n - c0);
+        // stage: start [m] i64 | end [m] i64 | chrom [m] i32 | hit [m] u8
+        if ((rc = reserve_roomy(ctx, s->stage, 21 * m + 8))) return rc;
+        uint8_t *sp = (uint8_t *)s->stage.p;
+        bam::IvQueryArgs a;
+        a.s = intervals_ref(s);
+        a.start = (const int64_t *)sp;
+        a.end = (const int64_t *)(sp + 8 * m);
+        a.chrom = (const int32_t *)(sp + 16 * m);
+        a.hit = sp + 20 * m;
+        a.n = (uint32_t)m;
+        HIPCHK(ctx, hipMemcpyAsync((void *)a.start, start + c0, 8 * m, hipMemcpyHostToDevice, L.stream));
+        HIPCHK(ctx, hipMemcpyAsync((void *)a.end, end + c0, 8 * m, hipMemcpyHostToDevice, L.stream));
+        HIPCHK(ctx, hipMemcpyAsync((void *)a.chrom, chrom + c0, 4 * m, hipMemcpyHostToDevice, L.stream));
+        hipLaunchKernelGGL(bam::intervals_overlap_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, L.stream, a);
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipMemcpyAsync(hit + c0, a.hit, m, hipMemcpyDeviceToHost, L.stream));
+        HIPCHK(ctx, hipStreamSynchronize(L.stream));
+    }
+    return 0;
+}
+
+int fadehip_intervals_load_bed(fadehip_ctx *ctx, const char *path, fadehip_intervals **out) {
+    if (!ctx) return set_err(nullptr, FADEHIP_E_INVALID, "ctx is NULL");
+    if (!path || !out) return set_err(ctx, FADEHIP_E_INVALID, "NULL argument");
+    *out = nullptr;
+    const std::string no = bed::path_refusal(path);
+    if (!no.empty()) return set_err(ctx, FADEHIP_E_INVALID, "bed: %s", no.c_str());
+    FILE *f = fopen(path, "rb");
+    if (!f) return set_err(ctx, FADEHIP_E_INVALID, "bed: cannot open %s: %s", path, strerror(errno));
+    struct Closer { FILE *f; ~Closer() { fclose(f); } } closer{f};
+    fadehip_intervals *s = nullptr;
+    int rc;
+    if ((rc = intervals_new(ctx, &s))) return rc;
+    BatchLane &L = ctx->batch;
+    bed::Parser *self = nullptr;
+    // a piece: the names it brought first (ids in order of first appearance, as the parser numbers them), then its intervals
+    bed::Parser parser([&](const int32_t *chrom, const int64_t *start, const int64_t *end, size_t n, std::string &why) {
+        std::lock_guard<std::mutex> lk(L.mu);
+        int r = intervals_lane(ctx, L);
+        std::lock_guard<std::mutex> sl(s->mu);
+        for (size_t c = s->names.size(); !r && c < self->names().size(); c++) r = intervals_name(s, self->names()[c]);
+        if (!r) r = intervals_add_locked(s, L, (int64_t)n, chrom, start, end);
+        if (r) {
+            rc = r;
+            why = fadehip_last_error(ctx);
+        }
+        return r == 0;
+    });
+    self = &parser;
+    std::vector<char> buf((size_t)1 << 20);
+    bool ok = true;
+    size_t got;
+    while (ok && (got = fread(buf.data(), 1, buf.size(), f)) > 0) ok = parser.feed(buf.data(), got);
+    if (ok && ferror(f)) {
+        fadehip_intervals_destroy(s);
+        return set_err(ctx, FADEHIP_E_INVALID, "bed: read error on %s", path);
+    }
+    ok = ok && parser.finish();
+    if (!ok) {
+        const std::string why = parser.error();
+        fadehip_intervals_destroy(s);
+        return rc ? set_err(ctx, rc, "bed: %s: %s", path, why.c_str()) : set_err(ctx, FADEHIP_E_INVALID, "bed: %s: %s", path, why.c_str());
+    }
+    {  // (a contig may be named by the last piece alone)
+        std::lock_guard<std::mutex> sl(s->mu);
+        for (size_t c = s->names.size(); !rc && c < parser.names().size(); c++) rc = intervals_name(s, parser.names()[c]);
+    }
+    if (!rc) rc = fadehip_intervals_seal(s);
+    if (rc) {
+        fadehip_intervals_destroy(s);
+        return rc;
+    }
+    *out = s;
+    return 0;
+}
+
+void fadehip_intervals_destroy(fadehip_intervals *s) {
+    if (!s) return;
+    (void)hipSetDevice(s->ctx->device);
+    (void)hipDeviceSynchronize();
+    for (DevBuf *b : {&s->key, &s->end32, &s->idx, &s->start, &s->maxend, &s->chrom_first, &s->name_bytes, &s->name_off, &s->stage}) release(*b);
+    delete s;
 }
 
 }  // extern "C"

@@ -14,6 +14,7 @@
 #include <memory>
 #include "hts_lite.hpp"
 #include "recstore_host.hpp"
+#include "bed_lite.hpp"
 #include "bgzf_feed.hpp"
 #include "../../../include/fadehip.h"
 
@@ -97,7 +98,8 @@ struct Opts {
     std::string extract;  // --extract PATH: `fade extract`'s records of this run's artifact calls, in the output's format
     bool sorted = false;  // `fade extract --sorted`: the records leave in coordinate order (a store of records on the device, sorted once at the end)
     bool extract_sorted = false;  // `fade annotate --extract PATH --extract-sorted`: PATH is written in coordinate order, PATH.bai beside it
-    std::string seen;  // one letter per option met: t m w b u c h g(pus) B(atch) s(tats) T(iming) S(hards) X (--extract) E (--eject) F (--fragments) K (--keep-sorted) O (--sorted) Y (--extract-sorted)
+    std::string repeats;  // `fade stats --gpus 1 --repeats PATH`: a BED of repeats; every row gains read_rpm and art_rpm (a set of intervals on the device)
+    std::string seen;  // R (--repeats); one letter per option met: t m w b u c h g(pus) B(atch) s(tats) T(iming) S(hards) X (--extract) E (--eject) F (--fragments) K (--keep-sorted) O (--sorted) Y (--extract-sorted)
 };
 
 // std.getopt with config.bundling: short flags bundle (-bu), values attach (-w100, -w 100, --window-size=100)
@@ -155,6 +157,15 @@ static bool parse_opts(int argc, char **argv, Opts &o, std::string &err) {
                 }
                 if (val.empty()) { err = "Invalid value for option --extract: (empty)"; return false; }
                 o.extract = val;
+            }
+            else if (name == "repeats") {
+                o.seen += 'R';
+                if (!has_val) {
+                    if (i + 1 >= argc) { err = "Missing value for argument --" + name; return false; }
+                    val = argv[++i];
+                }
+                if (val.empty()) { err = "Invalid value for option --repeats: (empty)"; return false; }
+                o.repeats = val;
             }
             else if (name == "write-index") {
                 o.seen += 'I';
@@ -2555,7 +2566,8 @@ static int annotate_main(const std::string &cl, const Opts &o) {
 static bool options_allowed(const Opts &o, const char *allowed) {
     for (char c : o.seen)
         if (!strchr(allowed, c)) {
-            fprintf(stderr, "std.getopt.GetOptException: Unrecognized option %s%c\n", "-", c);
+            if (c == 'R') fprintf(stderr, "std.getopt.GetOptException: Unrecognized option --repeats\n[E::fade] --repeats: the option goes with fade stats --gpus 1 (it adds two columns to that report's rows)\n");
+            else fprintf(stderr, "std.getopt.GetOptException: Unrecognized option %s%c\n", "-", c);
             return false;
         }
     return true;
@@ -2582,10 +2594,12 @@ static void print_report_help(bool stats) {
             "usage: fade %s --gpus 1 [options] <annotated BAM> [out.tsv]\n\n"
             "-t --threads extra threads for parsing the bam file\n"
             "      --gpus 1: the report's rows are written on one MI355X (the tags read back, the inverted repeats aligned, the text formatted by kernels)\n"
+            "%s"
             "    --timing print where the run spent its time to stderr\n"
             "-h    --help This help information.\n\n",
             kHeader, stats ? "stats: reports extended information about artifact reads (used after annotate)" : "stats-clip: reports extended information about all soft-clipped reads (used after annotate)",
-            stats ? "stats" : "stats-clip");
+            stats ? "stats" : "stats-clip",
+            stats ? "   --repeats PATH: a BED file of repeats (plain text), held on the MI355X: every row gains read_rpm and art_rpm, 1 where the read's / the artifact's region overlaps one\n" : "");
 }
 
 static bool parse_cigar_string(const std::string &s, std::vector<uint32_t> &ops) {
@@ -3016,6 +3030,7 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
     fadehip_nameset *names = nullptr;
     fadehip_mateset *mates = nullptr;
     fadehip_recstore *store = nullptr;  // `fade extract --sorted`: the run's extract records, on the device
+    fadehip_intervals *repeats = nullptr;  // `fade stats --repeats`: the BED's intervals, on the device
     Staging staging;
     struct Guard {
         fadehip_ctx *&c;
@@ -3023,16 +3038,18 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
         fadehip_nameset *&ns;
         fadehip_mateset *&ms;
         fadehip_recstore *&rs;
+        fadehip_intervals *&iv;
         Staging &stg;
         ~Guard() {
             if (s) fadehip_bam_close(s);
+            if (iv) fadehip_intervals_destroy(iv);
             if (ns) fadehip_nameset_destroy(ns);
             if (ms) fadehip_mateset_destroy(ms);
             if (rs) fadehip_recstore_destroy(rs);
             stg.unpin(c);
             if (c) fadehip_destroy(c);
         }
-    } guard{ctx, st, names, mates, store, staging};
+    } guard{ctx, st, names, mates, store, repeats, staging};
     try {
         fadehip_params prm;
         fadehip_params_default(&prm);
@@ -3056,6 +3073,7 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
             if ((mode & (FADEHIP_BAM_COLLECT_NAMES | FADEHIP_BAM_EJECT_NAMED | FADEHIP_BAM_COLLECT_MATES)) && fadehip_bam_use_nameset(st, names)) { create_err = fadehip_last_error(ctx); return 1; }
             if ((mode & (FADEHIP_BAM_COLLECT_MATES | FADEHIP_BAM_FIX_MATES)) && fadehip_bam_use_mateset(st, mates)) { create_err = fadehip_last_error(ctx); return 1; }
             if ((mode & FADEHIP_BAM_STORE_EXTRACT) && fadehip_bam_use_recstore(st, store)) { create_err = fadehip_last_error(ctx); return 1; }
+            if ((mode & FADEHIP_BAM_REPORT_REPEATS) && fadehip_bam_use_intervals(st, repeats)) { create_err = fadehip_last_error(ctx); return 1; }
             const size_t call_bytes = host_inflate ? chunk : std::min<size_t>(chunk * 3, (size_t)1 << 30);
             if (!(getenv("FADE_BAM_PREPARE") && atoi(getenv("FADE_BAM_PREPARE")) == 0) && fadehip_bam_prepare(st, call_bytes)) { create_err = fadehip_last_error(ctx); return 1; }
             return 0;
@@ -3066,6 +3084,17 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
                 if (fadehip_nameset_create(ctx, &names)) { create_err = fadehip_last_error(ctx); return 1; }
                 if (fix_mates && fadehip_mateset_create(ctx, &mates)) { create_err = fadehip_last_error(ctx); return 1; }
                 return open_stream(FADEHIP_BAM_COLLECT_NAMES | FADEHIP_BAM_NO_OUTPUT);
+            }
+            if (report && !o.repeats.empty()) {  // the set is loaded and sealed before the first call
+                StageClock ck_bed;
+                ck_bed.start();
+                if (fadehip_intervals_load_bed(ctx, o.repeats.c_str(), &repeats)) { create_err = fadehip_last_error(ctx); return 1; }
+                ck_bed.stop();
+                int64_t n_iv = 0;
+                int32_t n_chrom = 0;
+                fadehip_intervals_count(repeats, &n_iv, &n_chrom);
+                if (o.timing) fprintf(stderr, "[timing] --repeats: %lld intervals of %d contigs loaded and sealed on the device in %.3f s\n", (long long)n_iv, n_chrom, ck_bed.t);
+                return open_stream(FADEHIP_BAM_NO_OUTPUT | FADEHIP_BAM_REPORT_STATS | FADEHIP_BAM_REPORT_REPEATS);
             }
             if (report) return open_stream(FADEHIP_BAM_NO_OUTPUT | (job == TagsJob::STATS ? FADEHIP_BAM_REPORT_STATS : FADEHIP_BAM_REPORT_CLIP));
             int32_t mode = o.ubam ? FADEHIP_BAM_STORED : 0;
@@ -3258,8 +3287,9 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
         ck_pass2.start();
         if (report) {
             fputs(job == TagsJob::STATS ? "qname\trname\tpos\tcigar\tart_start\tart_end\taln_rname\taln_start\taln_end\tart_cigar\tstemloop\tstemloop_rc\t"
-                                          "predicted_inverted_repeat\tIR_identity\tavgbq\tart_avgbq\tart_bq\tIR_bq\tflagbinary\tflag\tstrand\n"
-                                        : "qname\tsc_q_scores\tsc_seq\tsc_avg_bq\tavg_bq\tart_status\n", rep_out);
+                                          "predicted_inverted_repeat\tIR_identity\tavgbq\tart_avgbq\tart_bq\tIR_bq\tflagbinary\tflag\tstrand"
+                                        : "qname\tsc_q_scores\tsc_seq\tsc_avg_bq\tavg_bq\tart_status", rep_out);
+            fputs(repeats ? "\tread_rpm\tart_rpm\n" : "\n", rep_out);
         } else if (job == TagsJob::EXTRACT && o.sorted) {
             // (nothing is written while the input streams through: header, records and marker follow the sort)
         } else if (job == TagsJob::EXTRACT) xwriter.reset(new Writer(stdout, fmt, out_hdr, &pool));
@@ -3405,6 +3435,11 @@ int main(int argc, char **argv) {
         std::string err;
         if (!parse_opts(argc, argv, o, err)) {
             fprintf(stderr, "std.getopt.GetOptException: %s\n", err.c_str());
+            return 1;
+        }
+        if (!o.repeats.empty()) {  // refused here, by name, before any device is opened
+            fprintf(stderr, "[E::fade-annotate] --repeats: %s\n", !o.stats_tsv.empty() ? "the repeat columns of --stats-tsv are out of scope: run fade stats --gpus 1 --repeats PATH on the annotated file"
+                                                                                      : "the option goes with fade stats --gpus 1 (it adds two columns to that report's rows)");
             return 1;
         }
         if (!options_allowed(o, "tmwbucgBsTSPQXEKIY")) return 1;
@@ -3669,7 +3704,19 @@ int main(int argc, char **argv) {
     if (sub == "stats" || sub == "stats-clip") {  // app.d:154-209
         Opts o;
         std::string err;
-        const bool with_gpus = parse_opts(argc, argv, o, err) && o.seen.find('g') != std::string::npos;
+        const bool parsed = parse_opts(argc, argv, o, err), with_gpus = parsed && o.seen.find('g') != std::string::npos;
+        if (parsed && !o.repeats.empty()) {  // refused here, by name, before any device is opened
+            const std::string no_bed = fadehip::bed::path_refusal(o.repeats);
+            struct stat rsb;
+            const char *why = sub != "stats" ? "the rows of stats-clip carry no coordinates: the option goes with fade stats"
+                              : !with_gpus ? "it goes with --gpus 1 (the intervals are held and queried on the device; there is no host loop)"
+                              : !no_bed.empty() ? no_bed.c_str()
+                              : (stat(o.repeats.c_str(), &rsb) != 0 || !S_ISREG(rsb.st_mode)) ? "the BED file is read as a plain file: not a pipe, not a directory, not a missing path" : nullptr;
+            if (why) {
+                fprintf(stderr, "[E::fade %s] --repeats: %s\n", sub.c_str(), why);
+                return 1;
+            }
+        }
         if (!with_gpus) {
             fprintf(stderr, "[E::fade] %s is outside the MI355X annotate hot path; run the reference fade for it, or write its report "
                             "during the run: fade annotate %s PATH.  On an annotated BAM file one MI355X writes it: fade %s --gpus 1 <annotated BAM> [out.tsv]\n",
@@ -3677,7 +3724,7 @@ int main(int argc, char **argv) {
             return 1;
         }
         const std::string who = "fade " + sub;
-        if (!options_allowed(o, "tgT")) return 1;
+        if (!options_allowed(o, "tgTR")) return 1;
         if (o.help || o.pos.size() < 2 || o.pos.size() > 3) { print_report_help(sub == "stats"); return o.pos.size() > 3 ? 1 : 0; }
         if (o.gpus != 1) {
             fprintf(stderr, "[E::%s] --gpus %d: the report is written on one device (--gpus 1)\n", who.c_str(), o.gpus);

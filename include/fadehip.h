@@ -403,6 +403,50 @@ int fadehip_recstore_drain(fadehip_recstore *s, int32_t flags, uint64_t max_payl
                            fadehip_index_call *idx /* NULL without FADEHIP_RECSTORE_INDEX */);
 void fadehip_recstore_destroy(fadehip_recstore *s);
 
+/* A set of genomic intervals resident on the device, and the overlap query over it (tests/intervals_model.py
+ * states the rule in Python): what `bedtools subtract -A` against a RepeatMasker BED decides, as one look-up per query.
+ *   interval  (chrom, start, end): chrom an index into the names the set was created with, start and end 0-based half-open,
+ *             0 <= start < end <= 2^31 - 1.  Duplicates and any order are fine.
+ *   query     (chrom, qs, qe) of int64, which may be negative: hit = 1 iff qs < qe and the set holds an interval of that
+ *             chrom with start < qe and qs < end — any overlap of at least one base.  chrom outside [0, n_chrom): 0.
+ *   create    n_chrom names (NUL-terminated, non-empty, compared as exact bytes); a name twice: FADEHIP_E_INVALID.
+ *   add       n intervals, any number of calls.  A bad interval — chrom outside the names, or the bounds above — is found on
+ *             the device: FADEHIP_E_INVALID, fadehip_last_error names its index in the call, and NOTHING of the call is added.
+ *             After seal: FADEHIP_E_STATE.
+ *   seal      sorts the intervals by (chrom, start) (the stable radix sort of FADEHIP_BAM_KEEP_SORTED) and leaves per interval
+ *             its start and the running maximum of chrom << 32 | end — which the chrom ids, rising along the order, segment
+ *             by contig — and every contig's range.  A second seal: FADEHIP_E_STATE.  A set without intervals seals fine.
+ *   overlap_batch  n queries, a binary search each (about log2 of the set's size probes).  Before seal: FADEHIP_E_INVALID.
+ *   count     the intervals added so far, and the names.
+ *   load_bed  create + add in pieces + seal over a BED file: lines end at LF (a CR in front of it is dropped, the last line may
+ *             lack its LF); empty lines and lines that start with '#', "track" or "browser" are skipped; fields are separated
+ *             by tabs, at least three, further ones ignored; the name is 1 to 255 bytes; start and end are decimal digits
+ *             only, within the bounds above; names get their ids in order of first appearance.  Anything else:
+ *             FADEHIP_E_INVALID, fadehip_last_error names the 1-based line.  The file is read in pieces and never stands in
+ *             memory as text.  A path ending in .gz or .bgz is refused by name (FADEHIP_E_INVALID): plain text only.
+ * The calls are synchronous and take the lock fadehip_clip_batch takes.  A sealed set never changes: any number of streams
+ * and calls may read it at once.  The raw arrays grow by doubling, with a copy on the device; a device allocation that
+ * fails is FADEHIP_E_NOMEM; more than 2^31 - 1 intervals is FADEHIP_E_UNSUPPORTED.  destroy comes after every stream that
+ * uses the set has been closed, and before fadehip_destroy.  Environment, read at create: FADEHIP_INTERVALS_CAP=N, the
+ * intervals the first arrays hold (default 1 Mi, at least 16).  Results do not depend on it. */
+typedef struct fadehip_intervals fadehip_intervals;
+int fadehip_intervals_create(fadehip_ctx *ctx, int32_t n_chrom, const char *const *chrom_names, fadehip_intervals **out);
+int fadehip_intervals_add(fadehip_intervals *s, int64_t n, const int32_t *chrom, const int64_t *start, const int64_t *end);
+int fadehip_intervals_seal(fadehip_intervals *s);
+int fadehip_intervals_count(fadehip_intervals *s, int64_t *n_intervals, int32_t *n_chrom);
+int fadehip_intervals_overlap_batch(fadehip_intervals *s, int64_t n, const int32_t *chrom, const int64_t *start, const int64_t *end, uint8_t *hit /* [n] */);
+int fadehip_intervals_load_bed(fadehip_ctx *ctx, const char *path, fadehip_intervals **out);
+void fadehip_intervals_destroy(fadehip_intervals *s);
+
+/* fadehip_report_batch's stats rows (which = FADEHIP_BAM_REPORT_STATS) with a sealed set of intervals: every row keeps its
+ * 21 columns byte for byte and gains "\tread_rpm\tart_rpm", each 0 or 1 — read_rpm is the query (rname, art_start, art_end),
+ * art_rpm the query (aln_rname, aln_start, aln_end), in exactly the values the row prints.  A contig is matched to the set by
+ * its name's bytes: rname through ref_names, aln_rname by its bytes as they stand in am, also when ref_names does not carry
+ * that name.  A name the set does not hold hits nothing.  The rule is per row.  A set that is not sealed, or of another ctx:
+ * FADEHIP_E_INVALID.  Everything else as fadehip_report_batch. */
+int fadehip_report_batch_repeats(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const int64_t *rec_off, int32_t n_ref, const char *const *ref_names,
+                                 fadehip_intervals *intervals, uint8_t *out, int64_t out_cap, int64_t *row_off /* [2n + 1] */);
+
 /* ------------------------------------------------------ Level 2: annotateTask over a batch -- */
 /* Upload the indexed FASTA once (what IndexedFastaFile + fetchSequence serve, analysis.d:63).
  * seqs[c] holds lengths[c] ASCII residues (any case; upper-cased on device as analysis.d:63 does).
@@ -707,7 +751,11 @@ typedef struct fadehip_bam_config {
                                    * into the record store attached with fadehip_bam_use_recstore (none attached: the first front
                                    * call fails with FADEHIP_E_STATE), in stream order, and stay on the device: no copy to the
                                    * host is made, and fadehip_bam_back_extract gives 0 bytes and the number of records the call
-                                   * added.  No other output byte changes.  A store that has been sorted: FADEHIP_E_STATE */
+                                   * added.  No other output byte changes.  A store that has been sorted: FADEHIP_E_STATE;
+                                   * FADEHIP_BAM_REPORT_REPEATS: only with REPORT_STATS (else FADEHIP_E_INVALID at fadehip_bam_open)
+                                   * and wherever it stands: the stats rows gain the two columns of fadehip_report_batch_repeats,
+                                   * against the sealed set attached with fadehip_bam_use_intervals (none attached: the first
+                                   * front call fails with FADEHIP_E_STATE).  The clip report's rows do not change */
     const char *const *ref_names; /* [n_ref] NUL-terminated */
     uint32_t first_record;        /* payload bytes of the first member passed to front that precede the first record */
     uint32_t tail_trim;           /* payload bytes at the END of the last member (front's last call) that are not this stream's:
@@ -730,6 +778,7 @@ typedef struct fadehip_bam_config {
 #define FADEHIP_BAM_COLLECT_MATES 8192
 #define FADEHIP_BAM_FIX_MATES 16384
 #define FADEHIP_BAM_STORE_EXTRACT 32768
+#define FADEHIP_BAM_REPORT_REPEATS 65536
 int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_bam_stream **out);
 /* The set a stream opened with FADEHIP_BAM_COLLECT_NAMES adds to, or one opened with FADEHIP_BAM_EJECT_NAMED looks names up
  * in: a set of the same ctx, attached before the first front call (later: FADEHIP_E_STATE).  The set is the caller's and
@@ -745,6 +794,10 @@ int fadehip_bam_mates(fadehip_bam_stream *st, int64_t *n_fixed, int64_t *n_ambig
  * attached before the first front call (later: FADEHIP_E_STATE).  The store is the caller's and outlives the stream; it is
  * sorted and drained after the stream's last back call. */
 int fadehip_bam_use_recstore(fadehip_bam_stream *st, fadehip_recstore *s);
+/* The set of intervals a stream opened with FADEHIP_BAM_REPORT_REPEATS queries: a SEALED set of the same ctx (not sealed:
+ * FADEHIP_E_INVALID), attached before the first front call (later: FADEHIP_E_STATE).  The set is the caller's and outlives
+ * the stream; several streams may share it. */
+int fadehip_bam_use_intervals(fadehip_bam_stream *st, fadehip_intervals *s);
 int fadehip_bam_prepare(fadehip_bam_stream *st, size_t call_bytes);
 int fadehip_bam_front(fadehip_bam_stream *st, const void *members, size_t n_bytes, int last);
 /* front for a caller that inflates itself (host cores otherwise idle; the device then spends its time on the rest):
