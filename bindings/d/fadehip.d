@@ -209,6 +209,18 @@ int fadehip_recstore_count(fadehip_recstore* s, long* n_records, long* n_bytes);
 int fadehip_recstore_sort(fadehip_recstore* s);
 int fadehip_recstore_drain(fadehip_recstore* s, int flags, ulong max_payload, const(ubyte)** out_, size_t* out_bytes, long* n_records, fadehip_index_call* idx);
 void fadehip_recstore_destroy(fadehip_recstore* s);
+/// the sorted main output (FADEHIP_BAM_STORE_OUTPUT streams): the most the store may cost, bytes + 64 per record (0: derived
+/// from the device's free memory; FADEHIP_RECSTORE_BUDGET overrides); the bucket table over the header's contig lengths, from
+/// which the windows of a file that does not fit are cut, and whether the measured pass went over the budget; the window of
+/// keys a pass keeps, both ends inclusive; reset empties the store for the next window, sized once for what is coming
+int fadehip_recstore_set_budget(fadehip_recstore* s, ulong bytes);
+int fadehip_recstore_budget(fadehip_recstore* s, ulong* bytes);  /// the budget in force; 0: none set
+int fadehip_recstore_measure(fadehip_recstore* s, int n_ref, const(long)* ref_len);
+int fadehip_recstore_over(fadehip_recstore* s, int* over);
+int fadehip_recstore_resets(fadehip_recstore* s, long* n_reset);  /// reset records (zero-filled, sorted last) the STORE_OUTPUT streams wrote: a file that ends in them cannot be indexed
+int fadehip_recstore_histogram(fadehip_recstore* s, ulong* bytes, ulong* records, long* n_buckets);
+int fadehip_recstore_set_window(fadehip_recstore* s, ulong lo_key, ulong hi_key_inclusive);
+int fadehip_recstore_reset(fadehip_recstore* s, ulong bytes, ulong records);
 
 /// A set of genomic intervals on the device and the overlap query over it (what `bedtools subtract -A` against a RepeatMasker
 /// BED decides): intervals (chrom, start, end), chrom an index into the names given at create, 0-based half-open,
@@ -287,7 +299,8 @@ int fadehip_bam_open(fadehip_ctx* ctx, const(fadehip_bam_config)* cfg, fadehip_b
 int fadehip_bam_use_nameset(fadehip_bam_stream* st, fadehip_nameset* s);
 int fadehip_bam_use_mateset(fadehip_bam_stream* st, fadehip_mateset* s);
 int fadehip_bam_mates(fadehip_bam_stream* st, long* n_fixed, long* n_ambiguous);
-/// the store of the same ctx a STORE_EXTRACT stream appends its extract records to; before the first front call
+enum FADEHIP_BAM_STORE_OUTPUT = 131072;  /// ... the calls' OUTPUT records go into the attached record store and stay on the device: sorted and drained there, they are the stream's records in coordinate order as they leave; fadehip_bam_back gives 0 bytes.  With the annotate path, FROM_TAGS, CLIP, EJECT, EJECT_GROUPS, EJECT_NAMED, FIX_MATES only
+/// the store of the same ctx a STORE_EXTRACT stream appends its extract records to, or a STORE_OUTPUT stream its output records; before the first front call
 int fadehip_bam_use_recstore(fadehip_bam_stream* st, fadehip_recstore* s);
 enum FADEHIP_BAM_REPORT_REPEATS = 65536;  /// ... with REPORT_STATS: the stats rows gain read_rpm and art_rpm against the attached set of intervals (fadehip_bam_use_intervals)
 /// the sealed set of the same ctx a REPORT_REPEATS stream queries; before the first front call

@@ -43,6 +43,8 @@ EXPORTS = [
     "fadehip_bam_use_mateset", "fadehip_bam_mates",
     "fadehip_recstore_create", "fadehip_recstore_add_batch", "fadehip_recstore_count", "fadehip_recstore_sort", "fadehip_recstore_drain",
     "fadehip_recstore_destroy", "fadehip_bam_use_recstore",
+    "fadehip_recstore_set_budget", "fadehip_recstore_measure", "fadehip_recstore_over", "fadehip_recstore_histogram",
+    "fadehip_recstore_set_window", "fadehip_recstore_reset", "fadehip_recstore_budget", "fadehip_recstore_resets",
     "fadehip_intervals_create", "fadehip_intervals_add", "fadehip_intervals_seal", "fadehip_intervals_count", "fadehip_intervals_overlap_batch",
     "fadehip_intervals_load_bed", "fadehip_intervals_destroy", "fadehip_report_batch_repeats", "fadehip_bam_use_intervals",
 ]
@@ -54,6 +56,7 @@ BAM_INDEX = 4096  # every call leaves the .bai entries of the records it writes 
 BAM_COLLECT_MATES, BAM_FIX_MATES = 8192, 16384  # mate fields that follow the hard clip: a MateSet attached (fadehip_bam_use_mateset)
 BAM_STORE_EXTRACT = 32768  # with BAM_EXTRACT: the extract records go into a RecStore attached (fadehip_bam_use_recstore), not to the host
 BAM_REPORT_REPEATS = 65536  # with BAM_REPORT_STATS: the rows gain read_rpm and art_rpm against an IntervalSet attached (fadehip_bam_use_intervals)
+BAM_STORE_OUTPUT = 131072  # the OUTPUT records go into a RecStore attached (fadehip_bam_use_recstore): sorted and drained there, back hands out nothing
 RECSTORE_RAW, RECSTORE_STORED, RECSTORE_INDEX = 1, 2, 4  # fadehip_recstore_drain's flags
 BGZF_BLOCK = 0xff00
 BGZF_LANES = 2
@@ -189,6 +192,14 @@ def load():
     L.fadehip_recstore_destroy.argtypes = [vp]
     L.fadehip_recstore_destroy.restype = None
     L.fadehip_bam_use_recstore.argtypes = [vp, vp]
+    L.fadehip_recstore_set_budget.argtypes = [vp, C.c_uint64]
+    L.fadehip_recstore_budget.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.fadehip_recstore_measure.argtypes = [vp, i32, vp]
+    L.fadehip_recstore_over.argtypes = [vp, C.POINTER(i32)]
+    L.fadehip_recstore_resets.argtypes = [vp, C.POINTER(i64)]
+    L.fadehip_recstore_histogram.argtypes = [vp, vp, vp, C.POINTER(i64)]
+    L.fadehip_recstore_set_window.argtypes = [vp, C.c_uint64, C.c_uint64]
+    L.fadehip_recstore_reset.argtypes = [vp, C.c_uint64, C.c_uint64]
     L.fadehip_intervals_create.argtypes = [vp, i32, C.POINTER(C.c_char_p), C.POINTER(vp)]
     L.fadehip_intervals_add.argtypes = [vp, i64, vp, vp, vp]
     L.fadehip_intervals_seal.argtypes = [vp]

@@ -549,7 +549,7 @@ class Context:
         return self.bgzf_deflate_wait(lane)
 
     def bam_stream(self, ref_names, floor_len=5, window=300, first_record=0, stored=False, tail_trim=0, no_output=False, clip=False, extract=False, eject=None, from_tags=False,
-                   collect_names=None, eject_named=None, keep_sorted=False, report=None, index=False, collect_mates=None, fix_mates=False, mateset=None, recstore=None, repeats=None):
+                   collect_names=None, eject_named=None, keep_sorted=False, report=None, index=False, collect_mates=None, fix_mates=False, mateset=None, recstore=None, repeats=None, store_output=None):
         """The file path on the device (fadehip_bam_*): BGZF members of a BAM's records in, BGZF members of the annotated
         records out.  ref_names: the BAM header's contigs (the genome must be uploaded).  clip: records called artifacts leave
         hard-clipped (`fade annotate -c`).  extract: every call also builds `fade extract`'s records of its artifact calls
@@ -580,9 +580,13 @@ class Context:
         and drained once the stream has ended (`fade extract --sorted`, `fade annotate --extract-sorted`).  True instead of a
         store sets the flag alone (the first front() then fails).  repeats (a sealed IntervalSet of this context; with
         report "stats" or "both"): the stats rows gain read_rpm and art_rpm (`fade stats --repeats`).  True instead of a set
-        sets the flag alone (the first front() then fails)."""
+        sets the flag alone (the first front() then fails).  store_output (a RecStore of this context; with the annotate path
+        or from_tags, beside them clip, eject, eject_named and fix_mates only): the records the stream would write stay on the
+        device, appended to the store in stream order — back() then gives no bytes — to be sorted and drained once the stream
+        has ended: the stream's records in coordinate order as they leave, whatever the input's order.  The store's budget,
+        bucket table and window apply (RecStore.set_budget, measure, set_window).  True instead of a store sets the flag alone."""
         return BamStream(self, ref_names, floor_len, window, first_record, stored, tail_trim, no_output, clip, extract, eject, from_tags,
-                         collect_names, eject_named, keep_sorted, report, index, collect_mates, fix_mates, mateset, recstore, repeats)
+                         collect_names, eject_named, keep_sorted, report, index, collect_mates, fix_mates, mateset, recstore, repeats, store_output)
 
     def bgzf_inflate(self, members, out_cap=None):
         """Whole BGZF members (bytes / uint8 array) -> their payloads, inflated on the device (CRC32 and ISIZE checked)."""
@@ -766,7 +770,7 @@ def format_tags(batch, contig_names, rs, aln):
 
 class BamStream:
     def __init__(self, ctx, ref_names, floor_len, window, first_record, stored=False, tail_trim=0, no_output=False, clip=False, extract=False, eject=None, from_tags=False,
-                 collect_names=None, eject_named=None, keep_sorted=False, report=None, index=False, collect_mates=None, fix_mates=False, mateset=None, recstore=None, repeats=None):
+                 collect_names=None, eject_named=None, keep_sorted=False, report=None, index=False, collect_mates=None, fix_mates=False, mateset=None, recstore=None, repeats=None, store_output=None):
         self._ctx, self._L = ctx, ctx._L
         if report not in (None, "stats", "clip", "both"):
             raise ValueError('report is None, "stats", "clip" or "both"')
@@ -779,7 +783,7 @@ class BamStream:
         cfg = _lib.BamConfig(floor_len, window, len(names), (_lib.BAM_STORED if stored else 0) | (_lib.BAM_NO_OUTPUT if no_output else 0) | (_lib.BAM_CLIP if clip else 0) | (_lib.BAM_EXTRACT if extract else 0) | (BAM_FROM_TAGS if from_tags else 0) | ej |
                              (_lib.BAM_COLLECT_NAMES if collect_names else 0) | (_lib.BAM_EJECT_NAMED if eject_named else 0) | (_lib.BAM_KEEP_SORTED if keep_sorted else 0) | rp | (_lib.BAM_INDEX if index else 0) |
                              (_lib.BAM_COLLECT_MATES if collect_mates else 0) | (_lib.BAM_FIX_MATES if fix_mates else 0) | (_lib.BAM_STORE_EXTRACT if recstore else 0) |
-                             (_lib.BAM_REPORT_REPEATS if repeats else 0), arr, first_record, tail_trim)
+                             (_lib.BAM_REPORT_REPEATS if repeats else 0) | (_lib.BAM_STORE_OUTPUT if store_output else 0), arr, first_record, tail_trim)
         h = C.c_void_p()
         ctx._chk(self._L.fadehip_bam_open(ctx._h, C.byref(cfg), C.byref(h)))
         self._h = h
@@ -800,12 +804,13 @@ class BamStream:
                 ctx._chk(rc)
             self._mates = mateset
         self._recstore = None
-        if isinstance(recstore, RecStore):
-            rc = self._L.fadehip_bam_use_recstore(self._h, recstore._h)
-            if rc:
-                self.close()
-                ctx._chk(rc)
-            self._recstore = recstore  # (the store outlives the stream)
+        for store in (recstore, store_output):
+            if isinstance(store, RecStore):
+                rc = self._L.fadehip_bam_use_recstore(self._h, store._h)
+                if rc:
+                    self.close()
+                    ctx._chk(rc)
+                self._recstore = store  # (the store outlives the stream)
         self._repeats = None
         if isinstance(repeats, IntervalSet):
             rc = self._L.fadehip_bam_use_intervals(self._h, repeats._h)
@@ -985,6 +990,51 @@ class RecStore:
         self._ctx._chk(self._L.fadehip_recstore_drain(self._h, flags, int(max_payload), C.byref(p), C.byref(n), C.byref(nr), C.byref(c) if index else None))
         out = C.string_at(p, n.value) if n.value else b""
         return (out, int(nr.value), index_call_dict(c)) if index else (out, int(nr.value))
+
+    # ---- the sorted main output (streams opened with store_output=...; DESIGN.md 3.8n, tests/sorted_out_model.py)
+    def set_budget(self, nbytes=0):
+        """The most the store may cost, bytes + 64 per record; 0: derived from the device's free memory.  FADEHIP_RECSTORE_BUDGET
+        in the environment overrides either."""
+        self._ctx._chk(self._L.fadehip_recstore_set_budget(self._h, int(nbytes)))
+
+    def budget(self):
+        """The budget in force (derived, given or from the environment); 0: none set."""
+        v = C.c_uint64(0)
+        self._ctx._chk(self._L.fadehip_recstore_budget(self._h, C.byref(v)))
+        return int(v.value)
+
+    def measure(self, ref_len):
+        """ref_len: the header's contig lengths.  From now until reset(), store_output streams add what they write to the
+        bucket table, and a call that would take the store over its budget sends it over() instead of failing."""
+        arr = np.ascontiguousarray(ref_len, dtype=np.int64)
+        self._ctx._chk(self._L.fadehip_recstore_measure(self._h, len(arr), arr.ctypes.data if len(arr) else None))
+
+    def over(self):
+        v = C.c_int32(0)
+        self._ctx._chk(self._L.fadehip_recstore_over(self._h, C.byref(v)))
+        return bool(v.value)
+
+    def resets(self):
+        """Reset records (reads a clip left nothing of) among what store_output streams have finished since create or reset."""
+        v = C.c_int64(0)
+        self._ctx._chk(self._L.fadehip_recstore_resets(self._h, C.byref(v)))
+        return int(v.value)
+
+    def histogram(self):
+        """(bytes per bucket, records per bucket), as lists."""
+        n = C.c_int64(0)
+        self._ctx._chk(self._L.fadehip_recstore_histogram(self._h, None, None, C.byref(n)))
+        b, r = np.zeros(n.value, dtype=np.uint64), np.zeros(n.value, dtype=np.uint64)
+        self._ctx._chk(self._L.fadehip_recstore_histogram(self._h, b.ctypes.data, r.ctypes.data, C.byref(n)))
+        return [int(x) for x in b], [int(x) for x in r]
+
+    def set_window(self, lo_key, hi_key):
+        """store_output streams keep the records whose key lies in [lo_key, hi_key], both inclusive."""
+        self._ctx._chk(self._L.fadehip_recstore_set_window(self._h, int(lo_key), int(hi_key)))
+
+    def reset(self, nbytes=0, records=0):
+        """Empties the store, sorted or not, and ends measuring; sized once for what is coming."""
+        self._ctx._chk(self._L.fadehip_recstore_reset(self._h, int(nbytes), int(records)))
 
     def close(self):
         if self._h:

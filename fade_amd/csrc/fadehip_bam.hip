@@ -11,6 +11,7 @@
 #include "bam_resort.hpp"
 #include "bam_index.hpp"
 #include "bam_recstore.hpp"
+#include "bam_sortwin.hpp"
 #include "bam_intervals.hpp"
 #include "host/bai_build.hpp"
 #include "host/recstore_host.hpp"
@@ -73,6 +74,15 @@ struct fadehip_recstore {
     bam::IndexCtl ixc;                // a drain's index ctl as it crosses (a member: the copy may outlive a call that fails)
     PinBuf h_out;                     // what a drain hands out: the raw records or the members
     std::vector<uint8_t> h_ix;        // the arrays *idx points into, until the next drain
+    // the sorted main output (bam_sortwin.hpp): none of it is set on a store that only collects extract records
+    bool budget_set = false;          // fadehip_recstore_set_budget has been called
+    uint64_t budget = 0;              // the most cost(used, n_items) may be
+    bool measuring = false, over = false;  // fadehip_recstore_measure .. _reset; a call took the cost over the budget meanwhile
+    recstore::BucketLayout lay;       // measure's buckets
+    bool have_table = false;
+    DevBuf table, lay_dev;            // bytes [n_buckets] | records [n_buckets]; first [n_ref] | nb [n_ref]
+    uint64_t win_lo = 0, win_hi = ~(uint64_t)0;  // fadehip_recstore_set_window
+    uint64_t n_reset = 0;             // reset records (written zero-filled, keyed as unmapped) among what STORE_OUTPUT streams wrote or measured since create / reset
 };
 
 // A set of intervals on the device (bam_intervals.hpp).  The host's part: the contigs' names and their ids, the raw items
@@ -1018,6 +1028,7 @@ struct fadehip_bam_stream {
     fadehip_nameset *names = nullptr;  // fadehip_bam_use_nameset
     fadehip_mateset *mates = nullptr;  // fadehip_bam_use_mateset
     bool store_extract = false;  // FADEHIP_BAM_STORE_EXTRACT: extract, and the calls' extract records stay on the device, in `recstore` (bam_recstore.hpp)
+    bool store_output = false;   // FADEHIP_BAM_STORE_OUTPUT: the calls' OUTPUT records stay on the device, in `recstore` (bam_sortwin.hpp); back hands out nothing
     fadehip_recstore *recstore = nullptr;  // fadehip_bam_use_recstore
     bool repeats = false;        // FADEHIP_BAM_REPORT_REPEATS: the stats rows gain read_rpm and art_rpm (bam_intervals.hpp)
     fadehip_intervals *intervals = nullptr;  // fadehip_bam_use_intervals
@@ -1062,7 +1073,8 @@ struct fadehip_bam_stream {
         DevBuf u;                             // the call's inflated bytes, the previous call's cut-off record in front
         DevBuf seg, slots, rec_off, info, sent_of, art_of, out_size, blk32, blk64, counts;
         DevBuf ex_size, ex_blk;               // extract: bytes per record, block sums and bases (the tag arrays' counterparts)
-        DevBuf rx_cnt;                        // store_extract: the append kernels' item counts per block, and their bases
+        DevBuf rx_cnt;                        // store_extract, store_output: the append kernels' item counts per block, and their bases
+        DevBuf sw_key;                        // store_output with clip: the keys the records leave with (bam_sortwin.hpp)
         DevBuf ej_head, ej_blk, ej_grp;       // eject: every record's group start, the blocks' last starts and carries, the groups' marks
         // from_tags: the stage's per-record arrays (rs byte, trims), per-side arrays (contig, position, ops, text), the ops'
         // block sums and bases, where a record's ops start, and the ops themselves (sized in back, when their total is known)
@@ -1517,13 +1529,21 @@ int recstore_room(fadehip_recstore *s, hipStream_t q, uint64_t bytes_new, uint64
     if (s->sorted) return set_err(ctx, FADEHIP_E_STATE, "recstore: the store has been sorted, nothing can be added to it any more");
     if (s->n_items + items_new > RECSTORE_MAX_ITEMS)
         return set_err(ctx, FADEHIP_E_UNSUPPORTED, "recstore: more than %llu records (the sort numbers its items in 32 bits)", (unsigned long long)RECSTORE_MAX_ITEMS);
+    if (s->budget_set && recstore::sortwin_cost(s->used + bytes_new, s->n_items + items_new) > s->budget)
+        return set_err(ctx, FADEHIP_E_NOMEM, "recstore: %llu bytes in %llu records would cost more than the budget of %llu bytes (the store holds every output record on the device)",
+                       (unsigned long long)(s->used + bytes_new), (unsigned long long)(s->n_items + items_new), (unsigned long long)s->budget);
     const bool grow_arena = s->used + bytes_new + 8 > (uint64_t)s->arena.cap, grow_items = s->n_items + items_new > s->item_cap;
     if (!grow_arena && !grow_items) return 0;
     HIPCHK(ctx, hipDeviceSynchronize());
     int rc;
-    if (grow_arena && (rc = recstore_regrow(ctx, q, s->arena, (size_t)s->used, (size_t)std::max<uint64_t>(2 * (uint64_t)s->arena.cap, s->used + bytes_new + 8)))) return rc;
+    // (under a budget a growth stops at what the budget lets the store hold: at most `budget` bytes, budget / 64 records)
+    const uint64_t need_bytes = s->used + bytes_new + 8, need_items = s->n_items + items_new;
+    uint64_t want_bytes = std::max<uint64_t>(2 * (uint64_t)s->arena.cap, need_bytes);
+    if (s->budget_set) want_bytes = std::max<uint64_t>(std::min<uint64_t>(want_bytes, s->budget + 8), need_bytes);
+    if (grow_arena && (rc = recstore_regrow(ctx, q, s->arena, (size_t)s->used, (size_t)want_bytes))) return rc;
     if (grow_items) {
-        const uint64_t cap = std::max<uint64_t>(std::max<uint64_t>(2 * s->item_cap, s->n_items + items_new), 1024);
+        uint64_t cap = std::max<uint64_t>(std::max<uint64_t>(2 * s->item_cap, need_items), 1024);
+        if (s->budget_set) cap = std::max<uint64_t>(std::min<uint64_t>(cap, std::max<uint64_t>(s->budget / recstore::SORTWIN_ITEM_COST, 1024)), need_items);
         if ((rc = recstore_regrow(ctx, q, s->key, 8 * (size_t)s->n_items, 8 * (size_t)cap)) || (rc = recstore_regrow(ctx, q, s->off, 8 * (size_t)s->n_items, 8 * (size_t)cap)) ||
             (rc = recstore_regrow(ctx, q, s->size, 4 * (size_t)s->n_items, 4 * (size_t)cap)))
             return rc;  // (an array that has grown already stays grown: it holds what it held)
@@ -1553,6 +1573,44 @@ int enqueue_recstore_append(fadehip_recstore *s, hipStream_t q, uint64_t base, u
     hipLaunchKernelGGL(bam::recstore_count_scan_kernel, dim3(1), dim3(1024), 0, q, a, ntb);
     HIPCHK(ctx, hipGetLastError());
     hipLaunchKernelGGL(bam::recstore_append_kernel, dim3(ntb), dim3(bam::TAG_BLOCK), 0, q, a);
+    HIPCHK(ctx, hipGetLastError());
+    return 0;
+}
+
+// FADEHIP_BAM_STORE_OUTPUT, B of a call behind the kernels that decide which records leave and in front of the scan of the
+// blocks' sums (bam_sortwin.hpp): the store's table, if it measures, and its window as they are now — both are set before a
+// pass begins.  S.ta and S.fa are the call's (the key follows the clip plan the rewrite will follow).
+int enqueue_sortwin(fadehip_bam_stream *st, fadehip_bam_stream::Set &S, hipStream_t q, uint32_t n_rec, uint32_t ntb, uint32_t *out_size, uint32_t *info, uint64_t *blk_sums) {
+    fadehip_ctx *ctx = st->ctx;
+    fadehip_recstore *rs = st->recstore;
+    bam::SortWinArgs a;
+    memset(&a, 0, sizeof a);
+    a.u = S.pa.u;
+    a.rec_off = S.pa.rec_off;
+    a.n = n_rec;
+    a.clip = st->clip ? 1u : 0u;
+    a.out_size = out_size;
+    a.info = info;
+    a.blk_sums = blk_sums;
+    a.counts = S.pa.counts;
+    if (st->clip) {
+        if (const int rc = reserve_roomy(ctx, S.sw_key, 8 * (size_t)n_rec)) return rc;
+        a.leave_key = (uint64_t *)S.sw_key.p;
+    }
+    {
+        std::lock_guard<std::mutex> sl(rs->mu);
+        if (rs->measuring) {
+            a.table = (unsigned long long *)rs->table.p;
+            a.first = (const uint32_t *)rs->lay_dev.p;
+            a.n_ref = (uint32_t)rs->lay.nb.size();
+            a.nb = a.first + a.n_ref;
+            a.n_buckets = rs->lay.n_buckets;
+        }
+        a.lo = rs->win_lo;
+        a.hi = rs->win_hi;
+    }
+    if (st->from_tags) hipLaunchKernelGGL(bam::bam_sortwin_kernel<true>, dim3(ntb), dim3(bam::TAG_BLOCK), 0, q, a, S.ta, S.fa);
+    else hipLaunchKernelGGL(bam::bam_sortwin_kernel<false>, dim3(ntb), dim3(bam::TAG_BLOCK), 0, q, a, S.ta, S.fa);
     HIPCHK(ctx, hipGetLastError());
     return 0;
 }
@@ -1713,7 +1771,29 @@ int bam_finish_one(fadehip_bam_stream *st, uint64_t k) {
             st->stats[0] += S.n_rec;
         }
         const uint64_t out_bytes = h_counts->out_bytes;
-        if (st->keep_sorted) {
+        std::unique_lock<std::mutex> store_lock;  // store_output: the store's, from the reservation until the append is enqueued
+        bool write = true;
+        if (st->store_output) {
+            // FADEHIP_BAM_STORE_OUTPUT: as bam_finish_extract does for the extract records — the call's bytes and records
+            // (pad2: what bam_sortwin_kernel counted) are reserved here, in call order and with numbers that have crossed to the
+            // host; the untouched rewrite kernel then writes at the arena's reserved place and the append kernels make the items.
+            // A store that measures goes OVER instead of failing: its contents are dropped and nothing more is written.
+            fadehip_recstore *rs = st->recstore;
+            const uint64_t n_keep = h_counts->pad2 & 0xffffffffull;
+            if (out_bytes > ((uint64_t)1 << 31)) return set_err(ctx, FADEHIP_E_UNSUPPORTED, "bam stream: %llu output bytes in one call (at most 2^31)", (unsigned long long)out_bytes);
+            store_lock = std::unique_lock<std::mutex>(rs->mu);
+            if (!rs->over && rs->measuring && rs->budget_set && recstore::sortwin_cost(rs->used + out_bytes, rs->n_items + n_keep) > rs->budget) {
+                rs->over = true;
+                rs->used = 0;
+                rs->n_items = 0;
+            }
+            write = !rs->over;
+            if (write) {
+                if ((rc = recstore_room(rs, q, out_bytes, n_keep)) || (rc = reserve_roomy(ctx, S.rx_cnt, 8 * (size_t)S.ntb + 8))) return rc;
+                S.ta.o = (uint8_t *)rs->arena.p + rs->used;
+                S.fa.o = S.ta.o;
+            }
+        } else if (st->keep_sorted) {
             // the order check first: nothing of a call that fails it is written.  The rewrite then goes to the staging bytes,
             // from where the move takes the records; what leaves is sized there
             const unsigned long long bad = ((const bam::ResortCtl *)S.h_rs.p)->bad;
@@ -1730,7 +1810,8 @@ int bam_finish_one(fadehip_bam_stream *st, uint64_t k) {
             S.ta.o = (uint8_t *)out->o.p;
             S.fa.o = (uint8_t *)out->o.p;
         }
-        if (st->fix_mates) {  // (under the set's lock: the arena may have moved since the plan, and must not move before this launch has run)
+        if (!write) {
+        } else if (st->fix_mates) {  // (under the set's lock: the arena may have moved since the plan, and must not move before this launch has run)
             fadehip_nameset *ms = &st->mates->core;
             std::lock_guard<std::mutex> ml(ms->mu);
             S.fa.ms = nameset_ref(ms);
@@ -1742,6 +1823,30 @@ int bam_finish_one(fadehip_bam_stream *st, uint64_t k) {
         else hipLaunchKernelGGL(bam::bam_rewrite_kernel<false>, dim3(S.ntb), dim3(bam::REWRITE_WAVES * 64), 0, q, S.ta);
         HIPCHK(ctx, hipGetLastError());
         out->bytes = (size_t)out_bytes;
+        if (st->store_output) {
+            fadehip_recstore *rs = st->recstore;
+            const uint32_t n_keep = (uint32_t)h_counts->pad2;
+            rs->n_reset += h_counts->pad2 >> 32;
+            if (write && n_keep) {
+                if ((rc = enqueue_recstore_append(rs, q, rs->used, rs->n_items, S.n_rec, n_keep, (const uint32_t *)S.out_size.p, (const uint64_t *)S.blk64.p + S.ntb, (uint32_t *)S.rx_cnt.p))) return rc;
+                if (st->clip) {  // (a reset record's item: the key it leaves with, not the one its zero-filled bytes spell)
+                    bam::RecAppendArgs ka;
+                    memset(&ka, 0, sizeof ka);
+                    ka.s = recstore_ref(rs);
+                    ka.item0 = rs->n_items;
+                    ka.n = S.n_rec;
+                    ka.n_items = n_keep;
+                    ka.x_size = (const uint32_t *)S.out_size.p;
+                    ka.cnt_base = (uint32_t *)S.rx_cnt.p + S.ntb;
+                    hipLaunchKernelGGL(bam::bam_sortwin_rekey_kernel, dim3(S.ntb), dim3(bam::TAG_BLOCK), 0, q, ka, (const uint64_t *)S.sw_key.p);
+                    HIPCHK(ctx, hipGetLastError());
+                }
+                rs->used += out_bytes;
+                rs->n_items += n_keep;
+            }
+            store_lock.unlock();
+            out->bytes = 0;  // (nothing for the compressor: back hands out 0 bytes)
+        }
         std::lock_guard<std::mutex> l(st->mu);
         st->n_records += S.n_rec;
         st->n_ejected += h_counts->n_ejected;
@@ -1768,7 +1873,7 @@ int bam_finish_one(fadehip_bam_stream *st, uint64_t k) {
 // their order (they are anyway: back takes them in order, and front finishes k - 2 before k - 1 exists; this says so).
 int bam_finish_call(fadehip_bam_stream *st, uint64_t k) {
     int rc;
-    if ((st->keep_sorted || st->store_extract) && k && (rc = bam_finish_one(st, k - 1))) return rc;  // (store_extract: a call's place in the store is handed out when it is finished)
+    if ((st->keep_sorted || st->store_extract || st->store_output) && k && (rc = bam_finish_one(st, k - 1))) return rc;  // (store_extract: a call's place in the store is handed out when it is finished)
     return bam_finish_one(st, k);
 }
 
@@ -1966,8 +2071,10 @@ int bam_enqueue_sizes(fadehip_bam_stream *st, fadehip_bam_stream::Set &S, Slot &
     if (st->clip) hipLaunchKernelGGL(bam::bam_tag_size_kernel<true>, dim3(ntb), dim3(bam::TAG_BLOCK), 0, q, ta);
     else hipLaunchKernelGGL(bam::bam_tag_size_kernel<false>, dim3(ntb), dim3(bam::TAG_BLOCK), 0, q, ta);
     HIPCHK(ctx, hipGetLastError());
-    // (eject: the scan comes behind the eject kernels, which come behind the extract sizes — see below)
+    // (eject: the scan comes behind the eject kernels, which come behind the extract sizes — see below; store_output: behind
+    // the window kernel, which comes behind those)
     if (!st->eject) {
+        if (st->store_output && (rc = enqueue_sortwin(st, S, q, n_rec, ntb, ta.out_size, pa.info, ta.blk_sums))) return rc;
         hipLaunchKernelGGL(bam::bam_tag_scan_kernel, dim3(1), dim3(1024), 0, q, ta, ntb);
         HIPCHK(ctx, hipGetLastError());
     }
@@ -2011,6 +2118,7 @@ int bam_enqueue_sizes(fadehip_bam_stream *st, fadehip_bam_stream::Set &S, Slot &
             ea.grp = (uint32_t *)S.ej_grp.p;
         }
         if ((rc = enqueue_eject(ctx, q, ea, ntb, st->eject_groups))) return rc;
+        if (st->store_output && (rc = enqueue_sortwin(st, S, q, n_rec, ntb, ta.out_size, pa.info, ta.blk_sums))) return rc;
         hipLaunchKernelGGL(bam::bam_tag_scan_kernel, dim3(1), dim3(1024), 0, q, ta, ntb);
         HIPCHK(ctx, hipGetLastError());
     }
@@ -2248,6 +2356,7 @@ int bam_front_tags(fadehip_bam_stream *st, fadehip_bam_stream::Set &S, Slot &s, 
         }
         HIPCHK(ctx, hipMemcpyAsync(S.h_ns.p + 32, ms->ctrl.p, 32, hipMemcpyDeviceToHost, q));
     }
+    if (st->store_output && (rc = enqueue_sortwin(st, S, q, n_rec, ntb, fa.out_size, pa.info, fa.blk_sums))) return rc;
     hipLaunchKernelGGL(bam::bam_tag_scan_kernel, dim3(1), dim3(1024), 0, q, ta, ntb);
     HIPCHK(ctx, hipGetLastError());
     if (st->report) {  // the reports' stage (bam_report.hpp); its ctl crosses with the counts
@@ -2290,6 +2399,8 @@ int bam_front_impl(fadehip_bam_stream *st, const uint8_t *members, size_t n_byte
         return set_err(ctx, FADEHIP_E_STATE, "bam stream: opened with FADEHIP_BAM_REPORT_REPEATS and no set of intervals attached (fadehip_bam_use_intervals)");
     if (st->store_extract && !st->recstore)
         return set_err(ctx, FADEHIP_E_STATE, "bam stream: opened with FADEHIP_BAM_STORE_EXTRACT and no record store attached (fadehip_bam_use_recstore)");
+    if (st->store_output && !st->recstore)
+        return set_err(ctx, FADEHIP_E_STATE, "bam stream: opened with FADEHIP_BAM_STORE_OUTPUT and no record store attached (fadehip_bam_use_recstore)");
     if ((st->collect_mates || st->fix_mates) && !st->mates)
         return set_err(ctx, FADEHIP_E_STATE, "bam stream: opened with FADEHIP_BAM_%s and no mate set attached (fadehip_bam_use_mateset)", st->collect_mates ? "COLLECT_MATES" : "FIX_MATES");
     if (k >= 2 && (rc = bam_finish_call(st, k - 2))) return rc;
@@ -2344,8 +2455,20 @@ int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_ba
     if (!cfg || !out || cfg->n_ref < 0 || (cfg->n_ref && !cfg->ref_names) || (cfg->window < 0 && !(cfg->flags & FADEHIP_BAM_FROM_TAGS)) ||
         (cfg->flags & ~(FADEHIP_BAM_STORED | FADEHIP_BAM_NO_OUTPUT | FADEHIP_BAM_CLIP | FADEHIP_BAM_EXTRACT | FADEHIP_BAM_EJECT | FADEHIP_BAM_EJECT_GROUPS | FADEHIP_BAM_FROM_TAGS |
                         FADEHIP_BAM_COLLECT_NAMES | FADEHIP_BAM_EJECT_NAMED | FADEHIP_BAM_KEEP_SORTED | FADEHIP_BAM_REPORT_STATS | FADEHIP_BAM_REPORT_CLIP | FADEHIP_BAM_INDEX |
-                        FADEHIP_BAM_COLLECT_MATES | FADEHIP_BAM_FIX_MATES | FADEHIP_BAM_STORE_EXTRACT | FADEHIP_BAM_REPORT_REPEATS)))
+                        FADEHIP_BAM_COLLECT_MATES | FADEHIP_BAM_FIX_MATES | FADEHIP_BAM_STORE_EXTRACT | FADEHIP_BAM_REPORT_REPEATS | FADEHIP_BAM_STORE_OUTPUT)))
         return set_err(ctx, FADEHIP_E_INVALID, "bam stream: bad configuration");
+    if (cfg->flags & FADEHIP_BAM_STORE_OUTPUT) {
+        // the store takes the records a stream writes, and gives them an order of its own: what writes nothing, what writes
+        // elsewhere and what keeps or indexes the stream's own order do not stand beside it
+        static const struct { int32_t flag; const char *name; } no[] = {
+            {FADEHIP_BAM_NO_OUTPUT, "FADEHIP_BAM_NO_OUTPUT"}, {FADEHIP_BAM_STORED, "FADEHIP_BAM_STORED"}, {FADEHIP_BAM_KEEP_SORTED, "FADEHIP_BAM_KEEP_SORTED"},
+            {FADEHIP_BAM_INDEX, "FADEHIP_BAM_INDEX"}, {FADEHIP_BAM_STORE_EXTRACT, "FADEHIP_BAM_STORE_EXTRACT"}, {FADEHIP_BAM_EXTRACT, "FADEHIP_BAM_EXTRACT"},
+            {FADEHIP_BAM_COLLECT_NAMES, "FADEHIP_BAM_COLLECT_NAMES"}, {FADEHIP_BAM_COLLECT_MATES, "FADEHIP_BAM_COLLECT_MATES"},
+            {FADEHIP_BAM_REPORT_REPEATS, "FADEHIP_BAM_REPORT_REPEATS"}, {FADEHIP_BAM_REPORT_STATS, "FADEHIP_BAM_REPORT_STATS"}, {FADEHIP_BAM_REPORT_CLIP, "FADEHIP_BAM_REPORT_CLIP"}};
+        for (const auto &f : no)
+            if (cfg->flags & f.flag)
+                return set_err(ctx, FADEHIP_E_INVALID, "bam stream: FADEHIP_BAM_STORE_OUTPUT does not combine with %s (it stands with FROM_TAGS, CLIP, EJECT, EJECT_GROUPS, EJECT_NAMED and FIX_MATES)", f.name);
+    }
     if ((cfg->flags & FADEHIP_BAM_REPORT_REPEATS) && !(cfg->flags & FADEHIP_BAM_REPORT_STATS))
         return set_err(ctx, FADEHIP_E_INVALID, "bam stream: FADEHIP_BAM_REPORT_REPEATS needs FADEHIP_BAM_REPORT_STATS (it adds two columns to that report's rows)");
     if ((cfg->flags & FADEHIP_BAM_STORE_EXTRACT) && !(cfg->flags & FADEHIP_BAM_EXTRACT))
@@ -2360,7 +2483,8 @@ int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_ba
     }
     // (STORE_EXTRACT only says where EXTRACT's records go: it stands wherever EXTRACT does)
     fadehip_bam_config cfg_plain = *cfg;
-    cfg_plain.flags &= ~(FADEHIP_BAM_INDEX | FADEHIP_BAM_STORE_EXTRACT | FADEHIP_BAM_REPORT_REPEATS);  // (REPORT_REPEATS stands wherever REPORT_STATS does)
+    // (REPORT_REPEATS stands wherever REPORT_STATS does; STORE_OUTPUT only says where the output goes: what it excludes was refused above)
+    cfg_plain.flags &= ~(FADEHIP_BAM_INDEX | FADEHIP_BAM_STORE_EXTRACT | FADEHIP_BAM_REPORT_REPEATS | FADEHIP_BAM_STORE_OUTPUT);
     cfg = &cfg_plain;
     if (cfg->flags & (FADEHIP_BAM_REPORT_STATS | FADEHIP_BAM_REPORT_CLIP)) {
         const int32_t need = FADEHIP_BAM_FROM_TAGS | FADEHIP_BAM_NO_OUTPUT;
@@ -2415,6 +2539,7 @@ int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_ba
     st->report = ((cfg->flags & FADEHIP_BAM_REPORT_STATS) ? bam::RP_STATS : 0u) | ((cfg->flags & FADEHIP_BAM_REPORT_CLIP) ? bam::RP_CLIP : 0u);
     st->index = (all_flags & FADEHIP_BAM_INDEX) != 0;
     st->store_extract = (all_flags & FADEHIP_BAM_STORE_EXTRACT) != 0;
+    st->store_output = (all_flags & FADEHIP_BAM_STORE_OUTPUT) != 0;
     st->repeats = (all_flags & FADEHIP_BAM_REPORT_REPEATS) != 0;
     std::string text;
     std::vector<uint32_t> off((size_t)cfg->n_ref + 1, 0);
@@ -2477,7 +2602,7 @@ int fadehip_bam_use_recstore(fadehip_bam_stream *st, fadehip_recstore *s) {
     fadehip_ctx *ctx = st->ctx;
     if (!s) return set_err(ctx, FADEHIP_E_INVALID, "recstore is NULL");
     if (s->ctx != ctx) return set_err(ctx, FADEHIP_E_INVALID, "bam stream: the record store belongs to another ctx");
-    if (!st->store_extract) return set_err(ctx, FADEHIP_E_INVALID, "bam stream: opened without FADEHIP_BAM_STORE_EXTRACT");
+    if (!st->store_extract && !st->store_output) return set_err(ctx, FADEHIP_E_INVALID, "bam stream: opened without FADEHIP_BAM_STORE_EXTRACT or FADEHIP_BAM_STORE_OUTPUT");
     if (st->k_front) return set_err(ctx, FADEHIP_E_STATE, "bam stream: use_recstore comes before the first front call");
     st->recstore = s;
     return 0;
@@ -2526,7 +2651,7 @@ int fadehip_bam_prepare(fadehip_bam_stream *st, size_t call_bytes) {
     static const bool one_stream = getenv("FADEHIP_BAM_BACK_STREAMS") && atoi(getenv("FADEHIP_BAM_BACK_STREAMS")) == 1;
     int rcs[4] = {0, 0, 0, 0};
     std::string errs[4];
-    const bool with_out = !st->no_output;
+    const bool with_out = !st->no_output && !st->store_output;
     // lane 0 first on this thread when the lanes share a stream (lane 1 borrows it); the function attributes are set once, there
     if (with_out && (rcs[0] = bgzf_lane_ready(ctx, 0, one_stream))) return rcs[0];
     const double t_lane0 = now_s();
@@ -2934,7 +3059,7 @@ void fadehip_recstore_destroy(fadehip_recstore *s) {
     if (!s) return;
     (void)hipSetDevice(s->ctx->device);
     (void)hipDeviceSynchronize();
-    for (DevBuf *b : {&s->arena, &s->key, &s->off, &s->size, &s->sort_arr, &s->stage, &s->at, &s->app, &s->ix_work, &s->ix_ctl, &s->ix_out}) release(*b);
+    for (DevBuf *b : {&s->arena, &s->key, &s->off, &s->size, &s->sort_arr, &s->stage, &s->at, &s->app, &s->ix_work, &s->ix_ctl, &s->ix_out, &s->table, &s->lay_dev}) release(*b);
     release(s->h_out);
     delete s;
 }
@@ -2996,6 +3121,170 @@ int fadehip_recstore_count(fadehip_recstore *s, int64_t *n_records, int64_t *n_b
     std::lock_guard<std::mutex> sl(s->mu);
     *n_records = (int64_t)s->n_items;
     *n_bytes = (int64_t)s->used;
+    return 0;
+}
+
+// ---- the sorted main output's part of the store (bam_sortwin.hpp): budget, bucket table, window, reset
+int fadehip_recstore_set_budget(fadehip_recstore *s, uint64_t bytes) {
+    if (!s) return set_err(nullptr, FADEHIP_E_INVALID, "recstore is NULL");
+    fadehip_ctx *ctx = s->ctx;
+    std::lock_guard<std::mutex> sl(s->mu);
+    if (s->sorted || s->n_items) return set_err(ctx, FADEHIP_E_STATE, "recstore: set_budget takes an empty, unsorted store");
+    if (const char *e = getenv("FADEHIP_RECSTORE_BUDGET")) {
+        char *end = nullptr;
+        const unsigned long long v = strtoull(e, &end, 10);
+        if (end == e || *end || !v) return set_err(ctx, FADEHIP_E_INVALID, "recstore: FADEHIP_RECSTORE_BUDGET=%s is not a positive number of bytes", e);
+        bytes = v;
+    }
+    if (!bytes) {
+        // Two fifths of what is free now, less a reserve.  Under a budget the arena stops at `budget` bytes and the item arrays
+        // (20 bytes a record) at budget / 64 records.  A growth holds the old and the new buffer, and the old arena may be
+        // nearly as large as the new one (the last step is clamped to the budget, not a doubling): 2 x budget for the arena
+        // and 20/64 x budget for the item arrays beside it, 2.32 x budget in all.  When the item arrays grow instead it is
+        // 1 + 2 x 20/64, and at the sort, when nothing grows any more, 1 + 20/64 + 37/64: both less.  2.5 x budget bounds every
+        // moment (§3.8n).  The reserve is for what else a pass holds: the stream's two sets of call buffers and a drain's
+        // staging and members; assumed, not measured.
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(ctx, hipMemGetInfo(&free_b, &total_b));
+        const uint64_t reserve_b = std::min<uint64_t>((uint64_t)2 << 30, (uint64_t)free_b / 8);
+        bytes = ((uint64_t)free_b - reserve_b) / 5 * 2;
+        if (!bytes) return set_err(ctx, FADEHIP_E_NOMEM, "recstore: no device memory is free to derive a budget from");
+    }
+    s->budget = bytes;
+    s->budget_set = true;
+    return 0;
+}
+
+int fadehip_recstore_budget(fadehip_recstore *s, uint64_t *bytes) {
+    if (!s) return set_err(nullptr, FADEHIP_E_INVALID, "recstore is NULL");
+    if (!bytes) return set_err(s->ctx, FADEHIP_E_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> sl(s->mu);
+    *bytes = s->budget_set ? s->budget : 0;
+    return 0;
+}
+
+int fadehip_recstore_measure(fadehip_recstore *s, int32_t n_ref, const int64_t *ref_len) {
+    if (!s) return set_err(nullptr, FADEHIP_E_INVALID, "recstore is NULL");
+    fadehip_ctx *ctx = s->ctx;
+    if (n_ref < 0 || (n_ref > 0 && !ref_len)) return set_err(ctx, FADEHIP_E_INVALID, "NULL argument");
+    std::vector<uint32_t> len((size_t)n_ref);
+    for (int32_t r = 0; r < n_ref; r++) {
+        if (ref_len[r] < 0 || ref_len[r] > (int64_t)0xffffffffll) return set_err(ctx, FADEHIP_E_INVALID, "recstore: ref_len[%d] = %lld is no contig length", r, (long long)ref_len[r]);
+        len[(size_t)r] = (uint32_t)ref_len[r];
+    }
+    std::lock_guard<std::mutex> sl(s->mu);
+    if (s->sorted || s->n_items) return set_err(ctx, FADEHIP_E_STATE, "recstore: measure takes an empty, unsorted store");
+    if (s->have_table) return set_err(ctx, FADEHIP_E_STATE, "recstore: measure has been called already (the table stays until the store is destroyed)");
+    recstore::BucketLayout lay;
+    if (!recstore::bucket_layout(len.data(), len.size(), lay)) return set_err(ctx, FADEHIP_E_UNSUPPORTED, "recstore: the header's contigs make more than 2^32 buckets");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc;
+    const size_t tb = 16 * (size_t)lay.n_buckets, lb = 8 * len.size();
+    if ((rc = recstore_alloc(ctx, s->table, tb)) || (rc = recstore_alloc(ctx, s->lay_dev, lb))) {
+        release(s->table);
+        return rc;
+    }
+    // (on the ctx's copy stream, as the contig names of a stream are: no null stream is brought up)
+    if (hipMemsetAsync(s->table.p, 0, tb, ctx->copy_stream) != hipSuccess ||
+        (n_ref && (hipMemcpyAsync(s->lay_dev.p, lay.first.data(), lb / 2, hipMemcpyHostToDevice, ctx->copy_stream) != hipSuccess ||
+                   hipMemcpyAsync((uint8_t *)s->lay_dev.p + lb / 2, lay.nb.data(), lb / 2, hipMemcpyHostToDevice, ctx->copy_stream) != hipSuccess)) ||
+        hipStreamSynchronize(ctx->copy_stream) != hipSuccess) {
+        release(s->table);
+        release(s->lay_dev);
+        return set_err(ctx, FADEHIP_E_HIP, "recstore: setting up the bucket table failed");
+    }
+    s->lay = std::move(lay);
+    s->have_table = true;
+    s->measuring = true;
+    s->over = false;
+    return 0;
+}
+
+int fadehip_recstore_over(fadehip_recstore *s, int32_t *over) {
+    if (!s) return set_err(nullptr, FADEHIP_E_INVALID, "recstore is NULL");
+    if (!over) return set_err(s->ctx, FADEHIP_E_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> sl(s->mu);
+    *over = s->over ? 1 : 0;
+    return 0;
+}
+
+int fadehip_recstore_resets(fadehip_recstore *s, int64_t *n_reset) {
+    if (!s) return set_err(nullptr, FADEHIP_E_INVALID, "recstore is NULL");
+    if (!n_reset) return set_err(s->ctx, FADEHIP_E_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> sl(s->mu);
+    *n_reset = (int64_t)s->n_reset;
+    return 0;
+}
+
+int fadehip_recstore_histogram(fadehip_recstore *s, uint64_t *bytes, uint64_t *records, int64_t *n_buckets) {
+    if (!s) return set_err(nullptr, FADEHIP_E_INVALID, "recstore is NULL");
+    fadehip_ctx *ctx = s->ctx;
+    if (!n_buckets || (!bytes) != (!records)) return set_err(ctx, FADEHIP_E_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> sl(s->mu);
+    if (!s->have_table) return set_err(ctx, FADEHIP_E_STATE, "recstore: histogram comes after fadehip_recstore_measure");
+    const int64_t n = (int64_t)s->lay.n_buckets;
+    if (!bytes) {
+        *n_buckets = n;
+        return 0;
+    }
+    if (*n_buckets < n) return set_err(ctx, FADEHIP_E_INVALID, "recstore: the table has %lld buckets, the arrays hold %lld", (long long)n, (long long)*n_buckets);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipDeviceSynchronize());  // the streams' kernels may be on any of the ctx's streams
+    if (hipMemcpyAsync(bytes, s->table.p, 8 * (size_t)n, hipMemcpyDeviceToHost, ctx->copy_stream) != hipSuccess ||
+        hipMemcpyAsync(records, (const uint8_t *)s->table.p + 8 * (size_t)n, 8 * (size_t)n, hipMemcpyDeviceToHost, ctx->copy_stream) != hipSuccess ||
+        hipStreamSynchronize(ctx->copy_stream) != hipSuccess)
+        return set_err(ctx, FADEHIP_E_HIP, "recstore: copying the bucket table failed");
+    *n_buckets = n;
+    return 0;
+}
+
+int fadehip_recstore_set_window(fadehip_recstore *s, uint64_t lo_key, uint64_t hi_key_inclusive) {
+    if (!s) return set_err(nullptr, FADEHIP_E_INVALID, "recstore is NULL");
+    fadehip_ctx *ctx = s->ctx;
+    if (lo_key > hi_key_inclusive) return set_err(ctx, FADEHIP_E_INVALID, "recstore: the window's first key lies behind its last");
+    std::lock_guard<std::mutex> sl(s->mu);
+    if (s->sorted || s->n_items) return set_err(ctx, FADEHIP_E_STATE, "recstore: set_window takes an empty, unsorted store (fadehip_recstore_reset empties it)");
+    s->win_lo = lo_key;
+    s->win_hi = hi_key_inclusive;
+    return 0;
+}
+
+int fadehip_recstore_reset(fadehip_recstore *s, uint64_t bytes, uint64_t records) {
+    if (!s) return set_err(nullptr, FADEHIP_E_INVALID, "recstore is NULL");
+    fadehip_ctx *ctx = s->ctx;
+    if (records > RECSTORE_MAX_ITEMS)
+        return set_err(ctx, FADEHIP_E_UNSUPPORTED, "recstore: more than %llu records (the sort numbers its items in 32 bits)", (unsigned long long)RECSTORE_MAX_ITEMS);
+    std::lock_guard<std::mutex> sl(s->mu);
+    if (s->budget_set && recstore::sortwin_cost(bytes, records) > s->budget)
+        return set_err(ctx, FADEHIP_E_NOMEM, "recstore: %llu bytes in %llu records would cost more than the budget of %llu bytes (the store holds every output record on the device)",
+                       (unsigned long long)bytes, (unsigned long long)records, (unsigned long long)s->budget);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipDeviceSynchronize());  // whatever still appends, sorts or drains
+    release(s->sort_arr);
+    s->h_dst.clear();
+    s->cursor = 0;
+    s->sorted = false;
+    s->used = 0;
+    s->n_items = 0;
+    s->over = false;
+    s->measuring = false;
+    s->n_reset = 0;
+    // (nothing is kept, so nothing is copied: the old buffer goes before the new one comes)
+    int rc;
+    if ((uint64_t)s->arena.cap < bytes + 8) {
+        release(s->arena);
+        if ((rc = recstore_alloc(ctx, s->arena, (size_t)(bytes + 8)))) return rc;
+    }
+    if (s->item_cap < records) {
+        s->item_cap = 0;
+        for (DevBuf *b : {&s->key, &s->off, &s->size}) release(*b);
+        if ((rc = recstore_alloc(ctx, s->key, 8 * (size_t)records)) || (rc = recstore_alloc(ctx, s->off, 8 * (size_t)records)) || (rc = recstore_alloc(ctx, s->size, 4 * (size_t)records))) {
+            for (DevBuf *b : {&s->key, &s->off, &s->size}) release(*b);
+            return rc;
+        }
+        s->item_cap = records;
+    }
     return 0;
 }
 
@@ -3207,7 +3496,7 @@ void fadehip_bam_close(fadehip_bam_stream *st) {
     release(st->ref_chrom);
     for (auto &S : st->set) {
         for (DevBuf *b : {&S.comp, &S.blocks, &S.status, &S.ticket, &S.u, &S.seg, &S.slots, &S.rec_off, &S.info, &S.sent_of, &S.art_of, &S.out_size, &S.blk32,
-                          &S.blk64, &S.counts, &S.ex_size, &S.ex_blk, &S.rx_cnt, &S.ej_head, &S.ej_blk, &S.ej_grp, &S.ft_rec, &S.ft_side, &S.ft_ops_blk, &S.ft_ops_at, &S.ft_ops})
+                          &S.blk64, &S.counts, &S.ex_size, &S.ex_blk, &S.rx_cnt, &S.sw_key,&S.ej_head, &S.ej_blk, &S.ej_grp, &S.ft_rec, &S.ft_side, &S.ft_ops_blk, &S.ft_ops_at, &S.ft_ops})
             release(*b);
         release(S.h_blocks);
         release(S.h_counts);

@@ -73,6 +73,7 @@ static void print_anno_help() {
             " --extract-sorted with --extract PATH, BAM file in, -b or -u out, one MI355X: PATH is written in coordinate order (@HD SO:coordinate), and its index PATH.bai beside it\n"
             "          --eject drop the artifact reads in the same pass, and on name-sorted input every read that shares their name (what `fade out` makes of the annotated file)\n"
             "    --keep-sorted with -c, coordinate-sorted BAM file in, -b or -u out, one MI355X: clipped records are written at their new coordinates, so the output stays coordinate-sorted\n"
+            "           --sort BAM file in, in any order, -b or -u out, one MI355X: the output is written in coordinate order (@HD SO:coordinate), sorted on the device (a file too large for it: sort in the fade out step)\n"
             "    --write-index PATH: also write the BAM index (.bai) of the output, made in the same pass (coordinate-sorted output, BAM file in, -b or -u out, one MI355X)\n"
             "          --gpus number of MI355X devices, one process each on its own range of the input (default 1)\n"
             "    --out-shards with --gpus N: every device writes a complete file PREFIX.<k>.bam (.sam), nothing is merged\n"
@@ -98,6 +99,7 @@ struct Opts {
     std::string extract;  // --extract PATH: `fade extract`'s records of this run's artifact calls, in the output's format
     bool sorted = false;  // `fade extract --sorted`: the records leave in coordinate order (a store of records on the device, sorted once at the end)
     bool extract_sorted = false;  // `fade annotate --extract PATH --extract-sorted`: PATH is written in coordinate order, PATH.bai beside it
+    bool sort = false;  // `fade out --sort`: the output leaves in coordinate order whatever the input's (its records in a store on the device, in windows when they do not fit)
     std::string repeats;  // `fade stats --gpus 1 --repeats PATH`: a BED of repeats; every row gains read_rpm and art_rpm (a set of intervals on the device)
     std::string seen;  // R (--repeats); one letter per option met: t m w b u c h g(pus) B(atch) s(tats) T(iming) S(hards) X (--extract) E (--eject) F (--fragments) K (--keep-sorted) O (--sorted) Y (--extract-sorted)
 };
@@ -206,6 +208,11 @@ static bool parse_opts(int argc, char **argv, Opts &o, std::string &err) {
                 if (has_val && val != "true" && val != "false") { err = "Invalid value for option --" + name + ": " + val; return false; }
                 (name == "sorted" ? o.sorted : o.extract_sorted) = !has_val || val == "true";
             }
+            else if (name == "sort") {  // (a flag, as --eject)
+                o.seen += 'Z';
+                if (has_val && val != "true" && val != "false") { err = "Invalid value for option --sort: " + val; return false; }
+                o.sort = !has_val || val == "true";
+            }
             else if (name == "help") o.help = true;
             else { err = "Unrecognized option --" + name; return false; }
         } else if (a.size() > 1 && a[0] == '-' && a != "-") {
@@ -301,53 +308,75 @@ struct IndexSink {
 // unsorted file gets —, then the store's drains in coordinate order, members straight from the device compressor, then the
 // end-of-file marker; with bai_path the .bai of it, from the header's size and every drain's entries, as IndexSink makes one.
 // `out` may be a pipe.  Returns the records written.
-static int64_t write_sorted_store(fadehip_ctx *ctx, fadehip_recstore *rs, FILE *out, bool stored, Header hdr, Pool *pool, const std::string &bai_path) {
-    hdr.text = fadehip::recstore::header_sorted(hdr.text);
-    char *mp = nullptr;
-    size_t mn = 0;
-    FILE *mf = open_memstream(&mp, &mn);
-    if (!mf) throw std::runtime_error("out of memory");
-    try {
-        Writer hw(mf, stored ? OutFmt::UBAM : OutFmt::BAM, hdr, pool, nullptr, true, false);
-        hw.close();
-    } catch (...) {
-        fclose(mf);
-        free(mp);
-        throw;
-    }
-    fclose(mf);
-    const bool ok = fwrite(mp, 1, mn, out) == mn;
-    free(mp);
-    if (!ok) throw std::runtime_error("write error on the sorted extract");
-    uint64_t at = mn;
-    struct Bai { fadehip_bai *b = nullptr; ~Bai() { if (b) fadehip_bai_destroy(b); } } bai;
-    if (!bai_path.empty() && !(bai.b = fadehip_bai_create((int32_t)hdr.names.size()))) throw std::runtime_error("out of memory");
-    if (fadehip_recstore_sort(rs)) throw std::runtime_error(fadehip_last_error(ctx));
-    const int32_t flags = (stored ? FADEHIP_RECSTORE_STORED : 0) | (bai.b ? FADEHIP_RECSTORE_INDEX : 0);
+// In three steps, so that `fade out --sort` can write a file whose records do not fit the device at once: begin (the header),
+// window (one sort of the store and its drains; the windows of the key space come in ascending order, and the one builder of
+// the index checks the order between drains), finish (the marker and the .bai).
+struct SortedWriter {
+    fadehip_ctx *ctx;
+    FILE *out;
+    bool stored;
+    std::string bai_path;
+    fadehip_bai *bai = nullptr;
+    uint64_t at = 0;  // file offset of the next drain's first member
     int64_t total = 0;
-    for (;;) {
-        const uint8_t *p = nullptr;
-        size_t n = 0;
-        int64_t n_rec = 0;
-        fadehip_index_call c;
-        if (fadehip_recstore_drain(rs, flags, (uint64_t)64 << 20, &p, &n, &n_rec, bai.b ? &c : nullptr)) throw std::runtime_error(fadehip_last_error(ctx));
-        if (!n_rec) break;
-        if (fwrite(p, 1, n, out) != n) throw std::runtime_error("write error on the sorted extract");
-        if (bai.b && fadehip_bai_add(bai.b, at, &c)) throw std::runtime_error(fadehip_bai_error(bai.b));
-        at += n;
-        total += n_rec;
+    SortedWriter(fadehip_ctx *c, FILE *o, bool st, const std::string &bp) : ctx(c), out(o), stored(st), bai_path(bp) {}
+    ~SortedWriter() { if (bai) fadehip_bai_destroy(bai); }
+    void begin(Header hdr, Pool *pool) {
+        hdr.text = fadehip::recstore::header_sorted(hdr.text);
+        char *mp = nullptr;
+        size_t mn = 0;
+        FILE *mf = open_memstream(&mp, &mn);
+        if (!mf) throw std::runtime_error("out of memory");
+        try {
+            Writer hw(mf, stored ? OutFmt::UBAM : OutFmt::BAM, hdr, pool, nullptr, true, false);
+            hw.close();
+        } catch (...) {
+            fclose(mf);
+            free(mp);
+            throw;
+        }
+        fclose(mf);
+        const bool ok = fwrite(mp, 1, mn, out) == mn;
+        free(mp);
+        if (!ok) throw std::runtime_error("write error on the sorted output");
+        at = mn;
+        if (!bai_path.empty() && !(bai = fadehip_bai_create((int32_t)hdr.names.size()))) throw std::runtime_error("out of memory");
     }
-    if (fwrite(BGZF_EOF, 1, sizeof BGZF_EOF, out) != sizeof BGZF_EOF || fflush(out) != 0 || ferror(out)) throw std::runtime_error("write error on the sorted extract");
-    if (bai.b) {
-        const uint8_t *p = nullptr;
-        size_t n = 0;
-        if (fadehip_bai_finish(bai.b, &p, &n)) throw std::runtime_error(fadehip_bai_error(bai.b));
-        FILE *f = fopen(bai_path.c_str(), "wb");
-        if (!f) throw std::runtime_error("cannot write " + bai_path + ": " + strerror(errno));
-        const bool wrote = fwrite(p, 1, n, f) == n;
-        if (fclose(f) != 0 || !wrote) throw std::runtime_error("write error on " + bai_path);
+    void window(fadehip_recstore *rs) {
+        if (fadehip_recstore_sort(rs)) throw std::runtime_error(fadehip_last_error(ctx));
+        const int32_t flags = (stored ? FADEHIP_RECSTORE_STORED : 0) | (bai ? FADEHIP_RECSTORE_INDEX : 0);
+        for (;;) {
+            const uint8_t *p = nullptr;
+            size_t n = 0;
+            int64_t n_rec = 0;
+            fadehip_index_call c;
+            if (fadehip_recstore_drain(rs, flags, (uint64_t)64 << 20, &p, &n, &n_rec, bai ? &c : nullptr)) throw std::runtime_error(fadehip_last_error(ctx));
+            if (!n_rec) break;
+            if (fwrite(p, 1, n, out) != n) throw std::runtime_error("write error on the sorted output");
+            if (bai && fadehip_bai_add(bai, at, &c)) throw std::runtime_error(fadehip_bai_error(bai));
+            at += n;
+            total += n_rec;
+        }
     }
-    return total;
+    void finish() {
+        if (fwrite(BGZF_EOF, 1, sizeof BGZF_EOF, out) != sizeof BGZF_EOF || fflush(out) != 0 || ferror(out)) throw std::runtime_error("write error on the sorted output");
+        if (bai) {
+            const uint8_t *p = nullptr;
+            size_t n = 0;
+            if (fadehip_bai_finish(bai, &p, &n)) throw std::runtime_error(fadehip_bai_error(bai));
+            FILE *f = fopen(bai_path.c_str(), "wb");
+            if (!f) throw std::runtime_error("cannot write " + bai_path + ": " + strerror(errno));
+            const bool wrote = fwrite(p, 1, n, f) == n;
+            if (fclose(f) != 0 || !wrote) throw std::runtime_error("write error on " + bai_path);
+        }
+    }
+};
+static int64_t write_sorted_store(fadehip_ctx *ctx, fadehip_recstore *rs, FILE *out, bool stored, Header hdr, Pool *pool, const std::string &bai_path) {
+    SortedWriter w(ctx, out, stored, bai_path);
+    w.begin(hdr, pool);
+    w.window(rs);
+    w.finish();
+    return w.total;
 }
 
 // What `fade out -c` and `fade annotate -c` say about their output (filter.d:184-185); with --keep-sorted, what holds instead
@@ -355,7 +384,9 @@ static const char *const kFixMatesLine =
     "[W::fade-out] --fix-mates: mate fields (next position, template length, mate strand and unmapped flags, MC) follow the clip: three passes over the file "
     "(names of the artifact reads, placements of their fragments, write)\n";
 static void clip_warnings(const Opts &o) {
-    if (o.keep_sorted)
+    if (o.sort)
+        fprintf(stderr, "[W::fade-out] --sort: the output is written in coordinate order, clipped records at their new coordinates; reads clipped to nothing go to the end as unmapped records\n");
+    else if (o.keep_sorted)
         fprintf(stderr, "[W::fade-out] --keep-sorted: clipped records are written at their new coordinates, so coordinate-sorted input stays sorted; reads clipped to nothing go to the end as unmapped records\n");
     else
         fprintf(stderr, "[W::fade-out] Using the -c flag means the output SAM/BAM will not be sorted (regardless of prior sorting)\n");
@@ -1729,7 +1760,7 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
     }
     *fall_back = false;
     if (o.timing) fprintf(stderr, "[timing] since process start %.3f s (annotate begins; file path on the device)\n", since_process_start());
-    if (!lane.on) fprintf(stderr, "[W::fade annotate] Output SAM/BAM will not be sorted (regardless of prior sorting)\n");
+    if (!lane.on && !o.sort) fprintf(stderr, "[W::fade annotate] Output SAM/BAM will not be sorted (regardless of prior sorting)\n");
     const bool eject_grouped = o.eject && eject_mode_grouped(eject_names);
     // a lane reads the members in front of coff_end whole and, of the member AT coff_end, the end_rec bytes in front of the next
     // lane's first record
@@ -1806,6 +1837,13 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
             if (o.extract_sorted) {  // --extract-sorted: ... and they stay on the device, in a store, until the main output is finished
                 cfg.flags |= FADEHIP_BAM_STORE_EXTRACT;
                 if (fadehip_recstore_create(ctx, &store)) { create_err = fadehip_last_error(ctx); return 1; }
+            }
+            if (o.sort) {  // --sort: the MAIN output stays on the device, in a store that measures it under the budget the device allows; the drains compress and index it
+                cfg.flags = (cfg.flags & ~(FADEHIP_BAM_STORED | FADEHIP_BAM_INDEX)) | FADEHIP_BAM_STORE_OUTPUT;
+                if (fadehip_recstore_create(ctx, &store) || fadehip_recstore_set_budget(store, 0) || fadehip_recstore_measure(store, (int32_t)hdr.lens.size(), hdr.lens.data())) {
+                    create_err = fadehip_last_error(ctx);
+                    return 1;
+                }
             }
             if (fadehip_bam_open(ctx, &cfg, &st)) { create_err = fadehip_last_error(ctx); return 1; }
             if (store && fadehip_bam_use_recstore(st, store)) { create_err = fadehip_last_error(ctx); return 1; }
@@ -1971,7 +2009,9 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
         if (genome.upload(ctx)) return 1;
         if (o.timing) genome.report();
         // the header goes out through the CPU writer (its members only: no end-of-file block yet; not a byte without a device)
-        if (!o.write_index.empty()) {
+        if (o.sort) {
+            // (--sort: nothing reaches stdout while the input streams through; header, records and marker follow the sort)
+        } else if (!o.write_index.empty()) {
             index.open(o.write_index, hdr.names.size());
             index.header([&](FILE *to) {
                 Writer hw(to, o.ubam ? OutFmt::UBAM : OutFmt::BAM, out_hdr, &pool, nullptr, true, false);
@@ -2111,10 +2151,30 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
             fprintf(stderr, "[E::fade annotate] cannot seek the output: %s\n", strerror(errno));
             return 1;
         }
-        if ((!lane.on || lane.shard) && fwrite(BGZF_EOF, 1, sizeof BGZF_EOF, stdout) != sizeof BGZF_EOF) { fprintf(stderr, "[E::fade annotate] write error on the output stream\n"); return 1; }
+        if (o.sort) {  // one window only: re-aligning the input once per window is not built
+            int32_t over = 0;
+            int64_t n_reset = 0;
+            uint64_t budget = 0;
+            if (fadehip_recstore_over(store, &over) || fadehip_recstore_resets(store, &n_reset) || fadehip_recstore_budget(store, &budget)) throw std::runtime_error(fadehip_last_error(ctx));
+            if (over) {
+                fprintf(stderr, "[E::fade-annotate] --sort: the output's records do not fit the budget of %llu bytes on the device, and annotate sorts in one piece: annotate without --sort and "
+                                "sort in the fade out step (fade out --gpus 1 --sort), which takes files of any size\n", (unsigned long long)budget);
+                return 1;
+            }
+            if (n_reset && !o.write_index.empty()) {
+                fprintf(stderr, "[E::fade-annotate] --sort --write-index: %lld reads are clipped to nothing; they are written zero-filled (refID 0, pos 0) at the end of the file, and a file that "
+                                "ends in them is not in coordinate order by its own bytes, so no index can be made of it (samtools index refuses it too): run without --write-index\n", (long long)n_reset);
+                return 1;
+            }
+            StageClock ck_sorted;
+            ck_sorted.start();
+            const int64_t n_sorted = write_sorted_store(ctx, store, stdout, o.ubam, out_hdr, &pool, o.write_index);
+            ck_sorted.stop();
+            if (o.timing) fprintf(stderr, "[timing] --sort: %lld records sorted on the device and written in coordinate order in %.3f s\n", (long long)n_sorted, ck_sorted.t);
+        } else if ((!lane.on || lane.shard) && fwrite(BGZF_EOF, 1, sizeof BGZF_EOF, stdout) != sizeof BGZF_EOF) { fprintf(stderr, "[E::fade annotate] write error on the output stream\n"); return 1; }
         if (fflush(stdout) != 0 || ferror(stdout)) { fprintf(stderr, "[E::fade annotate] write error on the output stream\n"); return 1; }
         if (index.on()) index.write();
-        if (store) {  // --extract-sorted: PATH in coordinate order and PATH.bai beside it, behind the finished main output
+        if (store && !o.sort) {  // --extract-sorted: PATH in coordinate order and PATH.bai beside it, behind the finished main output
             StageClock ck_sorted;
             ck_sorted.start();
             const int64_t n_sorted = write_sorted_store(ctx, store, xfile.f, o.ubam, out_hdr, &pool, o.extract + ".bai");
@@ -2567,6 +2627,7 @@ static bool options_allowed(const Opts &o, const char *allowed) {
     for (char c : o.seen)
         if (!strchr(allowed, c)) {
             if (c == 'R') fprintf(stderr, "std.getopt.GetOptException: Unrecognized option --repeats\n[E::fade] --repeats: the option goes with fade stats --gpus 1 (it adds two columns to that report's rows)\n");
+            else if (c == 'Z') fprintf(stderr, "std.getopt.GetOptException: Unrecognized option --sort\n[E::fade] --sort: the option goes with fade out --gpus 1 and fade annotate (the output's records are sorted on the device)\n");
             else fprintf(stderr, "std.getopt.GetOptException: Unrecognized option %s%c\n", "-", c);
             return false;
         }
@@ -2689,6 +2750,7 @@ static void print_out_help() {
             " --fragments BAM file in, -b or -u out, on one MI355X: eject every read that shares its name with an artifact read, input in any order (two passes over the file)\n"
             " --fix-mates with -c, BAM file in, -b or -u out, on one MI355X: every read's mate fields (next position, template length, flags 0x8 / 0x20, MC) follow the clip of its mate (three passes over the file)\n"
             "--keep-sorted with -c, coordinate-sorted BAM file in, -b or -u out, on one MI355X: clipped records are written at their new coordinates, so the output stays coordinate-sorted\n"
+            "      --sort with --gpus 1, BAM file in, in any order, -b or -u out: the output is written in coordinate order (@HD SO:coordinate), sorted on the MI355X; a file too large for it in several passes\n"
             "--write-index PATH: also write the BAM index (.bai) of the output, made in the same pass (coordinate-sorted output, BAM file in, -b or -u out, on one MI355X)\n"
             "    --timing print where the run spent its time to stderr\n"
             "-h    --help This help information.\n\n",
@@ -2974,6 +3036,7 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
     const bool report = job == TagsJob::STATS || job == TagsJob::STATS_CLIP;
     const char *who = job == TagsJob::EXTRACT ? "fade extract" : job == TagsJob::STATS ? "fade stats" : job == TagsJob::STATS_CLIP ? "fade stats-clip" : "fade out";
     const bool fragments = job == TagsJob::FRAGMENTS, fix_mates = job == TagsJob::FIX_MATES;
+    const bool sort_out = o.sort && !report && job != TagsJob::EXTRACT;  // `fade out --sort`: the pass that writes keeps its records on the device
     const std::string &path = o.pos[1];
     struct stat sb;
     if (!(o.bam || o.ubam || report) || path == "-" || stat(path.c_str(), &sb) != 0 || !S_ISREG(sb.st_mode)) return 1;
@@ -3072,11 +3135,23 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
             if (fadehip_bam_open(ctx, &cfg, &st)) { create_err = fadehip_last_error(ctx); return 1; }
             if ((mode & (FADEHIP_BAM_COLLECT_NAMES | FADEHIP_BAM_EJECT_NAMED | FADEHIP_BAM_COLLECT_MATES)) && fadehip_bam_use_nameset(st, names)) { create_err = fadehip_last_error(ctx); return 1; }
             if ((mode & (FADEHIP_BAM_COLLECT_MATES | FADEHIP_BAM_FIX_MATES)) && fadehip_bam_use_mateset(st, mates)) { create_err = fadehip_last_error(ctx); return 1; }
-            if ((mode & FADEHIP_BAM_STORE_EXTRACT) && fadehip_bam_use_recstore(st, store)) { create_err = fadehip_last_error(ctx); return 1; }
+            if ((mode & (FADEHIP_BAM_STORE_EXTRACT | FADEHIP_BAM_STORE_OUTPUT)) && fadehip_bam_use_recstore(st, store)) { create_err = fadehip_last_error(ctx); return 1; }
             if ((mode & FADEHIP_BAM_REPORT_REPEATS) && fadehip_bam_use_intervals(st, repeats)) { create_err = fadehip_last_error(ctx); return 1; }
             const size_t call_bytes = host_inflate ? chunk : std::min<size_t>(chunk * 3, (size_t)1 << 30);
             if (!(getenv("FADE_BAM_PREPARE") && atoi(getenv("FADE_BAM_PREPARE")) == 0) && fadehip_bam_prepare(st, call_bytes)) { create_err = fadehip_last_error(ctx); return 1; }
             return 0;
+        };
+        // --sort: the stream of the pass that writes, with `mode` as it would be without the option — its records go into a
+        // store that measures them under the budget the device allows (fadehip_recstore_set_budget 0), not to the compressor:
+        // the drains compress (and index) them once they are in order
+        int32_t sorting_mode = 0;
+        auto open_sorting = [&](int32_t mode) -> int {
+            sorting_mode = mode;
+            if (!store) {
+                if (fadehip_recstore_create(ctx, &store) || fadehip_recstore_set_budget(store, 0) ||
+                    fadehip_recstore_measure(store, (int32_t)hdr.lens.size(), hdr.lens.data())) { create_err = fadehip_last_error(ctx); return 1; }
+            }
+            return open_stream((mode & ~(FADEHIP_BAM_STORED | FADEHIP_BAM_INDEX)) | FADEHIP_BAM_STORE_OUTPUT);
         };
         std::future<int> creating = std::async(std::launch::async, [&]() -> int {
             if (fadehip_create(&ctx, device, &prm)) { create_err = fadehip_last_error(nullptr); return 1; }
@@ -3106,6 +3181,7 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
             }
             else if (o.clip) mode |= FADEHIP_BAM_CLIP | (o.keep_sorted ? FADEHIP_BAM_KEEP_SORTED : 0);
             else mode |= grouped ? FADEHIP_BAM_EJECT | FADEHIP_BAM_EJECT_GROUPS : FADEHIP_BAM_EJECT;
+            if (sort_out) return open_sorting(mode);
             if (!o.write_index.empty()) mode |= FADEHIP_BAM_INDEX;
             return open_stream(mode);
         });
@@ -3254,8 +3330,9 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
             ck_front = StageClock();
             ck_back = StageClock();
             ck_write = StageClock();
-            if (open_stream(fix_mates ? FADEHIP_BAM_COLLECT_MATES | FADEHIP_BAM_CLIP | FADEHIP_BAM_NO_OUTPUT
-                                      : FADEHIP_BAM_EJECT_NAMED | (o.ubam ? FADEHIP_BAM_STORED : 0) | (o.write_index.empty() ? 0 : FADEHIP_BAM_INDEX))) {
+            const int32_t mode2 = fix_mates ? FADEHIP_BAM_COLLECT_MATES | FADEHIP_BAM_CLIP | FADEHIP_BAM_NO_OUTPUT
+                                            : FADEHIP_BAM_EJECT_NAMED | (o.ubam ? FADEHIP_BAM_STORED : 0) | (o.write_index.empty() ? 0 : FADEHIP_BAM_INDEX);
+            if (fragments && sort_out ? open_sorting(mode2) : open_stream(mode2)) {
                 fprintf(stderr, "[E::%s] cannot open the GPU path: %s\n", who, create_err.c_str());
                 return 1;
             }
@@ -3276,8 +3353,9 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
             ck_front = StageClock();
             ck_back = StageClock();
             ck_write = StageClock();
-            if (open_stream(FADEHIP_BAM_FIX_MATES | FADEHIP_BAM_CLIP | (o.ubam ? FADEHIP_BAM_STORED : 0) | (o.keep_sorted ? FADEHIP_BAM_KEEP_SORTED : 0) |
-                            (o.write_index.empty() ? 0 : FADEHIP_BAM_INDEX))) {
+            const int32_t mode3 = FADEHIP_BAM_FIX_MATES | FADEHIP_BAM_CLIP | (o.ubam ? FADEHIP_BAM_STORED : 0) | (o.keep_sorted ? FADEHIP_BAM_KEEP_SORTED : 0) |
+                                  (o.write_index.empty() ? 0 : FADEHIP_BAM_INDEX);
+            if (sort_out ? open_sorting(mode3) : open_stream(mode3)) {
                 fprintf(stderr, "[E::%s] cannot open the GPU path: %s\n", who, create_err.c_str());
                 return 1;
             }
@@ -3293,7 +3371,9 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
         } else if (job == TagsJob::EXTRACT && o.sorted) {
             // (nothing is written while the input streams through: header, records and marker follow the sort)
         } else if (job == TagsJob::EXTRACT) xwriter.reset(new Writer(stdout, fmt, out_hdr, &pool));
-        else if (!o.write_index.empty()) {
+        else if (sort_out) {
+            // (nothing either: whether the records leave in one window or in several is known when the input is through)
+        } else if (!o.write_index.empty()) {
             index.open(o.write_index, hdr.names.size());
             index.header([&](FILE *to) {
                 Writer hw(to, fmt, out_hdr, &pool, nullptr, true, false);
@@ -3304,10 +3384,80 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
             hw.close();
         }
         if (run_calls()) return 1;
+        int64_t totals[8], n_rec = 0, n_over = 0, n_ej = 0;  // (of this pass: under --sort more passes may follow, one per window)
+        fadehip_bam_totals(st, totals, &n_rec, &n_over);
+        fadehip_bam_ejected(st, &n_ej);
+        int64_t n_fixed = 0, n_amb = 0;
+        if (fix_mates) fadehip_bam_mates(st, &n_fixed, &n_amb);
         if (report) {
             if (fflush(rep_out) != 0 || ferror(rep_out)) { fprintf(stderr, "[E::%s] write error on the report\n", who); return 1; }
         } else if (xwriter) xwriter->close();
-        else if (store) {
+        else if (sort_out) {
+            StageClock ck_sorted;
+            ck_sorted.start();
+            int32_t over = 0;
+            if (fadehip_recstore_over(store, &over)) throw std::runtime_error(fadehip_last_error(ctx));
+            int64_t n_reset = 0;
+            if (fadehip_recstore_resets(store, &n_reset)) throw std::runtime_error(fadehip_last_error(ctx));
+            if (n_reset && !o.write_index.empty()) {  // (known before a byte is on stdout: the pass has only measured and stored)
+                fprintf(stderr, "[E::fade-out] --sort --write-index: %lld reads are clipped to nothing; they are written zero-filled (refID 0, pos 0) at the end of the file, and a file that ends "
+                                "in them is not in coordinate order by its own bytes, so no index can be made of it (samtools index refuses it too): run without --write-index, or drop those "
+                                "reads from the input\n", (long long)n_reset);
+                return 1;
+            }
+            SortedWriter sw(ctx, stdout, o.ubam, o.write_index);
+            size_t n_windows = 1;
+            if (!over) {
+                sw.begin(out_hdr, &pool);
+                sw.window(store);
+            } else {
+                // the records do not fit the device at once: the key space in windows that each fit, cut from the table the
+                // pass has measured, and one more pass over the input per window
+                int64_t nb = 0;
+                if (fadehip_recstore_histogram(store, nullptr, nullptr, &nb)) throw std::runtime_error(fadehip_last_error(ctx));
+                std::vector<uint64_t> hb((size_t)nb), hr((size_t)nb);
+                if (fadehip_recstore_histogram(store, hb.data(), hr.data(), &nb)) throw std::runtime_error(fadehip_last_error(ctx));
+                uint64_t budget = 0;
+                if (fadehip_recstore_budget(store, &budget)) throw std::runtime_error(fadehip_last_error(ctx));
+                std::vector<uint32_t> len32;
+                for (int64_t l : hdr.lens) len32.push_back((uint32_t)l);
+                fadehip::recstore::BucketLayout lay;
+                fadehip::recstore::bucket_layout(len32.data(), len32.size(), lay);
+                std::vector<fadehip::recstore::SortWindow> wins;
+                const int64_t bad = fadehip::recstore::choose_windows(hb.data(), hr.data(), (uint32_t)nb, budget, wins);
+                uint64_t all_bytes = 0;
+                for (uint64_t b : hb) all_bytes += b;
+                if (bad >= 0) {
+                    uint64_t lo, hi;
+                    int64_t ref;
+                    fadehip::recstore::bucket_range(lay, (uint32_t)bad, &lo, &hi, &ref);
+                    fprintf(stderr, "[E::fade-out] --sort: the records of %s from position %llu on take %llu bytes (%llu records), more than the budget of %llu bytes lets the device hold at once: "
+                                    "a window of the sort is at least 65,536 positions\n", ref >= 0 ? hdr.names[(size_t)ref].c_str() : "no contig (unmapped)",
+                            (unsigned long long)((uint32_t)lo ? (uint32_t)lo - 1u : 0u), (unsigned long long)hb[(size_t)bad], (unsigned long long)hr[(size_t)bad], (unsigned long long)budget);
+                    return 1;
+                }
+                n_windows = wins.size();
+                fprintf(stderr, "[W::fade-out] --sort: %llu bytes of records do not fit the budget of %llu bytes on the device: written in %zu windows, one more pass over the input for each\n",
+                        (unsigned long long)all_bytes, (unsigned long long)budget, n_windows);
+                sw.begin(out_hdr, &pool);
+                for (const auto &w : wins) {
+                    uint64_t lo, hi, unused;
+                    fadehip::recstore::bucket_range(lay, w.b0, &lo, &unused);
+                    fadehip::recstore::bucket_range(lay, w.b1 - 1, &unused, &hi);
+                    fadehip_bam_close(st);
+                    st = nullptr;
+                    if (fadehip_recstore_reset(store, w.bytes, w.records) || fadehip_recstore_set_window(store, lo, hi)) throw std::runtime_error(fadehip_last_error(ctx));
+                    if (open_sorting(sorting_mode)) { fprintf(stderr, "[E::%s] cannot open the GPU path: %s\n", who, create_err.c_str()); return 1; }
+                    start_pass();
+                    if (run_calls()) return 1;
+                    sw.window(store);
+                }
+            }
+            sw.finish();
+            ck_sorted.stop();
+            if (o.timing) fprintf(stderr, "[timing] --sort: %lld records sorted on the device and written in coordinate order in %zu window%s, %.3f s behind the first pass\n", (long long)sw.total,
+                                  n_windows, n_windows == 1 ? "" : "s", ck_sorted.t);
+        } else if (store) {
             StageClock ck_sorted;
             ck_sorted.start();
             const int64_t n_sorted = write_sorted_store(ctx, store, stdout, o.ubam, out_hdr, &pool, o.write_index);
@@ -3316,16 +3466,11 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
         } else if (fwrite(BGZF_EOF, 1, sizeof BGZF_EOF, stdout) != sizeof BGZF_EOF) { fprintf(stderr, "[E::%s] write error on the output stream\n", who); return 1; }
         if (fflush(stdout) != 0 || ferror(stdout)) { fprintf(stderr, "[E::%s] write error on the output stream\n", who); return 1; }
         if (index.on()) index.write();
-        int64_t totals[8], n_rec = 0, n_over = 0, n_ej = 0;
-        fadehip_bam_totals(st, totals, &n_rec, &n_over);
-        fadehip_bam_ejected(st, &n_ej);
         report_held(o);
         ck_pass2.stop();
         if (fragments && o.timing)
             fprintf(stderr, "[timing] pass 2 (records whose name is not in the set) %.3f s: front %.3f | back %.3f | write %.3f\n", ck_pass2.t, ck_front.t, ck_back.t, ck_write.t);
         if (fix_mates && o.timing) {
-            int64_t n_fixed = 0, n_amb = 0;
-            fadehip_bam_mates(st, &n_fixed, &n_amb);
             fprintf(stderr, "[timing] pass 3 (clip, mate fields from the map, write) %.3f s: front %.3f | back %.3f | write %.3f; %lld records fixed, %lld left alone (mate ambiguous)\n", ck_pass2.t,
                     ck_front.t, ck_back.t, ck_write.t, (long long)n_fixed, (long long)n_amb);
         }
@@ -3396,6 +3541,34 @@ static std::string write_index_refusal(const Opts &o, bool reports) {
     return bgzf ? "" : kWriteIndexInput;
 }
 
+// --sort (`fade out`): why the option cannot run as the command line stands, or "".  The output's records are kept, sorted and
+// compressed on one device: there is no host loop behind the option.  Looks at the options, the environment and the first bytes
+// of the input: no device is opened for it.
+static const char *const kSortInput = "the input is read as a BAM file on the device, once per pass: not SAM text, not a pipe";
+static std::string sort_refusal(const Opts &o, bool annotate) {
+    if (o.keep_sorted) return "--keep-sorted holds back a tail of coordinate-sorted input, and --sort already gives the order for input in any order: not with --keep-sorted";
+    if (!(o.bam || o.ubam)) return "the output is SAM text: --sort writes BAM (-b) or uncompressed BAM (-u)";
+    if (annotate) {
+        if (!o.out_shards.empty()) return "it goes with one device and one output: not with --out-shards";
+        if (!o.extract.empty() || o.extract_sorted)
+            return std::string("the record store holds the main output: not with ") + (o.extract_sorted ? "--extract-sorted" : "--extract") + " (run fade extract --gpus 1 --sorted on the annotated file)";
+        if (!o.stats_tsv.empty() || !o.clip_tsv.empty())
+            return std::string("the run with ") + (!o.stats_tsv.empty() ? "--stats-tsv" : "--clip-tsv") + " does not take the file path on the device: not with it";
+    } else if (o.seen.find('g') == std::string::npos) return "it goes with --gpus 1 (the records are kept and sorted on the device; there is no host loop)";
+    if (o.gpus != 1) return "it goes with one device: not with --gpus N other than 1 (the store of records lives on one device)";
+    if (getenv("FADE_BAM_DEVICE") && atoi(getenv("FADE_BAM_DEVICE")) == 0) return "FADE_BAM_DEVICE=0 takes the device away, and the records are kept and sorted on it (no host loop)";
+    const std::string &path = o.pos[1];
+    struct stat sb;
+    uint8_t h[4] = {0, 0, 0, 0};
+    bool bgzf = false;
+    if (path != "-" && stat(path.c_str(), &sb) == 0 && S_ISREG(sb.st_mode))
+        if (FILE *f = fopen(path.c_str(), "rb")) {
+            bgzf = fread(h, 1, 4, f) == 4 && h[0] == 0x1f && h[1] == 0x8b && (h[3] & 4);
+            fclose(f);
+        }
+    return bgzf ? "" : kSortInput;
+}
+
 // --sorted (`fade extract`) and --extract-sorted (`fade annotate`): why the option cannot run as the command line stands, or
 // "".  The records are kept, sorted and compressed on one device: there is no host loop behind either option.  Looks at the
 // options, the environment and the first bytes of the input: no device is opened for it.  `first`: a reason the caller has.
@@ -3442,7 +3615,7 @@ int main(int argc, char **argv) {
                                                                                       : "the option goes with fade stats --gpus 1 (it adds two columns to that report's rows)");
             return 1;
         }
-        if (!options_allowed(o, "tmwbucgBsTSPQXEKIY")) return 1;
+        if (!options_allowed(o, "tmwbucgBsTSPQXEKIYZ")) return 1;
         // app.d:84-89: helpWanted | args.length < 3 (args = prog, "annotate", positionals...)
         if (o.help || o.pos.size() < 2) { print_anno_help(); return 0; }
         if (o.pos.size() < 3) {  // the reference indexes args[2] and dies; say why instead
@@ -3463,6 +3636,13 @@ int main(int argc, char **argv) {
         if (reports && o.clip) {  // the reports describe the unclipped records
             fprintf(stderr, "[E::fade-annotate] %s describes unclipped records: not with --clip\n", !o.stats_tsv.empty() ? "--stats-tsv" : "--clip-tsv");
             return 1;
+        }
+        if (o.sort) {  // refused here, by name, before any device is opened: the records are kept and sorted on one device, and there is no host loop
+            const std::string why = sort_refusal(o, true);
+            if (!why.empty()) {
+                fprintf(stderr, "[E::fade-annotate] --sort: %s\n", why.c_str());
+                return 1;
+            }
         }
         if (o.keep_sorted) {  // refused here, by name, before any device is opened
             if (const char *why = keep_sorted_refusal(o)) {
@@ -3534,6 +3714,10 @@ int main(int argc, char **argv) {
             bool fall_back = true;
             const int src = annotate_stream_main(cl, o, &fall_back);
             if (src == 0 || !fall_back) return src;
+        }
+        if (o.sort) {  // the store lives on the device: there is no host loop behind this option
+            fprintf(stderr, "[E::fade-annotate] --sort: %s\n", kSortInput);
+            return 1;
         }
         if (o.keep_sorted) {  // the tail is held on the device: there is no host loop behind this option
             fprintf(stderr, "[E::fade-annotate] --keep-sorted: %s\n", kKeepSortedInput);
@@ -3630,8 +3814,15 @@ int main(int argc, char **argv) {
             fprintf(stderr, "std.getopt.GetOptException: %s\n", err.c_str());
             return 1;
         }
-        if (!options_allowed(o, "ctbugTFKIM")) return 1;
+        if (!options_allowed(o, "ctbugTFKIMZ")) return 1;
         if (o.help || o.pos.size() < 2) { print_out_help(); return 0; }
+        if (o.sort) {  // refused here, by name, before any device is opened: the records are kept and sorted on one device, and there is no host loop
+            const std::string why = sort_refusal(o, false);
+            if (!why.empty()) {
+                fprintf(stderr, "[E::fade-out] --sort: %s\n", why.c_str());
+                return 1;
+            }
+        }
         if (o.fix_mates) {  // refused here, by name, before any device is opened: the map lives on one device, and there is no host loop
             const char *why = !o.clip ? "without -c no record moves and no mate field goes stale: the option goes with -c"
                               : o.fragments ? "--fragments ejects the artifact reads with every read of their name, and no mate is left to fix: not with --fragments"
@@ -3686,6 +3877,12 @@ int main(int argc, char **argv) {
             bool fall_back = true;
             const int rc = tags_stream_main(cl, o, TagsJob::FRAGMENTS, &fall_back);
             if (fall_back) fprintf(stderr, "[E::fade-out] --fragments: the input is read twice, as a BAM file on the device: not SAM text, not a pipe, not %s\n", o.pos[1].c_str());
+            return fall_back ? 1 : rc;
+        }
+        if (o.sort) {  // the store lives on the device: no host loop behind this option either
+            bool fall_back = true;
+            const int rc = tags_stream_main(cl, o, TagsJob::OUT, &fall_back);
+            if (fall_back) fprintf(stderr, "[E::fade-out] --sort: %s\n", kSortInput);
             return fall_back ? 1 : rc;
         }
         if (!o.write_index.empty()) {  // the entries are made on the device: no host loop behind this option either (--gpus 1 is implied)

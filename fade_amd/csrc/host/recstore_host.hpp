@@ -1,11 +1,13 @@
 // recstore_host.hpp — the host-only parts of the sorted extract (tests/recstore_model.py states both rules
 // in Python): where a drain of the record store ends, and the header text of a coordinate-sorted file.  No device, no
-// library call: build/recstore_selftest runs both under ASan + UBSan.
+// library call: build/recstore_selftest runs both under ASan + UBSan.  Behind them the buckets and windows of the sorted main
+// output (§3.8n; tests/sorted_out_model.py), which build/sortwin_selftest runs the same way.
 #pragma once
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <string>
+#include <vector>
 
 namespace fadehip {
 namespace recstore {
@@ -42,6 +44,82 @@ inline std::string header_sorted(const std::string &text) {
     }
     if (!done) out += std::string("\t") + so;
     return out + text.substr(eol);
+}
+
+// ---- the sorted main output's windows (tests/sorted_out_model.py states the rule in Python).  The key space
+// — bam_resort.hpp's (refID as u32) << 32 | (pos + 1 as u32) — is cut into buckets of 2^SORTWIN_SHIFT positions: reference r
+// has nb[r] = ((len[r] + 1) >> SHIFT) + 1 of them from first[r], and one more bucket, the last, takes refID -1 and every
+// refID outside the header.  bucket() is monotone in the key and total: a pos beyond the contig falls into the contig's last.
+constexpr uint32_t SORTWIN_SHIFT = 16;
+constexpr uint64_t SORTWIN_ITEM_COST = 64;  // per record, beside its bytes: the item and sort arrays (57 bytes, §3.8l)
+
+struct BucketLayout {
+    std::vector<uint32_t> first, nb;  // [n_ref]
+    uint32_t n_buckets = 1;
+};
+
+// false: more buckets than 32 bits number (no BAM header comes near it)
+inline bool bucket_layout(const uint32_t *ref_len, size_t n_ref, BucketLayout &out) {
+    out.first.assign(n_ref, 0);
+    out.nb.assign(n_ref, 0);
+    uint64_t at = 0;
+    for (size_t r = 0; r < n_ref; r++) {
+        out.first[r] = (uint32_t)at;
+        out.nb[r] = (uint32_t)((((uint64_t)ref_len[r] + 1) >> SORTWIN_SHIFT) + 1);
+        at += out.nb[r];
+        if (at >= UINT32_MAX) return false;
+    }
+    out.n_buckets = (uint32_t)at + 1;
+    return true;
+}
+
+inline uint32_t bucket_of(const BucketLayout &l, uint64_t key) {
+    const uint64_t r = key >> 32;
+    if (r >= l.nb.size()) return l.n_buckets - 1;
+    return l.first[(size_t)r] + std::min((uint32_t)key >> SORTWIN_SHIFT, l.nb[(size_t)r] - 1);
+}
+
+// the keys of bucket b, both ends inclusive; *ref: its reference, -1 for the last bucket
+inline void bucket_range(const BucketLayout &l, uint32_t b, uint64_t *lo, uint64_t *hi, int64_t *ref = nullptr) {
+    if (b + 1 >= l.n_buckets) {
+        *lo = (uint64_t)l.nb.size() << 32;
+        *hi = ~(uint64_t)0;
+        if (ref) *ref = -1;
+        return;
+    }
+    const size_t r = (size_t)(std::upper_bound(l.first.begin(), l.first.end(), b) - l.first.begin()) - 1;
+    const uint32_t j = b - l.first[r];
+    *lo = ((uint64_t)r << 32) | ((uint64_t)j << SORTWIN_SHIFT);
+    *hi = ((uint64_t)r << 32) | (j + 1 == l.nb[r] ? (uint64_t)0xffffffffu : (((uint64_t)j + 1) << SORTWIN_SHIFT) - 1);
+    if (ref) *ref = (int64_t)r;
+}
+
+inline uint64_t sortwin_cost(uint64_t bytes, uint64_t records) { return bytes + SORTWIN_ITEM_COST * records; }
+
+struct SortWindow {
+    uint32_t b0, b1;          // buckets b0 .. b1 - 1
+    uint64_t bytes, records;  // what they hold
+};
+
+// The windows: runs of consecutive buckets whose cost is at most `budget`, chosen greedily front to back; together they
+// cover every bucket (one window when nothing was measured).  A bucket that holds nothing joins the window it lies in.
+// -1: done; else the first bucket that alone costs more than the budget (nothing of `out` is to be used then).
+inline int64_t choose_windows(const uint64_t *bytes, const uint64_t *records, uint32_t n_buckets, uint64_t budget, std::vector<SortWindow> &out) {
+    out.clear();
+    SortWindow w = {0, 0, 0, 0};
+    for (uint32_t b = 0; b < n_buckets; b++) {
+        if (sortwin_cost(bytes[b], records[b]) > budget) return (int64_t)b;
+        if (sortwin_cost(w.bytes + bytes[b], w.records + records[b]) > budget) {
+            w.b1 = b;
+            out.push_back(w);
+            w = {b, b, 0, 0};
+        }
+        w.bytes += bytes[b];
+        w.records += records[b];
+    }
+    w.b1 = n_buckets;
+    out.push_back(w);
+    return -1;
 }
 
 }  // namespace recstore

@@ -402,6 +402,38 @@ int fadehip_recstore_sort(fadehip_recstore *s);
 int fadehip_recstore_drain(fadehip_recstore *s, int32_t flags, uint64_t max_payload, const uint8_t **out, size_t *out_bytes, int64_t *n_records,
                            fadehip_index_call *idx /* NULL without FADEHIP_RECSTORE_INDEX */);
 void fadehip_recstore_destroy(fadehip_recstore *s);
+/* The store behind a coordinate-sorted MAIN output: a stream opened with FADEHIP_BAM_STORE_OUTPUT appends every record it
+ * would have written, and a file whose records do not fit the device at once is written in windows of the key space, one pass
+ * over the input per window (tests/sorted_out_model.py states the rule in plain Python).  A store on which
+ * none of these calls is made behaves as it always has.
+ *   set_budget   the most the store may cost: cost = bytes + 64 per record (the item and the sort's arrays).  0: derived from
+ *                hipMemGetInfo — two fifths of what is free less 2 GiB — and FADEHIP_RECSTORE_BUDGET=N in the
+ *                environment overrides either at the call.  From then on a growth never allocates beyond the budget, and a
+ *                call that would take the cost over it fails with FADEHIP_E_NOMEM — unless the store measures.
+ *   measure      ref_len[n_ref]: the header's contig lengths.  Builds and zeroes the bucket table: reference r has
+ *                ((len[r] + 1) >> 16) + 1 buckets of 65,536 positions, and one more bucket, the last, takes refID -1 and
+ *                every refID outside the header.  From then on (until reset) FADEHIP_BAM_STORE_OUTPUT streams add the bytes
+ *                and records they write to their buckets, and a call that would take the cost over the budget sends the
+ *                store OVER instead of failing: its contents are dropped, later calls store nothing, measuring goes on.
+ *   over         *over: 1 when that happened.   histogram: the table — bytes[] and records[] of *n_buckets entries each
+ *                (on entry *n_buckets is what the arrays hold; both NULL: only the number is wanted).  Both wait for the device.
+ *   set_window   the keys [lo_key, hi_key_inclusive] a FADEHIP_BAM_STORE_OUTPUT stream keeps (keys as sort's); records
+ *                outside it are dropped as an ejected record is, and counted apart.  Default: every key.
+ *   reset        empties the store, sorted or not, and ends measuring; memory, budget, window and table stay.  The arena
+ *                and the item arrays are sized once for `bytes` and `records`, so that a window's pass never grows.
+ * set_budget, measure and set_window take an EMPTY, unsorted store (else FADEHIP_E_STATE); measure comes once; histogram
+ * comes after measure.  NULL arguments: FADEHIP_E_INVALID before any device call. */
+int fadehip_recstore_set_budget(fadehip_recstore *s, uint64_t bytes);
+int fadehip_recstore_budget(fadehip_recstore *s, uint64_t *bytes); /* the budget in force (derived, given or from the environment); 0: none set */
+int fadehip_recstore_measure(fadehip_recstore *s, int32_t n_ref, const int64_t *ref_len);
+int fadehip_recstore_over(fadehip_recstore *s, int32_t *over);
+/* Reset records — reads a clip left nothing of, written zero-filled (refID 0, pos 0) and sorted last — among what
+ * FADEHIP_BAM_STORE_OUTPUT streams have finished since create or reset, inside the window or not.  A file that ends in them
+ * is not in coordinate order by its own bytes: no index can be made of it. */
+int fadehip_recstore_resets(fadehip_recstore *s, int64_t *n_reset);
+int fadehip_recstore_histogram(fadehip_recstore *s, uint64_t *bytes, uint64_t *records, int64_t *n_buckets);
+int fadehip_recstore_set_window(fadehip_recstore *s, uint64_t lo_key, uint64_t hi_key_inclusive);
+int fadehip_recstore_reset(fadehip_recstore *s, uint64_t bytes, uint64_t records);
 
 /* A set of genomic intervals resident on the device, and the overlap query over it (tests/intervals_model.py
  * states the rule in Python): what `bedtools subtract -A` against a RepeatMasker BED decides, as one look-up per query.
@@ -752,6 +784,14 @@ typedef struct fadehip_bam_config {
                                    * call fails with FADEHIP_E_STATE), in stream order, and stay on the device: no copy to the
                                    * host is made, and fadehip_bam_back_extract gives 0 bytes and the number of records the call
                                    * added.  No other output byte changes.  A store that has been sorted: FADEHIP_E_STATE;
+                                   * FADEHIP_BAM_STORE_OUTPUT: the records the stream would write go into the record store attached
+                                   * with fadehip_bam_use_recstore (none attached: the first front call fails with
+                                   * FADEHIP_E_STATE), in stream order, and stay on the device; fadehip_bam_back hands out 0 bytes.
+                                   * Sorting and draining the store gives the stream's records, byte for byte, in coordinate order
+                                   * of the records AS THEY LEAVE — a clipped record at its new pos, a reset record last.  Stands
+                                   * with the annotate path and with FROM_TAGS, CLIP, EJECT, EJECT_GROUPS, EJECT_NAMED and
+                                   * FIX_MATES; any other flag beside it: FADEHIP_E_INVALID at fadehip_bam_open, naming the flag.
+                                   * The store's budget, table and window (fadehip_recstore_measure, _set_window) apply;
                                    * FADEHIP_BAM_REPORT_REPEATS: only with REPORT_STATS (else FADEHIP_E_INVALID at fadehip_bam_open)
                                    * and wherever it stands: the stats rows gain the two columns of fadehip_report_batch_repeats,
                                    * against the sealed set attached with fadehip_bam_use_intervals (none attached: the first
@@ -779,6 +819,7 @@ typedef struct fadehip_bam_config {
 #define FADEHIP_BAM_FIX_MATES 16384
 #define FADEHIP_BAM_STORE_EXTRACT 32768
 #define FADEHIP_BAM_REPORT_REPEATS 65536
+#define FADEHIP_BAM_STORE_OUTPUT 131072
 int fadehip_bam_open(fadehip_ctx *ctx, const fadehip_bam_config *cfg, fadehip_bam_stream **out);
 /* The set a stream opened with FADEHIP_BAM_COLLECT_NAMES adds to, or one opened with FADEHIP_BAM_EJECT_NAMED looks names up
  * in: a set of the same ctx, attached before the first front call (later: FADEHIP_E_STATE).  The set is the caller's and
@@ -790,7 +831,8 @@ int fadehip_bam_use_nameset(fadehip_bam_stream *st, fadehip_nameset *s);
  * left alone because their mate's key is ambiguous, over the calls finished so far. */
 int fadehip_bam_use_mateset(fadehip_bam_stream *st, fadehip_mateset *s);
 int fadehip_bam_mates(fadehip_bam_stream *st, int64_t *n_fixed, int64_t *n_ambiguous);
-/* The record store a stream opened with FADEHIP_BAM_STORE_EXTRACT appends its extract records to: a store of the same ctx,
+/* The record store a stream opened with FADEHIP_BAM_STORE_EXTRACT appends its extract records to, or one opened with
+ * FADEHIP_BAM_STORE_OUTPUT its output records (either flag; neither: FADEHIP_E_INVALID): a store of the same ctx,
  * attached before the first front call (later: FADEHIP_E_STATE).  The store is the caller's and outlives the stream; it is
  * sorted and drained after the stream's last back call. */
 int fadehip_bam_use_recstore(fadehip_bam_stream *st, fadehip_recstore *s);
