@@ -183,6 +183,16 @@ int fadehip_bai_add(fadehip_bai* b, ulong base_file_offset, const(fadehip_index_
 int fadehip_bai_finish(fadehip_bai* b, const(ubyte)** bytes, size_t* n);
 const(char)* fadehip_bai_error(const(fadehip_bai)* b);
 void fadehip_bai_destroy(fadehip_bai* b);
+/// The same entries under a CSI geometry (4 <= min_shift, 1 <= depth <= 8, min_shift + 3 * depth <= 32): bins of a tree of that depth,
+/// windows of 2^min_shift positions, the span held to 2^(min_shift + 3 * depth); (14, 5) gives fadehip_index_batch's arrays
+int fadehip_index_batch_csi(fadehip_ctx* ctx, int n, const(ubyte)* recs, const(long)* rec_off, const(ulong)* voff, int min_shift, int depth, fadehip_index_call* out_);
+/// ... and the host's part: one .csi's UNCOMPRESSED payload (every bin with its loffset, the pseudo-bin, n_no_coor); the writer puts it into BGZF members
+struct fadehip_csi;
+fadehip_csi* fadehip_csi_create(int n_ref, int min_shift, int depth);
+int fadehip_csi_add(fadehip_csi* b, ulong base_file_offset, const(fadehip_index_call)* call);
+int fadehip_csi_finish(fadehip_csi* b, const(ubyte)** payload, size_t* n);
+const(char)* fadehip_csi_error(const(fadehip_csi)* b);
+void fadehip_csi_destroy(fadehip_csi* b);
 /// A set of read names resident on the device (`fade out --fragments`): exact, growing; records in the shapes fadehip_eject_batch takes.
 /// add_batch: the names of the records with pick[k] != 0 (pick null: every record); contains_batch: hit[k] = 1 when record k's name is
 /// in the set; count: distinct names.  A malformed record: FADEHIP_E_INVALID with its index, the set unchanged.
@@ -211,6 +221,7 @@ int fadehip_recstore_add_batch(fadehip_recstore* s, int n, const(ubyte)* recs, c
 int fadehip_recstore_count(fadehip_recstore* s, long* n_records, long* n_bytes);
 int fadehip_recstore_sort(fadehip_recstore* s);
 int fadehip_recstore_drain(fadehip_recstore* s, int flags, ulong max_payload, const(ubyte)** out_, size_t* out_bytes, long* n_records, fadehip_index_call* idx);
+int fadehip_recstore_index_geometry(fadehip_recstore* s, int min_shift, int depth);  /// before the first drain: FADEHIP_RECSTORE_INDEX hands out the entries of a CSI of that geometry
 void fadehip_recstore_destroy(fadehip_recstore* s);
 /// the sorted main output (FADEHIP_BAM_STORE_OUTPUT streams): the most the store may cost, bytes + 64 per record (0: derived
 /// from the device's free memory; FADEHIP_RECSTORE_BUDGET overrides); the bucket table over the header's contig lengths, from
@@ -320,6 +331,8 @@ int fadehip_bam_back_extract(fadehip_bam_stream* st, const(ubyte)** recs, size_t
 int fadehip_bam_back_report(fadehip_bam_stream* st, int which, const(ubyte)** text, size_t* n_bytes, long* n_rows);
 /// With FADEHIP_BAM_INDEX: the .bai entries of the call the most recent back finished, relative to its first member, in pinned memory
 int fadehip_bam_back_index(fadehip_bam_stream* st, fadehip_index_call* out_);
+/// With FADEHIP_BAM_INDEX, before the first front call: the calls leave the entries of a CSI of that geometry (fadehip_index_batch_csi)
+int fadehip_bam_index_geometry(fadehip_bam_stream* st, int min_shift, int depth);
 int fadehip_bam_totals(fadehip_bam_stream* st, long* stats8, long* n_records, long* n_oversize);
 /// FADEHIP_BAM_EJECT: records not written, over the calls back has taken
 int fadehip_bam_ejected(fadehip_bam_stream* st, long* n_ejected);

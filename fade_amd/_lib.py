@@ -39,6 +39,8 @@ EXPORTS = [
     "fadehip_bam_back_report",
     "fadehip_index_batch", "fadehip_bam_back_index", "fadehip_bai_create", "fadehip_bai_add", "fadehip_bai_finish", "fadehip_bai_error",
     "fadehip_bai_destroy",
+    "fadehip_index_batch_csi", "fadehip_bam_index_geometry", "fadehip_recstore_index_geometry", "fadehip_csi_create", "fadehip_csi_add",
+    "fadehip_csi_finish", "fadehip_csi_error", "fadehip_csi_destroy",
     "fadehip_mateset_create", "fadehip_mateset_add_batch", "fadehip_mates_fix_batch", "fadehip_mateset_count", "fadehip_mateset_destroy",
     "fadehip_bam_use_mateset", "fadehip_bam_mates",
     "fadehip_calmd_batch", "fadehip_bam_calmd",
@@ -249,6 +251,17 @@ def load():
     L.fadehip_bai_error.restype = C.c_char_p
     L.fadehip_bai_destroy.argtypes = [vp]
     L.fadehip_bai_destroy.restype = None
+    L.fadehip_index_batch_csi.argtypes = [vp, i32, vp, vp, vp, i32, i32, C.POINTER(IndexCall)]
+    L.fadehip_bam_index_geometry.argtypes = [vp, i32, i32]
+    L.fadehip_recstore_index_geometry.argtypes = [vp, i32, i32]
+    L.fadehip_csi_create.argtypes = [i32, i32, i32]
+    L.fadehip_csi_create.restype = vp
+    L.fadehip_csi_add.argtypes = [vp, C.c_uint64, C.POINTER(IndexCall)]
+    L.fadehip_csi_finish.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.fadehip_csi_error.argtypes = [vp]
+    L.fadehip_csi_error.restype = C.c_char_p
+    L.fadehip_csi_destroy.argtypes = [vp]
+    L.fadehip_csi_destroy.restype = None
     L.fadehip_bam_totals.argtypes = [vp, C.POINTER(i64 * 8), C.POINTER(i64), C.POINTER(i64)]
     L.fadehip_bam_close.argtypes = [vp]
     L.fadehip_bam_close.restype = None

@@ -362,10 +362,12 @@ class Context:
                                                     order.ctypes.data if n > 0 else None))
         return order
 
-    def index_batch(self, recs, rec_off, voff):
+    def index_batch(self, recs, rec_off, voff, csi=None):
         """fadehip_index_batch: the .bai entries of coordinate-sorted BAM records (recs: uint8, concatenated; rec_off: n + 1
         offsets) at the virtual offsets voff (n + 1: record k lies in voff[k] .. voff[k + 1]).  Returns the call's entries as
-        index_call_dict gives them.  Keys that step back: FadeHipError -1; a record ending beyond 2^29: -5."""
+        index_call_dict gives them.  Keys that step back: FadeHipError -1; a record ending beyond 2^29: -5.
+        csi=(min_shift, depth): fadehip_index_batch_csi, the entries of a CSI of that geometry (CsiBuilder takes them); a
+        geometry that is not valid: -1; a record ending beyond 2^(min_shift + 3 * depth): -5."""
         recs = np.ascontiguousarray(recs, dtype=np.uint8)
         rec_off = np.ascontiguousarray(rec_off, dtype=np.int64)
         voff = np.ascontiguousarray(voff, dtype=np.uint64)
@@ -373,6 +375,10 @@ class Context:
         if len(voff) != n + 1:
             raise ValueError("voff holds n + 1 virtual offsets")
         c = _lib.IndexCall()
+        if csi is not None:
+            self._chk(self._L.fadehip_index_batch_csi(self._h, n, recs.ctypes.data if recs.nbytes else None, rec_off.ctypes.data, voff.ctypes.data,
+                                                      int(csi[0]), int(csi[1]), C.byref(c)))
+            return index_call_dict(c)
         self._chk(self._L.fadehip_index_batch(self._h, n, recs.ctypes.data if recs.nbytes else None, rec_off.ctypes.data, voff.ctypes.data, C.byref(c)))
         return index_call_dict(c)
 
@@ -673,10 +679,12 @@ class BaiBuilder:
         self._h = self._L.fadehip_bai_create(int(n_ref))
         if not self._h:
             raise FadeHipError(-1, "fadehip_bai_create failed")
+        self._add, self._finish, self._error, self._destroy = (self._L.fadehip_bai_add, self._L.fadehip_bai_finish, self._L.fadehip_bai_error,
+                                                               self._L.fadehip_bai_destroy)
 
     def _chk(self, rc):
         if rc != 0:
-            raise FadeHipError(rc, self._L.fadehip_bai_error(self._h).decode())
+            raise FadeHipError(rc, self._error(self._h).decode())
 
     def add(self, base_file_offset, call):
         ch = np.array(call["chunks"], dtype=_lib.INDEX_CHUNK_DTYPE) if call["chunks"] else np.zeros(0, _lib.INDEX_CHUNK_DTYPE)
@@ -686,17 +694,45 @@ class BaiBuilder:
             rf[k] = (tid, 0, u, v, nm, nu)
         c = _lib.IndexCall(ch.ctypes.data if len(ch) else None, li.ctypes.data if len(li) else None, rf.ctypes.data if len(rf) else None,
                            len(ch), len(li), len(rf), call["n"], call["first_key"], call["last_key"])
-        self._chk(self._L.fadehip_bai_add(self._h, int(base_file_offset), C.byref(c)))
+        self._chk(self._add(self._h, int(base_file_offset), C.byref(c)))
 
     def finish(self):
         p, n = C.c_void_p(), C.c_size_t(0)
-        self._chk(self._L.fadehip_bai_finish(self._h, C.byref(p), C.byref(n)))
+        self._chk(self._finish(self._h, C.byref(p), C.byref(n)))
         return C.string_at(p, n.value)
 
     def close(self):
         if self._h:
-            self._L.fadehip_bai_destroy(self._h)
+            self._destroy(self._h)
             self._h = None
+
+
+class CsiBuilder(BaiBuilder):
+    """fadehip_csi_*: a .csi out of the calls' index entries made under the geometry (min_shift, depth) —
+    BamStream.index_geometry(), RecStore.index_geometry(), Context.index_batch(csi=) —, on the host.  add() as BaiBuilder's;
+    finish() the uncompressed payload; file_bytes() the file: the payload in BGZF members of at most 0xff00 payload bytes
+    (zlib), then the end-of-file marker."""
+
+    _EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+
+    def __init__(self, n_ref, min_shift, depth):
+        self._L = _lib.load()
+        self._h = self._L.fadehip_csi_create(int(n_ref), int(min_shift), int(depth))
+        if not self._h:
+            raise FadeHipError(-1, "fadehip_csi_create failed (n_ref %d, min_shift %d, depth %d)" % (n_ref, min_shift, depth))
+        self._add, self._finish, self._error, self._destroy = (self._L.fadehip_csi_add, self._L.fadehip_csi_finish, self._L.fadehip_csi_error,
+                                                               self._L.fadehip_csi_destroy)
+
+    def file_bytes(self, level=6):
+        import struct
+        import zlib
+        payload, out = self.finish(), []
+        for at in range(0, len(payload), 0xff00):
+            part = payload[at:at + 0xff00]
+            co = zlib.compressobj(level, zlib.DEFLATED, -15)
+            body = co.compress(part) + co.flush()
+            out.append(b"\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0" + struct.pack("<H", len(body) + 25) + body + struct.pack("<II", zlib.crc32(part), len(part)))
+        return b"".join(out) + self._EOF
 
 
 class PinnedBatch:
@@ -893,6 +929,11 @@ class BamStream:
         self._ctx._chk(self._L.fadehip_bam_back_report(self._h, flag, C.byref(p), C.byref(n), C.byref(nr)))
         return (C.string_at(p, n.value) if n.value else b""), int(nr.value)
 
+    def index_geometry(self, min_shift, depth):
+        """index=True, before the first front(): the calls leave the entries of a CSI of that geometry (CsiBuilder takes them).
+        Later: FadeHipError -6; on a stream without index, or a geometry that is not valid: -1."""
+        self._ctx._chk(self._L.fadehip_bam_index_geometry(self._h, int(min_shift), int(depth)))
+
     def back_index(self):
         """index=True: the .bai entries of the call the last back() finished, as index_call_dict gives them."""
         c = _lib.IndexCall()
@@ -1026,6 +1067,10 @@ class RecStore:
 
     def sort(self):
         self._ctx._chk(self._L.fadehip_recstore_sort(self._h))
+
+    def index_geometry(self, min_shift, depth):
+        """Before the first drain: drain(index=True) hands out the entries of a CSI of that geometry (CsiBuilder takes them)."""
+        self._ctx._chk(self._L.fadehip_recstore_index_geometry(self._h, int(min_shift), int(depth)))
 
     def drain(self, max_payload, raw=False, stored=False, index=False):
         """The next maximal run of records, in final order, of at most max_payload bytes (at least one record): (bytes,

@@ -13,6 +13,8 @@
 //   write   chunks, linear entries and reference runs, dense and in stream order: a run's head writes where it begins, its
 //           last record where it ends, so the work per record does not grow with a run's length
 //   refs    the reference runs' record counts out of the running counts the write kernel left at their ends
+//   key under a CSI geometry (min_shift, depth): a second key kernel, bam_index_key_geo_kernel, with the bin by a level loop,
+//           windows of 2^min_shift positions and the span held to 2^(min_shift + 3 depth); the kernels behind it are the same
 //
 // All kernels here are new; a run without the flag launches none of them, and fadehip_index_batch runs the same kernels over
 // records and offsets the caller brings.  Nothing is carried from call to call on the device.
@@ -31,7 +33,7 @@ struct IndexCtl {
     unsigned long long n_chunks, n_linear, n_refs, n_mapped;  // (the last: mapped records, the write kernel's running count)
     unsigned long long first_key, last_key;
     uint32_t bad_order;   // the lowest record whose key is below the key in front of it, or IX_NONE
-    uint32_t bad_span;    // the lowest record with refID >= 0 and end > 2^29, or IX_NONE
+    uint32_t bad_span;    // the lowest record with refID >= 0 and end > 2^29 (under a geometry: its limit), or IX_NONE
     uint32_t n, pad;
 };
 
@@ -108,7 +110,32 @@ __device__ __forceinline__ uint64_t ix_block_max_scan(uint64_t v, uint64_t *excl
     return inc;
 }
 
-__global__ __launch_bounds__(TAG_BLOCK) void bam_index_key_kernel(IndexArgs a) {
+// The key stage under a CSI geometry (tests/csi_model.py): IndexArgs as it is, and beside it the geometry.
+// min_shift, depth and limit are kernel arguments, so they sit in scalar registers: the level loop below has a wave-uniform
+// trip count and shifts by scalar operands, and no lane leaves it early.
+struct IndexGeoArgs {
+    IndexArgs a;
+    uint32_t min_shift, depth;   // 4 <= min_shift, 1 <= depth <= 8, min_shift + 3 * depth <= 32 (the host checks)
+    uint64_t limit;              // 2^(min_shift + 3 * depth)
+};
+
+// the deepest bin that holds [beg, end], both below 2^32: level l = 1 .. depth has bins of 2^(min_shift + 3 (depth - l))
+// positions from number (8^l - 1) / 7.  Two positions that share a bin share its ancestors, so walking down from level 1 the
+// last level that still holds both is the deepest; the root (bin 0) holds everything.
+__device__ __forceinline__ uint32_t ix_reg2bin_geo(uint32_t beg, uint32_t end, uint32_t min_shift, uint32_t depth) {
+    uint32_t bin = 0, first = 1, s = min_shift + 3u * (depth - 1u);
+    for (uint32_t l = 1; l <= depth; l++) {
+        const uint32_t b = beg >> s;
+        if (b == end >> s) bin = first + b;
+        first = first * 8u + 1u;
+        s -= 3u;
+    }
+    return bin;
+}
+
+// the key kernel's body: GEO false is BAI's fixed tree (the three arguments behind `a` are not read), true the geometry's
+template <bool GEO>
+__device__ __forceinline__ void ix_key(const IndexArgs &a, uint32_t min_shift, uint32_t depth, uint64_t limit) {
     const uint32_t i = blockIdx.x * TAG_BLOCK + threadIdx.x;
     const uint32_t n = ix_n(a);
     uint64_t val = 0;
@@ -145,12 +172,14 @@ __global__ __launch_bounds__(TAG_BLOCK) void bam_index_key_kernel(IndexArgs a) {
         x.wlo = 1;
         x.heads = mapped ? 4u : 0u;
         if (tid >= 0) {
-            if (end > IX_MAX_END) atomicMin(&a.ctl->bad_span, i);
+            if (end > (GEO ? limit : IX_MAX_END)) atomicMin(&a.ctl->bad_span, i);
             else {
-                x.bin = ix_reg2bin((uint32_t)beg, (uint32_t)end);
+                x.bin = GEO ? ix_reg2bin_geo((uint32_t)beg, (uint32_t)(end - 1u), min_shift, depth) : ix_reg2bin((uint32_t)beg, (uint32_t)end);
                 if (mapped) {
-                    x.w0 = (uint32_t)(beg >> 14);
-                    x.w1 = (uint32_t)((end - 1u) >> 14);
+                    // (GEO: end <= limit <= 2^32, so (end - 1) >> min_shift < 2^(32 - min_shift) <= 2^28 with min_shift >= 4:
+                    // w1 + 1 <= 2^28 fits the low 32 bits of the packed maximum, as BAI's 2^15 does)
+                    x.w0 = (uint32_t)(beg >> (GEO ? min_shift : 14u));
+                    x.w1 = (uint32_t)((end - 1u) >> (GEO ? min_shift : 14u));
                     val = ((uint64_t)(uint32_t)tid << 32) | (x.w1 + 1u);
                 }
             }
@@ -163,6 +192,11 @@ __global__ __launch_bounds__(TAG_BLOCK) void bam_index_key_kernel(IndexArgs a) {
     const uint64_t m = ix_block_max_scan(val, &ex);
     if (threadIdx.x == TAG_BLOCK - 1) a.blk_max[blockIdx.x] = m;
 }
+
+__global__ __launch_bounds__(TAG_BLOCK) void bam_index_key_kernel(IndexArgs a) { ix_key<false>(a, 14u, 5u, IX_MAX_END); }
+
+// ... and under a geometry: everything behind it (max scan, count, sum scan, write, refs) reads only tid, bin, w0 and w1
+__global__ __launch_bounds__(TAG_BLOCK) void bam_index_key_geo_kernel(IndexGeoArgs g) { ix_key<true>(g.a, g.min_shift, g.depth, g.limit); }
 
 __global__ __launch_bounds__(1024) void bam_index_max_scan_kernel(IndexArgs a, uint32_t n_blocks) {
     scan_block_sums<uint64_t, true>(a.blk_max, a.blk_carry, n_blocks, (uint64_t *)nullptr);

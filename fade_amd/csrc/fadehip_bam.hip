@@ -15,6 +15,7 @@
 #include "bam_sortwin.hpp"
 #include "bam_intervals.hpp"
 #include "host/bai_build.hpp"
+#include "host/csi_build.hpp"
 #include "host/recstore_host.hpp"
 #include "host/bed_lite.hpp"
 #include <algorithm>
@@ -30,6 +31,14 @@
 
 using namespace fadehip;
 using namespace fadehip::host;
+
+// A CSI geometry as the calls take it (fadehip_index_batch_csi, fadehip_bam_index_geometry, fadehip_recstore_index_geometry);
+// depth 0 stands for "none": BAI's tree, limit and message.
+struct IndexGeometry {
+    int32_t min_shift = 0, depth = 0;
+    uint64_t limit() const { return 1ull << (min_shift + 3 * depth); }
+    static bool valid(int32_t min_shift, int32_t depth) { return min_shift >= 4 && depth >= 1 && depth <= 8 && min_shift + 3 * depth <= 32; }
+};
 
 // A set of read names on the device (bam_names.hpp).  The host's part: the buffers, bounds on what the kernels in flight may
 // have added (exact values as of the last wait, plus the bounds of every launch since), and growth.  Every launch that names
@@ -72,6 +81,8 @@ struct fadehip_recstore {
     uint64_t cursor = 0;              // records drained so far
     DevBuf stage, at, app;            // a drain's bytes and offsets; add_batch's sizes, bases and counts
     DevBuf ix_work, ix_ctl, ix_out;
+    IndexGeometry ix_geo;             // fadehip_recstore_index_geometry: the drains' entries are a CSI's (depth 0: a BAI's)
+    bool drained = false;             // a drain has handed out records: the geometry stays
     bam::IndexCtl ixc;                // a drain's index ctl as it crosses (a member: the copy may outlive a call that fails)
     PinBuf h_out;                     // what a drain hands out: the raw records or the members
     std::vector<uint8_t> h_ix;        // the arrays *idx points into, until the next drain
@@ -1088,6 +1099,7 @@ struct fadehip_bam_stream {
     bool keep_sorted = false;    // FADEHIP_BAM_KEEP_SORTED: clip, and the records leave in coordinate order (bam_resort.hpp)
     uint32_t report = 0;         // FADEHIP_BAM_REPORT_STATS / _CLIP as bam::RP_*: from_tags, and every call leaves the reports' rows (bam_report.hpp)
     bool index = false;          // FADEHIP_BAM_INDEX: every call leaves the .bai entries of the records it wrote (bam_index.hpp)
+    IndexGeometry ix_geo;        // fadehip_bam_index_geometry: ... the entries of a CSI of that geometry instead (depth 0: none)
     bool collect_mates = false;  // FADEHIP_BAM_COLLECT_MATES: from_tags and clip, and every primary paired-end record whose name is in `names` stores its placement in `mates` (bam_mates.hpp)
     bool fix_mates = false;      // FADEHIP_BAM_FIX_MATES: from_tags and clip, and every record's mate fields follow the placement `mates` holds for its mate
     bool calmd = false;          // FADEHIP_BAM_CALMD: from_tags and clip, and NM and MD of every record that leaves hard-clipped are recomputed against the genome (bam_calmd.hpp)
@@ -1308,11 +1320,20 @@ size_t index_out_layout(bam::IndexArgs &a, uint8_t *base, size_t n_cap, size_t c
 }
 
 // the stage up to its counts (a.n > 0): the ctl cleared, keys, the running maximum, heads and counts, their sums
-int enqueue_index_counts(fadehip_ctx *ctx, hipStream_t q, const bam::IndexArgs &a) {
+// (geo.depth 0: BAI's fixed tree, the key kernel as it always was; else the key kernel under the geometry)
+int enqueue_index_counts(fadehip_ctx *ctx, hipStream_t q, const bam::IndexArgs &a, IndexGeometry geo = IndexGeometry()) {
     const unsigned nb = (a.n + bam::TAG_BLOCK - 1u) / bam::TAG_BLOCK;
     HIPCHK(ctx, hipMemsetAsync(a.ctl, 0, sizeof(bam::IndexCtl), q));
     HIPCHK(ctx, hipMemsetAsync(&a.ctl->bad_order, 0xff, 8, q));  // (bad_order and bad_span: IX_NONE)
-    hipLaunchKernelGGL(bam::bam_index_key_kernel, dim3(nb), dim3(bam::TAG_BLOCK), 0, q, a);
+    if (geo.depth) {
+        bam::IndexGeoArgs g;
+        g.a = a;
+        g.min_shift = (uint32_t)geo.min_shift;
+        g.depth = (uint32_t)geo.depth;
+        g.limit = geo.limit();
+        hipLaunchKernelGGL(bam::bam_index_key_geo_kernel, dim3(nb), dim3(bam::TAG_BLOCK), 0, q, g);
+    } else
+        hipLaunchKernelGGL(bam::bam_index_key_kernel, dim3(nb), dim3(bam::TAG_BLOCK), 0, q, a);
     HIPCHK(ctx, hipGetLastError());
     hipLaunchKernelGGL(bam::bam_index_max_scan_kernel, dim3(1), dim3(1024), 0, q, a, nb);
     HIPCHK(ctx, hipGetLastError());
@@ -1334,9 +1355,12 @@ int enqueue_index_write(fadehip_ctx *ctx, hipStream_t q, const bam::IndexArgs &a
 }
 
 // what the stage's flags fail a call with: the lower record of the two, the order first; `first` is record 0's index in the stream
-int index_bad(fadehip_ctx *ctx, const bam::IndexCtl &c, long long first, const char *who) {
+int index_bad(fadehip_ctx *ctx, const bam::IndexCtl &c, long long first, const char *who, IndexGeometry geo = IndexGeometry()) {
     if (c.bad_order != bam::IX_NONE && c.bad_order <= c.bad_span)
         return set_err(ctx, FADEHIP_E_INVALID, "%s: record %lld: not in coordinate order (--write-index needs coordinate-sorted output)", who, first + (long long)c.bad_order);
+    if (c.bad_span != bam::IX_NONE && geo.depth)
+        return set_err(ctx, FADEHIP_E_UNSUPPORTED, "%s: record %lld: ends beyond 2^%d on its reference (a CSI index of min_shift %d and depth %d cannot hold it)", who,
+                       first + (long long)c.bad_span, geo.min_shift + 3 * geo.depth, geo.min_shift, geo.depth);
     if (c.bad_span != bam::IX_NONE)
         return set_err(ctx, FADEHIP_E_UNSUPPORTED, "%s: record %lld: ends beyond 2^29 on its reference (a BAI index cannot hold it)", who, first + (long long)c.bad_span);
     return 0;
@@ -1412,7 +1436,7 @@ int bam_enqueue_index(fadehip_bam_stream *st, uint64_t k, int lane) {
     a.behind_ptr = g.behind_ptr;
     a.member_stride = g.member_stride;
     a.behind = g.behind;
-    if ((rc = enqueue_index_counts(ctx, q, a)) || (rc = enqueue_index_write(ctx, q, a))) return rc;
+    if ((rc = enqueue_index_counts(ctx, q, a, st->ix_geo)) || (rc = enqueue_index_write(ctx, q, a))) return rc;
     HIPCHK(ctx, hipMemcpyAsync(pb.p, a.ctl, sizeof(bam::IndexCtl), hipMemcpyDeviceToHost, q));
     if (!o->iready) HIPCHK(ctx, hipEventCreateWithFlags(&o->iready, hipEventDisableTiming | (ctx->blocking_sync ? hipEventBlockingSync : 0)));
     HIPCHK(ctx, hipEventRecord(o->iready, q));
@@ -1432,7 +1456,7 @@ int bam_take_index(fadehip_bam_stream *st, uint64_t k, int lane) {
     HIPCHK(ctx, hipEventSynchronize(o->iready));
     bam::IndexCtl c = *(const bam::IndexCtl *)pb.p;
     int rc;
-    if ((rc = index_bad(ctx, c, (long long)st->ix_records, "bam stream"))) return rc;
+    if ((rc = index_bad(ctx, c, (long long)st->ix_records, "bam stream", st->ix_geo))) return rc;
     if (c.n && st->ix_have_key && c.first_key < st->ix_last_key)
         return set_err(ctx, FADEHIP_E_INVALID, "bam stream: record %lld: not in coordinate order (--write-index needs coordinate-sorted output)", (long long)st->ix_records);
     if (c.n_linear > o->ixa.cap_linear) {
@@ -2714,6 +2738,18 @@ int fadehip_bam_use_recstore(fadehip_bam_stream *st, fadehip_recstore *s) {
     return 0;
 }
 
+int fadehip_bam_index_geometry(fadehip_bam_stream *st, int32_t min_shift, int32_t depth) {
+    if (!st) return set_err(nullptr, FADEHIP_E_INVALID, "stream is NULL");
+    fadehip_ctx *ctx = st->ctx;
+    if (!st->index) return set_err(ctx, FADEHIP_E_INVALID, "bam stream: opened without FADEHIP_BAM_INDEX");
+    if (!IndexGeometry::valid(min_shift, depth))
+        return set_err(ctx, FADEHIP_E_INVALID, "bam stream: CSI geometry (min_shift %d, depth %d): 4 <= min_shift, 1 <= depth <= 8, min_shift + 3 * depth <= 32", (int)min_shift, (int)depth);
+    if (st->k_front) return set_err(ctx, FADEHIP_E_STATE, "bam stream: index_geometry comes before the first front call");
+    st->ix_geo.min_shift = min_shift;
+    st->ix_geo.depth = depth;
+    return 0;
+}
+
 int fadehip_bam_use_intervals(fadehip_bam_stream *st, fadehip_intervals *s) {
     if (!st) return set_err(nullptr, FADEHIP_E_INVALID, "stream is NULL");
     fadehip_ctx *ctx = st->ctx;
@@ -3058,7 +3094,22 @@ int fadehip_bam_back_index(fadehip_bam_stream *st, fadehip_index_call *out) {
 
 // The index entries of records the caller brings, at virtual offsets the caller brings: bam_index.hpp's kernels, the ones of
 // the file path under FADEHIP_BAM_INDEX, on the record-batch lane.
+static int index_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const int64_t *rec_off, const uint64_t *voff, IndexGeometry geo, fadehip_index_call *out);
 int fadehip_index_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const int64_t *rec_off, const uint64_t *voff, fadehip_index_call *out) {
+    return index_batch(ctx, n, recs, rec_off, voff, IndexGeometry(), out);
+}
+// ... and under a CSI geometry: the key kernel of bam_index.hpp that takes one, the kernels behind it as they are
+int fadehip_index_batch_csi(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const int64_t *rec_off, const uint64_t *voff, int32_t min_shift, int32_t depth,
+                            fadehip_index_call *out) {
+    if (!ctx) return set_err(nullptr, FADEHIP_E_INVALID, "ctx is NULL");
+    if (!IndexGeometry::valid(min_shift, depth))
+        return set_err(ctx, FADEHIP_E_INVALID, "index batch: CSI geometry (min_shift %d, depth %d): 4 <= min_shift, 1 <= depth <= 8, min_shift + 3 * depth <= 32", (int)min_shift, (int)depth);
+    IndexGeometry geo;
+    geo.min_shift = min_shift;
+    geo.depth = depth;
+    return index_batch(ctx, n, recs, rec_off, voff, geo, out);
+}
+static int index_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const int64_t *rec_off, const uint64_t *voff, IndexGeometry geo, fadehip_index_call *out) {
     if (!ctx) return set_err(nullptr, FADEHIP_E_INVALID, "ctx is NULL");
     if (n < 0 || !rec_off || !voff || !out || (n > 0 && !recs)) return set_err(ctx, FADEHIP_E_INVALID, "NULL argument");
     memset(out, 0, sizeof *out);
@@ -3081,11 +3132,11 @@ int fadehip_index_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const 
     a.at = (const uint64_t *)L.meta.p;
     a.n = (uint32_t)n;
     a.voff = (const uint64_t *)((uint8_t *)L.meta.p + m_voff);
-    if ((rc = enqueue_index_counts(ctx, L.stream, a))) return rc;
+    if ((rc = enqueue_index_counts(ctx, L.stream, a, geo))) return rc;
     bam::IndexCtl c;
     HIPCHK(ctx, hipMemcpyAsync(&c, a.ctl, sizeof c, hipMemcpyDeviceToHost, L.stream));
     HIPCHK(ctx, hipStreamSynchronize(L.stream));
-    if ((rc = index_bad(ctx, c, 0, "index batch"))) return rc;
+    if ((rc = index_bad(ctx, c, 0, "index batch", geo))) return rc;
     if (c.n_linear >> 31) return set_err(ctx, FADEHIP_E_UNSUPPORTED, "index batch: %llu linear index entries (at most 2^31)", (unsigned long long)c.n_linear);
     const size_t out_bytes = index_out_layout(a, nullptr, (size_t)n, (size_t)c.n_linear);
     if ((rc = reserve(ctx, L.out, out_bytes + 8))) return rc;
@@ -3149,6 +3200,48 @@ int fadehip_bai_finish(fadehip_bai *b, const uint8_t **bytes, size_t *n) {
 }
 const char *fadehip_bai_error(const fadehip_bai *b) { return b ? b->b.err.c_str() : g_bai_null_err.c_str(); }
 void fadehip_bai_destroy(fadehip_bai *b) { delete b; }
+
+// ... and of a CSI (host/csi_build.hpp)
+struct fadehip_csi {
+    fadehip::csi::Builder b;
+    fadehip_csi(int32_t n_ref, int32_t min_shift, int32_t depth) : b(n_ref, min_shift, depth) {}
+};
+static thread_local std::string g_csi_null_err;
+
+fadehip_csi *fadehip_csi_create(int32_t n_ref, int32_t min_shift, int32_t depth) {
+    if (n_ref < 0 || !fadehip::csi::valid_geometry(min_shift, depth)) return nullptr;
+    try {
+        return new fadehip_csi(n_ref, min_shift, depth);
+    } catch (...) {
+        return nullptr;
+    }
+}
+int fadehip_csi_add(fadehip_csi *b, uint64_t base_file_offset, const fadehip_index_call *call) {
+    if (!b) {
+        g_csi_null_err = "csi: builder is NULL";
+        return FADEHIP_E_INVALID;
+    }
+    try {
+        return b->b.add(base_file_offset, call);
+    } catch (...) {
+        b->b.err = "csi: out of memory";
+        return FADEHIP_E_NOMEM;
+    }
+}
+int fadehip_csi_finish(fadehip_csi *b, const uint8_t **payload, size_t *n) {
+    if (!b) {
+        g_csi_null_err = "csi: builder is NULL";
+        return FADEHIP_E_INVALID;
+    }
+    try {
+        return b->b.finish(payload, n);
+    } catch (...) {
+        b->b.err = "csi: out of memory";
+        return FADEHIP_E_NOMEM;
+    }
+}
+const char *fadehip_csi_error(const fadehip_csi *b) { return b ? b->b.err.c_str() : g_csi_null_err.c_str(); }
+void fadehip_csi_destroy(fadehip_csi *b) { delete b; }
 
 // ---- the record store over records the caller brings, its sort and its drains (bam_recstore.hpp)
 int fadehip_recstore_create(fadehip_ctx *ctx, fadehip_recstore **out) {
@@ -3533,7 +3626,7 @@ int fadehip_recstore_drain(fadehip_recstore *s, int32_t flags, uint64_t max_payl
             a.behind_ptr = geo.behind_ptr;
             a.member_stride = geo.member_stride;
             a.behind = geo.behind;
-            if ((rc = enqueue_index_counts(ctx, q, a))) return rc;
+            if ((rc = enqueue_index_counts(ctx, q, a, s->ix_geo))) return rc;
             HIPCHK(ctx, hipMemcpyAsync(&c, a.ctl, sizeof c, hipMemcpyDeviceToHost, q));
         }
         if (stored) {
@@ -3549,7 +3642,7 @@ int fadehip_recstore_drain(fadehip_recstore *s, int32_t flags, uint64_t max_payl
                 return code;
             };
             if (hipStreamSynchronize(q) != hipSuccess) return fail(set_err(ctx, FADEHIP_E_HIP, "recstore: the index stage failed"));
-            if ((rc = index_bad(ctx, c, (long long)j0, "recstore drain"))) return fail(rc);
+            if ((rc = index_bad(ctx, c, (long long)j0, "recstore drain", s->ix_geo))) return fail(rc);
             if (c.n_linear >> 31) return fail(set_err(ctx, FADEHIP_E_UNSUPPORTED, "recstore drain: %llu linear index entries (at most 2^31)", (unsigned long long)c.n_linear));
             const size_t ix_bytes = index_out_layout(a, nullptr, n, (size_t)c.n_linear);
             if ((rc = reserve_roomy(ctx, s->ix_out, ix_bytes + 8))) return fail(rc);
@@ -3573,6 +3666,19 @@ int fadehip_recstore_drain(fadehip_recstore *s, int32_t flags, uint64_t max_payl
     }
     *n_records = (int64_t)n;
     s->cursor = j1;
+    s->drained = true;
+    return 0;
+}
+
+int fadehip_recstore_index_geometry(fadehip_recstore *s, int32_t min_shift, int32_t depth) {
+    if (!s) return set_err(nullptr, FADEHIP_E_INVALID, "recstore is NULL");
+    fadehip_ctx *ctx = s->ctx;
+    if (!IndexGeometry::valid(min_shift, depth))
+        return set_err(ctx, FADEHIP_E_INVALID, "recstore: CSI geometry (min_shift %d, depth %d): 4 <= min_shift, 1 <= depth <= 8, min_shift + 3 * depth <= 32", (int)min_shift, (int)depth);
+    std::lock_guard<std::mutex> sl(s->mu);
+    if (s->drained) return set_err(ctx, FADEHIP_E_STATE, "recstore: index_geometry comes before the first drain");
+    s->ix_geo.min_shift = min_shift;
+    s->ix_geo.depth = depth;
     return 0;
 }
 

@@ -75,6 +75,7 @@ static void print_anno_help() {
             "    --keep-sorted with -c, coordinate-sorted BAM file in, -b or -u out, one MI355X: clipped records are written at their new coordinates, so the output stays coordinate-sorted\n"
             "           --sort BAM file in, in any order, -b or -u out, one MI355X: the output is written in coordinate order (@HD SO:coordinate), sorted on the device (a file too large for it: sort in the fade out step)\n"
             "    --write-index PATH: also write the BAM index (.bai) of the output, made in the same pass (coordinate-sorted output, BAM file in, -b or -u out, one MI355X)\n"
+            "            --csi with --write-index or --extract-sorted: the index is a CSI (min_shift 14, depth 5, or 6 for contigs longer than 2^29; PATH.csi beside --extract PATH)\n"
             "          --gpus number of MI355X devices, one process each on its own range of the input (default 1)\n"
             "    --out-shards with --gpus N: every device writes a complete file PREFIX.<k>.bam (.sam), nothing is merged\n"
             "         --batch records per device batch (default 262144)\n"
@@ -96,6 +97,7 @@ struct Opts {
     std::string out_shards;  // --out-shards PREFIX (with --gpus N)
     std::string stats_tsv, clip_tsv;  // --stats-tsv PATH, --clip-tsv PATH: the stats.d / noclip.d reports of this run
     std::string write_index;  // --write-index PATH: the .bai of the BAM on stdout, made on the device in the same pass
+    bool csi = false;  // --csi: the index --write-index (and --extract-sorted) writes is a CSI, min_shift 14 and the depth the longest contig needs, not a BAI
     std::string extract;  // --extract PATH: `fade extract`'s records of this run's artifact calls, in the output's format
     bool sorted = false;  // `fade extract --sorted`: the records leave in coordinate order (a store of records on the device, sorted once at the end)
     bool extract_sorted = false;  // `fade annotate --extract PATH --extract-sorted`: PATH is written in coordinate order, PATH.bai beside it
@@ -218,6 +220,11 @@ static bool parse_opts(int argc, char **argv, Opts &o, std::string &err) {
                 if (has_val && val != "true" && val != "false") { err = "Invalid value for option --" + name + ": " + val; return false; }
                 (name == "sorted" ? o.sorted : o.extract_sorted) = !has_val || val == "true";
             }
+            else if (name == "csi") {  // (a flag, as --eject)
+                o.seen += 'J';
+                if (has_val && val != "true" && val != "false") { err = "Invalid value for option --csi: " + val; return false; }
+                o.csi = !has_val || val == "true";
+            }
             else if (name == "sort") {  // (a flag, as --eject)
                 o.seen += 'Z';
                 if (has_val && val != "true" && val != "false") { err = "Invalid value for option --sort: " + val; return false; }
@@ -261,19 +268,70 @@ static void report_held(const Opts &o) {
     if (o.keep_sorted && o.timing) fprintf(stderr, "[timing] --keep-sorted: at most %lld records (%lld bytes) held on the device between calls\n", (long long)g_held_max_recs, (long long)g_held_max_bytes);
 }
 
+// The index file --write-index and --extract-sorted make: a .bai (fadehip_bai_*), or with --csi a .csi (fadehip_csi_*): min_shift
+// 14 and the smallest depth >= 5 whose limit 2^(14 + 3 depth) holds the longest @SQ LN — 5 for every genome a BAI can hold, 6
+// beyond, since pos has 32 bits.  A driver sets the depth once its header is read (0: a BAI); the streams and the store that
+// make the entries get the same geometry (index_geometry below).
+static const int32_t kCsiMinShift = 14;
+static int32_t g_csi_depth = 0;
+static const char *g_csi_who = "fade";  // whose [I::...] line reports the depth chosen
+static int32_t csi_depth_for(const Header &hdr) {
+    int64_t longest = 0;
+    for (const int64_t len : hdr.lens) longest = std::max(longest, len);
+    int32_t depth = 5;
+    while (depth < 6 && longest > ((int64_t)1 << (kCsiMinShift + 3 * depth))) depth++;
+    return depth;
+}
+struct IndexFile {
+    fadehip_bai *bai = nullptr;
+    fadehip_csi *csi = nullptr;
+    ~IndexFile() {
+        if (bai) fadehip_bai_destroy(bai);
+        if (csi) fadehip_csi_destroy(csi);
+    }
+    bool on() const { return bai || csi; }
+    void create(size_t n_ref) {
+        if (g_csi_depth) csi = fadehip_csi_create((int32_t)n_ref, kCsiMinShift, g_csi_depth);
+        else bai = fadehip_bai_create((int32_t)n_ref);
+        if (!on()) throw std::runtime_error("out of memory");
+    }
+    void add(uint64_t at, const fadehip_index_call *c) {
+        if (csi ? fadehip_csi_add(csi, at, c) : fadehip_bai_add(bai, at, c)) throw std::runtime_error(csi ? fadehip_csi_error(csi) : fadehip_bai_error(bai));
+    }
+    // the .bai's bytes as they are; the .csi's payload in BGZF members of the driver's own writer, then the end-of-file marker
+    void write(const std::string &path) {
+        const uint8_t *p = nullptr;
+        size_t n = 0;
+        if (csi ? fadehip_csi_finish(csi, &p, &n) : fadehip_bai_finish(bai, &p, &n)) throw std::runtime_error(csi ? fadehip_csi_error(csi) : fadehip_bai_error(bai));
+        std::vector<uint8_t> members;
+        if (csi) {
+            for (size_t at = 0; at < n; at += 0xff00) bgzf_compress_block(p + at, std::min<size_t>(n - at, 0xff00), 6, members);
+            members.insert(members.end(), BGZF_EOF, BGZF_EOF + sizeof BGZF_EOF);
+            p = members.data();
+            n = members.size();
+        }
+        FILE *f = fopen(path.c_str(), "wb");
+        if (!f) throw std::runtime_error("cannot write " + path + ": " + strerror(errno));
+        const bool ok = fwrite(p, 1, n, f) == n;
+        if (fclose(f) != 0 || !ok) throw std::runtime_error("write error on " + path);
+        if (csi)  // (a BAI is written without a word, as it always was)
+            fprintf(stderr, "[I::%s] --csi: %s is a CSI index of min_shift %d and depth %d (coordinates up to 2^%d)\n", g_csi_who, path.c_str(), (int)kCsiMinShift, (int)g_csi_depth,
+                    (int)(kCsiMinShift + 3 * g_csi_depth));
+    }
+    static int stream_geometry(fadehip_bam_stream *st) { return g_csi_depth ? fadehip_bam_index_geometry(st, kCsiMinShift, g_csi_depth) : 0; }
+};
 // --write-index PATH: the .bai of the BAM that goes to stdout.  Every call of the file path leaves its index entries at
 // offsets relative to its first member (fadehip_bam_back_index); the driver knows where that member lies in the output — the
 // header members it wrote, then the bytes of the calls before — so stdout may be a pipe.  PATH is written behind the
 // end-of-file marker.
 struct IndexSink {
-    fadehip_bai *b = nullptr;
+    IndexFile b;
     uint64_t at = 0;  // file offset of the next call's first member
     std::string path;
-    ~IndexSink() { if (b) fadehip_bai_destroy(b); }
-    bool on() const { return b != nullptr; }
+    bool on() const { return b.on(); }
     void open(const std::string &p, size_t n_ref) {
         path = p;
-        if (!(b = fadehip_bai_create((int32_t)n_ref))) throw std::runtime_error("out of memory");
+        b.create(n_ref);
     }
     // the header's members through `write` into memory first, so that their size is known whatever stdout is
     template <class WriteHeader>
@@ -299,18 +357,10 @@ struct IndexSink {
     void call(fadehip_bam_stream *st, fadehip_ctx *ctx, size_t n) {
         fadehip_index_call c;
         if (fadehip_bam_back_index(st, &c)) throw std::runtime_error(fadehip_last_error(ctx));
-        if (fadehip_bai_add(b, at, &c)) throw std::runtime_error(fadehip_bai_error(b));
+        b.add(at, &c);
         at += n;
     }
-    void write() {
-        const uint8_t *p = nullptr;
-        size_t n = 0;
-        if (fadehip_bai_finish(b, &p, &n)) throw std::runtime_error(fadehip_bai_error(b));
-        FILE *f = fopen(path.c_str(), "wb");
-        if (!f) throw std::runtime_error("cannot write " + path + ": " + strerror(errno));
-        const bool ok = fwrite(p, 1, n, f) == n;
-        if (fclose(f) != 0 || !ok) throw std::runtime_error("write error on " + path);
-    }
+    void write() { b.write(path); }
 };
 
 // `fade extract --sorted`, `fade annotate --extract-sorted`: the run's extract records are in a record store on the device
@@ -326,11 +376,11 @@ struct SortedWriter {
     FILE *out;
     bool stored;
     std::string bai_path;
-    fadehip_bai *bai = nullptr;
+    IndexFile bai;
+    bool geometry_set = false;  // --csi: the store has the geometry (set once, in front of its first drain)
     uint64_t at = 0;  // file offset of the next drain's first member
     int64_t total = 0;
     SortedWriter(fadehip_ctx *c, FILE *o, bool st, const std::string &bp) : ctx(c), out(o), stored(st), bai_path(bp) {}
-    ~SortedWriter() { if (bai) fadehip_bai_destroy(bai); }
     void begin(Header hdr, Pool *pool) {
         hdr.text = fadehip::recstore::header_sorted(hdr.text);
         char *mp = nullptr;
@@ -350,35 +400,31 @@ struct SortedWriter {
         free(mp);
         if (!ok) throw std::runtime_error("write error on the sorted output");
         at = mn;
-        if (!bai_path.empty() && !(bai = fadehip_bai_create((int32_t)hdr.names.size()))) throw std::runtime_error("out of memory");
+        if (!bai_path.empty()) bai.create(hdr.names.size());
     }
     void window(fadehip_recstore *rs) {
         if (fadehip_recstore_sort(rs)) throw std::runtime_error(fadehip_last_error(ctx));
-        const int32_t flags = (stored ? FADEHIP_RECSTORE_STORED : 0) | (bai ? FADEHIP_RECSTORE_INDEX : 0);
+        const int32_t flags = (stored ? FADEHIP_RECSTORE_STORED : 0) | (bai.on() ? FADEHIP_RECSTORE_INDEX : 0);
+        if (bai.csi && !geometry_set) {
+            if (fadehip_recstore_index_geometry(rs, kCsiMinShift, g_csi_depth)) throw std::runtime_error(fadehip_last_error(ctx));
+            geometry_set = true;
+        }
         for (;;) {
             const uint8_t *p = nullptr;
             size_t n = 0;
             int64_t n_rec = 0;
             fadehip_index_call c;
-            if (fadehip_recstore_drain(rs, flags, (uint64_t)64 << 20, &p, &n, &n_rec, bai ? &c : nullptr)) throw std::runtime_error(fadehip_last_error(ctx));
+            if (fadehip_recstore_drain(rs, flags, (uint64_t)64 << 20, &p, &n, &n_rec, bai.on() ? &c : nullptr)) throw std::runtime_error(fadehip_last_error(ctx));
             if (!n_rec) break;
             if (fwrite(p, 1, n, out) != n) throw std::runtime_error("write error on the sorted output");
-            if (bai && fadehip_bai_add(bai, at, &c)) throw std::runtime_error(fadehip_bai_error(bai));
+            if (bai.on()) bai.add(at, &c);
             at += n;
             total += n_rec;
         }
     }
     void finish() {
         if (fwrite(BGZF_EOF, 1, sizeof BGZF_EOF, out) != sizeof BGZF_EOF || fflush(out) != 0 || ferror(out)) throw std::runtime_error("write error on the sorted output");
-        if (bai) {
-            const uint8_t *p = nullptr;
-            size_t n = 0;
-            if (fadehip_bai_finish(bai, &p, &n)) throw std::runtime_error(fadehip_bai_error(bai));
-            FILE *f = fopen(bai_path.c_str(), "wb");
-            if (!f) throw std::runtime_error("cannot write " + bai_path + ": " + strerror(errno));
-            const bool wrote = fwrite(p, 1, n, f) == n;
-            if (fclose(f) != 0 || !wrote) throw std::runtime_error("write error on " + bai_path);
-        }
+        if (bai.on()) bai.write(bai_path);
     }
 };
 static int64_t write_sorted_store(fadehip_ctx *ctx, fadehip_recstore *rs, FILE *out, bool stored, Header hdr, Pool *pool, const std::string &bai_path) {
@@ -1773,6 +1819,8 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
         return 1;  // the host path reports what is wrong with the file
     }
     *fall_back = false;
+    g_csi_depth = o.csi ? csi_depth_for(hdr) : 0;
+    g_csi_who = "fade-annotate";
     if (o.timing) fprintf(stderr, "[timing] since process start %.3f s (annotate begins; file path on the device)\n", since_process_start());
     if (!lane.on && !o.sort) fprintf(stderr, "[W::fade annotate] Output SAM/BAM will not be sorted (regardless of prior sorting)\n");
     const bool eject_grouped = o.eject && eject_mode_grouped(eject_names);
@@ -1860,6 +1908,7 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
                 }
             }
             if (fadehip_bam_open(ctx, &cfg, &st)) { create_err = fadehip_last_error(ctx); return 1; }
+            if ((cfg.flags & FADEHIP_BAM_INDEX) && IndexFile::stream_geometry(st)) { create_err = fadehip_last_error(ctx); return 1; }  // --csi
             if (store && fadehip_bam_use_recstore(st, store)) { create_err = fadehip_last_error(ctx); return 1; }
             const size_t call_bytes = host_inflate ? chunk : std::min<size_t>(chunk * 3, (size_t)1 << 30);
             if (!(getenv("FADE_BAM_PREPARE") && atoi(getenv("FADE_BAM_PREPARE")) == 0) && fadehip_bam_prepare(st, call_bytes)) { create_err = fadehip_last_error(ctx); return 1; }
@@ -2191,7 +2240,7 @@ static int annotate_stream_main(const std::string &cl, const Opts &o, bool *fall
         if (store && !o.sort) {  // --extract-sorted: PATH in coordinate order and PATH.bai beside it, behind the finished main output
             StageClock ck_sorted;
             ck_sorted.start();
-            const int64_t n_sorted = write_sorted_store(ctx, store, xfile.f, o.ubam, out_hdr, &pool, o.extract + ".bai");
+            const int64_t n_sorted = write_sorted_store(ctx, store, xfile.f, o.ubam, out_hdr, &pool, o.extract + (o.csi ? ".csi" : ".bai"));
             ck_sorted.stop();
             if (o.timing) fprintf(stderr, "[timing] --extract-sorted: %lld records sorted on the device and written in coordinate order in %.3f s\n", (long long)n_sorted, ck_sorted.t);
         }
@@ -2643,6 +2692,7 @@ static bool options_allowed(const Opts &o, const char *allowed) {
             if (c == 'R') fprintf(stderr, "std.getopt.GetOptException: Unrecognized option --repeats\n[E::fade] --repeats: the option goes with fade stats --gpus 1 (it adds two columns to that report's rows)\n");
             else if (c == 'Z') fprintf(stderr, "std.getopt.GetOptException: Unrecognized option --sort\n[E::fade] --sort: the option goes with fade out --gpus 1 and fade annotate (the output's records are sorted on the device)\n");
             else if (c == 'N') fprintf(stderr, "std.getopt.GetOptException: Unrecognized option --calmd\n[E::fade] --calmd: the option goes with fade out -c --gpus 1 (NM and MD of the clipped reads follow the clip)\n");
+            else if (c == 'J') fprintf(stderr, "std.getopt.GetOptException: Unrecognized option --csi\n[E::fade] --csi: the option goes with --write-index PATH (fade annotate, fade out, fade extract --sorted) and fade annotate --extract-sorted (the index is written as a CSI)\n");
             else fprintf(stderr, "std.getopt.GetOptException: Unrecognized option %s%c\n", "-", c);
             return false;
         }
@@ -2659,6 +2709,7 @@ static void print_extract_help() {
             "      --gpus 1: BAM file in, -b or -u out: the records are built on one MI355X (rs and am read back by a kernel)\n"
             "    --sorted with --gpus 1: the records are kept on the MI355X, sorted once by coordinate and written in that order (@HD SO:coordinate)\n"
             "--write-index PATH: with --sorted, also write the BAM index (.bai) of the output, made in the same pass\n"
+            "--csi with --write-index: the index is a CSI (min_shift 14, depth 5, or 6 for contigs longer than 2^29), not a BAI\n"
             "    --timing print where the run spent its time to stderr\n"
             "-h    --help This help information.\n\n",
             kHeader);
@@ -2768,6 +2819,7 @@ static void print_out_help() {
             "--keep-sorted with -c, coordinate-sorted BAM file in, -b or -u out, on one MI355X: clipped records are written at their new coordinates, so the output stays coordinate-sorted\n"
             "      --sort with --gpus 1, BAM file in, in any order, -b or -u out: the output is written in coordinate order (@HD SO:coordinate), sorted on the MI355X; a file too large for it in several passes\n"
             "--write-index PATH: also write the BAM index (.bai) of the output, made in the same pass (coordinate-sorted output, BAM file in, -b or -u out, on one MI355X)\n"
+            "--csi with --write-index: the index is a CSI (min_shift 14, depth 5, or 6 for contigs longer than 2^29), not a BAI\n"
             "    --timing print where the run spent its time to stderr\n"
             "-h    --help This help information.\n\n",
             kHeader);
@@ -3086,6 +3138,8 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
         return 1;  // the host loop reports what is wrong with the file
     }
     *fall_back = false;
+    g_csi_depth = o.csi ? csi_depth_for(hdr) : 0;
+    g_csi_who = job == TagsJob::EXTRACT ? "fade extract" : "fade-out";
     if (o.timing) fprintf(stderr, "[timing] since process start %.3f s (%s begins; file path on the device)\n", since_process_start(), who);
     // `fade out -c --calmd REF.fa` (never beside --sort: main refuses that): the @SQ lines held against the FASTA here, before any device is opened and any output
     // written; the genome goes up once the context exists (the loader is `fade annotate`'s, as it stands)
@@ -3169,6 +3223,7 @@ static int tags_stream_main(const std::string &cl, const Opts &o, TagsJob job, b
             cfg.first_record = first_rec;
             cfg.flags = FADEHIP_BAM_FROM_TAGS | mode;
             if (fadehip_bam_open(ctx, &cfg, &st)) { create_err = fadehip_last_error(ctx); return 1; }
+            if ((mode & FADEHIP_BAM_INDEX) && IndexFile::stream_geometry(st)) { create_err = fadehip_last_error(ctx); return 1; }  // --csi
             if ((mode & (FADEHIP_BAM_COLLECT_NAMES | FADEHIP_BAM_EJECT_NAMED | FADEHIP_BAM_COLLECT_MATES)) && fadehip_bam_use_nameset(st, names)) { create_err = fadehip_last_error(ctx); return 1; }
             if ((mode & (FADEHIP_BAM_COLLECT_MATES | FADEHIP_BAM_FIX_MATES)) && fadehip_bam_use_mateset(st, mates)) { create_err = fadehip_last_error(ctx); return 1; }
             if ((mode & (FADEHIP_BAM_STORE_EXTRACT | FADEHIP_BAM_STORE_OUTPUT)) && fadehip_bam_use_recstore(st, store)) { create_err = fadehip_last_error(ctx); return 1; }
@@ -3585,6 +3640,9 @@ static std::string write_index_refusal(const Opts &o, bool reports) {
     return bgzf ? "" : kWriteIndexInput;
 }
 
+// --csi: the option says how an index is written, so without an index to write it is refused, by name, before any device is opened.
+static const char *const kCsiNoIndex = "it says how the index is written (a CSI, for references longer than 2^29): the option goes with --write-index PATH";
+
 // --sort (`fade out`): why the option cannot run as the command line stands, or "".  The output's records are kept, sorted and
 // compressed on one device: there is no host loop behind the option.  Looks at the options, the environment and the first bytes
 // of the input: no device is opened for it.
@@ -3659,7 +3717,7 @@ int main(int argc, char **argv) {
                                                                                       : "the option goes with fade stats --gpus 1 (it adds two columns to that report's rows)");
             return 1;
         }
-        if (!options_allowed(o, "tmwbucgBsTSPQXEKIYZN")) return 1;
+        if (!options_allowed(o, "tmwbucgBsTSPQXEKIYZNJ")) return 1;
         if (!o.calmd.empty()) {  // recognised, and refused by name: the fused pass also edits rs / am / as / ar / ab, and its rewrite kernel does not call the NM / MD functions yet
             fprintf(stderr, "[E::fade-annotate] --calmd: not built for the annotate pass; annotate first, then: fade out -c --calmd %s --gpus 1 -b <annotated BAM>\n", o.calmd.c_str());
             return 1;
@@ -3697,6 +3755,10 @@ int main(int argc, char **argv) {
                 fprintf(stderr, "[E::fade-annotate] --keep-sorted: %s\n", why);
                 return 1;
             }
+        }
+        if (o.csi && o.write_index.empty() && !o.extract_sorted) {  // refused here, by name, before any device is opened
+            fprintf(stderr, "[E::fade-annotate] --csi: %s or --extract-sorted\n", kCsiNoIndex);
+            return 1;
         }
         if (!o.write_index.empty()) {  // refused here, by name, before any device is opened
             const std::string why = write_index_refusal(o, reports);
@@ -3810,7 +3872,7 @@ int main(int argc, char **argv) {
             fprintf(stderr, "std.getopt.GetOptException: %s\n", err.c_str());
             return 1;
         }
-        if (!options_allowed(o, "tbugTOISN")) return 1;
+        if (!options_allowed(o, "tbugTOISNJ")) return 1;
         if (!o.calmd.empty()) {  // recognised, and refused by name
             fprintf(stderr, "[E::fade extract] --calmd: extract writes new records of the artifact sides, which carry no NM or MD: the option goes with fade out -c\n");
             return 1;
@@ -3820,6 +3882,10 @@ int main(int argc, char **argv) {
             // (in std.getopt's words, as before --sorted existed: without it this subcommand has no such option)
             fprintf(stderr, "std.getopt.GetOptException: Unrecognized option --write-index without --sorted\n"
                             "[E::fade extract] --write-index: the extract records leave in the order of the input's reads, and an index is of coordinate-sorted records: the option goes with --sorted\n");
+            return 1;
+        }
+        if (o.csi && o.write_index.empty()) {  // refused here, by name, before any device is opened
+            fprintf(stderr, "[E::fade extract] --csi: %s (with --sorted)\n", kCsiNoIndex);
             return 1;
         }
         if (!o.out_shards.empty()) {
@@ -3870,7 +3936,7 @@ int main(int argc, char **argv) {
             fprintf(stderr, "[E::fade-out] --calmd: --out-shards writes one file per device, and --calmd goes with one device (--gpus 1): not with --out-shards\n");
             return 1;
         }
-        if (!options_allowed(o, "ctbugTFKIMZN")) return 1;
+        if (!options_allowed(o, "ctbugTFKIMZNJ")) return 1;
         if (o.help || o.pos.size() < 2) { print_out_help(); return 0; }
         if (!o.calmd.empty()) {  // refused here, by name, before any device is opened: the genome lives on one device, and there is no host loop
             const char *why = !o.clip ? "without -c no record is clipped and NM and MD stay true: the option goes with -c"
@@ -3909,6 +3975,10 @@ int main(int argc, char **argv) {
                 fprintf(stderr, "[E::fade-out] --keep-sorted: %s\n", why);
                 return 1;
             }
+        }
+        if (o.csi && o.write_index.empty()) {  // refused here, by name, before any device is opened
+            fprintf(stderr, "[E::fade-out] --csi: %s\n", kCsiNoIndex);
+            return 1;
         }
         if (!o.write_index.empty()) {  // refused here, by name, before any device is opened
             const std::string why = write_index_refusal(o, false);

@@ -309,6 +309,20 @@ typedef struct {
 int fadehip_index_batch(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const int64_t *rec_off, const uint64_t *voff /* [n + 1] */,
                         fadehip_index_call *out);
 
+/* The same entries under a CSI geometry (min_shift, depth) — what `samtools index -c` answers BAI's 2^29 with (DESIGN.md
+ * 3.8p; tests/csi_model.py states the rule in Python).  4 <= min_shift, 1 <= depth <= 8, min_shift + 3 * depth <= 32, else
+ * FADEHIP_E_INVALID before any device call; limit = 2^(min_shift + 3 * depth).
+ *   bins     level l = 0 (the root) .. depth has 8^l bins of 2^(min_shift + 3 (depth - l)) positions, numbered from
+ *            (8^l - 1) / 7; a record's bin is the deepest one that holds [beg, end).  (14, 5) gives fadehip_index_batch's arrays
+ *   span     refID >= 0 with end > limit: FADEHIP_E_UNSUPPORTED; fadehip_last_error names the record, the limit as a power of
+ *            two and "CSI"
+ *   linear   windows of 2^min_shift positions.  A CSI file holds no linear index: fadehip_csi_finish derives every bin's
+ *            loffset from the entries
+ * Order, chunks, refs, offsets and the lifetime of *out are fadehip_index_batch's; so are all kernels but the first, which
+ * has a second form that takes the geometry. */
+int fadehip_index_batch_csi(fadehip_ctx *ctx, int32_t n, const uint8_t *recs, const int64_t *rec_off, const uint64_t *voff /* [n + 1] */,
+                            int32_t min_shift, int32_t depth, fadehip_index_call *out);
+
 /* The host's part: a .bai out of the calls' entries, in stream order.  No device is involved (a NULL builder or argument:
  * FADEHIP_E_INVALID; fadehip_bai_error has the message).
  *   add     offsets + (base_file_offset << 16); chunks, first-writer-wins linear entries and reference runs appended per
@@ -322,6 +336,23 @@ int fadehip_bai_add(fadehip_bai *b, uint64_t base_file_offset, const fadehip_ind
 int fadehip_bai_finish(fadehip_bai *b, const uint8_t **bytes, size_t *n);
 const char *fadehip_bai_error(const fadehip_bai *b); /* never NULL; b may be NULL */
 void fadehip_bai_destroy(fadehip_bai *b);
+
+/* ... and a .csi (CSI version 1) out of entries made under the same geometry.  create: NULL for a negative n_ref or a geometry
+ * that is not valid.  add is fadehip_bai_add's (bins up to the geometry's last, windows below 8^depth).
+ *   finish  chunks merge as a .bai's; bins in ascending number, each with its loffset: the linear entries back-filled (a window
+ *           without an entry takes the next higher window's value), read at the bin's first window — the k-th bin of level l
+ *           begins at window k << 3 (depth - l) —, 0 when that window lies behind the last one with a value; behind the bins the
+ *           pseudo-bin ((1 << (3 * depth + 3)) - 1) / 7 + 1 with loffset 0 and fadehip_bai_finish's two chunks; n_no_coor.
+ *           *payload is UNCOMPRESSED: "CSI\1", min_shift, depth, l_aux = 0, n_ref, the references, n_no_coor.  The file is the
+ *           payload in BGZF members followed by the end-of-file marker, which is the writer's to do.  *payload is the
+ *           builder's, good until it is destroyed or added to
+ * htslib's choice of a depth and its folding of bins are not reproduced; byte equality with `samtools index -c` is not claimed. */
+typedef struct fadehip_csi fadehip_csi;
+fadehip_csi *fadehip_csi_create(int32_t n_ref, int32_t min_shift, int32_t depth);
+int fadehip_csi_add(fadehip_csi *b, uint64_t base_file_offset, const fadehip_index_call *call);
+int fadehip_csi_finish(fadehip_csi *b, const uint8_t **payload, size_t *n);
+const char *fadehip_csi_error(const fadehip_csi *b); /* never NULL; b may be NULL */
+void fadehip_csi_destroy(fadehip_csi *b);
 
 /* A set of read names, resident on the device: what lets `fade out --fragments` eject whole fragments — the artifact read,
  * its mate, its supplementary and secondary lines — from input in any order, without a sort by name in front and a second
@@ -426,6 +457,11 @@ int fadehip_recstore_count(fadehip_recstore *s, int64_t *n_records, int64_t *n_b
 int fadehip_recstore_sort(fadehip_recstore *s);
 int fadehip_recstore_drain(fadehip_recstore *s, int32_t flags, uint64_t max_payload, const uint8_t **out, size_t *out_bytes, int64_t *n_records,
                            fadehip_index_call *idx /* NULL without FADEHIP_RECSTORE_INDEX */);
+/* The entries FADEHIP_RECSTORE_INDEX drains hand out are made under the CSI geometry (fadehip_index_batch_csi) from then on,
+ * for fadehip_csi_add; a record beyond the geometry's limit fails the drain as one beyond 2^29 does without.  Before the first
+ * drain that hands out records (later: FADEHIP_E_STATE; fadehip_recstore_reset does not open it again); a geometry that is not
+ * valid: FADEHIP_E_INVALID.  A store on which it is never called launches the kernels it always has. */
+int fadehip_recstore_index_geometry(fadehip_recstore *s, int32_t min_shift, int32_t depth);
 void fadehip_recstore_destroy(fadehip_recstore *s);
 /* The store behind a coordinate-sorted MAIN output: a stream opened with FADEHIP_BAM_STORE_OUTPUT appends every record it
  * would have written, and a file whose records do not fit the device at once is written in windows of the key space, one pass
@@ -895,6 +931,11 @@ int fadehip_bam_back_report(fadehip_bam_stream *st, int32_t which, const uint8_t
  * long as that back call's *out; a call that wrote nothing gives empty arrays.  Without the flag, or before any back:
  * FADEHIP_E_STATE. */
 int fadehip_bam_back_index(fadehip_bam_stream *st, fadehip_index_call *out);
+/* With FADEHIP_BAM_INDEX (without: FADEHIP_E_INVALID), before the first front call (later: FADEHIP_E_STATE): the calls' entries
+ * are made under the CSI geometry (fadehip_index_batch_csi; not valid: FADEHIP_E_INVALID), for fadehip_csi_add, and a record
+ * that ends beyond the geometry's limit fails the call at its back as one beyond 2^29 does without.  A stream on which it is
+ * never called launches the kernels it always has. */
+int fadehip_bam_index_geometry(fadehip_bam_stream *st, int32_t min_shift, int32_t depth);
 /* totals so far: the eight Stats.parse counters (stats.d:45-54), records, reads beyond the kernels' limits */
 int fadehip_bam_totals(fadehip_bam_stream *st, int64_t stats[8], int64_t *n_records, int64_t *n_oversize);
 /* FADEHIP_BAM_EJECT: records not written, over the calls back has taken (0 without the flag) */
